@@ -18,9 +18,16 @@ Rank 0 prints ONE JSON line. Besides the contract's fields it carries
   roofline      fp32-MFMA bound; achieved = EXECUTED FLOPs of the timed region / HIP-event time on the engine stream
                 (Winograd layers counted with the multiply-adds they really issue); `effective_tflops` is the same
                 time against the direct-convolution (algorithmic) FLOP count
-  cpu_baseline  the torch-CPU oracle port on a bounded sample of the same workload
+and, with --full only (a plain run sets up, warms up, times its steps and prints the line, nothing else):
+  roofline.per_launch  one extra profiled micro-batch with an event pair around every contraction launch
+  cpu_baseline  the torch-CPU oracle port on a bounded sample of the same workload (--cpu-sample 0 skips it)
   sub           at N = 1: BASELINE configs[1] (TOPIQ fp32 b256) and north_star's target line (TOPIQ+CLIP forward at
-                batch 256), each timed the same way with its own roofline
+                batch 256), the other precision policies and the VLM tagger, each timed the same way with its own roofline
+                (--no-sub skips them)
+
+--dump-outputs DIR writes what the last timed step returned - the per-image record table [global batch, R] in global image
+order (scores for --workload topiq) - as DIR/records.npy (float32). Images and weights are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -284,13 +291,20 @@ def main():
                     help="full = the metric's whole ensemble (TOPIQ + SAMP + CLIP + InsightFace-style faces); topiq = BASELINE.json configs[1]; "
                          "topiq_clip = the 'TOPIQ+CLIP forward' of north_star's roofline target; ensemble = TOPIQ + SAMP-Net/U2-Net-P + CLIP "
                          "ViT-L/14 + aesthetic MLP; faces = configs[2]: TOPIQ + SAMP-Net + SCRFD/landmarks/ArcFace")
-    ap.add_argument("--cpu-sample", type=int, default=2, help="images for the CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-sub", action="store_true", help="skip the configs[1] / TOPIQ+CLIP sub-measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-launch profile pass, the CPU baseline and the "
+                         "sub-measurements (other workloads, precision policies, the VLM tagger)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-image records to DIR/records.npy (float32)")
+    ap.add_argument("--cpu-sample", type=int, default=2, help="images for the CPU baseline leg of --full (0 = skip)")
+    ap.add_argument("--no-sub", action="store_true", help="skip the sub-measurements of --full")
     ap.add_argument("--dtype", choices=list(POLICY_NOTE), default="f32",
                     help="precision policy of TOPIQ / SAMP-Net / U2-Net-P / CLIP for the primary workload (facet_amd/precision.py; face graphs "
                          "always fp32); the headline stays f32 = the reference CPU path's arithmetic")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / gather path only, no engine (CPU test hook, gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -342,7 +356,8 @@ def main():
 
     B, HW = args.batch, args.size
     primary = args.workload
-    subs = [] if (args.no_sub or world > 1) else [w for w in ("topiq", "topiq_clip") if w != primary]
+    run_subs = args.full and not (args.no_sub or world > 1)      # sub-measurements: --full only, N = 1 only
+    subs = [w for w in ("topiq", "topiq_clip") if w != primary] if run_subs else []
     need = set([primary] + subs)
     need_mask = 0
     for w in need:
@@ -450,7 +465,7 @@ def main():
         fl, fx, fh = eng.flops(), eng.flops_executed(), eng.flops_half()
         if face_eng is not None and WL[wl][1]:
             fl, fx = fl + face_eng.flops(), fx + face_eng.flops_executed()      # the face graphs' contractions run on the other context
-        return float(t.item()), ev_ms, fl, fx, fh
+        return float(t.item()), ev_ms, fl, fx, fh, out
 
     def per_launch(wl, eng, policy):
         """Per-launch view of the dominant kernel family (rank 0, outside the timed region): one micro-batch with a HIP event pair
@@ -500,14 +515,17 @@ def main():
              "note": "achieved / frac count the FLOPs the matrix cores executed: fp32 3x3 stride-1 pad-1 convs with >= 96 input channels run as "
                      "Winograd F(4x4,3x3) (36 batched GEMMs per launch, 4x fewer multiply-adds); effective_tflops divides the direct "
                      "convolution's (algorithmic) FLOPs by the same time",
-             "event_ms": round(ev_ms, 3), "per_launch": per_launch(wl, eng, policy) if rank == 0 else None}
+             "event_ms": round(ev_ms, 3), "per_launch": per_launch(wl, eng, policy) if (rank == 0 and args.full) else None}
         if mixed:
             r["executed_flops_per_image_by_dtype"] = {"f32": round(f32_fl / (B * steps), 1), "2-byte": round(f16_fl / (B * steps), 1)}
             r["note"] += "; two dtypes share the launch stream: frac = (fp32 FLOPs / fp32 MFMA peak + 2-byte FLOPs / 2-byte MFMA peak) / measured time"
         return r
 
-    dt_max, ev_ms, flops, flops_exec, flops_half = measure(primary, args.steps, args.warmup, eng)
+    dt_max, ev_ms, flops, flops_exec, flops_half, last = measure(primary, args.steps, args.warmup, eng)
     progress(f"{primary} [{args.dtype}]: {B * world * args.steps / dt_max:.1f} images/s")
+    if args.dump_outputs and rank == 0:      # every rank holds the same gathered table
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "records.npy"), np.ascontiguousarray(last, dtype=np.float32))
     overrides = {k: v for k, v in os.environ.items() if k.startswith("FE_") or k == "FACET_AMD_LIB"}      # tuning hooks that change the measured path
     out = None
     if rank == 0:
@@ -529,7 +547,7 @@ def main():
     # metric's / configs[3]'s workload under the other precision policies - one spare context at a time (each holds tens of GB)
     sub = {}
     sub_runs = [(wl, wl, args.dtype, 10 if wl == "topiq_clip" else 3) for wl in subs]
-    if not (args.no_sub or world > 1) and args.dtype == "f32":
+    if run_subs and args.dtype == "f32":
         full = primary == "full"
         sub_runs += [("ensemble_parity", "ensemble", "parity", 3)]            # configs[3] under the policy that holds the 1e-3 gate
         if full:
@@ -547,7 +565,7 @@ def main():
                     spare.close()
                 spare, spare_pol = make_engine(pol, 7), pol
             e = spare
-        dts, evs, fl, fx, fh = measure(wl, s_steps, s_warm, e)
+        dts, evs, fl, fx, fh, _ = measure(wl, s_steps, s_warm, e)
         progress(f"sub.{key}: {B * s_steps / dts:.1f} images/s")
         sub[key] = {"value": round(B * s_steps / dts, 2), "unit": "images/s", "steps": s_steps, "warmup": s_warm,
                     "ms_per_step": round(dts / s_steps * 1e3, 3), "dtype": DTYPE_FIELD[pol],
@@ -556,12 +574,12 @@ def main():
                     "roofline": roofline(wl, s_steps, evs, fl, fx, fh, e, pol)}
     if spare is not None:
         spare.close()
-    if rank == 0 and not (args.no_sub or world > 1) and args.dtype == "f32" and primary == "full":
+    if rank == 0 and run_subs and args.dtype == "f32" and primary == "full":
         sub["vlm_tagger"] = vlm_sub(dev_index, progress)      # BASELINE configs[4]'s model: its own metric (tokens/s), not images/s
     if rank == 0:
         if sub:
             out["sub"] = sub
-        if args.cpu_sample > 0:
+        if args.full and args.cpu_sample > 0:
             progress("cpu_baseline ...")
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, HW, 3, primary)
             progress(f"cpu_baseline: {out['cpu_baseline']['value']} images/s on {out['cpu_baseline']['cores']} threads")

@@ -86,7 +86,7 @@ def test_bench_self_launches_its_ranks():
 
 
 def test_committed_bench_line_has_the_contract_fields():
-    """The driver parses ONE JSON line from `python bench.py`: the line committed under profiles/ (the end-of-round run) must carry
+    """The driver parses ONE JSON line from `python bench.py`: the line committed under profiles/ (the end-of-round run, --full) must carry
     every field of the contract, incl. the roofline and cpu_baseline objects, and its numbers must be consistent with each other."""
     import glob
     import json

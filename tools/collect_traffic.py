@@ -15,6 +15,6 @@ path = os.path.join(root, "profiles", f"{tag}_traffic.json")
 out = json.load(open(path)) if os.path.exists(path) else {}
 out[key] = {"fetch_kb_per_image": total(fd, "FETCH_SIZE") / n, "write_kb_per_image": total(wd, "WRITE_SIZE") / n,
             "image_size": hw, "images_in_run": n,
-            "command": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes, one TCC counter each) -- python3 bench.py {flags} --steps 1 --warmup 1 --batch 32 --cpu-sample 0 --no-sub"}
+            "command": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes, one TCC counter each) -- python3 bench.py {flags} --steps 1 --warmup 1 --batch 32 --full --cpu-sample 0 --no-sub"}
 json.dump(out, open(path, "w"), indent=1)
 print(key, out[key])
