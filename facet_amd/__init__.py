@@ -6,9 +6,9 @@ this package is the ctypes binding plus host-side mirrors of the reference's Pyt
 """
 import threading
 
-from ._lib import Engine, EngineError, load_library, LIB_PATH  # noqa: F401
+from ._lib import Engine, EngineError, EngineCapacityError, load_library, LIB_PATH  # noqa: F401
 
-__all__ = ["Engine", "EngineError", "load_library", "LIB_PATH", "default_engine"]
+__all__ = ["Engine", "EngineError", "EngineCapacityError", "load_library", "LIB_PATH", "default_engine"]
 
 _default = {}
 _default_lock = threading.Lock()

@@ -35,6 +35,14 @@ class EngineError(RuntimeError):
     pass
 
 
+class EngineCapacityError(EngineError):
+    """The batch did not fit (device memory, arena, KV cache): FE_ERR_CAPACITY, raised by the padded-batch image path only
+    (vlm_preprocess_rgb, vlm_encode_preprocessed, vlm_prefill with pad). Fewer images at a time may fit."""
+
+
+FE_ERR_CAPACITY = -4
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -112,6 +120,11 @@ SIGNATURES = {
     "fe_vlm_prefill_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_generate": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "fe_vlm_preprocess_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), _f32p, _f32p, _f32p]),
+    "fe_vlm_encode_preprocessed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                             C.POINTER(C.c_int32), C.c_int, _f32p]),
+    "fe_vlm_prefill_images_padded": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_ensemble_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
                                     C.POINTER(C.c_int)]),
     "fe_u2netp_saliency": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -190,6 +203,20 @@ def load_library():
         return lib
 
 
+def left_padding(attention_mask):
+    """attention_mask int [n, len] -> pad [n] int32, the number of leading zeros of every row. Only left padding is accepted (the one side
+    on which batched greedy generation of a decoder-only model is defined): a row whose ones are not one trailing run raises ValueError."""
+    am = np.asarray(attention_mask)
+    if am.ndim != 2 or not np.isin(am, (0, 1)).all():
+        raise ValueError("attention_mask must be a 0/1 matrix [n_seq, len]")
+    pad = np.where(am.any(axis=1), np.argmax(am == 1, axis=1), am.shape[1])
+    L = am.shape[1]
+    for b, p in enumerate(pad):
+        if p >= L or not am[b, p:].all():
+            raise ValueError(f"attention_mask row {b} is not left padding (zeros, then ones, at least one real token)")
+    return pad.astype(np.int32)
+
+
 def _f32(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a, a.ctypes.data_as(_f32p)
@@ -234,7 +261,7 @@ class Engine:
 
     def _ck(self, rc):
         if rc != 0:
-            raise EngineError((self.lib.fe_last_error(self.h) or b"?").decode())
+            raise (EngineCapacityError if rc == FE_ERR_CAPACITY else EngineError)((self.lib.fe_last_error(self.h) or b"?").decode())
 
     # -- misc -------------------------------------------------------------------------------
     def sync(self):
@@ -591,6 +618,35 @@ class Engine:
                                                out.ctypes.data_as(_f32p) if want_embeds else None))
         return out
 
+    def vlm_preprocess_rgb(self, images, sizes, mean, std, want_pixel_values=False):
+        """Qwen2-VL's image processor on the GPU: images = list of uint8 RGB arrays [h, w, 3], sizes = the target (oh, ow) of each
+        (facet_amd.vlm_tagger.smart_resize). The patch rows stay on the device for vlm_encode_preprocessed; with want_pixel_values they
+        are also returned as the processor's float32 pixel_values [n_patches, 1176]."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        assert imgs and all(a.ndim == 3 and a.shape[2] == 3 for a in imgs), [a.shape for a in imgs]
+        sz, szp = self._i32([[a.shape[0], a.shape[1], int(oh), int(ow)] for a, (oh, ow) in zip(imgs, sizes)])
+        assert sz.shape == (len(imgs), 4), sz.shape
+        packed = np.concatenate([a.reshape(-1) for a in imgs])
+        m, mp = _f32(mean)
+        s, sp = _f32(std)
+        n = int(((sz[:, 2] // 14) * (sz[:, 3] // 14)).sum())
+        out = np.empty((n, 1176), np.float32) if want_pixel_values else None
+        self._ck(self.lib.fe_vlm_preprocess_rgb(self.h, packed.ctypes.data_as(C.c_void_p), len(imgs), szp, mp, sp,
+                                                out.ctypes.data_as(_f32p) if want_pixel_values else None))
+        return out
+
+    def vlm_encode_preprocessed(self, patch_pos_hw, window_index, cu_window_seqlens, cu_seqlens, want_embeds=True):
+        """vlm_encode_images on the patch rows the last vlm_preprocess_rgb left on the device (same index arrays, no pixel upload)."""
+        pos, pp = self._i32(patch_pos_hw)
+        wi, wp = self._i32(window_index)
+        cw, cwp = self._i32(cu_window_seqlens)
+        cf, cfp = self._i32(cu_seqlens)
+        n = pos.shape[0]
+        assert wi.shape == (n // 4,), (pos.shape, wi.shape)
+        out = np.empty((n // 4, self.vlm_dims()["hidden"]), np.float32) if want_embeds else None
+        self._ck(self.lib.fe_vlm_encode_preprocessed(self.h, pp, wp, cwp, len(cw) - 1, cfp, len(cf) - 1, out.ctypes.data_as(_f32p) if want_embeds else None))
+        return out
+
     def vlm_dims(self):
         d = (C.c_int * 8)()
         self._ck(self.lib.fe_vlm_dims(self.h, d))
@@ -601,10 +657,11 @@ class Engine:
         a = np.ascontiguousarray(a, dtype=np.int32)
         return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
-    def vlm_prefill(self, tokens, position_ids=None, max_seq=None, want_logits=False, image_rows=None):
+    def vlm_prefill(self, tokens, position_ids=None, max_seq=None, want_logits=False, image_rows=None, pad=None):
         """tokens int [n_seq, len]; position_ids int [3, n_seq, len] (None: text-only positions 0..len-1 on all three axes).
         image_rows: flat row indices (sequence * len + position) of the <|image_pad|> tokens, in order - they take the embeddings of
-        the last vlm_encode_images.
+        the last vlm_encode_images. pad int [n_seq]: left padding of every sequence (fe_vlm_prefill_images_padded; kept for the decode
+        steps that follow).
         -> next token ids [n_seq] (greedy) and, with want_logits, the bf16 logits widened to float32 [n_seq, vocab]."""
         tok, tp = self._i32(tokens)
         n, L = tok.shape
@@ -614,7 +671,13 @@ class Engine:
         assert pos.shape == (3, n, L), pos.shape
         nxt = np.empty(n, np.int32)
         lg = np.empty((n, self.vlm_dims()["vocab"]), np.float32) if want_logits else None
-        if image_rows is not None:
+        if pad is not None:
+            pd, pdp = self._i32(pad)
+            assert pd.shape == (n,), pd.shape
+            ir, irp = self._i32(image_rows if image_rows is not None else np.zeros(0, np.int32))
+            self._ck(self.lib.fe_vlm_prefill_images_padded(self.h, tp, pp, n, L, int(max_seq or min(8192, L + 256)), pdp, irp, int(ir.size),
+                                                           nxt.ctypes.data_as(C.POINTER(C.c_int32)), lg.ctypes.data_as(_f32p) if want_logits else None))
+        elif image_rows is not None:
             ir, irp = self._i32(image_rows)
             self._ck(self.lib.fe_vlm_prefill_images(self.h, tp, pp, n, L, int(max_seq or min(8192, L + 256)), irp, int(ir.size),
                                                     nxt.ctypes.data_as(C.POINTER(C.c_int32)), lg.ctypes.data_as(_f32p) if want_logits else None))
@@ -634,20 +697,29 @@ class Engine:
         self._ck(self.lib.fe_vlm_decode_step(self.h, tp, pp, n, nxt.ctypes.data_as(C.POINTER(C.c_int32)), lg.ctypes.data_as(_f32p) if want_logits else None))
         return (nxt, lg) if want_logits else nxt
 
-    def vlm_generate(self, tokens, max_new_tokens, position_ids=None, eos_token_ids=(), want_logits=False, forced_tokens=None, image_rows=None):
+    def vlm_generate(self, tokens, max_new_tokens, position_ids=None, eos_token_ids=(), want_logits=False, forced_tokens=None, image_rows=None,
+                     attention_mask=None):
         """Greedy generation (`generate(..., do_sample=False)`, models/vlm_tagger.py:255-259): prefill + max_new_tokens - 1 decode
         steps for all sequences in lockstep; a sequence that emitted an EOS id keeps receiving that id (what generate's padding does).
         New positions continue from max(position_ids) + 1 per sequence. forced_tokens [n_seq, max_new_tokens]: teacher forcing - the
-        token FED at each step is taken from there instead of the engine's own choice (parity tests)."""
+        token FED at each step is taken from there instead of the engine's own choice (parity tests).
+        attention_mask int [n_seq, len]: a LEFT-padded batch (zeros, then ones, per row; position_ids must then be given, e.g.
+        vlm_tagger.rope_index(..., attention_mask=...)). None: every position is real (the unpadded path, unchanged)."""
         tok = np.ascontiguousarray(tokens, dtype=np.int32)
         n, L = tok.shape
+        pad = None
+        if attention_mask is not None:
+            pad = left_padding(attention_mask)
+            assert pad.shape == (n,), pad.shape
+            if position_ids is None:
+                raise ValueError("a padded batch needs its position_ids (vlm_tagger.rope_index with the attention mask)")
         if position_ids is None:
             position_ids = np.broadcast_to(np.arange(L, dtype=np.int32), (3, n, L))
         position_ids = np.ascontiguousarray(position_ids, dtype=np.int32)
         nxt_pos = position_ids.max(axis=(0, 2)) + 1            # [n_seq]
         if not want_logits and forced_tokens is None:
             # the product path: prefill, then every decode step on the device (fe_vlm_generate: captured graph, no host round trips)
-            first = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), image_rows=image_rows)
+            first = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), image_rows=image_rows, pad=pad)
             out = np.empty((n, max_new_tokens), np.int32)
             out[:, 0] = first
             if max_new_tokens > 1:
@@ -664,7 +736,7 @@ class Engine:
             return out
         out = np.zeros((n, max_new_tokens), np.int32)
         logits = []
-        r = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), want_logits=want_logits, image_rows=image_rows)
+        r = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), want_logits=want_logits, image_rows=image_rows, pad=pad)
         cur = r[0] if want_logits else r
         done = np.zeros(n, bool)
         eos = set(int(e) for e in eos_token_ids)

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <tuple>
+#include <cstring>
 
 using namespace fe;
 
@@ -1320,13 +1321,14 @@ int fe_vlm_vision_configure(fe_ctx* ctx, int n_heads, const int* fullatt_block_i
   for (int i = 0; i < n_fullatt; ++i) g.fullatt[i] = fullatt_block_indexes[i];
   FE_API_END(ctx)
 }
-int fe_vlm_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* window_index, const int32_t* cu_window_seqlens,
-                         int n_windows, const int32_t* cu_seqlens, int n_images, float* embeds) {
-  FE_API_BEGIN(ctx)
-  if (!ctx->c.vlm || !ctx->c.vlm->vis.present) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+extern "C++" {
+// shared by fe_vlm_encode_images (fp32 rows from the host) and fe_vlm_encode_preprocessed (pixel_values == nullptr: the bf16 rows the last
+// fe_vlm_preprocess_rgb left on the device)
+static void vlm_encode(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* window_index,
+                       const int32_t* cu_window_seqlens, int n_windows, const int32_t* cu_seqlens, int n_images, float* embeds) {
   Ctx& C = ctx->c;
   VlmModel& m = *C.vlm;
-  FE_CHECK(pixel_values && patch_pos_hw && window_index && cu_window_seqlens && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_windows > 0 && n_images > 0,
+  FE_CHECK(patch_pos_hw && window_index && cu_window_seqlens && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_windows > 0 && n_images > 0,
            "bad arguments");
   FE_CHECK(cu_window_seqlens[0] == 0 && cu_window_seqlens[n_windows] == n_patches && cu_seqlens[0] == 0 && cu_seqlens[n_images] == n_patches, "segment bounds must cover the patches");
   int max_win = 0, max_full = 0;
@@ -1341,17 +1343,18 @@ int fe_vlm_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, 
     m.img_cap = rows;
   }
   C.arena.reset();
-  float* d_pv = (float*)C.arena.alloc((size_t)n_patches * m.vis.patch_dim * sizeof(float));
+  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * m.vis.patch_dim * sizeof(float)) : nullptr;
   int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
   int* d_widx = (int*)C.arena.alloc((size_t)rows * sizeof(int));
   int* d_cw = (int*)C.arena.alloc((size_t)(n_windows + 1) * sizeof(int));
   int* d_cf = (int*)C.arena.alloc((size_t)(n_images + 1) * sizeof(int));
-  FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * m.vis.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
+  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * m.vis.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_widx, window_index, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_cw, cu_window_seqlens, (size_t)(n_windows + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_cf, cu_seqlens, (size_t)(n_images + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  vlm_vision_forward(C, m, d_pv, n_patches, d_pos, d_widx, d_cw, n_windows, max_win, d_cf, n_images, max_full, m.img_embeds);
+  vlm_vision_forward(C, m, d_pv, n_patches, d_pos, d_widx, d_cw, n_windows, max_win, d_cf, n_images, max_full, m.img_embeds,
+                     pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv);
   m.img_rows = rows;
   if (embeds) {
     float* d_f = (float*)C.arena.alloc((size_t)rows * m.hidden * sizeof(float));
@@ -1359,7 +1362,89 @@ int fe_vlm_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, 
     FE_HIP(hipMemcpyAsync(embeds, d_f, (size_t)rows * m.hidden * sizeof(float), hipMemcpyDeviceToHost, C.stream));
   }
   FE_HIP(hipStreamSynchronize(C.stream));
+}
+// The entry points of the padded-batch image path report a failure to fit (arena, device memory, KV-cache capacity) as FE_ERR_CAPACITY, so
+// a caller can retry with fewer images; every other failure stays FE_ERR_RUNTIME.
+static bool vlm_capacity_error(const char* msg) {
+  return strstr(msg, "arena exhausted") || strstr(msg, "out of memory") || strstr(msg, "do not fit") || strstr(msg, "max_seq <= 8192");
+}
+}  // extern "C++"
+#define FE_API_END_CAPACITY(ctx)                                      \
+  }                                                                   \
+  catch (const std::exception& e) {                                   \
+    (ctx)->c.err = e.what();                                          \
+    fe_drain(ctx);                                                    \
+    return vlm_capacity_error(e.what()) ? FE_ERR_CAPACITY : FE_ERR_RUNTIME; \
+  }                                                                   \
+  return FE_OK;
+
+int fe_vlm_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* window_index, const int32_t* cu_window_seqlens,
+                         int n_windows, const int32_t* cu_seqlens, int n_images, float* embeds) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm || !ctx->c.vlm->vis.present) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  FE_CHECK(pixel_values, "bad arguments");
+  vlm_encode(ctx, pixel_values, n_patches, patch_pos_hw, window_index, cu_window_seqlens, n_windows, cu_seqlens, n_images, embeds);
   FE_API_END(ctx)
+}
+int fe_vlm_encode_preprocessed(fe_ctx* ctx, const int32_t* patch_pos_hw, const int32_t* window_index, const int32_t* cu_window_seqlens, int n_windows,
+                               const int32_t* cu_seqlens, int n_images, float* embeds) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm || !ctx->c.vlm->vis.present) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  VlmModel& m = *ctx->c.vlm;
+  FE_CHECK(m.pre_pv && m.pre_rows > 0 && cu_seqlens && n_images > 0, "encode_preprocessed: call fe_vlm_preprocess_rgb first");
+  vlm_encode(ctx, nullptr, m.pre_rows, patch_pos_hw, window_index, cu_window_seqlens, n_windows, cu_seqlens, n_images, embeds);
+  FE_API_END_CAPACITY(ctx)
+}
+int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const int32_t* sizes, const float* mean, const float* stdv, float* pixel_values) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm || !ctx->c.vlm->vis.present) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  Ctx& C = ctx->c;
+  VlmModel& m = *C.vlm;
+  FE_CHECK(rgb && sizes && mean && stdv && n_images > 0, "bad arguments");
+  FE_CHECK(m.vis.patch_dim == 3 * 2 * 14 * 14, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x 14 x 14 built)", m.vis.patch_dim);
+  size_t in_b = 0, rows = 0, px_max = 0;
+  for (int i = 0; i < n_images; ++i) {
+    const int h = sizes[4 * i], w = sizes[4 * i + 1], oh = sizes[4 * i + 2], ow = sizes[4 * i + 3];
+    FE_CHECK(h > 0 && w > 0 && oh >= 28 && ow >= 28 && oh % 28 == 0 && ow % 28 == 0 && (size_t)oh * ow <= ((size_t)1 << 26),
+             "preprocess_rgb: image %d: %dx%d -> %dx%d (target sides must be positive multiples of 28)", i, h, w, oh, ow);
+    in_b += (size_t)h * w * 3;
+    rows += (size_t)(oh / 14) * (ow / 14);
+    px_max = std::max(px_max, (size_t)oh * ow * 3);
+  }
+  FE_CHECK(rows < ((size_t)1 << 31) / 1176, "preprocess_rgb: %zu patches", rows);
+  // the processor's arithmetic, once per (channel, value): float32(float64(u) * (1 / 255)), then float32 (x - mean) / std
+  std::vector<float> lut(3 * 256);
+  for (int c = 0; c < 3; ++c)
+    for (int u = 0; u < 256; ++u) {
+      const float x = (float)((double)u * (1.0 / 255.0));
+      lut[c * 256 + u] = (x - mean[c]) / stdv[c];
+    }
+  if ((int)rows > m.pre_cap) {
+    if (m.pre_pv) (void)hipFree(m.pre_pv);
+    m.pre_pv = nullptr; m.pre_cap = 0; m.pre_rows = 0;
+    FE_HIP(hipMalloc((void**)&m.pre_pv, rows * 1176 * sizeof(bf16)));
+    m.pre_cap = (int)rows;
+  }
+  m.pre_rows = 0;
+  C.arena.reset();
+  uint8_t* d_in = (uint8_t*)C.arena.alloc(in_b);
+  float* d_lut = (float*)C.arena.alloc(lut.size() * sizeof(float));
+  uint8_t* d_img = (uint8_t*)C.arena.alloc(px_max);
+  float* d_f = pixel_values ? (float*)C.arena.alloc(rows * 1176 * sizeof(float)) : nullptr;
+  FE_HIP(hipMemcpyAsync(d_in, rgb, in_b, hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, C.stream));
+  size_t off = 0, row0 = 0;
+  for (int i = 0; i < n_images; ++i) {      // one resample pair and one patchify launch per image (tagger batches are a few images)
+    const int h = sizes[4 * i], w = sizes[4 * i + 1], oh = sizes[4 * i + 2], ow = sizes[4 * i + 3];
+    resize_u8(C, d_in + off, 1, h, w, oh, ow, FE_BICUBIC, 0, oh, 0, ow, d_img);
+    vlm_patchify(C, d_img, oh, ow, d_lut, m.pre_pv + row0 * 1176, d_f ? d_f + row0 * 1176 : nullptr);
+    off += (size_t)h * w * 3;
+    row0 += (size_t)(oh / 14) * (ow / 14);
+  }
+  if (pixel_values) FE_HIP(hipMemcpyAsync(pixel_values, d_f, rows * 1176 * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  m.pre_rows = (int)rows;
+  FE_API_END_CAPACITY(ctx)
 }
 int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section) {
   FE_API_BEGIN(ctx)
@@ -1382,8 +1467,9 @@ int fe_vlm_dims(fe_ctx* ctx, int* dims) {
 }
 extern "C++" {
 // tokens (+ optional replacement rows for image tokens) -> embeddings -> decoder -> next tokens; shared by prefill and decode
+// pad: a prefill's left padding per sequence (nullptr: none; a prefill always sets the model's pad array, a decode step never touches it)
 static void vlm_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int len, int32_t* next_tokens, float* logits,
-                     const int32_t* image_rows = nullptr, int n_image_rows = 0) {
+                     const int32_t* image_rows = nullptr, int n_image_rows = 0, const int32_t* pad = nullptr, bool prefill = true) {
   Ctx& C = ctx->c;
   VlmModel& m = *C.vlm;
   const int rows = n_seq * len;
@@ -1395,6 +1481,10 @@ static void vlm_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* position
   bf16* x = C.arena.array<bf16>((size_t)rows * m.hidden);
   FE_HIP(hipMemcpyAsync(d_tok, tokens, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_pos, position_ids, (size_t)3 * rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  if (prefill) {
+    if (pad) FE_HIP(hipMemcpyAsync(m.pad, pad, (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice, C.stream));
+    else FE_HIP(hipMemsetAsync(m.pad, 0, (size_t)n_seq * sizeof(int), C.stream));
+  }
   vlm_embed(C, m, d_tok, rows, x);
   if (n_image_rows > 0) {      // inputs_embeds.masked_scatter(image_mask, image_embeds): the merged image embeddings replace the placeholder rows, in order
     int* d_idx = (int*)C.arena.alloc((size_t)n_image_rows * sizeof(int));
@@ -1430,6 +1520,22 @@ int fe_vlm_prefill_images(fe_ctx* ctx, const int32_t* tokens, const int32_t* pos
   vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits, image_rows, n_image_rows);
   FE_API_END(ctx)
 }
+int fe_vlm_prefill_images_padded(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int len, int max_seq, const int32_t* pad,
+                                 const int32_t* image_rows, int n_image_rows, int32_t* next_tokens, float* logits) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+  VlmModel& m = *ctx->c.vlm;
+  FE_CHECK(tokens && position_ids && pad && next_tokens && n_seq > 0 && len > 0 && max_seq >= len && max_seq <= 8192, "bad arguments (max_seq <= 8192)");
+  for (int b = 0; b < n_seq; ++b) FE_CHECK(pad[b] >= 0 && pad[b] < len, "prefill_images_padded: sequence %d: pad %d of %d positions (at least one real token)", b, pad[b], len);
+  FE_CHECK(n_image_rows == 0 || (image_rows && n_image_rows == m.img_rows), "prefill_images_padded: %d placeholder rows but the last image encode left %d embeddings",
+           n_image_rows, m.img_rows);
+  for (int i = 0; i < n_image_rows; ++i)
+    FE_CHECK(image_rows[i] >= 0 && image_rows[i] < n_seq * len && image_rows[i] % len >= pad[image_rows[i] / len], "prefill_images_padded: row index %d out of range or in the pad", image_rows[i]);
+  m.reserve_cache(n_seq, max_seq);
+  m.cur_len = 0;
+  vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits, image_rows, n_image_rows, pad);
+  FE_API_END_CAPACITY(ctx)
+}
 int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens) {
   FE_API_BEGIN(ctx)
   if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
@@ -1453,7 +1559,7 @@ int fe_vlm_decode_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* positi
   VlmModel& m = *ctx->c.vlm;
   FE_CHECK(tokens && position_ids && next_tokens && n_seq == m.cache_B && m.cur_len > 0, "decode_step: call fe_vlm_prefill for these %d sequences first", n_seq);
   FE_CHECK(m.cur_len < m.max_seq, "decode_step: the KV cache is full (%d positions)", m.max_seq);
-  vlm_step(ctx, tokens, position_ids, n_seq, 1, next_tokens, logits);
+  vlm_step(ctx, tokens, position_ids, n_seq, 1, next_tokens, logits, nullptr, 0, nullptr, false);
   FE_API_END(ctx)
 }
 

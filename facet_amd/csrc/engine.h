@@ -370,14 +370,24 @@ struct VlmModel {
   // contiguous KV cache: per layer [n_seq][n_kv_heads][max_seq][128] keys (rotated) and values
   std::vector<bf16*> kcache, vcache;
   int cache_B = 0, max_seq = 0, cur_len = 0;
+  // left padding of every sequence (device int [cache_B]): set by each prefill (zeros unless fe_vlm_prefill_images_padded), read by the
+  // attention kernels of the prefill and of every later decode step (a captured decode graph holds the pointer)
+  int* pad = nullptr;
+  // patch rows of the last fe_vlm_preprocess_rgb (device bf16 [pre_rows][patch_dim]), the input of fe_vlm_encode_preprocessed
+  bf16* pre_pv = nullptr; int pre_rows = 0, pre_cap = 0;
   void reserve_cache(int B, int max_seq);
   void release_cache();
-  ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); }
+  ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); }
 };
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg);
 void build_vlm_vision(VlmModel& m, const WeightStore& ws);
+// pv: fp32 patch rows, or (pv == nullptr) pv_bf16: the rows already in bf16 (fe_vlm_preprocess_rgb)
 void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* pos, const int* widx, const int* cu_win, int n_win, int max_win,
-                        const int* cu_full, int n_full, int max_full, bf16* out);
+                        const int* cu_full, int n_full, int max_full, bf16* out, const bf16* pv_bf16 = nullptr);
+// Qwen2-VL image processor after its resample (kernels_vlm_pre.hip): resized uint8 RGB [oh][ow][3] (oh, ow multiples of 28) -> patch rows
+// [oh/14 * ow/14][3*2*14*14] in the processor's (gh/2, gw/2, 2, 2, C, T, 14, 14) order, each value lut[c][u]; bf16 always, fp32 when
+// out_f32 is not null
+void vlm_patchify(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut, bf16* out_bf16, float* out_f32);
 // row kernels shared by the decoder and the vision tower (model_vlm.hip)
 void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps);
 void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n);

@@ -122,6 +122,7 @@ struct VlmAttnParams {
   bf16* o; int ldo;             // [B*Lq][nh*128]
   int B, nh, nkv, Lq, Lk, max_seq, qpos0;      // query i sits at sequence position qpos0 + i and sees keys 0 .. qpos0 + i
   float scale;
+  const int* pad;               // device [B]: sequence b's first pad[b] positions are left padding (masked keys, zero output rows)
 };
 union VA8 { uint4 u; fe_v4f f; };
 
@@ -139,12 +140,15 @@ __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnP
   const bool qok = q < p.Lq;
   const int qc = qok ? q : p.Lq - 1;
   const int qpos = p.qpos0 + q;
+  const int padb = p.pad[b];
   VA8 qf[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) qf[s].u = *reinterpret_cast<const uint4*>(Qp + (size_t)qc * p.ldq + 16 * s + 8 * h);
   // this workgroup's queries end at position qpos0 + (blockIdx.x + 1) * 128 - 1: later keys are masked for all of them
   const int kend = min(p.Lk, p.qpos0 + (int)(blockIdx.x + 1) * 128);
   const int nt = (kend + 31) / 32;
+  // left padding: the key loop starts at the first 32-key tile that holds a live key (whole pad tiles cost nothing)
+  const int kt0 = min(padb / 32, nt);
   uint4 kr[2], vr[2];
   auto load_tile = [&](int kt) {
 #pragma unroll
@@ -176,11 +180,11 @@ __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnP
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
   float m = -INFINITY, l = 0.f;
-  load_tile(0);
-  store_tile(0, 0);
+  load_tile(kt0);
+  store_tile(0, kt0);
   __syncthreads();
-  for (int kt = 0; kt < nt; ++kt) {
-    const int buf = kt & 1;
+  for (int kt = kt0; kt < nt; ++kt) {
+    const int buf = (kt - kt0) & 1;
     if (kt + 1 < nt) load_tile(kt + 1);
     fe_f32x16 st;
 #pragma unroll
@@ -197,12 +201,12 @@ __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnP
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = kbase + (e & 3) + 8 * (e >> 2);
-      st[e] = (key >= p.Lk || key > qpos) ? -INFINITY : st[e] * p.scale;
+      st[e] = (key >= p.Lk || key > qpos || key < padb) ? -INFINITY : st[e] * p.scale;
       tmax = fmaxf(tmax, st[e]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float mn = fmaxf(m, tmax);
-    const float msafe = mn == -INFINITY ? 0.f : mn;      // a query row whose keys so far are all masked (rows past Lq only)
+    const float msafe = mn == -INFINITY ? 0.f : mn;      // a query row whose keys so far are all masked (rows past Lq, pad rows)
     const float alpha = __expf(m - msafe);
     float psum = 0.f;
 #pragma unroll
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnP
     __syncthreads();
   }
   if (qok) {
-    const float inv = 1.f / l;
+    const float inv = l > 0.f ? 1.f / l : 0.f;      // a pad query row has no live key: zeros, not 0 / 0
     bf16* op = p.o + ((size_t)b * p.Lq + q) * p.ldo + head * 128;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -644,7 +648,7 @@ constexpr int VLM_DEC_CHUNK = 128;
 template <int G>
 __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16* __restrict__ q, const bf16* __restrict__ kc, const bf16* __restrict__ vc, float* __restrict__ po,
                                                                   float* __restrict__ pm, float* __restrict__ pl, int nh, int nkv, int Lk, int max_seq, float scale,
-                                                                  const int* __restrict__ len_dev, int nsplit) {
+                                                                  const int* __restrict__ len_dev, int nsplit, const int* __restrict__ pad) {
   __shared__ float sc[G][VLM_DEC_CHUNK];      // scores, then probabilities
   __shared__ float part[4][G][128];
   if (len_dev) Lk = *len_dev + 1;
@@ -652,7 +656,8 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16*
   const int bk = blockIdx.x, sp = blockIdx.y;
   const int b = bk / nkv, kvh = bk - b * nkv, head0 = kvh * G;
   const int k0 = sp * VLM_DEC_CHUNK, k1 = min(k0 + VLM_DEC_CHUNK, Lk);
-  if (k0 >= Lk) {      // a chunk past the cache length: neutral element of the merge
+  const int padb = pad[b];      // keys below it are left padding
+  if (k0 >= Lk || k1 <= padb) {      // a chunk past the cache length or wholly in the pad: neutral element of the merge
     if (t < G) { pm[((size_t)b * nh + head0 + t) * nsplit + sp] = -INFINITY; pl[((size_t)b * nh + head0 + t) * nsplit + sp] = 0.f; }
     return;
   }
@@ -681,7 +686,7 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16*
 #pragma unroll
         for (int e = 0; e < 8; ++e) a += kf[e] * qf[g][e];
         a = vlm_row16_sum(a);
-        if (sub == 0) sc[g][kl] = k0 + kl < k1 ? a * scale : -INFINITY;
+        if (sub == 0) sc[g][kl] = (k0 + kl < k1 && k0 + kl >= padb) ? a * scale : -INFINITY;
       }
     }
   }
@@ -825,11 +830,15 @@ void VlmModel::reserve_cache(int B, int max_seq_) {
     FE_HIP(hipMalloc(&v, per * sizeof(bf16)));
     vcache.push_back((bf16*)v);
   }
+  FE_HIP(hipMalloc((void**)&pad, (size_t)B * sizeof(int)));
+  FE_HIP(hipMemset(pad, 0, (size_t)B * sizeof(int)));
   cache_B = B; max_seq = max_seq_; cur_len = 0;
 }
 void VlmModel::release_cache() {
   for (bf16* p : kcache) (void)hipFree(p);
   for (bf16* p : vcache) (void)hipFree(p);
+  if (pad) (void)hipFree(pad);
+  pad = nullptr;
   kcache.clear(); vcache.clear();
   cache_B = 0; max_seq = 0; cur_len = 0;
 }
@@ -861,7 +870,7 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   const VlmConfig& g = m.cfg;
   const int rows = B * L, d = m.hidden, nh = g.n_heads, nkv = g.n_kv_heads, qd = nh * 128, qkvd = (nh + 2 * nkv) * 128;
   const int start = m.cur_len, Lk = start + L;
-  FE_CHECK(B == m.cache_B && Lk <= m.max_seq, "vlm: %d sequences x %d positions do not fit the cache (%d x %d)", B, Lk, m.cache_B, m.max_seq);
+  FE_CHECK(B == m.cache_B && Lk <= m.max_seq && m.pad, "vlm: %d sequences x %d positions do not fit the cache (%d x %d)", B, Lk, m.cache_B, m.max_seq);
   const size_t mark = c.arena.mark();
   bf16* n = c.arena.array<bf16>((size_t)rows * d);
   bf16* qkv = c.arena.array<bf16>((size_t)rows * qkvd);
@@ -892,7 +901,7 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
       const int G = nh / nkv;
 #define VLM_DEC_LAUNCH(GG)                                                                                                                            \
   hipLaunchKernelGGL(vlm_attn_decode_gqa_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, (const bf16*)qr, (const bf16*)m.kcache[li],       \
-                     (const bf16*)m.vcache[li], po, pm, pl, nh, nkv, Lk, m.max_seq, scale, len_dev, nsplit)
+                     (const bf16*)m.vcache[li], po, pm, pl, nh, nkv, Lk, m.max_seq, scale, len_dev, nsplit, (const int*)m.pad)
       switch (G) {
         case 1: VLM_DEC_LAUNCH(1); break;
         case 2: VLM_DEC_LAUNCH(2); break;
@@ -904,7 +913,7 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
 #undef VLM_DEC_LAUNCH
       hipLaunchKernelGGL(vlm_attn_combine_kernel, dim3(B * nh), dim3(128), 0, c.stream, (const float*)po, (const float*)pm, (const float*)pl, ao, nsplit);
     } else {
-      VlmAttnParams ap{qr, qd, m.kcache[li], m.vcache[li], ao, qd, B, nh, nkv, L, Lk, m.max_seq, start, scale};
+      VlmAttnParams ap{qr, qd, m.kcache[li], m.vcache[li], ao, qd, B, nh, nkv, L, Lk, m.max_seq, start, scale, m.pad};
       hipLaunchKernelGGL(vlm_attn_prefill_kernel, dim3((L + 127) / 128, B * nh), dim3(256), 0, c.stream, ap);
     }
     FE_HIP(hipGetLastError());

@@ -263,13 +263,13 @@ static void vis_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf
 // (window order -> raster group); cu_win / cu_full: device segment bounds (window order) with their host counts and longest segment;
 // out: device bf16 [N/4][out_hidden], raster order.
 void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* pos, const int* widx, const int* cu_win, int n_win, int max_win,
-                        const int* cu_full, int n_full, int max_full, bf16* out) {
+                        const int* cu_full, int n_full, int max_full, bf16* out, const bf16* pv_bf16) {
   VlmVisionW& v = m.vis;
   FE_CHECK(v.present, "vlm: the checkpoint had no vision tower (model.visual.*)");
   FE_CHECK(N > 0 && N % 4 == 0, "vlm vision: %d patches (whole 2x2 merge blocks expected)", N);
   const int d = v.hidden, H = v.heads;
   const size_t mark = c.arena.mark();
-  bf16* pvh = c.arena.array<bf16>((size_t)N * v.patch_dim);
+  bf16* pvh = pv ? c.arena.array<bf16>((size_t)N * v.patch_dim) : nullptr;
   bf16* h0 = c.arena.array<bf16>((size_t)N * d);
   bf16* x = c.arena.array<bf16>((size_t)N * d);
   bf16* n = c.arena.array<bf16>((size_t)N * d);
@@ -287,8 +287,8 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
     FE_HIP(hipMemsetAsync(gg, 0, (size_t)N * ip * sizeof(bf16), c.stream));
     FE_HIP(hipMemsetAsync(uu, 0, (size_t)N * ip * sizeof(bf16), c.stream));
   }
-  launch_convert(pv, pvh, (size_t)N * v.patch_dim, c.stream);      // pixel_values.to(bfloat16), as the patch embedding does
-  vis_linear(c, v.patch, pvh, v.patch_dim, N, h0, d);
+  if (pv) launch_convert(pv, pvh, (size_t)N * v.patch_dim, c.stream);      // pixel_values.to(bfloat16), as the patch embedding does
+  vis_linear(c, v.patch, pv ? (const bf16*)pvh : pv_bf16, v.patch_dim, N, h0, d);
   hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(vgrid((size_t)N * d / 8)), dim3(256), 0, c.stream, (const bf16*)h0, x, widx, N / 4, 4, d, 0);
   FE_HIP(hipGetLastError());
   const float scale = 1.0f / sqrtf(80.f);

@@ -4,18 +4,97 @@ SURVEY 8(f)-4 / BASELINE configs[4]: the vision tower and the text decoder run i
 `fe_vlm_generate`: greedy, bf16 as the reference loads the model, models/vlm_tagger.py:155-184); what stays here is what the reference also
 does on the host - the prompt built from the tag vocabulary (:88-148), the index arithmetic transformers derives from `image_grid_thw`
 (window order, segment bounds, M-RoPE position ids: `vision_indices`, `rope_index`), the generate loop's bookkeeping and the parsing of the
-generated text into vocabulary tags (:446-495). The tokenizer, chat template and image processor (resize to a multiple of 28, normalise,
-patchify) ship inside the Hugging Face checkpoint (`AutoProcessor.from_pretrained`, :181), which is not available offline and is not
-re-implemented: callers pass the processor's tensors - `input_ids`, `pixel_values`, `image_grid_thw` - exactly as the CLIP text tower takes
-token ids (facet_amd/tagger.py).
+generated text into vocabulary tags (:446-495). The photo path (`tag_image` / `tag_batch`, :202-308 / :327-368) restates the processor:
+smart_resize and the grids on the host, the resample / rescale / normalise / patchify on the GPU (`fe_vlm_preprocess_rgb`, matching
+transformers' PIL backend bit for bit), the chat text and its <|image_pad|> expansion here, left padding of the batch in the engine
+(`fe_vlm_prefill_images_padded`). The tokenizer stays the caller's (`encode` / `decode` callables of the checkpoint's processor, exactly as
+the CLIP text tower takes token ids, facet_amd/tagger.py); `generate_with_images` still takes the processor's own tensors.
 """
-from typing import Any, Dict, Iterable, List, Optional
+import math
+from typing import Any, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
-from ._lib import FE_MODEL_VLM
+from ._lib import FE_MODEL_VLM, EngineCapacityError
 
 QWEN2_5_VL_7B = dict(n_heads=28, n_kv_heads=4, head_dim=128, rope_theta=1e6, rms_eps=1e-6, mrope_section=(16, 24, 24))
+
+# [DEP-KNOWLEDGE: Qwen2.5-VL-7B-Instruct tokenizer_config / generation_config] special-token ids of the checkpoint's tokenizer; parameters of
+# VLMTagger (special_tokens=...), so a checkpoint with other ids only passes its own
+QWEN2_5_VL_TOKENS = dict(image_token_id=151655, vision_start_token_id=151652, vision_end_token_id=151653, pad_token_id=151643,
+                         eos_token_ids=(151645, 151643))
+# [DEP-KNOWLEDGE: transformers Qwen2VLImageProcessor defaults] OPENAI_CLIP_MEAN / OPENAI_CLIP_STD, min / max pixels of smart_resize
+IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
+IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+MIN_PIXELS, MAX_PIXELS = 56 * 56, 28 * 28 * 1280
+# [DEP-KNOWLEDGE: Qwen2.5-VL chat template - parity unpinned: the template ships inside the checkpoint (tokenizer_config.json /
+# chat_template.json), not available offline] apply_chat_template(messages = [user: image, text], add_generation_prompt=True) restated
+CHAT_TEMPLATE = ("<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n"
+                 "<|im_start|>user\n<|vision_start|><|image_pad|><|vision_end|>{prompt}<|im_end|>\n"
+                 "<|im_start|>assistant\n")
+IMAGE_PAD = "<|image_pad|>"
+
+
+def smart_resize(height: int, width: int, factor: int = 28, min_pixels: int = MIN_PIXELS, max_pixels: int = MAX_PIXELS):
+    """transformers.models.qwen2_vl.image_processing_qwen2_vl.smart_resize restated: both sides multiples of `factor`, the pixel count within
+    [min_pixels, max_pixels], the aspect ratio kept as closely as possible. -> (height, width)."""
+    if max(height, width) / min(height, width) > 200:
+        raise ValueError(f"absolute aspect ratio must be smaller than 200, got {max(height, width) / min(height, width)}")
+    h_bar = round(height / factor) * factor
+    w_bar = round(width / factor) * factor
+    if h_bar * w_bar > max_pixels:
+        beta = math.sqrt((height * width) / max_pixels)
+        h_bar = max(factor, math.floor(height / beta / factor) * factor)
+        w_bar = max(factor, math.floor(width / beta / factor) * factor)
+    elif h_bar * w_bar < min_pixels:
+        beta = math.sqrt(min_pixels / (height * width))
+        h_bar = math.ceil(height * beta / factor) * factor
+        w_bar = math.ceil(width * beta / factor) * factor
+    return h_bar, w_bar
+
+
+def to_rgb(image) -> np.ndarray:
+    """A PIL image (or an HWC uint8 array) -> uint8 RGB [h, w, 3], as the processor's convert_to_rgb does in transformers 5: any mode other
+    than RGB goes through `image.convert("RGB")` (RGBA drops its alpha; transformers 4.x composited RGBA on white first - unpinned)."""
+    if isinstance(image, np.ndarray):
+        a = image if image.ndim == 3 else np.repeat(image[..., None], 3, axis=2)
+        if a.dtype != np.uint8 or a.shape[2] != 3:
+            raise ValueError(f"expected uint8 RGB [h, w, 3], got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
+    if image.mode != "RGB":
+        image = image.convert("RGB")
+    return np.asarray(image, dtype=np.uint8)
+
+
+def chat_text(prompt: str) -> str:
+    """The chat-formatted text of one photo + prompt (CHAT_TEMPLATE), one <|image_pad|> placeholder before expansion."""
+    return CHAT_TEMPLATE.format(prompt=prompt)
+
+
+def expand_image_pads(text: str, grids, merge_size: int = 2, image_pad: str = IMAGE_PAD) -> str:
+    """The processor's text-level expansion: the i-th <|image_pad|> becomes t * h * w / merge^2 copies for grid i."""
+    parts = text.split(image_pad)
+    grids = np.asarray(grids, np.int64).reshape(-1, 3)
+    if len(parts) - 1 != len(grids):
+        raise ValueError(f"{len(parts) - 1} image placeholders for {len(grids)} images")
+    out = [parts[0]]
+    for g, rest in zip(grids, parts[1:]):
+        out.append(image_pad * int(g[0] * g[1] * g[2] // merge_size ** 2))
+        out.append(rest)
+    return "".join(out)
+
+
+def left_pad(id_rows: Sequence[Sequence[int]], pad_token_id: int):
+    """Token-id rows of different lengths -> (input_ids int32 [n, L], attention_mask int32 [n, L]), padded on the LEFT (the processor's
+    padding=True with padding_side='left', the only side on which batched greedy generation of a decoder-only model is defined)."""
+    L = max(len(r) for r in id_rows)
+    ids = np.full((len(id_rows), L), int(pad_token_id), np.int32)
+    am = np.zeros((len(id_rows), L), np.int32)
+    for b, r in enumerate(id_rows):
+        if len(r):
+            ids[b, L - len(r):] = np.asarray(r, np.int32)
+            am[b, L - len(r):] = 1
+    return ids, am
 
 
 def vision_indices(grid_thw, spatial_merge_size: int = 2, window_size: int = 112, patch_size: int = 14):
@@ -55,16 +134,20 @@ def vision_indices(grid_thw, spatial_merge_size: int = 2, window_size: int = 112
             "cu_seqlens": np.asarray(cu_full, np.int32)}
 
 
-def rope_index(input_ids, grid_thw, image_token_id: int, spatial_merge_size: int = 2):
+def rope_index(input_ids, grid_thw, image_token_id: int, spatial_merge_size: int = 2, attention_mask=None):
     """M-RoPE position ids [3, n_seq, len] of prompts with image placeholders: numpy restatement of Qwen2_5_VLModel.get_rope_index for
-    still images and unpadded sequences (what the reference's processor + generate compute): text tokens count up on all three axes; a
-    run of <|image_pad|> tokens takes (start, start + row, start + column) over its merged grid, and the next text token continues at
-    start + max(rows, columns). Returns (position_ids, next_position [n_seq] = the position of the first generated token)."""
+    still images (what the reference's processor + generate compute): text tokens count up on all three axes; a run of <|image_pad|>
+    tokens takes (start, start + row, start + column) over its merged grid, and the next text token continues at start + max(rows,
+    columns). With attention_mask, only the unmasked tokens of a row are counted (from 0) and masked positions keep 0, as transformers
+    does. Returns (position_ids, next_position [n_seq] = the position of the first generated token: the row's maximum + 1)."""
     ids = np.asarray(input_ids)
     grids = iter(np.asarray(grid_thw, dtype=np.int64).reshape(-1, 3))
     out = np.zeros((3,) + ids.shape, np.int32)
     nxt = np.zeros(ids.shape[0], np.int32)
-    for b, row in enumerate(ids):
+    keep = np.ones(ids.shape, bool) if attention_mask is None else np.asarray(attention_mask).astype(bool)
+    assert keep.shape == ids.shape, (keep.shape, ids.shape)
+    for b, full_row in enumerate(ids):
+        row = full_row[keep[b]]
         cur, i, cols = 0, 0, []
         while i < len(row):
             if row[i] == image_token_id:
@@ -83,7 +166,7 @@ def rope_index(input_ids, grid_thw, image_token_id: int, spatial_merge_size: int
                 cur += 1
                 i += 1
         p = np.concatenate(cols, 1)
-        out[:, b] = p
+        out[:, b, keep[b]] = p
         nxt[b] = p.max() + 1
     return out, nxt
 
@@ -105,10 +188,12 @@ def edit_distance(a: str, b: str) -> int:
 class VLMTagger:
     """Same constructor and public surface as the reference class (models/vlm_tagger.py:45-87): `model_config` (model_path,
     vlm_batch_size, max_new_tokens, ...), optional `scoring_config` for the tag vocabulary. `engine` is the facet_amd Engine the decoder
-    lives in; `decode` / `encode` are the tokenizer callables of the checkpoint's processor (ids -> text, chat-formatted text -> ids)."""
+    lives in; `decode` / `encode` are the tokenizer callables of the checkpoint's processor (ids -> text with special tokens skipped,
+    chat-formatted text -> ids); `special_tokens` overrides QWEN2_5_VL_TOKENS (image / vision / pad / EOS ids)."""
 
-    def __init__(self, model_config: Dict[str, Any], scoring_config=None, engine=None, decode=None, encode=None):
+    def __init__(self, model_config: Dict[str, Any], scoring_config=None, engine=None, decode=None, encode=None, special_tokens=None):
         self.model_config = model_config
+        self.tokens = dict(QWEN2_5_VL_TOKENS, **(special_tokens or {}))
         self.scoring_config = scoring_config
         self.engine = engine
         self.decode, self.encode = decode, encode
@@ -198,6 +283,75 @@ class VLMTagger:
             raise RuntimeError("VLMTagger.load() first")
         n_new = int(max_new_tokens or self.model_config.get("max_new_tokens", 100))
         return self.engine.vlm_generate(np.asarray(input_ids), n_new, position_ids=position_ids, eos_token_ids=eos_token_ids)
+
+    # -- photos in (reference :202-308 tag_image / tag_batch, :327-368 _batch_qwen2_5) -----------------------------------------------------
+    def prepare_inputs(self, images, prompt: Optional[str] = None):
+        """What `processor(text=[chat text] * n, images=images, padding=True)` yields, with the pixel work left to the GPU: -> dict of
+        rgb (uint8 arrays), sizes (smart_resize targets), grid_thw [n, 3], input_ids / attention_mask int32 [n, L] (left-padded),
+        position_ids [3, n, L] and image_rows (flat indices of the <|image_pad|> tokens, in order)."""
+        if self.encode is None:
+            raise RuntimeError("no tokenizer: pass encode= (the checkpoint's processor.tokenizer.encode)")
+        rgb = [to_rgb(im) for im in images]
+        lo, hi = int(self.model_config.get("min_pixels", MIN_PIXELS)), int(self.model_config.get("max_pixels", MAX_PIXELS))
+        sizes = [smart_resize(a.shape[0], a.shape[1], 28, lo, hi) for a in rgb]
+        grid = np.array([[1, oh // 14, ow // 14] for oh, ow in sizes], np.int64)
+        text = chat_text(self._build_prompt() if prompt is None else prompt)
+        rows = [list(self.encode(expand_image_pads(text, g[None]))) for g in grid]
+        ids, am = left_pad(rows, self.tokens["pad_token_id"])
+        img = self.tokens["image_token_id"]
+        pos, _ = rope_index(ids, grid, img, attention_mask=am)
+        image_rows = np.flatnonzero(((ids == img) & (am == 1)).reshape(-1)).astype(np.int32)
+        return dict(rgb=rgb, sizes=sizes, grid_thw=grid, input_ids=ids, attention_mask=am, position_ids=pos, image_rows=image_rows)
+
+    def generate_from_images(self, images, max_new_tokens: Optional[int] = None, prompt: Optional[str] = None):
+        """Greedy generation for a list of photos (any sizes): preprocessing and the vision tower on the GPU from uint8 pixels, one
+        left-padded batch through the decoder. -> int [n, max_new_tokens]. An EngineCapacityError means the batch did not fit."""
+        if self.model is None:
+            raise RuntimeError("VLMTagger.load() first")
+        x = self.prepare_inputs(images, prompt)
+        self.engine.vlm_preprocess_rgb(x["rgb"], x["sizes"], IMAGE_MEAN, IMAGE_STD)
+        idx = vision_indices(x["grid_thw"])
+        self.engine.vlm_encode_preprocessed(idx["patch_pos_hw"], idx["window_index"], idx["cu_window_seqlens"], idx["cu_seqlens"], want_embeds=False)
+        n_new = int(max_new_tokens or self.model_config.get("max_new_tokens", 100))
+        return self.engine.vlm_generate(x["input_ids"], n_new, position_ids=x["position_ids"], eos_token_ids=self.tokens["eos_token_ids"],
+                                        image_rows=x["image_rows"], attention_mask=x["attention_mask"])
+
+    def _texts(self, generated_ids) -> List[str]:
+        """Each row cut at its first EOS id, then the tokenizer's decode."""
+        if self.decode is None:
+            raise RuntimeError("no tokenizer: pass decode= (processor.decode of the checkpoint, skip_special_tokens=True)")
+        eos = [int(e) for e in self.tokens["eos_token_ids"]]
+        out = []
+        for row in np.asarray(generated_ids):
+            hit = np.flatnonzero(np.isin(row, eos))
+            out.append(self.decode([int(t) for t in row[:hit[0] if hit.size else len(row)]]))
+        return out
+
+    def tag_image(self, image, max_tags: int = 5) -> List[str]:
+        """Tags of one photo (PIL image of any mode and size)."""
+        return self._parse_tags(self._texts(self.generate_from_images([image]))[0], max_tags)
+
+    def _tag_sub_batch(self, images, max_tags: int) -> List[List[str]]:
+        if len(images) == 1:
+            return [self.tag_image(images[0], max_tags)]
+        return [self._parse_tags(t, max_tags) for t in self._texts(self.generate_from_images(images))]
+
+    def tag_batch(self, images, max_tags: int = 5) -> List[List[str]]:
+        """Tags of every photo, in order: sub-batches of vlm_batch_size as one left-padded batch each; a sub-batch that does not fit the
+        engine (EngineCapacityError, the engine's out-of-memory) is retried one image at a time, and an image that still does not fit
+        gets [] (reference :297-306). Every other error propagates."""
+        results: List[List[str]] = []
+        for i in range(0, len(images), self.batch_size):
+            sub = images[i:i + self.batch_size]
+            try:
+                results.extend(self._tag_sub_batch(sub, max_tags))
+            except EngineCapacityError:
+                for im in sub:
+                    try:
+                        results.append(self.tag_image(im, max_tags))
+                    except EngineCapacityError:
+                        results.append([])
+        return results
 
     def tags_from_ids(self, generated_ids, max_tags: int = 5) -> List[List[str]]:
         """Generated ids -> text (the checkpoint's tokenizer) -> vocabulary tags."""

@@ -33,7 +33,9 @@ enum fe_status {
   FE_OK = 0,
   FE_ERR_INVALID = -1,   /* bad argument / shape */
   FE_ERR_RUNTIME = -2,   /* HIP failure or internal check */
-  FE_ERR_NOT_LOADED = -3 /* model weights not committed */
+  FE_ERR_NOT_LOADED = -3, /* model weights not committed */
+  FE_ERR_CAPACITY = -4   /* the batch does not fit (device memory, arena, KV cache): returned by fe_vlm_preprocess_rgb,
+                            fe_vlm_encode_preprocessed and fe_vlm_prefill_images_padded only - retry with fewer images */
 };
 
 /* Model slots (reference names: models/model_manager.py:393-437 'topiq','clip','samp_net',...). */
@@ -119,6 +121,22 @@ int fe_vlm_decode_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* positi
  * device memory and one captured HIP graph of a decode step is replayed; out_tokens [n_steps][n_seq] = the token each step chose.
  * End-of-sequence handling is the caller's (cut the rows at the first EOS id). */
 int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens);
+/* Photos in (the image half of `processor(text=texts, images=images, padding=True)`, models/vlm_tagger.py:245-259 / :346-360):
+ * fe_vlm_preprocess_rgb = Qwen2-VL's image processor (PIL backend) after its size choice: rgb holds n_images uint8 RGB images [h][w][3] back
+ * to back; sizes [n_images][4] = h, w and the target oh, ow of each (transformers' smart_resize, computed by the caller: multiples of 28).
+ * Each image is resampled with PIL's bicubic filter (bit-exact), rescaled by 1/255, normalised by mean / std [3] and patchified into the
+ * processor's rows [oh/14 * ow/14][1176] ((gh/2, gw/2, 2, 2, C, T = 2, 14, 14) order, the frame duplicated), images concatenated. The rows
+ * stay on the device in bf16 (what the patch embedding converts pixel_values to) for the next fe_vlm_encode_preprocessed; when
+ * pixel_values is not NULL they are also copied out as the processor's fp32 values.
+ * fe_vlm_encode_preprocessed = fe_vlm_encode_images on those rows (same index arrays, no pixel upload).
+ * fe_vlm_prefill_images_padded = fe_vlm_prefill_images of a LEFT-padded batch: sequence b's first pad[b] positions (< len) are padding
+ * (attention_mask 0): no position attends to them, in the prefill or in any later fe_vlm_decode_step / fe_vlm_generate, and their own
+ * rows compute zeros. The other prefill entry points reset the padding to none. */
+int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const int32_t* sizes, const float* mean, const float* stdv, float* pixel_values);
+int fe_vlm_encode_preprocessed(fe_ctx* ctx, const int32_t* patch_pos_hw, const int32_t* window_index, const int32_t* cu_window_seqlens, int n_windows,
+                               const int32_t* cu_seqlens, int n_images, float* embeds);
+int fe_vlm_prefill_images_padded(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int len, int max_seq, const int32_t* pad,
+                                 const int32_t* image_rows, int n_image_rows, int32_t* next_tokens, float* logits);
 
 /* ---- device buffers (so callers can keep batches resident in HBM without torch) ------------- */
 int fe_dev_alloc(fe_ctx* ctx, size_t bytes, void** d_out);

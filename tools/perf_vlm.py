@@ -1,6 +1,10 @@
 """Throughput of the VLM tagger's text decoder at Qwen2.5-VL-7B's geometry (BASELINE configs[4] shape; slice 1 = decoder only).
 
-  python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32]
+  python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32] [--vision N] [--from-rgb N] [--pad P]
+
+--from-rgb N times the vision tower from N uint8 photos (GPU preprocessing: fe_vlm_preprocess_rgb + fe_vlm_encode_preprocessed) against
+the same photos' fp32 pixel_values uploaded by fe_vlm_encode_images; --pad P also times the decode steps of a left-padded batch (every
+other sequence carries P pad tokens; fe_vlm_prefill_images_padded) next to the unpadded one.
 
 Seeded synthetic weights in the 7B geometry (hidden 3584, 28 q heads over 4 KV heads of 128, intermediate 18944, vocab 152064); with
 --layers < 28 the per-layer work is measured on that many layers and the lm_head once, and both the measured and the 28-layer
@@ -20,12 +24,14 @@ ap.add_argument("--prompt", type=int, default=512)
 ap.add_argument("--new", type=int, default=16)
 ap.add_argument("--batches", default="1,8,32")
 ap.add_argument("--vision", type=int, default=0, help="also time the vision tower: this many images of 1036x1036 pixels (74x74 patches) per call, full depth 32")
+ap.add_argument("--from-rgb", type=int, default=0, help="time vision encode from this many uint8 1036x1036 photos against the fp32 pixel_values upload")
+ap.add_argument("--pad", type=int, default=0, help="also time decode steps with every other sequence left-padded by this many tokens")
 a = ap.parse_args()
 H, NH, NKV, INTER, V = 3584, 28, 4, 18944, 152064
 t0 = time.time()
 from facet_amd.weights import qwen2_5_vl_vision_spec
 spec = qwen2_5_vl_text_spec(hidden=H, layers=a.layers, heads=NH, kv_heads=NKV, inter=INTER, vocab=V)
-if a.vision:
+if a.vision or a.from_rgb:
     spec = spec + qwen2_5_vl_vision_spec()      # 32 blocks of 1280 (16 heads of 80), intermediate 3420, merger to 3584
 sd = synthetic_state_dict(None, 3, spec=spec)
 print(f"weights drawn in {time.time() - t0:.0f} s", flush=True)
@@ -47,6 +53,24 @@ if a.vision:
     ms = e.timer_stop()
     print(f"vision tower: {a.vision} images of 74x74 patches ({n // 4 // a.vision} image tokens each) in {ms:.2f} ms = {a.vision / ms * 1e3:.1f} images/s, "
           f"{e.flops() / ms / 1e9:.1f} TFLOP/s (projections; host patches uploaded inside the call)", flush=True)
+if a.from_rgb:
+    from facet_amd.vlm_tagger import vision_indices, IMAGE_MEAN, IMAGE_STD
+    rgb = [np.random.default_rng(i).integers(0, 256, (1036, 1036, 3), dtype=np.uint8) for i in range(a.from_rgb)]
+    sizes = [(1036, 1036)] * a.from_rgb
+    idx = vision_indices([[1, 74, 74]] * a.from_rgb)
+    args = (idx["patch_pos_hw"], idx["window_index"], idx["cu_window_seqlens"], idx["cu_seqlens"])
+    pv = e.vlm_preprocess_rgb(rgb, sizes, IMAGE_MEAN, IMAGE_STD, want_pixel_values=True)
+    e.vlm_encode_images(pv, *args, want_embeds=False)
+    t0 = time.perf_counter(); e.vlm_encode_images(pv, *args, want_embeds=False); t_f32 = (time.perf_counter() - t0) * 1e3
+    e.vlm_preprocess_rgb(rgb, sizes, IMAGE_MEAN, IMAGE_STD); e.vlm_encode_preprocessed(*args, want_embeds=False)
+    t0 = time.perf_counter()
+    e.vlm_preprocess_rgb(rgb, sizes, IMAGE_MEAN, IMAGE_STD)
+    t_pre = (time.perf_counter() - t0) * 1e3
+    e.vlm_encode_preprocessed(*args, want_embeds=False)
+    t_u8 = (time.perf_counter() - t0) * 1e3
+    print(f"vision from uint8: {a.from_rgb} photos 1036x1036 -> preprocess {t_pre:.2f} ms (uploads {sum(x.nbytes for x in rgb) / 1e6:.1f} MB) + encode = {t_u8:.2f} ms "
+          f"= {a.from_rgb / t_u8 * 1e3:.1f} images/s | fp32 pixel_values upload ({pv.nbytes / 1e6:.0f} MB) + encode {t_f32:.2f} ms = {a.from_rgb / t_f32 * 1e3:.1f} images/s "
+          f"(wall clock of the calls)", flush=True)
 layer_params = H * (NH + 2 * NKV) * 128 + NH * 128 * H + 3 * H * INTER
 head_params = V * H
 for B in [int(b) for b in a.batches.split(",")]:
@@ -71,4 +95,20 @@ for B in [int(b) for b in a.batches.split(",")]:
     print(f"B={B:3d} L={L}: prefill {t_pre:8.2f} ms = {B * L / t_pre * 1e3:9.0f} tok/s, {fl_pre / t_pre / 1e9:7.1f} TFLOP/s ({a.layers} layers; x28/{a.layers}: {full_pre:.1f} ms) | "
           f"decode {t_dec:6.3f} ms/step = {B / t_dec * 1e3:7.0f} tok/s, weights {wbytes / t_dec / 1e6:6.0f} GB/s = {wbytes / t_dec / 1e6 / 8000:.2f} of HBM peak "
           f"(28 layers: ~{full_dec:.2f} ms/step) | device-resident loop (fe_vlm_generate) {t_graph:6.3f} ms/step = {wbytes / t_graph / 1e6:6.0f} GB/s = {wbytes / t_graph / 1e6 / 8000:.2f} of peak", flush=True)
+    if a.pad:
+        am = np.ones((B, L), np.int32)
+        am[1::2, :min(a.pad, L - 1)] = 0
+        pp = np.where(am == 1, np.cumsum(am, 1) - 1, 0).astype(np.int32)
+        pos3 = np.broadcast_to(pp, (3, B, L))
+        e.vlm_prefill(p, pos3, max_seq=L + a.new + 8, pad=(am == 0).sum(1))
+        nxt = e.vlm_prefill(p, pos3, max_seq=L + a.new + 8, pad=(am == 0).sum(1))
+        posd = np.broadcast_to(pp.max(1) + 1, (3, B)).astype(np.int32)
+        e.vlm_decode_step(nxt, posd)
+        t0 = time.perf_counter()
+        for s in range(a.new):
+            nxt = e.vlm_decode_step(nxt, posd + 1 + s)
+        t_pd = (time.perf_counter() - t0) / a.new * 1e3
+        t0 = time.perf_counter(); e.vlm_generate(p, a.new + 1, position_ids=pos3, attention_mask=am); t_pall = (time.perf_counter() - t0) * 1e3
+        print(f"B={B:3d} L={L} padded (every other row {a.pad} pad tokens): decode {t_pd:6.3f} ms/step (unpadded {t_dec:6.3f}) | "
+              f"prefill + fe_vlm_generate {t_pall:.2f} ms (unpadded {t_all:.2f})", flush=True)
 e.close()
