@@ -123,6 +123,9 @@ SIGNATURES = {
     "fe_vlm_preprocess_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), _f32p, _f32p, _f32p]),
     "fe_vlm_encode_preprocessed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                              C.POINTER(C.c_int32), C.c_int, _f32p]),
+    "fe_vlm_vision_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "fe_vlm3_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "fe_vlm3_encode_images": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f32p, C.POINTER(C.c_int32), C.c_int, _f32p, _f32p]),
     "fe_vlm_prefill_images_padded": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_ensemble_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
@@ -621,7 +624,8 @@ class Engine:
     def vlm_preprocess_rgb(self, images, sizes, mean, std, want_pixel_values=False):
         """Qwen2-VL's image processor on the GPU: images = list of uint8 RGB arrays [h, w, 3], sizes = the target (oh, ow) of each
         (facet_amd.vlm_tagger.smart_resize). The patch rows stay on the device for vlm_encode_preprocessed; with want_pixel_values they
-        are also returned as the processor's float32 pixel_values [n_patches, 1176]."""
+        are also returned as the processor's float32 pixel_values [n_patches, 1176] (a Qwen3-VL model: 16-pixel patches, [n_patches, 1536];
+        the engine patchifies by the tower it holds, and so are the rows sized here)."""
         imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
         assert imgs and all(a.ndim == 3 and a.shape[2] == 3 for a in imgs), [a.shape for a in imgs]
         sz, szp = self._i32([[a.shape[0], a.shape[1], int(oh), int(ow)] for a, (oh, ow) in zip(imgs, sizes)])
@@ -629,8 +633,11 @@ class Engine:
         packed = np.concatenate([a.reshape(-1) for a in imgs])
         m, mp = _f32(mean)
         s, sp = _f32(std)
-        n = int(((sz[:, 2] // 14) * (sz[:, 3] // 14)).sum())
-        out = np.empty((n, 1176), np.float32) if want_pixel_values else None
+        out = None
+        if want_pixel_values:      # rows of the committed tower's patch side (the engine checks the sizes against it before writing)
+            patch = self.vlm_vision_dims()["patch"]
+            n = int(((sz[:, 2] // patch) * (sz[:, 3] // patch)).sum())
+            out = np.empty((n, 6 * patch * patch), np.float32)
         self._ck(self.lib.fe_vlm_preprocess_rgb(self.h, packed.ctypes.data_as(C.c_void_p), len(imgs), szp, mp, sp,
                                                 out.ctypes.data_as(_f32p) if want_pixel_values else None))
         return out
@@ -646,6 +653,45 @@ class Engine:
         out = np.empty((n // 4, self.vlm_dims()["hidden"]), np.float32) if want_embeds else None
         self._ck(self.lib.fe_vlm_encode_preprocessed(self.h, pp, wp, cwp, len(cw) - 1, cfp, len(cf) - 1, out.ctypes.data_as(_f32p) if want_embeds else None))
         return out
+
+    def vlm3_configure(self, n_heads=16, n_kv_heads=8, head_dim=128, rope_theta=5e6, rms_eps=1e-6, mrope_section=(24, 20, 20), vis_heads=16,
+                       deepstack_indexes=(5, 11, 17)):
+        """The NEXT load_weights(FE_MODEL_VLM, ...) builds Qwen3-VL (Qwen3VLForConditionalGeneration; defaults = Qwen3-VL-2B's geometry)."""
+        ms = (C.c_int * 3)(*[int(v) for v in mrope_section])
+        ds = (C.c_int * max(1, len(deepstack_indexes)))(*[int(v) for v in deepstack_indexes])
+        self._ck(self.lib.fe_vlm3_configure(self.h, int(n_heads), int(n_kv_heads), int(head_dim), float(rope_theta), float(rms_eps), ms, int(vis_heads),
+                                            ds, len(deepstack_indexes)))
+
+    def vlm_vision_dims(self):
+        """The committed vision tower: patch side, patch row width, DeepStack levels, position-table side (fe_vlm_vision_dims)."""
+        d = (C.c_int * 4)()
+        self._ck(self.lib.fe_vlm_vision_dims(self.h, d))
+        return dict(zip(("patch", "patch_dim", "n_deepstack", "pos_side"), list(d)))
+
+    def vlm3_encode_images(self, pixel_values, patch_pos_hw, interp_idx, interp_w, cu_seqlens, want_embeds=True, want_deepstack=False):
+        """Qwen3-VL `model.visual(pixel_values, grid_thw)`: pixel_values float [n_patches, 1536], or None = the rows of the last
+        vlm_preprocess_rgb. Index arrays: facet_amd.vlm_tagger.vision_inputs_qwen3. The merged embeddings and the DeepStack features stay
+        on the device for the next vlm_prefill(..., image_rows=...). -> (embeds [n/4, hidden] or None, deepstack [levels, n/4, hidden]
+        or None), bf16 values widened to float32; the output shapes come from the committed model (vlm_dims / vlm_vision_dims)."""
+        pos, pp = self._i32(patch_pos_hw)
+        n = pos.shape[0]
+        assert pos.shape == (n, 2) and n % 4 == 0, pos.shape
+        ii, iip = self._i32(np.asarray(interp_idx).reshape(n, 4))
+        iw, iwp = _f32(np.asarray(interp_w, np.float32).reshape(n, 4))
+        cf, cfp = self._i32(cu_seqlens)
+        vd = self.vlm_vision_dims()
+        pvp = None
+        if pixel_values is not None:
+            pv = np.ascontiguousarray(pixel_values, dtype=np.float32)
+            if pv.shape != (n, vd["patch_dim"]):
+                raise ValueError(f"pixel_values {pv.shape}: expected ({n}, {vd['patch_dim']})")
+            pvp = pv.ctypes.data_as(_f32p)
+        hidden = self.vlm_dims()["hidden"]
+        out = np.empty((n // 4, hidden), np.float32) if want_embeds else None
+        ds = np.empty((vd["n_deepstack"], n // 4, hidden), np.float32) if want_deepstack and vd["n_deepstack"] > 0 else None
+        self._ck(self.lib.fe_vlm3_encode_images(self.h, pvp, n, pp, iip, iwp, cfp, len(cf) - 1, out.ctypes.data_as(_f32p) if want_embeds else None,
+                                                ds.ctypes.data_as(_f32p) if ds is not None else None))
+        return out, ds
 
     def vlm_dims(self):
         d = (C.c_int * 8)()

@@ -1397,21 +1397,23 @@ int fe_vlm_encode_preprocessed(fe_ctx* ctx, const int32_t* patch_pos_hw, const i
 }
 int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const int32_t* sizes, const float* mean, const float* stdv, float* pixel_values) {
   FE_API_BEGIN(ctx)
-  if (!ctx->c.vlm || !ctx->c.vlm->vis.present) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;      // Qwen3-VL: 16-pixel patches (32-pixel merge blocks)
+  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
   Ctx& C = ctx->c;
   VlmModel& m = *C.vlm;
   FE_CHECK(rgb && sizes && mean && stdv && n_images > 0, "bad arguments");
-  FE_CHECK(m.vis.patch_dim == 3 * 2 * 14 * 14, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x 14 x 14 built)", m.vis.patch_dim);
+  const int P = q3 ? 16 : 14, F = 2 * P, PD = 6 * P * P;
+  FE_CHECK((q3 ? m.vis3.patch_dim : m.vis.patch_dim) == PD, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x %d x %d built)", q3 ? m.vis3.patch_dim : m.vis.patch_dim, P, P);
   size_t in_b = 0, rows = 0, px_max = 0;
   for (int i = 0; i < n_images; ++i) {
     const int h = sizes[4 * i], w = sizes[4 * i + 1], oh = sizes[4 * i + 2], ow = sizes[4 * i + 3];
-    FE_CHECK(h > 0 && w > 0 && oh >= 28 && ow >= 28 && oh % 28 == 0 && ow % 28 == 0 && (size_t)oh * ow <= ((size_t)1 << 26),
-             "preprocess_rgb: image %d: %dx%d -> %dx%d (target sides must be positive multiples of 28)", i, h, w, oh, ow);
+    FE_CHECK(h > 0 && w > 0 && oh >= F && ow >= F && oh % F == 0 && ow % F == 0 && (size_t)oh * ow <= ((size_t)1 << 26),
+             "preprocess_rgb: image %d: %dx%d -> %dx%d (target sides must be positive multiples of %d)", i, h, w, oh, ow, F);
     in_b += (size_t)h * w * 3;
-    rows += (size_t)(oh / 14) * (ow / 14);
+    rows += (size_t)(oh / P) * (ow / P);
     px_max = std::max(px_max, (size_t)oh * ow * 3);
   }
-  FE_CHECK(rows < ((size_t)1 << 31) / 1176, "preprocess_rgb: %zu patches", rows);
+  FE_CHECK(rows < ((size_t)1 << 31) / PD, "preprocess_rgb: %zu patches", rows);
   // the processor's arithmetic, once per (channel, value): float32(float64(u) * (1 / 255)), then float32 (x - mean) / std
   std::vector<float> lut(3 * 256);
   for (int c = 0; c < 3; ++c)
@@ -1422,7 +1424,7 @@ int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const i
   if ((int)rows > m.pre_cap) {
     if (m.pre_pv) (void)hipFree(m.pre_pv);
     m.pre_pv = nullptr; m.pre_cap = 0; m.pre_rows = 0;
-    FE_HIP(hipMalloc((void**)&m.pre_pv, rows * 1176 * sizeof(bf16)));
+    FE_HIP(hipMalloc((void**)&m.pre_pv, rows * PD * sizeof(bf16)));
     m.pre_cap = (int)rows;
   }
   m.pre_rows = 0;
@@ -1430,18 +1432,19 @@ int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const i
   uint8_t* d_in = (uint8_t*)C.arena.alloc(in_b);
   float* d_lut = (float*)C.arena.alloc(lut.size() * sizeof(float));
   uint8_t* d_img = (uint8_t*)C.arena.alloc(px_max);
-  float* d_f = pixel_values ? (float*)C.arena.alloc(rows * 1176 * sizeof(float)) : nullptr;
+  float* d_f = pixel_values ? (float*)C.arena.alloc(rows * PD * sizeof(float)) : nullptr;
   FE_HIP(hipMemcpyAsync(d_in, rgb, in_b, hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, C.stream));
   size_t off = 0, row0 = 0;
   for (int i = 0; i < n_images; ++i) {      // one resample pair and one patchify launch per image (tagger batches are a few images)
     const int h = sizes[4 * i], w = sizes[4 * i + 1], oh = sizes[4 * i + 2], ow = sizes[4 * i + 3];
     resize_u8(C, d_in + off, 1, h, w, oh, ow, FE_BICUBIC, 0, oh, 0, ow, d_img);
-    vlm_patchify(C, d_img, oh, ow, d_lut, m.pre_pv + row0 * 1176, d_f ? d_f + row0 * 1176 : nullptr);
+    if (q3) vlm_patchify16(C, d_img, oh, ow, d_lut, m.pre_pv + row0 * PD, d_f ? d_f + row0 * PD : nullptr);
+    else vlm_patchify(C, d_img, oh, ow, d_lut, m.pre_pv + row0 * PD, d_f ? d_f + row0 * PD : nullptr);
     off += (size_t)h * w * 3;
-    row0 += (size_t)(oh / 14) * (ow / 14);
+    row0 += (size_t)(oh / P) * (ow / P);
   }
-  if (pixel_values) FE_HIP(hipMemcpyAsync(pixel_values, d_f, rows * 1176 * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  if (pixel_values) FE_HIP(hipMemcpyAsync(pixel_values, d_f, rows * PD * sizeof(float), hipMemcpyDeviceToHost, C.stream));
   FE_HIP(hipStreamSynchronize(C.stream));
   m.pre_rows = (int)rows;
   FE_API_END_CAPACITY(ctx)
@@ -1454,6 +1457,105 @@ int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, flo
   VlmConfig& g = ctx->c.vlm_cfg;
   g.n_heads = n_heads; g.n_kv_heads = n_kv_heads; g.head_dim = head_dim; g.rope_theta = rope_theta; g.rms_eps = rms_eps;
   for (int i = 0; i < 3; ++i) g.mrope[i] = mrope_section[i];
+  g.qwen3 = false; g.n_deepstack = 0;      // (the Qwen2.5-VL family: what a context builds unless fe_vlm3_configure said otherwise)
+  FE_API_END(ctx)
+}
+// ---- Qwen3-VL: the same decoder entry points serve the family the next commit builds --------------------------------------------------------
+int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads,
+                      const int* deepstack_indexes, int n_deepstack) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && head_dim == 128 && rope_theta > 0.f && rms_eps > 0.f && mrope_section && vis_heads > 0 &&
+           n_deepstack >= 0 && n_deepstack <= 8 && (n_deepstack == 0 || deepstack_indexes),
+           "vlm3_configure: bad geometry (head_dim must be 128, at most 8 DeepStack levels)");
+  FE_CHECK(mrope_section[0] + mrope_section[1] + mrope_section[2] == 64 && mrope_section[0] >= 0 && mrope_section[1] >= 0 && mrope_section[2] >= 0,
+           "vlm3_configure: mrope sections must sum to head_dim / 2");
+  std::lock_guard<std::mutex> lk(ctx->c.mu);
+  VlmConfig& g = ctx->c.vlm_cfg;
+  g.n_heads = n_heads; g.n_kv_heads = n_kv_heads; g.head_dim = head_dim; g.rope_theta = rope_theta; g.rms_eps = rms_eps;
+  for (int i = 0; i < 3; ++i) g.mrope[i] = mrope_section[i];
+  g.vis_heads = vis_heads;
+  g.qwen3 = true;
+  g.n_deepstack = n_deepstack;
+  for (int i = 0; i < n_deepstack; ++i) g.deepstack[i] = deepstack_indexes[i];
+  FE_API_END(ctx)
+}
+int fe_vlm3_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* interp_idx, const float* interp_w,
+                          const int32_t* cu_seqlens, int n_seg, float* embeds, float* deepstack) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen3 || !ctx->c.vlm->vis3.present) {
+    ctx->c.err = "qwen3-vl vision tower not loaded (fe_vlm3_configure before the commit; the checkpoint needs model.visual.*)";
+    return FE_ERR_NOT_LOADED;
+  }
+  Ctx& C = ctx->c;
+  VlmModel& m = *C.vlm;
+  const Vlm3VisionW& v = m.vis3;
+  if (!pixel_values) {
+    FE_CHECK(m.pre_pv && m.pre_rows > 0, "vlm3_encode_images: no pixel_values and no rows of a fe_vlm_preprocess_rgb");
+    FE_CHECK(n_patches == m.pre_rows, "vlm3_encode_images: %d patches but the last fe_vlm_preprocess_rgb left %d rows", n_patches, m.pre_rows);
+  }
+  FE_CHECK(patch_pos_hw && interp_idx && interp_w && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_seg > 0, "bad arguments");
+  FE_CHECK(cu_seqlens[0] == 0 && cu_seqlens[n_seg] == n_patches, "segment bounds must cover the patches");
+  int max_seg = 0;
+  for (int i = 0; i < n_seg; ++i) { FE_CHECK(cu_seqlens[i + 1] > cu_seqlens[i], "empty image segment"); max_seg = std::max(max_seg, cu_seqlens[i + 1] - cu_seqlens[i]); }
+  for (size_t i = 0; i < (size_t)n_patches * 4; ++i) FE_CHECK(interp_idx[i] >= 0 && interp_idx[i] < v.n_pos, "interp_idx out of range (%d position embeddings)", v.n_pos);
+  const int rows = n_patches / 4, nds = (int)v.ds_blocks.size();
+  if (rows > m.img_cap) {
+    if (m.img_embeds) (void)hipFree(m.img_embeds);
+    m.img_embeds = nullptr; m.img_cap = 0;
+    FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
+    m.img_cap = rows;
+  }
+  if (nds > 0 && rows > m.ds_cap) {
+    if (m.ds_feats) (void)hipFree(m.ds_feats);
+    m.ds_feats = nullptr; m.ds_cap = 0; m.ds_n = 0;
+    FE_HIP(hipMalloc((void**)&m.ds_feats, (size_t)nds * rows * m.hidden * sizeof(bf16)));
+    m.ds_cap = rows;
+  }
+  m.img_rows = 0; m.ds_n = 0;
+  C.arena.reset();
+  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * v.patch_dim * sizeof(float)) : nullptr;
+  int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
+  int* d_ii = (int*)C.arena.alloc((size_t)n_patches * 4 * sizeof(int));
+  float* d_iw = (float*)C.arena.alloc((size_t)n_patches * 4 * sizeof(float));
+  int* d_cu = (int*)C.arena.alloc((size_t)(n_seg + 1) * sizeof(int));
+  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * v.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_ii, interp_idx, (size_t)n_patches * 4 * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_iw, interp_w, (size_t)n_patches * 4 * sizeof(float), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_cu, cu_seqlens, (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  vlm3_vision_forward(C, m, d_pv, pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv, n_patches, d_pos, d_ii, d_iw, d_cu, n_seg, max_seg, m.img_embeds,
+                      nds > 0 ? m.ds_feats : (bf16*)nullptr);
+  m.img_rows = rows; m.ds_n = nds;
+  const size_t per = (size_t)rows * m.hidden;
+  if (embeds || (deepstack && nds > 0)) {
+    float* d_f = (float*)C.arena.alloc(per * sizeof(float));
+    if (embeds) {
+      launch_convert((const bf16*)m.img_embeds, d_f, per, C.stream);
+      FE_HIP(hipMemcpyAsync(embeds, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+    }
+    for (int k = 0; deepstack && k < nds; ++k) {
+      launch_convert((const bf16*)m.ds_feats + (size_t)k * m.ds_cap * m.hidden, d_f, per, C.stream);
+      FE_HIP(hipMemcpyAsync(deepstack + (size_t)k * per, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+    }
+  }
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END_CAPACITY(ctx)
+}
+int fe_vlm_vision_dims(fe_ctx* ctx, int* dims) {
+  FE_API_BEGIN(ctx)
+  const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;
+  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
+  FE_CHECK(dims, "bad arguments");
+  const VlmModel& m = *ctx->c.vlm;
+  if (q3) {
+    int side = 0;
+    while ((side + 1) * (side + 1) <= m.vis3.n_pos) ++side;
+    dims[0] = m.vis3.patch_side; dims[1] = m.vis3.patch_dim; dims[2] = (int)m.vis3.ds_blocks.size(); dims[3] = side * side == m.vis3.n_pos ? side : 0;
+  } else {
+    dims[0] = 14; dims[1] = m.vis.patch_dim; dims[2] = 0; dims[3] = 0;
+  }
   FE_API_END(ctx)
 }
 int fe_vlm_dims(fe_ctx* ctx, int* dims) {
@@ -1490,6 +1592,16 @@ static void vlm_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* position
     int* d_idx = (int*)C.arena.alloc((size_t)n_image_rows * sizeof(int));
     FE_HIP(hipMemcpyAsync(d_idx, image_rows, (size_t)n_image_rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
     vlm_put_rows(C, x, m.img_embeds, d_idx, n_image_rows, m.hidden);
+  }
+  // Qwen3-VL prefill: the DeepStack features of the last image encode go to the image rows after the first decoder layers (row -> slot map)
+  struct SlotReset { VlmModel& m; ~SlotReset() { m.ds_slot = nullptr; } } slot_reset{m};
+  std::vector<int> slot;      // (host source of the copy: alive until the synchronisation below)
+  if (prefill && m.cfg.qwen3 && n_image_rows > 0 && m.ds_n > 0) {
+    slot.assign((size_t)rows, -1);
+    for (int i = 0; i < n_image_rows; ++i) slot[image_rows[i]] = i;
+    int* d_slot = (int*)C.arena.alloc((size_t)rows * sizeof(int));
+    FE_HIP(hipMemcpyAsync(d_slot, slot.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
+    m.ds_slot = d_slot;
   }
   vlm_forward(C, m, x, d_pos, n_seq, len, d_next, d_logits);
   FE_HIP(hipMemcpyAsync(next_tokens, d_next, (size_t)n_seq * sizeof(int), hipMemcpyDeviceToHost, C.stream));

@@ -205,6 +205,9 @@ struct GraphSlot;
 struct VlmConfig {
   int n_heads = 28, n_kv_heads = 4, head_dim = 128; float rope_theta = 1e6f, rms_eps = 1e-6f; int mrope[3] = {16, 24, 24};
   int vis_heads = 16, fullatt[8] = {7, 15, 23, 31, 0, 0, 0, 0}, n_fullatt = 4;      // vision tower (Qwen2_5_VLVisionConfig)
+  // Qwen3-VL (fe_vlm3_configure): q|k|v without bias, q_norm / k_norm, interleaved M-RoPE, tied lm_head allowed, DeepStack features
+  // from after vision blocks deepstack[0 .. n_deepstack) added to the image rows after decoder layers 0 .. n_deepstack - 1
+  bool qwen3 = false; int deepstack[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_deepstack = 0;
 };
 
 struct OpTiming { std::string name; double flops; double bytes; float ms; };
@@ -348,7 +351,7 @@ void aesthetic_forward(Ctx& c, const AestheticModel& m, const float* feat, int B
 void l2_normalize(Ctx& c, const float* x, float* y, int rows, int d);
 
 // ---- VLM tagger text decoder (transformers Qwen2_5_VLForConditionalGeneration; reference models/vlm_tagger.py) - model_vlm.hip ----------
-struct VlmLayerW { ConvW qkv, o, gate, up, down; bf16* ln1 = nullptr; bf16* ln2 = nullptr; };
+struct VlmLayerW { ConvW qkv, o, gate, up, down; bf16* ln1 = nullptr; bf16* ln2 = nullptr; bf16* qn = nullptr; bf16* kn = nullptr; };
 struct VlmVisionBlockW { ConvW qkv, proj, gate, up, down; bf16* n1 = nullptr; bf16* n2 = nullptr; };
 struct VlmVisionW {      // model.visual.* (model_vlm_vision.hip)
   bool present = false;
@@ -357,6 +360,20 @@ struct VlmVisionW {      // model.visual.* (model_vlm_vision.hip)
   bf16* ln_q = nullptr; float* inv_freq = nullptr;
   int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0;
   std::vector<int> fullatt;
+};
+// Qwen3-VL vision tower (model_vlm3_vision.hip): LayerNorm blocks with biases, learned position table, DeepStack mergers
+struct Vlm3MergerW { float* ln_g = nullptr; float* ln_b = nullptr; ConvW fc1, fc2; };
+struct Vlm3VisionBlockW { ConvW qkv, proj, fc1, fc2; float* n1g = nullptr; float* n1b = nullptr; float* n2g = nullptr; float* n2b = nullptr; };
+struct Vlm3VisionW {
+  bool present = false;
+  ConvW patch;
+  float* pos_table = nullptr;      // [n_pos][hidden]: the bf16 table widened to fp32
+  std::vector<Vlm3VisionBlockW> blocks;
+  Vlm3MergerW merger;
+  std::vector<Vlm3MergerW> ds_mergers;
+  std::vector<int> ds_blocks;
+  float* inv_freq = nullptr;
+  int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0, patch_side = 0, n_pos = 0;
 };
 struct VlmModel {
   DeviceWeights dw;
@@ -375,12 +392,22 @@ struct VlmModel {
   int* pad = nullptr;
   // patch rows of the last fe_vlm_preprocess_rgb (device bf16 [pre_rows][patch_dim]), the input of fe_vlm_encode_preprocessed
   bf16* pre_pv = nullptr; int pre_rows = 0, pre_cap = 0;
+  // Qwen3-VL: the vision tower, the DeepStack features of the last fe_vlm3_encode_images (device bf16 [n_ds][ds_cap][hidden], rows as
+  // img_embeds), and the row -> image-row slot map of the prefill in flight (device int [rows], -1 for text rows; null outside a prefill)
+  Vlm3VisionW vis3;
+  bf16* ds_feats = nullptr; int ds_n = 0, ds_cap = 0;
+  const int* ds_slot = nullptr;
   void reserve_cache(int B, int max_seq);
   void release_cache();
-  ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); }
+  ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); if (ds_feats) (void)hipFree(ds_feats); }
 };
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg);
 void build_vlm_vision(VlmModel& m, const WeightStore& ws);
+void build_vlm3_vision(VlmModel& m, const WeightStore& ws);
+// Qwen3-VL tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, block-major order); interp_idx [N][4] /
+// interp_w [N][4] (bilinear taps into the position table); cu [n_seg + 1] (one segment per image). out [N/4][out_hidden], ds [n_ds][N/4][out_hidden]
+void vlm3_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* interp_idx, const float* interp_w,
+                         const int* cu, int n_seg, int max_seg, bf16* out, bf16* ds);
 // pv: fp32 patch rows, or (pv == nullptr) pv_bf16: the rows already in bf16 (fe_vlm_preprocess_rgb)
 void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* pos, const int* widx, const int* cu_win, int n_win, int max_win,
                         const int* cu_full, int n_full, int max_full, bf16* out, const bf16* pv_bf16 = nullptr);
@@ -388,6 +415,8 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
 // [oh/14 * ow/14][3*2*14*14] in the processor's (gh/2, gw/2, 2, 2, C, T, 14, 14) order, each value lut[c][u]; bf16 always, fp32 when
 // out_f32 is not null
 void vlm_patchify(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut, bf16* out_bf16, float* out_f32);
+// the same for 16-pixel patches (Qwen3-VL): oh, ow multiples of 32, rows [oh/16 * ow/16][3*2*16*16]
+void vlm_patchify16(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut, bf16* out_bf16, float* out_f32);
 // row kernels shared by the decoder and the vision tower (model_vlm.hip)
 void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps);
 void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n);

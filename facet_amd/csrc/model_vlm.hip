@@ -86,6 +86,49 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
   }
 }
 
+// Qwen3-VL form of vlm_rope_cache_kernel: q_norm / k_norm (RMSNorm over each head's 128 dims), then the INTERLEAVED multimodal rotary
+// embedding, then the KV-cache append - one pass over the fused q|k|v rows. One wave per (row, head); lane l owns dims l and l + 64 (the
+// rotate_half pair of frequency l).
+//   norm: the fp32 sum of squares over the wave, n = bf16(x * rsqrt(mean + eps)), y = bf16(w * n)   (Qwen3VLTextRMSNorm on a bf16 tensor)
+//   rope: frequency j takes the height position when j % 3 == 1 and j < 3 s1, the width position when j % 3 == 2 and j < 3 s2, the temporal
+//         one otherwise (apply_interleaved_mrope); cos / sin rounded to bf16, products and sum rounded as vlm_rope_cache_kernel does
+__global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, const bf16* __restrict__ qn,
+                                          const bf16* __restrict__ kn, bf16* __restrict__ q_out, bf16* __restrict__ kc, bf16* __restrict__ vc, int rows, int L, int nh,
+                                          int nkv, int s1, int s2, int start, int max_seq, const int* __restrict__ start_dev, float eps) {
+  if (start_dev) start = *start_dev;      // decode steps replayed from a captured graph: the cache length lives in device memory
+  const int lane = threadIdx.x & 63;
+  const int heads = nh + 2 * nkv;
+  const size_t total = (size_t)rows * heads;
+  const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+  const int j = lane;
+  const int comp = (j % 3 == 1 && j < 3 * s1) ? 1 : ((j % 3 == 2 && j < 3 * s2) ? 2 : 0);
+  const float fr = inv_freq[j];
+  for (size_t wv = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < total; wv += nwaves) {
+    const int hd = (int)(wv % heads), row = (int)(wv / heads);
+    const bf16* src = qkv + wv * 128;
+    const int b = row / L, t = row - b * L;
+    const bf16 r1 = src[lane], r2 = src[lane + 64];
+    if (hd >= nh + nkv) {      // V: plain copy into the cache (wave-uniform branch)
+      bf16* dst = vc + (((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t) * 128;
+      dst[lane] = r1; dst[lane + 64] = r2;
+      continue;
+    }
+    const float x1 = (float)r1, x2 = (float)r2;
+    float ss = x1 * x1 + x2 * x2;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    const float rs = rsqrtf(ss / 128.f + eps);
+    const bf16* w = hd < nh ? qn : kn;
+    const float y1 = (float)(bf16)((float)w[lane] * (float)(bf16)(x1 * rs)), y2 = (float)(bf16)((float)w[lane + 64] * (float)(bf16)(x2 * rs));
+    const float ang = (float)pos[(size_t)comp * rows + row] * fr;
+    const float c = (float)(bf16)cosf(ang), s = (float)(bf16)sinf(ang);
+    const bf16 o1 = (bf16)((float)(bf16)(y1 * c) + (float)(bf16)(-y2 * s));
+    const bf16 o2 = (bf16)((float)(bf16)(y2 * c) + (float)(bf16)(y1 * s));
+    bf16* dst = hd < nh ? q_out + ((size_t)row * nh + hd) * 128 : kc + (((size_t)b * nkv + (hd - nh)) * max_seq + start + t) * 128;
+    dst[lane] = o1; dst[lane + 64] = o2;
+  }
+}
+
 // h = bf16(bf16(silu(g)) * u)   (Qwen2MLP: act_fn(gate_proj(x)) * up_proj(x) on bf16 tensors)
 __global__ void vlm_silu_mul_kernel(const bf16* g, const bf16* __restrict__ u, bf16* h, size_t n4) {      // h may be g
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -487,8 +530,11 @@ static bool vlm_uses_gemm32(const ConvW& w, int M) {
 // Finishing passes of the decode GEMM fused with what follows them (a 32-sequence step was ~30 launches per layer of which the 5-us ones -
 // split sums, residual sums, norms, the gate product - were a quarter of the time). One workgroup per sequence row.
 //   x = bf16(x + bf16(sum_k part + bias)); n = RMSNorm(x) * w   (w == nullptr: the sum only)
+// DS (Qwen3-VL prefill, layers below n_deepstack): rows with slot[row] >= 0 (image tokens) also take x = bf16(x + ds[slot][:]) before the norm
+template <bool DS>
 __global__ __launch_bounds__(1024) void vlm_finish_add_rmsnorm_kernel(const float* __restrict__ part, int splits, int M, int d, const float* __restrict__ bias, bf16* __restrict__ x,
-                                                                     const bf16* __restrict__ w, bf16* __restrict__ n, float eps) {
+                                                                     const bf16* __restrict__ w, bf16* __restrict__ n, float eps, const int* __restrict__ slot,
+                                                                     const bf16* __restrict__ ds) {
   __shared__ float red[16];
   const int row = blockIdx.x, t = threadIdx.x;      // 1024 threads: with 256 a row of 25 splits was 100 dependent-latency loads per thread
   bf16* const xr = x + (size_t)row * d;
@@ -508,8 +554,15 @@ __global__ __launch_bounds__(1024) void vlm_finish_add_rmsnorm_kernel(const floa
     if (bias) { const float4 b4 = *reinterpret_cast<const float4*>(bias + i); sum.x += b4.x; sum.y += b4.y; sum.z += b4.z; sum.w += b4.w; }
     const float4 a = ld4(xr + i);
     // the projection's output is a bf16 tensor, and so is the residual stream
-    const float4 v = make_float4((float)(bf16)(a.x + (float)(bf16)sum.x), (float)(bf16)(a.y + (float)(bf16)sum.y), (float)(bf16)(a.z + (float)(bf16)sum.z),
-                                 (float)(bf16)(a.w + (float)(bf16)sum.w));
+    float4 v = make_float4((float)(bf16)(a.x + (float)(bf16)sum.x), (float)(bf16)(a.y + (float)(bf16)sum.y), (float)(bf16)(a.z + (float)(bf16)sum.z),
+                           (float)(bf16)(a.w + (float)(bf16)sum.w));
+    if constexpr (DS) {
+      const int sl = slot[row];
+      if (sl >= 0) {
+        const float4 e = ld4(ds + (size_t)sl * d + i);
+        v = make_float4((float)(bf16)(v.x + e.x), (float)(bf16)(v.y + e.y), (float)(bf16)(v.z + e.z), (float)(bf16)(v.w + e.w));
+      }
+    }
     st4(xr + i, v);
     ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
   }
@@ -567,17 +620,25 @@ __global__ void vlm_advance_kernel(const int* __restrict__ next, int* __restrict
 
 // x = bf16(x + y) and, in the same pass, n = RMSNorm(x) * w (w == nullptr: the sum only). One wave per row: a decode step is a chain of
 // ~12 launches per layer whose small ones cost their launch latency, so the residual sum rides with the norm that follows it.
-__global__ void vlm_add_rmsnorm_kernel(bf16* __restrict__ x, const bf16* __restrict__ y, const bf16* __restrict__ w, bf16* __restrict__ n, int rows, int d, float eps) {
+// (DS: the DeepStack sum of vlm_finish_add_rmsnorm_kernel)
+template <bool DS>
+__global__ void vlm_add_rmsnorm_kernel(bf16* __restrict__ x, const bf16* __restrict__ y, const bf16* __restrict__ w, bf16* __restrict__ n, int rows, int d, float eps,
+                                       const int* __restrict__ slot, const bf16* __restrict__ ds) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
   for (int row = wave; row < rows; row += nwaves) {
     bf16* xr = x + (size_t)row * d;
     const bf16* yr = y + (size_t)row * d;
     float ss = 0.f;
+    const int sl = DS ? slot[row] : -1;
     for (int i = lane * 4; i < d; i += 256) {
       const float4 a = ld4(xr + i), b = ld4(yr + i);
       // the sum is rounded to bf16 first (the residual stream is a bf16 tensor), and the norm reads the rounded value
-      const float4 v = make_float4((float)(bf16)(a.x + b.x), (float)(bf16)(a.y + b.y), (float)(bf16)(a.z + b.z), (float)(bf16)(a.w + b.w));
+      float4 v = make_float4((float)(bf16)(a.x + b.x), (float)(bf16)(a.y + b.y), (float)(bf16)(a.z + b.z), (float)(bf16)(a.w + b.w));
+      if (DS && sl >= 0) {
+        const float4 e = ld4(ds + (size_t)sl * d + i);
+        v = make_float4((float)(bf16)(v.x + e.x), (float)(bf16)(v.y + e.y), (float)(bf16)(v.z + e.z), (float)(bf16)(v.w + e.w));
+      }
       st4(xr + i, v);
       ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
     }
@@ -781,13 +842,40 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
   FE_CHECK(cfg.n_heads > 0 && cfg.n_kv_heads > 0 && cfg.n_heads % cfg.n_kv_heads == 0, "vlm: %d heads / %d kv heads", cfg.n_heads, cfg.n_kv_heads);
   FE_CHECK(cfg.mrope[0] + cfg.mrope[1] + cfg.mrope[2] == 64, "vlm: mrope sections must sum to head_dim / 2");
   FE_CHECK(m.hidden % 64 == 0, "vlm: hidden size %d must be a multiple of 64", m.hidden);
-  m.embed = upload_bf16(m.dw, E.data);
+  // Qwen3-VL checkpoints may tie lm_head to embed_tokens (no lm_head.weight): the packed lm_head rows then serve as the embedding table too
+  const bool tied = cfg.qwen3 && !ws.has("lm_head.weight");
+  if (!tied) m.embed = upload_bf16(m.dw, E.data);
   m.layers.clear();
   const int qd = cfg.n_heads * 128, kd = cfg.n_kv_heads * 128;
   for (int i = 0;; ++i) {
     const std::string L = P + "layers." + std::to_string(i);
     if (!ws.has(L + ".self_attn.q_proj.weight")) break;
     VlmLayerW w;
+    if (cfg.qwen3) {      // Qwen3-VL: q | k | v without bias, then q_norm / k_norm over each head's 128 dims
+      HostTensor W;
+      W.shape = {qd + 2 * kd, m.hidden};
+      for (const char* n : {"q_proj", "k_proj", "v_proj"}) {
+        FE_CHECK(!ws.has(L + ".self_attn." + n + ".bias"), "vlm (qwen3): layer %d %s carries a bias", i, n);
+        const HostTensor& a = ws.get(L + ".self_attn." + n + ".weight");
+        FE_CHECK((int)a.shape[1] == m.hidden, "vlm: %s input width", n);
+        W.data.insert(W.data.end(), a.data.begin(), a.data.end());
+      }
+      FE_CHECK((int64_t)W.data.size() == W.shape[0] * W.shape[1], "vlm: layer %d q/k/v shapes do not match %d heads / %d kv heads of 128", i, cfg.n_heads, cfg.n_kv_heads);
+      w.qkv = build_linear_rows(m.dw, W, nullptr, 0, qd + 2 * kd);
+      const HostTensor& qn = ws.get(L + ".self_attn.q_norm.weight");
+      const HostTensor& kn = ws.get(L + ".self_attn.k_norm.weight");
+      FE_CHECK(qn.numel() == 128 && kn.numel() == 128, "vlm (qwen3): layer %d q_norm / k_norm must have 128 weights", i);
+      w.qn = upload_bf16(m.dw, qn.data);
+      w.kn = upload_bf16(m.dw, kn.data);
+      w.o = build_linear(m.dw, ws, L + ".self_attn.o_proj", false);
+      w.gate = build_linear(m.dw, ws, L + ".mlp.gate_proj", false);
+      w.up = build_linear(m.dw, ws, L + ".mlp.up_proj", false);
+      w.down = build_linear(m.dw, ws, L + ".mlp.down_proj", false);
+      w.ln1 = upload_bf16(m.dw, ws.get(L + ".input_layernorm.weight").data);
+      w.ln2 = upload_bf16(m.dw, ws.get(L + ".post_attention_layernorm.weight").data);
+      m.layers.push_back(w);
+      continue;
+    }
     // q | k | v as ONE projection: rows concatenated, biases concatenated
     HostTensor W, Bv;
     W.shape = {qd + 2 * kd, m.hidden}; Bv.shape = {qd + 2 * kd};
@@ -810,13 +898,22 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
   }
   FE_CHECK(!m.layers.empty(), "vlm: no decoder layers found");
   m.norm = upload_bf16(m.dw, ws.get(P + "norm.weight").data);
-  m.lm_head = build_linear(m.dw, ws, "lm_head", false);
+  if (tied) {
+    m.lm_head = build_linear_rows(m.dw, E, nullptr, 0, m.vocab);
+    FE_CHECK(m.lm_head.wh && m.lm_head.hprec == PREC_BF16, "vlm: tied lm_head needs the bf16 form");
+    if (m.lm_head.KpH == m.hidden) m.embed = (bf16*)m.lm_head.wh;      // one device copy: rows [vocab][hidden], row-major
+    else m.embed = upload_bf16(m.dw, E.data);
+  } else {
+    m.lm_head = build_linear(m.dw, ws, "lm_head", false);
+  }
+  FE_CHECK(cfg.n_deepstack <= (int)m.layers.size(), "vlm: %d DeepStack levels for %zu decoder layers", cfg.n_deepstack, m.layers.size());
   m.inter = m.layers[0].gate.Cout;
   // inv_freq as Qwen2_5_VLRotaryEmbedding.compute_default_rope_parameters: 1 / base^(2i / dim), fp32
   std::vector<float> inv(64);
   for (int i = 0; i < 64; ++i) inv[i] = 1.0f / powf(cfg.rope_theta, (float)(2 * i) / 128.0f);
   m.inv_freq = m.dw.upload(inv);
-  build_vlm_vision(m, ws);      // model.visual.* when the checkpoint carries it
+  if (cfg.qwen3) build_vlm3_vision(m, ws);      // model.visual.* when the checkpoint carries it
+  else build_vlm_vision(m, ws);
 }
 
 void VlmModel::reserve_cache(int B, int max_seq_) {
@@ -889,12 +986,18 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   // with no split sums to take, the finishing pass is x = bf16(x + 0), n = RMSNorm(x) w)
   const bool few_rows = rows <= 64 && d % 4 == 0;
   if (few_rows)
-    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel, dim3(rows), dim3(1024), 0, c.stream, (const float*)nullptr, 0, rows, d, (const float*)nullptr, x, (const bf16*)m.layers[0].ln1, n, g.rms_eps);
+    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)nullptr, 0, rows, d, (const float*)nullptr, x, (const bf16*)m.layers[0].ln1, n, g.rms_eps,
+                       (const int*)nullptr, (const bf16*)nullptr);
   else
     hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, (const bf16*)x, d, (const bf16*)m.layers[0].ln1, n, d, rows, d, g.rms_eps);
   for (size_t li = 0; li < m.layers.size(); ++li) {
     const VlmLayerW& w = m.layers[li];
     vlm_linear(c, w.qkv, (const bf16*)n, d, rows, qkv, qkvd);
+    if (g.qwen3)
+      hipLaunchKernelGGL(vlm3_qk_rope_cache_kernel, dim3(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), dim3(256), 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq,
+                         (const bf16*)w.qn, (const bf16*)w.kn, qr, m.kcache[li], m.vcache[li], rows, L, nh, nkv, g.mrope[1], g.mrope[2], start, m.max_seq,
+                         L == 1 ? len_dev : (const int*)nullptr, g.rms_eps);
+    else
     hipLaunchKernelGGL(vlm_rope_cache_kernel, dim3(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), dim3(256), 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, qr,
                        m.kcache[li], m.vcache[li], rows, L, nh, nkv, g.mrope[0], g.mrope[1], start, m.max_seq, L == 1 ? len_dev : (const int*)nullptr);
     if (L == 1) {
@@ -920,6 +1023,8 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
     c.flops_accum += 4.0 * B * nh * (double)L * (start + (L + 1) * 0.5) * 128;
     c.flops_half += 4.0 * B * nh * (double)L * (start + (L + 1) * 0.5) * 128;
     const bf16* const next_ln = li + 1 < m.layers.size() ? (const bf16*)m.layers[li + 1].ln1 : (const bf16*)nullptr;
+    // DeepStack (Qwen3-VL prefill): the image rows of this layer's output take feature block li (the slot map is set for a prefill only)
+    const bf16* const ds = m.ds_slot && (int)li < m.ds_n ? (const bf16*)m.ds_feats + (size_t)li * m.ds_cap * d : (const bf16*)nullptr;
     // 5 .. 32 sequences: the split sums of the weight-streaming GEMM are taken by the pass that follows the projection (residual +
     // norm, SwiGLU product) instead of a finishing launch of their own
     const bool fused = d % 4 == 0 && m.inter % 4 == 0 && vlm_uses_gemm32(w.o, rows) && vlm_uses_gemm32(w.gate, rows) && vlm_uses_gemm32(w.up, rows) &&
@@ -928,24 +1033,30 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
       const size_t pm = c.arena.mark();
       float *po_ = nullptr, *pg = nullptr, *pu = nullptr, *pd = nullptr;
       int sp = vlm_gemm32_partials(c, w.o, (const bf16*)ao, qd, rows, &po_);
-      hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel, dim3(rows), dim3(1024), 0, c.stream, (const float*)po_, sp, rows, d, (const float*)nullptr, x, (const bf16*)w.ln2, n, g.rms_eps);
+      hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)po_, sp, rows, d, (const float*)nullptr, x, (const bf16*)w.ln2, n, g.rms_eps,
+                         (const int*)nullptr, (const bf16*)nullptr);
       const int sg = vlm_gemm32_partials(c, w.gate, (const bf16*)n, d, rows, &pg, &w.up, &pu);      // gate and up: one launch
       const size_t mn4 = (size_t)rows * m.inter / 4;
       hipLaunchKernelGGL(vlm_finish_silu_mul_kernel, dim3(grid_n(mn4)), dim3(256), 0, c.stream, (const float*)pg, (const float*)pu, sg, mn4, gg);
       sp = vlm_gemm32_partials(c, w.down, (const bf16*)gg, m.inter, rows, &pd);
-      hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel, dim3(rows), dim3(1024), 0, c.stream, (const float*)pd, sp, rows, d, (const float*)nullptr, x, next_ln, n, g.rms_eps);
+      if (ds) hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<true>, dim3(rows), dim3(1024), 0, c.stream, (const float*)pd, sp, rows, d, (const float*)nullptr, x, next_ln, n, g.rms_eps, m.ds_slot, ds);
+      else hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)pd, sp, rows, d, (const float*)nullptr, x, next_ln, n, g.rms_eps,
+                              (const int*)nullptr, (const bf16*)nullptr);
       FE_HIP(hipGetLastError());
       c.arena.rewind(pm);
       continue;
     }
     vlm_linear(c, w.o, (const bf16*)ao, qd, rows, br, d);
-    hipLaunchKernelGGL(vlm_add_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, (const bf16*)w.ln2, n, rows, d, g.rms_eps);
+    hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<false>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, (const bf16*)w.ln2, n, rows, d, g.rms_eps,
+                       (const int*)nullptr, (const bf16*)nullptr);
     vlm_linear(c, w.gate, (const bf16*)n, d, rows, gg, m.inter);
     vlm_linear(c, w.up, (const bf16*)n, d, rows, uu, m.inter);
     hipLaunchKernelGGL(vlm_silu_mul_kernel, dim3(grid_n((size_t)rows * m.inter / 4)), dim3(256), 0, c.stream, (const bf16*)gg, (const bf16*)uu, gg, (size_t)rows * m.inter / 4);
     vlm_linear(c, w.down, (const bf16*)gg, m.inter, rows, br, d);
     // x += down(...) and, in the same launch, the next layer's input norm (none after the last layer)
-    hipLaunchKernelGGL(vlm_add_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps);
+    if (ds) hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<true>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps, m.ds_slot, ds);
+    else hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<false>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps,
+                            (const int*)nullptr, (const bf16*)nullptr);
     FE_HIP(hipGetLastError());
   }
   // final norm + lm_head on the last position of every sequence
@@ -953,7 +1064,8 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   bf16* lastn = c.arena.array<bf16>((size_t)B * d);
   hipLaunchKernelGGL(vlm_last_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, c.stream, (const bf16*)x, last, B, L, d);
   if (B <= 64 && d % 4 == 0)
-    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel, dim3(B), dim3(1024), 0, c.stream, (const float*)nullptr, 0, B, d, (const float*)nullptr, last, (const bf16*)m.norm, lastn, g.rms_eps);
+    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(B), dim3(1024), 0, c.stream, (const float*)nullptr, 0, B, d, (const float*)nullptr, last, (const bf16*)m.norm, lastn, g.rms_eps,
+                       (const int*)nullptr, (const bf16*)nullptr);
   else
     hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)B * 64)), dim3(256), 0, c.stream, (const bf16*)last, d, (const bf16*)m.norm, lastn, d, B, d, g.rms_eps);
   float* lg = logits_dev ? logits_dev : c.arena.array<float>((size_t)B * m.vocab);

@@ -34,6 +34,22 @@ CHAT_TEMPLATE = ("<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n"
                  "<|im_start|>assistant\n")
 IMAGE_PAD = "<|image_pad|>"
 
+# Qwen3-VL (transformers Qwen3VLForConditionalGeneration; the reference's 8gb / 16gb profiles tag with qwen3-vl-2b)
+# [DEP-KNOWLEDGE: Qwen3-VL-2B-Instruct config.json - confirm against the checkpoint] decoder geometry for Engine.vlm3_configure
+QWEN3_VL_2B = dict(n_heads=16, n_kv_heads=8, head_dim=128, rope_theta=5e6, rms_eps=1e-6, mrope_section=(24, 20, 20), vis_heads=16,
+                   deepstack_indexes=(5, 11, 17))
+# [DEP-KNOWLEDGE: Qwen3-VL tokenizer] the same special-token ids as Qwen2.5-VL's
+QWEN3_VL_TOKENS = dict(QWEN2_5_VL_TOKENS)
+# [DEP-KNOWLEDGE: Qwen3-VL preprocessor_config] mean / std 0.5, 16-pixel patches merged 2 x 2 (smart_resize factor 32), shortest_edge
+# 65536 = min_pixels; the reference passes max_pixels = model_config.get('max_pixels', 512*28*28) to the processor (vlm_tagger.py:178-181)
+IMAGE_MEAN_QWEN3 = (0.5, 0.5, 0.5)
+IMAGE_STD_QWEN3 = (0.5, 0.5, 0.5)
+MIN_PIXELS_QWEN3, MAX_PIXELS_QWEN3 = 65536, 512 * 28 * 28
+# [DEP-KNOWLEDGE: Qwen3-VL chat template - parity unpinned like CHAT_TEMPLATE; no default system turn] apply_chat_template(messages =
+# [user: image, text], add_generation_prompt=True) restated
+CHAT_TEMPLATE_QWEN3 = ("<|im_start|>user\n<|vision_start|><|image_pad|><|vision_end|>{prompt}<|im_end|>\n"
+                       "<|im_start|>assistant\n")
+
 
 def smart_resize(height: int, width: int, factor: int = 28, min_pixels: int = MIN_PIXELS, max_pixels: int = MAX_PIXELS):
     """transformers.models.qwen2_vl.image_processing_qwen2_vl.smart_resize restated: both sides multiples of `factor`, the pixel count within
@@ -66,9 +82,10 @@ def to_rgb(image) -> np.ndarray:
     return np.asarray(image, dtype=np.uint8)
 
 
-def chat_text(prompt: str) -> str:
-    """The chat-formatted text of one photo + prompt (CHAT_TEMPLATE), one <|image_pad|> placeholder before expansion."""
-    return CHAT_TEMPLATE.format(prompt=prompt)
+def chat_text(prompt: str, family: str = "qwen2_5") -> str:
+    """The chat-formatted text of one photo + prompt (CHAT_TEMPLATE, or CHAT_TEMPLATE_QWEN3 for family "qwen3"), one <|image_pad|>
+    placeholder before expansion."""
+    return (CHAT_TEMPLATE_QWEN3 if family == "qwen3" else CHAT_TEMPLATE).format(prompt=prompt)
 
 
 def expand_image_pads(text: str, grids, merge_size: int = 2, image_pad: str = IMAGE_PAD) -> str:
@@ -134,6 +151,51 @@ def vision_indices(grid_thw, spatial_merge_size: int = 2, window_size: int = 112
             "cu_seqlens": np.asarray(cu_full, np.int32)}
 
 
+def vision_inputs_qwen3(grid_thw, num_grid_per_side: int, spatial_merge_size: int = 2):
+    """The index arrays of Qwen3-VL's vision tower for images of `grid_thw` [n_images, 3]: numpy restatement of transformers.vision_utils
+    get_vision_position_ids (rows / columns in 2x2-block-major order), get_vision_interpolation_indices_and_weights(mode="bilinear",
+    align_corners=True) into the num_grid_per_side^2 position table (fp32 arithmetic as torch's), and get_vision_cu_seqlens (one segment
+    per frame). Returns a dict for Engine.vlm3_encode_images: patch_pos_hw [n, 2] int32, interp_idx [n, 4] int64, interp_w [n, 4] float32,
+    cu_seqlens int32."""
+    grid = np.asarray(grid_thw, dtype=np.int64).reshape(-1, 3)
+    m, side = spatial_merge_size, int(num_grid_per_side)
+    f32 = np.float32
+    pos, idx, wts, cu = [], [], [], [0]
+    for t, h, w in grid:
+        t, h, w = int(t), int(h), int(w)
+        hh, ww = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        blk = lambda a: a.reshape(h // m, m, w // m, m).transpose(0, 2, 1, 3).reshape(-1)      # block-major over the m x m merge blocks
+        row, col = blk(hh), blk(ww)
+        pos.append(np.tile(np.stack([row, col], -1), (t, 1)))
+
+        def axis(index, size):
+            src = index.astype(f32) * f32(side - 1) / f32(max(size - 1, 1))
+            fl = np.floor(src)
+            taps = np.clip(fl.astype(np.int64)[:, None] + np.arange(2), 0, side - 1)
+            dist = np.abs((src[:, None] - fl[:, None]) - np.arange(2).astype(f32))
+            return taps, np.maximum(f32(1) - dist, f32(0)).astype(f32)
+
+        ht, hw_ = axis(row, h)
+        wt, ww_ = axis(col, w)
+        idx.append(np.tile((ht[:, :, None] * side + wt[:, None, :]).reshape(-1, 4), (t, 1)))
+        wts.append(np.tile((hw_[:, :, None] * ww_[:, None, :]).reshape(-1, 4).astype(f32), (t, 1)))
+        for _ in range(t):
+            cu.append(cu[-1] + h * w)
+    return {"patch_pos_hw": np.concatenate(pos, 0).astype(np.int32), "interp_idx": np.concatenate(idx, 0).astype(np.int64),
+            "interp_w": np.concatenate(wts, 0).astype(np.float32), "cu_seqlens": np.asarray(cu, np.int32)}
+
+
+def interleaved_mrope_components(mrope_section=(24, 20, 20), n_freq: int = 64):
+    """Which position component (0 temporal, 1 height, 2 width) each rotary frequency of Qwen3-VL's interleaved M-RoPE takes
+    (Qwen3VLTextRotaryEmbedding.apply_interleaved_mrope): j % 3 == 1 and j < 3 s_h -> height, j % 3 == 2 and j < 3 s_w -> width, else
+    temporal. The engine's rotary kernel applies the same rule."""
+    j = np.arange(n_freq)
+    out = np.zeros(n_freq, np.int32)
+    out[(j % 3 == 1) & (j < 3 * mrope_section[1])] = 1
+    out[(j % 3 == 2) & (j < 3 * mrope_section[2])] = 2
+    return out
+
+
 def rope_index(input_ids, grid_thw, image_token_id: int, spatial_merge_size: int = 2, attention_mask=None):
     """M-RoPE position ids [3, n_seq, len] of prompts with image placeholders: numpy restatement of Qwen2_5_VLModel.get_rope_index for
     still images (what the reference's processor + generate compute): text tokens count up on all three axes; a run of <|image_pad|>
@@ -193,7 +255,6 @@ class VLMTagger:
 
     def __init__(self, model_config: Dict[str, Any], scoring_config=None, engine=None, decode=None, encode=None, special_tokens=None):
         self.model_config = model_config
-        self.tokens = dict(QWEN2_5_VL_TOKENS, **(special_tokens or {}))
         self.scoring_config = scoring_config
         self.engine = engine
         self.decode, self.encode = decode, encode
@@ -201,6 +262,7 @@ class VLMTagger:
         self.device = "cuda"
         path = model_config.get("model_path", "")
         self.family = "qwen3" if ("Qwen3" in path or "qwen3" in path) else "qwen2_5"
+        self.tokens = dict(QWEN3_VL_TOKENS if self.family == "qwen3" else QWEN2_5_VL_TOKENS, **(special_tokens or {}))
         self.batch_size = model_config.get("vlm_batch_size", 4 if self.family == "qwen3" else 2)
         self.valid_tags = set(scoring_config.get_tag_vocabulary().keys()) if scoring_config else set()
         self._prompt = None
@@ -211,11 +273,14 @@ class VLMTagger:
         arguments (default Qwen2.5-VL-7B-Instruct)."""
         if self.model is not None:
             return
-        if self.family != "qwen2_5":
-            raise NotImplementedError("the engine's decoder is Qwen2.5-VL's (Qwen3-VL: not built)")
         if state_dict is None:
             raise FileNotFoundError("no checkpoint: pass the model's state dict (the reference downloads it with from_pretrained, "
                                     "models/vlm_tagger.py:170-176; there is no network here)")
+        if self.family == "qwen3":      # Qwen3VLForConditionalGeneration: geometry = Engine.vlm3_configure's arguments (default Qwen3-VL-2B)
+            self.engine.vlm3_configure(**dict(geometry or QWEN3_VL_2B))
+            self.engine.load_weights(FE_MODEL_VLM, state_dict)
+            self.model = self.engine
+            return
         geometry = dict(geometry or QWEN2_5_VL_7B)
         vis = {k: geometry.pop(k) for k in ("vis_heads", "fullatt_block_indexes") if k in geometry}
         self.engine.vlm_configure(**geometry)
@@ -292,10 +357,13 @@ class VLMTagger:
         if self.encode is None:
             raise RuntimeError("no tokenizer: pass encode= (the checkpoint's processor.tokenizer.encode)")
         rgb = [to_rgb(im) for im in images]
-        lo, hi = int(self.model_config.get("min_pixels", MIN_PIXELS)), int(self.model_config.get("max_pixels", MAX_PIXELS))
-        sizes = [smart_resize(a.shape[0], a.shape[1], 28, lo, hi) for a in rgb]
-        grid = np.array([[1, oh // 14, ow // 14] for oh, ow in sizes], np.int64)
-        text = chat_text(self._build_prompt() if prompt is None else prompt)
+        q3 = self.family == "qwen3"
+        lo = int(self.model_config.get("min_pixels", MIN_PIXELS_QWEN3 if q3 else MIN_PIXELS))
+        hi = int(self.model_config.get("max_pixels", MAX_PIXELS_QWEN3 if q3 else MAX_PIXELS))
+        patch = 16 if q3 else 14
+        sizes = [smart_resize(a.shape[0], a.shape[1], 2 * patch, lo, hi) for a in rgb]
+        grid = np.array([[1, oh // patch, ow // patch] for oh, ow in sizes], np.int64)
+        text = chat_text(self._build_prompt() if prompt is None else prompt, self.family)
         rows = [list(self.encode(expand_image_pads(text, g[None]))) for g in grid]
         ids, am = left_pad(rows, self.tokens["pad_token_id"])
         img = self.tokens["image_token_id"]
@@ -309,9 +377,17 @@ class VLMTagger:
         if self.model is None:
             raise RuntimeError("VLMTagger.load() first")
         x = self.prepare_inputs(images, prompt)
-        self.engine.vlm_preprocess_rgb(x["rgb"], x["sizes"], IMAGE_MEAN, IMAGE_STD)
-        idx = vision_indices(x["grid_thw"])
-        self.engine.vlm_encode_preprocessed(idx["patch_pos_hw"], idx["window_index"], idx["cu_window_seqlens"], idx["cu_seqlens"], want_embeds=False)
+        if self.family == "qwen3":
+            self.engine.vlm_preprocess_rgb(x["rgb"], x["sizes"], IMAGE_MEAN_QWEN3, IMAGE_STD_QWEN3)
+            side = self.engine.vlm_vision_dims()["pos_side"]
+            if side <= 0:
+                raise ValueError("the committed tower's position table is not a square grid")
+            v = vision_inputs_qwen3(x["grid_thw"], side)
+            self.engine.vlm3_encode_images(None, v["patch_pos_hw"], v["interp_idx"], v["interp_w"], v["cu_seqlens"], want_embeds=False)
+        else:
+            self.engine.vlm_preprocess_rgb(x["rgb"], x["sizes"], IMAGE_MEAN, IMAGE_STD)
+            idx = vision_indices(x["grid_thw"])
+            self.engine.vlm_encode_preprocessed(idx["patch_pos_hw"], idx["window_index"], idx["cu_window_seqlens"], idx["cu_seqlens"], want_embeds=False)
         n_new = int(max_new_tokens or self.model_config.get("max_new_tokens", 100))
         return self.engine.vlm_generate(x["input_ids"], n_new, position_ids=x["position_ids"], eos_token_ids=self.tokens["eos_token_ids"],
                                         image_rows=x["image_rows"], attention_mask=x["attention_mask"])

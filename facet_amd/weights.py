@@ -264,6 +264,61 @@ def qwen2_5_vl_vision_spec(hidden=1280, depth=32, inter=3420, out_hidden=3584, p
     return spec
 
 
+def qwen3_vl_text_spec(hidden=2048, layers=28, heads=16, kv_heads=8, inter=6144, vocab=151936, tied=True):
+    """Text decoder of transformers' Qwen3VLForConditionalGeneration (model.language_model.*): q / k / v WITHOUT bias, q_norm / k_norm
+    over each head's 128 dims, SwiGLU MLP; lm_head tied to embed_tokens (no lm_head.weight) unless tied=False. Defaults = Qwen3-VL-2B."""
+    hd = 128
+    # (a tied table is also the read-out: 1 / sqrt(hidden) scale keeps its logits O(1); an untied one is unit scale as Qwen2.5-VL's)
+    spec = [("model.language_model.embed_tokens.weight", (vocab, hidden), "linear" if tied else "emb1")]
+    for i in range(layers):
+        p = f"model.language_model.layers.{i}"
+        _linear(spec, p + ".self_attn.q_proj", heads * hd, hidden, bias=False)
+        _linear(spec, p + ".self_attn.k_proj", kv_heads * hd, hidden, bias=False)
+        _linear(spec, p + ".self_attn.v_proj", kv_heads * hd, hidden, bias=False)
+        _linear(spec, p + ".self_attn.o_proj", hidden, heads * hd, bias=False)
+        spec.append((p + ".self_attn.q_norm.weight", (hd,), "ln_w"))
+        spec.append((p + ".self_attn.k_norm.weight", (hd,), "ln_w"))
+        _linear(spec, p + ".mlp.gate_proj", inter, hidden, bias=False)
+        _linear(spec, p + ".mlp.up_proj", inter, hidden, bias=False)
+        _linear(spec, p + ".mlp.down_proj", hidden, inter, bias=False)
+        spec.append((p + ".input_layernorm.weight", (hidden,), "ln_w"))
+        spec.append((p + ".post_attention_layernorm.weight", (hidden,), "ln_w"))
+    spec.append(("model.language_model.norm.weight", (hidden,), "ln_w"))
+    if not tied:
+        spec.append(("lm_head.weight", (vocab, hidden), "linear"))
+    return spec
+
+
+def qwen3_vl_vision_spec(hidden=1024, depth=24, inter=4096, out_hidden=2048, patch=16, temporal=2, n_pos=2304, n_deepstack=3):
+    """Vision tower of Qwen3VLForConditionalGeneration (`model.visual.*`): Conv3d patch embedding with bias, learned position table, `depth`
+    blocks of LayerNorm (+bias) - fused qkv (+bias) - proj (+bias) - LayerNorm - fc1 / fc2 (+biases, tanh GELU), the final merger
+    (LayerNorm over hidden) and n_deepstack DeepStack mergers (LayerNorm over 4 hidden). Defaults = Qwen3-VL-2B (16 heads of 64)."""
+    v = "model.visual."
+    spec = [(v + "patch_embed.proj.weight", (hidden, 3, temporal, patch, patch), "linear_nd"), (v + "patch_embed.proj.bias", (hidden,), "bias"),
+            (v + "pos_embed.weight", (n_pos, hidden), "emb1")]
+    for i in range(depth):
+        b = f"{v}blocks.{i}"
+        for n in ("norm1", "norm2"):
+            spec.append((f"{b}.{n}.weight", (hidden,), "ln_w"))
+            spec.append((f"{b}.{n}.bias", (hidden,), "ln_b"))
+        _linear(spec, b + ".attn.qkv", 3 * hidden, hidden)
+        _linear(spec, b + ".attn.proj", hidden, hidden)
+        _linear(spec, b + ".mlp.linear_fc1", inter, hidden)
+        _linear(spec, b + ".mlp.linear_fc2", hidden, inter)
+    for name, width in [("merger", hidden)] + [(f"deepstack_merger_list.{k}", 4 * hidden) for k in range(n_deepstack)]:
+        spec.append((f"{v}{name}.norm.weight", (width,), "ln_w"))
+        spec.append((f"{v}{name}.norm.bias", (width,), "ln_b"))
+        _linear(spec, f"{v}{name}.linear_fc1", 4 * hidden, 4 * hidden)
+        _linear(spec, f"{v}{name}.linear_fc2", out_hidden, 4 * hidden)
+    return spec
+
+
+# the reduced Qwen3-VL of the parity tests (tests/golden/make_vlm3_golden.py): head_dim 128 with 2:1 grouped KV heads in the decoder,
+# head_dim 64 in the tower, an 8 x 8 position table, DeepStack after three non-contiguous blocks including the last
+VLM3_TINY = dict(hidden=256, layers=4, heads=4, kv_heads=2, inter=512, vocab=2048)
+VLM3_VISION_TINY = dict(hidden=128, depth=4, inter=256, out_hidden=256, n_pos=64, n_deepstack=3)
+VLM3_TINY_DEEPSTACK = (0, 2, 3)
+
 # reduced vision tower of the parity tests: Qwen2.5-VL's head_dim 80, window attention with one full-attention block
 VLM_VISION_TINY = dict(hidden=160, depth=3, inter=320, out_hidden=512)
 
@@ -275,6 +330,10 @@ SPECS = {
     "qwen2_5_vl_text": qwen2_5_vl_text_spec,
     "qwen2_5_vl_text_tiny": lambda: qwen2_5_vl_text_spec(**VLM_TINY),
     "qwen2_5_vl_tiny": lambda: qwen2_5_vl_text_spec(**VLM_TINY) + qwen2_5_vl_vision_spec(**VLM_VISION_TINY),
+    "qwen3_vl_text": qwen3_vl_text_spec,
+    "qwen3_vl_2b": lambda: qwen3_vl_text_spec() + qwen3_vl_vision_spec(),
+    "qwen3_vl_tiny": lambda: qwen3_vl_text_spec(**VLM3_TINY) + qwen3_vl_vision_spec(**VLM3_VISION_TINY),
+    "qwen3_vl_tiny_untied": lambda: qwen3_vl_text_spec(**VLM3_TINY, tied=False) + qwen3_vl_vision_spec(**VLM3_VISION_TINY),
     "topiq": topiq_spec,
     "resnet50": lambda: resnet_spec("semantic_model.", True, [3, 4, 6, 3]),
     "clip": clip_vit_spec,

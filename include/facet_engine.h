@@ -35,7 +35,7 @@ enum fe_status {
   FE_ERR_RUNTIME = -2,   /* HIP failure or internal check */
   FE_ERR_NOT_LOADED = -3, /* model weights not committed */
   FE_ERR_CAPACITY = -4   /* the batch does not fit (device memory, arena, KV cache): returned by fe_vlm_preprocess_rgb,
-                            fe_vlm_encode_preprocessed and fe_vlm_prefill_images_padded only - retry with fewer images */
+                            fe_vlm_encode_preprocessed, fe_vlm3_encode_images and fe_vlm_prefill_images_padded only - retry with fewer images */
 };
 
 /* Model slots (reference names: models/model_manager.py:393-437 'topiq','clip','samp_net',...). */
@@ -137,6 +137,28 @@ int fe_vlm_encode_preprocessed(fe_ctx* ctx, const int32_t* patch_pos_hw, const i
                                const int32_t* cu_seqlens, int n_images, float* embeds);
 int fe_vlm_prefill_images_padded(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int len, int max_seq, const int32_t* pad,
                                  const int32_t* image_rows, int n_image_rows, int32_t* next_tokens, float* logits);
+
+/* Qwen3-VL (transformers Qwen3VLForConditionalGeneration, the 8gb / 16gb profiles' qwen3-vl-2b): fe_vlm3_configure makes the NEXT
+ * fe_weights_commit(FE_MODEL_VLM) build that family: q / k / v without bias, q_norm / k_norm (RMSNorm over each head's 128 dims before the
+ * rotary embedding), interleaved M-RoPE over mrope_section (24 / 20 / 20 at 2B), lm_head tied to embed_tokens when the checkpoint has no
+ * lm_head.weight; vision tower of vis_heads heads of 64 with LayerNorm blocks, a learned position table and DeepStack mergers after the
+ * blocks deepstack_indexes[0 .. n_deepstack) (5 / 11 / 17 at 2B). A later fe_vlm_configure selects Qwen2.5-VL again.
+ * fe_vlm3_encode_images = `model.visual(pixel_values, grid_thw)` of that class: pixel_values [n_patches][1536] (3 x 2 x 16 x 16 patches,
+ * fp32) or NULL = the bf16 rows of the last fe_vlm_preprocess_rgb (which patchifies 16-pixel patches, sides multiples of 32, for this
+ * family); patch_pos_hw [n_patches][2] = (row, column) of every patch in the processor's 2x2-block-major order; interp_idx / interp_w
+ * [n_patches][4] = the bilinear taps (int32 rows of the position table, fp32 weights) of
+ * get_vision_interpolation_indices_and_weights(align_corners=True); cu_seqlens [n_seg + 1] = one segment per image. The merged
+ * embeddings [n_patches / 4][hidden] and the n_deepstack feature blocks of the same shape stay on the device for the next
+ * fe_vlm_prefill_images(_padded), which puts the embeddings into the image rows and adds feature block i to them after decoder layer i
+ * (decode steps never do); they are also copied to `embeds` / `deepstack` [n_deepstack][n_patches / 4][hidden] when those are not NULL.
+ * Returns FE_ERR_CAPACITY when the batch does not fit.
+ * fe_vlm_vision_dims (either family): dims4 = patch side (14 / 16), patch row width (1176 / 1536), DeepStack levels (0 for Qwen2.5-VL),
+ * side of the square position table (0 for Qwen2.5-VL) of the committed tower - what sizes the pixel_values / deepstack outputs above. */
+int fe_vlm_vision_dims(fe_ctx* ctx, int* dims4);
+int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads,
+                      const int* deepstack_indexes, int n_deepstack);
+int fe_vlm3_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* interp_idx, const float* interp_w,
+                          const int32_t* cu_seqlens, int n_seg, float* embeds, float* deepstack);
 
 /* ---- device buffers (so callers can keep batches resident in HBM without torch) ------------- */
 int fe_dev_alloc(fe_ctx* ctx, size_t bytes, void** d_out);

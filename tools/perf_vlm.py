@@ -1,6 +1,12 @@
 """Throughput of the VLM tagger's text decoder at Qwen2.5-VL-7B's geometry (BASELINE configs[4] shape; slice 1 = decoder only).
 
   python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32] [--vision N] [--from-rgb N] [--pad P]
+  python tools/perf_vlm.py --family qwen3 [--prompt 512] [--new 32] [--batches 1,4,32] [--vision N]
+
+--family qwen3: Qwen3-VL-2B at full depth (28 decoder layers of hidden 2048, 16 / 8 heads of 128, intermediate 6144, tied vocab 151936;
+tower of 24 blocks of 1024, 16 heads of 64, DeepStack after 5 / 11 / 17), ~4 GB of seeded synthetic weights, no extrapolation: prefill
+tokens/s, decode ms/step and the fraction of HBM peak of the weight stream, the Qwen2.5-VL decoder at --qwen25-layers layers at batch 4 in
+the same run for comparison, and the vision tower's images/s at the max_pixels grid (480 x 768 -> 30 x 48 patches) with inputs resident.
 
 --from-rgb N times the vision tower from N uint8 photos (GPU preprocessing: fe_vlm_preprocess_rgb + fe_vlm_encode_preprocessed) against
 the same photos' fp32 pixel_values uploaded by fe_vlm_encode_images; --pad P also times the decode steps of a left-padded batch (every
@@ -26,7 +32,77 @@ ap.add_argument("--batches", default="1,8,32")
 ap.add_argument("--vision", type=int, default=0, help="also time the vision tower: this many images of 1036x1036 pixels (74x74 patches) per call, full depth 32")
 ap.add_argument("--from-rgb", type=int, default=0, help="time vision encode from this many uint8 1036x1036 photos against the fp32 pixel_values upload")
 ap.add_argument("--pad", type=int, default=0, help="also time decode steps with every other sequence left-padded by this many tokens")
+ap.add_argument("--family", default="qwen2_5", choices=("qwen2_5", "qwen3"))
+ap.add_argument("--qwen25-layers", type=int, default=4, help="--family qwen3: layers of the Qwen2.5-VL-7B decoder timed at batch 4 for comparison")
 a = ap.parse_args()
+
+
+def decode_rate(e, B, L, new, V):
+    """(prefill ms, decode ms/step through fe_vlm_decode_step, device-resident ms/step through fe_vlm_generate) of B random prompts of L."""
+    p = np.random.default_rng(B).integers(0, V, (B, L)).astype(np.int32)
+    e.vlm_prefill(p, max_seq=L + new + 8)
+    e.timer_start(); nxt = e.vlm_prefill(p, max_seq=L + new + 8); t_pre = e.timer_stop()
+    pos = np.full((3, B), L, np.int32)
+    e.vlm_decode_step(nxt, pos)
+    t0 = time.perf_counter()
+    for s in range(new):
+        nxt = e.vlm_decode_step(nxt, pos + 1 + s)
+    t_dec = (time.perf_counter() - t0) / new * 1e3
+    e.vlm_prefill(p, max_seq=L + new + 8)
+    t0 = time.perf_counter(); e.vlm_generate(p, new + 1); t_all = (time.perf_counter() - t0) * 1e3
+    return t_pre, t_dec, (t_all - t_pre) / new
+
+
+if a.family == "qwen3":
+    from facet_amd.weights import qwen3_vl_text_spec, qwen3_vl_vision_spec
+    from facet_amd.vlm_tagger import QWEN3_VL_2B, vision_inputs_qwen3
+    H, NH, NKV, INTER, V, NL = 2048, 16, 8, 6144, 151936, 28
+    t0 = time.time()
+    spec = qwen3_vl_text_spec(hidden=H, layers=NL, heads=NH, kv_heads=NKV, inter=INTER, vocab=V) + (qwen3_vl_vision_spec() if a.vision else [])
+    sd = synthetic_state_dict(None, 3, spec=spec)
+    print(f"weights drawn in {time.time() - t0:.0f} s ({sum(v.size for v in sd.values()) / 1e9:.2f} G parameters)", flush=True)
+    e = Engine(0, arena_bytes=40 << 30)
+    e.vlm3_configure(**QWEN3_VL_2B)
+    t0 = time.time(); e.load_weights(FE_MODEL_VLM, sd); del sd
+    print(f"committed in {time.time() - t0:.0f} s", flush=True)
+    if a.vision:
+        g = [[1, 30, 48]] * a.vision                     # smart_resize(900, 1400, 32, 65536, 512*28*28) = 480 x 768
+        v = vision_inputs_qwen3(g, 48)
+        n = 30 * 48 * a.vision
+        pv = np.random.default_rng(0).normal(0, 1, (n, 1536)).astype(np.float32)
+        args = (v["patch_pos_hw"], v["interp_idx"], v["interp_w"], v["cu_seqlens"])
+        e.vlm3_encode_images(pv, *args, want_embeds=False)
+        # inputs resident: the bf16 rows of a preprocess stay on the device (pixel_values=None)
+        rgb = [np.random.default_rng(i).integers(0, 256, (480, 768, 3), dtype=np.uint8) for i in range(a.vision)]
+        e.vlm_preprocess_rgb(rgb, [(480, 768)] * a.vision, (0.5,) * 3, (0.5,) * 3)
+        e.vlm3_encode_images(None, *args, want_embeds=False)
+        e.flops_reset(); e.timer_start()
+        e.vlm3_encode_images(None, *args, want_embeds=False)
+        ms = e.timer_stop()
+        print(f"vision tower (qwen3, 24 blocks): {a.vision} images of 30x48 patches (360 image tokens each), rows resident: {ms:.2f} ms = "
+              f"{a.vision / ms * 1e3:.1f} images/s, {e.flops() / ms / 1e9:.1f} TFLOP/s (projections)", flush=True)
+    layer_params = H * (NH + 2 * NKV) * 128 + NH * 128 * H + 3 * H * INTER
+    wbytes = 2.0 * (NL * layer_params + V * H)
+    for B in [int(b) for b in a.batches.split(",")]:
+        L = a.prompt
+        t_pre, t_dec, t_loop = decode_rate(e, B, L, a.new, V)
+        print(f"qwen3 B={B:3d} L={L}: prefill {t_pre:8.2f} ms = {B * L / t_pre * 1e3:9.0f} tok/s | decode {t_dec:6.3f} ms/step = "
+              f"{wbytes / t_dec / 1e6 / 8000:.2f} of HBM peak | device-resident loop {t_loop:6.3f} ms/step = {wbytes / t_loop / 1e6:6.0f} GB/s = "
+              f"{wbytes / t_loop / 1e6 / 8000:.2f} of peak ({NL} layers, {wbytes / 1e9:.2f} GB of weights per step)", flush=True)
+    e.close()
+    if a.qwen25_layers > 0:      # the Qwen2.5-VL-7B decoder at batch 4 in the same process, for the HBM-fraction comparison
+        H2, NH2, NKV2, I2, V2 = 3584, 28, 4, 18944, 152064
+        sd = synthetic_state_dict(None, 3, spec=qwen2_5_vl_text_spec(hidden=H2, layers=a.qwen25_layers, heads=NH2, kv_heads=NKV2, inter=I2, vocab=V2))
+        e = Engine(0, arena_bytes=40 << 30)
+        e.vlm_configure(NH2, NKV2, 128, 1e6, 1e-6, (16, 24, 24))
+        e.load_weights(FE_MODEL_VLM, sd); del sd
+        lp2 = H2 * (NH2 + 2 * NKV2) * 128 + NH2 * 128 * H2 + 3 * H2 * I2
+        wb2 = 2.0 * (a.qwen25_layers * lp2 + V2 * H2)
+        t_pre, t_dec, t_loop = decode_rate(e, 4, a.prompt, a.new, V2)
+        print(f"qwen2.5-7B ({a.qwen25_layers} layers) B=  4: decode {t_dec:6.3f} ms/step = {wb2 / t_dec / 1e6 / 8000:.2f} of HBM peak | device-resident loop "
+              f"{t_loop:6.3f} ms/step = {wb2 / t_loop / 1e6 / 8000:.2f} of peak", flush=True)
+        e.close()
+    sys.exit(0)
 H, NH, NKV, INTER, V = 3584, 28, 4, 18944, 152064
 t0 = time.time()
 from facet_amd.weights import qwen2_5_vl_vision_spec
