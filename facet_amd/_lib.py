@@ -92,6 +92,7 @@ SIGNATURES = {
     "fe_op_adaptive_avgpool": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _f32p]),
     "fe_op_layernorm": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_float, _f32p]),
+    "fe_op_vlm_select": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
     "fe_topiq_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -120,6 +121,8 @@ SIGNATURES = {
     "fe_vlm_prefill_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_generate": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "fe_vlm_generate_scored": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
+    "fe_vlm_last_logprobs": (C.c_int, [C.c_void_p, _f32p]),
     "fe_vlm_preprocess_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), _f32p, _f32p, _f32p]),
     "fe_vlm_encode_preprocessed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                              C.POINTER(C.c_int32), C.c_int, _f32p]),
@@ -743,14 +746,34 @@ class Engine:
         self._ck(self.lib.fe_vlm_decode_step(self.h, tp, pp, n, nxt.ctypes.data_as(C.POINTER(C.c_int32)), lg.ctypes.data_as(_f32p) if want_logits else None))
         return (nxt, lg) if want_logits else nxt
 
+    def _vlm_last_logprobs(self, n_seq):
+        """Log-probabilities [n_seq] of the tokens chosen by the most recent prefill, decode step or generate step (fe_vlm_last_logprobs;
+        n_seq: the sequence count of that prefill)."""
+        out = np.empty(int(n_seq), np.float32)
+        self._ck(self.lib.fe_vlm_last_logprobs(self.h, out.ctypes.data_as(_f32p)))
+        return out
+
+    def select(self, logits):
+        """The decoder's greedy selection on caller logits (fe_op_vlm_select): float [rows, vocab], rounded to bf16 first ->
+        (ids int32 [rows], log-probabilities float32 [rows] of those ids)."""
+        lg, lgp = _f32(logits)
+        rows, vocab = lg.shape
+        ids = np.empty(rows, np.int32)
+        lp = np.empty(rows, np.float32)
+        self._ck(self.lib.fe_op_vlm_select(self.h, lgp, rows, vocab, ids.ctypes.data_as(C.POINTER(C.c_int32)), lp.ctypes.data_as(_f32p)))
+        return ids, lp
+
     def vlm_generate(self, tokens, max_new_tokens, position_ids=None, eos_token_ids=(), want_logits=False, forced_tokens=None, image_rows=None,
-                     attention_mask=None):
+                     attention_mask=None, return_logprobs=False):
         """Greedy generation (`generate(..., do_sample=False)`, models/vlm_tagger.py:255-259): prefill + max_new_tokens - 1 decode
         steps for all sequences in lockstep; a sequence that emitted an EOS id keeps receiving that id (what generate's padding does).
         New positions continue from max(position_ids) + 1 per sequence. forced_tokens [n_seq, max_new_tokens]: teacher forcing - the
         token FED at each step is taken from there instead of the engine's own choice (parity tests).
         attention_mask int [n_seq, len]: a LEFT-padded batch (zeros, then ones, per row; position_ids must then be given, e.g.
-        vlm_tagger.rope_index(..., attention_mask=...)). None: every position is real (the unpadded path, unchanged)."""
+        vlm_tagger.rope_index(..., attention_mask=...)). None: every position is real (the unpadded path, unchanged).
+        return_logprobs: also the log-probability of every chosen token, float32 [n_seq, max_new_tokens] (log_softmax of the step's bf16
+        logits at that id, as `generate(..., output_scores=True)` gives it); steps after a row's first EOS are NaN (not generated). Returns
+        (ids, logprobs), or (ids, logits, logprobs) with want_logits. The ids are the same with or without it."""
         tok = np.ascontiguousarray(tokens, dtype=np.int32)
         n, L = tok.shape
         pad = None
@@ -768,28 +791,43 @@ class Engine:
             first = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), image_rows=image_rows, pad=pad)
             out = np.empty((n, max_new_tokens), np.int32)
             out[:, 0] = first
+            lps = np.empty((n, max_new_tokens), np.float32) if return_logprobs else None
+            if return_logprobs:
+                lps[:, 0] = self._vlm_last_logprobs(n)
             if max_new_tokens > 1:
                 ft, fp = self._i32(first)
                 ps, pp = self._i32(np.broadcast_to(nxt_pos.astype(np.int32), (3, n)))
                 steps = np.empty((max_new_tokens - 1, n), np.int32)
-                self._ck(self.lib.fe_vlm_generate(self.h, fp, pp, n, max_new_tokens - 1, steps.ctypes.data_as(C.POINTER(C.c_int32))))
+                if return_logprobs:      # the same device loop, each step's log-probs beside its ids (fe_vlm_generate_scored)
+                    slp = np.empty((max_new_tokens - 1, n), np.float32)
+                    self._ck(self.lib.fe_vlm_generate_scored(self.h, fp, pp, n, max_new_tokens - 1, steps.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                             slp.ctypes.data_as(_f32p)))
+                    lps[:, 1:] = slp.T
+                else:
+                    self._ck(self.lib.fe_vlm_generate(self.h, fp, pp, n, max_new_tokens - 1, steps.ctypes.data_as(C.POINTER(C.c_int32))))
                 out[:, 1:] = steps.T
             eos = [int(e) for e in eos_token_ids]
             for b in range(n if eos else 0):      # generate() pads a finished sequence with its EOS id
                 hit = np.flatnonzero(np.isin(out[b], eos))
                 if hit.size:
                     out[b, hit[0]:] = out[b, hit[0]]
-            return out
+                    if return_logprobs:
+                        lps[b, hit[0] + 1:] = np.nan
+            return (out, lps) if return_logprobs else out
         out = np.zeros((n, max_new_tokens), np.int32)
+        lps = np.full((n, max_new_tokens), np.nan, np.float32) if return_logprobs else None
         logits = []
         r = self.vlm_prefill(tok, position_ids, max_seq=min(8192, L + max_new_tokens), want_logits=want_logits, image_rows=image_rows, pad=pad)
         cur = r[0] if want_logits else r
+        cur_lp = self._vlm_last_logprobs(n) if return_logprobs else None
         done = np.zeros(n, bool)
         eos = set(int(e) for e in eos_token_ids)
         for step in range(max_new_tokens):
             if want_logits:
                 logits.append(r[1])
             out[:, step] = cur
+            if return_logprobs:
+                lps[:, step] = cur_lp
             done |= np.isin(cur, list(eos)) if eos else False
             if step + 1 == max_new_tokens or done.all():
                 out[:, step + 1:] = cur[:, None] if done.all() else 0
@@ -799,6 +837,10 @@ class Engine:
             nxt_pos = nxt_pos + 1
             new = r[0] if want_logits else r
             cur = np.where(done, cur, new)
+            if return_logprobs:
+                cur_lp = np.where(done, np.float32(np.nan), self._vlm_last_logprobs(n))
+        if return_logprobs:
+            return (out, np.stack(logits, 1), lps) if want_logits else (out, lps)
         return (out, np.stack(logits, 1)) if want_logits else out
 
     # -- ONNX graphs (InsightFace sessions) -------------------------------------------------------------

@@ -711,6 +711,25 @@ int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g
   FE_API_END(ctx)
 }
 
+// Bring-up hook: the VLM decoder's greedy selection (vlm_select) on caller logits [rows][vocab], rounded to bf16 first as in the decoder.
+// ids [rows]; logprobs [rows] (nullable: the plain kernels) the log-probability of each chosen id.
+int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(logits && ids && rows > 0 && rows <= 65535 && vocab > 0, "bad arguments (1 <= rows <= 65535, vocab > 0)");
+  C.arena.reset();
+  const size_t bytes = (size_t)rows * vocab * sizeof(float);
+  float* d_lg = (float*)C.arena.alloc(bytes);
+  int* d_ids = (int*)C.arena.alloc((size_t)rows * sizeof(int));
+  float* d_lp = logprobs ? (float*)C.arena.alloc((size_t)rows * sizeof(float)) : nullptr;
+  FE_HIP(hipMemcpyAsync(d_lg, logits, bytes, hipMemcpyHostToDevice, C.stream));
+  vlm_select(C, d_lg, rows, vocab, d_ids, d_lp);
+  FE_HIP(hipMemcpyAsync(ids, d_ids, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  if (d_lp) FE_HIP(hipMemcpyAsync(logprobs, d_lp, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+
 // Developer hook: time one conv shape on random data (device-resident), `iters` launches, forced tile variant.
 int fe_bench_conv(fe_ctx* ctx, int n, int h, int w, int cin, int cout, int k, int stride, int pad, int with_res, int act,
                   int variant, int iters, float* ms_out) {
@@ -1603,7 +1622,7 @@ static void vlm_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* position
     FE_HIP(hipMemcpyAsync(d_slot, slot.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
     m.ds_slot = d_slot;
   }
-  vlm_forward(C, m, x, d_pos, n_seq, len, d_next, d_logits);
+  vlm_forward(C, m, x, d_pos, n_seq, len, d_next, d_logits, nullptr, m.last_lp);      // (the chosen tokens' log-probs: fe_vlm_last_logprobs)
   FE_HIP(hipMemcpyAsync(next_tokens, d_next, (size_t)n_seq * sizeof(int), hipMemcpyDeviceToHost, C.stream));
   if (logits) FE_HIP(hipMemcpyAsync(logits, d_logits, (size_t)n_seq * m.vocab * sizeof(float), hipMemcpyDeviceToHost, C.stream));
   FE_HIP(hipStreamSynchronize(C.stream));
@@ -1648,7 +1667,9 @@ int fe_vlm_prefill_images_padded(fe_ctx* ctx, const int32_t* tokens, const int32
   vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits, image_rows, n_image_rows, pad);
   FE_API_END_CAPACITY(ctx)
 }
-int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens) {
+extern "C++" {
+// fe_vlm_generate and fe_vlm_generate_scored: out_logprobs == nullptr takes the plain selection kernels
+static int vlm_generate_impl(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens, float* out_logprobs) {
   FE_API_BEGIN(ctx)
   if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
   Ctx& C = ctx->c;
@@ -1658,10 +1679,30 @@ int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_
   int* d_tok = (int*)C.arena.alloc((size_t)n_seq * sizeof(int));
   int* d_pos = (int*)C.arena.alloc((size_t)3 * n_seq * sizeof(int));
   int* d_out = (int*)C.arena.alloc((size_t)n_steps * n_seq * sizeof(int));
+  float* d_lp = out_logprobs ? (float*)C.arena.alloc((size_t)n_steps * n_seq * sizeof(float)) : nullptr;
   FE_HIP(hipMemcpyAsync(d_tok, tokens, (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice, C.stream));
   FE_HIP(hipMemcpyAsync(d_pos, position_ids, (size_t)3 * n_seq * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  vlm_decode_steps(C, m, d_tok, d_pos, n_seq, n_steps, d_out);
+  vlm_decode_steps(C, m, d_tok, d_pos, n_seq, n_steps, d_out, d_lp);
   FE_HIP(hipMemcpyAsync(out_tokens, d_out, (size_t)n_steps * n_seq * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  if (d_lp) FE_HIP(hipMemcpyAsync(out_logprobs, d_lp, (size_t)n_steps * n_seq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+}  // extern "C++"
+int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens) {
+  return vlm_generate_impl(ctx, tokens, position_ids, n_seq, n_steps, out_tokens, nullptr);
+}
+int fe_vlm_generate_scored(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens, float* out_logprobs) {
+  if (ctx && !out_logprobs) { ctx->c.err = "generate_scored: out_logprobs is null (fe_vlm_generate takes no scores)"; return FE_ERR_INVALID; }
+  return vlm_generate_impl(ctx, tokens, position_ids, n_seq, n_steps, out_tokens, out_logprobs);
+}
+int fe_vlm_last_logprobs(fe_ctx* ctx, float* out) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+  Ctx& C = ctx->c;
+  const VlmModel& m = *C.vlm;
+  FE_CHECK(out && m.cache_B > 0 && m.last_lp, "last_logprobs: no prefill yet");
+  FE_HIP(hipMemcpyAsync(out, m.last_lp, (size_t)m.cache_B * sizeof(float), hipMemcpyDeviceToHost, C.stream));
   FE_HIP(hipStreamSynchronize(C.stream));
   FE_API_END(ctx)
 }

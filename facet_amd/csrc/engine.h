@@ -390,6 +390,9 @@ struct VlmModel {
   // left padding of every sequence (device int [cache_B]): set by each prefill (zeros unless fe_vlm_prefill_images_padded), read by the
   // attention kernels of the prefill and of every later decode step (a captured decode graph holds the pointer)
   int* pad = nullptr;
+  // log-probabilities of the tokens chosen by the last selection (device float [cache_B], NaN before the first): written by every prefill and
+  // decode step, and by each step of a scored fe_vlm_generate_scored (fe_vlm_last_logprobs reads it)
+  float* last_lp = nullptr;
   // patch rows of the last fe_vlm_preprocess_rgb (device bf16 [pre_rows][patch_dim]), the input of fe_vlm_encode_preprocessed
   bf16* pre_pv = nullptr; int pre_rows = 0, pre_cap = 0;
   // Qwen3-VL: the vision tower, the DeepStack features of the last fe_vlm3_encode_images (device bf16 [n_ds][ds_cap][hidden], rows as
@@ -423,8 +426,11 @@ void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n);
 void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n);
 void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, int d);
 void vlm_embed(Ctx& c, const VlmModel& m, const int* tok_dev, int rows, bf16* x);
-void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev = nullptr);
-void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev);
+void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev = nullptr,
+                 float* lp_dev = nullptr);
+void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp = nullptr);
+// greedy ids (+ log-probabilities when lp_dev != nullptr) of fp32 logit rows, rounded to bf16 in place (model_vlm.hip)
+void vlm_select(Ctx& c, float* lg, int B, int vocab, int* next_dev, float* lp_dev);
 
 void build_topiq_head(TopiqModel& m, const WeightStore& ws);
 // feats: the 5 pyramid levels for nb images; scores_dev: device [nb]

@@ -603,15 +603,17 @@ static void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf
 }
 
 // device-resident decode state (graph replay): after a step, the chosen tokens become the next step's input, every position and the
-// cache length advance by one, and the tokens are appended to the output table [step][B]
+// cache length advance by one, and the tokens are appended to the output table [step][B] (LP: their log-probs lp [B] to out_lp [step][B])
+template <bool LP>
 __global__ void vlm_advance_kernel(const int* __restrict__ next, int* __restrict__ tok, int* __restrict__ pos, int* __restrict__ len, int* __restrict__ step,
-                                   int* __restrict__ out, int B) {
+                                   int* __restrict__ out, int B, const float* __restrict__ lp, float* __restrict__ out_lp) {
   const int b = threadIdx.x;
   const int st = *step;
   if (b < B) {
     const int t = next[b];
     tok[b] = t;
     out[(size_t)st * B + b] = t;
+    if (LP) out_lp[(size_t)st * B + b] = lp[b];
     pos[b] += 1; pos[B + b] += 1; pos[2 * B + b] += 1;
   }
   __syncthreads();
@@ -656,14 +658,27 @@ __global__ void vlm_add_rmsnorm_kernel(bf16* __restrict__ x, const bf16* __restr
 
 // argmax over a vocabulary row in two launches (one 256-thread block walked 152064 logits in 180 us): 64 chunks per row, then one wave
 // per row over the 64 partial results. Logits are rounded to bf16 in place first; ties go to the lowest index (torch.argmax).
+// LP: the same pass also takes the log-probability of the chosen token, -log sum_i exp(l_i - max_j l_j) over the bf16-rounded logits (the
+// chosen logit is the maximum). Every thread keeps sum exp(l - best) beside its running best (rescaled when the best moves); the block and
+// then the final wave merge (max, sum) pairs with s = s1 e^(m1 - m) + s2 e^(m2 - m). exp2 with a log2(e) scale (v_exp_f32); a part whose
+// maximum is -inf contributes 0.
 constexpr int VLM_AM_CHUNKS = 64;
-__global__ void vlm_argmax_part_kernel(float* __restrict__ lg, int vocab, float* __restrict__ pv, int* __restrict__ pi) {
+constexpr float VLM_LOG2E = 1.4426950408889634f;
+// s e^(mi - m) for mi <= m, 0 for an empty part (mi = -inf: no NaN from -inf - -inf)
+__device__ __forceinline__ float vlm_lse_rescale(float s, float mi, float m) { return mi == -INFINITY ? 0.f : s * exp2f((mi - m) * VLM_LOG2E); }
+template <bool LP>
+__global__ void vlm_argmax_part_kernel(float* __restrict__ lg, int vocab, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ ps) {
   float* row = lg + (size_t)blockIdx.y * vocab;
   const int per = (vocab + VLM_AM_CHUNKS - 1) / VLM_AM_CHUNKS, i0 = blockIdx.x * per, i1 = min(i0 + per, vocab);
   float best = -INFINITY; int bi = 0x7fffffff;
+  float s = 0.f;      // (LP) sum exp(l - best) over this thread's logits
   for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
     const float v = (float)(bf16)row[i];
     row[i] = v;
+    if (LP) {
+      if (v > best) s = vlm_lse_rescale(s, best, v) + 1.f;
+      else if (v != -INFINITY) s += exp2f((v - best) * VLM_LOG2E);
+    }
     if (v > best || (v == best && i < bi)) { best = v; bi = i; }
   }
   __shared__ float sv[256]; __shared__ int si[256];
@@ -676,15 +691,33 @@ __global__ void vlm_argmax_part_kernel(float* __restrict__ lg, int vocab, float*
     }
     __syncthreads();
   }
+  if (LP) {      // sv[0] is the chunk's maximum: every thread's sum rescaled to it, summed over the block (waves, then 4 partials)
+    __shared__ float sw[4];
+    float t = vlm_lse_rescale(s, best, sv[0]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) ps[blockIdx.y * VLM_AM_CHUNKS + blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+  }
   if (threadIdx.x == 0) { pv[blockIdx.y * VLM_AM_CHUNKS + blockIdx.x] = sv[0]; pi[blockIdx.y * VLM_AM_CHUNKS + blockIdx.x] = si[0]; }
 }
-__global__ void vlm_argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int* __restrict__ next) {
+template <bool LP>
+__global__ void vlm_argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int* __restrict__ next, const float* __restrict__ ps,
+                                        float* __restrict__ lp) {
   const int b = blockIdx.x, t = threadIdx.x;      // 64 threads = one wave
-  float v = pv[b * VLM_AM_CHUNKS + t]; int j = pi[b * VLM_AM_CHUNKS + t];
+  const float v0 = pv[b * VLM_AM_CHUNKS + t];
+  float v = v0; int j = pi[b * VLM_AM_CHUNKS + t];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float v2 = __shfl_xor(v, o); const int j2 = __shfl_xor(j, o);
     if (v2 > v || (v2 == v && j2 < j)) { v = v2; j = j2; }
+  }
+  if (LP) {      // v: the row maximum, in every lane after the butterfly
+    float s = vlm_lse_rescale(ps[b * VLM_AM_CHUNKS + t], v0, v);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (t == 0) lp[b] = -logf(s);
   }
   if (t == 0) next[b] = j;
 }
@@ -929,13 +962,16 @@ void VlmModel::reserve_cache(int B, int max_seq_) {
   }
   FE_HIP(hipMalloc((void**)&pad, (size_t)B * sizeof(int)));
   FE_HIP(hipMemset(pad, 0, (size_t)B * sizeof(int)));
+  FE_HIP(hipMalloc((void**)&last_lp, (size_t)B * sizeof(float)));
+  FE_HIP(hipMemset(last_lp, 0xff, (size_t)B * sizeof(float)));      // NaN until a selection writes it
   cache_B = B; max_seq = max_seq_; cur_len = 0;
 }
 void VlmModel::release_cache() {
   for (bf16* p : kcache) (void)hipFree(p);
   for (bf16* p : vcache) (void)hipFree(p);
   if (pad) (void)hipFree(pad);
-  pad = nullptr;
+  if (last_lp) (void)hipFree(last_lp);
+  pad = nullptr; last_lp = nullptr;
   kcache.clear(); vcache.clear();
   cache_B = 0; max_seq = 0; cur_len = 0;
 }
@@ -960,10 +996,10 @@ void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, in
 }
 
 // x: [B*L][hidden] bf16 rows (token embeddings, image rows already in place), pos: device [3][B*L]. Appends L positions to the cache of
-// every sequence, leaves the next token of every sequence in next_dev [B] and (optionally) the bf16-rounded logits in logits_dev [B][vocab].
-// len_dev (decode steps only): the cache length in device memory, read by the kernels instead of the host's cur_len - the form a
-// captured graph replays.
-void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev) {
+// every sequence, leaves the next token of every sequence in next_dev [B], (optionally) the bf16-rounded logits in logits_dev [B][vocab] and
+// (optionally) the log-probabilities of the chosen tokens in lp_dev [B]. len_dev (decode steps only): the cache length in device memory,
+// read by the kernels instead of the host's cur_len - the form a captured graph replays.
+void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev, float* lp_dev) {
   const VlmConfig& g = m.cfg;
   const int rows = B * L, d = m.hidden, nh = g.n_heads, nkv = g.n_kv_heads, qd = nh * 128, qkvd = (nh + 2 * nkv) * 128;
   const int start = m.cur_len, Lk = start + L;
@@ -1072,20 +1108,37 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   if (B <= 4 && !vlm_uses_gemm32(m.lm_head, B)) vlm_gemv(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
   else if (B <= 32 && d % 128 == 0) vlm_gemm32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
   else linear_forward_f32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab, ACT_NONE);
+  vlm_select(c, lg, B, m.vocab, next_dev, lp_dev);
+  m.cur_len = Lk;
+  c.arena.rewind(mark);
+}
+
+// greedy selection over rows of fp32 logits lg [B][vocab] (rounded to bf16 in place): next_dev [B] the chosen ids, lp_dev [B] (nullable) their
+// log-probabilities. lp_dev == nullptr launches the plain kernels: the ids do not depend on it.
+void vlm_select(Ctx& c, float* lg, int B, int vocab, int* next_dev, float* lp_dev) {
+  FE_CHECK(B > 0 && B <= 65535 && vocab > 0, "vlm select: %d rows of %d logits", B, vocab);
+  const size_t mark = c.arena.mark();
   float* apv = c.arena.array<float>((size_t)B * VLM_AM_CHUNKS);
   int* api = c.arena.array<int>((size_t)B * VLM_AM_CHUNKS);
-  hipLaunchKernelGGL(vlm_argmax_part_kernel, dim3(VLM_AM_CHUNKS, B), dim3(256), 0, c.stream, lg, m.vocab, apv, api);
-  hipLaunchKernelGGL(vlm_argmax_final_kernel, dim3(B), dim3(64), 0, c.stream, (const float*)apv, (const int*)api, next_dev);
+  if (lp_dev) {
+    float* aps = c.arena.array<float>((size_t)B * VLM_AM_CHUNKS);
+    hipLaunchKernelGGL(vlm_argmax_part_kernel<true>, dim3(VLM_AM_CHUNKS, B), dim3(256), 0, c.stream, lg, vocab, apv, api, aps);
+    hipLaunchKernelGGL(vlm_argmax_final_kernel<true>, dim3(B), dim3(64), 0, c.stream, (const float*)apv, (const int*)api, next_dev, (const float*)aps, lp_dev);
+  } else {
+    hipLaunchKernelGGL(vlm_argmax_part_kernel<false>, dim3(VLM_AM_CHUNKS, B), dim3(256), 0, c.stream, lg, vocab, apv, api, (float*)nullptr);
+    hipLaunchKernelGGL(vlm_argmax_final_kernel<false>, dim3(B), dim3(64), 0, c.stream, (const float*)apv, (const int*)api, next_dev, (const float*)nullptr,
+                       (float*)nullptr);
+  }
   FE_HIP(hipGetLastError());
-  m.cur_len = Lk;
   c.arena.rewind(mark);
 }
 
 // n_steps greedy decode steps with NO host round trip: token ids, positions and the cache length live in device memory, one step is
 // captured into a HIP graph (~12 launches per layer: at the reference's batch sizes a step is launch-bound otherwise) and replayed.
 // tok_dev [B] holds the tokens to feed first (the prefill's choice), pos_dev [3][B] their positions; out_dev [n_steps][B] receives the
-// tokens chosen by the steps. Leaves cur_len advanced by n_steps.
-void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev) {
+// tokens chosen by the steps and (out_lp != nullptr) out_lp [n_steps][B] their log-probabilities, by way of the model's last_lp. Leaves
+// cur_len advanced by n_steps.
+void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp) {
   if (n_steps <= 0) return;
   FE_CHECK(B == m.cache_B && m.cur_len > 0 && m.cur_len + n_steps <= m.max_seq, "vlm: %d more positions do not fit the cache (%d of %d used)", n_steps, m.cur_len, m.max_seq);
   const size_t mark = c.arena.mark();
@@ -1096,8 +1149,13 @@ void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, in
   FE_HIP(hipMemcpyAsync(st, init, sizeof init, hipMemcpyHostToDevice, c.stream));
   auto one_step = [&]() {
     vlm_embed(c, m, tok_dev, B, x);
-    vlm_forward(c, m, x, pos_dev, B, 1, next, nullptr, st);
-    hipLaunchKernelGGL(vlm_advance_kernel, dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1, out_dev, B);
+    vlm_forward(c, m, x, pos_dev, B, 1, next, nullptr, st, out_lp ? m.last_lp : nullptr);
+    if (out_lp)
+      hipLaunchKernelGGL(vlm_advance_kernel<true>, dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1, out_dev, B,
+                         (const float*)m.last_lp, out_lp);
+    else
+      hipLaunchKernelGGL(vlm_advance_kernel<false>, dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1, out_dev, B,
+                         (const float*)nullptr, (float*)nullptr);
     FE_HIP(hipGetLastError());
   };
   const int len0 = m.cur_len;

@@ -8,7 +8,9 @@ generated text into vocabulary tags (:446-495). The photo path (`tag_image` / `t
 smart_resize and the grids on the host, the resample / rescale / normalise / patchify on the GPU (`fe_vlm_preprocess_rgb`, matching
 transformers' PIL backend bit for bit), the chat text and its <|image_pad|> expansion here, left padding of the batch in the engine
 (`fe_vlm_prefill_images_padded`). The tokenizer stays the caller's (`encode` / `decode` callables of the checkpoint's processor, exactly as
-the CLIP text tower takes token ids, facet_amd/tagger.py); `generate_with_images` still takes the processor's own tensors.
+the CLIP text tower takes token ids, facet_amd/tagger.py); `generate_with_images` still takes the processor's own tensors. The scored half
+(`tag_image_with_scores` / `get_tags_with_scores`, :497-626) takes the greedy tokens' log-probs from the engine's selection pass
+(`Engine.vlm_generate(return_logprobs=True)`) and splits them into tags here (`tag_confidences`).
 """
 import math
 from typing import Any, Dict, Iterable, List, Optional, Sequence
@@ -247,6 +249,34 @@ def edit_distance(a: str, b: str) -> int:
     return int(row[-1])
 
 
+def tag_confidences(token_ids: Sequence[int], logprobs: Sequence[float], tags: Sequence[str], token_text) -> Dict[str, float]:
+    """Per-tag confidences of one generated row, as the reference's tag_image_with_scores computes them (models/vlm_tagger.py:590-618):
+    token_ids / logprobs are the generated tokens up to and including the first EOS (HF stops there at batch 1 and that step is in
+    `outputs.scores`), tags the `_parse_tags` result of the row's decoded text, token_text(id) the text of one token. The log-probs are
+    split into segments at tokens whose text contains ',' - such a token closes a non-empty segment and is dropped, but is appended to an
+    empty one (a leading or repeated comma). Tag i takes segment i BY INDEX (even where _parse_tags dropped or merged pieces): confidence
+    clamp(exp(mean log-prob), 0, 1), 1.0 when there is no such segment. token_text is the caller's `decode([id])`, which skips special
+    tokens (""), where the reference decodes them with skip_special_tokens=False into their literal text; neither contains a comma, so the
+    segments are the same."""
+    segments: List[List[float]] = []
+    cur: List[float] = []
+    for tid, lp in zip(token_ids, logprobs):
+        if "," in token_text(int(tid)) and cur:
+            segments.append(cur)
+            cur = []
+        else:
+            cur.append(float(lp))
+    if cur:
+        segments.append(cur)
+    out: Dict[str, float] = {}
+    for i, tag in enumerate(tags):
+        if i < len(segments) and segments[i]:
+            out[tag] = max(0.0, min(1.0, math.exp(sum(segments[i]) / len(segments[i]))))
+        else:
+            out[tag] = 1.0
+    return out
+
+
 class VLMTagger:
     """Same constructor and public surface as the reference class (models/vlm_tagger.py:45-87): `model_config` (model_path,
     vlm_batch_size, max_new_tokens, ...), optional `scoring_config` for the tag vocabulary. `engine` is the facet_amd Engine the decoder
@@ -371,9 +401,10 @@ class VLMTagger:
         image_rows = np.flatnonzero(((ids == img) & (am == 1)).reshape(-1)).astype(np.int32)
         return dict(rgb=rgb, sizes=sizes, grid_thw=grid, input_ids=ids, attention_mask=am, position_ids=pos, image_rows=image_rows)
 
-    def generate_from_images(self, images, max_new_tokens: Optional[int] = None, prompt: Optional[str] = None):
+    def generate_from_images(self, images, max_new_tokens: Optional[int] = None, prompt: Optional[str] = None, return_logprobs: bool = False):
         """Greedy generation for a list of photos (any sizes): preprocessing and the vision tower on the GPU from uint8 pixels, one
-        left-padded batch through the decoder. -> int [n, max_new_tokens]. An EngineCapacityError means the batch did not fit."""
+        left-padded batch through the decoder. -> int [n, max_new_tokens] or, with return_logprobs, (ids, log-probs float32 [n,
+        max_new_tokens], NaN after a row's first EOS). An EngineCapacityError means the batch did not fit."""
         if self.model is None:
             raise RuntimeError("VLMTagger.load() first")
         x = self.prepare_inputs(images, prompt)
@@ -390,7 +421,7 @@ class VLMTagger:
             self.engine.vlm_encode_preprocessed(idx["patch_pos_hw"], idx["window_index"], idx["cu_window_seqlens"], idx["cu_seqlens"], want_embeds=False)
         n_new = int(max_new_tokens or self.model_config.get("max_new_tokens", 100))
         return self.engine.vlm_generate(x["input_ids"], n_new, position_ids=x["position_ids"], eos_token_ids=self.tokens["eos_token_ids"],
-                                        image_rows=x["image_rows"], attention_mask=x["attention_mask"])
+                                        image_rows=x["image_rows"], attention_mask=x["attention_mask"], return_logprobs=return_logprobs)
 
     def _texts(self, generated_ids) -> List[str]:
         """Each row cut at its first EOS id, then the tokenizer's decode."""
@@ -427,6 +458,56 @@ class VLMTagger:
                         results.append(self.tag_image(im, max_tags))
                     except EngineCapacityError:
                         results.append([])
+        return results
+
+    # -- confidence scores (reference :497-626) -----------------------------------------------------------------------------------------
+    def _scored_tags(self, ids_row, lp_row, max_tags: int) -> Dict[str, float]:
+        """One generated row and its log-probs -> {tag: confidence}: the row up to and including its first EOS, its text, _parse_tags,
+        tag_confidences."""
+        if self.decode is None:
+            raise RuntimeError("no tokenizer: pass decode= (processor.decode of the checkpoint, skip_special_tokens=True)")
+        ids_row = np.asarray(ids_row)
+        hit = np.flatnonzero(np.isin(ids_row, [int(e) for e in self.tokens["eos_token_ids"]]))
+        n = int(hit[0]) + 1 if hit.size else len(ids_row)
+        gen = [int(t) for t in ids_row[:n]]
+        tags = self._parse_tags(self.decode(gen), max_tags)
+        if not tags:
+            return {}
+        return tag_confidences(gen, [float(v) for v in np.asarray(lp_row)[:n]], tags, lambda t: self.decode([t]))
+
+    def tag_image_with_scores(self, image, max_tags: int = 5) -> Dict[str, float]:
+        """Tags of one photo with confidences in [0, 1]: exp of the mean log-probability of each tag's tokens (the greedy tokens'
+        log-probs come from the decoder's selection pass on the device; see tag_confidences for the split into tags)."""
+        ids, lps = self.generate_from_images([image], return_logprobs=True)
+        return self._scored_tags(ids[0], lps[0], max_tags)
+
+    def get_tags_with_scores(self, image, threshold: float = 0.0) -> Dict[str, float]:
+        """tag_image_with_scores with its default max_tags; a threshold > 0 keeps the tags whose confidence is >= threshold."""
+        scores = self.tag_image_with_scores(image)
+        if threshold > 0:
+            scores = {tag: conf for tag, conf in scores.items() if conf >= threshold}
+        return scores
+
+    def tag_batch_with_scores(self, images, max_tags: int = 5) -> List[Dict[str, float]]:
+        """facet_amd extension (the reference scores one photo at a time): tag_image_with_scores for every photo, in order, with
+        sub-batches of vlm_batch_size run as one left-padded batch each. A row has the tags tag_image_with_scores gives that photo alone;
+        its confidences agree to within the batch's rounding of the logits. A sub-batch that does not fit the engine (EngineCapacityError)
+        is retried one image at a time, and an image that still does not fit gets {} (as tag_batch)."""
+        results: List[Dict[str, float]] = []
+        for i in range(0, len(images), self.batch_size):
+            sub = images[i:i + self.batch_size]
+            try:
+                if len(sub) == 1:
+                    results.append(self.tag_image_with_scores(sub[0], max_tags))
+                else:
+                    ids, lps = self.generate_from_images(sub, return_logprobs=True)
+                    results.extend(self._scored_tags(r, lp, max_tags) for r, lp in zip(ids, lps))
+            except EngineCapacityError:
+                for im in sub:
+                    try:
+                        results.append(self.tag_image_with_scores(im, max_tags))
+                    except EngineCapacityError:
+                        results.append({})
         return results
 
     def tags_from_ids(self, generated_ids, max_tags: int = 5) -> List[List[str]]:

@@ -121,6 +121,14 @@ int fe_vlm_decode_step(fe_ctx* ctx, const int32_t* tokens, const int32_t* positi
  * device memory and one captured HIP graph of a decode step is replayed; out_tokens [n_steps][n_seq] = the token each step chose.
  * End-of-sequence handling is the caller's (cut the rows at the first EOS id). */
 int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens);
+/* Scores of the greedy tokens (what `generate(..., output_scores=True)` + log_softmax at the chosen ids gives, models/vlm_tagger.py:497-626):
+ * the selection pass that picks a token also takes its log-probability, -log sum_i exp(l_i - max_j l_j) over the bf16-rounded logits.
+ * fe_vlm_generate_scored = fe_vlm_generate plus out_logprobs [n_steps][n_seq] (not NULL), each step's log-probs in the same device loop.
+ * fe_vlm_last_logprobs: out [n_seq] = the log-probs of the tokens chosen by the most recent prefill (any of the three forms), decode step
+ * or generate step (NaN before the first). */
+int fe_vlm_generate_scored(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens,
+                           float* out_logprobs);
+int fe_vlm_last_logprobs(fe_ctx* ctx, float* out);
 /* Photos in (the image half of `processor(text=texts, images=images, padding=True)`, models/vlm_tagger.py:245-259 / :346-360):
  * fe_vlm_preprocess_rgb = Qwen2-VL's image processor (PIL backend) after its size choice: rgb holds n_images uint8 RGB images [h][w][3] back
  * to back; sizes [n_images][4] = h, w and the target oh, ow of each (transformers' smart_resize, computed by the caller: multiples of 28).
@@ -215,6 +223,9 @@ int fe_op_maxpool2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int
 int fe_op_bilinear(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_adaptive_avgpool(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g, const float* b, float eps, float* y);
+/* test hook of the VLM decoder's greedy selection: logits [rows][vocab] (rows <= 65535) are rounded to bf16 as in the decoder; ids [rows] =
+   argmax (first index on ties), logprobs [rows] (NULL: not computed) = the log-probability of that id. */
+int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs);
 
 /* developer hook: force a tile variant of the contraction kernel for every later launch (0 = automatic choice) */
 int fe_set_conv_variant(fe_ctx* ctx, int variant);

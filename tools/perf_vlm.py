@@ -2,6 +2,11 @@
 
   python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32] [--vision N] [--from-rgb N] [--pad P]
   python tools/perf_vlm.py --family qwen3 [--prompt 512] [--new 32] [--batches 1,4,32] [--vision N]
+  python tools/perf_vlm.py --scores [--layers 4] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 7]
+
+--scores: the device-resident decode loop with the chosen tokens' log-probs (fe_vlm_generate_scored) against the plain loop
+(fe_vlm_generate) at the 7B geometry, same prefill, --reps alternating repetitions of each; prints the median ms/step of both and the
+difference, and checks that the ids are identical.
 
 --family qwen3: Qwen3-VL-2B at full depth (28 decoder layers of hidden 2048, 16 / 8 heads of 128, intermediate 6144, tied vocab 151936;
 tower of 24 blocks of 1024, 16 heads of 64, DeepStack after 5 / 11 / 17), ~4 GB of seeded synthetic weights, no extrapolation: prefill
@@ -34,6 +39,8 @@ ap.add_argument("--from-rgb", type=int, default=0, help="time vision encode from
 ap.add_argument("--pad", type=int, default=0, help="also time decode steps with every other sequence left-padded by this many tokens")
 ap.add_argument("--family", default="qwen2_5", choices=("qwen2_5", "qwen3"))
 ap.add_argument("--qwen25-layers", type=int, default=4, help="--family qwen3: layers of the Qwen2.5-VL-7B decoder timed at batch 4 for comparison")
+ap.add_argument("--scores", action="store_true", help="time fe_vlm_generate_scored against fe_vlm_generate (ms/step) and stop")
+ap.add_argument("--reps", type=int, default=7, help="--scores: alternating repetitions of each loop")
 a = ap.parse_args()
 
 
@@ -117,6 +124,39 @@ t0 = time.time()
 e.load_weights(FE_MODEL_VLM, sd)
 del sd
 print(f"committed in {time.time() - t0:.0f} s", flush=True)
+if a.scores:
+    import ctypes as C
+    i32p = C.POINTER(C.c_int32)
+    print(f"fe_vlm_generate_scored vs fe_vlm_generate: {a.layers} layers of the 7B geometry + lm_head (vocab {V}), prompt {a.prompt}, "
+          f"{a.new} decode steps per call, median of {a.reps} alternating calls each", flush=True)
+    for B in [int(b) for b in a.batches.split(",")]:
+        L = a.prompt
+        p = np.random.default_rng(B).integers(0, V, (B, L)).astype(np.int32)
+        tok = np.empty(B, np.int32)
+        pos = np.full((3, B), L, np.int32)
+        ids = {False: np.empty((a.new, B), np.int32), True: np.empty((a.new, B), np.int32)}
+        lp = np.empty((a.new, B), np.float32)
+        times = {False: [], True: []}
+        for r in range(a.reps + 1):                      # (the first round warms up: graph capture, first-use attributes)
+            for scored in (False, True):
+                tok[:] = e.vlm_prefill(p, max_seq=L + a.new + 8)
+                e.sync()
+                t0 = time.perf_counter()
+                if scored:
+                    e._ck(e.lib.fe_vlm_generate_scored(e.h, tok.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), B, a.new, ids[True].ctypes.data_as(i32p),
+                                                       lp.ctypes.data_as(C.POINTER(C.c_float))))
+                else:
+                    e._ck(e.lib.fe_vlm_generate(e.h, tok.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), B, a.new, ids[False].ctypes.data_as(i32p)))
+                dt = (time.perf_counter() - t0) * 1e3 / a.new
+                if r:
+                    times[scored].append(dt)
+            assert np.array_equal(ids[False], ids[True]), "scored and plain loops chose different ids"
+        t_p, t_s = float(np.median(times[False])), float(np.median(times[True]))
+        print(f"B={B:3d}: plain {t_p:7.4f} ms/step | scored {t_s:7.4f} ms/step | +{(t_s - t_p) * 1e3:6.1f} us/step = {100 * (t_s - t_p) / t_p:+.2f} % "
+              f"(spread plain {min(times[False]):.4f}..{max(times[False]):.4f}, scored {min(times[True]):.4f}..{max(times[True]):.4f}); "
+              f"ids identical; log-probs {lp.min():.3f}..{lp.max():.3f}", flush=True)
+    e.close()
+    sys.exit(0)
 if a.vision:
     from facet_amd.vlm_tagger import vision_indices
     g = [[1, 74, 74]] * a.vision
