@@ -158,6 +158,8 @@ SIGNATURES = {
     "fe_swap_rb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "fe_leading_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
 }
 
 
@@ -965,6 +967,40 @@ class Engine:
             max_lines = int(counts.max())          # rare: more segments than room - run again with enough
         out = [lines[i, :counts[i]].copy() for i in range(n)]
         return (out, edges) if want_edges else out
+
+    def phash(self, images, bgr=False, want_small=False, want_dct=False):
+        """uint8 [n,h,w,3] (or device tuple), RGB or (bgr=True) BGR bytes -> uint64 [n]: imagehash.phash(pil_img) of every image as
+        an integer (facet_amd.phash.to_hex gives the reference's strings). With want_small / want_dct the return is
+        (hashes, small uint8 [n,32,32] | None, lo float64 [n,8,8] | None): the resized gray image and the low-frequency DCT block."""
+        p, n, h, w, dev, keep = self._img_ptr(images)
+        hashes = np.empty((n,), np.uint64)
+        small = np.empty((n, 32, 32), np.uint8) if want_small else None
+        lo = np.empty((n, 8, 8), np.float64) if want_dct else None
+        self._ck(self.lib.fe_phash(self.h, p, n, h, w, 1 if bgr else 0, dev, hashes.ctypes.data_as(C.c_void_p),
+                                   small.ctypes.data_as(C.c_void_p) if want_small else None,
+                                   lo.ctypes.data_as(C.c_void_p) if want_dct else None))
+        return (hashes, small, lo) if (want_small or want_dct) else hashes
+
+    def hamming_pairs(self, hashes, max_distance, max_pairs=None):
+        """hashes: uint64 [n] (host array) or (device_ptr, n). -> int32 [k,2]: every i < j whose hashes differ in at most
+        max_distance bits, in ascending (i, j) order. max_pairs: room for the first attempt (default max(1024, 4 n)); when there
+        are more, the call is repeated once with exactly enough."""
+        if isinstance(hashes, tuple):
+            p, n = hashes
+            dev, keep = 1, None
+        else:
+            keep = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1)
+            p, n, dev = keep.ctypes.data_as(C.c_void_p), keep.shape[0], 0
+        room = int(max_pairs) if max_pairs is not None else max(1024, 4 * n)
+        count = C.c_int64(0)
+        for _ in range(2):
+            pairs = np.empty((room, 2), np.int32)
+            self._ck(self.lib.fe_hamming_pairs(self.h, p, n, dev, int(max_distance), room, pairs.ctypes.data_as(C.c_void_p) if room else None,
+                                               C.byref(count)))
+            if count.value <= room:
+                return pairs[:count.value].copy()
+            room = count.value
+        raise EngineError(f"hamming_pairs: {count.value} pairs found after making room for {room}")
 
     def cv_resize_linear(self, imgs, oh, ow):
         a = np.ascontiguousarray(imgs, dtype=np.uint8)

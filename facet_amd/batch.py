@@ -8,14 +8,16 @@ Each dict carries, under the reference's own key names (batch_processor.py:298-3
 a pixel scan: CLIP aesthetic + embedding blob, TOPIQ quality, SAMP-Net composition score / pattern, the face dict's fields,
 the seven technical-metric groups, tags, and the two cross terms the reference derives on the spot (face_ratio :244,
 isolation_bonus :264-269). What stays with the caller because it needs files, configuration policy or libraries outside the
-hot path: path / EXIF columns, phash (imagehash), leading lines (CompositionAnalyzer.detect_leading_lines: Canny + probabilistic
-Hough; `detect_lines=True` computes them through `fe_leading_lines`, or pass `leading_lines=` scores in). With `policy=` (an `aggregate.AggregatePolicy` made from the
+hot path: path / EXIF columns, leading lines (CompositionAnalyzer.detect_leading_lines: Canny + probabilistic
+Hough; `detect_lines=True` computes them through `fe_leading_lines`, or pass `leading_lines=` scores in). `phash=True` adds the
+`phash` column (`str(imagehash.phash(pil_img))`, batch_processor.py:216) through `fe_phash`; off by default. With `policy=` (an `aggregate.AggregatePolicy` made from the
 scoring configuration) the category and aggregate score (`Facet.calculate_aggregate_logic`) are computed for the whole batch
 as the last step, from the multi-pass metrics mapping (multi_pass.py:713-752); `metrics_for_aggregate()` returns the
 narrower mapping of the single-pass path (batch_processor.py:272-296).
 
 Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P + SAMP-Net), fe_image_stats (technical scans),
-fe_face_analyze + fe_roi_laplacian (through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger).
+fe_face_analyze + fe_roi_laplacian (through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
+fe_phash (with `phash=True`).
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -65,7 +67,8 @@ def detect_silhouette(histogram_silhouette, tags, face_count):
 class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
-                 aux_engine=None):
+                 aux_engine=None, phash=False):
+        self.phash = phash      # add the 'phash' column (16 hex digits) from the resident BGR copy
         self.engine, self.tagger, self.face_analyzer, self.policy, self.detect_lines = engine, tagger, face_analyzer, policy, detect_lines
         # second context on the same GPU for statistics / faces / lines (see module docstring); None = everything on `engine`, in sequence
         self.aux_engine = aux_engine
@@ -101,17 +104,21 @@ class BatchScorer:
                 if lines_ is None and self.detect_lines:      # CompositionAnalyzer.detect_leading_lines (multi_pass.py:702-705), batched
                     from .composition import score_lines
                     lines_ = [score_lines(l, h, w)['leading_lines_score'] for l in eng.leading_lines(bgr_dev)]
-                return tech_, faces_, lines_
+                hashes_ = None
+                if self.phash:      # the same bytes as the PIL image, in B,G,R order
+                    from .phash import phash_batch
+                    hashes_ = phash_batch(eng, bgr_dev, bgr=True)
+                return tech_, faces_, lines_, hashes_
 
             if self._pool is not None:
                 fut = self._pool.submit(rest, self.aux_engine)      # fe_swap_rb_u8 has synchronised: the BGR copy is complete
                 try:
                     rec, mask = e.ensemble_score(rgb_dev)
                 finally:
-                    tech, faces, leading_lines = fut.result()       # also on error: the worker must be done before the buffers go
+                    tech, faces, leading_lines, hashes = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score(rgb_dev)
-                tech, faces, leading_lines = rest(e)
+                tech, faces, leading_lines, hashes = rest(e)
         finally:
             e.dev_free(d_rgb)
             e.dev_free(d_bgr)
@@ -164,6 +171,8 @@ class BatchScorer:
             res['is_silhouette'] = detect_silhouette(t['histogram'].get('is_silhouette', 0), res.get('tags'), res.get('face_count', 0))
             if leading_lines is not None:
                 res['leading_lines_score'] = float(leading_lines[i])
+            if hashes is not None:
+                res['phash'] = hashes[i]
             out.append(res)
         if self.policy is not None:
             rows = [self.metrics_multi_pass(r, exif[i] if exif else None) for i, r in enumerate(out)]

@@ -26,6 +26,7 @@ struct fe_ctx {
   // face path: device copies of OpenCV's interpolation tables (built once / per size)
   short* warp_wtab = nullptr;
   int* hsv_sdiv = nullptr; int* hsv_hdiv = nullptr;   // cv2 HSV division tables
+  double* phash_cos = nullptr;                        // DCT-II cosine table of fe_phash
   struct CvResizeTab { int* ofs; short* coef; };
   std::map<std::tuple<int, int, int>, CvResizeTab> cvresize;   // (src, dst, clamp) -> tables
   std::vector<void*> misc_allocs;
@@ -2331,6 +2332,81 @@ int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int o
     FE_HIP(hipStreamSynchronize(C.stream));
     lines_host_stage(maps, nb, h, w, threshold, min_line_length, max_line_gap, max_lines, lines ? lines + (size_t)i0 * max_lines * 4 : nullptr,
                      counts ? counts + i0 : nullptr, threads);
+  }
+  FE_API_END(ctx)
+}
+
+/* imagehash.phash (hash_size 8, highfreq_factor 4) of every image of an RGB / BGR batch (reference batch_processor.py:216) */
+int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, uint64_t* hashes, uint8_t* small_out, double* dct_out) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(img && hashes && n > 0 && h > 0 && w > 0, "bad arguments");
+  if (!ctx->phash_cos) {
+    double tab[8 * 32];
+    phash_cos_table(tab);
+    FE_HIP(hipMalloc((void**)&ctx->phash_cos, sizeof(tab)));
+    ctx->misc_allocs.push_back(ctx->phash_cos);
+    FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
+  }
+  const size_t per = (size_t)h * w * 3;
+  // chunks of up to 256 images whatever the model micro-batch (a wave per row: large chunks fill the chip, scratch is 32 B per
+  // row), but at most 1 GiB of pixels: host input is staged through two device buffers of one chunk each
+  const int mb = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1 << 30) / per));
+  ImageStager st(ctx, img, n, per, mb, on_device);
+  for (int k = 0; k < st.chunks(); ++k) {
+    const int i0 = k * mb, nb = st.count(k);
+    C.arena.reset();
+    const uint8_t* d_in = st.get(k);
+    uint8_t* d_tmp = (uint8_t*)C.arena.alloc(phash_tmp_bytes(nb, h));
+    uint64_t* d_hash = (uint64_t*)C.arena.alloc((size_t)nb * sizeof(uint64_t));
+    uint8_t* d_small = small_out ? (uint8_t*)C.arena.alloc((size_t)nb * 1024) : nullptr;
+    double* d_dct = dct_out ? (double*)C.arena.alloc((size_t)nb * 64 * sizeof(double)) : nullptr;
+    launch_phash(C, d_in, nb, h, w, bgr ? 1 : 0, d_tmp, ctx->phash_cos, d_hash, d_small, d_dct);
+    st.done(k);
+    FE_HIP(hipMemcpyAsync(hashes + i0, d_hash, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, C.stream));
+    if (small_out) FE_HIP(hipMemcpyAsync(small_out + (size_t)i0 * 1024, d_small, (size_t)nb * 1024, hipMemcpyDeviceToHost, C.stream));
+    if (dct_out) FE_HIP(hipMemcpyAsync(dct_out + (size_t)i0 * 64, d_dct, (size_t)nb * 64 * sizeof(double), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next micro-batch
+  }
+  FE_API_END(ctx)
+}
+
+/* every i < j with popcount(hashes[i] ^ hashes[j]) <= max_distance, ascending (reference utils/duplicate.py:89-119) */
+int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, int max_distance, int64_t max_pairs, int32_t* pairs,
+                     int64_t* count) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(count && n >= 0 && (n == 0 || hashes) && max_distance >= 0 && max_pairs >= 0 && (max_pairs == 0 || pairs), "bad arguments");
+  *count = 0;
+  if (n < 2) return FE_OK;
+  C.arena.reset();
+  const uint64_t* d_h = hashes;
+  if (!on_device) {
+    uint64_t* d = (uint64_t*)C.arena.alloc((size_t)n * sizeof(uint64_t));
+    FE_HIP(hipMemcpyAsync(d, hashes, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, C.stream));
+    d_h = d;
+  }
+  // one block: pairs [max_pairs][2], then the hit counter, then a canary word. A store past the capacity would land on the counter
+  // first and on the canary next, so the kernel's own bounds check is visible from outside (exact count + intact canary).
+  const unsigned long long canary = 0xA5A5A5A5A5A5A5A5ull;
+  uint8_t* d_block = (uint8_t*)C.arena.alloc((size_t)max_pairs * 2 * sizeof(int) + 2 * sizeof(unsigned long long));
+  int* d_pairs = max_pairs ? (int*)d_block : nullptr;
+  unsigned long long* d_count = (unsigned long long*)(d_block + (size_t)max_pairs * 2 * sizeof(int));
+  FE_HIP(hipMemsetAsync(d_count + 1, 0xA5, sizeof(unsigned long long), C.stream));
+  launch_hamming_pairs(d_h, n, std::min(max_distance, 64), max_pairs, d_pairs, d_count, C.stream);
+  unsigned long long tail[2] = {0, 0};
+  FE_HIP(hipMemcpyAsync(tail, d_count, sizeof(tail), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_CHECK(tail[1] == canary, "hamming_pairs: the word after the pair buffer was overwritten");
+  const unsigned long long found = tail[0];
+  *count = (int64_t)found;
+  if (found && found <= (unsigned long long)max_pairs) {
+    FE_HIP(hipMemcpyAsync(pairs, d_pairs, (size_t)found * 2 * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    // the order of arrival is the order the waves ran in; the caller gets ascending (i, j)
+    struct P { int32_t i, j; };
+    P* p = reinterpret_cast<P*>(pairs);
+    std::sort(p, p + found, [](const P& a, const P& b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
   }
   FE_API_END(ctx)
 }

@@ -195,8 +195,19 @@ enum ResizeFilter : int { FE_FILTER_LANCZOS = 1, FE_FILTER_BILINEAR = 2, FE_FILT
 struct ResizeCoeffs { std::vector<int> kk, bounds; int ksize = 0, out = 0; };
 struct ResizeCoeffsDev { int* kk = nullptr; int* bounds = nullptr; int ksize = 0; };
 void build_resize_coeffs(int in_size, int out_size, int filter, ResizeCoeffs& rc);
+// third member of a Ctx::resize_cache key that is no PIL filter: fe_phash's tables to 32 samples (LANCZOS, or the identity for a skipped pass)
+constexpr int FE_FILTER_KEY_PHASH = -1;
+struct Ctx;
+const ResizeCoeffsDev& upload_resize_coeffs(Ctx& c, const std::tuple<int, int, int>& key, const ResizeCoeffs& rc);
 void resize_u8(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow, int filter, int y0, int ch, int x0,
                int cw, uint8_t* d_dst);
+
+// ---- perceptual hash + all-pairs Hamming search (kernels_phash.hip) ------------------------------------
+void phash_cos_table(double* out);                       // [8][32] = cos(pi k (2n+1) / 64), host
+size_t phash_tmp_bytes(int n, int h);
+void launch_phash(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, uint8_t* d_tmp, const double* d_cos, uint64_t* d_hashes,
+                  uint8_t* d_small, double* d_dct);
+void launch_hamming_pairs(const uint64_t* d_hashes, int n, int maxd, int64_t cap, int* d_pairs, unsigned long long* d_count, hipStream_t s);
 
 class Graph;   // onnx_graph.h
 struct GraphSlot;

@@ -133,12 +133,8 @@ __global__ void crop_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restr
   }
 }
 
-static const ResizeCoeffsDev& coeffs_dev(Ctx& c, int in_size, int out_size, int filter) {
-  const auto key = std::make_tuple(in_size, out_size, filter);
-  auto it = c.resize_cache.find(key);
-  if (it != c.resize_cache.end()) return it->second;
-  ResizeCoeffs rc;
-  build_resize_coeffs(in_size, out_size, filter, rc);
+// uploads a host table and parks it in the context's cache under `key`
+const ResizeCoeffsDev& upload_resize_coeffs(Ctx& c, const std::tuple<int, int, int>& key, const ResizeCoeffs& rc) {
   ResizeCoeffsDev d;
   d.ksize = rc.ksize;
   FE_HIP(hipMalloc((void**)&d.kk, rc.kk.size() * sizeof(int)));
@@ -146,6 +142,15 @@ static const ResizeCoeffsDev& coeffs_dev(Ctx& c, int in_size, int out_size, int 
   FE_HIP(hipMemcpy(d.kk, rc.kk.data(), rc.kk.size() * sizeof(int), hipMemcpyHostToDevice));
   FE_HIP(hipMemcpy(d.bounds, rc.bounds.data(), rc.bounds.size() * sizeof(int), hipMemcpyHostToDevice));
   return c.resize_cache.emplace(key, d).first->second;
+}
+
+static const ResizeCoeffsDev& coeffs_dev(Ctx& c, int in_size, int out_size, int filter) {
+  const auto key = std::make_tuple(in_size, out_size, filter);
+  auto it = c.resize_cache.find(key);
+  if (it != c.resize_cache.end()) return it->second;
+  ResizeCoeffs rc;
+  build_resize_coeffs(in_size, out_size, filter, rc);
+  return upload_resize_coeffs(c, key, rc);
 }
 
 static inline int grid_sz(size_t work) { size_t g = (work + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }

@@ -413,6 +413,26 @@ int fe_swap_rb_u8(fe_ctx* ctx, const uint8_t* src, int on_device, size_t pixels,
 int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int canny_low, int canny_high, int threshold,
                      int min_line_length, int max_line_gap, int max_lines, int* lines, int* counts, uint8_t* edges_out);
 
+/* Perceptual hash: `imagehash.phash(pil_img)` with its defaults (hash_size 8, highfreq_factor 4), which the reference stores as
+ * str(...) in the `phash` column for every image (processing/batch_processor.py:216, multi_pass.py:449, scorer.py:972):
+ * image.convert('L') ((R*19595 + G*38470 + B*7471 + 0x8000) >> 16), .resize((32, 32), LANCZOS) (PIL's two-pass 22-bit fixed-point
+ * resampler, horizontal pass first, each pass clipped to uint8, a pass skipped when its axis is already 32),
+ * scipy.fftpack.dct over axis 0 then axis 1 (unnormalised DCT-II, fp64), the top-left 8x8 block compared with its numpy.median.
+ * img [n][h][w][3] uint8 on the host (on_device = 0) or the device, read once; bgr = 1: the bytes of a pixel are B,G,R.
+ * hashes [n]: bit 63 = coefficient [0][0], row-major downwards, so the reference's string is the value as 16 lowercase hex
+ * digits. small_out [n][32][32] uint8 (nullable): the resized gray image; dct_out [n][64] doubles (nullable): the 8x8 block,
+ * row-major. A coefficient closer to the median than the rounding of the DCT (differences of up to 9e-11 from scipy were
+ * observed; the tests allow 1e-6) may fall on either side. */
+int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, uint64_t* hashes, uint8_t* small_out,
+             double* dct_out);
+
+/* Near-duplicate search over stored hashes (reference utils/duplicate.py:89-119, an O(n^2) numpy loop): every pair i < j with
+ * popcount(hashes[i] ^ hashes[j]) <= max_distance. hashes [n] on the host (on_device = 0) or the device. count receives the
+ * exact number of such pairs; pairs [max_pairs][2] (host; nullable when max_pairs = 0) receives them in ascending (i, j) order
+ * when count <= max_pairs. When count > max_pairs only count is defined - call again with more room. n < 2 gives count = 0. */
+int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, int max_distance, int64_t max_pairs, int32_t* pairs,
+                     int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif
