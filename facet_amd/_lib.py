@@ -160,6 +160,10 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
+    "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "fe_cosine_best_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -1001,6 +1005,52 @@ class Engine:
                 return pairs[:count.value].copy()
             room = count.value
         raise EngineError(f"hamming_pairs: {count.value} pairs found after making room for {room}")
+
+    @staticmethod
+    def _rows_ptr(x):
+        """x: float32 [n,d] (host array) or (device_ptr, n, d)."""
+        if isinstance(x, tuple):
+            p, n, d = x
+            return p, int(n), int(d), 1, None
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        assert a.ndim == 2
+        return a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], 0, a
+
+    def core_distances(self, x, k, normalise=True):
+        """x: float32 [n,d] (or device tuple) -> (core float64 [n], core_idx int32 [n]): distance to, and index of, the k-th nearest
+        row, the row itself counting as the first (HDBSCAN's min_samples). Rows are L2-normalised first unless normalise=False."""
+        p, n, d, dev, keep = self._rows_ptr(x)
+        core = np.empty((n,), np.float64)
+        idx = np.empty((n,), np.int32)
+        self._ck(self.lib.fe_knn_core_distances(self.h, p, n, d, dev, 1 if normalise else 0, int(k), core.ctypes.data_as(C.c_void_p),
+                                                idx.ctypes.data_as(C.c_void_p)))
+        return core, idx
+
+    def mreach_mst(self, x, k, normalise=True):
+        """x: float32 [n,d] (or device tuple) -> (edge_u int32 [n-1], edge_v int32 [n-1], edge_w float64 [n-1], core float64 [n],
+        rounds): the minimum spanning tree of the mutual-reachability graph max(core_u, core_v, |x_u - x_v|) with k = min_samples."""
+        p, n, d, dev, keep = self._rows_ptr(x)
+        m = max(n - 1, 0)
+        eu, ev = np.empty((m,), np.int32), np.empty((m,), np.int32)
+        ew = np.empty((m,), np.float64)
+        core = np.empty((n,), np.float64)
+        rounds = C.c_int32(0)
+        self._ck(self.lib.fe_mreach_mst(self.h, p, n, d, dev, 1 if normalise else 0, int(k), eu.ctypes.data_as(C.c_void_p),
+                                        ev.ctypes.data_as(C.c_void_p), ew.ctypes.data_as(C.c_void_p), core.ctypes.data_as(C.c_void_p),
+                                        C.cast(C.byref(rounds), C.c_void_p)))
+        return eu, ev, ew, core, int(rounds.value)
+
+    def cosine_best_match(self, queries, candidates):
+        """float32 [nq,d], [nc,d] (host) -> (best_sim float32 [nq], best_idx int32 [nq]): for every query the candidate of largest
+        cosine similarity, the first among equals. Both sides are L2-normalised inside."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        c = np.ascontiguousarray(candidates, dtype=np.float32)
+        assert q.ndim == 2 and c.ndim == 2 and q.shape[1] == c.shape[1]
+        sim = np.empty((q.shape[0],), np.float32)
+        idx = np.empty((q.shape[0],), np.int32)
+        self._ck(self.lib.fe_cosine_best_match(self.h, q.ctypes.data_as(C.c_void_p), q.shape[0], c.ctypes.data_as(C.c_void_p), c.shape[0],
+                                               q.shape[1], sim.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
+        return sim, idx
 
     def cv_resize_linear(self, imgs, oh, ow):
         a = np.ascontiguousarray(imgs, dtype=np.uint8)

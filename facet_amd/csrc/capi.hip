@@ -2411,4 +2411,45 @@ int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, 
   FE_API_END(ctx)
 }
 
+/* shapes the clustering sweeps accept; anything else is FE_ERR_INVALID with a message, never a launch */
+static bool cluster_shape_ok(fe_ctx* ctx, const char* who, int n, int n_min, int d) {
+  char b[160];
+  if (n < n_min || n > 262144) { snprintf(b, sizeof(b), "%s: %d rows (supported: %d .. 262144)", who, n, n_min); ctx->c.err = b; return false; }
+  if (d < 32 || d > 1024 || d % 32 != 0) { snprintf(b, sizeof(b), "%s: d = %d (supported: multiples of 32 in 32 .. 1024)", who, d); ctx->c.err = b; return false; }
+  return true;
+}
+static bool cluster_k_ok(fe_ctx* ctx, const char* who, int n, int k) {
+  char b[160];
+  if (k < 1 || k > 32 || k > n) { snprintf(b, sizeof(b), "%s: k = %d (supported: 1 .. min(32, n = %d))", who, k, n); ctx->c.err = b; return false; }
+  return true;
+}
+
+/* core distance (distance to the k-th nearest row, the row itself counted) of every row: HDBSCAN's first stage (reference faces/clusterer.py:188-197) */
+int fe_knn_core_distances(fe_ctx* ctx, const float* x, int n, int d, int on_device, int normalise, int k, double* core, int32_t* core_idx) {
+  FE_API_BEGIN(ctx)
+  if (!x || !core) { ctx->c.err = "fe_knn_core_distances: null pointer"; return FE_ERR_INVALID; }
+  if (!cluster_shape_ok(ctx, "fe_knn_core_distances", n, 2, d) || !cluster_k_ok(ctx, "fe_knn_core_distances", n, k)) return FE_ERR_INVALID;
+  cluster_core_distances(ctx->c, x, n, d, on_device, normalise, k, core, core_idx);
+  FE_API_END(ctx)
+}
+
+/* minimum spanning tree of the mutual-reachability graph: HDBSCAN's second stage (reference faces/clusterer.py:188-197) */
+int fe_mreach_mst(fe_ctx* ctx, const float* x, int n, int d, int on_device, int normalise, int k, int32_t* edge_u, int32_t* edge_v, double* edge_w,
+                  double* core, int32_t* rounds) {
+  FE_API_BEGIN(ctx)
+  if (!x || !edge_u || !edge_v || !edge_w) { ctx->c.err = "fe_mreach_mst: null pointer"; return FE_ERR_INVALID; }
+  if (!cluster_shape_ok(ctx, "fe_mreach_mst", n, 2, d) || !cluster_k_ok(ctx, "fe_mreach_mst", n, k)) return FE_ERR_INVALID;
+  cluster_mreach_mst(ctx->c, x, n, d, on_device, normalise, k, edge_u, edge_v, edge_w, core, rounds);
+  FE_API_END(ctx)
+}
+
+/* best cosine match of every query row among the candidate rows (reference faces/clusterer.py:399-405, :508-518) */
+int fe_cosine_best_match(fe_ctx* ctx, const float* q, int nq, const float* c, int nc, int d, float* best_sim, int32_t* best_idx) {
+  FE_API_BEGIN(ctx)
+  if (!q || !c || !best_sim || !best_idx) { ctx->c.err = "fe_cosine_best_match: null pointer"; return FE_ERR_INVALID; }
+  if (!cluster_shape_ok(ctx, "fe_cosine_best_match", nq, 1, d) || !cluster_shape_ok(ctx, "fe_cosine_best_match", nc, 1, d)) return FE_ERR_INVALID;
+  cluster_best_match(ctx->c, q, nq, c, nc, d, best_sim, best_idx);
+  FE_API_END(ctx)
+}
+
 }  // extern "C"

@@ -209,6 +209,13 @@ void launch_phash(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, ui
                   uint8_t* d_small, double* d_dct);
 void launch_hamming_pairs(const uint64_t* d_hashes, int n, int maxd, int64_t cap, int* d_pairs, unsigned long long* d_count, hipStream_t s);
 
+// ---- face clustering sweeps: core distances, mutual-reachability MST, best cosine match (kernels_cluster.hip) ----
+int cluster_max_rounds(int n);                           // ceil(log2 n) + 1: the Boruvka round bound
+void cluster_core_distances(Ctx& c, const float* x, int n, int d, int on_device, int normalise, int k, double* core, int32_t* core_idx);
+void cluster_mreach_mst(Ctx& c, const float* x, int n, int d, int on_device, int normalise, int k, int32_t* edge_u, int32_t* edge_v,
+                        double* edge_w, double* core, int32_t* rounds_out);
+void cluster_best_match(Ctx& c, const float* q, int nq, const float* cc, int nc, int d, float* best_sim, int32_t* best_idx);
+
 class Graph;   // onnx_graph.h
 struct GraphSlot;
 

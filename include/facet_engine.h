@@ -433,6 +433,34 @@ int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int 
 int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, int max_distance, int64_t max_pairs, int32_t* pairs,
                      int64_t* count);
 
+/* Face clustering (reference faces/clusterer.py): `FaceClusterer.cluster_faces` L2-normalises the stored ArcFace embeddings
+ * (:157-158) and runs HDBSCAN on them (:188-197 with the `hdbscan` package's approximate boruvka_balltree, or cuML on an NVIDIA GPU
+ * :167-181). The three calls below are the O(n^2 d) parts as exact sweeps on the fp32 matrix cores; the n x n matrix is never
+ * stored. The tree condensing and the person bookkeeping are host code (facet_amd/face_cluster.py).
+ * Common: x [n][d] fp32 rows on the host (on_device = 0) or the device; 2 <= n <= 262144, d a multiple of 32 in 32 .. 1024;
+ * normalise = 1: rows become x / (|x| + 1e-10) in fp32 first (clusterer.py:158), 0: rows are used as they are (unit length
+ * expected). Anything else returns FE_ERR_INVALID. Squared distances are swept as |a|^2 + |b|^2 - 2 a.b (>= 0) in fp32; every
+ * distance that is RETURNED is recomputed from direct differences in fp64, so only the choice of a neighbour or an edge rests on the
+ * swept value (error below 2 d 2^-24 for unit rows).
+ *
+ * fe_knn_core_distances: core [n] = distance to the k-th nearest row, the row itself being the first (1 <= k <= min(32, n)), as
+ * `hdbscan` and sklearn.cluster.HDBSCAN define min_samples; core_idx [n] (nullable) = that neighbour. */
+int fe_knn_core_distances(fe_ctx* ctx, const float* x, int n, int d, int on_device, int normalise, int k, double* core,
+                          int32_t* core_idx);
+
+/* fe_mreach_mst: minimum spanning tree of the mutual-reachability graph mr(i, j) = max(core_i, core_j, |x_i - x_j|) by Boruvka
+ * rounds: every row's lightest edge to another component comes from one sweep, edges are ordered by (fp32 bits of the swept mr^2,
+ * min(i, j), max(i, j)) - one value from both ends, so no round closes a cycle. edge_u / edge_v / edge_w [n - 1] (host): the edges
+ * (u < v) in the order they were accepted, edge_w = max(core_u, core_v, exact distance). core [n] (nullable): as above. rounds
+ * (nullable): sweeps used, at most ceil(log2 n) + 1 - more is an error. The same input gives the same bytes on every run. */
+int fe_mreach_mst(fe_ctx* ctx, const float* x, int n, int d, int on_device, int normalise, int k, int32_t* edge_u, int32_t* edge_v,
+                  double* edge_w, double* core, int32_t* rounds);
+
+/* fe_cosine_best_match: for every query row the candidate row of largest cosine similarity (the centroid loops of
+ * clusterer.py:399-405 and :508-518). q [nq][d], c [nc][d] on the host, 1 <= nq, nc <= 262144; both are normalised inside.
+ * best_sim [nq] fp32, best_idx [nq]: the first candidate among equals. Thresholds stay with the caller. */
+int fe_cosine_best_match(fe_ctx* ctx, const float* q, int nq, const float* c, int nc, int d, float* best_sim, int32_t* best_idx);
+
 #ifdef __cplusplus
 }
 #endif
