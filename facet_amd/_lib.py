@@ -164,7 +164,69 @@ SIGNATURES = {
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
     "fe_cosine_best_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fe_similar_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p]),
+    "fe_similar_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_int64, C.c_void_p, C.c_void_p, _i64p]),
 }
+
+FE_SIM_FUSED, FE_SIM_COSINE = 0, 1
+FE_SIM_K_MAX = 32
+FE_SIM_NO_DATE = -(1 << 63)
+
+
+class _SimRowsC(C.Structure):
+    """fe_sim_rows of include/facet_engine.h"""
+    _fields_ = [("emb", C.c_void_p), ("n", C.c_int32), ("on_device", C.c_int32), ("normalise", C.c_int32), ("n_person_ids", C.c_int32),
+                ("has_emb", C.c_void_p), ("date", C.c_void_p), ("aggregate", C.c_void_p), ("person_off", C.c_void_p), ("person_ids", C.c_void_p)]
+
+
+class SimRows:
+    """One side (queries or candidates) of Engine.similar_topk / similar_pairs: embeddings plus the optional per-row metadata of the
+    fused score. Host form: emb float32 [n,d]; has_emb uint8 [n]; date int64 [n] seconds (FE_SIM_NO_DATE = absent); aggregate float32
+    [n] (0 / NaN = absent); person_off int32 [n+1] and person_ids int32 (CSR, ascending and unique per row). Engine.upload_sim_rows
+    gives the resident form, in which emb is a (device_ptr, n, d) tuple and the other fields are device pointers."""
+    FIELDS = (("has_emb", np.uint8), ("date", np.int64), ("aggregate", np.float32), ("person_off", np.int32), ("person_ids", np.int32))
+
+    def __init__(self, emb, has_emb=None, date=None, aggregate=None, person_off=None, person_ids=None, normalise=True):
+        self.on_device = isinstance(emb, tuple)
+        self.normalise = bool(normalise)
+        self.keep = None                                  # whatever owns the device memory
+        self.n_person_ids = 0
+        if self.on_device:
+            self.emb = (int(emb[0]), int(emb[1]), int(emb[2]))
+            self.n, self.d = self.emb[1], self.emb[2]
+            self.has_emb, self.date, self.aggregate, self.person_off = has_emb, date, aggregate, person_off
+            if person_ids is not None:
+                self.person_ids, self.n_person_ids = int(person_ids[0]), int(person_ids[1])   # (device_ptr, count)
+            else:
+                self.person_ids = None
+        else:
+            self.emb = np.ascontiguousarray(emb, dtype=np.float32)
+            if self.emb.ndim != 2:
+                raise ValueError("emb must be [n, d]")
+            self.n, self.d = self.emb.shape
+            given = dict(has_emb=has_emb, date=date, aggregate=aggregate, person_off=person_off, person_ids=person_ids)
+            for name, dt in self.FIELDS:
+                v = given[name]
+                v = None if v is None else np.ascontiguousarray(v, dtype=dt).reshape(-1)
+                want = {"person_off": self.n + 1, "person_ids": None}.get(name, self.n)
+                if v is not None and want is not None and v.shape[0] != want:
+                    raise ValueError(f"{name}: {v.shape[0]} entries for {self.n} rows")
+                setattr(self, name, v)
+            if (self.person_off is None) != (self.person_ids is None):
+                raise ValueError("person_off and person_ids go together")
+            if self.person_ids is not None:
+                self.n_person_ids = int(self.person_ids.shape[0])
+
+    def c_struct(self):
+        def ptr(v):
+            if v is None:
+                return None
+            return int(v) if self.on_device else v.ctypes.data
+        emb = self.emb[0] if self.on_device else self.emb.ctypes.data
+        return _SimRowsC(emb, self.n, 1 if self.on_device else 0, 1 if self.normalise else 0, self.n_person_ids, ptr(self.has_emb),
+                         ptr(self.date), ptr(self.aggregate), ptr(self.person_off), ptr(self.person_ids))
 
 
 def _share_hip_runtime_with_torch():
@@ -1051,6 +1113,93 @@ class Engine:
         self._ck(self.lib.fe_cosine_best_match(self.h, q.ctypes.data_as(C.c_void_p), q.shape[0], c.ctypes.data_as(C.c_void_p), c.shape[0],
                                                q.shape[1], sim.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
         return sim, idx
+
+    # -- similar photos / merge suggestions --------------------------------------------------
+    @staticmethod
+    def _sim_rows(x):
+        return x if isinstance(x, SimRows) else SimRows(x)
+
+    def upload_sim_rows(self, rows):
+        """SimRows on the host -> the same rows resident on this engine's GPU (torch owns the memory; the result keeps it alive).
+        Upload a library once and pass the result to any number of similar_topk / similar_pairs calls."""
+        import torch
+        rows = self._sim_rows(rows)
+        if rows.on_device:
+            return rows
+        dev = torch.device("cuda", int(self.device))
+        keep = {"emb": torch.from_numpy(rows.emb).to(dev)}
+        for name, _ in SimRows.FIELDS:
+            v = getattr(rows, name)
+            if v is not None and v.shape[0]:
+                keep[name] = torch.from_numpy(v).to(dev)
+        torch.cuda.synchronize(dev)
+        p = {k: t.data_ptr() for k, t in keep.items()}
+        has_ids = "person_ids" in p
+        out = SimRows((p["emb"], rows.n, rows.d), p.get("has_emb"), p.get("date"), p.get("aggregate"), p.get("person_off") if has_ids else None,
+                      (p["person_ids"], rows.n_person_ids) if has_ids else None, normalise=rows.normalise)
+        out.keep = keep
+        return out
+
+    def _sim_args(self, queries, candidates, weights, cosine, q_self, visible):
+        q, c = self._sim_rows(queries), self._sim_rows(candidates)
+        if q.d != c.d:
+            raise ValueError(f"queries have d = {q.d}, candidates d = {c.d}")
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if w.shape[0] != 4:
+            raise ValueError("weights = (clip, person, date, score)")
+        qs = None if q_self is None else np.ascontiguousarray(q_self, dtype=np.int32).reshape(-1)
+        vis = None if visible is None else np.ascontiguousarray(visible, dtype=np.uint8).reshape(-1)
+        if qs is not None and qs.shape[0] != q.n:
+            raise ValueError("q_self: one entry per query")
+        if vis is not None and vis.shape[0] != c.n:
+            raise ValueError("visible: one entry per candidate")
+        qc, cc = q.c_struct(), (None if candidates is queries else c.c_struct())
+        cc = qc if cc is None else cc
+        head = (self.h, C.cast(C.byref(qc), C.c_void_p), C.cast(C.byref(cc), C.c_void_p), q.d, FE_SIM_COSINE if cosine else FE_SIM_FUSED,
+                w.ctypes.data_as(C.c_void_p), None if qs is None else qs.ctypes.data_as(C.c_void_p),
+                None if vis is None else vis.ctypes.data_as(C.c_void_p))
+        return q, c, head, (q, c, qc, cc, w, qs, vis)
+
+    def similar_topk(self, queries, candidates, k, weights=(0.4, 0.3, 0.2, 0.1), cosine=False, q_self=None, visible=None):
+        """queries / candidates: SimRows (host or resident), or plain float32 [n,d] rows / (device_ptr, n, d). -> (idx int32 [nq,k],
+        score float32 [nq,k]): per query the k best candidates by the fused "similar photos" score (or the plain cosine), score
+        descending, candidate index ascending among equals, -1 / 0 padded. q_self int [nq]: the candidate index of the query itself
+        (-1: none), visible uint8 [n]: candidates with 0 are skipped. 1 <= k <= FE_SIM_K_MAX."""
+        q, c, head, keep = self._sim_args(queries, candidates, weights, cosine, q_self, visible)
+        idx = np.empty((q.n, int(k)), np.int32)
+        score = np.empty((q.n, int(k)), np.float32)
+        self._ck(self.lib.fe_similar_topk(*head, int(k), idx.ctypes.data_as(C.c_void_p), score.ctypes.data_as(C.c_void_p)))
+        return idx, score
+
+    def similar_pairs(self, queries, candidates, thr, weights=(0.4, 0.3, 0.2, 0.1), cosine=False, q_self=None, visible=None, upper=False,
+                      max_pairs=None):
+        """-> (pairs int32 [m,2] = (query, candidate), score float32 [m]) in ascending (query, candidate) order: every pair whose
+        score is >= thr (one value, or one per query); upper=True (queries is candidates): candidate > query only. max_pairs: room
+        for the first attempt (default max(1024, 4 (nq + n))); when there are more the call is repeated once with exactly enough."""
+        q, c, head, keep = self._sim_args(queries, candidates, weights, cosine, q_self, visible)
+        t = np.ascontiguousarray(thr, dtype=np.float32).reshape(-1)
+        room = int(max_pairs) if max_pairs is not None else max(1024, 4 * (q.n + c.n))
+        count = C.c_int64(0)
+        for _ in range(2):
+            pairs = np.empty((room, 2), np.int32)
+            score = np.empty((room,), np.float32)
+            self._ck(self.lib.fe_similar_pairs(*head, t.ctypes.data_as(C.c_void_p), t.shape[0], 1 if upper else 0, room,
+                                               pairs.ctypes.data_as(C.c_void_p) if room else None,
+                                               score.ctypes.data_as(C.c_void_p) if room else None, C.byref(count)))
+            if count.value <= room:
+                return pairs[:count.value].copy(), score[:count.value].copy()
+            room = count.value
+        raise EngineError(f"similar_pairs: {count.value} pairs found after making room for {room}")
+
+    def similar_pairs_count(self, queries, candidates, thr, **kw):
+        """The exact number of pairs similar_pairs would return, without fetching them."""
+        q, c, head, keep = self._sim_args(queries, candidates, kw.get("weights", (0.4, 0.3, 0.2, 0.1)), kw.get("cosine", False), kw.get("q_self"),
+                                          kw.get("visible"))
+        t = np.ascontiguousarray(thr, dtype=np.float32).reshape(-1)
+        count = C.c_int64(0)
+        self._ck(self.lib.fe_similar_pairs(*head, t.ctypes.data_as(C.c_void_p), t.shape[0], 1 if kw.get("upper") else 0, 0, None, None,
+                                           C.byref(count)))
+        return int(count.value)
 
     def cv_resize_linear(self, imgs, oh, ow):
         a = np.ascontiguousarray(imgs, dtype=np.uint8)

@@ -2452,4 +2452,45 @@ int fe_cosine_best_match(fe_ctx* ctx, const float* q, int nq, const float* c, in
   FE_API_END(ctx)
 }
 
+/* one side of fe_similar_topk / fe_similar_pairs */
+static bool sim_rows_ok(fe_ctx* ctx, const char* who, const fe_sim_rows* r, int d) {
+  char b[200];
+  if (!r || !r->emb) { snprintf(b, sizeof(b), "%s: null rows", who); ctx->c.err = b; return false; }
+  if (!cluster_shape_ok(ctx, who, r->n, 1, d)) return false;
+  if (r->n_person_ids < 0 || ((r->person_off == nullptr) != (r->person_ids == nullptr) && r->n_person_ids > 0)) {
+    snprintf(b, sizeof(b), "%s: person_off and person_ids go together (n_person_ids = %d)", who, r->n_person_ids); ctx->c.err = b; return false;
+  }
+  return true;
+}
+static bool sim_common_ok(fe_ctx* ctx, const char* who, const fe_sim_rows* q, const fe_sim_rows* c, int d, int kind, const float* weights) {
+  if (!sim_rows_ok(ctx, who, q, d) || !sim_rows_ok(ctx, who, c, d)) return false;
+  if (kind != FE_SIM_FUSED && kind != FE_SIM_COSINE) { ctx->c.err = std::string(who) + ": score_kind must be FE_SIM_FUSED or FE_SIM_COSINE"; return false; }
+  if (kind == FE_SIM_FUSED && !weights) { ctx->c.err = std::string(who) + ": the fused score needs weights [4]"; return false; }
+  return true;
+}
+
+/* top-k similar candidates per query (reference api/routers/gallery.py:410-539) */
+int fe_similar_topk(fe_ctx* ctx, const fe_sim_rows* q, const fe_sim_rows* c, int d, int score_kind, const float* weights, const int32_t* q_self,
+                    const uint8_t* visible, int k, int32_t* idx, float* score) {
+  FE_API_BEGIN(ctx)
+  if (!idx || !score) { ctx->c.err = "fe_similar_topk: null pointer"; return FE_ERR_INVALID; }
+  if (!sim_common_ok(ctx, "fe_similar_topk", q, c, d, score_kind, weights)) return FE_ERR_INVALID;
+  if (k < 1 || k > FE_SIM_K_MAX) { char b[120]; snprintf(b, sizeof(b), "fe_similar_topk: k = %d (supported: 1 .. %d)", k, FE_SIM_K_MAX); ctx->c.err = b; return FE_ERR_INVALID; }
+  similar_topk(ctx->c, *q, *c, d, score_kind == FE_SIM_COSINE, weights, q_self, visible, k, idx, score);
+  FE_API_END(ctx)
+}
+
+/* every (query, candidate) at or above a threshold (similar photos' tie sets; reference faces/merge_analyzer.py:64-72) */
+int fe_similar_pairs(fe_ctx* ctx, const fe_sim_rows* q, const fe_sim_rows* c, int d, int score_kind, const float* weights, const int32_t* q_self,
+                     const uint8_t* visible, const float* thr, int n_thr, int upper, int64_t max_pairs, int32_t* pairs, float* scores, int64_t* count) {
+  FE_API_BEGIN(ctx)
+  if (!count || !thr || max_pairs < 0 || (max_pairs > 0 && (!pairs || !scores))) { ctx->c.err = "fe_similar_pairs: null pointer or negative max_pairs"; return FE_ERR_INVALID; }
+  if (!sim_common_ok(ctx, "fe_similar_pairs", q, c, d, score_kind, weights)) return FE_ERR_INVALID;
+  if (n_thr != 1 && n_thr != q->n) { ctx->c.err = "fe_similar_pairs: n_thr must be 1 or the number of queries"; return FE_ERR_INVALID; }
+  if (upper && q->n != c->n) { ctx->c.err = "fe_similar_pairs: upper = 1 needs as many queries as candidates"; return FE_ERR_INVALID; }
+  *count = 0;
+  similar_pairs(ctx->c, *q, *c, d, score_kind == FE_SIM_COSINE, weights, q_self, visible, thr, n_thr, upper, max_pairs, pairs, scores, count);
+  FE_API_END(ctx)
+}
+
 }  // extern "C"

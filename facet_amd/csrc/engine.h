@@ -1,6 +1,7 @@
 // Engine-side runtime: context, weight store, layer builders and the model graphs of the hot path.
 #pragma once
 #include "fe_common.h"
+#include "../../include/facet_engine.h"   // fe_sim_rows
 #include <memory>
 #include <tuple>
 
@@ -215,6 +216,11 @@ void cluster_core_distances(Ctx& c, const float* x, int n, int d, int on_device,
 void cluster_mreach_mst(Ctx& c, const float* x, int n, int d, int on_device, int normalise, int k, int32_t* edge_u, int32_t* edge_v,
                         double* edge_w, double* core, int32_t* rounds_out);
 void cluster_best_match(Ctx& c, const float* q, int nq, const float* cc, int nc, int d, float* best_sim, int32_t* best_idx);
+// ---- similar photos / merge suggestions: two more epilogues of the same sweep (kernels_cluster.hip; arguments as fe_similar_topk / fe_similar_pairs) ----
+void similar_topk(Ctx& c, const fe_sim_rows& q, const fe_sim_rows& cand, int d, int cosine, const float* w, const int32_t* q_self, const uint8_t* visible,
+                  int k, int32_t* idx, float* score);
+void similar_pairs(Ctx& c, const fe_sim_rows& q, const fe_sim_rows& cand, int d, int cosine, const float* w, const int32_t* q_self, const uint8_t* visible,
+                   const float* thr, int n_thr, int upper, int64_t max_pairs, int32_t* pairs, float* scores, int64_t* count);
 
 class Graph;   // onnx_graph.h
 struct GraphSlot;

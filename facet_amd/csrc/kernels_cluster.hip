@@ -30,6 +30,18 @@
 //               full triple needs 32 + 18 + 18 bits, so the minimum per component and the union-find run on the host over the n row
 //               keys (8 n bytes per round); rounds are bounded by ceil(log2 n) + 1.
 //   CL_MATCH:   rows of Q against rows of C, both normalised: largest dot product, first column on ties.
+//
+// Similar-photo search and person-merge suggestions (reference api/routers/gallery.py:410-539, faces/merge_analyzer.py:29-187) are two
+// more epilogues of the same tile core, rows = queries, columns = candidates, both normalised so that the dot product is the cosine:
+//   SIM_TOPK:   score = sim_score() (the reference's four weighted factors in fp32, or the plain cosine); the scanning thread keeps its
+//               k best (cl_sim_key(score) << 32 | column) keys in the same sorted LDS lists as CL_KNN - ascending keys are (score
+//               descending, column ascending) - and sim_merge_kernel merges the 2 x strips lists of a query into idx / score [k].
+//   SIM_PAIRS:  every (query, column) with score >= thr[query] is appended to a capacity-checked triple buffer under one counter
+//               (the fe_hamming_pairs protocol: the count is exact, a store happens only below the capacity); with `upper` only
+//               column > row, and the column tiles left of the diagonal are not formed at all.
+//   sim_gemv_kernel: for at most SIM_GEMV_Q queries the sweep is a read of C, not a GEMM - a 128-row tile would spend 128 / nq times
+//               the matrix work on zero rows. One wave per candidate row: the row is read once (float4 per lane), dotted with every
+//               query row held in LDS, lane q evaluates sim_score() for query q and feeds the same list / triple outputs.
 #include "engine.h"
 #include <algorithm>
 #include <cmath>
@@ -46,8 +58,32 @@ constexpr int CL_ES = CL_T + 2;                        // row stride of the epil
 constexpr int CL_STAGE = 2 * 2 * CL_T * CL_S;          // floats: [2 buffers][A | B][128][36]
 constexpr int CL_META = 3 * CL_T;                      // per column of the tile: |b|^2, core^2, component
 static_assert(CL_T * CL_ES <= CL_STAGE, "the epilogue image must fit in the staging buffers");
-enum : int { CL_KNN = 0, CL_BORUVKA = 1, CL_MATCH = 2 };
+enum : int { CL_KNN = 0, CL_BORUVKA = 1, CL_MATCH = 2, SIM_TOPK = 3, SIM_PAIRS = 4 };
 constexpr unsigned long long CL_NONE = ~0ull;
+constexpr int SIM_META = 6 * CL_T;                     // floats, per column of the tile: date (8 B), aggregate, person start, person count, eligible
+constexpr int SIM_K_MAX = 32;                          // 72 KB staging + 4.5 KB metadata + k x 2 KB lists <= 160 KB of LDS: 41 would fit, 32 matches CL_KNN
+constexpr int SIM_GEMV_Q = 8;                          // queries up to which the sweep is the one-wave-per-candidate read
+constexpr long long SIM_NO_DATE = (long long)0x8000000000000000ull;   // FE_SIM_NO_DATE
+static_assert(SIM_K_MAX == FE_SIM_K_MAX, "the header's K_MAX is the kernel's");
+
+// per-row metadata of one side of a similarity sweep: device pointers, any of them null (= absent for every row)
+struct SimSide {
+  const unsigned char* has_emb;           // [n]
+  const long long* date;                  // [n] seconds, SIM_NO_DATE = absent
+  const float* agg;                       // [n], 0 / NaN = absent
+  const int* poff; const int* pid;        // CSR person lists: ids of row r are pid [poff[r] .. poff[r + 1]), ascending, unique
+  int npid;
+};
+struct SimParams {
+  SimSide q, c;
+  const int* q_self;                      // [nq] candidate index of the query itself, -1: none (nullable)
+  const unsigned char* visible;           // [nc] (nullable)
+  float wc, wp, wd, ws;
+  int cosine, upper;
+  const float* thr; int thr_stride;       // PAIRS: thr [row * thr_stride]
+  unsigned long long cap;                 // PAIRS: room in pairs / pscore
+  int* pairs; float* pscore; unsigned long long* count;
+};
 
 struct SweepParams {
   const float* a; int na;                 // rows    [na][d]
@@ -57,6 +93,7 @@ struct SweepParams {
   const float* core2; const int* comp;    // BORUVKA: fp32 core distance squared, component id, per point
   int k; unsigned long long* part;        // KNN: part [na][2 * strips][k]
   unsigned long long* rowkey;             // BORUVKA, MATCH: [na], preset to CL_NONE
+  SimParams sim;                          // SIM_TOPK (with k, part), SIM_PAIRS
 };
 
 // sim -> 32 bits that DEcrease as sim grows, so that atomicMin finds the largest similarity and, among equals, the first column
@@ -72,6 +109,67 @@ static inline float cl_sim_from_key(uint32_t k) {
   return f;
 }
 
+// what a scanning thread (tile path) or lane (gemv path) knows about its query
+struct SimRow { int emb; long long date; float agg; int p0, pn, self; float thr; };
+
+__device__ __forceinline__ void sim_person_range(const SimSide& s, int row, int& p0, int& pn) {
+  p0 = 0; pn = 0;
+  if (!s.poff || !s.pid) return;
+  const int a = min(max(s.poff[row], 0), s.npid), b = min(max(s.poff[row + 1], a), s.npid);   // the clamp only guards the loads
+  p0 = a; pn = b - a;
+}
+__device__ __forceinline__ SimRow sim_load_row(const SimParams& sp, int row, bool valid) {
+  SimRow q{1, SIM_NO_DATE, 0.f, 0, 0, -1, 0.f};
+  if (!valid) return q;
+  if (sp.q.has_emb) q.emb = sp.q.has_emb[row] ? 1 : 0;
+  if (sp.q.date) q.date = sp.q.date[row];
+  if (sp.q.agg) q.agg = sp.q.agg[row];
+  sim_person_range(sp.q, row, q.p0, q.pn);
+  if (sp.q_self) q.self = sp.q_self[row];
+  if (sp.thr) q.thr = sp.thr[(size_t)row * sp.thr_stride];
+  return q;
+}
+__device__ __forceinline__ bool sim_agg_present(float a) { return a == a && a != 0.f; }
+
+// the score of (query, candidate) from their cosine: the one epilogue function of the tile path and the gemv path.
+//   wc (cos + 1) / 2 [query has an embedding] + wp |Pq n Pc| / max(|Pq|, |Pc|) [both non-empty]
+//   + wd D(|floor((tq - tc) / 86400)|) [both dated] + ws max(0, 1 - |aq - ac| / 10) [both aggregates present and non-zero]
+// every operation is one fp32 rounding (-ffp-contract=off): facet_amd/similar.py derives the error bound from this sequence.
+__device__ __forceinline__ float sim_score(const SimParams& sp, const SimRow& q, long long cdate, float cagg, int cp0, int cpn, float cosv) {
+  if (sp.cosine) return cosv;
+  float s = 0.f;
+  if (q.emb) s = sp.wc * ((cosv + 1.f) * 0.5f);
+  if (q.pn > 0 && cpn > 0) {
+    int i = 0, j = 0, shared = 0;
+    while (i < q.pn && j < cpn) {
+      const int a = sp.q.pid[q.p0 + i], b = sp.c.pid[cp0 + j];
+      shared += a == b ? 1 : 0;
+      i += a <= b ? 1 : 0;
+      j += b <= a ? 1 : 0;
+    }
+    s += sp.wp * ((float)shared / (float)max(q.pn, cpn));
+  }
+  if (q.date != SIM_NO_DATE && cdate != SIM_NO_DATE) {
+    // the reference takes abs((t_q - t_c).days): the SIGNED difference is floored to whole days first, so a candidate 30 days and one
+    // second after the query is 31 days away, one 30 days and one second before it 30 (gallery.py:491)
+    const long long diff = q.date - cdate;
+    long long whole = diff / 86400;
+    if (diff % 86400 != 0 && diff < 0) --whole;
+    const long long days = whole < 0 ? -whole : whole;
+    const float dsim = days == 0 ? 1.f : days <= 7 ? 0.5f : days <= 30 ? 0.2f : fmaxf(0.f, 1.f - (float)days / 365.f);
+    s += sp.wd * dsim;
+  }
+  if (sim_agg_present(q.agg) && sim_agg_present(cagg)) s += sp.ws * fmaxf(0.f, 1.f - fabsf(q.agg - cagg) / 10.f);
+  return s;
+}
+// fused scores keep only s > 0 (the reference's `if total_similarity > 0`), a NaN is never kept
+__device__ __forceinline__ bool sim_keep(const SimParams& sp, float s) { return sp.cosine ? s == s : s > 0.f; }
+
+__device__ __forceinline__ void sim_emit(const SimParams& sp, int row, int col, float s) {
+  const unsigned long long at = atomicAdd(sp.count, 1ull);
+  if (at < sp.cap) { sp.pairs[2 * at] = row; sp.pairs[2 * at + 1] = col; sp.pscore[at] = s; }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
   extern __shared__ __attribute__((aligned(16))) float cl_lds[];
@@ -81,7 +179,14 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
   float* cn2 = cl_lds + CL_STAGE;
   float* ccore = cn2 + CL_T;
   int* ccomp = reinterpret_cast<int*>(ccore + CL_T);
-  unsigned long long* lists = reinterpret_cast<unsigned long long*>(cl_lds + CL_STAGE + CL_META);   // KNN: [k][256]
+  constexpr bool SIM = MODE == SIM_TOPK || MODE == SIM_PAIRS;
+  constexpr bool LISTS = MODE == CL_KNN || MODE == SIM_TOPK;
+  long long* sdate = reinterpret_cast<long long*>(cl_lds + CL_STAGE + CL_META);                    // SIM: the tile's column metadata
+  float* sagg = cl_lds + CL_STAGE + CL_META + 2 * CL_T;
+  int* sp0 = reinterpret_cast<int*>(sagg + CL_T);
+  int* spn = sp0 + CL_T;
+  int* sok = spn + CL_T;
+  unsigned long long* lists = reinterpret_cast<unsigned long long*>(cl_lds + CL_STAGE + CL_META + (SIM ? SIM_META : 0));   // KNN, SIM_TOPK: [k][256]
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
@@ -95,10 +200,12 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
   const bool rvalid = grow < p.na;
   float rn2 = 0.f, rcore = 0.f;
   int rcomp = 0;
-  if (MODE != CL_MATCH && rvalid) rn2 = p.n2a[grow];
+  if (MODE != CL_MATCH && !SIM && rvalid) rn2 = p.n2a[grow];
+  SimRow qrow{};
+  if (SIM) qrow = sim_load_row(p.sim, grow, rvalid);
   if (MODE == CL_BORUVKA && rvalid) { rcore = p.core2[grow]; rcomp = p.comp[grow]; }
   unsigned long long best = CL_NONE;                    // BORUVKA / MATCH; KNN: the list's last (k-th) key
-  if (MODE == CL_KNN)
+  if (LISTS)
     for (int s = 0; s < p.k; ++s) lists[s * 256 + t] = CL_NONE;
 
   const float* arow[4];
@@ -112,6 +219,7 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
 
   for (int tj = blockIdx.y; tj < p.tiles_b; tj += gridDim.y) {
     const int col0 = tj * CL_T;
+    if (MODE == SIM_PAIRS && p.sim.upper && tj < (int)blockIdx.x) continue;   // block-uniform: the tile lies left of the diagonal
     const float* brow[4];
     bool bval[4];
 #pragma unroll
@@ -181,7 +289,17 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
 #pragma unroll
         for (int e = 0; e < 16; ++e)
           E[(wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * CL_ES + wn * 64 + j * 32 + r] = acc[i][j][e];
-    if (MODE != CL_MATCH && t < CL_T) {
+    if (SIM && t < CL_T) {
+      const int c = col0 + t;
+      const bool ok = c < p.nb && (!p.sim.visible || p.sim.visible[c]);
+      sok[t] = ok ? 1 : 0;
+      sdate[t] = ok && p.sim.c.date ? p.sim.c.date[c] : SIM_NO_DATE;
+      sagg[t] = ok && p.sim.c.agg ? p.sim.c.agg[c] : 0.f;
+      int c0 = 0, cn = 0;
+      if (ok) sim_person_range(p.sim.c, c, c0, cn);
+      sp0[t] = c0; spn[t] = cn;
+    }
+    if (MODE != CL_MATCH && !SIM && t < CL_T) {
       const int c = col0 + t;
       const bool ok = c < p.nb;
       cn2[t] = ok ? p.n2b[c] : 0.f;
@@ -195,7 +313,27 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
       for (int c = half; c < ncol; c += 2) {
         const int gc = col0 + c;
         const float dot = Er[c];
-        if (MODE == CL_MATCH) {
+        if (SIM) {
+          if (!sok[c] || gc == qrow.self || (p.sim.upper && gc <= grow)) continue;
+          const float sc = sim_score(p.sim, qrow, sdate[c], sagg[c], sp0[c], spn[c], dot);
+          if (!sim_keep(p.sim, sc)) continue;
+          if (MODE == SIM_PAIRS) {
+            if (sc >= qrow.thr) sim_emit(p.sim, grow, gc, sc);
+          } else {
+            const unsigned long long key = ((unsigned long long)cl_sim_key(sc) << 32) | (uint32_t)gc;
+            if (key < best) {                           // the insertion of CL_KNN: ascending keys = (score descending, column ascending)
+              int q = p.k - 1;
+              while (q > 0) {
+                const unsigned long long prev = lists[(q - 1) * 256 + t];
+                if (prev <= key) break;
+                lists[q * 256 + t] = prev;
+                --q;
+              }
+              lists[q * 256 + t] = key;
+              best = lists[(p.k - 1) * 256 + t];
+            }
+          }
+        } else if (MODE == CL_MATCH) {
           const unsigned long long key = ((unsigned long long)cl_sim_key(dot) << 32) | (uint32_t)gc;
           best = key < best ? key : best;
         } else {
@@ -226,12 +364,12 @@ __global__ __launch_bounds__(256) void cl_sweep_kernel(SweepParams p) {
     __syncthreads();                                    // the next tile's staging overwrites the image
   }
 
-  if (MODE == CL_KNN) {
+  if (LISTS) {
     if (rvalid) {
       unsigned long long* out = p.part + ((size_t)grow * (2 * gridDim.y) + 2 * blockIdx.y + half) * p.k;
       for (int s = 0; s < p.k; ++s) out[s] = lists[s * 256 + t];
     }
-  } else {
+  } else if (MODE != SIM_PAIRS) {
     const unsigned long long other = __shfl_xor(best, 1);
     best = other < best ? other : best;
     if (half == 0 && rvalid && best != CL_NONE) atomicMin(p.rowkey + grow, best);
@@ -311,6 +449,122 @@ __global__ __launch_bounds__(256) void cl_refine_edges_kernel(const float* __res
   if (lane == 0) ew[e] = fmax(fmax(core[u], core[v]), sqrt(s));
 }
 
+// ---- similarity sweeps: the small-nq path and the list merge ---------------------------------------------------------------------
+
+// na <= SIM_GEMV_Q queries against nb candidates, one wave per candidate row: the row is read once as float4 per lane and dotted
+// with every query row held in LDS (a butterfly leaves the sum in every lane), then lane q scores the candidate for query q.
+// TOPK: lane q keeps the wave's sorted k-list of query q in LDS; part [na][waves][k]. PAIRS: lane q appends its hits.
+// LDS: [na][d] floats, then (TOPK) [4 waves][na][k] keys.
+template <int MODE>
+__global__ __launch_bounds__(256) void sim_gemv_kernel(SweepParams p) {
+  extern __shared__ __attribute__((aligned(16))) float sg_lds[];
+  float* qs = sg_lds;
+  unsigned long long* lists = reinterpret_cast<unsigned long long*>(sg_lds + (size_t)p.na * p.d);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int i = t; i < p.na * p.d; i += 256) qs[i] = p.a[i];
+  const bool qlane = lane < p.na;
+  const SimRow qrow = sim_load_row(p.sim, lane, qlane);
+  unsigned long long* mine = lists + ((size_t)wave * p.na + (qlane ? lane : 0)) * p.k;
+  unsigned long long best = CL_NONE;
+  if (MODE == SIM_TOPK && qlane)
+    for (int s = 0; s < p.k; ++s) mine[s] = CL_NONE;
+  __syncthreads();
+
+  const int gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
+  for (int c = gw; c < p.nb; c += nw) {                  // wave-uniform
+    if (p.sim.visible && !p.sim.visible[c]) continue;
+    const float* row = p.b + (size_t)c * p.d;
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k0 = (i * 64 + lane) * 4;
+      v[i] = k0 < p.d ? *reinterpret_cast<const float4*>(row + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float cosv = 0.f;
+    for (int q = 0; q < p.na; ++q) {
+      const float* qr = qs + (size_t)q * p.d;
+      float acc = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int k0 = (i * 64 + lane) * 4;
+        if (k0 < p.d) {
+          const float4 w = *reinterpret_cast<const float4*>(qr + k0);
+          acc += v[i].x * w.x; acc += v[i].y * w.y; acc += v[i].z * w.z; acc += v[i].w * w.w;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      if (lane == q) cosv = acc;
+    }
+    if (!qlane || c == qrow.self || (p.sim.upper && c <= lane)) continue;
+    long long cdate = SIM_NO_DATE;
+    float cagg = 0.f;
+    int cp0 = 0, cpn = 0;
+    if (!p.sim.cosine) {
+      if (p.sim.c.date) cdate = p.sim.c.date[c];
+      if (p.sim.c.agg) cagg = p.sim.c.agg[c];
+      sim_person_range(p.sim.c, c, cp0, cpn);
+    }
+    const float sc = sim_score(p.sim, qrow, cdate, cagg, cp0, cpn, cosv);
+    if (!sim_keep(p.sim, sc)) continue;
+    if (MODE == SIM_PAIRS) {
+      if (sc >= qrow.thr) sim_emit(p.sim, lane, c, sc);
+    } else {
+      const unsigned long long key = ((unsigned long long)cl_sim_key(sc) << 32) | (uint32_t)c;
+      if (key < best) {
+        int q = p.k - 1;
+        while (q > 0) {
+          const unsigned long long prev = mine[q - 1];
+          if (prev <= key) break;
+          mine[q] = prev;
+          --q;
+        }
+        mine[q] = key;
+        best = mine[p.k - 1];
+      }
+    }
+  }
+  if (MODE == SIM_TOPK && qlane) {
+    unsigned long long* out = p.part + ((size_t)lane * nw + gw) * p.k;
+    for (int s = 0; s < p.k; ++s) out[s] = mine[s];
+  }
+}
+
+// part [nq][lists][k]: ascending partial lists, CL_NONE padded, keys unique per query (a column sits in one list) -> idx / score
+// [nq][k], -1 / 0 padded. One wave per query: lane l owns the lists l, l + 64, ... and their heads (LDS, one byte per list); a rank
+// is the smallest head of all lists, and the one lane that holds it advances that list.
+__global__ __launch_bounds__(64) void sim_merge_kernel(const unsigned long long* __restrict__ part, int lists, int k, int* __restrict__ idx,
+                                                       float* __restrict__ score) {
+  extern __shared__ unsigned char sm_heads[];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const unsigned long long* p = part + (size_t)row * lists * k;
+  for (int l = lane; l < lists; l += 64) sm_heads[l] = 0;
+  for (int rnk = 0; rnk < k; ++rnk) {
+    unsigned long long cur = CL_NONE;
+    int from = -1;
+    for (int l = lane; l < lists; l += 64) {
+      const int hd = sm_heads[l];
+      if (hd < k) {
+        const unsigned long long v = p[(size_t)l * k + hd];
+        if (v < cur) { cur = v; from = l; }
+      }
+    }
+    unsigned long long m = cur;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(m, o);
+      m = other < m ? other : m;
+    }
+    if (m != CL_NONE && cur == m) sm_heads[from] += 1;
+    if (lane == 0) {
+      const uint32_t kb = ~(uint32_t)(m >> 32);          // cl_sim_key backwards
+      const uint32_t fb = (kb & 0x80000000u) ? (kb ^ 0x80000000u) : ~kb;
+      idx[(size_t)row * k + rnk] = m == CL_NONE ? -1 : (int)(uint32_t)(m & 0xFFFFFFFFull);
+      score[(size_t)row * k + rnk] = m == CL_NONE ? 0.f : __uint_as_float(fb);
+    }
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -335,9 +589,11 @@ void cl_launch_sweep(SweepParams p, hipStream_t s, int* strips_out = nullptr, in
   // enough blocks for four rounds of the chip's 256 CUs when the row tiles alone are too few
   const int strips = strips_fixed ? strips_fixed : std::max(1, std::min(p.tiles_b, (1024 + tiles_a - 1) / tiles_a));
   if (strips_out) *strips_out = strips;
-  const size_t lds = (size_t)(CL_STAGE + CL_META) * sizeof(float) + (MODE == CL_KNN ? (size_t)p.k * 256 * sizeof(unsigned long long) : 0);
+  constexpr bool lists = MODE == CL_KNN || MODE == SIM_TOPK;
+  constexpr size_t fixed = (size_t)(CL_STAGE + CL_META + (MODE == SIM_TOPK || MODE == SIM_PAIRS ? SIM_META : 0)) * sizeof(float);
+  const size_t lds = fixed + (lists ? (size_t)p.k * 256 * sizeof(unsigned long long) : 0);
   static std::atomic<uint64_t> lds_set{0};
-  ensure_dynamic_lds((const void*)cl_sweep_kernel<MODE>, (size_t)(CL_STAGE + CL_META) * sizeof(float) + (MODE == CL_KNN ? 32 * 256 * 8 : 0), lds_set);
+  ensure_dynamic_lds((const void*)cl_sweep_kernel<MODE>, fixed + (lists ? 32 * 256 * 8 : 0), lds_set);
   hipLaunchKernelGGL(cl_sweep_kernel<MODE>, dim3(tiles_a, strips), dim3(256), lds, s, p);
   FE_HIP(hipGetLastError());
 }
@@ -495,6 +751,139 @@ void cluster_best_match(Ctx& c, const float* q, int nq, const float* cc, int nc,
     FE_CHECK(keys[i] != CL_NONE, "cosine_best_match: row %d found no column", i);
     best_sim[i] = cl_sim_from_key((uint32_t)(keys[i] >> 32));
     best_idx[i] = (int32_t)(uint32_t)(keys[i] & 0xFFFFFFFFull);
+  }
+}
+
+// ---- similar photos / merge suggestions -----------------------------------------------------------------------------------------
+namespace {
+
+template <typename T> const T* sim_to_device(Ctx& c, DevMem& mem, const T* src, size_t count, int on_device) {
+  if (!src || on_device) return src;
+  T* d = mem.get<T>(count);
+  FE_HIP(hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, c.stream));
+  return d;
+}
+
+// the rows of one side on the device: normalised (or copied up), or the caller's own when they are resident and taken as they are
+const float* sim_rows(Ctx& c, DevMem& mem, const fe_sim_rows& r, int d) {
+  if (!r.normalise && r.on_device) return r.emb;
+  float *xn, *n2;
+  cl_prepare(c, mem, r.emb, r.n, d, r.on_device, r.normalise, xn, n2);
+  return xn;
+}
+
+SimSide sim_meta(Ctx& c, DevMem& mem, const fe_sim_rows& r) {
+  if (!r.on_device && r.person_off) {                   // host lists can be checked here; device lists are clamped where they are read
+    FE_CHECK(r.person_off[0] == 0 && r.person_off[r.n] == r.n_person_ids, "similar: person_off must run from 0 to n_person_ids");
+    for (int i = 0; i < r.n; ++i) FE_CHECK(r.person_off[i] <= r.person_off[i + 1], "similar: person_off decreases at row %d", i);
+  }
+  SimSide out{};
+  out.has_emb = sim_to_device(c, mem, r.has_emb, (size_t)r.n, r.on_device);
+  out.date = reinterpret_cast<const long long*>(sim_to_device(c, mem, r.date, (size_t)r.n, r.on_device));
+  out.agg = sim_to_device(c, mem, r.aggregate, (size_t)r.n, r.on_device);
+  const bool persons = r.person_off && r.person_ids && r.n_person_ids > 0;
+  out.poff = persons ? sim_to_device(c, mem, r.person_off, (size_t)r.n + 1, r.on_device) : nullptr;
+  out.pid = persons ? sim_to_device(c, mem, r.person_ids, (size_t)r.n_person_ids, r.on_device) : nullptr;
+  out.npid = persons ? r.n_person_ids : 0;
+  return out;
+}
+
+SweepParams sim_params(Ctx& c, DevMem& mem, const fe_sim_rows& q, const fe_sim_rows& cand, int d, int cosine, const float* w, const int32_t* q_self,
+                       const uint8_t* visible) {
+  SweepParams p{};
+  p.d = d; p.na = q.n; p.nb = cand.n;
+  p.a = sim_rows(c, mem, q, d);
+  // Q == C (every photo against every photo, the merge suggestions): the rows are prepared once
+  const bool same = q.emb == cand.emb && q.n == cand.n && q.on_device == cand.on_device && q.normalise == cand.normalise;
+  p.b = same ? p.a : sim_rows(c, mem, cand, d);
+  if (!cosine) { p.sim.q = sim_meta(c, mem, q); p.sim.c = sim_meta(c, mem, cand); }
+  p.sim.q_self = sim_to_device(c, mem, q_self, (size_t)q.n, 0);
+  p.sim.visible = sim_to_device(c, mem, visible, (size_t)cand.n, 0);
+  p.sim.cosine = cosine ? 1 : 0;
+  if (w) { p.sim.wc = w[0]; p.sim.wp = w[1]; p.sim.wd = w[2]; p.sim.ws = w[3]; }
+  return p;
+}
+
+int sim_gemv_blocks(int nb) { return std::max(1, std::min(1024, (nb + 3) / 4)); }
+
+template <int MODE> void sim_launch_gemv(SweepParams p, int blocks, hipStream_t s) {
+  const size_t lds = (size_t)p.na * p.d * sizeof(float) + (MODE == SIM_TOPK ? (size_t)4 * p.na * p.k * sizeof(unsigned long long) : 0);
+  hipLaunchKernelGGL(sim_gemv_kernel<MODE>, dim3(blocks), dim3(256), lds, s, p);   // at most 32 KB + 8 KB: below the static limit
+  FE_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+void similar_topk(Ctx& c, const fe_sim_rows& q, const fe_sim_rows& cand, int d, int cosine, const float* w, const int32_t* q_self,
+                  const uint8_t* visible, int k, int32_t* idx, float* score) {
+  DevMem mem;
+  SweepParams p = sim_params(c, mem, q, cand, d, cosine, w, q_self, visible);
+  p.k = k;
+  const bool gemv = q.n <= SIM_GEMV_Q;
+  const int blocks = sim_gemv_blocks(cand.n);
+  const int lists = gemv ? 4 * blocks : 2 * cl_strips(q.n, cand.n);
+  const size_t words = (size_t)q.n * lists * k;
+  unsigned long long* part = mem.get<unsigned long long>(words + 1);        // then a canary word, as cl_core does
+  FE_HIP(hipMemsetAsync(part + words, 0xA5, sizeof(unsigned long long), c.stream));
+  p.part = part;
+  if (gemv) sim_launch_gemv<SIM_TOPK>(p, blocks, c.stream);
+  else cl_launch_sweep<SIM_TOPK>(p, c.stream, nullptr, lists / 2);
+  int* d_idx = mem.get<int>((size_t)q.n * k + 1);
+  float* d_score = mem.get<float>((size_t)q.n * k);
+  FE_HIP(hipMemsetAsync(d_idx + (size_t)q.n * k, 0xA5, sizeof(int), c.stream));
+  hipLaunchKernelGGL(sim_merge_kernel, dim3(q.n), dim3(64), (size_t)lists, c.stream, part, lists, k, d_idx, d_score);
+  FE_HIP(hipGetLastError());
+  unsigned long long tail = 0;
+  int tail2 = 0;
+  FE_HIP(hipMemcpyAsync(&tail, part + words, sizeof(tail), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipMemcpyAsync(&tail2, d_idx + (size_t)q.n * k, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipMemcpyAsync(idx, d_idx, (size_t)q.n * k * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipMemcpyAsync(score, d_score, (size_t)q.n * k * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipStreamSynchronize(c.stream));
+  FE_CHECK(tail == CL_CANARY && (uint32_t)tail2 == 0xA5A5A5A5u, "similar_topk: a word after an output buffer was overwritten");
+}
+
+void similar_pairs(Ctx& c, const fe_sim_rows& q, const fe_sim_rows& cand, int d, int cosine, const float* w, const int32_t* q_self,
+                   const uint8_t* visible, const float* thr, int n_thr, int upper, int64_t max_pairs, int32_t* pairs, float* scores, int64_t* count) {
+  DevMem mem;
+  SweepParams p = sim_params(c, mem, q, cand, d, cosine, w, q_self, visible);
+  p.sim.upper = upper ? 1 : 0;
+  p.sim.thr = sim_to_device(c, mem, thr, (size_t)n_thr, 0);
+  p.sim.thr_stride = n_thr == 1 ? 0 : 1;
+  // pairs [max_pairs][2], scores [max_pairs], then the counter and a canary word: a store past the capacity would show on them
+  int* d_pairs = mem.get<int>((size_t)max_pairs * 2);
+  float* d_scores = mem.get<float>((size_t)max_pairs + 4);
+  unsigned long long* d_count = mem.get<unsigned long long>(2);
+  FE_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), c.stream));
+  FE_HIP(hipMemsetAsync(d_count + 1, 0xA5, sizeof(unsigned long long), c.stream));
+  FE_HIP(hipMemsetAsync(d_scores + max_pairs, 0xA5, 4 * sizeof(float), c.stream));
+  p.sim.cap = (unsigned long long)max_pairs; p.sim.pairs = d_pairs; p.sim.pscore = d_scores; p.sim.count = d_count;
+  if (q.n <= SIM_GEMV_Q) sim_launch_gemv<SIM_PAIRS>(p, sim_gemv_blocks(cand.n), c.stream);
+  else cl_launch_sweep<SIM_PAIRS>(p, c.stream);
+  unsigned long long tail[2] = {0, 0};
+  uint32_t guard[4] = {0, 0, 0, 0};
+  FE_HIP(hipMemcpyAsync(tail, d_count, sizeof(tail), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipMemcpyAsync(guard, d_scores + max_pairs, sizeof(guard), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipStreamSynchronize(c.stream));
+  FE_CHECK(tail[1] == CL_CANARY && guard[0] == 0xA5A5A5A5u, "similar_pairs: a word after an output buffer was overwritten");
+  *count = (int64_t)tail[0];
+  const size_t found = (size_t)tail[0];
+  if (found && found <= (size_t)max_pairs) {
+    std::vector<int32_t> hp(found * 2);
+    std::vector<float> hs(found);
+    FE_HIP(hipMemcpyAsync(hp.data(), d_pairs, found * 2 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    FE_HIP(hipMemcpyAsync(hs.data(), d_scores, found * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+    FE_HIP(hipStreamSynchronize(c.stream));
+    // the order of arrival is the order the waves ran in; the caller gets ascending (q, c)
+    std::vector<size_t> order(found);
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+      return hp[2 * a] != hp[2 * b] ? hp[2 * a] < hp[2 * b] : hp[2 * a + 1] < hp[2 * b + 1];
+    });
+    for (size_t i = 0; i < found; ++i) {
+      pairs[2 * i] = hp[2 * order[i]]; pairs[2 * i + 1] = hp[2 * order[i] + 1];
+      scores[i] = hs[order[i]];
+    }
   }
 }
 

@@ -461,6 +461,63 @@ int fe_mreach_mst(fe_ctx* ctx, const float* x, int n, int d, int on_device, int 
  * best_sim [nq] fp32, best_idx [nq]: the first candidate among equals. Thresholds stay with the caller. */
 int fe_cosine_best_match(fe_ctx* ctx, const float* q, int nq, const float* c, int nc, int d, float* best_sim, int32_t* best_idx);
 
+/* Similar photos and person-merge suggestions: two more sweeps of the clustering tile core, rows = queries Q [nq][d], columns =
+ * candidates C [n][d] (1 <= nq, n <= 262144; d a multiple of 32 in 32 .. 1024), the nq x n matrix never stored.
+ *   "similar photos" (reference api/routers/gallery.py:410-539) scores one photo against every other one:
+ *       s = wc (cos + 1) / 2 [the query has an embedding]
+ *         + wp |Pq n Pc| / max(|Pq|, |Pc|)              [both person sets non-empty]
+ *         + wd D(|floor((tq - tc) / 86400)|)            [both dates present]   D(0) = 1, D(<= 7) = 0.5, D(<= 30) = 0.2, else
+ *                                                                             max(0, 1 - days / 365); the signed difference is
+ *                                                                             floored first, as Python's abs(timedelta.days)
+ *                                                                             does: one second later is a day, one second
+ *                                                                             earlier is none
+ *         + ws max(0, 1 - |aq - ac| / 10)               [both aggregates present and non-zero]
+ *     with weights = {wc, wp, wd, ws} (the reference's defaults are 0.4, 0.3, 0.2, 0.1), every operation one fp32 rounding;
+ *     cos is the dot product of the normalised rows. score_kind = FE_SIM_FUSED.
+ *   person merge suggestions (reference faces/merge_analyzer.py:29-187) need the plain cosine: score_kind = FE_SIM_COSINE, the
+ *     metadata and the weights are not read.
+ * A candidate is dropped when it is the query itself (q_self [nq], host, candidate index or -1; nullable), when visible [n] (host,
+ * uint8, nullable) is 0 for it, or - fused score only - when s <= 0 (the reference's `if total_similarity > 0`); a NaN score is dropped.
+ *
+ * fe_sim_rows describes one side. emb and the metadata arrays all live on the host (on_device = 0) or all on the device, so a
+ * library can be uploaded once and stay resident between calls; normalise = 1: rows become x / (|x| + 1e-10) in fp32 first, as in
+ * the clustering calls, 0: they are used as they are (unit length expected; resident rows are then read in place). Metadata
+ * pointers may be null (= absent for every row). person_off [n + 1] / person_ids: CSR lists of dense int32 person ids, ascending
+ * and unique within a row, of any length. The same pointer, n and flags on both sides prepare the rows once (Q == C).
+ * With nq <= 8 the sweep is a single read of C by one wave per candidate row (no matrix tile); its dot products are summed in
+ * another order than the tile path's, so a query scored alone and in a batch of more than 8 may differ in the last bits.
+ * Bad shapes, k, kinds or null pointers return FE_ERR_INVALID with a message and launch nothing; the context stays usable. */
+#define FE_SIM_FUSED 0
+#define FE_SIM_COSINE 1
+#define FE_SIM_K_MAX 32
+#define FE_SIM_NO_DATE INT64_MIN
+typedef struct fe_sim_rows {
+  const float* emb;          /* [n][d] */
+  int32_t n;
+  int32_t on_device;         /* where emb and the five arrays below live */
+  int32_t normalise;
+  int32_t n_person_ids;      /* length of person_ids */
+  const uint8_t* has_emb;    /* [n], 0: the row has no embedding (its emb row is not used as a query term); read on the query side only -
+                                a candidate without one is masked out through `visible`, as the reference's SQL does */
+  const int64_t* date;       /* [n] seconds, FE_SIM_NO_DATE = absent */
+  const float* aggregate;    /* [n], 0 or NaN = absent */
+  const int32_t* person_off; /* [n + 1] */
+  const int32_t* person_ids;
+} fe_sim_rows;
+
+/* fe_similar_topk: per query the k best candidates (1 <= k <= FE_SIM_K_MAX) under the order (score descending, candidate index
+ * ascending). idx [nq][k] (-1 padded), score [nq][k] fp32 (0 padded), host. The same input gives the same bytes on every run. */
+int fe_similar_topk(fe_ctx* ctx, const fe_sim_rows* q, const fe_sim_rows* c, int d, int score_kind, const float* weights,
+                    const int32_t* q_self, const uint8_t* visible, int k, int32_t* idx, float* score);
+
+/* fe_similar_pairs: every (query, candidate) with score >= thr; thr (host) holds one value (n_thr = 1) or one per query (n_thr =
+ * nq). upper = 1 (Q == C): only candidate index > query index. The fe_hamming_pairs protocol: count receives the exact number;
+ * pairs [max_pairs][2] = (query, candidate) and scores [max_pairs] (host; nullable when max_pairs = 0) receive them in ascending
+ * (query, candidate) order when count <= max_pairs, otherwise only count is defined - call again with more room. */
+int fe_similar_pairs(fe_ctx* ctx, const fe_sim_rows* q, const fe_sim_rows* c, int d, int score_kind, const float* weights,
+                     const int32_t* q_self, const uint8_t* visible, const float* thr, int n_thr, int upper, int64_t max_pairs,
+                     int32_t* pairs, float* scores, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif
