@@ -129,6 +129,10 @@ SIGNATURES = {
     "fe_vlm_vision_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "fe_vlm3_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]),
     "fe_vlm3_encode_images": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f32p, C.POINTER(C.c_int32), C.c_int, _f32p, _f32p]),
+    "fe_vlm2_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.c_int]),
+    "fe_vlm2_encode_images": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _f32p]),
+    "fe_vlm_generate_until": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), _f32p, C.POINTER(C.c_int)]),
     "fe_vlm_prefill_images_padded": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_ensemble_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
@@ -733,6 +737,31 @@ class Engine:
         self._ck(self.lib.fe_vlm3_configure(self.h, int(n_heads), int(n_kv_heads), int(head_dim), float(rope_theta), float(rms_eps), ms, int(vis_heads),
                                             ds, len(deepstack_indexes)))
 
+    def vlm2_configure(self, n_heads=12, n_kv_heads=2, head_dim=128, rope_theta=1e6, rms_eps=1e-6, mrope_section=(16, 24, 24), vis_heads=16):
+        """The NEXT load_weights(FE_MODEL_VLM, ...) builds Qwen2-VL (Qwen2VLForConditionalGeneration; defaults = Qwen2-VL-2B's geometry)."""
+        ms = (C.c_int * 3)(*[int(v) for v in mrope_section])
+        self._ck(self.lib.fe_vlm2_configure(self.h, int(n_heads), int(n_kv_heads), int(head_dim), float(rope_theta), float(rms_eps), ms, int(vis_heads)))
+
+    def vlm2_encode_images(self, pixel_values, patch_pos_hw, cu_seqlens, want_embeds=True):
+        """Qwen2-VL `model.visual(pixel_values, grid_thw).pooler_output`: pixel_values float [n_patches, 1176], or None = the rows of the
+        last vlm_preprocess_rgb; patch_pos_hw [n_patches, 2] and cu_seqlens [n_images + 1] as facet_amd.vlm_tagger.vision_inputs_qwen2
+        gives them. The merged embeddings stay on the device for the next vlm_prefill(..., image_rows=...). -> [n/4, hidden] float32
+        (bf16 values widened) or None."""
+        pos, pp = self._i32(patch_pos_hw)
+        n = pos.shape[0]
+        assert pos.shape == (n, 2) and n % 4 == 0, pos.shape
+        cf, cfp = self._i32(cu_seqlens)
+        pvp = None
+        if pixel_values is not None:
+            pv = np.ascontiguousarray(pixel_values, dtype=np.float32)
+            pd = self.vlm_vision_dims()["patch_dim"]
+            if pv.shape != (n, pd):
+                raise ValueError(f"pixel_values {pv.shape}: expected ({n}, {pd})")
+            pvp = pv.ctypes.data_as(_f32p)
+        out = np.empty((n // 4, self.vlm_dims()["hidden"]), np.float32) if want_embeds else None
+        self._ck(self.lib.fe_vlm2_encode_images(self.h, pvp, n, pp, cfp, len(cf) - 1, out.ctypes.data_as(_f32p) if want_embeds else None))
+        return out
+
     def vlm_vision_dims(self):
         """The committed vision tower: patch side, patch row width, DeepStack levels, position-table side (fe_vlm_vision_dims)."""
         d = (C.c_int * 4)()
@@ -831,8 +860,23 @@ class Engine:
         self._ck(self.lib.fe_op_vlm_select(self.h, lgp, rows, vocab, ids.ctypes.data_as(C.POINTER(C.c_int32)), lp.ctypes.data_as(_f32p)))
         return ids, lp
 
+    def vlm_generate_until(self, first_tokens, position_ids, max_steps, eos_token_ids, poll=8, return_logprobs=False):
+        """fe_vlm_generate_until after a prefill: first_tokens int [n_seq] (the prefill's choice), position_ids int [3, n_seq] ->
+        (tokens int32 [max_steps, n_seq], log-probs float32 [max_steps, n_seq] or None, steps_run)."""
+        ft, fp = self._i32(first_tokens)
+        n = ft.shape[0]
+        ps, pp = self._i32(position_ids)
+        assert ps.shape == (3, n), ps.shape
+        eos, ep = self._i32(np.asarray([int(e) for e in eos_token_ids], np.int32))
+        out = np.empty((int(max_steps), n), np.int32)
+        lp = np.empty((int(max_steps), n), np.float32) if return_logprobs else None
+        ran = C.c_int(0)
+        self._ck(self.lib.fe_vlm_generate_until(self.h, fp, pp, n, int(max_steps), ep, int(eos.size), int(poll), out.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                lp.ctypes.data_as(_f32p) if return_logprobs else None, C.byref(ran)))
+        return out, lp, int(ran.value)
+
     def vlm_generate(self, tokens, max_new_tokens, position_ids=None, eos_token_ids=(), want_logits=False, forced_tokens=None, image_rows=None,
-                     attention_mask=None, return_logprobs=False):
+                     attention_mask=None, return_logprobs=False, stop_at_eos=False, poll=8):
         """Greedy generation (`generate(..., do_sample=False)`, models/vlm_tagger.py:255-259): prefill + max_new_tokens - 1 decode
         steps for all sequences in lockstep; a sequence that emitted an EOS id keeps receiving that id (what generate's padding does).
         New positions continue from max(position_ids) + 1 per sequence. forced_tokens [n_seq, max_new_tokens]: teacher forcing - the
@@ -841,7 +885,9 @@ class Engine:
         vlm_tagger.rope_index(..., attention_mask=...)). None: every position is real (the unpadded path, unchanged).
         return_logprobs: also the log-probability of every chosen token, float32 [n_seq, max_new_tokens] (log_softmax of the step's bf16
         logits at that id, as `generate(..., output_scores=True)` gives it); steps after a row's first EOS are NaN (not generated). Returns
-        (ids, logprobs), or (ids, logits, logprobs) with want_logits. The ids are the same with or without it."""
+        (ids, logprobs), or (ids, logits, logprobs) with want_logits. The ids are the same with or without it.
+        stop_at_eos (the device loop only: no want_logits / forced_tokens): the decode loop ends once every row has emitted one of
+        eos_token_ids (at most 8), checked on the host every `poll` steps (fe_vlm_generate_until); same ids and log-probs, fewer steps."""
         tok = np.ascontiguousarray(tokens, dtype=np.int32)
         n, L = tok.shape
         pad = None
@@ -866,7 +912,11 @@ class Engine:
                 ft, fp = self._i32(first)
                 ps, pp = self._i32(np.broadcast_to(nxt_pos.astype(np.int32), (3, n)))
                 steps = np.empty((max_new_tokens - 1, n), np.int32)
-                if return_logprobs:      # the same device loop, each step's log-probs beside its ids (fe_vlm_generate_scored)
+                if stop_at_eos:
+                    steps, slp, _ = self.vlm_generate_until(ft, ps, max_new_tokens - 1, eos_token_ids, poll=poll, return_logprobs=return_logprobs)
+                    if return_logprobs:
+                        lps[:, 1:] = slp.T
+                elif return_logprobs:      # the same device loop, each step's log-probs beside its ids (fe_vlm_generate_scored)
                     slp = np.empty((max_new_tokens - 1, n), np.float32)
                     self._ck(self.lib.fe_vlm_generate_scored(self.h, fp, pp, n, max_new_tokens - 1, steps.ctypes.data_as(C.POINTER(C.c_int32)),
                                                              slp.ctypes.data_as(_f32p)))

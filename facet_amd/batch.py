@@ -67,7 +67,9 @@ def detect_silhouette(histogram_silhouette, tags, face_count):
 class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
-                 aux_engine=None, phash=False):
+                 aux_engine=None, phash=False, vlm_composition=None):
+        # Qwen2-VL composition analyzer (facet_amd/vlm_composition.py; the 24gb profile): its SCORE overwrites comp_score, scorer.py:698-705
+        self.vlm_composition = vlm_composition
         self.phash = phash      # add the 'phash' column (16 hex digits) from the resident BGR copy
         self.engine, self.tagger, self.face_analyzer, self.policy, self.detect_lines = engine, tagger, face_analyzer, policy, detect_lines
         # second context on the same GPU for statistics / faces / lines (see module docstring); None = everything on `engine`, in sequence
@@ -174,12 +176,25 @@ class BatchScorer:
             if hashes is not None:
                 res['phash'] = hashes[i]
             out.append(res)
+        if self.vlm_composition is not None:
+            self.apply_vlm_composition(out, imgs)
         if self.policy is not None:
             rows = [self.metrics_multi_pass(r, exif[i] if exif else None) for i, r in enumerate(out)]
             scores, cats = aggregate_batch(rows, self.policy)
             for r, s, c in zip(out, scores.tolist(), cats):
                 r['aggregate'], r['category'] = s, c
         return out
+
+    def apply_vlm_composition(self, results, images_rgb):
+        """The VLM step of Facet.get_composition_scores (scorer.py:698-705), after the SAMP step: one batch_analyze for the batch; each dict
+        takes comp_score from the analyzer's score (rounded to 2 decimals like every comp_score the batch step stores,
+        batch_processor.py:313) and gains composition_explanation (batch_processor.py:348). A result without a score leaves its dict alone."""
+        from PIL import Image
+        for res, r in zip(results, self.vlm_composition.batch_analyze([Image.fromarray(np.asarray(a, np.uint8)) for a in images_rgb])):
+            if r.get('composition_score') is not None:
+                res['comp_score'] = round(float(r['composition_score']), 2)
+                res['composition_explanation'] = r.get('explanation')
+        return results
 
     def process_images(self, images_rgb, exif=None, leading_lines=None):
         """Images of ANY sizes (a list of uint8 [h,w,3] arrays / PIL images, as a chunk of the reference's loader holds them): grouped by

@@ -1418,12 +1418,14 @@ int fe_vlm_encode_preprocessed(fe_ctx* ctx, const int32_t* patch_pos_hw, const i
 int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const int32_t* sizes, const float* mean, const float* stdv, float* pixel_values) {
   FE_API_BEGIN(ctx)
   const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;      // Qwen3-VL: 16-pixel patches (32-pixel merge blocks)
-  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  const bool q2 = ctx->c.vlm && ctx->c.vlm->cfg.qwen2;      // Qwen2-VL: the 14-pixel patches of Qwen2.5-VL
+  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : (q2 ? ctx->c.vlm->vis2.present : ctx->c.vlm->vis.present))) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
   Ctx& C = ctx->c;
   VlmModel& m = *C.vlm;
   FE_CHECK(rgb && sizes && mean && stdv && n_images > 0, "bad arguments");
   const int P = q3 ? 16 : 14, F = 2 * P, PD = 6 * P * P;
-  FE_CHECK((q3 ? m.vis3.patch_dim : m.vis.patch_dim) == PD, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x %d x %d built)", q3 ? m.vis3.patch_dim : m.vis.patch_dim, P, P);
+  const int tower_pd = q3 ? m.vis3.patch_dim : (q2 ? m.vis2.patch_dim : m.vis.patch_dim);
+  FE_CHECK(tower_pd == PD, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x %d x %d built)", tower_pd, P, P);
   size_t in_b = 0, rows = 0, px_max = 0;
   for (int i = 0; i < n_images; ++i) {
     const int h = sizes[4 * i], w = sizes[4 * i + 1], oh = sizes[4 * i + 2], ow = sizes[4 * i + 3];
@@ -1477,7 +1479,7 @@ int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, flo
   VlmConfig& g = ctx->c.vlm_cfg;
   g.n_heads = n_heads; g.n_kv_heads = n_kv_heads; g.head_dim = head_dim; g.rope_theta = rope_theta; g.rms_eps = rms_eps;
   for (int i = 0; i < 3; ++i) g.mrope[i] = mrope_section[i];
-  g.qwen3 = false; g.n_deepstack = 0;      // (the Qwen2.5-VL family: what a context builds unless fe_vlm3_configure said otherwise)
+  g.qwen3 = false; g.qwen2 = false; g.n_deepstack = 0;      // (the Qwen2.5-VL family: what a context builds unless fe_vlm2_ / fe_vlm3_configure said otherwise)
   FE_API_END(ctx)
 }
 // ---- Qwen3-VL: the same decoder entry points serve the family the next commit builds --------------------------------------------------------
@@ -1494,7 +1496,7 @@ int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, fl
   g.n_heads = n_heads; g.n_kv_heads = n_kv_heads; g.head_dim = head_dim; g.rope_theta = rope_theta; g.rms_eps = rms_eps;
   for (int i = 0; i < 3; ++i) g.mrope[i] = mrope_section[i];
   g.vis_heads = vis_heads;
-  g.qwen3 = true;
+  g.qwen3 = true; g.qwen2 = false;
   g.n_deepstack = n_deepstack;
   for (int i = 0; i < n_deepstack; ++i) g.deepstack[i] = deepstack_indexes[i];
   FE_API_END(ctx)
@@ -1563,9 +1565,73 @@ int fe_vlm3_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches,
   FE_HIP(hipStreamSynchronize(C.stream));
   FE_API_END_CAPACITY(ctx)
 }
+// ---- Qwen2-VL (the composition model, models/vlm_composition.py): the Qwen2.5-VL decoder entry points, a tower of its own ---------------------
+int fe_vlm2_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && head_dim == 128 && rope_theta > 0.f && rms_eps > 0.f && mrope_section && vis_heads > 0,
+           "vlm2_configure: bad geometry (head_dim must be 128)");
+  FE_CHECK(mrope_section[0] + mrope_section[1] + mrope_section[2] == 64 && mrope_section[0] >= 0 && mrope_section[1] >= 0 && mrope_section[2] >= 0,
+           "vlm2_configure: mrope sections must sum to head_dim / 2");
+  std::lock_guard<std::mutex> lk(ctx->c.mu);
+  VlmConfig& g = ctx->c.vlm_cfg;
+  g.n_heads = n_heads; g.n_kv_heads = n_kv_heads; g.head_dim = head_dim; g.rope_theta = rope_theta; g.rms_eps = rms_eps;
+  for (int i = 0; i < 3; ++i) g.mrope[i] = mrope_section[i];
+  g.vis_heads = vis_heads;
+  g.qwen2 = true; g.qwen3 = false; g.n_deepstack = 0;
+  FE_API_END(ctx)
+}
+int fe_vlm2_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* cu_seqlens, int n_seg, float* embeds) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen2 || !ctx->c.vlm->vis2.present) {
+    ctx->c.err = "qwen2-vl vision tower not loaded (fe_vlm2_configure before the commit; the checkpoint needs model.visual.*)";
+    return FE_ERR_NOT_LOADED;
+  }
+  Ctx& C = ctx->c;
+  VlmModel& m = *C.vlm;
+  const Vlm2VisionW& v = m.vis2;
+  if (!pixel_values) {
+    FE_CHECK(m.pre_pv && m.pre_rows > 0, "vlm2_encode_images: no pixel_values and no rows of a fe_vlm_preprocess_rgb");
+    FE_CHECK(n_patches == m.pre_rows, "vlm2_encode_images: %d patches but the last fe_vlm_preprocess_rgb left %d rows", n_patches, m.pre_rows);
+  }
+  FE_CHECK(patch_pos_hw && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_seg > 0, "bad arguments");
+  FE_CHECK(cu_seqlens[0] == 0 && cu_seqlens[n_seg] == n_patches, "segment bounds must cover the patches");
+  int max_seg = 0;
+  for (int i = 0; i < n_seg; ++i) { FE_CHECK(cu_seqlens[i + 1] > cu_seqlens[i], "empty image segment"); max_seg = std::max(max_seg, cu_seqlens[i + 1] - cu_seqlens[i]); }
+  const int rows = n_patches / 4;
+  if (rows > m.img_cap) {
+    if (m.img_embeds) (void)hipFree(m.img_embeds);
+    m.img_embeds = nullptr; m.img_cap = 0;
+    FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
+    m.img_cap = rows;
+  }
+  m.img_rows = 0;
+  C.arena.reset();
+  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * v.patch_dim * sizeof(float)) : nullptr;
+  int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
+  int* d_cu = (int*)C.arena.alloc((size_t)(n_seg + 1) * sizeof(int));
+  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * v.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_cu, cu_seqlens, (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  vlm2_vision_forward(C, m, d_pv, pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv, n_patches, d_pos, d_cu, n_seg, max_seg, m.img_embeds);
+  m.img_rows = rows;
+  if (embeds) {
+    const size_t per = (size_t)rows * m.hidden;
+    float* d_f = (float*)C.arena.alloc(per * sizeof(float));
+    launch_convert((const bf16*)m.img_embeds, d_f, per, C.stream);
+    FE_HIP(hipMemcpyAsync(embeds, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  }
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END_CAPACITY(ctx)
+}
 int fe_vlm_vision_dims(fe_ctx* ctx, int* dims) {
   FE_API_BEGIN(ctx)
   const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;
+  if (ctx->c.vlm && ctx->c.vlm->cfg.qwen2) {
+    if (!ctx->c.vlm->vis2.present) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
+    FE_CHECK(dims, "bad arguments");
+    dims[0] = 14; dims[1] = ctx->c.vlm->vis2.patch_dim; dims[2] = 0; dims[3] = 0;
+    return FE_OK;
+  }
   if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
   FE_CHECK(dims, "bad arguments");
   const VlmModel& m = *ctx->c.vlm;
@@ -1690,6 +1756,51 @@ static int vlm_generate_impl(fe_ctx* ctx, const int32_t* tokens, const int32_t* 
   FE_API_END(ctx)
 }
 }  // extern "C++"
+// fe_vlm_generate(_scored) that stops: the same device loop, with the stop rule of VlmUntil (model_vlm.hip). Steps that were not run are
+// filled in here with what they would have held: each sequence's EOS id, NaN log-probs.
+int fe_vlm_generate_until(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int max_steps, const int32_t* eos_ids, int n_eos, int poll,
+                          int32_t* out_tokens, float* out_logprobs, int* steps_run) {
+  FE_API_BEGIN(ctx)
+  if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+  Ctx& C = ctx->c;
+  VlmModel& m = *C.vlm;
+  FE_CHECK(tokens && position_ids && out_tokens && steps_run && max_steps > 0 && n_seq == m.cache_B && m.cur_len > 0, "generate_until: call fe_vlm_prefill for these %d sequences first", n_seq);
+  FE_CHECK(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos_ids) && poll >= 1, "generate_until: at most 8 eos ids, poll >= 1");
+  *steps_run = 0;
+  VlmUntil u;
+  u.n_eos = n_eos; u.poll = poll;
+  for (int e = 0; e < n_eos; ++e) u.eos[e] = eos_ids[e];
+  std::vector<int> fin((size_t)n_seq + 1, -1);      // [n_seq] the EOS id of a finished sequence, then the running count
+  int live = 0;
+  for (int b = 0; b < n_seq; ++b) {      // a first token that already is an EOS id: finished before the first step
+    for (int e = 0; e < n_eos; ++e) if (tokens[b] == eos_ids[e]) fin[b] = tokens[b];
+    live += fin[b] < 0;
+  }
+  fin[n_seq] = live;
+  C.arena.reset();
+  int* d_tok = (int*)C.arena.alloc((size_t)n_seq * sizeof(int));
+  int* d_pos = (int*)C.arena.alloc((size_t)3 * n_seq * sizeof(int));
+  int* d_out = (int*)C.arena.alloc((size_t)max_steps * n_seq * sizeof(int));
+  float* d_lp = out_logprobs ? (float*)C.arena.alloc((size_t)max_steps * n_seq * sizeof(float)) : nullptr;
+  int* d_fin = (int*)C.arena.alloc(((size_t)n_seq + 1) * sizeof(int));
+  u.fin_dev = d_fin; u.live_dev = d_fin + n_seq;
+  FE_HIP(hipMemcpyAsync(d_tok, tokens, (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_pos, position_ids, (size_t)3 * n_seq * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipMemcpyAsync(d_fin, fin.data(), fin.size() * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  vlm_decode_steps(C, m, d_tok, d_pos, n_seq, max_steps, d_out, d_lp, &u);
+  const int ran = u.steps_run;
+  FE_HIP(hipMemcpyAsync(out_tokens, d_out, (size_t)ran * n_seq * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  if (d_lp) FE_HIP(hipMemcpyAsync(out_logprobs, d_lp, (size_t)ran * n_seq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipMemcpyAsync(fin.data(), d_fin, (size_t)n_seq * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  for (int s = ran; s < max_steps; ++s)      // (reached only when every sequence has finished)
+    for (int b = 0; b < n_seq; ++b) {
+      out_tokens[(size_t)s * n_seq + b] = fin[b];
+      if (out_logprobs) out_logprobs[(size_t)s * n_seq + b] = NAN;
+    }
+  *steps_run = ran;
+  FE_API_END(ctx)
+}
 int fe_vlm_generate(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int n_steps, int32_t* out_tokens) {
   return vlm_generate_impl(ctx, tokens, position_ids, n_seq, n_steps, out_tokens, nullptr);
 }

@@ -232,6 +232,8 @@ struct VlmConfig {
   // Qwen3-VL (fe_vlm3_configure): q|k|v without bias, q_norm / k_norm, interleaved M-RoPE, tied lm_head allowed, DeepStack features
   // from after vision blocks deepstack[0 .. n_deepstack) added to the image rows after decoder layers 0 .. n_deepstack - 1
   bool qwen3 = false; int deepstack[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_deepstack = 0;
+  // Qwen2-VL (fe_vlm2_configure): the Qwen2.5-VL decoder with a tied lm_head allowed, and the LayerNorm / QuickGELU tower (model_vlm2_vision.hip)
+  bool qwen2 = false;
 };
 
 struct OpTiming { std::string name; double flops; double bytes; float ms; };
@@ -399,6 +401,15 @@ struct Vlm3VisionW {
   float* inv_freq = nullptr;
   int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0, patch_side = 0, n_pos = 0;
 };
+// Qwen2-VL vision tower (model_vlm2_vision.hip): LayerNorm blocks with biases, head_dim 80 over each whole image, fc1 / QuickGELU / fc2
+struct Vlm2VisionW {
+  bool present = false;
+  ConvW patch;
+  std::vector<Vlm3VisionBlockW> blocks;
+  Vlm3MergerW merger;      // ln_q (LayerNorm per patch row), mlp.0, erf GELU, mlp.2
+  float* inv_freq = nullptr;
+  int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0;
+};
 struct VlmModel {
   DeviceWeights dw;
   VlmConfig cfg;
@@ -424,6 +435,7 @@ struct VlmModel {
   Vlm3VisionW vis3;
   bf16* ds_feats = nullptr; int ds_n = 0, ds_cap = 0;
   const int* ds_slot = nullptr;
+  Vlm2VisionW vis2;      // Qwen2-VL
   void reserve_cache(int B, int max_seq);
   void release_cache();
   ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); if (ds_feats) (void)hipFree(ds_feats); }
@@ -431,6 +443,19 @@ struct VlmModel {
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg);
 void build_vlm_vision(VlmModel& m, const WeightStore& ws);
 void build_vlm3_vision(VlmModel& m, const WeightStore& ws);
+void build_vlm2_vision(VlmModel& m, const WeightStore& ws);
+// Qwen2-VL tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, 2x2-block-major order); cu [n_seg + 1]
+// (one segment per image). out [N/4][out_hidden], rows in the order of the patches' merge blocks
+void vlm2_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* cu, int n_seg, int max_seg, bf16* out);
+// pieces of the towers shared between the families (model_vlm_vision.hip: head_dim 80; model_vlm3_vision.hip: the LayerNorm merger)
+//   2-D rotary embedding on the q / k thirds of fused qkv rows [rows][3 * heads * 80] -> q_out / k_out [rows][heads * 80]
+void vlm_vis_rope80(Ctx& c, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads);
+//   non-causal attention inside the segments cu [n_seg + 1] (longest: max_seg rows), v = the V third of the fused qkv rows
+void vlm_vis_attention80(Ctx& c, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads);
+//   the 20 frequencies of VisionRotaryEmbedding(head_dim 80 / 2)
+float* vlm_vis_inv_freq80(DeviceWeights& dw);
+//   LayerNorm (over 4 d: postshuffle, or per d-wide row), fc1, erf GELU, fc2 on [N][d] rows viewed as [N/4][4 d]; n / t0: [N][d] scratch
+void vlm_ln_merger(Ctx& c, const Vlm3MergerW& w, const bf16* x, int N, int d, bool postshuffle, bf16* n, bf16* t0, bf16* out, int out_d);
 // Qwen3-VL tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, block-major order); interp_idx [N][4] /
 // interp_w [N][4] (bilinear taps into the position table); cu [n_seg + 1] (one segment per image). out [N/4][out_hidden], ds [n_ds][N/4][out_hidden]
 void vlm3_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* interp_idx, const float* interp_w,
@@ -452,7 +477,11 @@ void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, in
 void vlm_embed(Ctx& c, const VlmModel& m, const int* tok_dev, int rows, bf16* x);
 void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev = nullptr,
                  float* lp_dev = nullptr);
-void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp = nullptr);
+// fe_vlm_generate_until: the stop rule of a decode loop. fin_dev [B]: -1 while a sequence runs, else the EOS id it emitted (set by the
+// caller for sequences whose first token already is one); live_dev [1]: the count of running sequences after the last step, read by the
+// host after every `poll` steps. steps_run: out, the steps executed.
+struct VlmUntil { int n_eos = 0; int eos[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int poll = 1; int* fin_dev = nullptr; int* live_dev = nullptr; int steps_run = 0; };
+void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp = nullptr, VlmUntil* until = nullptr);
 // greedy ids (+ log-probabilities when lp_dev != nullptr) of fp32 logit rows, rounded to bf16 in place (model_vlm.hip)
 void vlm_select(Ctx& c, float* lg, int B, int vocab, int* next_dev, float* lp_dev);
 

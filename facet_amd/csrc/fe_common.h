@@ -39,7 +39,7 @@ inline void ensure_dynamic_lds(const void* kernel, size_t bytes, std::atomic<uin
 }
 
 // Activation codes shared by the GEMM/conv epilogue.
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SIGMOID = 3, ACT_PRELU = 4, ACT_SOFTPLUS = 5 };  // PRELU: per-channel slope
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SIGMOID = 3, ACT_PRELU = 4, ACT_SOFTPLUS = 5, ACT_QUICKGELU = 6 };  // PRELU: per-channel slope; QUICKGELU: x sigmoid(1.702 x)
 
 // Scalar activations of the contraction epilogues (PReLU is handled by the callers: it needs the per-channel slope).
 // Softplus follows torch.nn.Softplus(beta=1, threshold=20): x above the threshold passes through.
@@ -48,6 +48,7 @@ __device__ __forceinline__ float fe_apply_act(float v, int act) {
   if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
   if (act == ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
   if (act == ACT_SOFTPLUS) return v > 20.f ? v : log1pf(expf(v));
+  if (act == ACT_QUICKGELU) return v / (1.f + __expf(-1.702f * v));
   return v;
 }
 
@@ -68,6 +69,7 @@ __device__ __forceinline__ float fe_apply_act_precise(float v, int act) {      /
   if (act == ACT_RELU) return v > 0.f ? v : 0.f;
   if (act == ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
   if (act == ACT_SOFTPLUS) return v > 20.f ? v : log1pf(expf(v));
+  if (act == ACT_QUICKGELU) return v / (1.f + __expf(-1.702f * v));
   return v;
 }
 
@@ -87,6 +89,7 @@ __device__ __forceinline__ float fe_apply_act_fast(float v, int act) {   // bf16
   if (act == ACT_GELU) return fe_gelu_fast(v);
   if (act == ACT_SIGMOID) return fe_rcp_fast(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
   if (act == ACT_SOFTPLUS) return fmaxf(v, 0.f) + __logf(1.f + __expf(-fabsf(v)));   // |error| ~1e-7: far below the bf16 rounding of the result
+  if (act == ACT_QUICKGELU) return v * fe_rcp_fast(1.f + __builtin_amdgcn_exp2f(-2.4554669595930156f * v));      // x sigmoid(1.702 x): -1.702 log2(e)
   return v;
 }
 

@@ -14,6 +14,7 @@
 #include "engine.h"
 #include <type_traits>
 #include <cmath>
+#include <cstring>
 
 namespace fe {
 
@@ -604,20 +605,38 @@ static void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf
 
 // device-resident decode state (graph replay): after a step, the chosen tokens become the next step's input, every position and the
 // cache length advance by one, and the tokens are appended to the output table [step][B] (LP: their log-probs lp [B] to out_lp [step][B])
-template <bool LP>
+// UNTIL (fe_vlm_generate_until): fin [B] holds -1 while a sequence runs, else the EOS id it emitted. A finished sequence takes that id
+// again instead of the step's choice (what generate's padding feeds it) and NaN as its log-prob; a running one that picks one of the
+// eos ids is marked; *live = the sequences still running after this step (the host reads it between launches).
+struct VlmEosIds { int n; int id[8]; };
+template <bool LP, bool UNTIL>
 __global__ void vlm_advance_kernel(const int* __restrict__ next, int* __restrict__ tok, int* __restrict__ pos, int* __restrict__ len, int* __restrict__ step,
-                                   int* __restrict__ out, int B, const float* __restrict__ lp, float* __restrict__ out_lp) {
+                                   int* __restrict__ out, int B, const float* __restrict__ lp, float* __restrict__ out_lp, const VlmEosIds eos,
+                                   int* __restrict__ fin, int* __restrict__ live) {
   const int b = threadIdx.x;
   const int st = *step;
+  bool running = false;
   if (b < B) {
-    const int t = next[b];
+    int t = next[b];
+    float l = LP ? lp[b] : 0.f;
+    if (UNTIL) {
+      const int f = fin[b];
+      if (f >= 0) { t = f; l = __builtin_nanf(""); }
+      else {
+        bool hit = false;
+        for (int e = 0; e < eos.n; ++e) hit = hit || t == eos.id[e];
+        if (hit) fin[b] = t;
+        running = !hit;
+      }
+    }
     tok[b] = t;
     out[(size_t)st * B + b] = t;
-    if (LP) out_lp[(size_t)st * B + b] = lp[b];
+    if (LP) out_lp[(size_t)st * B + b] = l;
     pos[b] += 1; pos[B + b] += 1; pos[2 * B + b] += 1;
   }
-  __syncthreads();
-  if (b == 0) { *len += 1; *step = st + 1; }
+  const int n_live = UNTIL ? __syncthreads_count(running) : 0;
+  if (!UNTIL) __syncthreads();
+  if (b == 0) { *len += 1; *step = st + 1; if (UNTIL) *live = n_live; }
 }
 
 // x = bf16(x + y) and, in the same pass, n = RMSNorm(x) * w (w == nullptr: the sum only). One wave per row: a decode step is a chain of
@@ -876,7 +895,12 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
   FE_CHECK(cfg.mrope[0] + cfg.mrope[1] + cfg.mrope[2] == 64, "vlm: mrope sections must sum to head_dim / 2");
   FE_CHECK(m.hidden % 64 == 0, "vlm: hidden size %d must be a multiple of 64", m.hidden);
   // Qwen3-VL checkpoints may tie lm_head to embed_tokens (no lm_head.weight): the packed lm_head rows then serve as the embedding table too
-  const bool tied = cfg.qwen3 && !ws.has("lm_head.weight");
+  // Qwen2-VL-2B ties it too; safetensors drops the shared tensor, a torch state dict keeps it under both names (equal values: one copy)
+  bool tied = (cfg.qwen3 || cfg.qwen2) && !ws.has("lm_head.weight");
+  if (!tied && cfg.qwen2) {
+    const HostTensor& H = ws.get("lm_head.weight");
+    tied = H.data.size() == E.data.size() && memcmp(H.data.data(), E.data.data(), E.data.size() * sizeof(float)) == 0;
+  }
   if (!tied) m.embed = upload_bf16(m.dw, E.data);
   m.layers.clear();
   const int qd = cfg.n_heads * 128, kd = cfg.n_kv_heads * 128;
@@ -946,6 +970,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
   for (int i = 0; i < 64; ++i) inv[i] = 1.0f / powf(cfg.rope_theta, (float)(2 * i) / 128.0f);
   m.inv_freq = m.dw.upload(inv);
   if (cfg.qwen3) build_vlm3_vision(m, ws);      // model.visual.* when the checkpoint carries it
+  else if (cfg.qwen2) build_vlm2_vision(m, ws);
   else build_vlm_vision(m, ws);
 }
 
@@ -1044,10 +1069,13 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
       switch (G) {
         case 1: VLM_DEC_LAUNCH(1); break;
         case 2: VLM_DEC_LAUNCH(2); break;
+        case 3: VLM_DEC_LAUNCH(3); break;
         case 4: VLM_DEC_LAUNCH(4); break;
+        case 5: VLM_DEC_LAUNCH(5); break;
+        case 6: VLM_DEC_LAUNCH(6); break;
         case 7: VLM_DEC_LAUNCH(7); break;
         case 8: VLM_DEC_LAUNCH(8); break;
-        default: FE_CHECK(false, "vlm decode attention: %d query heads per KV head (1, 2, 4, 7, 8 are built)", G);
+        default: FE_CHECK(false, "vlm decode attention: %d query heads per KV head (1 .. 8 are built)", G);
       }
 #undef VLM_DEC_LAUNCH
       hipLaunchKernelGGL(vlm_attn_combine_kernel, dim3(B * nh), dim3(128), 0, c.stream, (const float*)po, (const float*)pm, (const float*)pl, ao, nsplit);
@@ -1138,8 +1166,11 @@ void vlm_select(Ctx& c, float* lg, int B, int vocab, int* next_dev, float* lp_de
 // tok_dev [B] holds the tokens to feed first (the prefill's choice), pos_dev [3][B] their positions; out_dev [n_steps][B] receives the
 // tokens chosen by the steps and (out_lp != nullptr) out_lp [n_steps][B] their log-probabilities, by way of the model's last_lp. Leaves
 // cur_len advanced by n_steps.
-void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp) {
+void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, int n_steps, int* out_dev, float* out_lp, VlmUntil* until) {
+  if (until) until->steps_run = 0;
   if (n_steps <= 0) return;
+  FE_CHECK(B <= 1024, "vlm: %d sequences (one workgroup advances the decode state: at most 1024)", B);
+  FE_CHECK(!until || (until->n_eos >= 0 && until->n_eos <= 8 && until->poll >= 1 && until->fin_dev && until->live_dev), "vlm: bad stop rule");
   FE_CHECK(B == m.cache_B && m.cur_len > 0 && m.cur_len + n_steps <= m.max_seq, "vlm: %d more positions do not fit the cache (%d of %d used)", n_steps, m.cur_len, m.max_seq);
   const size_t mark = c.arena.mark();
   int* st = c.arena.array<int>(4);                 // [0] cache length, [1] step counter
@@ -1147,23 +1178,37 @@ void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, in
   bf16* x = c.arena.array<bf16>((size_t)B * m.hidden);
   const int init[2] = {m.cur_len, 0};
   FE_HIP(hipMemcpyAsync(st, init, sizeof init, hipMemcpyHostToDevice, c.stream));
+  VlmEosIds eos{};
+  if (until) { eos.n = until->n_eos; for (int e = 0; e < until->n_eos; ++e) eos.id[e] = until->eos[e]; }
   auto one_step = [&]() {
     vlm_embed(c, m, tok_dev, B, x);
     vlm_forward(c, m, x, pos_dev, B, 1, next, nullptr, st, out_lp ? m.last_lp : nullptr);
-    if (out_lp)
-      hipLaunchKernelGGL(vlm_advance_kernel<true>, dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1, out_dev, B,
-                         (const float*)m.last_lp, out_lp);
-    else
-      hipLaunchKernelGGL(vlm_advance_kernel<false>, dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1, out_dev, B,
-                         (const float*)nullptr, (float*)nullptr);
+#define VLM_ADVANCE(LP, UNTIL)                                                                                                                  \
+  hipLaunchKernelGGL((vlm_advance_kernel<LP, UNTIL>), dim3(1), dim3(64 * ((B + 63) / 64)), 0, c.stream, (const int*)next, tok_dev, pos_dev, st, st + 1,   \
+                     out_dev, B, LP ? (const float*)m.last_lp : (const float*)nullptr, out_lp, eos, until ? until->fin_dev : (int*)nullptr,   \
+                     until ? until->live_dev : (int*)nullptr)
+    if (until) { if (out_lp) VLM_ADVANCE(true, true); else VLM_ADVANCE(false, true); }
+    else { if (out_lp) VLM_ADVANCE(true, false); else VLM_ADVANCE(false, false); }
+#undef VLM_ADVANCE
     FE_HIP(hipGetLastError());
+  };
+  // the stop rule: after every `poll` steps (and never after the last) the host reads the running count and stops launching at zero
+  int done = 1;      // steps launched so far
+  auto stop_here = [&]() {
+    if (!until || done % until->poll != 0 || done >= n_steps) return false;
+    int live = 0;
+    FE_HIP(hipMemcpyAsync(&live, until->live_dev, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    FE_HIP(hipStreamSynchronize(c.stream));
+    return live == 0;
   };
   const int len0 = m.cur_len;
   one_step();                                      // outside the graph: first-use attributes (dynamic LDS sizes) are set here
   static const bool no_graph = getenv("FE_VLM_NO_GRAPH") != nullptr;      // A/B hook
   // replayed from a graph the ~60 launches of a step carry a dependency edge each: worth it while the step is launch-bound (1-2 sequences:
   // 0.68 vs 0.70 ms per 4-layer step), slower than back-to-back stream launches above that (32 sequences: 1.21 vs 1.10 ms; profiles/r03_vlm_perf.txt)
-  if (n_steps > 1 && !no_graph && B <= 2) {
+  if (stop_here()) {
+    // every sequence had finished after the first step
+  } else if (n_steps > 1 && !no_graph && B <= 2) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     FE_HIP(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
@@ -1171,14 +1216,18 @@ void vlm_decode_steps(Ctx& c, VlmModel& m, int* tok_dev, int* pos_dev, int B, in
     try { one_step(); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(c.stream, &g); if (g) (void)hipGraphDestroy(g); throw; }
     FE_HIP(hipStreamEndCapture(c.stream, &graph));
     FE_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    for (int s = 1; s < n_steps; ++s) FE_HIP(hipGraphLaunch(exec, c.stream));
-    FE_HIP(hipStreamSynchronize(c.stream));
+    bool stop = false;
+    try {
+      for (; done < n_steps && !stop; stop = stop_here()) { FE_HIP(hipGraphLaunch(exec, c.stream)); ++done; }
+      FE_HIP(hipStreamSynchronize(c.stream));
+    } catch (...) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); throw; }
     (void)hipGraphExecDestroy(exec);
     (void)hipGraphDestroy(graph);
   } else {
-    for (int s = 1; s < n_steps; ++s) { m.cur_len = len0 + s; one_step(); }
+    for (bool stop = false; done < n_steps && !stop; stop = stop_here()) { m.cur_len = len0 + done; one_step(); ++done; }
   }
-  m.cur_len = len0 + n_steps;
+  if (until) until->steps_run = done;
+  m.cur_len = len0 + done;
   c.arena.rewind(mark);
 }
 

@@ -279,8 +279,8 @@ static inline int v3grid(size_t n, int per = 256) { size_t g = (n + per - 1) / p
 
 static void vis3_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy, int act = ACT_NONE) { linear_forward(c, w, x, ldx, M, y, ldy, act); }
 
-// a merger on the [N][d] rows: post-shuffle norm (DeepStack: LayerNorm over the 4 d-wide view) or per-row norm (final), fc1, erf GELU, fc2
-static void vis3_merger(Ctx& c, const Vlm3MergerW& w, const bf16* x, int N, int d, bool postshuffle, bf16* n, bf16* t0, bf16* out, int out_d) {
+// (shared with the Qwen2-VL tower, whose ln_q merger is the per-row form) a merger on the [N][d] rows: post-shuffle norm (DeepStack: LayerNorm over the 4 d-wide view) or per-row norm (final), fc1, erf GELU, fc2
+void vlm_ln_merger(Ctx& c, const Vlm3MergerW& w, const bf16* x, int N, int d, bool postshuffle, bf16* n, bf16* t0, bf16* out, int out_d) {
   if (postshuffle) launch_layernorm<bf16, bf16>(x, 4 * d, n, 4 * d, w.ln_g, w.ln_b, N / 4, 4 * d, 1e-6f, c.stream);
   else launch_layernorm<bf16, bf16>(x, d, n, d, w.ln_g, w.ln_b, N, d, 1e-6f, c.stream);
   vis3_linear(c, w.fc1, n, 4 * d, N / 4, t0, 4 * d);
@@ -332,12 +332,12 @@ void vlm3_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf
       const size_t mm = c.arena.mark();
       bf16* n4 = c.arena.array<bf16>((size_t)N * d);
       bf16* t4 = c.arena.array<bf16>((size_t)N * d);
-      vis3_merger(c, v.ds_mergers[k], x, N, d, true, n4, t4, ds + k * ds_stride, v.out_hidden);
+      vlm_ln_merger(c, v.ds_mergers[k], x, N, d, true, n4, t4, ds + k * ds_stride, v.out_hidden);
       c.arena.rewind(mm);
     }
   }
   bf16* t0 = c.arena.array<bf16>((size_t)N * d);
-  vis3_merger(c, v.merger, x, N, d, false, n, t0, out, v.out_hidden);
+  vlm_ln_merger(c, v.merger, x, N, d, false, n, t0, out, v.out_hidden);
   c.arena.rewind(mark);
 }
 

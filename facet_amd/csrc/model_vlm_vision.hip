@@ -248,14 +248,30 @@ void build_vlm_vision(VlmModel& m, const WeightStore& ws) {
   v.out_hidden = v.m2.Cout;
   FE_CHECK(v.m0.Cin == 4 * v.hidden && v.out_hidden == m.hidden, "vlm vision: merger %d -> %d does not fit the tower (%d) / decoder (%d)", v.m0.Cin, v.out_hidden, v.hidden, m.hidden);
   // Qwen2_5_VisionRotaryEmbedding(head_dim // 2): inv_freq = 1 / 10000^(arange(0, dim, 2) / dim), dim = head_dim / 2
-  std::vector<float> inv(20);
-  for (int i = 0; i < 20; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / 40.0f);
-  v.inv_freq = m.dw.upload(inv);
+  v.inv_freq = vlm_vis_inv_freq80(m.dw);
   v.fullatt.assign(m.cfg.fullatt, m.cfg.fullatt + m.cfg.n_fullatt);
   v.present = true;
 }
 
 static inline int vgrid(size_t n, int per = 256) { size_t g = (n + per - 1) / per; return (int)(g > 262140 ? 262140 : (g ? g : 1)); }
+
+// ---- the head_dim-80 pieces, shared with the Qwen2-VL tower (model_vlm2_vision.hip) --------------------------------------------------------
+float* vlm_vis_inv_freq80(DeviceWeights& dw) {
+  std::vector<float> inv(20);
+  for (int i = 0; i < 20; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / 40.0f);
+  return dw.upload(inv);
+}
+void vlm_vis_rope80(Ctx& c, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads) {
+  hipLaunchKernelGGL(vlm_vis_rope_kernel, dim3(vgrid((size_t)rows * 2 * heads * 40)), dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads, 80);
+  FE_HIP(hipGetLastError());
+}
+void vlm_vis_attention80(Ctx& c, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads) {
+  const int d = heads * 80;
+  VisAttnParams ap{q, k, d, qkv + 2 * d, 3 * d, o, d, cu, heads, 1.0f / sqrtf(80.f)};
+  if (max_seg <= 64) hipLaunchKernelGGL(vlm_vis_attn_kernel<2>, dim3((max_seg + 63) / 64, n_seg, heads), dim3(128), 0, c.stream, ap);
+  else hipLaunchKernelGGL(vlm_vis_attn_kernel<4>, dim3((max_seg + 127) / 128, n_seg, heads), dim3(256), 0, c.stream, ap);
+  FE_HIP(hipGetLastError());
+}
 
 static void vis_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy) { linear_forward(c, w, x, ldx, M, y, ldy, ACT_NONE); }
 
@@ -291,18 +307,13 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
   vis_linear(c, v.patch, pv ? (const bf16*)pvh : pv_bf16, v.patch_dim, N, h0, d);
   hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(vgrid((size_t)N * d / 8)), dim3(256), 0, c.stream, (const bf16*)h0, x, widx, N / 4, 4, d, 0);
   FE_HIP(hipGetLastError());
-  const float scale = 1.0f / sqrtf(80.f);
   for (size_t li = 0; li < v.blocks.size(); ++li) {
     const VlmVisionBlockW& w = v.blocks[li];
     const bool full = std::find(v.fullatt.begin(), v.fullatt.end(), (int)li) != v.fullatt.end();
     vlm_rmsnorm(c, x, d, w.n1, n, d, N, d, 1e-6f);
     vis_linear(c, w.qkv, n, d, N, qkv, 3 * d);
-    hipLaunchKernelGGL(vlm_vis_rope_kernel, dim3(vgrid((size_t)N * 2 * H * 40)), dim3(256), 0, c.stream, (const bf16*)qkv, pos, (const float*)v.inv_freq, qr, kr, N, H, 80);
-    VisAttnParams ap{qr, kr, d, qkv + 2 * d, 3 * d, ao, d, full ? cu_full : cu_win, H, scale};
-    const int nseg = full ? n_full : n_win, mx = full ? max_full : max_win;
-    if (mx <= 64) hipLaunchKernelGGL(vlm_vis_attn_kernel<2>, dim3((mx + 63) / 64, nseg, H), dim3(128), 0, c.stream, ap);
-    else hipLaunchKernelGGL(vlm_vis_attn_kernel<4>, dim3((mx + 127) / 128, nseg, H), dim3(256), 0, c.stream, ap);
-    FE_HIP(hipGetLastError());
+    vlm_vis_rope80(c, qkv, pos, v.inv_freq, qr, kr, N, H);
+    vlm_vis_attention80(c, qr, kr, qkv, ao, full ? cu_full : cu_win, full ? n_full : n_win, full ? max_full : max_win, H);
     vis_linear(c, w.proj, ao, d, N, br, d);
     vlm_add(c, x, br, (size_t)N * d);
     vlm_rmsnorm(c, x, d, w.n2, n, d, N, d, 1e-6f);

@@ -54,6 +54,32 @@ class ModelManager:
             prof = self.config.get_model_config().get('vram_profile')
         return prof if prof and prof != 'auto' else self.get_recommended_profile(self.detect_vram())
 
+    # -- composition model (reference :83-125, :228-231) ----------------------------------------------------
+    @property
+    def model_settings(self):
+        return self.config.get_model_config() if (self.config is not None and hasattr(self.config, 'get_model_config')) else {}
+
+    def _profile_settings(self):
+        """The active profile's entry of the config's `profiles` table (the reference's get_active_profile dict); without a table, the
+        reference's scoring_config.json choice: Qwen2-VL composition on the 24gb profile, SAMP-Net below it."""
+        name = self.get_active_profile()
+        profiles = self.model_settings.get('profiles')
+        if profiles:
+            return profiles.get(name, profiles.get('legacy', {}))
+        return {'composition_model': 'qwen2-vl-2b' if name == '24gb' else 'samp-net'}
+
+    def is_using_qwen_composition(self):
+        return self._profile_settings().get('composition_model') == 'qwen2-vl-2b'
+
+    def load_composition_model(self):
+        """{'model', 'processor'} for the Qwen2-VL analyzer (facet_amd/vlm_composition.py) when the profile names it, else None."""
+        kind = self._profile_settings().get('composition_model', 'rule-based')
+        if kind == 'qwen2-vl-2b':
+            return self.load_model_only('qwen2_vl')
+        if kind != 'rule-based':
+            print(f"Unknown composition model: {kind}, using rule-based")
+        return None
+
     def get_model_vram(self, name):
         return MODEL_VRAM_GB.get(name, 4)
 
@@ -118,6 +144,16 @@ class ModelManager:
             except FileNotFoundError as e:
                 raise EngineError(str(e))
             return FaceEngine(self.engine, models, det_size=(640, 640))
+        if name == 'qwen2_vl':
+            # reference _load_qwen2_vl (model_manager.py:96-125) returns {'model': Qwen2VLForConditionalGeneration, 'processor': AutoProcessor};
+            # here the model is the engine with the given state dict committed, the processor the caller's tokenizer + pixel limits
+            from .vlm_composition import Qwen2VLModel, Qwen2VLProcessor
+            q = cfg.get('qwen2_vl', {})
+            if q.get('state_dict') is None:
+                raise FileNotFoundError("no checkpoint: pass the model's state dict as qwen2_vl.state_dict (the reference downloads it with "
+                                        "from_pretrained, models/model_manager.py:111-117; there is no network here)")
+            proc = q.get('processor') or Qwen2VLProcessor(q.get('encode'), q.get('decode'), **{k: q[k] for k in ('min_pixels', 'max_pixels', 'special_tokens') if k in q})
+            return {'model': Qwen2VLModel(self.engine, q['state_dict'], q.get('geometry')).to(self.device), 'processor': proc}
         raise KeyError(f"model '{name}' is not served by the engine (hot-path models: {HOT_PATH_MODELS})")
 
     @staticmethod

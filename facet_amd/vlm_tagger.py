@@ -187,6 +187,23 @@ def vision_inputs_qwen3(grid_thw, num_grid_per_side: int, spatial_merge_size: in
             "interp_w": np.concatenate(wts, 0).astype(np.float32), "cu_seqlens": np.asarray(cu, np.int32)}
 
 
+def vision_inputs_qwen2(grid_thw, spatial_merge_size: int = 2):
+    """The index arrays of Qwen2-VL's vision tower (no windows, no position table) for images of `grid_thw` [n_images, 3]: rows / columns
+    of every patch in 2x2-block-major order (transformers.vision_utils.get_vision_position_ids) and one attention segment per frame
+    (get_vision_cu_seqlens). Returns a dict for Engine.vlm2_encode_images: patch_pos_hw [n, 2] int32, cu_seqlens int32."""
+    grid = np.asarray(grid_thw, dtype=np.int64).reshape(-1, 3)
+    m = spatial_merge_size
+    pos, cu = [], [0]
+    for t, h, w in grid:
+        t, h, w = int(t), int(h), int(w)
+        hh, ww = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        blk = lambda a: a.reshape(h // m, m, w // m, m).transpose(0, 2, 1, 3).reshape(-1)      # block-major over the m x m merge blocks
+        pos.append(np.tile(np.stack([blk(hh), blk(ww)], -1), (t, 1)))
+        for _ in range(t):
+            cu.append(cu[-1] + h * w)
+    return {"patch_pos_hw": np.concatenate(pos, 0).astype(np.int32), "cu_seqlens": np.asarray(cu, np.int32)}
+
+
 def interleaved_mrope_components(mrope_section=(24, 20, 20), n_freq: int = 64):
     """Which position component (0 temporal, 1 height, 2 width) each rotary frequency of Qwen3-VL's interleaved M-RoPE takes
     (Qwen3VLTextRotaryEmbedding.apply_interleaved_mrope): j % 3 == 1 and j < 3 s_h -> height, j % 3 == 2 and j < 3 s_w -> width, else

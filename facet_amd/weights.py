@@ -313,6 +313,38 @@ def qwen3_vl_vision_spec(hidden=1024, depth=24, inter=4096, out_hidden=2048, pat
     return spec
 
 
+def qwen2_vl_text_spec(hidden=1536, layers=28, heads=12, kv_heads=2, inter=8960, vocab=151936, tied=True):
+    """Text decoder of transformers' Qwen2VLForConditionalGeneration (the composition model of the 24gb profile): the Qwen2.5-VL layer
+    (head_dim 128, q / k / v with bias, SwiGLU MLP); lm_head tied to embed_tokens (no lm_head.weight) unless tied=False. Defaults =
+    Qwen2-VL-2B-Instruct (12 heads over 2 KV heads: GQA group 6)."""
+    spec = qwen2_5_vl_text_spec(hidden, layers, heads, kv_heads, inter, vocab)
+    if tied:      # (a tied table is also the read-out: the 1 / sqrt(hidden) scale keeps its logits O(1), as qwen3_vl_text_spec does)
+        spec = [(n, s, "linear" if n.endswith("embed_tokens.weight") else k) for n, s, k in spec if n != "lm_head.weight"]
+    return spec
+
+
+def qwen2_vl_vision_spec(hidden=1280, depth=32, inter=5120, out_hidden=1536, patch=14, temporal=2):
+    """Vision tower of Qwen2VLForConditionalGeneration (`model.visual.*`): Conv3d patch embedding (no bias), `depth` blocks of LayerNorm
+    (+bias) - fused qkv (+bias) - proj (+bias) - LayerNorm - fc1 / QuickGELU / fc2 (+biases), the patch merger (LayerNorm ln_q,
+    Linear(4 hidden, 4 hidden), GELU, Linear(4 hidden, out_hidden)). Defaults = Qwen2-VL-2B-Instruct (16 heads of 80)."""
+    v = "model.visual."
+    spec = [(v + "patch_embed.proj.weight", (hidden, 3, temporal, patch, patch), "linear_nd")]
+    for i in range(depth):
+        b = f"{v}blocks.{i}"
+        for n in ("norm1", "norm2"):
+            spec.append((f"{b}.{n}.weight", (hidden,), "ln_w"))
+            spec.append((f"{b}.{n}.bias", (hidden,), "ln_b"))
+        _linear(spec, b + ".attn.qkv", 3 * hidden, hidden)
+        _linear(spec, b + ".attn.proj", hidden, hidden)
+        _linear(spec, b + ".mlp.fc1", inter, hidden)
+        _linear(spec, b + ".mlp.fc2", hidden, inter)
+    spec.append((v + "merger.ln_q.weight", (hidden,), "ln_w"))
+    spec.append((v + "merger.ln_q.bias", (hidden,), "ln_b"))
+    _linear(spec, v + "merger.mlp.0", 4 * hidden, 4 * hidden)
+    _linear(spec, v + "merger.mlp.2", out_hidden, 4 * hidden)
+    return spec
+
+
 # the reduced Qwen3-VL of the parity tests (tests/golden/make_vlm3_golden.py): head_dim 128 with 2:1 grouped KV heads in the decoder,
 # head_dim 64 in the tower, an 8 x 8 position table, DeepStack after three non-contiguous blocks including the last
 VLM3_TINY = dict(hidden=256, layers=4, heads=4, kv_heads=2, inter=512, vocab=2048)
@@ -326,6 +358,11 @@ VLM_VISION_TINY = dict(hidden=160, depth=3, inter=320, out_hidden=512)
 # KV heads at a size the CPU oracle generates from in seconds
 VLM_TINY = dict(hidden=512, layers=4, heads=4, kv_heads=2, inter=1408, vocab=2048)
 
+# the reduced Qwen2-VL of the parity tests (tests/golden/make_vlm2_golden.py): the 2B checkpoint's GQA group of 6 (6 heads over 1 KV head of
+# 128) in the decoder, head_dim 80 and mlp_ratio 4 in the tower
+VLM2_TINY = dict(hidden=768, layers=4, heads=6, kv_heads=1, inter=1408, vocab=2048)
+VLM2_VISION_TINY = dict(hidden=160, depth=4, inter=640, out_hidden=768)
+
 SPECS = {
     "qwen2_5_vl_text": qwen2_5_vl_text_spec,
     "qwen2_5_vl_text_tiny": lambda: qwen2_5_vl_text_spec(**VLM_TINY),
@@ -334,6 +371,10 @@ SPECS = {
     "qwen3_vl_2b": lambda: qwen3_vl_text_spec() + qwen3_vl_vision_spec(),
     "qwen3_vl_tiny": lambda: qwen3_vl_text_spec(**VLM3_TINY) + qwen3_vl_vision_spec(**VLM3_VISION_TINY),
     "qwen3_vl_tiny_untied": lambda: qwen3_vl_text_spec(**VLM3_TINY, tied=False) + qwen3_vl_vision_spec(**VLM3_VISION_TINY),
+    "qwen2_vl_text": qwen2_vl_text_spec,
+    "qwen2_vl_2b": lambda: qwen2_vl_text_spec() + qwen2_vl_vision_spec(),
+    "qwen2_vl_tiny": lambda: qwen2_vl_text_spec(**VLM2_TINY) + qwen2_vl_vision_spec(**VLM2_VISION_TINY),
+    "qwen2_vl_tiny_untied": lambda: qwen2_vl_text_spec(**VLM2_TINY, tied=False) + qwen2_vl_vision_spec(**VLM2_VISION_TINY),
     "topiq": topiq_spec,
     "resnet50": lambda: resnet_spec("semantic_model.", True, [3, 4, 6, 3]),
     "clip": clip_vit_spec,

@@ -168,6 +168,30 @@ int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, fl
 int fe_vlm3_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* interp_idx, const float* interp_w,
                           const int32_t* cu_seqlens, int n_seg, float* embeds, float* deepstack);
 
+/* Qwen2-VL (transformers Qwen2VLForConditionalGeneration, the 24gb profile's composition model qwen2-vl-2b, models/vlm_composition.py):
+ * fe_vlm2_configure makes the NEXT fe_weights_commit(FE_MODEL_VLM) build that family: the Qwen2.5-VL decoder (q / k / v with bias,
+ * sectioned M-RoPE over mrope_section, 16 / 24 / 24) with lm_head tied to embed_tokens when the checkpoint has no lm_head.weight or
+ * carries one equal to embed_tokens (2B ties it); vision tower of vis_heads heads of 80 with LayerNorm blocks, fc1 / QuickGELU / fc2 and
+ * attention over each whole image in every block. Defaults of the Python wrapper = Qwen2-VL-2B-Instruct (12 heads over 2 KV heads of 128,
+ * theta 1e6). A later fe_vlm_configure / fe_vlm3_configure selects its family again.
+ * fe_vlm2_encode_images = `model.visual(pixel_values, grid_thw)` of that class: pixel_values [n_patches][1176] fp32 or NULL = the bf16
+ * rows of the last fe_vlm_preprocess_rgb (14-pixel patches, sides multiples of 28, as for Qwen2.5-VL); patch_pos_hw [n_patches][2] =
+ * (row, column) of every patch in the processor's 2x2-block-major order; cu_seqlens [n_seg + 1] = one segment per image. The merged
+ * embeddings [n_patches / 4][hidden] stay on the device for the next fe_vlm_prefill_images(_padded) and are copied to `embeds` when it
+ * is not NULL. Returns FE_ERR_CAPACITY when the batch does not fit. fe_vlm_vision_dims answers 14, 1176, 0, 0 for this family. */
+int fe_vlm2_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads);
+int fe_vlm2_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* cu_seqlens, int n_seg, float* embeds);
+/* Greedy decode that stops (what `generate` does when every row has emitted EOS; all three families): the device loop of fe_vlm_generate /
+ * fe_vlm_generate_scored (out_logprobs NULL / not NULL) for at most max_steps steps. The selection pass marks a sequence finished when it
+ * picks one of eos_ids (n_eos <= 8; a first token in `tokens` that already is one counts); a finished sequence keeps being fed that id. The
+ * count of unfinished sequences lives in device memory; the host reads it after every `poll` (>= 1) steps and stops launching at zero.
+ * steps_run = the steps executed. Rows [0, steps_run) of out_tokens [max_steps][n_seq] are what fe_vlm_generate writes for the same
+ * inputs with every sequence's tail after its first EOS holding that EOS id; rows [steps_run, max_steps) hold each sequence's EOS id.
+ * out_logprobs is NaN after a sequence's first EOS. The captured decode-step graph is the one fe_vlm_generate replays: the stop is a host
+ * decision between replays. */
+int fe_vlm_generate_until(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_ids, int n_seq, int max_steps, const int32_t* eos_ids, int n_eos, int poll,
+                          int32_t* out_tokens, float* out_logprobs, int* steps_run);
+
 /* ---- device buffers (so callers can keep batches resident in HBM without torch) ------------- */
 int fe_dev_alloc(fe_ctx* ctx, size_t bytes, void** d_out);
 int fe_dev_free(fe_ctx* ctx, void* d_ptr);

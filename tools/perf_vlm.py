@@ -37,7 +37,7 @@ ap.add_argument("--batches", default="1,8,32")
 ap.add_argument("--vision", type=int, default=0, help="also time the vision tower: this many images of 1036x1036 pixels (74x74 patches) per call, full depth 32")
 ap.add_argument("--from-rgb", type=int, default=0, help="time vision encode from this many uint8 1036x1036 photos against the fp32 pixel_values upload")
 ap.add_argument("--pad", type=int, default=0, help="also time decode steps with every other sequence left-padded by this many tokens")
-ap.add_argument("--family", default="qwen2_5", choices=("qwen2_5", "qwen3"))
+ap.add_argument("--family", default="qwen2_5", choices=("qwen2_5", "qwen3", "qwen2"))
 ap.add_argument("--qwen25-layers", type=int, default=4, help="--family qwen3: layers of the Qwen2.5-VL-7B decoder timed at batch 4 for comparison")
 ap.add_argument("--scores", action="store_true", help="time fe_vlm_generate_scored against fe_vlm_generate (ms/step) and stop")
 ap.add_argument("--reps", type=int, default=7, help="--scores: alternating repetitions of each loop")
@@ -60,6 +60,77 @@ def decode_rate(e, B, L, new, V):
     return t_pre, t_dec, (t_all - t_pre) / new
 
 
+if a.family == "qwen2":
+    # Qwen2-VL-2B (the composition model) at full depth: tower at 1296 and 5120 patches, prefill, decode ms/step at the --batches, and the
+    # stop-at-EOS loop against the full one at 256 steps when every row finishes by step 64. Every figure beside its HBM-bound estimate.
+    from facet_amd.weights import qwen2_vl_text_spec, qwen2_vl_vision_spec
+    from facet_amd.vlm_composition import QWEN2_VL_2B
+    from facet_amd.vlm_tagger import vision_inputs_qwen2
+    H, NH, NKV, INTER, V, NL = 1536, 12, 2, 8960, 151936, 28
+    t0 = time.time()
+    sd = synthetic_state_dict(None, 3, spec=qwen2_vl_text_spec() + qwen2_vl_vision_spec())
+    print(f"weights drawn in {time.time() - t0:.0f} s ({sum(v.size for v in sd.values()) / 1e9:.2f} G parameters)", flush=True)
+    e = Engine(0, arena_bytes=40 << 30)
+    e.vlm2_configure(**QWEN2_VL_2B)
+    t0 = time.time(); e.load_weights(FE_MODEL_VLM, sd); del sd
+    print(f"committed in {time.time() - t0:.0f} s", flush=True)
+    vis_params = 32 * (4 * 1280 * 1280 + 2 * 1280 * 5120) + 5120 * 5120 + 5120 * 1536 + 1176 * 1280
+    for gh, gw in ((36, 36), (64, 80)):      # 1296 and 5120 patches
+        v = vision_inputs_qwen2([[1, gh, gw]])
+        n = gh * gw
+        pv = np.random.default_rng(0).normal(0, 1, (n, 1176)).astype(np.float32)
+        e.vlm2_encode_images(pv, v["patch_pos_hw"], v["cu_seqlens"], want_embeds=False)
+        rgb = [np.random.default_rng(1).integers(0, 256, (gh * 14, gw * 14, 3), dtype=np.uint8)]
+        e.vlm_preprocess_rgb(rgb, [(gh * 14, gw * 14)], (0.5,) * 3, (0.5,) * 3)
+        e.vlm2_encode_images(None, v["patch_pos_hw"], v["cu_seqlens"], want_embeds=False)
+        e.flops_reset(); e.timer_start()
+        e.vlm2_encode_images(None, v["patch_pos_hw"], v["cu_seqlens"], want_embeds=False)
+        ms = e.timer_stop()
+        attn = 4.0 * 32 * n * n * 1280
+        print(f"vision tower (qwen2, 32 blocks): {n} patches ({n // 4} image tokens), rows resident: {ms:.2f} ms, {e.flops() / ms / 1e9:.1f} TFLOP/s "
+              f"(projections), attention {attn / 1e9:.0f} GFLOP more | weight stream {2 * vis_params / 1e9:.2f} GB = {2 * vis_params / 8e9:.3f} ms at HBM peak "
+              f"(compute-bound: {(2.0 * n * vis_params + attn) / 2.5e12:.2f} ms at 2.5 PFLOP/s dense bf16)", flush=True)
+    layer_params = H * (NH + 2 * NKV) * 128 + NH * 128 * H + 3 * H * INTER
+    wbytes = 2.0 * (NL * layer_params + V * H)
+    for B in [int(b) for b in a.batches.split(",")]:
+        L = a.prompt
+        t_pre, t_dec, t_loop = decode_rate(e, B, L, a.new, V)
+        print(f"qwen2 B={B:3d} L={L}: prefill {t_pre:8.2f} ms = {B * L / t_pre * 1e3:9.0f} tok/s | decode {t_dec:6.3f} ms/step | device-resident loop "
+              f"{t_loop:6.3f} ms/step = {wbytes / t_loop / 1e6:6.0f} GB/s = {wbytes / t_loop / 1e6 / 8000:.2f} of HBM peak (HBM-bound estimate "
+              f"{wbytes / 8e9:.3f} ms/step: {wbytes / 1e9:.2f} GB of bf16 weights per step)", flush=True)
+    # generate_until against generate: 256 steps, EOS ids = what each row emits at step 63 of the full run (every row finishes by step 64)
+    B, L, STEPS = 8, a.prompt, 256
+    p = np.random.default_rng(B).integers(0, V, (B, L)).astype(np.int32)
+    pos = np.full((3, B), L, np.int32)
+    first = e.vlm_prefill(p, max_seq=L + STEPS + 8)
+    full, _, ran = e.vlm_generate_until(first, pos, STEPS, [], poll=8)
+    assert ran == STEPS
+    eos = sorted(set(int(t) for t in full[63]))[:8]
+    import ctypes as C
+    i32p = C.POINTER(C.c_int32)
+    sink = np.empty((STEPS, B), np.int32)
+    tg = 1e9      # the baseline: fe_vlm_generate, which never reads anything back between steps
+    for _ in range(3):
+        first = np.ascontiguousarray(e.vlm_prefill(p, max_seq=L + STEPS + 8), dtype=np.int32)
+        t0 = time.perf_counter()
+        e._ck(e.lib.fe_vlm_generate(e.h, first.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), B, STEPS, sink.ctypes.data_as(i32p)))
+        tg = min(tg, (time.perf_counter() - t0) * 1e3)
+    assert np.array_equal(sink, full)
+    print(f"qwen2 B={B} fe_vlm_generate: {tg:.1f} ms for {STEPS} steps = {tg / STEPS:.3f} ms/step", flush=True)
+    for poll in (8, 1):
+        t = {}
+        for name, ids in (("noeos", []), ("until", eos)):
+            best = 1e9
+            for _ in range(3):
+                first = e.vlm_prefill(p, max_seq=L + STEPS + 8)
+                t0 = time.perf_counter(); _, _, ran = e.vlm_generate_until(first, pos, STEPS, ids, poll=poll); best = min(best, (time.perf_counter() - t0) * 1e3)
+            t[name] = (best, ran)
+        (tn, rn), (tu, ru) = t["noeos"], t["until"]
+        print(f"qwen2 B={B} generate_until poll={poll}: {tu:.1f} ms for {ru} steps: until / generate = {tu / tg:.3f} beside steps_run / {STEPS} = {ru / STEPS:.3f} "
+              f"({tu / ru:.3f} vs {tg / STEPS:.3f} ms/step, {ru // poll} host reads of the running count) | all {rn} steps with the polls and no EOS id: "
+              f"{tn:.1f} ms = {tn / tg:.3f} of generate: the poll syncs cost {(tn - tg) / max(1, rn // poll) * 1e3:.0f} us each", flush=True)
+    e.close()
+    sys.exit(0)
 if a.family == "qwen3":
     from facet_amd.weights import qwen3_vl_text_spec, qwen3_vl_vision_spec
     from facet_amd.vlm_tagger import QWEN3_VL_2B, vision_inputs_qwen3
