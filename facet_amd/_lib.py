@@ -37,7 +37,8 @@ class EngineError(RuntimeError):
 
 class EngineCapacityError(EngineError):
     """The batch did not fit (device memory, arena, KV cache): FE_ERR_CAPACITY, raised by the padded-batch image path only
-    (vlm_preprocess_rgb, vlm_encode_preprocessed, vlm_prefill with pad). Fewer images at a time may fit."""
+    (vlm_preprocess_rgb, vlm_encode_preprocessed, vlm_prefill with pad). Fewer images at a time may fit. jpeg_encode raises it when the
+    caller's `cap` is too small for an image."""
 
 
 FE_ERR_CAPACITY = -4
@@ -163,6 +164,12 @@ SIGNATURES = {
     "fe_leading_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_resize_u8_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "fe_reduce_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "fe_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "fe_jpeg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fe_thumbnail_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
     "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1096,6 +1103,64 @@ class Engine:
                                    small.ctypes.data_as(C.c_void_p) if want_small else None,
                                    lo.ctypes.data_as(C.c_void_p) if want_dct else None))
         return (hashes, small, lo) if (want_small or want_dct) else hashes
+
+    def resize_u8_box(self, imgs, oh, ow, box, filter="lanczos"):
+        """PIL `resize((ow, oh), filter, box)` of a uint8 [n,h,w,3] batch; box = (x0, y0, x1, y1) in source pixels, fractional."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        n, h, w, _ = a.shape
+        b = np.asarray(box, dtype=np.float32).reshape(4)
+        out = np.empty((n, oh, ow, 3), np.uint8)
+        self._ck(self.lib.fe_resize_u8_box(self.h, a.ctypes.data_as(C.c_void_p), n, h, w, oh, ow, FILTERS[filter], b.ctypes.data_as(C.c_void_p), 0,
+                                           out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reduce_u8(self, imgs, factor, box=None):
+        """PIL `reduce(factor, box)` of a uint8 [n,h,w,3] batch: factor an int or (fx, fy), box (x0, y0, x1, y1) in pixels."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        n, h, w, _ = a.shape
+        fx, fy = (factor, factor) if isinstance(factor, int) else factor
+        b = np.asarray(box if box is not None else (0, 0, w, h), dtype=np.int32).reshape(4)
+        out = np.empty((n, -(-int(b[3] - b[1]) // fy), -(-int(b[2] - b[0]) // fx), 3), np.uint8)
+        self._ck(self.lib.fe_reduce_u8(self.h, a.ctypes.data_as(C.c_void_p), n, h, w, fx, fy, b.ctypes.data_as(C.c_void_p), 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def jpeg_bound(self, h, w):
+        """Bytes that no JPEG of an h x w image exceeds (fe_jpeg_bound)."""
+        return int(self.lib.fe_jpeg_bound(int(h), int(w)))
+
+    @staticmethod
+    def _jpeg_rows(out, lengths):
+        return [out[i, :int(lengths[i])].tobytes() for i in range(out.shape[0])]
+
+    def jpeg_encode(self, images, quality=80, bgr=False, cap=None):
+        """uint8 [n,h,w,3] (or device tuple), RGB or (bgr=True) BGR bytes -> list of bytes: what PIL `save(buf, "JPEG", quality=quality)`
+        writes for each image. cap: bytes of room per image (default: fe_jpeg_bound, which always fits; less raises EngineCapacityError
+        when an image needs more)."""
+        p, n, h, w, dev, keep = self._img_ptr(images)
+        cap = self.jpeg_bound(h, w) if cap is None else int(cap)
+        out = np.empty((n, cap), np.uint8)
+        lengths = np.zeros(n, np.int32)
+        self._ck(self.lib.fe_jpeg_encode(self.h, p, n, h, w, 1 if bgr else 0, dev, int(quality), out.ctypes.data_as(C.c_void_p), cap,
+                                         lengths.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths)
+
+    def thumbnail_jpeg(self, images, plan, quality=80, bgr=False):
+        """uint8 [n,h,w,3] (or device tuple) -> list of bytes: the reference's generate_photo_thumbnail of each image; plan =
+        facet_amd.thumbnail.thumbnail_plan(w, h, size). Reduce, resize and encode run back to back on the device."""
+        p, n, h, w, dev, keep = self._img_ptr(images)
+        if (plan.src_w, plan.src_h) != (w, h):
+            raise ValueError(f"thumbnail_jpeg: the plan is for {plan.src_w} x {plan.src_h} images, these are {w} x {h}")
+        ow, oh = plan.size
+        fx, fy = plan.factors
+        rbox = np.asarray(plan.reduce_box, dtype=np.int32).reshape(4) if plan.reduce_box is not None else None
+        box = np.asarray(plan.resize_box, dtype=np.float32).reshape(4)
+        cap = self.jpeg_bound(oh, ow)
+        out = np.empty((n, cap), np.uint8)
+        lengths = np.zeros(n, np.int32)
+        self._ck(self.lib.fe_thumbnail_jpeg(self.h, p, n, h, w, 1 if bgr else 0, dev, oh, ow, fx, fy,
+                                            rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None, box.ctypes.data_as(C.c_void_p),
+                                            1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths)
 
     def hamming_pairs(self, hashes, max_distance, max_pairs=None):
         """hashes: uint64 [n] (host array) or (device_ptr, n). -> int32 [k,2]: every i < j whose hashes differ in at most

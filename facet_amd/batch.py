@@ -10,14 +10,15 @@ the seven technical-metric groups, tags, and the two cross terms the reference d
 isolation_bonus :264-269). What stays with the caller because it needs files, configuration policy or libraries outside the
 hot path: path / EXIF columns, leading lines (CompositionAnalyzer.detect_leading_lines: Canny + probabilistic
 Hough; `detect_lines=True` computes them through `fe_leading_lines`, or pass `leading_lines=` scores in). `phash=True` adds the
-`phash` column (`str(imagehash.phash(pil_img))`, batch_processor.py:216) through `fe_phash`; off by default. With `policy=` (an `aggregate.AggregatePolicy` made from the
+`phash` column (`str(imagehash.phash(pil_img))`, batch_processor.py:216) through `fe_phash`; off by default. `thumbnails=True` adds the
+`thumbnail` column (`generate_photo_thumbnail(pil_img, 640, 80)`, scorer.py:1611-1617: JPEG bytes) through `fe_thumbnail_jpeg`; off by default. With `policy=` (an `aggregate.AggregatePolicy` made from the
 scoring configuration) the category and aggregate score (`Facet.calculate_aggregate_logic`) are computed for the whole batch
 as the last step, from the multi-pass metrics mapping (multi_pass.py:713-752); `metrics_for_aggregate()` returns the
 narrower mapping of the single-pass path (batch_processor.py:272-296).
 
 Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P + SAMP-Net), fe_image_stats (technical scans),
 fe_face_analyze + fe_roi_laplacian (through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
-fe_phash (with `phash=True`).
+fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`).
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -67,10 +68,12 @@ def detect_silhouette(histogram_silhouette, tags, face_count):
 class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
-                 aux_engine=None, phash=False, vlm_composition=None):
+                 aux_engine=None, phash=False, vlm_composition=None, thumbnails=False, thumbnail_size=640, thumbnail_quality=80):
         # Qwen2-VL composition analyzer (facet_amd/vlm_composition.py; the 24gb profile): its SCORE overwrites comp_score, scorer.py:698-705
         self.vlm_composition = vlm_composition
         self.phash = phash      # add the 'phash' column (16 hex digits) from the resident BGR copy
+        # add the 'thumbnail' column (JPEG bytes, generate_photo_thumbnail(pil_img, size, quality)) from the resident BGR copy
+        self.thumbnails, self.thumbnail_size, self.thumbnail_quality = thumbnails, thumbnail_size, thumbnail_quality
         self.engine, self.tagger, self.face_analyzer, self.policy, self.detect_lines = engine, tagger, face_analyzer, policy, detect_lines
         # second context on the same GPU for statistics / faces / lines (see module docstring); None = everything on `engine`, in sequence
         self.aux_engine = aux_engine
@@ -110,17 +113,21 @@ class BatchScorer:
                 if self.phash:      # the same bytes as the PIL image, in B,G,R order
                     from .phash import phash_batch
                     hashes_ = phash_batch(eng, bgr_dev, bgr=True)
-                return tech_, faces_, lines_, hashes_
+                thumbs_ = None
+                if self.thumbnails:
+                    from .thumbnail import thumbnails
+                    thumbs_ = thumbnails(eng, bgr_dev, self.thumbnail_size, self.thumbnail_quality, bgr=True)
+                return tech_, faces_, lines_, hashes_, thumbs_
 
             if self._pool is not None:
                 fut = self._pool.submit(rest, self.aux_engine)      # fe_swap_rb_u8 has synchronised: the BGR copy is complete
                 try:
                     rec, mask = e.ensemble_score(rgb_dev)
                 finally:
-                    tech, faces, leading_lines, hashes = fut.result()      # also on error: the worker must be done before the buffers go
+                    tech, faces, leading_lines, hashes, thumbs = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score(rgb_dev)
-                tech, faces, leading_lines, hashes = rest(e)
+                tech, faces, leading_lines, hashes, thumbs = rest(e)
         finally:
             e.dev_free(d_rgb)
             e.dev_free(d_bgr)
@@ -175,6 +182,8 @@ class BatchScorer:
                 res['leading_lines_score'] = float(leading_lines[i])
             if hashes is not None:
                 res['phash'] = hashes[i]
+            if thumbs is not None:
+                res['thumbnail'] = thumbs[i]
             out.append(res)
         if self.vlm_composition is not None:
             self.apply_vlm_composition(out, imgs)

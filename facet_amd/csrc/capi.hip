@@ -10,6 +10,7 @@
 #include <cmath>
 #include <tuple>
 #include <cstring>
+#include <stdexcept>
 
 using namespace fe;
 
@@ -1203,6 +1204,167 @@ int fe_resize_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, i
   if (!on_device) FE_HIP(hipMemcpyAsync(dst, d_out, out_b, hipMemcpyDeviceToHost, C.stream));
   FE_HIP(hipStreamSynchronize(C.stream));
   FE_API_END(ctx)
+}
+
+/* PIL `resize((ow, oh), filter, box)` with a fractional source box (x0, y0, x1, y1); box NULL = the whole image */
+int fe_resize_u8_box(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, int ow, int filter, const float* box, int on_device,
+                     uint8_t* dst) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(src && dst && n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "bad arguments");
+  const float whole[4] = {0.0f, 0.0f, (float)w, (float)h};
+  C.arena.reset();
+  const size_t in_b = (size_t)n * h * w * 3, out_b = (size_t)n * oh * ow * 3;
+  const uint8_t* d_in = src;
+  uint8_t* d_out = dst;
+  if (!on_device) {
+    uint8_t* t = (uint8_t*)C.arena.alloc(in_b);
+    FE_HIP(hipMemcpyAsync(t, src, in_b, hipMemcpyHostToDevice, C.stream));
+    d_in = t;
+    d_out = (uint8_t*)C.arena.alloc(out_b);
+  }
+  resize_u8_box(C, d_in, n, h, w, oh, ow, filter, box ? box : whole, d_out);
+  if (!on_device) FE_HIP(hipMemcpyAsync(dst, d_out, out_b, hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+
+/* PIL `reduce((fx, fy), box)`: dst [n, ceil(bh / fy), ceil(bw / fx), 3]; box (x0, y0, x1, y1) in pixels, NULL = the whole image */
+int fe_reduce_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int fx, int fy, const int32_t* box, int on_device, uint8_t* dst) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(src && dst && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1, "bad arguments");
+  const int b[4] = {box ? box[0] : 0, box ? box[1] : 0, box ? box[2] : w, box ? box[3] : h};
+  FE_CHECK(b[0] >= 0 && b[1] >= 0 && b[2] <= w && b[3] <= h && b[0] < b[2] && b[1] < b[3], "reduce: box outside the image or empty");
+  const int ow = (b[2] - b[0] + fx - 1) / fx, oh = (b[3] - b[1] + fy - 1) / fy;
+  C.arena.reset();
+  const size_t in_b = (size_t)n * h * w * 3, out_b = (size_t)n * oh * ow * 3;
+  const uint8_t* d_in = src;
+  uint8_t* d_out = dst;
+  if (!on_device) {
+    uint8_t* t = (uint8_t*)C.arena.alloc(in_b);
+    FE_HIP(hipMemcpyAsync(t, src, in_b, hipMemcpyHostToDevice, C.stream));
+    d_in = t;
+    d_out = (uint8_t*)C.arena.alloc(out_b);
+  }
+  reduce_u8(C, d_in, n, h, w, fx, fy, b, d_out);
+  if (!on_device) FE_HIP(hipMemcpyAsync(dst, d_out, out_b, hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+
+// ---- thumbnails: reduce -> boxed LANCZOS resize -> baseline JPEG, one chain on the device ----------------------------------------
+namespace {
+struct ThumbPlan { int oh, ow, fx, fy; int rbox[4]; float box[4]; int tall; };
+struct ThumbOverflow : std::runtime_error { using std::runtime_error::runtime_error; };
+}
+
+// plan NULL: the images are encoded as they are. out [n][cap] and lengths [n] are host buffers.
+static void thumbnail_run(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, const ThumbPlan* plan, int quality,
+                          uint8_t* out, size_t cap, int32_t* lengths) {
+  Ctx& C = ctx->c;
+  int rh = h, rw = w, oh = h, ow = w;
+  bool do_reduce = false, do_resize = false;
+  if (plan) {
+    oh = plan->oh; ow = plan->ow;
+    do_reduce = plan->fx > 1 || plan->fy > 1;
+    if (do_reduce) {
+      FE_CHECK(plan->rbox[0] >= 0 && plan->rbox[1] >= 0 && plan->rbox[2] <= w && plan->rbox[3] <= h && plan->rbox[0] < plan->rbox[2] && plan->rbox[1] < plan->rbox[3],
+               "thumbnail: reduce box outside the image or empty");
+      rw = (plan->rbox[2] - plan->rbox[0] + plan->fx - 1) / plan->fx;
+      rh = (plan->rbox[3] - plan->rbox[1] + plan->fy - 1) / plan->fy;
+    }
+    do_resize = oh != rh || ow != rw || plan->box[0] != 0.0f || plan->box[1] != 0.0f || plan->box[2] != (float)rw || plan->box[3] != (float)rh;
+  }
+  FE_CHECK(oh > 0 && ow > 0 && oh <= 65535 && ow <= 65535, "thumbnail: bad output size %d x %d", ow, oh);
+  const size_t dcap = std::min(cap, jpeg_bound(oh, ow));      // no encode is longer, so the device rows need not be
+  const size_t per_in = (size_t)h * w * 3;
+  const size_t per = (do_reduce ? (size_t)rh * rw * 3 : 0) + (do_resize ? (size_t)rh * ow * 3 + (size_t)rw * oh * 3 + (size_t)oh * ow * 3 : 0) +
+                     jpeg_scratch_bytes(oh, ow) + dcap + 2048;
+  const size_t budget = std::min<size_t>((size_t)1 << 30, C.arena.capacity() - C.arena.capacity() / 8);
+  int mb = (int)std::max<size_t>(1, std::min<size_t>(256, budget / per));
+  if (!on_device) mb = (int)std::max<size_t>(1, std::min<size_t>(mb, ((size_t)1 << 30) / per_in));
+  std::vector<int32_t> lens(n);
+  ImageStager st(ctx, img, n, per_in, mb, on_device);
+  bool overflow = false;
+  for (int k = 0; k < st.chunks(); ++k) {
+    const int i0 = k * mb, nb = st.count(k);
+    C.arena.reset();
+    const uint8_t* cur = st.get(k);
+    if (do_reduce) {
+      uint8_t* d = (uint8_t*)C.arena.alloc((size_t)nb * rh * rw * 3);
+      reduce_u8(C, cur, nb, h, w, plan->fx, plan->fy, plan->rbox, d);
+      cur = d;
+    }
+    if (do_resize) {
+      uint8_t* d = (uint8_t*)C.arena.alloc((size_t)nb * oh * ow * 3);
+      if (plan->tall) {      // Image.resize's two calls for images more than 100 times taller than wide: rows first, then columns
+        uint8_t* mid = (uint8_t*)C.arena.alloc((size_t)nb * oh * rw * 3);
+        const float b1[4] = {0.0f, plan->box[1], (float)rw, plan->box[3]}, b2[4] = {plan->box[0], 0.0f, plan->box[2], (float)oh};
+        resize_u8_box(C, cur, nb, rh, rw, oh, rw, FE_FILTER_LANCZOS, b1, mid);
+        resize_u8_box(C, mid, nb, oh, rw, oh, ow, FE_FILTER_LANCZOS, b2, d);
+      } else {
+        resize_u8_box(C, cur, nb, rh, rw, oh, ow, FE_FILTER_LANCZOS, plan->box, d);
+      }
+      cur = d;
+    }
+    uint8_t* d_out = (uint8_t*)C.arena.alloc((size_t)nb * dcap);
+    int32_t* d_len = (int32_t*)C.arena.alloc((size_t)nb * sizeof(int32_t));
+    launch_jpeg_encode(C, cur, nb, oh, ow, bgr ? 1 : 0, quality, d_out, dcap, d_len);
+    st.done(k);
+    FE_HIP(hipMemcpyAsync(lens.data() + i0, d_len, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    for (int i = 0; i < nb; ++i) {
+      const int32_t len = lens[i0 + i];
+      lengths[i0 + i] = len;
+      if (len <= 0 || (size_t)len > cap) { overflow = true; continue; }
+      FE_HIP(hipMemcpyAsync(out + (size_t)(i0 + i) * cap, d_out + (size_t)i * dcap, (size_t)len, hipMemcpyDeviceToHost, C.stream));
+    }
+    FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next chunk
+  }
+  if (overflow) {
+    char b[160];
+    snprintf(b, sizeof(b), "jpeg: an image needs more than the %zu bytes of its output row (fe_jpeg_bound(%d, %d) = %zu always fits)", cap, oh, ow, jpeg_bound(oh, ow));
+    throw ThumbOverflow(b);
+  }
+}
+
+size_t fe_jpeg_bound(int h, int w) { return (h > 0 && w > 0) ? jpeg_bound(h, w) : 0; }
+
+#define FE_THUMB_END(ctx)                         \
+  }                                               \
+  catch (const ThumbOverflow& e) {                \
+    (ctx)->c.err = e.what();                      \
+    fe_drain(ctx);                                \
+    return FE_ERR_CAPACITY;                       \
+  }                                               \
+  catch (const std::exception& e) {               \
+    (ctx)->c.err = e.what();                      \
+    fe_drain(ctx);                                \
+    return FE_ERR_RUNTIME;                        \
+  }                                               \
+  return FE_OK;
+
+/* what Pillow's `Image.save(buf, "JPEG", quality=q)` writes for each RGB (bgr = 1: B,G,R bytes) image of the batch */
+int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int quality, uint8_t* out, size_t cap,
+                   int32_t* lengths) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(img && out && lengths && n > 0 && h > 0 && w > 0, "bad arguments");
+  thumbnail_run(ctx, img, n, h, w, bgr, on_device, nullptr, quality, out, cap, lengths);
+  FE_THUMB_END(ctx)
+}
+
+/* the reference's generate_photo_thumbnail (utils/image_transforms.py:32-50) for a batch, with the plan of facet_amd.thumbnail.thumbnail_plan */
+int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int oh, int ow, int fx, int fy,
+                      const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(img && out && lengths && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1, "bad arguments");
+  FE_CHECK((fx == 1 && fy == 1) || reduce_box, "thumbnail: reduce factors without a reduce box");
+  ThumbPlan p;
+  p.oh = oh; p.ow = ow; p.fx = fx; p.fy = fy; p.tall = tall;
+  for (int i = 0; i < 4; ++i) { p.rbox[i] = reduce_box ? reduce_box[i] : 0; p.box[i] = resize_box[i]; }
+  thumbnail_run(ctx, img, n, h, w, bgr, on_device, &p, quality, out, cap, lengths);
+  FE_THUMB_END(ctx)
 }
 
 // uint8 images -> the model's normalised NHWC4 input, preprocessing exactly like the reference's PIL/torchvision path

@@ -195,13 +195,25 @@ TensorT<T> resnet_forward(Ctx& c, const ResNet& r, const Tensor& x_nhwc4, std::v
 enum ResizeFilter : int { FE_FILTER_LANCZOS = 1, FE_FILTER_BILINEAR = 2, FE_FILTER_BICUBIC = 3 };  // PIL's enum values
 struct ResizeCoeffs { std::vector<int> kk, bounds; int ksize = 0, out = 0; };
 struct ResizeCoeffsDev { int* kk = nullptr; int* bounds = nullptr; int ksize = 0; };
+// in0 / in1: the source interval the outputs cover (PIL passes the box as C floats); the whole axis is (0, in_size)
 void build_resize_coeffs(int in_size, int out_size, int filter, ResizeCoeffs& rc);
+void build_resize_coeffs(int in_size, float in0, float in1, int out_size, int filter, ResizeCoeffs& rc);
 // third member of a Ctx::resize_cache key that is no PIL filter: fe_phash's tables to 32 samples (LANCZOS, or the identity for a skipped pass)
 constexpr int FE_FILTER_KEY_PHASH = -1;
 struct Ctx;
 const ResizeCoeffsDev& upload_resize_coeffs(Ctx& c, const std::tuple<int, int, int>& key, const ResizeCoeffs& rc);
 void resize_u8(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow, int filter, int y0, int ch, int x0,
                int cw, uint8_t* d_dst);
+// PIL `resize((ow, oh), filter, box)`: box = (x0, y0, x1, y1) in source pixels, fractional; the support is clamped to the image, not the box
+void resize_u8_box(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow, int filter, const float box[4], uint8_t* d_dst);
+
+// ---- thumbnails: Pillow's box reduce + baseline JPEG encoder (kernels_jpeg.hip, jpeg_core.h) ------------
+// PIL `reduce((fx, fy), box)`: d_dst [n][ceil(bh / fy)][ceil(bw / fx)][3]
+void reduce_u8(Ctx& c, const uint8_t* d_src, int n, int h, int w, int fx, int fy, const int box[4], uint8_t* d_dst);
+size_t jpeg_bound(int h, int w);                          // bytes no encode of an h x w image exceeds
+size_t jpeg_scratch_bytes(int h, int w);      // arena bytes per image of launch_jpeg_encode
+// d_out [n][cap]; d_lengths [n]: bytes written, or < 0 when the image needs more than cap (nothing is stored past cap)
+void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, int quality, uint8_t* d_out, size_t cap, int32_t* d_lengths);
 
 // ---- perceptual hash + all-pairs Hamming search (kernels_phash.hip) ------------------------------------
 void phash_cos_table(double* out);                       // [8][32] = cos(pi k (2n+1) / 64), host
@@ -260,6 +272,9 @@ struct Ctx {
   size_t topiq_f32_below = 0;   // 2-byte TOPIQ: images with fewer pixels run on the model's fp32 weights (fe_topiq_f32_below; 0 = never)
 
   std::map<std::tuple<int, int, int>, ResizeCoeffsDev> resize_cache;  // (in, out, filter) -> device tables
+  // (in, out, filter, bits of box start, bits of box end) -> device tables of a boxed resize
+  std::map<std::tuple<int, int, int, uint32_t, uint32_t>, ResizeCoeffsDev> resize_box_cache;
+  std::map<std::tuple<int, int, int>, void*> jpeg_cache;               // (h, w, quality) -> jpeg::Tables on the device
   WeightStore staging[8];
   std::unique_ptr<struct TopiqModel> topiq;
   std::unique_ptr<struct U2NetPModel> u2netp;

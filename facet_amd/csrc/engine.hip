@@ -55,6 +55,8 @@ const float* to_f32(Ctx& c, const f16* p, size_t n) {
 
 Ctx::~Ctx() {
   topiq.reset();
+  for (auto& kv : resize_box_cache) { (void)hipFree(kv.second.kk); (void)hipFree(kv.second.bounds); }
+  for (auto& kv : jpeg_cache) (void)hipFree(kv.second);
   arena.release();
   if (stream) (void)hipStreamDestroy(stream);
 }

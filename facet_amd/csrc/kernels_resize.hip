@@ -11,6 +11,7 @@
 // kernels with the same int32 arithmetic, so results are bit-exact (tests/test_resize_gpu.py compares with PIL itself).
 #include "engine.h"
 #include <cmath>
+#include <cstring>
 
 namespace fe {
 
@@ -28,6 +29,11 @@ static double filt_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc_filt
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 
 void build_resize_coeffs(int in_size, int out_size, int filter, ResizeCoeffs& rc) {
+  build_resize_coeffs(in_size, 0.0f, (float)in_size, out_size, filter, rc);
+}
+
+// Resample.c precompute_coeffs: in0 / in1 are C floats there too, their difference is taken in float
+void build_resize_coeffs(int in_size, float in0, float in1, int out_size, int filter, ResizeCoeffs& rc) {
   double (*f)(double);
   double fsupport;
   switch (filter) {
@@ -36,9 +42,8 @@ void build_resize_coeffs(int in_size, int out_size, int filter, ResizeCoeffs& rc
     case FE_FILTER_LANCZOS: f = filt_lanczos; fsupport = 3.0; break;
     default: throw Error("resize: unknown filter " + std::to_string(filter));
   }
-  const double in0 = 0.0, in1 = (double)in_size;
   double scale, filterscale;
-  filterscale = scale = (in1 - in0) / out_size;
+  filterscale = scale = (double)(in1 - in0) / out_size;
   if (filterscale < 1.0) filterscale = 1.0;
   const double support = fsupport * filterscale;
   const int ksize = (int)std::ceil(support) * 2 + 1;
@@ -153,6 +158,26 @@ static const ResizeCoeffsDev& coeffs_dev(Ctx& c, int in_size, int out_size, int 
   return upload_resize_coeffs(c, key, rc);
 }
 
+static const ResizeCoeffsDev& coeffs_dev_box(Ctx& c, int in_size, float in0, float in1, int out_size, int filter) {
+  uint32_t b0, b1;
+  memcpy(&b0, &in0, 4); memcpy(&b1, &in1, 4);
+  const auto key = std::make_tuple(in_size, out_size, filter, b0, b1);
+  auto it = c.resize_box_cache.find(key);
+  if (it != c.resize_box_cache.end()) return it->second;
+  ResizeCoeffs rc;
+  build_resize_coeffs(in_size, in0, in1, out_size, filter, rc);
+  for (int i = 0; i < out_size; ++i)
+    FE_CHECK(rc.bounds[2 * i] >= 0 && rc.bounds[2 * i + 1] >= 0 && rc.bounds[2 * i + 1] <= rc.ksize && rc.bounds[2 * i] + rc.bounds[2 * i + 1] <= in_size,
+             "resize: coefficient window leaves the axis");
+  ResizeCoeffsDev d;
+  d.ksize = rc.ksize;
+  FE_HIP(hipMalloc((void**)&d.kk, rc.kk.size() * sizeof(int)));
+  FE_HIP(hipMalloc((void**)&d.bounds, rc.bounds.size() * sizeof(int)));
+  FE_HIP(hipMemcpy(d.kk, rc.kk.data(), rc.kk.size() * sizeof(int), hipMemcpyHostToDevice));
+  FE_HIP(hipMemcpy(d.bounds, rc.bounds.data(), rc.bounds.size() * sizeof(int), hipMemcpyHostToDevice));
+  return c.resize_box_cache.emplace(key, d).first->second;
+}
+
 static inline int grid_sz(size_t work) { size_t g = (work + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }
 
 // d_src [n][h][w][3] u8 (device) -> d_dst [n][ch][cw][3]: PIL resize to (ow, oh) then crop (x0,y0,cw,ch).
@@ -182,6 +207,33 @@ void resize_u8(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow
   }
   FE_HIP(hipGetLastError());
   c.arena.rewind(mark);  // the intermediate is only read by the kernel just queued on this same stream
+}
+
+// PIL's Image.resize((ow, oh), filter, box) (ImagingResample): a pass runs when its axis changes size or the box does not span it;
+// the horizontal pass comes first, over every row (PIL runs it over the rows the vertical pass reads: the same bytes).
+void resize_u8_box(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow, int filter, const float box[4], uint8_t* d_dst) {
+  FE_CHECK(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "resize: bad geometry");
+  FE_CHECK(box[0] >= 0.0f && box[1] >= 0.0f && box[2] <= (float)w && box[3] <= (float)h && box[0] < box[2] && box[1] < box[3],
+           "resize: box (%g, %g, %g, %g) outside the %d x %d image or empty", box[0], box[1], box[2], box[3], w, h);
+  const bool need_h = ow != w || box[0] != 0.0f || box[2] != (float)w;
+  const bool need_v = oh != h || box[1] != 0.0f || box[3] != (float)h;
+  const uint8_t* cur = d_src;
+  const size_t mark = c.arena.mark();
+  if (need_h) {
+    const ResizeCoeffsDev& t = coeffs_dev_box(c, w, box[0], box[2], ow, filter);
+    uint8_t* dst = need_v ? (uint8_t*)c.arena.alloc((size_t)n * h * ow * 3) : d_dst;
+    hipLaunchKernelGGL(resize_h_kernel, dim3(grid_sz((size_t)n * h * ow)), dim3(256), 0, c.stream, cur, dst, t.kk, t.bounds, t.ksize, (size_t)n * h, w, ow);
+    FE_HIP(hipGetLastError());
+    cur = dst;
+  }
+  if (need_v) {
+    const ResizeCoeffsDev& t = coeffs_dev_box(c, h, box[1], box[3], oh, filter);
+    hipLaunchKernelGGL(resize_v_kernel, dim3(grid_sz((size_t)n * oh * ow)), dim3(256), 0, c.stream, cur, d_dst, t.kk, t.bounds, t.ksize, n, h, ow, 0, oh, 0, ow);
+  } else if (!need_h) {
+    hipLaunchKernelGGL(crop_u8_kernel, dim3(grid_sz((size_t)n * oh * ow * 3)), dim3(256), 0, c.stream, cur, d_dst, n, h, w, 0, oh, 0, ow);
+  }
+  FE_HIP(hipGetLastError());
+  c.arena.rewind(mark);
 }
 
 }  // namespace fe

@@ -35,7 +35,8 @@ enum fe_status {
   FE_ERR_RUNTIME = -2,   /* HIP failure or internal check */
   FE_ERR_NOT_LOADED = -3, /* model weights not committed */
   FE_ERR_CAPACITY = -4   /* the batch does not fit (device memory, arena, KV cache): returned by fe_vlm_preprocess_rgb,
-                            fe_vlm_encode_preprocessed, fe_vlm3_encode_images and fe_vlm_prefill_images_padded only - retry with fewer images */
+                            fe_vlm_encode_preprocessed, fe_vlm3_encode_images and fe_vlm_prefill_images_padded - retry with fewer images - and by
+                            fe_jpeg_encode / fe_thumbnail_jpeg when an output row is too small for its image */
 };
 
 /* Model slots (reference names: models/model_manager.py:393-437 'topiq','clip','samp_net',...). */
@@ -306,6 +307,33 @@ enum fe_filter { FE_LANCZOS = 1, FE_BILINEAR = 2, FE_BICUBIC = 3 }; /* PIL.Image
  * (models/pyiqa_scorer.py:153 LANCZOS; torchvision Resize inside models/samp_net.py:823-830; open_clip transform). */
 int fe_resize_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, int ow, int filter, int on_device,
                  uint8_t* dst);
+
+/* The same with a fractional source box: PIL `image.resize((ow,oh), filter, box)`, box = (x0, y0, x1, y1) in source pixels as C
+ * floats (what PIL's own C entry takes); NULL = the whole image. Output sample xx is centred at x0 + (xx + 0.5)(x1 - x0)/ow and its
+ * support is clamped to the image, not to the box. */
+int fe_resize_u8_box(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, int ow, int filter, const float* box, int on_device,
+                     uint8_t* dst);
+/* PIL `image.reduce((fx, fy), box)`: integer box (x0, y0, x1, y1), NULL = the whole image; dst [n, ceil((y1-y0)/fy), ceil((x1-x0)/fx), 3].
+ * Rounded means of fx*fy samples; the last column / row / corner average what remains (libImaging/Reduce.c, bit-exact). */
+int fe_reduce_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int fx, int fy, const int32_t* box, int on_device, uint8_t* dst);
+
+/* ---- thumbnails: baseline JPEG encoder (byte-exact with Pillow + libjpeg defaults) ----------------------- */
+/* Bytes that no encode of an h x w image can exceed (every block at its longest code, every byte stuffed, header, EOI). */
+size_t fe_jpeg_bound(int h, int w);
+/* img [n,h,w,3] uint8 (bgr = 1: the bytes are B,G,R) -> what PIL `image.save(buf, "JPEG", quality=quality)` writes for each image:
+ * JFIF 1.01, YCbCr 4:2:0, integer slow DCT, standard Huffman tables (utils/image_transforms.py:49). out [n][cap] and lengths [n] are
+ * host buffers; image i occupies out[i*cap .. i*cap + lengths[i]). When an image needs more than cap bytes the call returns
+ * FE_ERR_CAPACITY with a message, lengths[i] is minus the bytes needed (or INT32_MIN) and its row is left alone; nothing is ever stored
+ * past a row. cap = fe_jpeg_bound(h, w) always fits. */
+int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int quality, uint8_t* out, size_t cap,
+                   int32_t* lengths);
+/* generate_photo_thumbnail (utils/image_transforms.py:32-50; processing/scorer.py:1611-1617, :1680-1686) of a batch:
+ * `thumb.thumbnail((size, size), LANCZOS); thumb.save(buf, "JPEG", quality=quality)` as reduce -> boxed LANCZOS resize -> encode on the
+ * device. (ow, oh), (fx, fy), reduce_box (x0, y0, x1, y1; may be NULL when fx = fy = 1), resize_box (in pixels of the reduced image) and
+ * tall (the reduced image is more than 100 times taller than wide: PIL resizes rows first) are facet_amd.thumbnail.thumbnail_plan's values
+ * for (w, h, size). out / cap / lengths as fe_jpeg_encode, with cap against fe_jpeg_bound(oh, ow). */
+int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int oh, int ow, int fx, int fy,
+                      const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
 /* ---- image-level entry points (uint8 HWC images in, per-image results out) ------------------------------ */
 /* CLIP from raw RGB images: open_clip eval transform on the GPU (PIL-bicubic shorter side -> 224, center crop 224,
