@@ -170,6 +170,8 @@ SIGNATURES = {
     "fe_jpeg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_thumbnail_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fe_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fe_jpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
     "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1161,6 +1163,46 @@ class Engine:
                                             rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None, box.ctypes.data_as(C.c_void_p),
                                             1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)
+
+    @staticmethod
+    def jpeg_probe(blob):
+        """The markers of one JPEG file (bytes) -> dict(width, height, components, hsamp, vsamp, restart_interval, orientation, status);
+        status 0: jpeg_decode takes the file, > 0: a kind it leaves to Pillow, < 0: corrupt (JPEG_STATUS names them). Host only."""
+        blob = bytes(blob)
+        info = (C.c_int32 * 8)()
+        rc = load_library().fe_jpeg_probe(blob, len(blob), info)
+        if rc != 0:
+            raise EngineError("fe_jpeg_probe failed")
+        return dict(zip(("width", "height", "components", "hsamp", "vsamp", "restart_interval", "orientation", "status"), (int(v) for v in info)))
+
+    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False):
+        """JPEG files (a list of bytes) whose decoded size is h x w -> (pixels, status). pixels: uint8 [n,h,w,3], what Pillow's
+        `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives (apply_orientation=False: without the transpose; bgr: B,G,R bytes),
+        a host array, or with device=True a (device_ptr, n, h, w) tuple whose buffer the caller releases with dev_free (device=<pointer>
+        decodes into the caller's own buffer). status: int32 [n], 0 where the image was decoded; the slot of any other image is left as it
+        was (zeros in a host array allocated here, undefined in a device buffer allocated here)."""
+        blobs = [bytes(b) for b in blobs]
+        n = len(blobs)
+        if n == 0:
+            raise ValueError("jpeg_decode: no files")
+        ptrs = (C.c_char_p * n)(*blobs)
+        lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+        status = np.zeros(n, np.int32)
+        if device is False or device is None:
+            out = np.zeros((n, h, w, 3), np.uint8)
+            self._ck(self.lib.fe_jpeg_decode(self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, 0,
+                                             out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+            return out, status
+        own = device is True
+        d = self.dev_alloc(n * h * w * 3) if own else device
+        try:
+            self._ck(self.lib.fe_jpeg_decode(self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, 1,
+                                             d, status.ctypes.data_as(C.c_void_p)))
+        except Exception:
+            if own:
+                self.dev_free(d)
+            raise
+        return (d, n, h, w), status
 
     def hamming_pairs(self, hashes, max_distance, max_pairs=None):
         """hashes: uint64 [n] (host array) or (device_ptr, n). -> int32 [k,2]: every i < j whose hashes differ in at most

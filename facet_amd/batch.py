@@ -86,17 +86,29 @@ class BatchScorer:
         self.tag_threshold, self.max_tags = tag_threshold, max_tags           # utils/tags.py:50-51 defaults
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
-    def process_batch(self, images_rgb, exif=None, leading_lines=None):
+    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
-        leading_lines_score, both only used by the aggregate step (policy given)."""
-        imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
-        n, h, w, _ = imgs.shape
-        # one upload; the BGR copy the reference keeps as img_cv is made on the device, and every engine call reads the resident batch
+        leading_lines_score, both only used by the aggregate step (policy given).
+        _resident (process_files): (device_ptr, n, h, w) of an RGB batch that is already on the device, handed over - it is freed here -
+        with images_rgb None; the pixels are fetched only when a stage that works on host arrays (faces, the VLM analyzer) is on."""
         e = self.engine
-        d_rgb, d_bgr = e.dev_alloc(imgs.nbytes), e.dev_alloc(imgs.nbytes)
+        if _resident is None:
+            imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
+            n, h, w, _ = imgs.shape
+            d_rgb = e.dev_alloc(imgs.nbytes)
+        else:
+            imgs = None
+            d_rgb, n, h, w = _resident
+        d_bgr = None
         try:
-            e.h2d(d_rgb, imgs)
+            # one upload; the BGR copy the reference keeps as img_cv is made on the device, and every engine call reads the resident batch
+            if _resident is None:
+                e.h2d(d_rgb, imgs)
+            elif (self.face_analyzer is not None and self.face_analyzer.available) or self.vlm_composition is not None:
+                imgs = np.empty((n, h, w, 3), np.uint8)
+                e.d2h(imgs, d_rgb)
+            d_bgr = e.dev_alloc(n * h * w * 3)
             e.swap_rb(d_rgb, n * h * w, d_bgr)
             rgb_dev, bgr_dev = (d_rgb, n, h, w), (d_bgr, n, h, w)
 
@@ -130,7 +142,8 @@ class BatchScorer:
                 tech, faces, leading_lines, hashes, thumbs = rest(e)
         finally:
             e.dev_free(d_rgb)
-            e.dev_free(d_bgr)
+            if d_bgr is not None:
+                e.dev_free(d_bgr)
         tags = None
         if self.tagger is not None and self.tagger.text_embeddings is not None and mask & 2:
             tags = self.tagger.get_tags_batch(rec[:, 21:789], self.engine, self.tag_threshold, self.max_tags)
@@ -218,6 +231,31 @@ class BatchScorer:
         for idx in groups.values():
             res = self.process_batch(np.stack([arrs[i] for i in idx]), exif=[exif[i] for i in idx] if exif else None,
                                      leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None)
+            for i, r in zip(idx, res):
+                out[i] = r
+        return out
+
+    def process_files(self, paths_or_blobs, exif=None, leading_lines=None):
+        """Image FILES (paths, or the files' bytes) instead of decoded arrays: the reference's `_load_images` + batch step. JPEG files the
+        engine decodes (facet_amd.image_loading) are decoded on the device per output size and scored from that resident batch, with no
+        copy of the pixels down and up again; every other file is opened with Pillow as load_image_from_path does and goes through
+        process_images. Results come back in input order; a file the reference could not load gives None."""
+        from .image_loading import decode_groups, pillow_rgb, read_blob
+        blobs = [read_blob(p) for p in paths_or_blobs]
+        out = [None] * len(blobs)
+        e = self.engine
+        groups, rest = decode_groups(e, blobs, device=True)
+        for idx, dev in groups:
+            res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
+                                     leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev)
+            for i, r in zip(idx, res):
+                out[i] = r
+        arrs = [(i, pillow_rgb(blobs[i])) for i in rest]
+        arrs = [(i, a) for i, a in arrs if a is not None]
+        if arrs:
+            idx = [i for i, _ in arrs]
+            res = self.process_images([a for _, a in arrs], exif=[exif[i] for i in idx] if exif else None,
+                                      leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None)
             for i, r in zip(idx, res):
                 out[i] = r
         return out

@@ -1367,6 +1367,29 @@ int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int 
   FE_THUMB_END(ctx)
 }
 
+/* ---- JPEG decode: what `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives, from the file's bytes ---- */
+int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info) {
+  if (!info) return FE_ERR_INVALID;
+  try {
+    int32_t v[8];
+    static const uint8_t none[1] = {0};
+    jpeg_probe(data ? data : none, data ? len : 0, v);
+    info->width = v[0]; info->height = v[1]; info->components = v[2]; info->hsamp = v[3]; info->vsamp = v[4];
+    info->restart_interval = v[5]; info->orientation = v[6]; info->status = v[7];
+  } catch (const std::exception&) {
+    return FE_ERR_RUNTIME;
+  }
+  return FE_OK;
+}
+
+int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                   uint8_t* dst, int32_t* status) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0, "bad arguments");
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, dst, status);
+  FE_API_END(ctx)
+}
+
 // uint8 images -> the model's normalised NHWC4 input, preprocessing exactly like the reference's PIL/torchvision path
 static Tensor preprocess_square224(Ctx& C, const uint8_t* d_rgb, int nb, int h, int w, int filter, bool shorter_side_crop,
                                    const float mean[3], const float stdv[3], int bgr) {

@@ -215,6 +215,11 @@ size_t jpeg_scratch_bytes(int h, int w);      // arena bytes per image of launch
 // d_out [n][cap]; d_lengths [n]: bytes written, or < 0 when the image needs more than cap (nothing is stored past cap)
 void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, int quality, uint8_t* d_out, size_t cap, int32_t* d_lengths);
 
+// ---- JPEG decode: file bytes -> resident uint8 batch, Pillow's pixels (kernels_jpeg_dec.hip, jpeg_dec_core.h) ----
+void jpeg_probe(const uint8_t* data, size_t len, int32_t out[8]);      // the fields of fe_jpeg_info, host only
+void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                       uint8_t* dst, int32_t* status);
+
 // ---- perceptual hash + all-pairs Hamming search (kernels_phash.hip) ------------------------------------
 void phash_cos_table(double* out);                       // [8][32] = cos(pi k (2n+1) / 64), host
 size_t phash_tmp_bytes(int n, int h);
@@ -275,6 +280,8 @@ struct Ctx {
   // (in, out, filter, bits of box start, bits of box end) -> device tables of a boxed resize
   std::map<std::tuple<int, int, int, uint32_t, uint32_t>, ResizeCoeffsDev> resize_box_cache;
   std::map<std::tuple<int, int, int>, void*> jpeg_cache;               // (h, w, quality) -> jpeg::Tables on the device
+  void* jpegdec_stage = nullptr;      // pinned host block of fe_jpeg_decode's single upload; grows, never shrinks
+  size_t jpegdec_stage_cap = 0;
   WeightStore staging[8];
   std::unique_ptr<struct TopiqModel> topiq;
   std::unique_ptr<struct U2NetPModel> u2netp;

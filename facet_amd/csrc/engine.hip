@@ -57,6 +57,7 @@ Ctx::~Ctx() {
   topiq.reset();
   for (auto& kv : resize_box_cache) { (void)hipFree(kv.second.kk); (void)hipFree(kv.second.bounds); }
   for (auto& kv : jpeg_cache) (void)hipFree(kv.second);
+  if (jpegdec_stage) (void)hipHostFree(jpegdec_stage);
   arena.release();
   if (stream) (void)hipStreamDestroy(stream);
 }

@@ -1,0 +1,656 @@
+// Baseline JPEG decoding arithmetic shared by the kernels of kernels_jpeg_dec.hip and by host code: the inverse of jpeg_core.h.
+// libjpeg's Huffman decoder (jdhuff.c), dequantiser + integer slow IDCT (jidctint.c), fancy upsampling (jdsample.c) and YCbCr -> RGB
+// (jdcolor.c), restated per segment / block / pixel. Integer end to end, so the same functions give the same pixels on the device and on
+// the host, and those are the pixels of Pillow's `Image.open(f).convert('RGB')`.
+//
+// Layout of a decode: an image's entropy data is cut at its restart markers into segments (one when it has none); a segment decodes
+// serially into int16 coefficient blocks in natural order, stored per component in that component's block grid padded to whole MCUs
+// (DecGeom); every block is dequantised and transformed into its component's plane; a pixel takes its luma sample, its two chroma samples
+// through the triangle filters and the colour conversion, and lands at the address its EXIF orientation gives it.
+#pragma once
+#include <string.h>
+
+#include <vector>
+
+#include "jpeg_core.h"
+
+namespace fe {
+namespace jpegdec {
+
+// status of an image: 0 decoded, > 0 a kind of file this decoder leaves to the caller, < 0 a corrupt stream (FE_JPEG_* of facet_engine.h)
+enum Status : int32_t {
+  ST_OK = 0,
+  ST_PROGRESSIVE = 1,      // SOF2
+  ST_ARITHMETIC = 2,       // SOF9 .. SOF15, DAC
+  ST_PRECISION = 3,        // 12-bit (or any precision but 8)
+  ST_COMPONENTS = 4,       // 4 components (CMYK / YCCK), 2 components
+  ST_ADOBE_RGB = 5,        // 3 components stored as RGB (Adobe transform 0, or component ids 'R' 'G' 'B')
+  ST_SAMPLING = 6,         // sampling factors other than luma 1x1 / 2x1 / 2x2 with chroma 1x1
+  ST_MULTISCAN = 7,        // more than one scan
+  ST_OTHER = 8,            // lossless / hierarchical frames, DNL, scan components out of frame order, EXIF blocks only Pillow should judge
+  ST_BAD_MARKER = -1,
+  ST_BAD_HUFFMAN = -2,
+  ST_PREMATURE_END = -3,
+  ST_BAD_RESTART = -4,
+  ST_BAD_DIMENSIONS = -5,
+  ST_BAD_COEFFICIENT = -6,   // samples so far out of range that libjpeg's own IDCT variants (C, SIMD) stop agreeing with each other
+};
+
+constexpr int LOOK_BITS = 9;
+
+struct HuffDec {                       // jdhuff.c d_derived_tbl
+  uint16_t look[1 << LOOK_BITS];       // next LOOK_BITS bits -> length << 8 | symbol; 0: the code is longer
+  int32_t maxcode[17];                 // [l]: largest code of length l, -1 when there is none
+  int32_t valoff[17];                  // [l]: index into vals of the first code of length l, minus that code
+  uint8_t vals[256];
+};
+
+struct DecTables {                     // one per image
+  uint16_t q[4][64];                   // natural order
+  HuffDec huff[8];                     // 0 .. 3 DC, 4 .. 7 AC
+};
+
+struct DecGeom {
+  int w, h, ncomp, hs, vs;             // hs, vs: luma sampling (1 for grayscale)
+  int mw, mh;                          // MCUs per row / column
+  int bw[3], bh[3];                    // blocks per row / column of each component's padded grid
+  uint32_t blk_off[3];                 // first block of each component in the image's coefficient buffer
+  uint32_t plane_off[3];               // first byte of each component in the image's plane buffer; a plane is [bh * 8][bw * 8]
+  uint32_t nblk, plane_bytes;
+  int cw, ch;                          // real extent of a chroma plane: ceil(w / hs), ceil(h / vs)
+};
+
+FE_JHD DecGeom make_dec_geom(int w, int h, int ncomp, int hs, int vs) {
+  DecGeom g;
+  g.w = w; g.h = h; g.ncomp = ncomp; g.hs = hs; g.vs = vs;
+  g.mw = (w + 8 * hs - 1) / (8 * hs); g.mh = (h + 8 * vs - 1) / (8 * vs);
+  uint32_t b = 0, p = 0;
+  for (int c = 0; c < 3; ++c) {
+    const bool on = c < ncomp;
+    g.bw[c] = on ? g.mw * (c ? 1 : hs) : 0; g.bh[c] = on ? g.mh * (c ? 1 : vs) : 0;
+    g.blk_off[c] = b; g.plane_off[c] = p;
+    b += (uint32_t)g.bw[c] * g.bh[c]; p += (uint32_t)g.bw[c] * g.bh[c] * 64;
+  }
+  g.nblk = b; g.plane_bytes = p;
+  g.cw = (w + hs - 1) / hs; g.ch = (h + vs - 1) / vs;
+  return g;
+}
+
+// ---- bit reader over one segment ---------------------------------------------------------------------------------------------------
+// The bytes of all files of a call sit in one buffer whose start is 16-byte aligned and whose size is a multiple of 16, so the aligned
+// 16-byte chunk around any byte of a segment is inside it. A segment holds entropy-coded bytes only (the host cut it at the markers), so
+// a 0xFF in it is followed by its stuffed 0x00, which is skipped. Past the segment's end the reader supplies zero bits, as libjpeg's
+// jpeg_fill_bit_buffer does, and counts them: a decoder that consumed any has run past the end of its data.
+struct Chunk16 { uint32_t w[4]; };
+
+FE_JHD Chunk16 load16(const uint8_t* p) {
+  Chunk16 c;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 u = *reinterpret_cast<const uint4*>(p);
+  c.w[0] = u.x; c.w[1] = u.y; c.w[2] = u.z; c.w[3] = u.w;
+#else
+  memcpy(c.w, p, 16);
+#endif
+  return c;
+}
+
+struct BitReader {
+  const uint8_t* base;
+  uint32_t pos, end, chunk;
+  Chunk16 cur;
+  uint64_t acc;
+  int nbits, pad;
+  FE_JHD void init(const uint8_t* b, uint32_t start, uint32_t stop) {
+    base = b; pos = start; end = stop; chunk = 0xFFFFFFFFu; acc = 0; nbits = 0; pad = 0;
+    cur.w[0] = cur.w[1] = cur.w[2] = cur.w[3] = 0;
+  }
+  FE_JHD uint32_t byte_at(uint32_t p) {
+    if ((p >> 4) != chunk) { chunk = p >> 4; cur = load16(base + ((size_t)chunk << 4)); }
+    const uint32_t j = p & 15u;
+    const uint32_t word = j < 8 ? (j < 4 ? cur.w[0] : cur.w[1]) : (j < 12 ? cur.w[2] : cur.w[3]);
+    return (word >> (8 * (j & 3u))) & 255u;
+  }
+  FE_JHD void fill() {                           // at least 57 bits afterwards
+    while (nbits <= 56) {
+      uint32_t b = 0;
+      if (pos < end) {
+        b = byte_at(pos++);
+        if (b == 255u) ++pos;                    // the stuffed zero
+      } else {
+        pad += 8;
+      }
+      acc = (acc << 8) | b;
+      nbits += 8;
+    }
+  }
+  FE_JHD uint32_t peek(int n) const { return (uint32_t)(acc >> (nbits - n)) & ((1u << n) - 1u); }      // 1 <= n <= 16 <= nbits
+  FE_JHD void skip(int n) { nbits -= n; }
+  FE_JHD bool overread() const { return pad > nbits; }
+};
+
+// one Huffman symbol; < 0: no code matches (jdhuff.c jpeg_huff_decode's "corrupt JPEG data: bad Huffman code")
+FE_JHD int decode_symbol(BitReader& br, const HuffDec& t) {
+  const uint32_t v = br.peek(16);
+  const uint32_t e = t.look[v >> (16 - LOOK_BITS)];
+  if (e) { br.skip((int)(e >> 8)); return (int)(e & 255u); }
+  for (int l = LOOK_BITS + 1; l <= 16; ++l) {
+    const int32_t c = (int32_t)(v >> (16 - l));
+    if (c <= t.maxcode[l]) { br.skip(l); return t.vals[(c + t.valoff[l]) & 255]; }
+  }
+  return -1;
+}
+
+FE_JHD int huff_extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }
+
+// jdhuff.c decode_mcu for one block: blk (64 coefficients, natural order, zero on entry) receives the DC value and the non-zero AC values.
+// nat: the zigzag -> natural table. Returns 0 or ST_BAD_HUFFMAN.
+FE_JHD int decode_block(BitReader& br, const HuffDec& dc, const HuffDec& ac, int& pred, int16_t* blk, const uint8_t* nat) {
+  br.fill();
+  int s = decode_symbol(br, dc);
+  if (s < 0 || s > 15) return ST_BAD_HUFFMAN;
+  if (s) {
+    const int r = (int)br.peek(s);
+    br.skip(s);
+    s = huff_extend(r, s);
+  }
+  pred = (int32_t)((uint32_t)pred + (uint32_t)s);
+  blk[0] = (int16_t)pred;
+  for (int k = 1; k < 64; ++k) {
+    br.fill();
+    s = decode_symbol(br, ac);
+    if (s < 0) return ST_BAD_HUFFMAN;
+    const int r = s >> 4;
+    s &= 15;
+    if (s) {
+      k += r;
+      const int v = (int)br.peek(s);
+      br.skip(s);
+      if (k >= 64) return ST_BAD_HUFFMAN;          // a run past the block: libjpeg would store it at 63, no encoder writes it
+      blk[nat[k]] = (int16_t)huff_extend(v, s);
+    } else {
+      if (r != 15) break;                          // EOB
+      k += 15;
+    }
+  }
+  return 0;
+}
+
+// MCUs mcu0 .. mcu0 + nmcu - 1 of an image from one segment. huff: the image's 8 tables; td / ta: DC / AC table of each component;
+// coef: the image's coefficient buffer. DC prediction starts at 0: a segment begins at the scan's start or behind a restart marker.
+FE_JHD int decode_segment(BitReader& br, const DecGeom& g, const HuffDec* huff, const uint8_t* td, const uint8_t* ta, uint32_t mcu0, uint32_t nmcu,
+                          int16_t* coef, const uint8_t* nat) {
+  int pred[3] = {0, 0, 0};
+  int my = (int)(mcu0 / (uint32_t)g.mw), mx = (int)(mcu0 % (uint32_t)g.mw);
+  for (uint32_t m = 0; m < nmcu && my < g.mh; ++m) {
+    for (int c = 0; c < g.ncomp; ++c) {
+      const int ch = c ? 1 : g.hs, cv = c ? 1 : g.vs;
+      for (int by = 0; by < cv; ++by)
+        for (int bx = 0; bx < ch; ++bx) {
+          const uint32_t b = g.blk_off[c] + (uint32_t)(my * cv + by) * g.bw[c] + (uint32_t)(mx * ch + bx);
+          const int rc = decode_block(br, huff[td[c] & 3], huff[4 + (ta[c] & 3)], pred[c], coef + (size_t)b * 64, nat);
+          if (rc) return rc;
+        }
+    }
+    if (br.overread()) return ST_PREMATURE_END;
+    if (++mx == g.mw) { mx = 0; ++my; }
+  }
+  return 0;
+}
+
+// ---- dequantise + jidctint.c jpeg_idct_islow ------------------------------------------------------------------------------------------
+// Two's complement arithmetic that wraps: coefficients a hostile stream chose may overflow 32 bits, which must stay defined behaviour.
+FE_JHD int32_t wmul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
+FE_JHD int32_t wadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+FE_JHD int32_t wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
+FE_JHD int32_t wshl(int32_t a, int n) { return (int32_t)((uint32_t)a << n); }
+FE_JHD int32_t wdescale(int32_t x, int n) { return wadd(x, 1 << (n - 1)) >> n; }
+
+// libjpeg's range_limit[x & RANGE_MASK] behind IDCT_range_limit: x + 128 clamped for the values an honest block gives, wrapped beyond
+FE_JHD uint8_t idct_range_limit(int32_t x) {
+  const int v = x & 1023;
+  return (uint8_t)(v < 128 ? v + 128 : (v < 512 ? 255 : (v < 896 ? 0 : v - 896)));
+}
+
+// d[0], d[s], .. d[7s] -> the 1-D inverse transform in place, scaled up by 2^13; the caller descales
+FE_JHD void idct_1d(int32_t* d, const int s, int32_t* o) {
+  int32_t z2 = d[2 * s], z3 = d[6 * s];
+  int32_t z1 = wmul(wadd(z2, z3), 4433);
+  int32_t tmp2 = wadd(z1, wmul(z3, -15137));
+  int32_t tmp3 = wadd(z1, wmul(z2, 6270));
+  z2 = d[0]; z3 = d[4 * s];
+  int32_t tmp0 = wshl(wadd(z2, z3), 13), tmp1 = wshl(wsub(z2, z3), 13);
+  const int32_t tmp10 = wadd(tmp0, tmp3), tmp13 = wsub(tmp0, tmp3), tmp11 = wadd(tmp1, tmp2), tmp12 = wsub(tmp1, tmp2);
+  tmp0 = d[7 * s]; tmp1 = d[5 * s]; tmp2 = d[3 * s]; tmp3 = d[s];
+  z1 = wadd(tmp0, tmp3); z2 = wadd(tmp1, tmp2); z3 = wadd(tmp0, tmp2);
+  int32_t z4 = wadd(tmp1, tmp3);
+  const int32_t z5 = wmul(wadd(z3, z4), 9633);
+  tmp0 = wmul(tmp0, 2446); tmp1 = wmul(tmp1, 16819); tmp2 = wmul(tmp2, 25172); tmp3 = wmul(tmp3, 12299);
+  z1 = wmul(z1, -7373); z2 = wmul(z2, -20995); z3 = wadd(wmul(z3, -16069), z5); z4 = wadd(wmul(z4, -3196), z5);
+  tmp0 = wadd(tmp0, wadd(z1, z3)); tmp1 = wadd(tmp1, wadd(z2, z4)); tmp2 = wadd(tmp2, wadd(z2, z3)); tmp3 = wadd(tmp3, wadd(z1, z4));
+  o[0] = wadd(tmp10, tmp3); o[7] = wsub(tmp10, tmp3);
+  o[1] = wadd(tmp11, tmp2); o[6] = wsub(tmp11, tmp2);
+  o[2] = wadd(tmp12, tmp1); o[5] = wsub(tmp12, tmp1);
+  o[3] = wadd(tmp13, tmp0); o[4] = wsub(tmp13, tmp0);
+}
+
+// 8 samples of a plane row, little-endian in two words; p is 8-byte aligned (planes are, and their strides are multiples of 8)
+FE_JHD void store8(uint8_t* p, uint32_t lo, uint32_t hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *reinterpret_cast<uint2*>(p) = make_uint2(lo, hi);
+#else
+  for (int i = 0; i < 4; ++i) { p[i] = (uint8_t)(lo >> (8 * i)); p[4 + i] = (uint8_t)(hi >> (8 * i)); }
+#endif
+}
+
+// coef, q: natural order. out: 8 rows of `stride` bytes. Returns false when the block left the range in which libjpeg's C code (wrapping
+// 32-bit sums, masked range-limit table) and libjpeg-turbo's SIMD code (16-bit products, saturating packs) give the same samples: a
+// dequantised value or a first-pass value outside int16, or a sample before the table outside [-512, 511]. No encoder writes such a block.
+FE_JHD bool idct_block(const int16_t* coef, const uint16_t* q, uint8_t* out, size_t stride) {
+  int32_t ws[64];
+  constexpr int CONST_BITS = 13, PASS1_BITS = 2;
+  uint32_t wide = 0;                     // bits that are set only when some value v is outside [-lim, lim): (v + lim) >> shift != 0
+#pragma unroll
+  for (int i = 0; i < 64; ++i) {
+    ws[i] = wmul(coef[i], q[i]);
+    wide |= (uint32_t)wadd(ws[i], 32768) >> 16;
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    int32_t o[8];
+    idct_1d(ws + c, 8, o);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      ws[r * 8 + c] = wdescale(o[r], CONST_BITS - PASS1_BITS);
+      wide |= (uint32_t)wadd(ws[r * 8 + c], 32768) >> 16;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    int32_t o[8];
+    idct_1d(ws + r * 8, 1, o);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int32_t v = wdescale(o[c], CONST_BITS + PASS1_BITS + 3);
+      wide |= (uint32_t)wadd(v, 512) >> 10;
+      if (c < 4) lo |= (uint32_t)idct_range_limit(v) << (8 * c);
+      else hi |= (uint32_t)idct_range_limit(v) << (8 * (c - 4));
+    }
+    store8(out + r * stride, lo, hi);
+  }
+  return wide == 0;
+}
+
+// ---- upsampling (jdsample.c with do_fancy_upsampling) + jdcolor.c ---------------------------------------------------------------------
+// Chroma sample for pixel (x, y) of a component subsampled hs x vs; p: its plane, stride bytes per row; cw x ch: its real extent.
+// A component no wider than 2 samples is replicated (jinit_upsampler takes the fancy routines for downsampled_width > 2 only).
+FE_JHD int chroma_at(const uint8_t* p, int stride, int cw, int ch, int hs, int vs, int x, int y) {
+  if (hs == 1) return p[(size_t)y * stride + x];      // vs == 1 as well
+  const int cx = x >> 1;
+  if (vs == 1) {                                      // h2v1
+    const uint8_t* r = p + (size_t)y * stride;
+    if (cw <= 2) return r[cx];
+    if (x & 1) return cx == cw - 1 ? r[cx] : (3 * r[cx] + r[cx + 1] + 2) >> 2;
+    return cx == 0 ? r[cx] : (3 * r[cx] + r[cx - 1] + 1) >> 2;
+  }
+  const int cy = y >> 1;                              // h2v2
+  if (cw <= 2) return p[(size_t)cy * stride + cx];
+  int fy = (y & 1) ? cy + 1 : cy - 1;                 // the nearer of the two neighbouring rows; the image's first / last row repeats
+  fy = fy < 0 ? 0 : (fy > ch - 1 ? ch - 1 : fy);
+  const uint8_t* r0 = p + (size_t)cy * stride;
+  const uint8_t* r1 = p + (size_t)fy * stride;
+  const int cur = 3 * r0[cx] + r1[cx];
+  if (x & 1) return cx == cw - 1 ? (4 * cur + 7) >> 4 : (3 * cur + 3 * r0[cx + 1] + r1[cx + 1] + 7) >> 4;
+  return cx == 0 ? (4 * cur + 8) >> 4 : (3 * cur + 3 * r0[cx - 1] + r1[cx - 1] + 8) >> 4;
+}
+
+FE_JHD uint8_t clamp_u8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// jdcolor.c ycc_rgb_convert: 16.16 constants 1.40200, 1.77200, 0.71414, 0.34414 with ONE_HALF inside the tables
+FE_JHD void ycc_to_rgb(int y, int cb, int cr, uint8_t* r, uint8_t* g, uint8_t* b) {
+  cb -= 128; cr -= 128;
+  *r = clamp_u8(y + ((91881 * cr + 32768) >> 16));
+  *g = clamp_u8(y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+  *b = clamp_u8(y + ((116130 * cb + 32768) >> 16));
+}
+
+// pixel (x, y) of the decoded image from its planes -> rgb[3]
+FE_JHD void pixel_rgb(const uint8_t* planes, const DecGeom& g, int x, int y, uint8_t* rgb) {
+  const int yv = planes[g.plane_off[0] + (size_t)y * (g.bw[0] * 8) + x];
+  if (g.ncomp == 1) { rgb[0] = rgb[1] = rgb[2] = (uint8_t)yv; return; }
+  const int cb = chroma_at(planes + g.plane_off[1], g.bw[1] * 8, g.cw, g.ch, g.hs, g.vs, x, y);
+  const int cr = chroma_at(planes + g.plane_off[2], g.bw[2] * 8, g.cw, g.ch, g.hs, g.vs, x, y);
+  ycc_to_rgb(yv, cb, cr, rgb, rgb + 1, rgb + 2);
+}
+
+// where pixel (x, y) of a w x h image lands under EXIF orientation o (ImageOps.exif_transpose): pixel index in the output, whose width is
+// w for o <= 4 and h above
+FE_JHD size_t oriented_index(int o, int w, int h, int x, int y) {
+  switch (o) {
+    case 2: return (size_t)y * w + (w - 1 - x);                    // FLIP_LEFT_RIGHT
+    case 3: return (size_t)(h - 1 - y) * w + (w - 1 - x);          // ROTATE_180
+    case 4: return (size_t)(h - 1 - y) * w + x;                    // FLIP_TOP_BOTTOM
+    case 5: return (size_t)x * h + y;                              // TRANSPOSE
+    case 6: return (size_t)x * h + (h - 1 - y);                    // ROTATE_270
+    case 7: return (size_t)(w - 1 - x) * h + (h - 1 - y);          // TRANSVERSE
+    case 8: return (size_t)(w - 1 - x) * h + y;                    // ROTATE_90
+    default: return (size_t)y * w + x;
+  }
+}
+
+// ---- host: marker parser, table builder, whole-image decode -----------------------------------------------------------------------------
+static const uint8_t kNatural[64] = FE_JPEG_NATURAL_ORDER;
+
+struct Component { uint8_t id, hs, vs, tq, td, ta; };
+
+struct Parsed {
+  int32_t status = ST_BAD_MARKER;
+  int width = 0, height = 0, ncomp = 0, hs = 1, vs = 1, ri = 0, orientation = 1;
+  Component comp[3] = {};
+  uint16_t q[4][64] = {};
+  uint8_t bits[8][16] = {}, vals[8][256] = {};
+  bool q_set[4] = {}, h_set[8] = {};
+  std::vector<uint32_t> seg_start, seg_end;      // byte offsets of the entropy-coded segments in the file
+};
+
+// jdhuff.c jpeg_make_d_derived_tbl; false: the counts describe no prefix code
+inline bool build_huff_dec(const uint8_t* bits, const uint8_t* vals, HuffDec& t) {
+  memset(&t, 0, sizeof(t));
+  int total = 0;
+  for (int l = 1; l <= 16; ++l) total += bits[l - 1];
+  if (total > 256) return false;
+  uint32_t code = 0;
+  int p = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int n = bits[l - 1];
+    if (n == 0) { t.maxcode[l] = -1; t.valoff[l] = 0; code <<= 1; continue; }
+    if (code + (uint32_t)n > (1u << l)) return false;
+    t.valoff[l] = p - (int32_t)code;
+    for (int i = 0; i < n; ++i, ++p, ++code) {
+      t.vals[p] = vals[p];
+      if (l <= LOOK_BITS) {
+        const uint32_t first = code << (LOOK_BITS - l);
+        for (uint32_t f = 0; f < (1u << (LOOK_BITS - l)); ++f) t.look[first + f] = (uint16_t)((l << 8) | vals[p]);
+      }
+    }
+    t.maxcode[l] = (int32_t)code - 1;
+    code <<= 1;
+  }
+  t.maxcode[0] = -1;
+  return true;
+}
+
+namespace detail {
+inline uint32_t be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
+
+// IFD0's orientation tag of an APP1/Exif payload (after "Exif\0\0"). 0: no tag; -1: a block this parser does not judge
+inline int exif_orientation(const uint8_t* p, size_t n) {
+  if (n < 8) return -1;
+  const bool le = p[0] == 'I' && p[1] == 'I', be = p[0] == 'M' && p[1] == 'M';
+  if (!le && !be) return -1;
+  auto u16 = [&](size_t o) { return le ? (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) : ((uint32_t)p[o] << 8) | p[o + 1]; };
+  auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+  if (u16(2) != 42) return -1;
+  const size_t ifd = u32(4);
+  if (ifd > n || n - ifd < 2) return -1;
+  const size_t cnt = u16(ifd);
+  for (size_t i = 0; i < cnt; ++i) {
+    const size_t e = ifd + 2 + 12 * i;
+    if (e > n || n - e < 12) return -1;
+    if (u16(e) != 0x0112) continue;
+    const uint32_t type = u16(e + 2), count = u32(e + 4);
+    if (count != 1) return -1;
+    if (type == 3) return (int)u16(e + 8);
+    if (type == 4) { const uint32_t v = u32(e + 8); return v > 65535 ? -1 : (int)v; }
+    return -1;
+  }
+  return 0;
+}
+
+inline bool contains(const uint8_t* p, size_t n, const char* s) {
+  const size_t m = strlen(s);
+  for (size_t i = 0; i + m <= n; ++i)
+    if (memcmp(p + i, s, m) == 0) return true;
+  return false;
+}
+}  // namespace detail
+
+// Reads the markers of one file. P.status: 0 when this decoder takes the file, then everything in P is set and the tables named by the
+// scan exist and are prefix codes; otherwise the first reason found. Width, height and components are set whenever a frame header was read.
+inline void parse(const uint8_t* d, size_t len, Parsed& P) {
+  using detail::be16;
+  P = Parsed();
+  auto fail = [&P](int32_t s) { P.status = s; };
+  if (len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(ST_BAD_MARKER);
+  size_t pos = 2;
+  bool have_sof = false, jfif = false, adobe = false, exif_seen = false, exif_odd = false, xmp_orient = false;
+  int adobe_transform = -1, exif_orient = 0;
+  for (;;) {
+    if (pos + 2 > len) return fail(ST_PREMATURE_END);
+    if (d[pos] != 0xFF) return fail(ST_BAD_MARKER);
+    while (pos + 1 < len && d[pos + 1] == 0xFF) ++pos;      // fill bytes
+    if (pos + 2 > len) return fail(ST_PREMATURE_END);
+    const int m = d[pos + 1];
+    pos += 2;
+    if (m == 0x01) continue;                                 // TEM
+    if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x00) return fail(ST_BAD_MARKER);
+    if (m == 0xD9) return fail(ST_PREMATURE_END);            // EOI before any scan
+    if (pos + 2 > len) return fail(ST_PREMATURE_END);
+    const size_t L = be16(d + pos);
+    if (L < 2) return fail(ST_BAD_MARKER);
+    if (L > len - pos) return fail(ST_PREMATURE_END);
+    const uint8_t* s = d + pos + 2;
+    const size_t n = L - 2;
+    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {      // a frame header
+      if (have_sof) return fail(ST_BAD_MARKER);
+      if (n < 6) return fail(ST_BAD_MARKER);
+      have_sof = true;
+      P.height = (int)be16(s + 1); P.width = (int)be16(s + 3); P.ncomp = s[5];
+      if (m == 0xC2) return fail(ST_PROGRESSIVE);
+      if (m >= 0xC9) return fail(ST_ARITHMETIC);
+      if (m != 0xC0 && m != 0xC1) return fail(ST_OTHER);
+      if (s[0] != 8) return fail(ST_PRECISION);
+      if (P.width == 0) return fail(ST_BAD_MARKER);
+      if (P.height == 0) return fail(ST_OTHER);              // the height comes in a DNL marker
+      if (P.ncomp != 1 && P.ncomp != 3) return fail(P.ncomp == 0 ? ST_BAD_MARKER : ST_COMPONENTS);
+      if (n != (size_t)(6 + 3 * P.ncomp)) return fail(ST_BAD_MARKER);
+      for (int c = 0; c < P.ncomp; ++c) {
+        Component& k = P.comp[c];
+        k.id = s[6 + 3 * c]; k.hs = s[7 + 3 * c] >> 4; k.vs = s[7 + 3 * c] & 15; k.tq = s[8 + 3 * c];
+        if (k.hs < 1 || k.hs > 4 || k.vs < 1 || k.vs > 4 || k.tq > 3) return fail(ST_BAD_MARKER);
+      }
+      if (P.ncomp == 3) {
+        const Component* k = P.comp;
+        const bool luma_ok = (k[0].hs == 1 && k[0].vs == 1) || (k[0].hs == 2 && k[0].vs == 1) || (k[0].hs == 2 && k[0].vs == 2);
+        if (!luma_ok || k[1].hs != 1 || k[1].vs != 1 || k[2].hs != 1 || k[2].vs != 1) return fail(ST_SAMPLING);
+        P.hs = k[0].hs; P.vs = k[0].vs;
+      } else {
+        P.hs = P.vs = 1;                                     // a single-component scan is not interleaved: one block per MCU
+      }
+    } else if (m == 0xCC) {
+      return fail(ST_ARITHMETIC);
+    } else if (m == 0xC4) {
+      size_t o = 0;
+      while (o < n) {
+        if (n - o < 17) return fail(ST_BAD_MARKER);
+        const int tc = s[o] >> 4, th = s[o] & 15;
+        if (tc > 1 || th > 3) return fail(ST_BAD_MARKER);
+        int total = 0;
+        for (int i = 0; i < 16; ++i) total += s[o + 1 + i];
+        if (total > 256 || (size_t)total > n - o - 17) return fail(ST_BAD_MARKER);
+        const int slot = tc * 4 + th;
+        memcpy(P.bits[slot], s + o + 1, 16);
+        memset(P.vals[slot], 0, 256);
+        memcpy(P.vals[slot], s + o + 17, (size_t)total);
+        P.h_set[slot] = true;
+        o += 17 + (size_t)total;
+      }
+    } else if (m == 0xDB) {
+      size_t o = 0;
+      while (o < n) {
+        const int pq = s[o] >> 4, tq = s[o] & 15;
+        if (pq > 1 || tq > 3) return fail(ST_BAD_MARKER);
+        const size_t need = 1 + (pq ? 128 : 64);
+        if (n - o < need) return fail(ST_BAD_MARKER);
+        for (int z = 0; z < 64; ++z) P.q[tq][kNatural[z]] = (uint16_t)(pq ? be16(s + o + 1 + 2 * z) : s[o + 1 + z]);
+        P.q_set[tq] = true;
+        o += need;
+      }
+    } else if (m == 0xDD) {
+      if (n != 2) return fail(ST_BAD_MARKER);
+      P.ri = (int)be16(s);
+    } else if (m == 0xE0) {
+      if (n >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
+    } else if (m == 0xEE) {
+      if (n >= 12 && memcmp(s, "Adobe", 5) == 0) { adobe = true; adobe_transform = s[11]; }
+    } else if (m == 0xE1) {
+      if (n >= 6 && memcmp(s, "Exif\0\0", 6) == 0) {
+        if (exif_seen) exif_odd = true;                      // a second block: Pillow joins them
+        else {
+          exif_seen = true;
+          exif_orient = detail::exif_orientation(s + 6, n - 6);
+          if (exif_orient < 0) exif_odd = true;
+        }
+      } else if (detail::contains(s, n, "tiff:Orientation")) {
+        xmp_orient = true;                                   // Pillow reads it when the EXIF block has no orientation
+      }
+    } else if (m == 0xDA) {
+      if (!have_sof) return fail(ST_BAD_MARKER);
+      if (n < 1) return fail(ST_BAD_MARKER);
+      const int ns = s[0];
+      if (ns < 1 || ns > 4 || n != (size_t)(4 + 2 * ns)) return fail(ST_BAD_MARKER);
+      if (ns != P.ncomp) return fail(ST_MULTISCAN);
+      for (int c = 0; c < ns; ++c) {
+        if (s[1 + 2 * c] != P.comp[c].id) return fail(ST_OTHER);
+        P.comp[c].td = s[2 + 2 * c] >> 4; P.comp[c].ta = s[2 + 2 * c] & 15;
+        if (P.comp[c].td > 3 || P.comp[c].ta > 3) return fail(ST_BAD_MARKER);
+      }
+      pos += L;
+      break;
+    }
+    pos += L;
+  }
+  // what Pillow would see that this decoder does not reproduce
+  if (exif_odd || (xmp_orient && exif_orient == 0)) return fail(ST_OTHER);
+  P.orientation = exif_orient >= 2 && exif_orient <= 8 ? exif_orient : 1;
+  if (P.ncomp == 3) {                                        // jdapimin.c default_decompress_parms
+    bool ycc = true;
+    if (jfif) ycc = true;
+    else if (adobe) ycc = adobe_transform != 0;
+    else ycc = !(P.comp[0].id == 'R' && P.comp[1].id == 'G' && P.comp[2].id == 'B');
+    if (!ycc) return fail(ST_ADOBE_RGB);
+  }
+  for (int c = 0; c < P.ncomp; ++c) {
+    if (!P.q_set[P.comp[c].tq] || !P.h_set[P.comp[c].td] || !P.h_set[4 + P.comp[c].ta]) return fail(ST_BAD_MARKER);
+    HuffDec t;
+    if (!build_huff_dec(P.bits[P.comp[c].td], P.vals[P.comp[c].td], t)) return fail(ST_BAD_HUFFMAN);
+    for (int i = 0; i < 256; ++i)
+      if (P.vals[P.comp[c].td][i] > 15) return fail(ST_BAD_HUFFMAN);
+    if (!build_huff_dec(P.bits[4 + P.comp[c].ta], P.vals[4 + P.comp[c].ta], t)) return fail(ST_BAD_HUFFMAN);
+  }
+  // the entropy-coded data: cut at the restart markers
+  const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+  const uint64_t mcus = (uint64_t)g.mw * g.mh;
+  const uint64_t want = P.ri ? (mcus + P.ri - 1) / P.ri : 1;
+  if (len > 0xFFFFFFF0u) return fail(ST_OTHER);
+  size_t start = pos, i = pos;
+  int marker = -1;
+  while (i < len) {
+    if (d[i] != 0xFF) { ++i; continue; }
+    size_t j = i + 1;
+    while (j < len && d[j] == 0xFF) ++j;                     // fill bytes before a marker
+    if (j >= len) { i = len; break; }
+    if (d[j] == 0x00) {
+      if (j != i + 1) return fail(ST_BAD_MARKER);            // fill bytes in front of a stuffed zero
+      i += 2;
+      continue;
+    }
+    P.seg_start.push_back((uint32_t)start);
+    P.seg_end.push_back((uint32_t)i);
+    if (d[j] >= 0xD0 && d[j] <= 0xD7) {
+      if (!P.ri || d[j] != 0xD0 + (int)((P.seg_start.size() - 1) & 7)) return fail(ST_BAD_RESTART);
+      if (P.seg_start.size() >= want) return fail(ST_BAD_RESTART);      // a restart marker behind the last interval
+      start = i = j + 1;
+      continue;
+    }
+    marker = d[j];
+    i = j + 1;
+    break;
+  }
+  if (marker < 0) return fail(ST_PREMATURE_END);
+  if (P.seg_start.size() < want) return fail(ST_PREMATURE_END);
+  while (marker != 0xD9) {                                   // what follows the scan: another scan makes the file multi-scan
+    if (marker == 0xDA) return fail(ST_MULTISCAN);
+    if (marker == 0xC4 || marker == 0xDB || marker == 0xDD || marker == 0xDC || marker == 0xFE || (marker >= 0xE0 && marker <= 0xEF)) {
+      if (i + 2 > len) return fail(ST_PREMATURE_END);
+      const size_t L = be16(d + i);
+      if (L < 2) return fail(ST_BAD_MARKER);
+      if (L > len - i) return fail(ST_PREMATURE_END);
+      if (marker == 0xDC) return fail(ST_OTHER);
+      i += L;
+      if (i + 2 > len) return fail(ST_PREMATURE_END);
+      if (d[i] != 0xFF) return fail(ST_BAD_MARKER);
+      while (i + 1 < len && d[i + 1] == 0xFF) ++i;
+      if (i + 2 > len) return fail(ST_PREMATURE_END);
+      marker = d[i + 1];
+      i += 2;
+    } else {
+      return fail(ST_BAD_MARKER);
+    }
+  }
+  P.status = ST_OK;
+}
+
+inline void build_tables(const Parsed& P, DecTables& T) {
+  memset(&T, 0, sizeof(T));
+  for (int t = 0; t < 4; ++t)
+    if (P.q_set[t]) memcpy(T.q[t], P.q[t], sizeof(T.q[t]));
+  for (int c = 0; c < P.ncomp; ++c) {
+    build_huff_dec(P.bits[P.comp[c].td], P.vals[P.comp[c].td], T.huff[P.comp[c].td]);
+    build_huff_dec(P.bits[4 + P.comp[c].ta], P.vals[4 + P.comp[c].ta], T.huff[4 + P.comp[c].ta]);
+  }
+}
+
+// The whole decode of one parsed file on the host, stage by stage as the kernels run it. buf: the file copied into a 16-byte aligned
+// buffer padded to a multiple of 16 bytes. out: [oh][ow][3] with (oh, ow) = (height, width), exchanged for orientations 5 .. 8 when
+// apply_orientation. Returns the status; out is written only for 0.
+inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int apply_orientation, uint8_t* out) {
+  if (P.status != ST_OK) return P.status;
+  const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+  DecTables* T = new DecTables;
+  build_tables(P, *T);
+  std::vector<int16_t> coef((size_t)g.nblk * 64, 0);
+  std::vector<uint8_t> planes(g.plane_bytes);
+  uint8_t td[3], ta[3];
+  for (int c = 0; c < 3; ++c) { td[c] = P.comp[c].td; ta[c] = P.comp[c].ta; }
+  const uint32_t mcus = (uint32_t)g.mw * g.mh, per = P.ri ? (uint32_t)P.ri : mcus;
+  int32_t st = ST_OK;
+  for (size_t k = 0; k < P.seg_start.size() && st == ST_OK; ++k) {
+    BitReader br;
+    br.init(buf, P.seg_start[k], P.seg_end[k]);
+    const uint32_t m0 = (uint32_t)k * per;
+    st = decode_segment(br, g, T->huff, td, ta, m0, mcus - m0 < per ? mcus - m0 : per, coef.data(), kNatural);
+  }
+  if (st == ST_OK) {
+    for (int c = 0; c < g.ncomp; ++c)
+      for (int by = 0; by < g.bh[c]; ++by)
+        for (int bx = 0; bx < g.bw[c]; ++bx)
+          if (!idct_block(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c] + bx) * 64, T->q[P.comp[c].tq],
+                          planes.data() + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, (size_t)g.bw[c] * 8))
+            st = ST_BAD_COEFFICIENT;
+  }
+  if (st == ST_OK) {
+    const int o = apply_orientation ? P.orientation : 1;
+    for (int y = 0; y < g.h; ++y)
+      for (int x = 0; x < g.w; ++x) {
+        uint8_t rgb[3];
+        pixel_rgb(planes.data(), g, x, y, rgb);
+        uint8_t* p = out + oriented_index(o, g.w, g.h, x, y) * 3;
+        p[0] = rgb[bgr ? 2 : 0]; p[1] = rgb[1]; p[2] = rgb[bgr ? 0 : 2];
+      }
+  }
+  delete T;
+  return st;
+}
+}  // namespace jpegdec
+}  // namespace fe

@@ -1,0 +1,300 @@
+// JPEG decode: file bytes in, a resident uint8 [n][h][w][3] batch out, the pixels Pillow gives for
+// `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` (reference utils/image_loading.py:100-106). The arithmetic lives in
+// jpeg_dec_core.h; here are its stages over a batch of files that may differ in everything but their output size:
+//   A host:    parse every file (markers, tables, EXIF orientation), cut its entropy data at the restart markers into segments, and put
+//              descriptors, tables, segment offsets and the compressed bytes of the whole chunk into one pinned block: one upload
+//   B entropy: a lane decodes one segment serially into zeroed int16 coefficient blocks; a workgroup is one wave holding up to 64
+//              segments of ONE image, whose Huffman tables sit in LDS. A file without restart markers is one segment: one lane of its wave.
+//   C idct:    one lane per block: dequantise, integer slow IDCT, 8 rows of 8 samples into the component's plane (padded to the block grid)
+//   D colour:  one lane per 4 pixels of a row: triangle-filter upsampling, YCbCr -> RGB, store as RGB or BGR at the address the EXIF
+//              orientation gives (all 8 cases; there is no transpose pass)
+// A segment's error (bad code, data that ends early) and a block outside the range honest coefficients reach become the image's negative
+// status by atomicMin; stage D leaves the slot of such an image untouched.
+#include <chrono>
+
+#include "engine.h"
+#include "jpeg_dec_core.h"
+
+namespace fe {
+
+using namespace jpegdec;
+
+namespace {
+
+struct DevImage {
+  uint64_t coef_off;                     // int16 elements from the chunk's coefficient base
+  uint64_t plane_off;                    // bytes from the chunk's plane base
+  uint32_t seg_first, nseg;              // this image's rows of the segment offset arrays
+  int32_t w, h, ncomp, hs, vs, ri, orientation;
+  int32_t slot;                          // image index in the destination
+  uint8_t td[4], ta[4], tq[4];
+};
+
+constexpr int JD_WAVE = 64;
+constexpr int JD_THREADS = 256;
+
+__global__ __launch_bounds__(JD_WAVE) void jpegdec_entropy_kernel(const DevImage* __restrict__ imgs, const DecTables* __restrict__ tabs,
+                                                                  const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_end,
+                                                                  const uint8_t* __restrict__ bytes, int16_t* __restrict__ coef,
+                                                                  int32_t* __restrict__ status) {
+  __shared__ HuffDec H[8];
+  __shared__ uint8_t nat[64];
+  const DevImage im = imgs[blockIdx.x];
+  if (blockIdx.y * JD_WAVE >= im.nseg) return;               // uniform over the wave
+  {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(tabs[blockIdx.x].huff);
+    uint32_t* d = reinterpret_cast<uint32_t*>(H);
+    for (int t = threadIdx.x; t < (int)(sizeof(H) / 4); t += JD_WAVE) d[t] = s[t];
+    constexpr uint8_t order[64] = FE_JPEG_NATURAL_ORDER;
+    nat[threadIdx.x] = order[threadIdx.x];
+  }
+  __syncthreads();
+  const uint32_t k = blockIdx.y * JD_WAVE + threadIdx.x;
+  if (k >= im.nseg) return;
+  const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  const uint32_t mcus = (uint32_t)g.mw * (uint32_t)g.mh, per = im.ri ? (uint32_t)im.ri : mcus;
+  const uint32_t m0 = k * per;                               // nseg = ceil(mcus / per): m0 < mcus
+  BitReader br;
+  br.init(bytes, seg_start[im.seg_first + k], seg_end[im.seg_first + k]);
+  const int rc = decode_segment(br, g, H, im.td, im.ta, m0, min(per, mcus - m0), coef + im.coef_off, nat);
+  if (rc) atomicMin(status + blockIdx.x, rc);
+}
+static_assert(sizeof(HuffDec) % 4 == 0 && offsetof(DecTables, huff) % 4 == 0, "the tables are copied by dwords");
+
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_idct_kernel(const DevImage* __restrict__ imgs, const DecTables* __restrict__ tabs,
+                                                                  const int16_t* __restrict__ coef, uint8_t* __restrict__ planes,
+                                                                  int32_t* __restrict__ status) {
+  __shared__ uint16_t q[4][64];
+  const DevImage im = imgs[blockIdx.y];
+  const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  if (blockIdx.x * JD_THREADS >= g.nblk) return;             // uniform over the workgroup
+  (&q[0][0])[threadIdx.x] = (&tabs[blockIdx.y].q[0][0])[threadIdx.x];
+  __syncthreads();
+  const uint32_t b = blockIdx.x * JD_THREADS + threadIdx.x;
+  if (b >= g.nblk) return;
+  const int c = (g.ncomp == 3 && b >= g.blk_off[1]) ? (b >= g.blk_off[2] ? 2 : 1) : 0;
+  const uint32_t lb = b - g.blk_off[c];
+  const uint32_t by = lb / (uint32_t)g.bw[c], bx = lb % (uint32_t)g.bw[c];
+  int16_t blk[64];
+  const uint4* src = reinterpret_cast<const uint4*>(coef + im.coef_off + (size_t)b * 64);      // 128 bytes per block, 16-byte aligned
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const uint4 u = src[v];
+    const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { blk[8 * v + 2 * j] = (int16_t)(wds[j] & 0xFFFFu); blk[8 * v + 2 * j + 1] = (int16_t)(wds[j] >> 16); }
+  }
+  const size_t stride = (size_t)g.bw[c] * 8;
+  if (!idct_block(blk, q[im.tq[c] & 3], planes + im.plane_off + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, stride))
+    atomicMin(status + blockIdx.y, (int32_t)ST_BAD_COEFFICIENT);
+}
+
+// dst [slots][oh][ow][3]. A lane takes pixels 4 t .. 4 t + 3 of a source row. Where the destination keeps the source's row direction
+// (orientation 1 or 4) and rows are a whole number of dwords, the 12 bytes go out as three dwords; otherwise byte by byte.
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_colour_kernel(const DevImage* __restrict__ imgs, const uint8_t* __restrict__ planes,
+                                                                    const int32_t* __restrict__ status, uint8_t* __restrict__ dst, int oh, int ow,
+                                                                    int bgr, int apply_orientation, int dst_aligned) {
+  const DevImage im = imgs[blockIdx.y];
+  if (status[blockIdx.y] != 0) return;
+  const int w4 = (im.w + 3) >> 2;
+  const uint32_t i = blockIdx.x * JD_THREADS + threadIdx.x;
+  if (i >= (uint32_t)w4 * (uint32_t)im.h) return;
+  const int y = (int)(i / (uint32_t)w4), x0 = (int)(i % (uint32_t)w4) * 4;
+  const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  const uint8_t* pl = planes + im.plane_off;
+  const int o = apply_orientation ? im.orientation : 1;
+  uint8_t* out = dst + (size_t)im.slot * oh * ow * 3;
+  const int ir = bgr ? 2 : 0, ib = bgr ? 0 : 2;
+  uint8_t px[12];
+  const int nx = min(4, im.w - x0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint8_t rgb[3] = {0, 0, 0};
+    if (j < nx) pixel_rgb(pl, g, x0 + j, y, rgb);
+    px[3 * j + ir] = rgb[0]; px[3 * j + 1] = rgb[1]; px[3 * j + ib] = rgb[2];
+  }
+  if ((o == 1 || o == 4) && dst_aligned && (im.w & 3) == 0) {
+    uint32_t* p = reinterpret_cast<uint32_t*>(out + oriented_index(o, im.w, im.h, x0, y) * 3);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p[j] = px[4 * j] | ((uint32_t)px[4 * j + 1] << 8) | ((uint32_t)px[4 * j + 2] << 16) | ((uint32_t)px[4 * j + 3] << 24);
+  } else {
+    for (int j = 0; j < nx; ++j) {
+      uint8_t* p = out + oriented_index(o, im.w, im.h, x0 + j, y) * 3;
+      p[0] = px[3 * j]; p[1] = px[3 * j + 1]; p[2] = px[3 * j + 2];
+    }
+  }
+}
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct StageTimer {                      // with fe_profile_enable: one record per stage
+  Ctx& c;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  explicit StageTimer(Ctx& ctx) : c(ctx) {
+    if (c.profile) { FE_HIP(hipEventCreate(&e0)); FE_HIP(hipEventCreate(&e1)); }
+  }
+  ~StageTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  void begin() { if (c.profile) FE_HIP(hipEventRecord(e0, c.stream)); }
+  void end(const char* name, double bytes) {
+    if (!c.profile) return;
+    FE_HIP(hipEventRecord(e1, c.stream));
+    FE_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    FE_HIP(hipEventElapsedTime(&ms, e0, e1));
+    c.timings.push_back({name, 0.0, bytes, ms});
+  }
+};
+
+}  // namespace
+
+void jpeg_probe(const uint8_t* data, size_t len, int32_t out[8]) {
+  Parsed P;
+  parse(data, len, P);
+  out[0] = P.width; out[1] = P.height; out[2] = P.ncomp; out[3] = P.hs; out[4] = P.vs; out[5] = P.ri; out[6] = P.orientation; out[7] = P.status;
+}
+
+// dst: [n][h][w][3] on the device or on the host; status: host [n]. See fe_jpeg_decode.
+void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                       uint8_t* dst, int32_t* status) {
+  FE_CHECK(n > 0 && h > 0 && w > 0 && h <= 65535 && w <= 65535, "jpeg_decode: bad shape %d x %d x %d", n, h, w);
+  const auto t_parse = std::chrono::steady_clock::now();
+  std::vector<Parsed> parsed((size_t)n);
+  std::vector<int> todo;
+  for (int i = 0; i < n; ++i) {
+    Parsed& P = parsed[i];
+    if (!data[i]) { P.status = ST_BAD_MARKER; status[i] = P.status; continue; }
+    parse(data[i], len[i], P);
+    if (P.status == ST_OK) {
+      const bool swap = apply_orientation && P.orientation >= 5;
+      if ((swap ? P.width : P.height) != h || (swap ? P.height : P.width) != w) P.status = ST_BAD_DIMENSIONS;
+    }
+    status[i] = P.status;
+    if (P.status == ST_OK) todo.push_back(i);
+  }
+  if (c.profile)
+    c.timings.push_back({"jpeg_decode A: parse (host)", 0.0, 0.0,
+                         std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_parse).count()});
+  const size_t out_b = (size_t)h * w * 3;
+  auto need = [&](const Parsed& P) {      // arena bytes of one image, alignment slack included
+    const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+    const size_t bytes = (size_t)(P.seg_end.back() - P.seg_start.front());
+    return (size_t)g.nblk * 128 + up256(g.plane_bytes) + up256(bytes + 16) + sizeof(DevImage) + sizeof(DecTables) + P.seg_start.size() * 8 + 4 +
+           (dst_on_device ? 0 : out_b) + 64;
+  };
+  const size_t budget = c.arena.capacity() - c.arena.capacity() / 8;
+  StageTimer tm(c);
+  std::vector<int32_t> st_host;
+  for (size_t first = 0; first < todo.size();) {
+    // the images of this chunk: as many as the workspace holds
+    size_t used = 8 * 256, last = first;
+    uint64_t comp_bytes = 0;
+    while (last < todo.size() && last - first < 4096) {
+      const Parsed& P = parsed[todo[last]];
+      const size_t nb = need(P);
+      if (last > first && (used + nb > budget || comp_bytes + (P.seg_end.back() - P.seg_start.front()) > 0xE0000000ull)) break;
+      FE_CHECK(used + nb <= budget, "jpeg_decode: one %d x %d image needs %zu bytes of workspace, the arena holds %zu", P.width, P.height, nb, budget);
+      used += nb; comp_bytes += P.seg_end.back() - P.seg_start.front();
+      ++last;
+    }
+    const int nd = (int)(last - first);
+    size_t nseg = 0;
+    for (size_t k = first; k < last; ++k) nseg += parsed[todo[k]].seg_start.size();
+    // ---- stage A: one block of host memory -> one upload
+    const size_t o_img = 0, o_tab = up256(o_img + (size_t)nd * sizeof(DevImage)), o_s0 = up256(o_tab + (size_t)nd * sizeof(DecTables)),
+                 o_s1 = up256(o_s0 + nseg * 4), o_bytes = up256(o_s1 + nseg * 4);
+    size_t blob = o_bytes;
+    for (size_t k = first; k < last; ++k) blob += ((size_t)(parsed[todo[k]].seg_end.back() - parsed[todo[k]].seg_start.front()) + 15) & ~(size_t)15;
+    blob += 16;                                              // 16-byte loads at the tail stay inside
+    FE_CHECK(blob - o_bytes < 0xFFFFFFF0ull, "jpeg_decode: compressed bytes of a chunk exceed 32-bit offsets");
+    if (blob > c.jpegdec_stage_cap) {
+      if (c.jpegdec_stage) (void)hipHostFree(c.jpegdec_stage);
+      c.jpegdec_stage = nullptr; c.jpegdec_stage_cap = 0;
+      const size_t cap = blob + blob / 4;
+      FE_HIP(hipHostMalloc(&c.jpegdec_stage, cap, hipHostMallocDefault));
+      c.jpegdec_stage_cap = cap;
+    }
+    uint8_t* hb = (uint8_t*)c.jpegdec_stage;
+    DevImage* h_img = (DevImage*)(hb + o_img);
+    DecTables* h_tab = (DecTables*)(hb + o_tab);
+    uint32_t* h_s0 = (uint32_t*)(hb + o_s0);
+    uint32_t* h_s1 = (uint32_t*)(hb + o_s1);
+    size_t coef_el = 0, plane_b = 0, seg_at = 0, byte_at = 0;
+    uint32_t max_groups = 1, max_blk = 1;
+    for (int k = 0; k < nd; ++k) {
+      const int src = todo[first + k];
+      const Parsed& P = parsed[src];
+      const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+      DevImage& D = h_img[k];
+      memset(&D, 0, sizeof(D));
+      D.coef_off = coef_el; D.plane_off = plane_b;
+      D.seg_first = (uint32_t)seg_at; D.nseg = (uint32_t)P.seg_start.size();
+      D.w = P.width; D.h = P.height; D.ncomp = P.ncomp; D.hs = P.hs; D.vs = P.vs; D.ri = P.ri; D.orientation = P.orientation;
+      D.slot = dst_on_device ? src : k;
+      for (int cc = 0; cc < P.ncomp; ++cc) { D.td[cc] = P.comp[cc].td; D.ta[cc] = P.comp[cc].ta; D.tq[cc] = P.comp[cc].tq; }
+      build_tables(P, h_tab[k]);
+      const uint32_t s0 = P.seg_start.front(), nbytes = P.seg_end.back() - s0;
+      memcpy(hb + o_bytes + byte_at, data[src] + s0, nbytes);
+      for (size_t s = 0; s < P.seg_start.size(); ++s) {
+        h_s0[seg_at + s] = (uint32_t)byte_at + (P.seg_start[s] - s0);
+        h_s1[seg_at + s] = (uint32_t)byte_at + (P.seg_end[s] - s0);
+      }
+      const size_t padded = ((size_t)nbytes + 15) & ~(size_t)15;
+      memset(hb + o_bytes + byte_at + nbytes, 0, padded - nbytes);
+      byte_at += padded;
+      seg_at += P.seg_start.size();
+      coef_el += (size_t)g.nblk * 64;
+      plane_b += up256(g.plane_bytes);
+      max_groups = std::max(max_groups, (D.nseg + JD_WAVE - 1) / JD_WAVE);
+      max_blk = std::max(max_blk, g.nblk);
+    }
+    memset(hb + o_bytes + byte_at, 0, 16);
+    FE_CHECK(max_groups <= 65535, "jpeg_decode: an image has too many restart intervals");
+    c.arena.reset();
+    uint8_t* d_blob = (uint8_t*)c.arena.alloc(blob);
+    int32_t* d_status = (int32_t*)c.arena.alloc((size_t)nd * 4);
+    int16_t* d_coef = (int16_t*)c.arena.alloc(coef_el * 2);
+    uint8_t* d_planes = (uint8_t*)c.arena.alloc(plane_b);
+    uint8_t* d_out = dst_on_device ? dst : (uint8_t*)c.arena.alloc((size_t)nd * out_b);
+    tm.begin();
+    FE_HIP(hipMemcpyAsync(d_blob, hb, blob, hipMemcpyHostToDevice, c.stream));
+    tm.end("jpeg_decode A: upload", (double)blob);
+    const DevImage* d_img = (const DevImage*)(d_blob + o_img);
+    const DecTables* d_tab = (const DecTables*)(d_blob + o_tab);
+    tm.begin();
+    FE_HIP(hipMemsetAsync(d_status, 0, (size_t)nd * 4, c.stream));
+    FE_HIP(hipMemsetAsync(d_coef, 0, coef_el * 2, c.stream));
+    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3((unsigned)nd, max_groups), dim3(JD_WAVE), 0, c.stream, d_img, d_tab, (const uint32_t*)(d_blob + o_s0),
+                       (const uint32_t*)(d_blob + o_s1), (const uint8_t*)(d_blob + o_bytes), d_coef, d_status);
+    tm.end("jpeg_decode B: entropy", (double)(blob - o_bytes));
+    tm.begin();
+    hipLaunchKernelGGL(jpegdec_idct_kernel, dim3((max_blk + JD_THREADS - 1) / JD_THREADS, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, d_tab,
+                       (const int16_t*)d_coef, d_planes, d_status);
+    tm.end("jpeg_decode C: idct", (double)coef_el * 2);
+    tm.begin();
+    const unsigned quads = (unsigned)(((size_t)((std::max(h, w) + 3) / 4) * std::max(h, w) + JD_THREADS - 1) / JD_THREADS);      // either orientation
+    hipLaunchKernelGGL(jpegdec_colour_kernel, dim3(quads, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, (const uint8_t*)d_planes,
+                       (const int32_t*)d_status, d_out, h, w, bgr ? 1 : 0, apply_orientation ? 1 : 0, (int)(((uintptr_t)d_out & 3) == 0 && (out_b & 3) == 0));
+    tm.end("jpeg_decode D: colour", (double)nd * out_b);
+    FE_HIP(hipGetLastError());
+    st_host.resize((size_t)nd);
+    FE_HIP(hipMemcpyAsync(st_host.data(), d_status, (size_t)nd * 4, hipMemcpyDeviceToHost, c.stream));
+    FE_HIP(hipStreamSynchronize(c.stream));
+    for (int k = 0; k < nd; ++k) status[todo[first + k]] = st_host[k];
+    if (!dst_on_device) {                                    // runs of decoded neighbours come down in one copy each
+      for (int k = 0; k < nd;) {
+        if (st_host[k] != 0) { ++k; continue; }
+        int e = k + 1;
+        while (e < nd && st_host[e] == 0 && todo[first + e] == todo[first + e - 1] + 1) ++e;
+        FE_HIP(hipMemcpyAsync(dst + (size_t)todo[first + k] * out_b, d_out + (size_t)k * out_b, (size_t)(e - k) * out_b, hipMemcpyDeviceToHost, c.stream));
+        k = e;
+      }
+      FE_HIP(hipStreamSynchronize(c.stream));
+    }
+    first = last;
+  }
+}
+
+}  // namespace fe

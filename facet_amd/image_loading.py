@@ -1,0 +1,118 @@
+"""Image loading: the reference's utils/image_loading.py `load_image_from_path` (:44-112) with the JPEG decode on the GPU.
+
+    decode_jpegs(engine, blobs)            -> [uint8 [h,w,3] | None]   RGB pixels of each file, in input order
+    load_image_from_path(engine, path)     -> (pil_img, img_cv)        the reference's signature, for one file
+    decode_groups(engine, blobs, device)   -> the resident batches BatchScorer.process_files scores, and what is left for Pillow
+
+The reference opens every file with `Image.open`, `ImageOps.exif_transpose` and `convert('RGB')` (:100-103). `fe_jpeg_decode` gives those
+pixels for baseline Huffman JPEG files (YCbCr 4:4:4 / 4:2:2 / 4:2:0 or grayscale, one scan, any tables, with or without restart markers,
+all eight EXIF orientations) from the files' bytes. Every other input - progressive or CMYK files, corrupt streams, PNG, anything the
+probe or the decode gives a non-zero status - goes through that same Pillow recipe here, so the functions always return what the
+reference would, and None where it returns (None, None). RAW files (CR2 / CR3) stay with the caller: rawpy is its dependency.
+"""
+import io
+import os
+
+import numpy as np
+
+RAW_SUFFIXES = ('.cr2', '.cr3')
+
+# status codes of Engine.jpeg_probe / jpeg_decode (FE_JPEG_* in include/facet_engine.h)
+JPEG_STATUS = {0: 'ok', 1: 'progressive', 2: 'arithmetic', 3: 'precision', 4: 'components', 5: 'adobe_rgb', 6: 'sampling', 7: 'multiscan',
+               8: 'other', -1: 'bad_marker', -2: 'bad_huffman', -3: 'premature_end', -4: 'bad_restart', -5: 'bad_dimensions',
+               -6: 'bad_coefficient'}
+
+
+def read_blob(path_or_blob):
+    """bytes stay bytes; a path is read. CR2 / CR3 paths raise ValueError: RAW development stays with the caller."""
+    if isinstance(path_or_blob, (bytes, bytearray, memoryview)):
+        return bytes(path_or_blob)
+    p = os.fspath(path_or_blob)
+    if p.lower().endswith(RAW_SUFFIXES):
+        raise ValueError(f"{p}: RAW files are not decoded here (the reference uses rawpy); pass the developed image instead")
+    with open(p, 'rb') as f:
+        return f.read()
+
+
+def pillow_image(blob):
+    """utils/image_loading.py:100-103 on the file's bytes -> PIL RGB image, or None where the reference gives up."""
+    from PIL import Image, ImageOps
+    try:
+        im = Image.open(io.BytesIO(blob))
+        im = ImageOps.exif_transpose(im)
+        if im.mode != 'RGB':
+            im = im.convert('RGB')
+        im.load()
+        return im
+    except Exception as e:
+        print(f"Error loading image: {e}")
+        return None
+
+
+def pillow_rgb(blob):
+    im = pillow_image(blob)
+    return None if im is None else np.asarray(im, dtype=np.uint8)
+
+
+def decode_groups(engine, blobs, device=False):
+    """Probe every file, group the decodable ones by output size and decode each group with one fe_jpeg_decode.
+    -> (groups, rest): groups = [(indices, pixels)], pixels a uint8 [k,h,w,3] array or with device=True a (device_ptr, k, h, w) tuple the
+    caller frees, holding exactly the images of `indices` in that order; rest = the indices left for Pillow."""
+    sizes, rest = {}, []
+    for i, b in enumerate(blobs):
+        info = engine.jpeg_probe(b)
+        if info['status'] != 0:
+            rest.append(i)
+            continue
+        h, w = info['height'], info['width']
+        if info['orientation'] >= 5:
+            h, w = w, h
+        sizes.setdefault((h, w), []).append(i)
+    groups = []
+    for (h, w), idx in sizes.items():
+        px, status = engine.jpeg_decode([blobs[i] for i in idx], h, w, device=device)
+        good = [k for k in range(len(idx)) if status[k] == 0]
+        if len(good) < len(idx):      # rare: a stream that only the entropy decoder finds corrupt. The batch must have no holes.
+            rest.extend(idx[k] for k in range(len(idx)) if status[k] != 0)
+            if device:
+                engine.dev_free(px[0])
+                px = None
+                if good:
+                    px, status = engine.jpeg_decode([blobs[idx[k]] for k in good], h, w, device=True)
+                    assert not status.any()
+            else:
+                px = px[good]
+            idx = [idx[k] for k in good]
+        if idx:
+            groups.append((idx, px))
+    return groups, sorted(rest)
+
+
+def decode_jpegs(engine, blobs):
+    """The RGB pixels of every file (bytes), as uint8 [h,w,3] arrays in input order: what load_image_from_path's pil_img holds, None
+    where it fails."""
+    blobs = [bytes(b) for b in blobs]
+    out = [None] * len(blobs)
+    groups, rest = decode_groups(engine, blobs, device=False)
+    for idx, px in groups:
+        for k, i in enumerate(idx):
+            out[i] = px[k]
+    for i in rest:
+        out[i] = pillow_rgb(blobs[i])
+    return out
+
+
+def load_image_from_path(engine, photo_path):
+    """(pil_img, img_cv): PIL RGB image and BGR array of one file, (None, None) on error - utils/image_loading.py:44-112 for non-RAW files."""
+    from PIL import Image
+    try:
+        blob = read_blob(photo_path)
+    except ValueError:
+        raise
+    except Exception as e:
+        print(f"Error loading image {photo_path}: {e}")
+        return None, None
+    rgb = decode_jpegs(engine, [blob])[0]
+    if rgb is None:
+        return None, None
+    return Image.fromarray(rgb), np.ascontiguousarray(rgb[..., ::-1])

@@ -335,6 +335,37 @@ int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr
 int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int oh, int ow, int fx, int fy,
                       const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
+/* ---- JPEG decode: file bytes -> uint8 batch, Pillow's pixels -------------------------------------------- */
+/* Status of a file. 0: decoded (or decodable). Positive: a kind of file left to the caller's own decoder, nothing was attempted.
+ * Negative: a corrupt stream. */
+#define FE_JPEG_OK 0
+#define FE_JPEG_PROGRESSIVE 1        /* SOF2 */
+#define FE_JPEG_ARITHMETIC 2         /* arithmetic coding */
+#define FE_JPEG_PRECISION 3          /* 12-bit samples */
+#define FE_JPEG_COMPONENTS 4         /* 4 components (CMYK / YCCK) or 2 */
+#define FE_JPEG_ADOBE_RGB 5          /* 3 components stored as RGB (Adobe transform 0) */
+#define FE_JPEG_SAMPLING 6           /* sampling other than luma 1x1 / 2x1 / 2x2 with chroma 1x1 (4:4:0, 4:1:1, ...) */
+#define FE_JPEG_MULTISCAN 7          /* baseline file with more than one scan */
+#define FE_JPEG_OTHER 8              /* lossless / hierarchical frame, DNL, an EXIF / XMP block only Pillow should judge */
+#define FE_JPEG_BAD_MARKER (-1)      /* not a JPEG file, a marker segment that makes no sense, a table that is missing */
+#define FE_JPEG_BAD_HUFFMAN (-2)     /* a table that is no prefix code, a code that is in no table, a run past the block */
+#define FE_JPEG_PREMATURE_END (-3)   /* the file or a segment ends before its data does */
+#define FE_JPEG_BAD_RESTART (-4)     /* a restart marker out of sequence, or where none belongs */
+#define FE_JPEG_BAD_DIMENSIONS (-5)  /* the file's size is not the h, w of the call */
+#define FE_JPEG_BAD_COEFFICIENT (-6) /* samples so far out of range that libjpeg's C and SIMD transforms stop agreeing */
+typedef struct { int32_t width, height, components, hsamp, vsamp, restart_interval, orientation, status; } fe_jpeg_info;
+/* Reads the markers of one file on the host; needs no context. width / height as stored (before any EXIF transpose), hsamp / vsamp the
+ * luma sampling factors, orientation the EXIF tag 0x0112 (1 when absent), status as above with 0 = fe_jpeg_decode takes this file. */
+int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info);
+/* n files -> dst [n,h,w,3] uint8 (device memory with dst_on_device, else host), the pixels of Pillow's
+ * `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` (utils/image_loading.py:100-106; apply_orientation = 0: without the transpose),
+ * as B,G,R with bgr. Baseline Huffman files, YCbCr 4:4:4 / 4:2:2 / 4:2:0 or grayscale, one scan, with or without restart markers; the
+ * files of a call may differ in quality, tables, subsampling, restart interval and orientation, and agree on the output size h x w
+ * (after the transpose). status [n] (host): see above; the slot of an image with a non-zero status is left untouched. Returns FE_OK when
+ * every image got a status. Temporaries come from the context's workspace, in as many chunks as it takes. */
+int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation,
+                   int dst_on_device, uint8_t* dst, int32_t* status);
+
 /* ---- image-level entry points (uint8 HWC images in, per-image results out) ------------------------------ */
 /* CLIP from raw RGB images: open_clip eval transform on the GPU (PIL-bicubic shorter side -> 224, center crop 224,
  * /255, CLIP mean/std) + fe_clip_encode_image. Replaces batch_processor.py:95 `scorer.preprocess(pil)` +
