@@ -1527,6 +1527,34 @@ int fe_vlm_vision_configure(fe_ctx* ctx, int n_heads, const int* fullatt_block_i
   FE_API_END(ctx)
 }
 extern "C++" {
+// ---- the blocks every vision encode entry point repeats ----
+// room for `rows` merged embeddings in m.img_embeds
+static void vlm_grow_img_embeds(VlmModel& m, int rows) {
+  if (rows <= m.img_cap) return;
+  if (m.img_embeds) (void)hipFree(m.img_embeds);
+  m.img_embeds = nullptr; m.img_cap = 0;
+  FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
+  m.img_cap = rows;
+}
+// every segment of cu [n + 1] holds a row (`what` names the segments in the error); returns the longest
+static int vlm_longest_segment(const int32_t* cu, int n, const char* what) {
+  int longest = 0;
+  for (int i = 0; i < n; ++i) { FE_CHECK(cu[i + 1] > cu[i], "empty %s segment", what); longest = std::max(longest, cu[i + 1] - cu[i]); }
+  return longest;
+}
+// n elements of a host array into the arena, copied on the stream (src == nullptr: nothing, nullptr)
+template <class T>
+static T* vlm_upload(Ctx& C, const T* src, size_t n) {
+  if (!src) return nullptr;
+  T* d = (T*)C.arena.alloc(n * sizeof(T));
+  FE_HIP(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, C.stream));
+  return d;
+}
+// n bf16 embedding values as fp32 to the host through the arena buffer d_f (copied on the stream: the caller synchronises)
+static void vlm_download_f32(Ctx& C, const bf16* src, size_t n, float* d_f, float* dst) {
+  launch_convert(src, d_f, n, C.stream);
+  FE_HIP(hipMemcpyAsync(dst, d_f, n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+}
 // shared by fe_vlm_encode_images (fp32 rows from the host) and fe_vlm_encode_preprocessed (pixel_values == nullptr: the bf16 rows the last
 // fe_vlm_preprocess_rgb left on the device)
 static void vlm_encode(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* window_index,
@@ -1536,35 +1564,68 @@ static void vlm_encode(fe_ctx* ctx, const float* pixel_values, int n_patches, co
   FE_CHECK(patch_pos_hw && window_index && cu_window_seqlens && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_windows > 0 && n_images > 0,
            "bad arguments");
   FE_CHECK(cu_window_seqlens[0] == 0 && cu_window_seqlens[n_windows] == n_patches && cu_seqlens[0] == 0 && cu_seqlens[n_images] == n_patches, "segment bounds must cover the patches");
-  int max_win = 0, max_full = 0;
-  for (int i = 0; i < n_windows; ++i) { FE_CHECK(cu_window_seqlens[i + 1] > cu_window_seqlens[i], "empty window segment"); max_win = std::max(max_win, cu_window_seqlens[i + 1] - cu_window_seqlens[i]); }
-  for (int i = 0; i < n_images; ++i) { FE_CHECK(cu_seqlens[i + 1] > cu_seqlens[i], "empty image segment"); max_full = std::max(max_full, cu_seqlens[i + 1] - cu_seqlens[i]); }
+  const int max_win = vlm_longest_segment(cu_window_seqlens, n_windows, "window"), max_full = vlm_longest_segment(cu_seqlens, n_images, "image");
   for (int i = 0; i < n_patches / 4; ++i) FE_CHECK(window_index[i] >= 0 && window_index[i] < n_patches / 4, "window_index out of range");
   const int rows = n_patches / 4;
-  if (rows > m.img_cap) {
-    if (m.img_embeds) (void)hipFree(m.img_embeds);
-    m.img_embeds = nullptr; m.img_cap = 0;
-    FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
-    m.img_cap = rows;
-  }
+  vlm_grow_img_embeds(m, rows);
   C.arena.reset();
-  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * m.vis.patch_dim * sizeof(float)) : nullptr;
-  int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
-  int* d_widx = (int*)C.arena.alloc((size_t)rows * sizeof(int));
-  int* d_cw = (int*)C.arena.alloc((size_t)(n_windows + 1) * sizeof(int));
-  int* d_cf = (int*)C.arena.alloc((size_t)(n_images + 1) * sizeof(int));
-  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * m.vis.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_widx, window_index, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_cw, cu_window_seqlens, (size_t)(n_windows + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_cf, cu_seqlens, (size_t)(n_images + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
+  float* d_pv = vlm_upload(C, pixel_values, (size_t)n_patches * m.vis.patch_dim);
+  int* d_pos = vlm_upload(C, patch_pos_hw, (size_t)n_patches * 2);
+  int* d_widx = vlm_upload(C, window_index, (size_t)rows);
+  int* d_cw = vlm_upload(C, cu_window_seqlens, (size_t)n_windows + 1);
+  int* d_cf = vlm_upload(C, cu_seqlens, (size_t)n_images + 1);
   vlm_vision_forward(C, m, d_pv, n_patches, d_pos, d_widx, d_cw, n_windows, max_win, d_cf, n_images, max_full, m.img_embeds,
                      pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv);
   m.img_rows = rows;
-  if (embeds) {
-    float* d_f = (float*)C.arena.alloc((size_t)rows * m.hidden * sizeof(float));
-    launch_convert((const bf16*)m.img_embeds, d_f, (size_t)rows * m.hidden, C.stream);
-    FE_HIP(hipMemcpyAsync(embeds, d_f, (size_t)rows * m.hidden * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  const size_t per = (size_t)rows * m.hidden;
+  if (embeds) vlm_download_f32(C, m.img_embeds, per, (float*)C.arena.alloc(per * sizeof(float)), embeds);
+  FE_HIP(hipStreamSynchronize(C.stream));
+}
+// shared by fe_vlm2_encode_images and fe_vlm3_encode_images: the LayerNorm tower. `fn` names the entry point in the errors; Qwen2-VL has
+// no interpolation taps (interp_idx == interp_w == nullptr) and no DeepStack blocks
+static void vlm_ln_encode(fe_ctx* ctx, const char* fn, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* interp_idx,
+                          const float* interp_w, const int32_t* cu_seqlens, int n_seg, float* embeds, float* deepstack) {
+  Ctx& C = ctx->c;
+  VlmModel& m = *C.vlm;
+  const VlmLnVisionW& v = m.vis_ln;
+  const bool taps = m.cfg.qwen3;
+  if (!pixel_values) {
+    FE_CHECK(m.pre_pv && m.pre_rows > 0, "%s: no pixel_values and no rows of a fe_vlm_preprocess_rgb", fn);
+    FE_CHECK(n_patches == m.pre_rows, "%s: %d patches but the last fe_vlm_preprocess_rgb left %d rows", fn, n_patches, m.pre_rows);
+  }
+  FE_CHECK(patch_pos_hw && (!taps || (interp_idx && interp_w)) && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_seg > 0, "bad arguments");
+  FE_CHECK(cu_seqlens[0] == 0 && cu_seqlens[n_seg] == n_patches, "segment bounds must cover the patches");
+  const int max_seg = vlm_longest_segment(cu_seqlens, n_seg, "image");
+  for (size_t i = 0; taps && i < (size_t)n_patches * 4; ++i) FE_CHECK(interp_idx[i] >= 0 && interp_idx[i] < v.n_pos, "interp_idx out of range (%d position embeddings)", v.n_pos);
+  const int rows = n_patches / 4, nds = (int)v.ds_blocks.size();
+  vlm_grow_img_embeds(m, rows);
+  if (nds > 0 && rows > m.ds_cap) {
+    if (m.ds_feats) (void)hipFree(m.ds_feats);
+    m.ds_feats = nullptr; m.ds_cap = 0; m.ds_n = 0;
+    FE_HIP(hipMalloc((void**)&m.ds_feats, (size_t)nds * rows * m.hidden * sizeof(bf16)));
+    m.ds_cap = rows;
+  }
+  m.img_rows = 0; m.ds_n = 0;
+  C.arena.reset();
+  float* d_pv = vlm_upload(C, pixel_values, (size_t)n_patches * v.patch_dim);
+  int* d_pos = vlm_upload(C, patch_pos_hw, (size_t)n_patches * 2);
+  int* d_ii = taps ? vlm_upload(C, interp_idx, (size_t)n_patches * 4) : nullptr;
+  float* d_iw = taps ? vlm_upload(C, interp_w, (size_t)n_patches * 4) : nullptr;
+  int* d_cu = vlm_upload(C, cu_seqlens, (size_t)n_seg + 1);
+  vlm_ln_vision_forward(C, m, d_pv, pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv, n_patches, d_pos, d_ii, d_iw, d_cu, n_seg, max_seg, m.img_embeds,
+                        nds > 0 ? m.ds_feats : (bf16*)nullptr);
+  m.img_rows = rows; m.ds_n = nds;
+  const size_t per = (size_t)rows * m.hidden;
+  if (embeds || (deepstack && nds > 0)) {
+    float* d_f = (float*)C.arena.alloc(per * sizeof(float));
+    if (embeds) {
+      vlm_download_f32(C, m.img_embeds, per, d_f, embeds);
+      FE_HIP(hipStreamSynchronize(C.stream));      // d_f is reused: each copy drains before the next
+    }
+    for (int k = 0; deepstack && k < nds; ++k) {
+      vlm_download_f32(C, m.ds_feats + (size_t)k * m.ds_cap * m.hidden, per, d_f, deepstack + (size_t)k * per);
+      FE_HIP(hipStreamSynchronize(C.stream));
+    }
   }
   FE_HIP(hipStreamSynchronize(C.stream));
 }
@@ -1604,12 +1665,12 @@ int fe_vlm_preprocess_rgb(fe_ctx* ctx, const uint8_t* rgb, int n_images, const i
   FE_API_BEGIN(ctx)
   const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;      // Qwen3-VL: 16-pixel patches (32-pixel merge blocks)
   const bool q2 = ctx->c.vlm && ctx->c.vlm->cfg.qwen2;      // Qwen2-VL: the 14-pixel patches of Qwen2.5-VL
-  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : (q2 ? ctx->c.vlm->vis2.present : ctx->c.vlm->vis.present))) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
+  if (!ctx->c.vlm || !(q3 || q2 ? ctx->c.vlm->vis_ln.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded (checkpoint had no model.visual.* tensors)"; return FE_ERR_NOT_LOADED; }
   Ctx& C = ctx->c;
   VlmModel& m = *C.vlm;
   FE_CHECK(rgb && sizes && mean && stdv && n_images > 0, "bad arguments");
   const int P = q3 ? 16 : 14, F = 2 * P, PD = 6 * P * P;
-  const int tower_pd = q3 ? m.vis3.patch_dim : (q2 ? m.vis2.patch_dim : m.vis.patch_dim);
+  const int tower_pd = q3 || q2 ? m.vis_ln.patch_dim : m.vis.patch_dim;
   FE_CHECK(tower_pd == PD, "preprocess_rgb: the vision tower takes %d-value patches (3 x 2 x %d x %d built)", tower_pd, P, P);
   size_t in_b = 0, rows = 0, px_max = 0;
   for (int i = 0; i < n_images; ++i) {
@@ -1689,65 +1750,11 @@ int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, fl
 int fe_vlm3_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* interp_idx, const float* interp_w,
                           const int32_t* cu_seqlens, int n_seg, float* embeds, float* deepstack) {
   FE_API_BEGIN(ctx)
-  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen3 || !ctx->c.vlm->vis3.present) {
+  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen3 || !ctx->c.vlm->vis_ln.present) {
     ctx->c.err = "qwen3-vl vision tower not loaded (fe_vlm3_configure before the commit; the checkpoint needs model.visual.*)";
     return FE_ERR_NOT_LOADED;
   }
-  Ctx& C = ctx->c;
-  VlmModel& m = *C.vlm;
-  const Vlm3VisionW& v = m.vis3;
-  if (!pixel_values) {
-    FE_CHECK(m.pre_pv && m.pre_rows > 0, "vlm3_encode_images: no pixel_values and no rows of a fe_vlm_preprocess_rgb");
-    FE_CHECK(n_patches == m.pre_rows, "vlm3_encode_images: %d patches but the last fe_vlm_preprocess_rgb left %d rows", n_patches, m.pre_rows);
-  }
-  FE_CHECK(patch_pos_hw && interp_idx && interp_w && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_seg > 0, "bad arguments");
-  FE_CHECK(cu_seqlens[0] == 0 && cu_seqlens[n_seg] == n_patches, "segment bounds must cover the patches");
-  int max_seg = 0;
-  for (int i = 0; i < n_seg; ++i) { FE_CHECK(cu_seqlens[i + 1] > cu_seqlens[i], "empty image segment"); max_seg = std::max(max_seg, cu_seqlens[i + 1] - cu_seqlens[i]); }
-  for (size_t i = 0; i < (size_t)n_patches * 4; ++i) FE_CHECK(interp_idx[i] >= 0 && interp_idx[i] < v.n_pos, "interp_idx out of range (%d position embeddings)", v.n_pos);
-  const int rows = n_patches / 4, nds = (int)v.ds_blocks.size();
-  if (rows > m.img_cap) {
-    if (m.img_embeds) (void)hipFree(m.img_embeds);
-    m.img_embeds = nullptr; m.img_cap = 0;
-    FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
-    m.img_cap = rows;
-  }
-  if (nds > 0 && rows > m.ds_cap) {
-    if (m.ds_feats) (void)hipFree(m.ds_feats);
-    m.ds_feats = nullptr; m.ds_cap = 0; m.ds_n = 0;
-    FE_HIP(hipMalloc((void**)&m.ds_feats, (size_t)nds * rows * m.hidden * sizeof(bf16)));
-    m.ds_cap = rows;
-  }
-  m.img_rows = 0; m.ds_n = 0;
-  C.arena.reset();
-  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * v.patch_dim * sizeof(float)) : nullptr;
-  int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
-  int* d_ii = (int*)C.arena.alloc((size_t)n_patches * 4 * sizeof(int));
-  float* d_iw = (float*)C.arena.alloc((size_t)n_patches * 4 * sizeof(float));
-  int* d_cu = (int*)C.arena.alloc((size_t)(n_seg + 1) * sizeof(int));
-  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * v.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_ii, interp_idx, (size_t)n_patches * 4 * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_iw, interp_w, (size_t)n_patches * 4 * sizeof(float), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_cu, cu_seqlens, (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  vlm3_vision_forward(C, m, d_pv, pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv, n_patches, d_pos, d_ii, d_iw, d_cu, n_seg, max_seg, m.img_embeds,
-                      nds > 0 ? m.ds_feats : (bf16*)nullptr);
-  m.img_rows = rows; m.ds_n = nds;
-  const size_t per = (size_t)rows * m.hidden;
-  if (embeds || (deepstack && nds > 0)) {
-    float* d_f = (float*)C.arena.alloc(per * sizeof(float));
-    if (embeds) {
-      launch_convert((const bf16*)m.img_embeds, d_f, per, C.stream);
-      FE_HIP(hipMemcpyAsync(embeds, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
-      FE_HIP(hipStreamSynchronize(C.stream));
-    }
-    for (int k = 0; deepstack && k < nds; ++k) {
-      launch_convert((const bf16*)m.ds_feats + (size_t)k * m.ds_cap * m.hidden, d_f, per, C.stream);
-      FE_HIP(hipMemcpyAsync(deepstack + (size_t)k * per, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
-      FE_HIP(hipStreamSynchronize(C.stream));
-    }
-  }
-  FE_HIP(hipStreamSynchronize(C.stream));
+  vlm_ln_encode(ctx, "vlm3_encode_images", pixel_values, n_patches, patch_pos_hw, interp_idx, interp_w, cu_seqlens, n_seg, embeds, deepstack);
   FE_API_END_CAPACITY(ctx)
 }
 // ---- Qwen2-VL (the composition model, models/vlm_composition.py): the Qwen2.5-VL decoder entry points, a tower of its own ---------------------
@@ -1767,65 +1774,25 @@ int fe_vlm2_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, fl
 }
 int fe_vlm2_encode_images(fe_ctx* ctx, const float* pixel_values, int n_patches, const int32_t* patch_pos_hw, const int32_t* cu_seqlens, int n_seg, float* embeds) {
   FE_API_BEGIN(ctx)
-  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen2 || !ctx->c.vlm->vis2.present) {
+  if (!ctx->c.vlm || !ctx->c.vlm->cfg.qwen2 || !ctx->c.vlm->vis_ln.present) {
     ctx->c.err = "qwen2-vl vision tower not loaded (fe_vlm2_configure before the commit; the checkpoint needs model.visual.*)";
     return FE_ERR_NOT_LOADED;
   }
-  Ctx& C = ctx->c;
-  VlmModel& m = *C.vlm;
-  const Vlm2VisionW& v = m.vis2;
-  if (!pixel_values) {
-    FE_CHECK(m.pre_pv && m.pre_rows > 0, "vlm2_encode_images: no pixel_values and no rows of a fe_vlm_preprocess_rgb");
-    FE_CHECK(n_patches == m.pre_rows, "vlm2_encode_images: %d patches but the last fe_vlm_preprocess_rgb left %d rows", n_patches, m.pre_rows);
-  }
-  FE_CHECK(patch_pos_hw && cu_seqlens && n_patches > 0 && n_patches % 4 == 0 && n_seg > 0, "bad arguments");
-  FE_CHECK(cu_seqlens[0] == 0 && cu_seqlens[n_seg] == n_patches, "segment bounds must cover the patches");
-  int max_seg = 0;
-  for (int i = 0; i < n_seg; ++i) { FE_CHECK(cu_seqlens[i + 1] > cu_seqlens[i], "empty image segment"); max_seg = std::max(max_seg, cu_seqlens[i + 1] - cu_seqlens[i]); }
-  const int rows = n_patches / 4;
-  if (rows > m.img_cap) {
-    if (m.img_embeds) (void)hipFree(m.img_embeds);
-    m.img_embeds = nullptr; m.img_cap = 0;
-    FE_HIP(hipMalloc((void**)&m.img_embeds, (size_t)rows * m.hidden * sizeof(bf16)));
-    m.img_cap = rows;
-  }
-  m.img_rows = 0;
-  C.arena.reset();
-  float* d_pv = pixel_values ? (float*)C.arena.alloc((size_t)n_patches * v.patch_dim * sizeof(float)) : nullptr;
-  int* d_pos = (int*)C.arena.alloc((size_t)n_patches * 2 * sizeof(int));
-  int* d_cu = (int*)C.arena.alloc((size_t)(n_seg + 1) * sizeof(int));
-  if (pixel_values) FE_HIP(hipMemcpyAsync(d_pv, pixel_values, (size_t)n_patches * v.patch_dim * sizeof(float), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_pos, patch_pos_hw, (size_t)n_patches * 2 * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  FE_HIP(hipMemcpyAsync(d_cu, cu_seqlens, (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice, C.stream));
-  vlm2_vision_forward(C, m, d_pv, pixel_values ? (const bf16*)nullptr : (const bf16*)m.pre_pv, n_patches, d_pos, d_cu, n_seg, max_seg, m.img_embeds);
-  m.img_rows = rows;
-  if (embeds) {
-    const size_t per = (size_t)rows * m.hidden;
-    float* d_f = (float*)C.arena.alloc(per * sizeof(float));
-    launch_convert((const bf16*)m.img_embeds, d_f, per, C.stream);
-    FE_HIP(hipMemcpyAsync(embeds, d_f, per * sizeof(float), hipMemcpyDeviceToHost, C.stream));
-  }
-  FE_HIP(hipStreamSynchronize(C.stream));
+  vlm_ln_encode(ctx, "vlm2_encode_images", pixel_values, n_patches, patch_pos_hw, nullptr, nullptr, cu_seqlens, n_seg, embeds, nullptr);
   FE_API_END_CAPACITY(ctx)
 }
 int fe_vlm_vision_dims(fe_ctx* ctx, int* dims) {
   FE_API_BEGIN(ctx)
-  const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3;
-  if (ctx->c.vlm && ctx->c.vlm->cfg.qwen2) {
-    if (!ctx->c.vlm->vis2.present) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
-    FE_CHECK(dims, "bad arguments");
-    dims[0] = 14; dims[1] = ctx->c.vlm->vis2.patch_dim; dims[2] = 0; dims[3] = 0;
-    return FE_OK;
-  }
-  if (!ctx->c.vlm || !(q3 ? ctx->c.vlm->vis3.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
+  const bool q3 = ctx->c.vlm && ctx->c.vlm->cfg.qwen3, q2 = ctx->c.vlm && ctx->c.vlm->cfg.qwen2;
+  if (!ctx->c.vlm || !(q3 || q2 ? ctx->c.vlm->vis_ln.present : ctx->c.vlm->vis.present)) { ctx->c.err = "vlm vision tower not loaded"; return FE_ERR_NOT_LOADED; }
   FE_CHECK(dims, "bad arguments");
   const VlmModel& m = *ctx->c.vlm;
   if (q3) {
     int side = 0;
-    while ((side + 1) * (side + 1) <= m.vis3.n_pos) ++side;
-    dims[0] = m.vis3.patch_side; dims[1] = m.vis3.patch_dim; dims[2] = (int)m.vis3.ds_blocks.size(); dims[3] = side * side == m.vis3.n_pos ? side : 0;
+    while ((side + 1) * (side + 1) <= m.vis_ln.n_pos) ++side;
+    dims[0] = m.vis_ln.patch_side; dims[1] = m.vis_ln.patch_dim; dims[2] = (int)m.vis_ln.ds_blocks.size(); dims[3] = side * side == m.vis_ln.n_pos ? side : 0;
   } else {
-    dims[0] = 14; dims[1] = m.vis.patch_dim; dims[2] = 0; dims[3] = 0;
+    dims[0] = 14; dims[1] = q2 ? m.vis_ln.patch_dim : m.vis.patch_dim; dims[2] = 0; dims[3] = 0;
   }
   FE_API_END(ctx)
 }

@@ -249,7 +249,7 @@ struct VlmConfig {
   // Qwen3-VL (fe_vlm3_configure): q|k|v without bias, q_norm / k_norm, interleaved M-RoPE, tied lm_head allowed, DeepStack features
   // from after vision blocks deepstack[0 .. n_deepstack) added to the image rows after decoder layers 0 .. n_deepstack - 1
   bool qwen3 = false; int deepstack[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_deepstack = 0;
-  // Qwen2-VL (fe_vlm2_configure): the Qwen2.5-VL decoder with a tied lm_head allowed, and the LayerNorm / QuickGELU tower (model_vlm2_vision.hip)
+  // Qwen2-VL (fe_vlm2_configure): the Qwen2.5-VL decoder with a tied lm_head allowed, and the LayerNorm / QuickGELU tower (model_vlm_ln_vision.hip)
   bool qwen2 = false;
 };
 
@@ -409,28 +409,21 @@ struct VlmVisionW {      // model.visual.* (model_vlm_vision.hip)
   int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0;
   std::vector<int> fullatt;
 };
-// Qwen3-VL vision tower (model_vlm3_vision.hip): LayerNorm blocks with biases, learned position table, DeepStack mergers
-struct Vlm3MergerW { float* ln_g = nullptr; float* ln_b = nullptr; ConvW fc1, fc2; };
-struct Vlm3VisionBlockW { ConvW qkv, proj, fc1, fc2; float* n1g = nullptr; float* n1b = nullptr; float* n2g = nullptr; float* n2b = nullptr; };
-struct Vlm3VisionW {
+// the LayerNorm towers (model_vlm_ln_vision.hip): Qwen2-VL (head_dim 80, QuickGELU) and Qwen3-VL (head_dim 64, tanh GELU, learned position
+// table, DeepStack mergers) - LayerNorm blocks with biases, attention over each whole image, fc1 / act / fc2
+struct VlmLnMergerW { float* ln_g = nullptr; float* ln_b = nullptr; ConvW fc1, fc2; };      // LayerNorm, fc1, erf GELU, fc2
+struct VlmLnBlockW { ConvW qkv, proj, fc1, fc2; float* n1g = nullptr; float* n1b = nullptr; float* n2g = nullptr; float* n2b = nullptr; };
+struct VlmLnVisionW {
   bool present = false;
   ConvW patch;
-  float* pos_table = nullptr;      // [n_pos][hidden]: the bf16 table widened to fp32
-  std::vector<Vlm3VisionBlockW> blocks;
-  Vlm3MergerW merger;
-  std::vector<Vlm3MergerW> ds_mergers;
+  float* pos_table = nullptr;      // Qwen3 only: [n_pos][hidden], the bf16 table widened to fp32
+  std::vector<VlmLnBlockW> blocks;
+  VlmLnMergerW merger;             // per-row LayerNorm form
+  std::vector<VlmLnMergerW> ds_mergers;      // Qwen3 only (DeepStack: LayerNorm over the 4 hidden-wide view), after the blocks ds_blocks
   std::vector<int> ds_blocks;
   float* inv_freq = nullptr;
+  int head_dim = 0, act = ACT_NONE;      // 80 / ACT_QUICKGELU or 64 / ACT_GELU
   int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0, patch_side = 0, n_pos = 0;
-};
-// Qwen2-VL vision tower (model_vlm2_vision.hip): LayerNorm blocks with biases, head_dim 80 over each whole image, fc1 / QuickGELU / fc2
-struct Vlm2VisionW {
-  bool present = false;
-  ConvW patch;
-  std::vector<Vlm3VisionBlockW> blocks;
-  Vlm3MergerW merger;      // ln_q (LayerNorm per patch row), mlp.0, erf GELU, mlp.2
-  float* inv_freq = nullptr;
-  int hidden = 0, heads = 0, inter = 0, out_hidden = 0, patch_dim = 0;
 };
 struct VlmModel {
   DeviceWeights dw;
@@ -452,36 +445,33 @@ struct VlmModel {
   float* last_lp = nullptr;
   // patch rows of the last fe_vlm_preprocess_rgb (device bf16 [pre_rows][patch_dim]), the input of fe_vlm_encode_preprocessed
   bf16* pre_pv = nullptr; int pre_rows = 0, pre_cap = 0;
-  // Qwen3-VL: the vision tower, the DeepStack features of the last fe_vlm3_encode_images (device bf16 [n_ds][ds_cap][hidden], rows as
-  // img_embeds), and the row -> image-row slot map of the prefill in flight (device int [rows], -1 for text rows; null outside a prefill)
-  Vlm3VisionW vis3;
+  // Qwen2-VL / Qwen3-VL: the LayerNorm tower. Qwen3-VL: the DeepStack features of the last fe_vlm3_encode_images (device bf16
+  // [n_ds][ds_cap][hidden], rows as img_embeds), and the row -> image-row slot map of the prefill in flight (device int [rows], -1 for text
+  // rows; null outside a prefill)
+  VlmLnVisionW vis_ln;
   bf16* ds_feats = nullptr; int ds_n = 0, ds_cap = 0;
   const int* ds_slot = nullptr;
-  Vlm2VisionW vis2;      // Qwen2-VL
   void reserve_cache(int B, int max_seq);
   void release_cache();
   ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); if (ds_feats) (void)hipFree(ds_feats); }
 };
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg);
 void build_vlm_vision(VlmModel& m, const WeightStore& ws);
-void build_vlm3_vision(VlmModel& m, const WeightStore& ws);
-void build_vlm2_vision(VlmModel& m, const WeightStore& ws);
-// Qwen2-VL tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, 2x2-block-major order); cu [n_seg + 1]
-// (one segment per image). out [N/4][out_hidden], rows in the order of the patches' merge blocks
-void vlm2_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* cu, int n_seg, int max_seg, bf16* out);
-// pieces of the towers shared between the families (model_vlm_vision.hip: head_dim 80; model_vlm3_vision.hip: the LayerNorm merger)
-//   2-D rotary embedding on the q / k thirds of fused qkv rows [rows][3 * heads * 80] -> q_out / k_out [rows][heads * 80]
-void vlm_vis_rope80(Ctx& c, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads);
+void build_vlm_ln_vision(VlmModel& m, const WeightStore& ws);      // the family: m.cfg.qwen3, else Qwen2-VL
+// pieces shared by the three towers (model_vlm_vision.hip), hd = head_dim 64 or 80
+//   2-D rotary embedding on the q / k thirds of fused qkv rows [rows][3 * heads * hd] -> q_out / k_out [rows][heads * hd]
+void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads);
 //   non-causal attention inside the segments cu [n_seg + 1] (longest: max_seg rows), v = the V third of the fused qkv rows
-void vlm_vis_attention80(Ctx& c, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads);
-//   the 20 frequencies of VisionRotaryEmbedding(head_dim 80 / 2)
-float* vlm_vis_inv_freq80(DeviceWeights& dw);
-//   LayerNorm (over 4 d: postshuffle, or per d-wide row), fc1, erf GELU, fc2 on [N][d] rows viewed as [N/4][4 d]; n / t0: [N][d] scratch
-void vlm_ln_merger(Ctx& c, const Vlm3MergerW& w, const bf16* x, int N, int d, bool postshuffle, bf16* n, bf16* t0, bf16* out, int out_d);
-// Qwen3-VL tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, block-major order); interp_idx [N][4] /
-// interp_w [N][4] (bilinear taps into the position table); cu [n_seg + 1] (one segment per image). out [N/4][out_hidden], ds [n_ds][N/4][out_hidden]
-void vlm3_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* interp_idx, const float* interp_w,
-                         const int* cu, int n_seg, int max_seg, bf16* out, bf16* ds);
+void vlm_vis_attention(Ctx& c, int hd, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads);
+//   the hd / 4 frequencies of VisionRotaryEmbedding(hd / 2)
+float* vlm_vis_inv_freq(DeviceWeights& dw, int hd);
+//   x = bf16(gelu_erf(x)) on n elements (a multiple of 4)
+void vlm_gelu_erf(Ctx& c, bf16* x, size_t n);
+// LayerNorm tower: pv fp32 patch rows or (pv == nullptr) pv_bf16; pos [N][2] (row, column per patch, 2x2-block-major order); interp_idx [N][4] /
+// interp_w [N][4] (bilinear taps into the position table; nullptr: no table, Qwen2-VL); cu [n_seg + 1] (one segment per image). out
+// [N/4][out_hidden], rows in the order of the patches' merge blocks; ds [n_ds][ds_cap][out_hidden] (nullptr: no DeepStack features)
+void vlm_ln_vision_forward(Ctx& c, VlmModel& m, const float* pv, const bf16* pv_bf16, int N, const int* pos, const int* interp_idx, const float* interp_w,
+                           const int* cu, int n_seg, int max_seg, bf16* out, bf16* ds);
 // pv: fp32 patch rows, or (pv == nullptr) pv_bf16: the rows already in bf16 (fe_vlm_preprocess_rgb)
 void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* pos, const int* widx, const int* cu_win, int n_win, int max_win,
                         const int* cu_full, int n_full, int max_full, bf16* out, const bf16* pv_bf16 = nullptr);
@@ -491,7 +481,9 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
 void vlm_patchify(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut, bf16* out_bf16, float* out_f32);
 // the same for 16-pixel patches (Qwen3-VL): oh, ow multiples of 32, rows [oh/16 * ow/16][3*2*16*16]
 void vlm_patchify16(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut, bf16* out_bf16, float* out_f32);
-// row kernels shared by the decoder and the vision tower (model_vlm.hip)
+// row kernels and helpers shared by the decoder and the vision towers (model_vlm.hip)
+inline int grid_n(size_t n, int per = 256) { size_t g = (n + per - 1) / per; return (int)(g > 65535 * 4 ? 65535 * 4 : (g ? g : 1)); }      // grid-stride launches
+bf16* upload_bf16(DeviceWeights& dw, const std::vector<float>& v);
 void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps);
 void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n);
 void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n);

@@ -12,6 +12,7 @@
 // (tests/golden/make_vlm_golden.py) - pinned.
 // Not in this slice: the vision tower (window attention, patch merger) and fp8 attention; image tokens enter as rows of `embeds`.
 #include "engine.h"
+#include "vlm_attn_tile.h"
 #include <type_traits>
 #include <cmath>
 #include <cstring>
@@ -154,12 +155,8 @@ __global__ void vlm_last_rows_kernel(const bf16* __restrict__ x, bf16* __restric
 }
 
 // ---- prefill attention: causal, grouped-query, head_dim 128, on the bf16 matrix cores --------------------------------------------------
-// One wave owns 32 queries; a workgroup (4 waves = 128 queries) shares 32-key K / V tiles through LDS. Same scheme as
-// kernels_attn_bf16.hip (S^T = K Q^T with one query per accumulator column, online softmax per lane, the exponentiated accumulator
-// rounded to bf16 IS the B operand of O^T += V^T P^T), with 8 k-steps per S tile and four 32-row d-tiles of O. K / V come straight from
-// the cache rows ([pos][128]); V is transposed on its way into LDS (two-byte scatter), K rows are copied as they are.
-constexpr int VA_KS = 272;      // K tile row stride in bytes (256 + 16: conflict-free 16-byte reads over rows distinct mod 16... )
-constexpr int VA_VS = 72;       // V^T tile row stride in bytes (64 + 8)
+// One wave owns 32 queries; a workgroup (4 waves = 128 queries) shares 32-key K / V tiles through LDS: the tile of vlm_attn_tile.h (the
+// vision towers' too) with 8 k-steps per S tile and four 32-row d-tiles of O. K / V come straight from the cache rows ([pos][128]).
 struct VlmAttnParams {
   const bf16* q; int ldq;       // [B*Lq][nh*128]
   const bf16* kc; const bf16* vc;   // caches [B][nkv][max_seq][128]
@@ -168,12 +165,11 @@ struct VlmAttnParams {
   float scale;
   const int* pad;               // device [B]: sequence b's first pad[b] positions are left padding (masked keys, zero output rows)
 };
-union VA8 { uint4 u; fe_v4f f; };
 
 __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnParams p) {
-  __shared__ __attribute__((aligned(16))) char Ks[2][32 * VA_KS];
-  __shared__ __attribute__((aligned(16))) char Vs[2][128 * VA_VS];
-  const bf16* const tag = nullptr;
+  using T = VlmAttnTile<128>;
+  __shared__ __attribute__((aligned(16))) char Ks[2][T::K_BYTES];
+  __shared__ __attribute__((aligned(16))) char Vs[2][T::V_BYTES];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int bh = blockIdx.y, b = bh / p.nh, head = bh - b * p.nh, kvh = head / (p.nh / p.nkv);
@@ -185,109 +181,34 @@ __global__ __launch_bounds__(256, 2) void vlm_attn_prefill_kernel(const VlmAttnP
   const int qc = qok ? q : p.Lq - 1;
   const int qpos = p.qpos0 + q;
   const int padb = p.pad[b];
-  VA8 qf[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) qf[s].u = *reinterpret_cast<const uint4*>(Qp + (size_t)qc * p.ldq + 16 * s + 8 * h);
+  T::F8 qf[T::KSTEPS];
+  T::load_q(qf, Qp + (size_t)qc * p.ldq, h);
   // this workgroup's queries end at position qpos0 + (blockIdx.x + 1) * 128 - 1: later keys are masked for all of them
   const int kend = min(p.Lk, p.qpos0 + (int)(blockIdx.x + 1) * 128);
   const int nt = (kend + 31) / 32;
   // left padding: the key loop starts at the first 32-key tile that holds a live key (whole pad tiles cost nothing)
   const int kt0 = min(padb / 32, nt);
-  uint4 kr[2], vr[2];
-  auto load_tile = [&](int kt) {
+  uint4 kr[T::pieces(256)], vr[T::pieces(256)];
+  fe_f32x16 o[T::DT];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = t + i * 256;                 // 512 chunks of 16 B: key = c >> 4, d = (c & 15) * 8
-      int key = kt * 32 + (c >> 4);
-      if (key > p.Lk - 1) key = p.Lk - 1;        // masked after QK^T
-      kr[i] = *reinterpret_cast<const uint4*>(Kp + (size_t)key * 128 + (c & 15) * 8);
-      vr[i] = *reinterpret_cast<const uint4*>(Vp + (size_t)key * 128 + (c & 15) * 8);
-    }
-  };
-  auto store_tile = [&](int buf, int kt) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = t + i * 256, key = c >> 4, d0 = (c & 15) * 8;
-      *reinterpret_cast<uint4*>(&Ks[buf][key * VA_KS + d0 * 2]) = kr[i];
-      const bool live = kt * 32 + key < p.Lk;   // keys past Lk contribute zero rows of V (their probabilities are zero anyway)
-      const unsigned w[4] = {vr[i].x, vr[i].y, vr[i].z, vr[i].w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const unsigned short v = live ? (unsigned short)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xFFFFu)) : (unsigned short)0;
-        *reinterpret_cast<unsigned short*>(&Vs[buf][(d0 + e) * VA_VS + key * 2]) = v;
-      }
-    }
-  };
-  fe_f32x16 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
+  for (int dt = 0; dt < T::DT; ++dt)
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
   float m = -INFINITY, l = 0.f;
-  load_tile(kt0);
-  store_tile(0, kt0);
+  T::load<256>(kr, vr, Kp, 128, Vp, 128, kt0, p.Lk - 1, t);
+  T::store<256>(Ks[0], Vs[0], kr, vr, kt0, p.Lk, t);
   __syncthreads();
   for (int kt = kt0; kt < nt; ++kt) {
     const int buf = (kt - kt0) & 1;
-    if (kt + 1 < nt) load_tile(kt + 1);
-    fe_f32x16 st;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[e] = 0.f;
-    const char* kb = &Ks[buf][r * VA_KS + 16 * h];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      VA8 kf;
-      kf.u = *reinterpret_cast<const uint4*>(kb + 32 * s);
-      st = fe_mfma16(tag, kf.f, qf[s].f, st);
-    }
-    const int kbase = kt * 32 + 4 * h;
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = kbase + (e & 3) + 8 * (e >> 2);
-      st[e] = (key >= p.Lk || key > qpos || key < padb) ? -INFINITY : st[e] * p.scale;
-      tmax = fmaxf(tmax, st[e]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-    const float mn = fmaxf(m, tmax);
-    const float msafe = mn == -INFINITY ? 0.f : mn;      // a query row whose keys so far are all masked (rows past Lq, pad rows)
-    const float alpha = __expf(m - msafe);
-    float psum = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { st[e] = __expf(st[e] - msafe); psum += st[e]; }
-    psum += __shfl_xor(psum, 32);
-    l = l * alpha + psum;
-    m = mn;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
-    const char* vb = &Vs[buf][r * VA_VS + 8 * h];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      VA8 pf;
-      pf.u = make_uint4(fe_pack2(tag, st[8 * s], st[8 * s + 1]), fe_pack2(tag, st[8 * s + 2], st[8 * s + 3]),
-                        fe_pack2(tag, st[8 * s + 4], st[8 * s + 5]), fe_pack2(tag, st[8 * s + 6], st[8 * s + 7]));
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const uint2 a0 = *reinterpret_cast<const uint2*>(vb + dt * 32 * VA_VS + 32 * s), a1 = *reinterpret_cast<const uint2*>(vb + dt * 32 * VA_VS + 32 * s + 16);
-        VA8 v;
-        v.u = make_uint4(a0.x, a0.y, a1.x, a1.y);
-        o[dt] = fe_mfma16(tag, v.f, pf.f, o[dt]);
-      }
-    }
-    if (kt + 1 < nt) store_tile(buf ^ 1, kt + 1);
+    if (kt + 1 < nt) T::load<256>(kr, vr, Kp, 128, Vp, 128, kt + 1, p.Lk - 1, t);
+    fe_f32x16 st = T::scores(Ks[buf], qf, r, h);
+    // a query row whose keys so far are all masked (rows past Lq, pad rows) keeps a zero sum: it writes zeros
+    T::softmax(st, m, l, o, p.scale, kt, h, [&](int key) { return (key >= p.Lk) | (key > qpos) | (key < padb); });
+    T::pv(o, st, Vs[buf], r, h);
+    if (kt + 1 < nt) T::store<256>(Ks[buf ^ 1], Vs[buf ^ 1], kr, vr, kt + 1, p.Lk, t);
     __syncthreads();
   }
-  if (qok) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;      // a pad query row has no live key: zeros, not 0 / 0
-    bf16* op = p.o + ((size_t)b * p.Lq + q) * p.ldo + head * 128;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        st4(op + dt * 32 + 8 * g + 4 * h, make_float4(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv));
-  }
+  if (qok) T::write(p.o + ((size_t)b * p.Lq + q) * p.ldo + head * 128, o, l, h);
 }
 
 // x[index[i]][:] = rows[i][:]   (image embeddings into the rows of their <|image_pad|> tokens)
@@ -877,7 +798,7 @@ __global__ void vlm_attn_combine_kernel(const float* __restrict__ po, const floa
 }
 
 // ---- model ---------------------------------------------------------------------------------------------------------------------------
-static bf16* upload_bf16(DeviceWeights& dw, const std::vector<float>& v) {
+bf16* upload_bf16(DeviceWeights& dw, const std::vector<float>& v) {
   std::vector<uint16_t> h(v.size());
   for (size_t i = 0; i < v.size(); ++i) h[i] = f32_to_bf16_bits(v[i]);
   return (bf16*)dw.upload_raw(h.data(), h.size() * sizeof(uint16_t));
@@ -969,8 +890,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
   std::vector<float> inv(64);
   for (int i = 0; i < 64; ++i) inv[i] = 1.0f / powf(cfg.rope_theta, (float)(2 * i) / 128.0f);
   m.inv_freq = m.dw.upload(inv);
-  if (cfg.qwen3) build_vlm3_vision(m, ws);      // model.visual.* when the checkpoint carries it
-  else if (cfg.qwen2) build_vlm2_vision(m, ws);
+  if (cfg.qwen3 || cfg.qwen2) build_vlm_ln_vision(m, ws);      // model.visual.* when the checkpoint carries it
   else build_vlm_vision(m, ws);
 }
 
@@ -1001,7 +921,6 @@ void VlmModel::release_cache() {
   cache_B = 0; max_seq = 0; cur_len = 0;
 }
 
-static inline int grid_n(size_t n, int per = 256) { size_t g = (n + per - 1) / per; return (int)(g > 65535 * 4 ? 65535 * 4 : (g ? g : 1)); }
 
 void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps) {
   hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, ldx, w, y, ldy, rows, d, eps);

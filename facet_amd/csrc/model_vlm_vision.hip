@@ -8,11 +8,12 @@
 // windows (<= 64 patches) except in the `fullatt_block_indexes` blocks (whole image) -> patch merger (RMSNorm, 4 rows -> 1, Linear - GELU -
 // Linear to the decoder width) -> rows back in raster order. bf16 with the rounding points of the bf16 torch modules (each Linear output,
 // RMSNorm before the weight multiply, SiLU before the gate multiply, residual sums, GELU); the rotary embedding is applied in fp32 on the
-// bf16 q / k and rounded once, as apply_rotary_pos_emb_vision does. head_dim is 80 (1280 / 16): the attention kernel below runs 5 k-steps
-// per S tile and three 32-row d-tiles of O (rows 80..95 of V^T are zeros). The index arrays (positions, window order, segment bounds) are
+// bf16 q / k and rounded once, as apply_rotary_pos_emb_vision does. head_dim is 80 (1280 / 16): the attention tile (vlm_attn_tile.h) runs 5
+// k-steps per S tile and three 32-row d-tiles of O (rows 80..95 of V^T are zeros). The index arrays (positions, window order, segment bounds) are
 // the host's (facet_amd/vlm_tagger.py: numpy restatements of transformers.vision_utils, pinned by the golden vectors).
 // Parity: tests/test_vlm_gpu.py against tests/golden/vlm_vision_golden.npz (the reference's own class) - pinned.
 #include "engine.h"
+#include "vlm_attn_tile.h"
 #include <algorithm>
 #include <cmath>
 
@@ -31,12 +32,14 @@ __global__ void vlm_vis_gather_kernel(const bf16* __restrict__ src, bf16* __rest
   }
 }
 
-// 2-D rotary embedding of the vision tower on the q and k thirds of a fused qkv row block. Frequencies: inv_freq[j], j < hd/4; dimension
-// i of a head (pairs (i, i + hd/2)) takes, with jj = i % (hd/2): the row position and inv_freq[jj] for jj < hd/4, the column position and
-// inv_freq[jj - hd/4] otherwise. fp32 arithmetic on the bf16 values, one rounding (apply_rotary_pos_emb_vision).
+// 2-D rotary embedding of a vision tower on the q and k thirds of a fused qkv row block. Frequencies: inv_freq[j], j < HD/4; dimension
+// i of a head (pairs (i, i + HD/2)) takes, with jj = i % (HD/2): the row position and inv_freq[jj] for jj < HD/4, the column position and
+// inv_freq[jj - HD/4] otherwise. fp32 arithmetic on the bf16 values, one rounding (apply_rotary_pos_emb_vision).
+template <int HD>
 __global__ void vlm_vis_rope_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, bf16* __restrict__ q_out,
-                                    bf16* __restrict__ k_out, int rows, int heads, int hd) {
-  const int half = hd / 2, quarter = hd / 4, dim = heads * hd;
+                                    bf16* __restrict__ k_out, int rows, int heads) {
+  constexpr int hd = HD, half = HD / 2, quarter = HD / 4;
+  const int dim = heads * hd;
   const size_t total = (size_t)rows * 2 * heads * half;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int d = (int)(i % half), hh = (int)((i / half) % (2 * heads)), row = (int)(i / ((size_t)half * 2 * heads));
@@ -52,7 +55,7 @@ __global__ void vlm_vis_rope_kernel(const bf16* __restrict__ qkv, const int* __r
   }
 }
 
-// y = bf16(gelu_erf(x)) elementwise (nn.GELU() of the patch merger on a bf16 tensor)
+// y = bf16(gelu_erf(x)) elementwise (nn.GELU() of the patch mergers on a bf16 tensor)
 __global__ void vlm_gelu_kernel(bf16* __restrict__ x, size_t n4) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const float4 a = ld4(x + 4 * i);
@@ -61,25 +64,21 @@ __global__ void vlm_gelu_kernel(bf16* __restrict__ x, size_t n4) {
   }
 }
 
-// ---- attention over packed variable-length segments, head_dim 80, non-causal ---------------------------------------------------------------
-// Segment s = rows cu[s] .. cu[s+1]-1 of the packed sequence (a window, or a whole image in the full-attention blocks). One workgroup =
-// NW waves x 32 queries of one (segment, head); K / V tiles of 32 keys through LDS (V transposed on the way in). Same accumulate-in-place
-// scheme as the decoder's prefill kernel (model_vlm.hip).
-constexpr int VV_KS = 176;      // K tile row stride in bytes (160 + 16)
-constexpr int VV_VS = 72;       // V^T tile row stride in bytes (64 + 8)
+// ---- attention over packed variable-length segments, head_dim 64 or 80, non-causal ---------------------------------------------------------
+// Segment s = rows cu[s] .. cu[s+1]-1 of the packed sequence (a window, or a whole image). One workgroup = NW waves x 32 queries of one
+// (segment, head) on the tile of vlm_attn_tile.h, which the decoder's prefill kernel (model_vlm.hip) runs too.
 struct VisAttnParams {
-  const bf16* q; const bf16* k; int ldqk;       // rotated q / k: [N][heads*80]
-  const bf16* v; int ldv;                       // V third of the fused projection: [N][3*heads*80] + 2*heads*80
+  const bf16* q; const bf16* k; int ldqk;       // rotated q / k: [N][heads*HD]
+  const bf16* v; int ldv;                       // V third of the fused projection: [N][3*heads*HD] + 2*heads*HD
   bf16* o; int ldo;
   const int* cu; int heads; float scale;
 };
-union VV8 { uint4 u; fe_v4f f; };
 
-template <int NW>
+template <int HD, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void vlm_vis_attn_kernel(const VisAttnParams p) {
-  __shared__ __attribute__((aligned(16))) char Ks[2][32 * VV_KS];
-  __shared__ __attribute__((aligned(16))) char Vs[2][96 * VV_VS];
-  const bf16* const tag = nullptr;
+  using T = VlmAttnTile<HD>;
+  __shared__ __attribute__((aligned(16))) char Ks[2][T::K_BYTES];
+  __shared__ __attribute__((aligned(16))) char Vs[2][T::V_BYTES];
   constexpr int NT = NW * 64;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -87,131 +86,39 @@ __global__ __launch_bounds__(NW * 64, 2) void vlm_vis_attn_kernel(const VisAttnP
   const int s0 = p.cu[seg], len = p.cu[seg + 1] - s0;
   const int q0 = blockIdx.x * NW * 32;
   if (q0 >= len) return;
-  for (int i = t; i < 2 * 16 * VV_VS / 4; i += NT) {      // rows 80..95 of both V^T buffers: zeros, never written again
-    const int b = i / (16 * VV_VS / 4), o = i % (16 * VV_VS / 4);
-    reinterpret_cast<unsigned*>(&Vs[b][80 * VV_VS])[o] = 0u;
-  }
-  const bf16* Qp = p.q + (size_t)s0 * p.ldqk + head * 80;
-  const bf16* Kp = p.k + (size_t)s0 * p.ldqk + head * 80;
-  const bf16* Vp = p.v + (size_t)s0 * p.ldv + head * 80;
+  T::template zero_vt_tail<NT>(Vs, t);
+  const bf16* Qp = p.q + (size_t)s0 * p.ldqk + head * HD;
+  const bf16* Kp = p.k + (size_t)s0 * p.ldqk + head * HD;
+  const bf16* Vp = p.v + (size_t)s0 * p.ldv + head * HD;
   const int q = q0 + wave * 32 + r;
   const bool qok = q < len;
   const int qc = qok ? q : len - 1;
-  VV8 qf[5];
+  typename T::F8 qf[T::KSTEPS];
+  T::load_q(qf, Qp + (size_t)qc * p.ldqk, h);
+  uint4 kr[T::pieces(NT)], vr[T::pieces(NT)];
+  fe_f32x16 o[T::DT];
 #pragma unroll
-  for (int s = 0; s < 5; ++s) qf[s].u = *reinterpret_cast<const uint4*>(Qp + (size_t)qc * p.ldqk + 16 * s + 8 * h);
-  constexpr int PIECES = (320 + NT - 1) / NT;      // 32 keys x 10 chunks of 16 B
-  uint4 kr[PIECES], vr[PIECES];
-  auto load_tile = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int c = t + i * NT;
-      if (c < 320) {
-        int key = kt * 32 + c / 10;
-        if (key > len - 1) key = len - 1;
-        kr[i] = *reinterpret_cast<const uint4*>(Kp + (size_t)key * p.ldqk + (c % 10) * 8);
-        vr[i] = *reinterpret_cast<const uint4*>(Vp + (size_t)key * p.ldv + (c % 10) * 8);
-      }
-    }
-  };
-  auto store_tile = [&](int buf, int kt) {
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int c = t + i * NT;
-      if (c < 320) {
-        const int key = c / 10, d0 = (c % 10) * 8;
-        *reinterpret_cast<uint4*>(&Ks[buf][key * VV_KS + d0 * 2]) = kr[i];
-        const bool live = kt * 32 + key < len;
-        const unsigned w[4] = {vr[i].x, vr[i].y, vr[i].z, vr[i].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const unsigned short v = live ? (unsigned short)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xFFFFu)) : (unsigned short)0;
-          *reinterpret_cast<unsigned short*>(&Vs[buf][(d0 + e) * VV_VS + key * 2]) = v;
-        }
-      }
-    }
-  };
-  fe_f32x16 o[3];
-#pragma unroll
-  for (int dt = 0; dt < 3; ++dt)
+  for (int dt = 0; dt < T::DT; ++dt)
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int nt = (len + 31) / 32;
-  load_tile(0);
-  store_tile(0, 0);
+  T::template load<NT>(kr, vr, Kp, p.ldqk, Vp, p.ldv, 0, len - 1, t);
+  T::template store<NT>(Ks[0], Vs[0], kr, vr, 0, len, t);
   __syncthreads();
   for (int kt = 0; kt < nt; ++kt) {
     const int buf = kt & 1;
-    if (kt + 1 < nt) load_tile(kt + 1);
-    fe_f32x16 st;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[e] = 0.f;
-    const char* kb = &Ks[buf][r * VV_KS + 16 * h];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-      VV8 kf;
-      kf.u = *reinterpret_cast<const uint4*>(kb + 32 * s);
-      st = fe_mfma16(tag, kf.f, qf[s].f, st);
-    }
-    const int kbase = kt * 32 + 4 * h;
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = kbase + (e & 3) + 8 * (e >> 2);
-      st[e] = key >= len ? -INFINITY : st[e] * p.scale;
-      tmax = fmaxf(tmax, st[e]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-    const float mn = fmaxf(m, tmax);
-    const float alpha = __expf(m - mn);
-    float psum = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { st[e] = __expf(st[e] - mn); psum += st[e]; }
-    psum += __shfl_xor(psum, 32);
-    l = l * alpha + psum;
-    m = mn;
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
-    const char* vb = &Vs[buf][r * VV_VS + 8 * h];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      VV8 pf;
-      pf.u = make_uint4(fe_pack2(tag, st[8 * s], st[8 * s + 1]), fe_pack2(tag, st[8 * s + 2], st[8 * s + 3]),
-                        fe_pack2(tag, st[8 * s + 4], st[8 * s + 5]), fe_pack2(tag, st[8 * s + 6], st[8 * s + 7]));
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt) {
-        const uint2 a0 = *reinterpret_cast<const uint2*>(vb + dt * 32 * VV_VS + 32 * s), a1 = *reinterpret_cast<const uint2*>(vb + dt * 32 * VV_VS + 32 * s + 16);
-        VV8 v;
-        v.u = make_uint4(a0.x, a0.y, a1.x, a1.y);
-        o[dt] = fe_mfma16(tag, v.f, pf.f, o[dt]);
-      }
-    }
-    if (kt + 1 < nt) store_tile(buf ^ 1, kt + 1);
+    if (kt + 1 < nt) T::template load<NT>(kr, vr, Kp, p.ldqk, Vp, p.ldv, kt + 1, len - 1, t);
+    fe_f32x16 st = T::scores(Ks[buf], qf, r, h);
+    T::softmax(st, m, l, o, p.scale, kt, h, [&](int key) { return key >= len; });      // every tile holds a live key: m stays finite
+    T::pv(o, st, Vs[buf], r, h);
+    if (kt + 1 < nt) T::template store<NT>(Ks[buf ^ 1], Vs[buf ^ 1], kr, vr, kt + 1, len, t);
     __syncthreads();
   }
-  if (qok) {
-    const float inv = 1.f / l;
-    bf16* op = p.o + (size_t)(s0 + q) * p.ldo + head * 80;
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = dt * 32 + 8 * g + 4 * h;
-        if (d0 < 80) st4(op + d0, make_float4(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv));
-      }
-  }
+  if (qok) T::write(p.o + (size_t)(s0 + q) * p.ldo + head * HD, o, l, h);
 }
 
 // ---- model ---------------------------------------------------------------------------------------------------------------------------------
-static bf16* vis_upload_bf16(DeviceWeights& dw, const std::vector<float>& v) {
-  std::vector<uint16_t> h(v.size());
-  for (size_t i = 0; i < v.size(); ++i) h[i] = f32_to_bf16_bits(v[i]);
-  return (bf16*)dw.upload_raw(h.data(), h.size() * sizeof(uint16_t));
-}
-
 void build_vlm_vision(VlmModel& m, const WeightStore& ws) {
   VlmVisionW& v = m.vis;
   const std::string P = "model.visual.";
@@ -236,40 +143,53 @@ void build_vlm_vision(VlmModel& m, const WeightStore& ws) {
     w.gate = build_linear(m.dw, ws, B + ".mlp.gate_proj", true);
     w.up = build_linear(m.dw, ws, B + ".mlp.up_proj", true);
     w.down = build_linear(m.dw, ws, B + ".mlp.down_proj", true);
-    w.n1 = vis_upload_bf16(m.dw, ws.get(B + ".norm1.weight").data);
-    w.n2 = vis_upload_bf16(m.dw, ws.get(B + ".norm2.weight").data);
+    w.n1 = upload_bf16(m.dw, ws.get(B + ".norm1.weight").data);
+    w.n2 = upload_bf16(m.dw, ws.get(B + ".norm2.weight").data);
     v.blocks.push_back(w);
   }
   FE_CHECK(!v.blocks.empty(), "vlm vision: no blocks found");
   v.inter = v.blocks[0].gate.Cout;
-  v.ln_q = vis_upload_bf16(m.dw, ws.get(P + "merger.ln_q.weight").data);
+  v.ln_q = upload_bf16(m.dw, ws.get(P + "merger.ln_q.weight").data);
   v.m0 = build_linear(m.dw, ws, P + "merger.mlp.0", true);
   v.m2 = build_linear(m.dw, ws, P + "merger.mlp.2", true);
   v.out_hidden = v.m2.Cout;
   FE_CHECK(v.m0.Cin == 4 * v.hidden && v.out_hidden == m.hidden, "vlm vision: merger %d -> %d does not fit the tower (%d) / decoder (%d)", v.m0.Cin, v.out_hidden, v.hidden, m.hidden);
-  // Qwen2_5_VisionRotaryEmbedding(head_dim // 2): inv_freq = 1 / 10000^(arange(0, dim, 2) / dim), dim = head_dim / 2
-  v.inv_freq = vlm_vis_inv_freq80(m.dw);
+  v.inv_freq = vlm_vis_inv_freq(m.dw, 80);
   v.fullatt.assign(m.cfg.fullatt, m.cfg.fullatt + m.cfg.n_fullatt);
   v.present = true;
 }
 
-static inline int vgrid(size_t n, int per = 256) { size_t g = (n + per - 1) / per; return (int)(g > 262140 ? 262140 : (g ? g : 1)); }
-
-// ---- the head_dim-80 pieces, shared with the Qwen2-VL tower (model_vlm2_vision.hip) --------------------------------------------------------
-float* vlm_vis_inv_freq80(DeviceWeights& dw) {
-  std::vector<float> inv(20);
-  for (int i = 0; i < 20; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / 40.0f);
+// ---- rope, segment attention and erf GELU of all three towers (the LayerNorm towers: model_vlm_ln_vision.hip) -----------------------------
+static void vis_check_hd(int hd) { FE_CHECK(hd == 64 || hd == 80, "vlm vision: head_dim %d (the rope and attention kernels are built for 64 and 80)", hd); }
+// VisionRotaryEmbedding(head_dim // 2): inv_freq = 1 / 10000^(arange(0, dim, 2) / dim), dim = head_dim / 2
+float* vlm_vis_inv_freq(DeviceWeights& dw, int hd) {
+  vis_check_hd(hd);
+  std::vector<float> inv(hd / 4);
+  for (int i = 0; i < hd / 4; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)(hd / 2));
   return dw.upload(inv);
 }
-void vlm_vis_rope80(Ctx& c, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads) {
-  hipLaunchKernelGGL(vlm_vis_rope_kernel, dim3(vgrid((size_t)rows * 2 * heads * 40)), dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads, 80);
+void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads) {
+  vis_check_hd(hd);
+  const dim3 grid(grid_n((size_t)rows * 2 * heads * (hd / 2)));
+  if (hd == 80) hipLaunchKernelGGL(vlm_vis_rope_kernel<80>, grid, dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads);
+  else hipLaunchKernelGGL(vlm_vis_rope_kernel<64>, grid, dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads);
   FE_HIP(hipGetLastError());
 }
-void vlm_vis_attention80(Ctx& c, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads) {
-  const int d = heads * 80;
-  VisAttnParams ap{q, k, d, qkv + 2 * d, 3 * d, o, d, cu, heads, 1.0f / sqrtf(80.f)};
-  if (max_seg <= 64) hipLaunchKernelGGL(vlm_vis_attn_kernel<2>, dim3((max_seg + 63) / 64, n_seg, heads), dim3(128), 0, c.stream, ap);
-  else hipLaunchKernelGGL(vlm_vis_attn_kernel<4>, dim3((max_seg + 127) / 128, n_seg, heads), dim3(256), 0, c.stream, ap);
+template <int HD>
+static void vis_attention_launch(Ctx& c, const VisAttnParams& ap, int n_seg, int max_seg) {
+  if (max_seg <= 64) hipLaunchKernelGGL((vlm_vis_attn_kernel<HD, 2>), dim3((max_seg + 63) / 64, n_seg, ap.heads), dim3(128), 0, c.stream, ap);
+  else hipLaunchKernelGGL((vlm_vis_attn_kernel<HD, 4>), dim3((max_seg + 127) / 128, n_seg, ap.heads), dim3(256), 0, c.stream, ap);
+  FE_HIP(hipGetLastError());
+}
+void vlm_vis_attention(Ctx& c, int hd, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads) {
+  vis_check_hd(hd);
+  const int d = heads * hd;
+  const VisAttnParams ap{q, k, d, qkv + 2 * d, 3 * d, o, d, cu, heads, 1.0f / sqrtf((float)hd)};
+  if (hd == 80) vis_attention_launch<80>(c, ap, n_seg, max_seg);
+  else vis_attention_launch<64>(c, ap, n_seg, max_seg);
+}
+void vlm_gelu_erf(Ctx& c, bf16* x, size_t n) {
+  hipLaunchKernelGGL(vlm_gelu_kernel, dim3(grid_n(n / 4)), dim3(256), 0, c.stream, x, n / 4);
   FE_HIP(hipGetLastError());
 }
 
@@ -305,15 +225,15 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
   }
   if (pv) launch_convert(pv, pvh, (size_t)N * v.patch_dim, c.stream);      // pixel_values.to(bfloat16), as the patch embedding does
   vis_linear(c, v.patch, pv ? (const bf16*)pvh : pv_bf16, v.patch_dim, N, h0, d);
-  hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(vgrid((size_t)N * d / 8)), dim3(256), 0, c.stream, (const bf16*)h0, x, widx, N / 4, 4, d, 0);
+  hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(grid_n((size_t)N * d / 8)), dim3(256), 0, c.stream, (const bf16*)h0, x, widx, N / 4, 4, d, 0);
   FE_HIP(hipGetLastError());
   for (size_t li = 0; li < v.blocks.size(); ++li) {
     const VlmVisionBlockW& w = v.blocks[li];
     const bool full = std::find(v.fullatt.begin(), v.fullatt.end(), (int)li) != v.fullatt.end();
     vlm_rmsnorm(c, x, d, w.n1, n, d, N, d, 1e-6f);
     vis_linear(c, w.qkv, n, d, N, qkv, 3 * d);
-    vlm_vis_rope80(c, qkv, pos, v.inv_freq, qr, kr, N, H);
-    vlm_vis_attention80(c, qr, kr, qkv, ao, full ? cu_full : cu_win, full ? n_full : n_win, full ? max_full : max_win, H);
+    vlm_vis_rope(c, 80, qkv, pos, v.inv_freq, qr, kr, N, H);
+    vlm_vis_attention(c, 80, qr, kr, qkv, ao, full ? cu_full : cu_win, full ? n_full : n_win, full ? max_full : max_win, H);
     vis_linear(c, w.proj, ao, d, N, br, d);
     vlm_add(c, x, br, (size_t)N * d);
     vlm_rmsnorm(c, x, d, w.n2, n, d, N, d, 1e-6f);
@@ -328,9 +248,9 @@ void vlm_vision_forward(Ctx& c, VlmModel& m, const float* pv, int N, const int* 
   bf16* t0 = c.arena.array<bf16>((size_t)(N / 4) * 4 * d);
   bf16* e = c.arena.array<bf16>((size_t)(N / 4) * v.out_hidden);
   vis_linear(c, v.m0, n, 4 * d, N / 4, t0, 4 * d);
-  hipLaunchKernelGGL(vlm_gelu_kernel, dim3(vgrid((size_t)N * d / 4)), dim3(256), 0, c.stream, t0, (size_t)N * d / 4);
+  vlm_gelu_erf(c, t0, (size_t)N * d);
   vis_linear(c, v.m2, t0, 4 * d, N / 4, e, v.out_hidden);
-  hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(vgrid((size_t)(N / 4) * v.out_hidden / 8)), dim3(256), 0, c.stream, (const bf16*)e, out, widx, N / 4, 1, v.out_hidden, 1);
+  hipLaunchKernelGGL(vlm_vis_gather_kernel, dim3(grid_n((size_t)(N / 4) * v.out_hidden / 8)), dim3(256), 0, c.stream, (const bf16*)e, out, widx, N / 4, 1, v.out_hidden, 1);
   FE_HIP(hipGetLastError());
   c.arena.rewind(mark);
 }
