@@ -163,6 +163,9 @@ SIGNATURES = {
     "fe_swap_rb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "fe_leading_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_external_contours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    "fe_subject_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_resize_u8_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "fe_reduce_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -183,6 +186,7 @@ SIGNATURES = {
                                    C.c_int, C.c_int64, C.c_void_p, C.c_void_p, _i64p]),
 }
 
+FE_CONTOUR_FIELDS = 8      # long longs per contour record
 FE_SIM_FUSED, FE_SIM_COSINE = 0, 1
 FE_SIM_K_MAX = 32
 FE_SIM_NO_DATE = -(1 << 63)
@@ -1092,6 +1096,45 @@ class Engine:
             max_lines = int(counts.max())          # rare: more segments than room - run again with enough
         out = [lines[i, :counts[i]].copy() for i in range(n)]
         return (out, edges) if want_edges else out
+
+    def external_contours(self, binary, min_twice_area=0, max_contours=256):
+        """binary: uint8 [n,h,w] (host array, nonzero = foreground) or (device_ptr, n, h, w) -> list of int64 [k,8] record arrays, one per
+        image: start_index, a00, a10, a01, x_min, y_min, x_max, y_max of every external contour (cv2.findContours RETR_EXTERNAL) with
+        |a00| >= min_twice_area, in descending start_index order (include/facet_engine.h). Runs again with more room when an image has
+        more than max_contours."""
+        if isinstance(binary, tuple):
+            p, n, h, w = binary
+            dev, keep = 1, None
+        else:
+            keep = np.ascontiguousarray(binary, dtype=np.uint8)
+            assert keep.ndim == 3, "expected [n,h,w]"
+            (n, h, w), p, dev = keep.shape, keep.ctypes.data_as(C.c_void_p), 0
+        return self._contour_call(lambda room, rec, cnt: self.lib.fe_external_contours(self.h, p, n, h, w, dev, int(min_twice_area), room, rec, cnt),
+                                  n, max_contours)
+
+    def _contour_call(self, call, n, max_contours):
+        room = max(1, int(max_contours))
+        for _ in range(2):
+            rec = np.zeros((n, room, FE_CONTOUR_FIELDS), np.int64)
+            counts = np.zeros(n, np.int32)
+            self._ck(call(room, rec.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+            if int(counts.max()) <= room:
+                return [rec[i, :counts[i]].copy() for i in range(n)]
+            room = int(counts.max())
+        raise EngineError(f"contours: {int(counts.max())} contours found after making room for {room}")
+
+    def subject_contours(self, images, max_contours=256, want_edges=False, want_thresholds=False):
+        """BGR uint8 [n,h,w,3] (or device tuple) -> list of int64 [k,8] record arrays (as external_contours) of the external contours of
+        cv2.Canny(gray, 0.5 median, 1.5 median) whose area can pass the reference's `> h*w*0.0001` filter (fe_subject_region;
+        facet_amd.composition.subject_box picks the subject). With want_edges / want_thresholds the return is
+        (records, edges uint8 [n,h,w] | None, thresholds int32 [n,2] | None)."""
+        p, n, h, w, dev, keep = self._img_ptr(images)
+        edges = np.empty((n, h, w), np.uint8) if want_edges else None
+        thr = np.zeros((n, 2), np.int32) if want_thresholds else None
+        out = self._contour_call(lambda room, rec, cnt: self.lib.fe_subject_region(
+            self.h, p, n, h, w, dev, room, rec, cnt, thr.ctypes.data_as(C.c_void_p) if want_thresholds else None,
+            edges.ctypes.data_as(C.c_void_p) if want_edges else None), n, max_contours)
+        return (out, edges, thr) if (want_edges or want_thresholds) else out
 
     def phash(self, images, bgr=False, want_small=False, want_dct=False):
         """uint8 [n,h,w,3] (or device tuple), RGB or (bgr=True) BGR bytes -> uint64 [n]: imagehash.phash(pil_img) of every image as

@@ -11,14 +11,16 @@ isolation_bonus :264-269). What stays with the caller because it needs files, co
 hot path: path / EXIF columns, leading lines (CompositionAnalyzer.detect_leading_lines: Canny + probabilistic
 Hough; `detect_lines=True` computes them through `fe_leading_lines`, or pass `leading_lines=` scores in). `phash=True` adds the
 `phash` column (`str(imagehash.phash(pil_img))`, batch_processor.py:216) through `fe_phash`; off by default. `thumbnails=True` adds the
-`thumbnail` column (`generate_photo_thumbnail(pil_img, 640, 80)`, scorer.py:1611-1617: JPEG bytes) through `fe_thumbnail_jpeg`; off by default. With `policy=` (an `aggregate.AggregatePolicy` made from the
+`thumbnail` column (`generate_photo_thumbnail(pil_img, 640, 80)`, scorer.py:1611-1617: JPEG bytes) through `fe_thumbnail_jpeg`; off by default.
+`subject_region=True` makes power_point_score and the rule-based comp_score those of the multi-pass path (multi_pass.py:685-701:
+placement of the subject box `CompositionAnalyzer.detect_subject_region` finds in the image) through `fe_subject_region`; off by default. With `policy=` (an `aggregate.AggregatePolicy` made from the
 scoring configuration) the category and aggregate score (`Facet.calculate_aggregate_logic`) are computed for the whole batch
 as the last step, from the multi-pass metrics mapping (multi_pass.py:713-752); `metrics_for_aggregate()` returns the
 narrower mapping of the single-pass path (batch_processor.py:272-296).
 
 Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P + SAMP-Net), fe_image_stats (technical scans),
 fe_face_analyze + fe_roi_laplacian (through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
-fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`).
+fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_subject_region (with `subject_region=True`).
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -68,7 +70,11 @@ def detect_silhouette(histogram_silhouette, tags, face_count):
 class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
-                 aux_engine=None, phash=False, vlm_composition=None, thumbnails=False, thumbnail_size=640, thumbnail_quality=80):
+                 aux_engine=None, phash=False, vlm_composition=None, thumbnails=False, thumbnail_size=640, thumbnail_quality=80,
+                 subject_region=False):
+        # multi-pass placement (multi_pass.py:685-701): get_placement_data(None, w, h, config, img_cv) - the subject box detected from the
+        # resident BGR copy (fe_subject_region) is what power_point_score and the rule-based comp_score are computed from, faces or not
+        self.subject_region = subject_region
         # Qwen2-VL composition analyzer (facet_amd/vlm_composition.py; the 24gb profile): its SCORE overwrites comp_score, scorer.py:698-705
         self.vlm_composition = vlm_composition
         self.phash = phash      # add the 'phash' column (16 hex digits) from the resident BGR copy
@@ -129,17 +135,21 @@ class BatchScorer:
                 if self.thumbnails:
                     from .thumbnail import thumbnails
                     thumbs_ = thumbnails(eng, bgr_dev, self.thumbnail_size, self.thumbnail_quality, bgr=True)
-                return tech_, faces_, lines_, hashes_, thumbs_
+                subjects_ = None
+                if self.subject_region:
+                    from .composition import CompositionAnalyzer
+                    subjects_ = CompositionAnalyzer.detect_subject_region_batch(eng, bgr_dev)
+                return tech_, faces_, lines_, hashes_, thumbs_, subjects_
 
             if self._pool is not None:
                 fut = self._pool.submit(rest, self.aux_engine)      # fe_swap_rb_u8 has synchronised: the BGR copy is complete
                 try:
                     rec, mask = e.ensemble_score(rgb_dev)
                 finally:
-                    tech, faces, leading_lines, hashes, thumbs = fut.result()      # also on error: the worker must be done before the buffers go
+                    tech, faces, leading_lines, hashes, thumbs, subjects = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score(rgb_dev)
-                tech, faces, leading_lines, hashes, thumbs = rest(e)
+                tech, faces, leading_lines, hashes, thumbs, subjects = rest(e)
         finally:
             e.dev_free(d_rgb)
             if d_bgr is not None:
@@ -187,7 +197,7 @@ class BatchScorer:
                             'face_confidence': f.get('max_face_confidence', 0), 'isolation_bonus': round(isolation, 2), 'is_blink': blink,
                             'face_details': f.get('face_details', []), '_face_bbox': f.get('bbox'), '_isolation_bonus_raw': isolation})
             # rule-based placement of the (union) face box, then SAMP-Net's score on top when it ran (scorer.py:675-690)
-            comp = placement_data(res.get('_face_bbox'), w, h, self.power_weight, self.line_weight)
+            comp = placement_data(subjects[i] if subjects is not None else res.get('_face_bbox'), w, h, self.power_weight, self.line_weight)
             res['power_point_score'] = float(comp['power_point_score'])
             res.setdefault('comp_score', round(comp['score'], 2))
             res['is_silhouette'] = detect_silhouette(t['histogram'].get('is_silhouette', 0), res.get('tags'), res.get('face_count', 0))

@@ -1,13 +1,22 @@
 """Mirror of the reference's `CompositionAnalyzer` (analyzers/composition.py) over the engine.
 
-    CompositionAnalyzer.get_placement_data(bbox, w, h, config)        rule-of-thirds placement (:111-187; facet_amd/batch.py)
+    CompositionAnalyzer.get_placement_data(bbox, w, h, config, img_cv)  rule-of-thirds placement (:111-187; facet_amd/batch.py)
+    CompositionAnalyzer.detect_subject_region(img_cv)                 :16-93 - subject box of a photo without a face box
+    CompositionAnalyzer.detect_subject_region_batch(engine, bgr_batch) the same for a whole batch in one engine call
     CompositionAnalyzer.detect_leading_lines(img_cv, cache=None)      :191-261 - one image
     CompositionAnalyzer.detect_leading_lines_batch(engine, bgr_batch) the same for a whole batch in one engine call
     CompositionAnalyzer.integrate_leading_lines(base, lines, faces)   :262-283
 
 The reference runs cv2.GaussianBlur + cv2.Canny + cv2.HoughLinesP per image; here `fe_leading_lines` does the pixel scans on
 the GPU and the sequential Hough stage on host threads (include/facet_engine.h). Scoring of the segments follows :231-256 with
-the same numpy types (int32 coordinates, float64 arithmetic, numpy's round)."""
+the same numpy types (int32 coordinates, float64 arithmetic, numpy's round).
+
+The subject region (median-threshold cv2.Canny + cv2.findContours(RETR_EXTERNAL) + contourArea / moments per image in the reference)
+comes from `fe_subject_region`, which keeps every stage on the GPU and returns a few integer records per image; `subject_box` makes the
+reference's choice among them in float64. The reference's second strategy (cv2.saliency spectral residual, :77-91) is not built: the
+opencv-python wheel the reference installs has no `saliency` module, so that branch ends in its `except AttributeError` and the
+function returns None - as this mirror does when strategy 1 finds nothing. Parity of the contour stage with cv2 itself is unpinned
+(cv2 is not available offline); the selection arithmetic is pinned by tests/golden/subject_golden.json."""
 import numpy as np
 
 from . import default_engine
@@ -30,9 +39,55 @@ def score_lines(lines, h, w):
     return {'leading_lines_score': round(score, 2), 'line_count': len(lines)}
 
 
+def subject_box(records, h, w):
+    """The reference's choice among the contours (:40-75). records: int [k,8] = start_index, a00, a10, a01, x_min, y_min, x_max, y_max in
+    cv2.findContours' order (Engine.subject_contours). -> [x1, y1, x2, y2] or None."""
+    min_area = (h * w) * 0.0001
+    thirds_x = [w / 3, 2 * w / 3]
+    thirds_y = [h / 3, 2 * h / 3]
+    best, best_score = None, 0
+    for start, a00, a10, a01, x_min, y_min, x_max, y_max in np.asarray(records, dtype=np.int64).reshape(-1, 8).tolist():
+        area = abs(a00) * 0.5                                   # cv2.contourArea
+        if not area > min_area:
+            continue
+        sgn = -1 if a00 < 0 else 1                              # cv2.moments: m00 = a00 / 2, m10 = a10 / 6, m01 = a01 / 6, sign of a00
+        m00, m10, m01 = sgn * a00 / 2, sgn * a10 / 6, sgn * a01 / 6
+        if m00 == 0:
+            continue
+        cx = m10 / m00
+        cy = m01 / m00
+        area_score = area / (h * w)
+        dist_x = min(abs(cx - t) for t in thirds_x) / w
+        dist_y = min(abs(cy - t) for t in thirds_y) / h
+        score = area_score * (1 + max(0, 1 - (dist_x + dist_y)))
+        if score > best_score:
+            best_score, best = score, [x_min, y_min, x_max + 1, y_max + 1]
+    return best
+
+
 class CompositionAnalyzer:
     @staticmethod
-    def get_placement_data(bbox, img_w, img_h, config=None):
+    def detect_subject_region_batch(engine, bgr_batch):
+        """bgr_batch: uint8 [n,h,w,3] or a resident (device_ptr, n, h, w) -> one [x1, y1, x2, y2] or None per image."""
+        if isinstance(bgr_batch, tuple):
+            h, w = bgr_batch[2], bgr_batch[3]
+        else:
+            bgr_batch = np.ascontiguousarray(bgr_batch, dtype=np.uint8)
+            h, w = bgr_batch.shape[1:3]
+        return [subject_box(r, h, w) for r in engine.subject_contours(bgr_batch)]
+
+    @staticmethod
+    def detect_subject_region(img_cv, engine=None):
+        """Strategy 1 of the reference (:32-75); None where the reference's saliency fallback is unavailable too (module docstring)."""
+        if img_cv is None:
+            return None
+        engine = engine or default_engine()
+        return CompositionAnalyzer.detect_subject_region_batch(engine, np.asarray(img_cv)[None])[0]
+
+    @staticmethod
+    def get_placement_data(bbox, img_w, img_h, config=None, img_cv=None, engine=None):
+        if bbox is None and img_cv is not None:      # edge-based fallback for photos without faces (:125-126)
+            bbox = CompositionAnalyzer.detect_subject_region(img_cv, engine)
         wts = config.get_composition_weights() if config is not None else {}
         return placement_data(bbox, img_w, img_h, wts.get('power_point_weight', 2.0), wts.get('line_weight', 1.0))
 

@@ -2480,21 +2480,133 @@ int fe_cv_resize_linear_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w,
   FE_API_END(ctx)
 }
 
+}  // extern "C"
+
+// the two division tables of cv2's 8-bit HSV conversion, made once per context (fe_image_stats, fe_subject_region)
+static void ensure_hsv_tables(fe_ctx* ctx) {
+  if (ctx->hsv_sdiv) return;
+  std::vector<int> sd, hd;
+  cv_hsv_tables(sd, hd);
+  FE_HIP(hipMalloc((void**)&ctx->hsv_sdiv, 256 * sizeof(int)));
+  ctx->misc_allocs.push_back(ctx->hsv_sdiv);
+  FE_HIP(hipMalloc((void**)&ctx->hsv_hdiv, 256 * sizeof(int)));
+  ctx->misc_allocs.push_back(ctx->hsv_hdiv);
+  FE_HIP(hipMemcpy(ctx->hsv_sdiv, sd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
+  FE_HIP(hipMemcpy(ctx->hsv_hdiv, hd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
+}
+
+// Brings the contour records of one micro-batch to the host: counts [nb] exact; records [nb][max_contours][8], per image the first
+// max_contours in descending start_index order. The device list holds every qualifying contour (its capacity is the largest number
+// of components an image can have), in the order the walks finished, so the order is made here.
+static void collect_contours(fe_ctx* ctx, const ContourScratch& sc, int nb, int h, int w, int max_contours, long long* records, int* counts) {
+  Ctx& C = ctx->c;
+  const int cap = contour_work_cap(h, w);
+  std::vector<int> found(nb), listed(nb);
+  int err = 0;
+  FE_HIP(hipMemcpyAsync(found.data(), sc.rec_count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipMemcpyAsync(listed.data(), sc.work_count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipMemcpyAsync(&err, sc.error, sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_CHECK(!(err & 1), "contours: a border walk did not close within 8 * pixels + 8 steps");
+  FE_CHECK(!(err & 2), "contours: more component roots than an image can hold");
+  std::vector<std::vector<long long>> got(nb);
+  for (int i = 0; i < nb; ++i) {
+    FE_CHECK(found[i] >= 0 && found[i] <= listed[i] && listed[i] <= cap, "contours: inconsistent counts (%d of %d, room %d)", found[i], listed[i], cap);
+    counts[i] = found[i];
+  }
+  for (int i = 0; i < nb; ++i) {      // nothing below throws while a copy into `got` is in flight
+    if (!found[i]) continue;
+    got[i].resize((size_t)found[i] * FE_CONTOUR_RECORD);
+    FE_HIP(hipMemcpyAsync(got[i].data(), sc.recs + (size_t)i * cap * FE_CONTOUR_RECORD, got[i].size() * sizeof(long long), hipMemcpyDeviceToHost,
+                          C.stream));
+  }
+  FE_HIP(hipStreamSynchronize(C.stream));
+  struct Rec { long long f[FE_CONTOUR_RECORD]; };
+  for (int i = 0; i < nb; ++i) {
+    if (!found[i]) continue;
+    Rec* r = reinterpret_cast<Rec*>(got[i].data());
+    std::sort(r, r + found[i], [](const Rec& a, const Rec& b) { return a.f[0] > b.f[0]; });
+    const size_t keep = (size_t)std::min(found[i], max_contours);
+    memcpy(records + (size_t)i * max_contours * FE_CONTOUR_RECORD, r, keep * sizeof(Rec));
+  }
+}
+
+// images per micro-batch such that `per_image` bytes each fit the arena with room to spare
+static int contour_microbatch(fe_ctx* ctx, int n, size_t per_image) {
+  const size_t room = ctx->c.arena.capacity() / 8 * 7;
+  FE_CHECK(per_image + 4096 <= room, "contours: one image needs %zu bytes of workspace, the arena holds %zu", per_image, ctx->c.arena.capacity());
+  return (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)64, room / (per_image + 4096)}));
+}
+
+extern "C" {
+
+/* External contours of binary images: labelling, RETR_EXTERNAL test and border sums on the device (kernels_contours.hip) */
+int fe_external_contours(fe_ctx* ctx, const uint8_t* binary, int n, int h, int w, int on_device, long long min_twice_area, int max_contours,
+                         long long* records, int* counts) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(binary && records && counts && n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 30) && max_contours > 0 && min_twice_area >= 0,
+           "bad arguments");
+  const size_t npx = (size_t)h * w;
+  const int mb = contour_microbatch(ctx, n, contour_scratch_bytes(1, h, w));
+  ImageStager st(ctx, binary, n, npx, mb, on_device);
+  for (int k = 0; k < st.chunks(); ++k) {
+    const int i0 = k * mb, nb = st.count(k);
+    C.arena.reset();
+    const uint8_t* d_in = st.get(k);
+    ContourScratch sc;
+    contour_scratch_carve(sc, C.arena.alloc(contour_scratch_bytes(nb, h, w)), nb, h, w);
+    launch_external_contours(d_in, nb, h, w, 0, min_twice_area, sc, C.stream);
+    st.done(k);
+    collect_contours(ctx, sc, nb, h, w, max_contours, records + (size_t)i0 * max_contours * FE_CONTOUR_RECORD, counts + i0);
+  }
+  FE_API_END(ctx)
+}
+
+/* Subject region (reference analyzers/composition.py:16-93): median thresholds, Canny, hysteresis, external contours - all on the device */
+int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int max_contours, long long* records, int* counts,
+                      int* thresholds, uint8_t* edges_out) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(bgr && records && counts && n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 30) && max_contours > 0, "bad arguments");
+  ensure_hsv_tables(ctx);
+  const size_t npx = (size_t)h * w, per = npx * 3;
+  const long long min_twice_area = ((long long)npx + 4999) / 5000;      // smallest a with a * 5000 >= h * w  (area > h * w * 0.0001, not strict)
+  const size_t per_image = contour_scratch_bytes(1, h, w) + 8 * npx + stats_accum_bytes(1) + FE_STATS_COUNT * sizeof(double) + 2048;
+  const int mb = contour_microbatch(ctx, n, per_image);
+  ImageStager st(ctx, bgr, n, per, mb, on_device);
+  for (int k = 0; k < st.chunks(); ++k) {
+    const int i0 = k * mb, nb = st.count(k);
+    C.arena.reset();
+    const uint8_t* d_in = st.get(k);
+    uint8_t* d_gray = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+    void* d_acc = C.arena.alloc(stats_accum_bytes(nb));
+    double* d_stats = (double*)C.arena.alloc((size_t)nb * FE_STATS_COUNT * sizeof(double));
+    int* d_thr = (int*)C.arena.alloc((size_t)nb * 2 * sizeof(int));
+    void* d_grad = C.arena.alloc((size_t)nb * npx * 4);
+    void* d_mag = C.arena.alloc((size_t)nb * npx * 2);
+    uint8_t* d_map = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+    ContourScratch sc;
+    contour_scratch_carve(sc, C.arena.alloc(contour_scratch_bytes(nb, h, w)), nb, h, w);
+    // gray and its histogram come from the statistics pass, so the conversion exists once
+    launch_image_stats(d_in, nb, h, w, d_gray, nullptr, ctx->hsv_sdiv, ctx->hsv_hdiv, d_acc, d_stats, C.stream);
+    st.done(k);
+    launch_median_thresholds(d_stats, nb, (long long)npx, d_thr, C.stream);
+    launch_canny_map_gray(d_gray, nb, h, w, d_thr, d_grad, d_mag, d_map, C.stream);
+    launch_external_contours(d_map, nb, h, w, 1, min_twice_area, sc, C.stream);
+    if (thresholds) FE_HIP(hipMemcpyAsync(thresholds + (size_t)i0 * 2, d_thr, (size_t)nb * 2 * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+    if (edges_out) FE_HIP(hipMemcpyAsync(edges_out + (size_t)i0 * npx, sc.edge, (size_t)nb * npx, hipMemcpyDeviceToHost, C.stream));
+    collect_contours(ctx, sc, nb, h, w, max_contours, records + (size_t)i0 * max_contours * FE_CONTOUR_RECORD, counts + i0);
+  }
+  FE_API_END(ctx)
+}
+
 /* Per-image technical statistics of a BGR batch (reference analyzers/image_cache.py:28-33 + analyzers/technical.py) */
 int fe_image_stats(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, double* stats, uint8_t* gray_out, uint8_t* hsv_out) {
   FE_API_BEGIN(ctx)
   Ctx& C = ctx->c;
   FE_CHECK(bgr && stats && n > 0 && h > 0 && w > 0, "bad arguments");
-  if (!ctx->hsv_sdiv) {
-    std::vector<int> sd, hd;
-    cv_hsv_tables(sd, hd);
-    FE_HIP(hipMalloc((void**)&ctx->hsv_sdiv, 256 * sizeof(int)));
-    ctx->misc_allocs.push_back(ctx->hsv_sdiv);
-    FE_HIP(hipMalloc((void**)&ctx->hsv_hdiv, 256 * sizeof(int)));
-    ctx->misc_allocs.push_back(ctx->hsv_hdiv);
-    FE_HIP(hipMemcpy(ctx->hsv_sdiv, sd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
-    FE_HIP(hipMemcpy(ctx->hsv_hdiv, hd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
-  }
+  ensure_hsv_tables(ctx);
   const size_t per = (size_t)h * w * 3, npx = (size_t)h * w;
   // two blocks per image in pass 1: large chunks keep all 256 CUs busy (the footprint is only ~2-5 bytes per pixel)
   const int mb = std::max(1, std::max(ctx->microbatch, 256));

@@ -465,5 +465,33 @@ void launch_roi_laplacian(const uint8_t* bgr, int h, int w, const int* img_of, c
 // kernels_lines.hip: Gaussian 5x5 + Canny non-maximum-suppression map on the GPU (host stage: lines_host.h)
 void launch_canny_map(const uint8_t* d_bgr, int n, int h, int w, int low, int high, uint8_t* d_blur, void* d_grad, void* d_mag, uint8_t* d_map,
                       hipStream_t s);
+void launch_canny_map_gray(const uint8_t* d_gray, int n, int h, int w, const int* d_thr, void* d_grad, void* d_mag, uint8_t* d_map, hipStream_t s);
+// kernels_contours.hip: connected components, the RETR_EXTERNAL test and the border sums of external contours
+struct ContourScratch {      // device buffers of one micro-batch of nb images, npx = h * w pixels each
+  int* lab_fg;               // [nb][npx] root (smallest pixel index) of the pixel's 8-connected component, -1 outside the set
+  int* lab_bg;               // [nb][npx] the same for the 4-connected background of the final edge image
+  int* cnt;                  // [nb][npx] at a root: pixel count
+  int* strong;               // [nb][npx] at a root: owns a pixel above the upper threshold
+  int* xmin;                 // [nb][npx] at a root: bounding box (y_min is the root's own row)
+  int* xmax;
+  int* ymax;
+  uint8_t* outer;            // [nb][npx] at a background root: owns a pixel on the image frame
+  uint8_t* edge;             // [nb][npx] final edge image (0 / 255), subject mode only
+  int* work;                 // [nb][work_cap] roots whose border is walked
+  int* work_count;           // [nb]
+  long long* recs;           // [nb][work_cap][8]
+  int* rec_count;            // [nb] qualifying contours (those beyond work_cap are counted, not stored)
+  int* error;                // [1] set when a walk ran into its step bound or a list into its capacity
+};
+constexpr int FE_CONTOUR_RECORD = 8;
+int contour_work_cap(int h, int w);
+size_t contour_scratch_bytes(int nb, int h, int w);
+void contour_scratch_carve(ContourScratch& sc, void* base, int nb, int h, int w);
+// thresholds from the gray histograms of fe_image_stats records: d_stats [n][FE_STATS_COUNT] doubles -> d_thr [n][2] = lower, upper
+void launch_median_thresholds(const double* d_stats, int n, long long npx, int* d_thr, hipStream_t s);
+// candidates = 1: d_img is a Canny map (2 strong, 0 weak, 1 none), the foreground is every component that owns a 2 (hysteresis), and
+// sc.edge receives it; candidates = 0: d_img is a binary image (nonzero = foreground) that is used as it is.
+void launch_external_contours(const uint8_t* d_img, int nb, int h, int w, int candidates, long long min_twice_area, ContourScratch& sc,
+                              hipStream_t s);
 
 }  // namespace fe

@@ -65,10 +65,13 @@ __global__ void lines_sobel_kernel(const uint8_t* __restrict__ blur, int h, int 
   mag[base + (size_t)y * w + x] = (unsigned short)(abs(dx) + abs(dy));
 }
 
+// PER_IMAGE: the two thresholds of image blockIdx.z are read from thr[2 * blockIdx.z] (lower, upper) instead of low / high
+template <bool PER_IMAGE>
 __global__ void lines_nms_kernel(const short2* __restrict__ grad, const unsigned short* __restrict__ mag, int h, int w, int low, int high,
-                                 uint8_t* __restrict__ map) {
+                                 const int* __restrict__ thr, uint8_t* __restrict__ map) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= w || y >= h) return;
+  if (PER_IMAGE) { low = thr[2 * blockIdx.z]; high = thr[2 * blockIdx.z + 1]; }
   const size_t base = (size_t)blockIdx.z * h * w;
   const unsigned short* mg = mag + base;
   auto M = [&](int yy, int xx) -> int { return (xx < 0 || xx >= w || yy < 0 || yy >= h) ? 0 : (int)mg[(size_t)yy * w + xx]; };   // zero outside
@@ -103,7 +106,19 @@ void launch_canny_map(const uint8_t* d_bgr, int n, int h, int w, int low, int hi
   const dim3 blk(64, 4), grid((w + 63) / 64, (h + 3) / 4, n);
   hipLaunchKernelGGL(lines_sobel_kernel, grid, blk, 0, s, d_blur, h, w, (short2*)d_grad, (unsigned short*)d_mag);
   FE_HIP(hipGetLastError());
-  hipLaunchKernelGGL(lines_nms_kernel, grid, blk, 0, s, (const short2*)d_grad, (const unsigned short*)d_mag, h, w, low, high, d_map);
+  hipLaunchKernelGGL(lines_nms_kernel<false>, grid, blk, 0, s, (const short2*)d_grad, (const unsigned short*)d_mag, h, w, low, high, (const int*)nullptr,
+                     d_map);
+  FE_HIP(hipGetLastError());
+}
+
+// Canny map of an image that is gray already and is NOT blurred (cv2.Canny(gray, lower, upper)), with one pair of thresholds per image in
+// device memory: d_thr [n][2] = lower, upper. Same Sobel, same suppression as above.
+void launch_canny_map_gray(const uint8_t* d_gray, int n, int h, int w, const int* d_thr, void* d_grad, void* d_mag, uint8_t* d_map, hipStream_t s) {
+  FE_CHECK(n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 31) && n <= 65535, "canny: bad shape");
+  const dim3 blk(64, 4), grid((w + 63) / 64, (h + 3) / 4, n);
+  hipLaunchKernelGGL(lines_sobel_kernel, grid, blk, 0, s, d_gray, h, w, (short2*)d_grad, (unsigned short*)d_mag);
+  FE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(lines_nms_kernel<true>, grid, blk, 0, s, (const short2*)d_grad, (const unsigned short*)d_mag, h, w, 0, 0, d_thr, d_map);
   FE_HIP(hipGetLastError());
 }
 

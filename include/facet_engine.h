@@ -496,6 +496,40 @@ int fe_swap_rb_u8(fe_ctx* ctx, const uint8_t* src, int on_device, size_t pixels,
 int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int canny_low, int canny_high, int threshold,
                      int min_line_length, int max_line_gap, int max_lines, int* lines, int* counts, uint8_t* edges_out);
 
+/* External contours of binary images, as cv2.findContours(img, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) followed by cv2.contourArea /
+ * cv2.moments / cv2.boundingRect of every contour would give them [DEP-KNOWLEDGE: OpenCV contours.cpp, moments.cpp; parity with
+ * cv2 unpinned]. binary [n][h][w] uint8 on the host (on_device = 0) or the device, nonzero = foreground; the image is treated as
+ * surrounded by background. Components are 8-connected. A component is external when it does not lie inside a hole of another
+ * component, i.e. when the 4-connected background region left of its first pixel (raster order) reaches the image frame.
+ * One record of FE_CONTOUR_FIELDS long longs per external contour: [0] start_index = y * w + x of the component's first pixel,
+ * [1] a00, [2] a10, [3] a01 = the Green sums over the closed outer-border polygon through the pixel centres (consecutive border
+ * points p, q, d = p.x q.y - q.x p.y: a00 += d, a10 += d (p.x + q.x), a01 += d (p.y + q.y)), so contourArea = |a00| / 2,
+ * m00 = a00 / 2, m10 = a10 / 6, m01 = a01 / 6, the three moments negated when a00 < 0; [4..7] x_min, y_min, x_max, y_max
+ * (inclusive; boundingRect = x_min, y_min, x_max - x_min + 1, y_max - y_min + 1). All fields are exact integers; CHAIN_APPROX_SIMPLE
+ * only drops collinear points, which changes none of them.
+ * A contour is reported when |a00| >= min_twice_area. records [n][max_contours][FE_CONTOUR_FIELDS], per image in descending
+ * start_index order: findContours returns the contour it found last first [DEP-KNOWLEDGE]. counts [n] = contours reported per image
+ * (may exceed max_contours: only the first max_contours are stored - call again with more room). A border walk that does not close
+ * within 8 * (pixels of the component) + 8 steps makes the call fail (fe_last_error); it cannot for a well-formed labelling. */
+#define FE_CONTOUR_FIELDS 8
+int fe_external_contours(fe_ctx* ctx, const uint8_t* binary, int n, int h, int w, int on_device, long long min_twice_area, int max_contours,
+                         long long* records, int* counts);
+
+/* Subject region for photos without a face box: strategy 1 of the reference's CompositionAnalyzer.detect_subject_region
+ * (analyzers/composition.py:16-75), which runs cv2.cvtColor(BGR2GRAY), np.median, cv2.Canny(gray, int(max(0, 0.5 median)),
+ * int(min(255, 1.5 median))) and cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) per image on the CPU. Here every stage runs on
+ * the device: gray and its histogram (the fe_image_stats pass), the median as twice its value m2 (an even pixel count takes the mean of
+ * the two middle values) with lower = m2 / 4 and upper = min(255, 3 m2 / 4), the Canny front end of fe_leading_lines on the
+ * un-blurred gray (3x3 Sobel, BORDER_REPLICATE, L1 magnitude, thresholds low < m, high < m) [DEP-KNOWLEDGE], hysteresis as a
+ * connected-component labelling of the candidate map (a component stays when it owns a pixel above the upper threshold), and the
+ * contours of fe_external_contours over the resulting edge image with min_twice_area = the smallest integer a with
+ * a * 5000 >= h * w - a superset of the reference's `contourArea > h * w * 0.0001`, which the caller applies in floating point
+ * (facet_amd/composition.py: subject_box). records / counts as in fe_external_contours; thresholds [n][2] (nullable) receives lower,
+ * upper; edges_out [n][h][w] (nullable, host) the Canny edge image (0 / 255). Strategy 2 of the reference (cv2.saliency) is not built:
+ * the module is absent from the opencv-python wheel the reference installs, so its fallback returns None there too. */
+int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int max_contours, long long* records, int* counts,
+                      int* thresholds, uint8_t* edges_out);
+
 /* Perceptual hash: `imagehash.phash(pil_img)` with its defaults (hash_size 8, highfreq_factor 4), which the reference stores as
  * str(...) in the `phash` column for every image (processing/batch_processor.py:216, multi_pass.py:449, scorer.py:972):
  * image.convert('L') ((R*19595 + G*38470 + B*7471 + 0x8000) >> 16), .resize((32, 32), LANCZOS) (PIL's two-pass 22-bit fixed-point
