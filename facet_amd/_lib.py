@@ -175,6 +175,9 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_jpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fe_jpeg_probe_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "fe_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
     "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -189,6 +192,7 @@ SIGNATURES = {
 FE_CONTOUR_FIELDS = 8      # long longs per contour record
 FE_SIM_FUSED, FE_SIM_COSINE = 0, 1
 FE_SIM_K_MAX = 32
+FE_JPEG_PROGRESSIVE = 1    # flag of fe_jpeg_probe_ex / fe_jpeg_decode_ex (and the status of a progressive file without it)
 FE_SIM_NO_DATE = -(1 << 63)
 
 
@@ -1208,22 +1212,32 @@ class Engine:
         return self._jpeg_rows(out, lengths)
 
     @staticmethod
-    def jpeg_probe(blob):
+    def jpeg_probe(blob, progressive=False):
         """The markers of one JPEG file (bytes) -> dict(width, height, components, hsamp, vsamp, restart_interval, orientation, status);
-        status 0: jpeg_decode takes the file, > 0: a kind it leaves to Pillow, < 0: corrupt (JPEG_STATUS names them). Host only."""
+        status 0: jpeg_decode takes the file, > 0: a kind it leaves to Pillow, < 0: corrupt (JPEG_STATUS names them). Host only.
+        progressive=True (fe_jpeg_probe_ex): the answer for jpeg_decode(..., progressive=True), where a complete progressive file is 0
+        too; the dict gains `progressive` (the frame is SOF2) and `scans`."""
         blob = bytes(blob)
+        if progressive:
+            info = (C.c_int32 * 10)()
+            rc = load_library().fe_jpeg_probe_ex(blob, len(blob), FE_JPEG_PROGRESSIVE, info)
+            if rc != 0:
+                raise EngineError("fe_jpeg_probe_ex failed")
+            return dict(zip(("width", "height", "components", "hsamp", "vsamp", "restart_interval", "orientation", "status", "progressive", "scans"),
+                            (int(v) for v in info)))
         info = (C.c_int32 * 8)()
         rc = load_library().fe_jpeg_probe(blob, len(blob), info)
         if rc != 0:
             raise EngineError("fe_jpeg_probe failed")
         return dict(zip(("width", "height", "components", "hsamp", "vsamp", "restart_interval", "orientation", "status"), (int(v) for v in info)))
 
-    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False):
+    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False, progressive=False):
         """JPEG files (a list of bytes) whose decoded size is h x w -> (pixels, status). pixels: uint8 [n,h,w,3], what Pillow's
         `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives (apply_orientation=False: without the transpose; bgr: B,G,R bytes),
         a host array, or with device=True a (device_ptr, n, h, w) tuple whose buffer the caller releases with dev_free (device=<pointer>
         decodes into the caller's own buffer). status: int32 [n], 0 where the image was decoded; the slot of any other image is left as it
-        was (zeros in a host array allocated here, undefined in a device buffer allocated here)."""
+        was (zeros in a host array allocated here, undefined in a device buffer allocated here). progressive=True (fe_jpeg_decode_ex):
+        progressive files that jpeg_probe(blob, progressive=True) gives status 0 are decoded too, in the same call as baseline ones."""
         blobs = [bytes(b) for b in blobs]
         n = len(blobs)
         if n == 0:
@@ -1231,16 +1245,20 @@ class Engine:
         ptrs = (C.c_char_p * n)(*blobs)
         lens = (C.c_size_t * n)(*[len(b) for b in blobs])
         status = np.zeros(n, np.int32)
+        def call(on_device, dst):
+            head = (self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, on_device)
+            if progressive:
+                self._ck(self.lib.fe_jpeg_decode_ex(*head, FE_JPEG_PROGRESSIVE, dst, status.ctypes.data_as(C.c_void_p)))
+            else:
+                self._ck(self.lib.fe_jpeg_decode(*head, dst, status.ctypes.data_as(C.c_void_p)))
         if device is False or device is None:
             out = np.zeros((n, h, w, 3), np.uint8)
-            self._ck(self.lib.fe_jpeg_decode(self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, 0,
-                                             out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+            call(0, out.ctypes.data_as(C.c_void_p))
             return out, status
         own = device is True
         d = self.dev_alloc(n * h * w * 3) if own else device
         try:
-            self._ck(self.lib.fe_jpeg_decode(self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, 1,
-                                             d, status.ctypes.data_as(C.c_void_p)))
+            call(1, d)
         except Exception:
             if own:
                 self.dev_free(d)

@@ -1368,17 +1368,27 @@ int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int 
 }
 
 /* ---- JPEG decode: what `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives, from the file's bytes ---- */
-int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info) {
-  if (!info) return FE_ERR_INVALID;
+int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info) {
+  if (!info || (flags & ~FE_JPEG_PROGRESSIVE)) return FE_ERR_INVALID;
   try {
-    int32_t v[8];
+    int32_t v[10];
     static const uint8_t none[1] = {0};
-    jpeg_probe(data ? data : none, data ? len : 0, v);
+    jpeg_probe(data ? data : none, data ? len : 0, flags, v);
     info->width = v[0]; info->height = v[1]; info->components = v[2]; info->hsamp = v[3]; info->vsamp = v[4];
-    info->restart_interval = v[5]; info->orientation = v[6]; info->status = v[7];
+    info->restart_interval = v[5]; info->orientation = v[6]; info->status = v[7]; info->progressive = v[8]; info->scans = v[9];
   } catch (const std::exception&) {
     return FE_ERR_RUNTIME;
   }
+  return FE_OK;
+}
+
+int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info) {
+  if (!info) return FE_ERR_INVALID;
+  fe_jpeg_info_ex x;
+  const int rc = fe_jpeg_probe_ex(data, len, 0, &x);
+  if (rc != FE_OK) return rc;
+  info->width = x.width; info->height = x.height; info->components = x.components; info->hsamp = x.hsamp; info->vsamp = x.vsamp;
+  info->restart_interval = x.restart_interval; info->orientation = x.orientation; info->status = x.status;
   return FE_OK;
 }
 
@@ -1386,7 +1396,15 @@ int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, i
                    uint8_t* dst, int32_t* status) {
   FE_API_BEGIN(ctx)
   FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0, "bad arguments");
-  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, dst, status);
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, 0, dst, status);
+  FE_API_END(ctx)
+}
+
+int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                      int flags, uint8_t* dst, int32_t* status) {
+  FE_API_BEGIN(ctx)
+  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~FE_JPEG_PROGRESSIVE), "bad arguments");
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, flags, dst, status);
   FE_API_END(ctx)
 }
 

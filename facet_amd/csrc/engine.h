@@ -216,8 +216,8 @@ size_t jpeg_scratch_bytes(int h, int w);      // arena bytes per image of launch
 void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, int quality, uint8_t* d_out, size_t cap, int32_t* d_lengths);
 
 // ---- JPEG decode: file bytes -> resident uint8 batch, Pillow's pixels (kernels_jpeg_dec.hip, jpeg_dec_core.h) ----
-void jpeg_probe(const uint8_t* data, size_t len, int32_t out[8]);      // the fields of fe_jpeg_info, host only
-void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]);      // the fields of fe_jpeg_info_ex, host only
+void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device, int flags,
                        uint8_t* dst, int32_t* status);
 
 // ---- perceptual hash + all-pairs Hamming search (kernels_phash.hip) ------------------------------------

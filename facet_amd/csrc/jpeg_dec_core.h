@@ -1,5 +1,5 @@
-// Baseline JPEG decoding arithmetic shared by the kernels of kernels_jpeg_dec.hip and by host code: the inverse of jpeg_core.h.
-// libjpeg's Huffman decoder (jdhuff.c), dequantiser + integer slow IDCT (jidctint.c), fancy upsampling (jdsample.c) and YCbCr -> RGB
+// JPEG decoding arithmetic shared by the kernels of kernels_jpeg_dec.hip and by host code: the inverse of jpeg_core.h.
+// libjpeg's Huffman decoders (jdhuff.c; jdphuff.c for the scans of a progressive file), dequantiser + integer slow IDCT (jidctint.c), fancy upsampling (jdsample.c) and YCbCr -> RGB
 // (jdcolor.c), restated per segment / block / pixel. Integer end to end, so the same functions give the same pixels on the device and on
 // the host, and those are the pixels of Pillow's `Image.open(f).convert('RGB')`.
 //
@@ -7,6 +7,8 @@
 // serially into int16 coefficient blocks in natural order, stored per component in that component's block grid padded to whole MCUs
 // (DecGeom); every block is dequantised and transformed into its component's plane; a pixel takes its luma sample, its two chroma samples
 // through the triangle filters and the colour conversion, and lands at the address its EXIF orientation gives it.
+// A progressive file is a sequence of scans over that same coefficient buffer, each cut into segments of its own; once the last scan has
+// run the buffer holds what a baseline file's single scan would have left, and everything behind the entropy stage is shared.
 #pragma once
 #include <string.h>
 
@@ -205,6 +207,159 @@ FE_JHD int32_t wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint
 FE_JHD int32_t wshl(int32_t a, int n) { return (int32_t)((uint32_t)a << n); }
 FE_JHD int32_t wdescale(int32_t x, int n) { return wadd(x, 1 << (n - 1)) >> n; }
 
+// ---- progressive scans (jdphuff.c) ----------------------------------------------------------------------------------------------------
+// What belongs to one scan. A progressive file brings a fresh DHT in front of every Huffman scan and may change DRI between scans, so the
+// tables, the restart interval and the segments are the scan's; quantisation tables, geometry and orientation stay the image's.
+constexpr int MAX_SCANS = 32;          // libjpeg's default scripts have 10 (colour) and 6 (gray)
+constexpr int FLAG_PROGRESSIVE = 1;    // parse(): take SOF2 files
+
+struct ScanDesc {
+  uint32_t seg_first, nseg;            // this scan's rows of the segment offset arrays
+  uint32_t tab_first;                  // first of its Huffman tables in the table pool: ntab of them
+  int32_t ri;                          // restart interval in units of this scan, 0: none
+  uint8_t ns, comp[3];                 // components, ascending frame indices
+  uint8_t tab[3];                      // table of component j, counted from tab_first (DC first); an AC scan has table 0
+  uint8_t ntab, ss, se, ah, al;
+};
+
+// The units ("MCUs") a scan walks: whole MCUs when it interleaves components, else single blocks over the component's real extent,
+// ceil(ceil(w * hs_c / hs_max) / 8) by the same in h, which is not the MCU-padded grid
+FE_JHD void scan_extent(const DecGeom& g, const ScanDesc& s, int& uw, int& uh) {
+  if (s.ns > 1) { uw = g.mw; uh = g.mh; return; }
+  const bool luma = s.comp[0] == 0;    // a grayscale image has cw = w, ch = h
+  uw = ((luma ? g.w : g.cw) + 7) >> 3; uh = ((luma ? g.h : g.ch) + 7) >> 3;
+}
+
+FE_JHD uint32_t take_bits(BitReader& br, int n) {      // 0 <= n <= 16 <= nbits
+  if (n == 0) return 0;
+  const uint32_t v = br.peek(n);
+  br.skip(n);
+  return v;
+}
+FE_JHD uint32_t take_bit(BitReader& br) {
+  if (br.nbits < 16) br.fill();
+  return take_bits(br, 1);
+}
+
+// decode_mcu_DC_first for one block
+FE_JHD int prog_dc_first(BitReader& br, const HuffDec& t, int al, int& pred, int16_t* blk) {
+  br.fill();
+  int s = decode_symbol(br, t);
+  if (s < 0 || s > 15) return ST_BAD_HUFFMAN;
+  if (s) s = huff_extend((int)take_bits(br, s), s);
+  pred = wadd(pred, s);
+  blk[0] = (int16_t)wshl(pred, al);
+  return 0;
+}
+
+// decode_mcu_AC_first for one block; eobrun: blocks still to be skipped, carried from block to block of a segment
+FE_JHD int prog_ac_first(BitReader& br, const HuffDec& t, int ss, int se, int al, uint32_t& eobrun, int16_t* blk, const uint8_t* nat) {
+  if (eobrun > 0) { --eobrun; return 0; }
+  for (int k = ss; k <= se; ++k) {
+    br.fill();
+    int s = decode_symbol(br, t);
+    if (s < 0) return ST_BAD_HUFFMAN;
+    const int r = s >> 4;
+    s &= 15;
+    if (s) {
+      k += r;
+      const int v = (int)take_bits(br, s);
+      if (k > se) return ST_BAD_HUFFMAN;             // a run past the band
+      blk[nat[k & 63]] = (int16_t)wshl(huff_extend(v, s), al);
+    } else if (r == 15) {
+      k += 15;                                       // ZRL
+    } else {
+      eobrun = (1u << r) + take_bits(br, r) - 1u;    // this block ends here, and so do the next eobrun
+      break;
+    }
+  }
+  return 0;
+}
+
+// one correction bit for a coefficient that is already non-zero
+FE_JHD void prog_correct(BitReader& br, int16_t* c, int p1) {
+  if (take_bit(br) && (*c & p1) == 0) *c = (int16_t)(*c >= 0 ? *c + p1 : *c - p1);
+}
+
+// decode_mcu_AC_refine for one block
+FE_JHD int prog_ac_refine(BitReader& br, const HuffDec& t, int ss, int se, int al, uint32_t& eobrun, int16_t* blk, const uint8_t* nat) {
+  const int p1 = 1 << al;
+  int k = ss;
+  if (eobrun == 0) {
+    for (; k <= se; ++k) {
+      br.fill();
+      int s = decode_symbol(br, t);
+      if (s < 0) return ST_BAD_HUFFMAN;
+      int r = s >> 4;
+      s &= 15;
+      int val = 0;
+      if (s) {
+        if (s != 1) return ST_BAD_HUFFMAN;           // a new coefficient has magnitude 1 << al
+        val = take_bits(br, 1) ? p1 : -p1;
+      } else if (r != 15) {
+        eobrun = (1u << r) + take_bits(br, r);       // this block included: the rest of its band is refined below
+        break;
+      }
+      do {                                           // past r coefficients whose history is zero, correcting the others on the way
+        int16_t* c = blk + nat[k & 63];
+        if (*c != 0) prog_correct(br, c, p1);
+        else if (--r < 0) break;
+        ++k;
+      } while (k <= se);
+      if (val) {
+        if (k > se) return ST_BAD_HUFFMAN;           // no zero-history position left in the band
+        blk[nat[k & 63]] = (int16_t)val;
+      }
+    }
+  }
+  if (eobrun > 0) {
+    for (; k <= se; ++k) {
+      int16_t* c = blk + nat[k & 63];
+      if (*c != 0) prog_correct(br, c, p1);
+    }
+    --eobrun;
+  }
+  return 0;
+}
+
+// Units u0 .. u0 + nu - 1 of one scan from one segment, in place on the image's coefficient buffer. huff: the scan's tables. The DC
+// predictions and EOBRUN start at zero: a segment begins at the scan's start or behind a restart marker.
+FE_JHD int decode_scan_segment(BitReader& br, const DecGeom& g, const ScanDesc& sc, const HuffDec* huff, uint32_t u0, uint32_t nu, int16_t* coef,
+                               const uint8_t* nat) {
+  int uw, uh;
+  scan_extent(g, sc, uw, uh);
+  int pred[3] = {0, 0, 0};
+  uint32_t eobrun = 0;
+  int uy = (int)(u0 / (uint32_t)uw), ux = (int)(u0 % (uint32_t)uw);
+  for (uint32_t m = 0; m < nu && uy < uh; ++m) {
+    if (sc.ss == 0) {
+      for (int j = 0; j < sc.ns && j < 3; ++j) {
+        const int c = sc.comp[j] < g.ncomp ? sc.comp[j] : 0;
+        const int ch = (sc.ns > 1 && c == 0) ? g.hs : 1, cv = (sc.ns > 1 && c == 0) ? g.vs : 1;
+        for (int by = 0; by < cv; ++by)
+          for (int bx = 0; bx < ch; ++bx) {
+            int16_t* blk = coef + (size_t)(g.blk_off[c] + (uint32_t)(uy * cv + by) * g.bw[c] + (uint32_t)(ux * ch + bx)) * 64;
+            if (sc.ah == 0) {
+              const int rc = prog_dc_first(br, huff[sc.tab[j] < 3 ? sc.tab[j] : 0], sc.al, pred[j], blk);
+              if (rc) return rc;
+            } else if (take_bit(br)) {               // decode_mcu_DC_refine
+              blk[0] = (int16_t)(blk[0] | (1 << sc.al));
+            }
+          }
+      }
+    } else {
+      const int c = sc.comp[0] < g.ncomp ? sc.comp[0] : 0;
+      int16_t* blk = coef + (size_t)(g.blk_off[c] + (uint32_t)uy * g.bw[c] + (uint32_t)ux) * 64;
+      const int rc = sc.ah == 0 ? prog_ac_first(br, huff[0], sc.ss, sc.se, sc.al, eobrun, blk, nat)
+                                : prog_ac_refine(br, huff[0], sc.ss, sc.se, sc.al, eobrun, blk, nat);
+      if (rc) return rc;
+    }
+    if (br.overread()) return ST_PREMATURE_END;
+    if (++ux == uw) { ux = 0; ++uy; }
+  }
+  return 0;
+}
+
 // libjpeg's range_limit[x & RANGE_MASK] behind IDCT_range_limit: x + 128 clamped for the values an honest block gives, wrapped beyond
 FE_JHD uint8_t idct_range_limit(int32_t x) {
   const int v = x & 1023;
@@ -350,7 +505,12 @@ struct Parsed {
   uint16_t q[4][64] = {};
   uint8_t bits[8][16] = {}, vals[8][256] = {};
   bool q_set[4] = {}, h_set[8] = {};
-  std::vector<uint32_t> seg_start, seg_end;      // byte offsets of the entropy-coded segments in the file
+  std::vector<uint32_t> seg_start, seg_end;      // byte offsets of the entropy-coded segments in the file; of all scans, in file order
+  // a progressive file (FLAG_PROGRESSIVE): its scans, and the decoding tables each was written with (ri: the first scan's)
+  bool progressive = false;
+  bool incomplete = false;                       // status ST_OTHER because the scans stop short of all 64 coefficients at full precision
+  std::vector<ScanDesc> scans;
+  std::vector<HuffDec> scan_tabs;
 };
 
 // jdhuff.c jpeg_make_d_derived_tbl; false: the counts describe no prefix code
@@ -415,9 +575,66 @@ inline bool contains(const uint8_t* p, size_t n, const char* s) {
 }
 }  // namespace detail
 
+// the payload of a DHT segment into P's current tables; 0 or the status
+inline int32_t read_dht(const uint8_t* s, size_t n, Parsed& P) {
+  size_t o = 0;
+  while (o < n) {
+    if (n - o < 17) return ST_BAD_MARKER;
+    const int tc = s[o] >> 4, th = s[o] & 15;
+    if (tc > 1 || th > 3) return ST_BAD_MARKER;
+    int total = 0;
+    for (int i = 0; i < 16; ++i) total += s[o + 1 + i];
+    if (total > 256 || (size_t)total > n - o - 17) return ST_BAD_MARKER;
+    const int slot = tc * 4 + th;
+    memcpy(P.bits[slot], s + o + 1, 16);
+    memset(P.vals[slot], 0, 256);
+    memcpy(P.vals[slot], s + o + 17, (size_t)total);
+    P.h_set[slot] = true;
+    o += 17 + (size_t)total;
+  }
+  return ST_OK;
+}
+
+// Entropy-coded data from `pos` on, cut at its restart markers into P.seg_start / seg_end; `want` segments belong there. Returns the
+// marker that ends it (> 0) and sets `next` behind that marker, or the negative status of a stream that is cut wrongly.
+inline int cut_segments(const uint8_t* d, size_t len, size_t pos, int ri, uint64_t want, Parsed& P, size_t& next) {
+  const size_t seg0 = P.seg_start.size();
+  size_t start = pos, i = pos;
+  int marker = -1;
+  while (i < len) {
+    if (d[i] != 0xFF) { ++i; continue; }
+    size_t j = i + 1;
+    while (j < len && d[j] == 0xFF) ++j;                     // fill bytes before a marker
+    if (j >= len) { i = len; break; }
+    if (d[j] == 0x00) {
+      if (j != i + 1) return ST_BAD_MARKER;                 // fill bytes in front of a stuffed zero
+      i += 2;
+      continue;
+    }
+    P.seg_start.push_back((uint32_t)start);
+    P.seg_end.push_back((uint32_t)i);
+    const size_t have = P.seg_start.size() - seg0;
+    if (d[j] >= 0xD0 && d[j] <= 0xD7) {
+      if (!ri || d[j] != 0xD0 + (int)((have - 1) & 7)) return ST_BAD_RESTART;
+      if (have >= want) return ST_BAD_RESTART;              // a restart marker behind the last interval
+      start = i = j + 1;
+      continue;
+    }
+    marker = d[j];
+    i = j + 1;
+    break;
+  }
+  if (marker < 0) return ST_PREMATURE_END;
+  if (P.seg_start.size() - seg0 < want) return ST_PREMATURE_END;
+  next = i;
+  return marker;
+}
+inline void parse_scans(const uint8_t* d, size_t len, size_t pos, Parsed& P);
+
 // Reads the markers of one file. P.status: 0 when this decoder takes the file, then everything in P is set and the tables named by the
 // scan exist and are prefix codes; otherwise the first reason found. Width, height and components are set whenever a frame header was read.
-inline void parse(const uint8_t* d, size_t len, Parsed& P) {
+// flags: FLAG_PROGRESSIVE takes SOF2 files whose scans form a complete normal progression (parse_scans); without it they get ST_PROGRESSIVE.
+inline void parse(const uint8_t* d, size_t len, Parsed& P, int flags = 0) {
   using detail::be16;
   P = Parsed();
   auto fail = [&P](int32_t s) { P.status = s; };
@@ -446,9 +663,10 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
       if (n < 6) return fail(ST_BAD_MARKER);
       have_sof = true;
       P.height = (int)be16(s + 1); P.width = (int)be16(s + 3); P.ncomp = s[5];
-      if (m == 0xC2) return fail(ST_PROGRESSIVE);
+      if (m == 0xC2 && !(flags & FLAG_PROGRESSIVE)) return fail(ST_PROGRESSIVE);
       if (m >= 0xC9) return fail(ST_ARITHMETIC);
-      if (m != 0xC0 && m != 0xC1) return fail(ST_OTHER);
+      if (m != 0xC0 && m != 0xC1 && m != 0xC2) return fail(ST_OTHER);
+      P.progressive = m == 0xC2;
       if (s[0] != 8) return fail(ST_PRECISION);
       if (P.width == 0) return fail(ST_BAD_MARKER);
       if (P.height == 0) return fail(ST_OTHER);              // the height comes in a DNL marker
@@ -470,21 +688,8 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
     } else if (m == 0xCC) {
       return fail(ST_ARITHMETIC);
     } else if (m == 0xC4) {
-      size_t o = 0;
-      while (o < n) {
-        if (n - o < 17) return fail(ST_BAD_MARKER);
-        const int tc = s[o] >> 4, th = s[o] & 15;
-        if (tc > 1 || th > 3) return fail(ST_BAD_MARKER);
-        int total = 0;
-        for (int i = 0; i < 16; ++i) total += s[o + 1 + i];
-        if (total > 256 || (size_t)total > n - o - 17) return fail(ST_BAD_MARKER);
-        const int slot = tc * 4 + th;
-        memcpy(P.bits[slot], s + o + 1, 16);
-        memset(P.vals[slot], 0, 256);
-        memcpy(P.vals[slot], s + o + 17, (size_t)total);
-        P.h_set[slot] = true;
-        o += 17 + (size_t)total;
-      }
+      const int32_t rc = read_dht(s, n, P);
+      if (rc) return fail(rc);
     } else if (m == 0xDB) {
       size_t o = 0;
       while (o < n) {
@@ -516,6 +721,7 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
       }
     } else if (m == 0xDA) {
       if (!have_sof) return fail(ST_BAD_MARKER);
+      if (P.progressive) break;                              // pos stays at this first SOS: parse_scans reads every scan header
       if (n < 1) return fail(ST_BAD_MARKER);
       const int ns = s[0];
       if (ns < 1 || ns > 4 || n != (size_t)(4 + 2 * ns)) return fail(ST_BAD_MARKER);
@@ -540,6 +746,7 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
     else ycc = !(P.comp[0].id == 'R' && P.comp[1].id == 'G' && P.comp[2].id == 'B');
     if (!ycc) return fail(ST_ADOBE_RGB);
   }
+  if (P.progressive) return parse_scans(d, len, pos, P);
   for (int c = 0; c < P.ncomp; ++c) {
     if (!P.q_set[P.comp[c].tq] || !P.h_set[P.comp[c].td] || !P.h_set[4 + P.comp[c].ta]) return fail(ST_BAD_MARKER);
     HuffDec t;
@@ -553,32 +760,9 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
   const uint64_t mcus = (uint64_t)g.mw * g.mh;
   const uint64_t want = P.ri ? (mcus + P.ri - 1) / P.ri : 1;
   if (len > 0xFFFFFFF0u) return fail(ST_OTHER);
-  size_t start = pos, i = pos;
-  int marker = -1;
-  while (i < len) {
-    if (d[i] != 0xFF) { ++i; continue; }
-    size_t j = i + 1;
-    while (j < len && d[j] == 0xFF) ++j;                     // fill bytes before a marker
-    if (j >= len) { i = len; break; }
-    if (d[j] == 0x00) {
-      if (j != i + 1) return fail(ST_BAD_MARKER);            // fill bytes in front of a stuffed zero
-      i += 2;
-      continue;
-    }
-    P.seg_start.push_back((uint32_t)start);
-    P.seg_end.push_back((uint32_t)i);
-    if (d[j] >= 0xD0 && d[j] <= 0xD7) {
-      if (!P.ri || d[j] != 0xD0 + (int)((P.seg_start.size() - 1) & 7)) return fail(ST_BAD_RESTART);
-      if (P.seg_start.size() >= want) return fail(ST_BAD_RESTART);      // a restart marker behind the last interval
-      start = i = j + 1;
-      continue;
-    }
-    marker = d[j];
-    i = j + 1;
-    break;
-  }
-  if (marker < 0) return fail(ST_PREMATURE_END);
-  if (P.seg_start.size() < want) return fail(ST_PREMATURE_END);
+  size_t i = pos;
+  int marker = cut_segments(d, len, pos, P.ri, want, P, i);
+  if (marker < 0) return fail(marker);
   while (marker != 0xD9) {                                   // what follows the scan: another scan makes the file multi-scan
     if (marker == 0xDA) return fail(ST_MULTISCAN);
     if (marker == 0xC4 || marker == 0xDB || marker == 0xDD || marker == 0xDC || marker == 0xFE || (marker >= 0xE0 && marker <= 0xEF)) {
@@ -601,11 +785,127 @@ inline void parse(const uint8_t* d, size_t len, Parsed& P) {
   P.status = ST_OK;
 }
 
+// The scans of a progressive file, from its first SOS (pos: at that segment's length field) to EOI. Status 0 only for what libjpeg decodes
+// without inter-block smoothing and exactly as a baseline file from there on: every scan within jdphuff.c's parameter rules, the scans
+// in the normal progression (a coefficient's first scan has Ah = 0, every later one has Ah = the Al it was left at), and complete (all
+// 64 coefficients of every component down to Al = 0). A file whose scans are in order but stop short is ST_OTHER with P.incomplete: its
+// scans can still be run to tell whether the stream is corrupt as well.
+inline void parse_scans(const uint8_t* d, size_t len, size_t pos, Parsed& P) {
+  using detail::be16;
+  auto fail = [&P](int32_t s) { P.status = s; };
+  for (int c = 0; c < P.ncomp; ++c)
+    if (!P.q_set[P.comp[c].tq]) return fail(ST_BAD_MARKER);
+  if (len > 0xFFFFFFF0u) return fail(ST_OTHER);
+  const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+  int8_t left[3][64];                                        // the Al each coefficient was left at, -1: no scan has touched it
+  memset(left, -1, sizeof(left));
+  for (;;) {
+    if (pos + 2 > len) return fail(ST_PREMATURE_END);
+    const size_t L = be16(d + pos);
+    if (L < 2) return fail(ST_BAD_MARKER);
+    if (L > len - pos) return fail(ST_PREMATURE_END);
+    const uint8_t* s = d + pos + 2;
+    const size_t n = L - 2;
+    if (n < 1) return fail(ST_BAD_MARKER);
+    const int ns = s[0];
+    if (ns < 1 || ns > 4 || n != (size_t)(4 + 2 * ns) || ns > P.ncomp) return fail(ST_BAD_MARKER);
+    if (P.scans.size() >= (size_t)MAX_SCANS) return fail(ST_OTHER);
+    ScanDesc sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.ns = (uint8_t)ns;
+    int td[3] = {0, 0, 0}, ta = 0, prev = -1;
+    for (int j = 0; j < ns; ++j) {
+      int c = prev + 1;
+      while (c < P.ncomp && P.comp[c].id != s[1 + 2 * j]) ++c;
+      if (c >= P.ncomp) return fail(ST_OTHER);               // not a component of the frame, or out of frame order
+      prev = c;
+      sc.comp[j] = (uint8_t)c;
+      td[j] = s[2 + 2 * j] >> 4; ta = s[2 + 2 * j] & 15;
+      if (td[j] > 3 || ta > 3) return fail(ST_BAD_MARKER);
+    }
+    const int ss = s[1 + 2 * ns], se = s[2 + 2 * ns], ah = s[3 + 2 * ns] >> 4, al = s[3 + 2 * ns] & 15;
+    // jdphuff.c start_pass_phuff_decoder
+    if (ss == 0 ? se != 0 : (ss > se || se > 63 || ns != 1)) return fail(ST_BAD_MARKER);
+    if ((ah != 0 && al != ah - 1) || al > 13) return fail(ST_BAD_MARKER);
+    sc.ss = (uint8_t)ss; sc.se = (uint8_t)se; sc.ah = (uint8_t)ah; sc.al = (uint8_t)al;
+    for (int j = 0; j < ns; ++j) {
+      int8_t* l = left[sc.comp[j]];
+      if (ss != 0 && l[0] < 0) return fail(ST_OTHER);        // AC before the component's DC
+      for (int k = ss; k <= se; ++k) {
+        if (ah == 0 ? l[k] != -1 : l[k] != ah) return fail(ST_OTHER);
+        l[k] = (int8_t)al;
+      }
+    }
+    // the tables this scan decodes with, as they stand now
+    sc.tab_first = (uint32_t)P.scan_tabs.size();
+    if (ss != 0 || ah == 0) {
+      for (int j = 0; j < ns; ++j) {
+        const int slot = ss ? 4 + ta : td[j];
+        int same = 0;
+        while (same < j && td[same] != td[j]) ++same;
+        if (same < j) { sc.tab[j] = sc.tab[same]; continue; }
+        if (!P.h_set[slot]) return fail(ST_BAD_MARKER);
+        HuffDec t;
+        if (!build_huff_dec(P.bits[slot], P.vals[slot], t)) return fail(ST_BAD_HUFFMAN);
+        if (ss == 0)
+          for (int i = 0; i < 256; ++i)
+            if (P.vals[slot][i] > 15) return fail(ST_BAD_HUFFMAN);
+        sc.tab[j] = sc.ntab++;
+        P.scan_tabs.push_back(t);
+      }
+    }
+    // its entropy-coded data
+    sc.ri = P.ri;
+    int uw, uh;
+    scan_extent(g, sc, uw, uh);
+    const uint64_t units = (uint64_t)uw * uh;
+    sc.seg_first = (uint32_t)P.seg_start.size();
+    size_t i = 0;
+    int marker = cut_segments(d, len, pos + L, sc.ri, sc.ri ? (units + sc.ri - 1) / sc.ri : 1, P, i);
+    if (marker < 0) return fail(marker);
+    sc.nseg = (uint32_t)P.seg_start.size() - sc.seg_first;
+    P.scans.push_back(sc);
+    // what stands between two scans: tables and the restart interval of the next
+    while (marker != 0xD9 && marker != 0xDA) {
+      if (marker == 0xC4 || marker == 0xDB || marker == 0xDD || marker == 0xDC || marker == 0xFE || (marker >= 0xE0 && marker <= 0xEF)) {
+        if (i + 2 > len) return fail(ST_PREMATURE_END);
+        const size_t M = be16(d + i);
+        if (M < 2) return fail(ST_BAD_MARKER);
+        if (M > len - i) return fail(ST_PREMATURE_END);
+        if (marker == 0xDC || marker == 0xDB) return fail(ST_OTHER);      // a quantisation table behind the first SOS is left to libjpeg
+        if (marker == 0xC4) {
+          const int32_t rc = read_dht(d + i + 2, M - 2, P);
+          if (rc) return fail(rc);
+        } else if (marker == 0xDD) {
+          if (M != 4) return fail(ST_BAD_MARKER);
+          P.ri = (int)be16(d + i + 2);
+        }
+        i += M;
+        if (i + 2 > len) return fail(ST_PREMATURE_END);
+        if (d[i] != 0xFF) return fail(ST_BAD_MARKER);
+        while (i + 1 < len && d[i + 1] == 0xFF) ++i;
+        if (i + 2 > len) return fail(ST_PREMATURE_END);
+        marker = d[i + 1];
+        i += 2;
+      } else {
+        return fail(ST_BAD_MARKER);
+      }
+    }
+    if (marker == 0xD9) break;
+    pos = i;
+  }
+  P.ri = P.scans[0].ri;
+  for (int c = 0; c < P.ncomp; ++c)
+    for (int k = 0; k < 64; ++k)
+      if (left[c][k] != 0) { P.incomplete = true; return fail(ST_OTHER); }
+  P.status = ST_OK;
+}
+
 inline void build_tables(const Parsed& P, DecTables& T) {
   memset(&T, 0, sizeof(T));
   for (int t = 0; t < 4; ++t)
     if (P.q_set[t]) memcpy(T.q[t], P.q[t], sizeof(T.q[t]));
-  for (int c = 0; c < P.ncomp; ++c) {
+  for (int c = 0; c < P.ncomp && !P.progressive; ++c) {      // a progressive file's Huffman tables are its scans' (P.scan_tabs)
     build_huff_dec(P.bits[P.comp[c].td], P.vals[P.comp[c].td], T.huff[P.comp[c].td]);
     build_huff_dec(P.bits[4 + P.comp[c].ta], P.vals[4 + P.comp[c].ta], T.huff[4 + P.comp[c].ta]);
   }
@@ -613,9 +913,10 @@ inline void build_tables(const Parsed& P, DecTables& T) {
 
 // The whole decode of one parsed file on the host, stage by stage as the kernels run it. buf: the file copied into a 16-byte aligned
 // buffer padded to a multiple of 16 bytes. out: [oh][ow][3] with (oh, ow) = (height, width), exchanged for orientations 5 .. 8 when
-// apply_orientation. Returns the status; out is written only for 0.
+// apply_orientation. Returns the status; out is written only for 0. An incomplete progression has its scans run and its blocks transformed
+// all the same, so that a stream that is corrupt as well is reported as that; it keeps ST_OTHER when nothing is found.
 inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int apply_orientation, uint8_t* out) {
-  if (P.status != ST_OK) return P.status;
+  if (P.status != ST_OK && !P.incomplete) return P.status;
   const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
   DecTables* T = new DecTables;
   build_tables(P, *T);
@@ -625,7 +926,19 @@ inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int app
   for (int c = 0; c < 3; ++c) { td[c] = P.comp[c].td; ta[c] = P.comp[c].ta; }
   const uint32_t mcus = (uint32_t)g.mw * g.mh, per = P.ri ? (uint32_t)P.ri : mcus;
   int32_t st = ST_OK;
-  for (size_t k = 0; k < P.seg_start.size() && st == ST_OK; ++k) {
+  for (size_t n = 0; n < P.scans.size() && st == ST_OK; ++n) {      // file order: a later scan refines what an earlier one left
+    const ScanDesc& sc = P.scans[n];
+    int uw, uh;
+    scan_extent(g, sc, uw, uh);
+    const uint32_t units = (uint32_t)uw * uh, each = sc.ri ? (uint32_t)sc.ri : units;
+    for (uint32_t k = 0; k < sc.nseg && st == ST_OK; ++k) {
+      BitReader br;
+      br.init(buf, P.seg_start[sc.seg_first + k], P.seg_end[sc.seg_first + k]);
+      const uint32_t u0 = k * each;
+      st = decode_scan_segment(br, g, sc, P.scan_tabs.data() + sc.tab_first, u0, units - u0 < each ? units - u0 : each, coef.data(), kNatural);
+    }
+  }
+  for (size_t k = 0; k < P.seg_start.size() && st == ST_OK && !P.progressive; ++k) {
     BitReader br;
     br.init(buf, P.seg_start[k], P.seg_end[k]);
     const uint32_t m0 = (uint32_t)k * per;
@@ -639,6 +952,7 @@ inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int app
                           planes.data() + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, (size_t)g.bw[c] * 8))
             st = ST_BAD_COEFFICIENT;
   }
+  if (st == ST_OK && P.incomplete) st = ST_OTHER;
   if (st == ST_OK) {
     const int o = apply_orientation ? P.orientation : 1;
     for (int y = 0; y < g.h; ++y)

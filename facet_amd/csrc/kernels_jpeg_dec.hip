@@ -5,6 +5,8 @@
 //              descriptors, tables, segment offsets and the compressed bytes of the whole chunk into one pinned block: one upload
 //   B entropy: a lane decodes one segment serially into zeroed int16 coefficient blocks; a workgroup is one wave holding up to 64
 //              segments of ONE image, whose Huffman tables sit in LDS. A file without restart markers is one segment: one lane of its wave.
+//              A progressive file (FE_JPEG_PROGRESSIVE) has one such pass per scan, over the segments and with the tables of that scan:
+//              launch s runs scan s of every image that has one, and the stream keeps an image's scans in file order.
 //   C idct:    one lane per block: dequantise, integer slow IDCT, 8 rows of 8 samples into the component's plane (padded to the block grid)
 //   D colour:  one lane per 4 pixels of a row: triangle-filter upsampling, YCbCr -> RGB, store as RGB or BGR at the address the EXIF
 //              orientation gives (all 8 cases; there is no transpose pass)
@@ -28,6 +30,7 @@ struct DevImage {
   int32_t w, h, ncomp, hs, vs, ri, orientation;
   int32_t slot;                          // image index in the destination
   uint8_t td[4], ta[4], tq[4];
+  uint32_t scan_first, nscan;            // a progressive image: its rows of the scan descriptors, and nseg = 0
 };
 
 constexpr int JD_WAVE = 64;
@@ -60,6 +63,42 @@ __global__ __launch_bounds__(JD_WAVE) void jpegdec_entropy_kernel(const DevImage
   if (rc) atomicMin(status + blockIdx.x, rc);
 }
 static_assert(sizeof(HuffDec) % 4 == 0 && offsetof(DecTables, huff) % 4 == 0, "the tables are copied by dwords");
+
+// Scan `scan` of every progressive image of the chunk that has that many: the shape of the kernel above with the scan's tables (at most
+// one per component) and the scan's segments. It updates the coefficients earlier scans left, so the launches of a chunk follow each
+// other on one stream in scan order; within a launch two lanes never share a block.
+__global__ __launch_bounds__(JD_WAVE) void jpegdec_scan_entropy_kernel(const DevImage* __restrict__ imgs, const ScanDesc* __restrict__ scans,
+                                                                       const HuffDec* __restrict__ pool, const uint32_t* __restrict__ seg_start,
+                                                                       const uint32_t* __restrict__ seg_end, const uint8_t* __restrict__ bytes,
+                                                                       int16_t* __restrict__ coef, int32_t* __restrict__ status, uint32_t scan) {
+  __shared__ HuffDec H[3];
+  __shared__ uint8_t nat[64];
+  const DevImage im = imgs[blockIdx.x];
+  if (scan >= im.nscan) return;                              // uniform over the wave, as are the next two
+  const ScanDesc sc = scans[im.scan_first + scan];
+  if (blockIdx.y * JD_WAVE >= sc.nseg) return;
+  {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(pool + sc.tab_first);
+    uint32_t* d = reinterpret_cast<uint32_t*>(H);
+    const int nw = (int)(min((uint32_t)sc.ntab, 3u) * (sizeof(HuffDec) / 4));
+    for (int t = threadIdx.x; t < nw; t += JD_WAVE) d[t] = s[t];
+    constexpr uint8_t order[64] = FE_JPEG_NATURAL_ORDER;
+    nat[threadIdx.x] = order[threadIdx.x];
+  }
+  __syncthreads();
+  const uint32_t k = blockIdx.y * JD_WAVE + threadIdx.x;
+  if (k >= sc.nseg) return;
+  const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  int uw, uh;
+  scan_extent(g, sc, uw, uh);
+  const uint32_t units = (uint32_t)uw * (uint32_t)uh, per = sc.ri ? (uint32_t)sc.ri : units;
+  const uint32_t u0 = k * per;                               // nseg = ceil(units / per): u0 < units
+  BitReader br;
+  br.init(bytes, seg_start[sc.seg_first + k], seg_end[sc.seg_first + k]);
+  const int rc = decode_scan_segment(br, g, sc, H, u0, min(per, units - u0), coef + im.coef_off, nat);
+  if (rc) atomicMin(status + blockIdx.x, rc);
+}
+static_assert(sizeof(ScanDesc) % 4 == 0, "scan descriptors are read as an array in the upload block");
 
 __global__ __launch_bounds__(JD_THREADS) void jpegdec_idct_kernel(const DevImage* __restrict__ imgs, const DecTables* __restrict__ tabs,
                                                                   const int16_t* __restrict__ coef, uint8_t* __restrict__ planes,
@@ -150,15 +189,16 @@ struct StageTimer {                      // with fe_profile_enable: one record p
 
 }  // namespace
 
-void jpeg_probe(const uint8_t* data, size_t len, int32_t out[8]) {
+void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]) {
   Parsed P;
-  parse(data, len, P);
+  parse(data, len, P, flags);
+  out[8] = P.progressive ? 1 : 0; out[9] = (int32_t)P.scans.size();
   out[0] = P.width; out[1] = P.height; out[2] = P.ncomp; out[3] = P.hs; out[4] = P.vs; out[5] = P.ri; out[6] = P.orientation; out[7] = P.status;
 }
 
 // dst: [n][h][w][3] on the device or on the host; status: host [n]. See fe_jpeg_decode.
 void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
-                       uint8_t* dst, int32_t* status) {
+                       int flags, uint8_t* dst, int32_t* status) {
   FE_CHECK(n > 0 && h > 0 && w > 0 && h <= 65535 && w <= 65535, "jpeg_decode: bad shape %d x %d x %d", n, h, w);
   const auto t_parse = std::chrono::steady_clock::now();
   std::vector<Parsed> parsed((size_t)n);
@@ -166,13 +206,13 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
   for (int i = 0; i < n; ++i) {
     Parsed& P = parsed[i];
     if (!data[i]) { P.status = ST_BAD_MARKER; status[i] = P.status; continue; }
-    parse(data[i], len[i], P);
-    if (P.status == ST_OK) {
+    parse(data[i], len[i], P, flags);
+    if (P.status == ST_OK || P.incomplete) {
       const bool swap = apply_orientation && P.orientation >= 5;
-      if ((swap ? P.width : P.height) != h || (swap ? P.height : P.width) != w) P.status = ST_BAD_DIMENSIONS;
+      if ((swap ? P.width : P.height) != h || (swap ? P.height : P.width) != w) { P.status = ST_BAD_DIMENSIONS; P.incomplete = false; }
     }
     status[i] = P.status;
-    if (P.status == ST_OK) todo.push_back(i);
+    if (P.status == ST_OK || P.incomplete) todo.push_back(i);      // an incomplete progression has its scans run: it may be corrupt as well
   }
   if (c.profile)
     c.timings.push_back({"jpeg_decode A: parse (host)", 0.0, 0.0,
@@ -182,14 +222,14 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
     const size_t bytes = (size_t)(P.seg_end.back() - P.seg_start.front());
     return (size_t)g.nblk * 128 + up256(g.plane_bytes) + up256(bytes + 16) + sizeof(DevImage) + sizeof(DecTables) + P.seg_start.size() * 8 + 4 +
-           (dst_on_device ? 0 : out_b) + 64;
+           P.scans.size() * sizeof(ScanDesc) + P.scan_tabs.size() * sizeof(HuffDec) + (dst_on_device ? 0 : out_b) + 64;
   };
   const size_t budget = c.arena.capacity() - c.arena.capacity() / 8;
   StageTimer tm(c);
   std::vector<int32_t> st_host;
   for (size_t first = 0; first < todo.size();) {
     // the images of this chunk: as many as the workspace holds
-    size_t used = 8 * 256, last = first;
+    size_t used = 12 * 256, last = first;
     uint64_t comp_bytes = 0;
     while (last < todo.size() && last - first < 4096) {
       const Parsed& P = parsed[todo[last]];
@@ -200,11 +240,15 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
       ++last;
     }
     const int nd = (int)(last - first);
-    size_t nseg = 0;
-    for (size_t k = first; k < last; ++k) nseg += parsed[todo[k]].seg_start.size();
+    size_t nseg = 0, nscan = 0, npool = 0;
+    for (size_t k = first; k < last; ++k) {
+      const Parsed& P = parsed[todo[k]];
+      nseg += P.seg_start.size(); nscan += P.scans.size(); npool += P.scan_tabs.size();
+    }
     // ---- stage A: one block of host memory -> one upload
     const size_t o_img = 0, o_tab = up256(o_img + (size_t)nd * sizeof(DevImage)), o_s0 = up256(o_tab + (size_t)nd * sizeof(DecTables)),
-                 o_s1 = up256(o_s0 + nseg * 4), o_bytes = up256(o_s1 + nseg * 4);
+                 o_s1 = up256(o_s0 + nseg * 4), o_scan = up256(o_s1 + nseg * 4), o_pool = up256(o_scan + nscan * sizeof(ScanDesc)),
+                 o_st0 = up256(o_pool + npool * sizeof(HuffDec)), o_bytes = up256(o_st0 + (size_t)nd * 4);
     size_t blob = o_bytes;
     for (size_t k = first; k < last; ++k) blob += ((size_t)(parsed[todo[k]].seg_end.back() - parsed[todo[k]].seg_start.front()) + 15) & ~(size_t)15;
     blob += 16;                                              // 16-byte loads at the tail stay inside
@@ -221,8 +265,13 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     DecTables* h_tab = (DecTables*)(hb + o_tab);
     uint32_t* h_s0 = (uint32_t*)(hb + o_s0);
     uint32_t* h_s1 = (uint32_t*)(hb + o_s1);
-    size_t coef_el = 0, plane_b = 0, seg_at = 0, byte_at = 0;
-    uint32_t max_groups = 1, max_blk = 1;
+    ScanDesc* h_scan = (ScanDesc*)(hb + o_scan);
+    HuffDec* h_pool = (HuffDec*)(hb + o_pool);
+    int32_t* h_st0 = (int32_t*)(hb + o_st0);                 // what each image's status starts from
+    size_t coef_el = 0, plane_b = 0, seg_at = 0, byte_at = 0, scan_at = 0, pool_at = 0;
+    uint32_t max_groups = 0, max_blk = 1;
+    uint32_t scan_groups[MAX_SCANS] = {};                    // [s]: workgroups per image of the launch for scan s, 0: no image has one
+    bool held_back = false;
     for (int k = 0; k < nd; ++k) {
       const int src = todo[first + k];
       const Parsed& P = parsed[src];
@@ -235,6 +284,20 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
       D.slot = dst_on_device ? src : k;
       for (int cc = 0; cc < P.ncomp; ++cc) { D.td[cc] = P.comp[cc].td; D.ta[cc] = P.comp[cc].ta; D.tq[cc] = P.comp[cc].tq; }
       build_tables(P, h_tab[k]);
+      h_st0[k] = P.incomplete ? (int32_t)ST_OTHER : (int32_t)ST_OK;
+      held_back |= P.incomplete;
+      if (P.progressive) {
+        D.nseg = 0;                                          // nothing for the baseline kernel
+        D.scan_first = (uint32_t)scan_at; D.nscan = (uint32_t)P.scans.size();
+        for (size_t s = 0; s < P.scans.size(); ++s) {
+          ScanDesc& S = h_scan[scan_at + s];
+          S = P.scans[s];
+          S.seg_first += (uint32_t)seg_at; S.tab_first += (uint32_t)pool_at;
+          scan_groups[s] = std::max(scan_groups[s], (S.nseg + JD_WAVE - 1) / JD_WAVE);
+        }
+        if (!P.scan_tabs.empty()) memcpy(h_pool + pool_at, P.scan_tabs.data(), P.scan_tabs.size() * sizeof(HuffDec));
+        scan_at += P.scans.size(); pool_at += P.scan_tabs.size();
+      }
       const uint32_t s0 = P.seg_start.front(), nbytes = P.seg_end.back() - s0;
       memcpy(hb + o_bytes + byte_at, data[src] + s0, nbytes);
       for (size_t s = 0; s < P.seg_start.size(); ++s) {
@@ -252,6 +315,7 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     }
     memset(hb + o_bytes + byte_at, 0, 16);
     FE_CHECK(max_groups <= 65535, "jpeg_decode: an image has too many restart intervals");
+    for (int s = 0; s < MAX_SCANS; ++s) FE_CHECK(scan_groups[s] <= 65535, "jpeg_decode: a scan has too many restart intervals");
     c.arena.reset();
     uint8_t* d_blob = (uint8_t*)c.arena.alloc(blob);
     int32_t* d_status = (int32_t*)c.arena.alloc((size_t)nd * 4);
@@ -264,10 +328,16 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     const DevImage* d_img = (const DevImage*)(d_blob + o_img);
     const DecTables* d_tab = (const DecTables*)(d_blob + o_tab);
     tm.begin();
-    FE_HIP(hipMemsetAsync(d_status, 0, (size_t)nd * 4, c.stream));
+    if (held_back) FE_HIP(hipMemcpyAsync(d_status, d_blob + o_st0, (size_t)nd * 4, hipMemcpyDeviceToDevice, c.stream));
+    else FE_HIP(hipMemsetAsync(d_status, 0, (size_t)nd * 4, c.stream));
     FE_HIP(hipMemsetAsync(d_coef, 0, coef_el * 2, c.stream));
-    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3((unsigned)nd, max_groups), dim3(JD_WAVE), 0, c.stream, d_img, d_tab, (const uint32_t*)(d_blob + o_s0),
-                       (const uint32_t*)(d_blob + o_s1), (const uint8_t*)(d_blob + o_bytes), d_coef, d_status);
+    if (max_groups)
+      hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3((unsigned)nd, max_groups), dim3(JD_WAVE), 0, c.stream, d_img, d_tab, (const uint32_t*)(d_blob + o_s0),
+                         (const uint32_t*)(d_blob + o_s1), (const uint8_t*)(d_blob + o_bytes), d_coef, d_status);
+    for (int s = 0; s < MAX_SCANS && scan_groups[s]; ++s)    // every image's scan s before any image's scan s + 1
+      hipLaunchKernelGGL(jpegdec_scan_entropy_kernel, dim3((unsigned)nd, scan_groups[s]), dim3(JD_WAVE), 0, c.stream, d_img,
+                         (const ScanDesc*)(d_blob + o_scan), (const HuffDec*)(d_blob + o_pool), (const uint32_t*)(d_blob + o_s0),
+                         (const uint32_t*)(d_blob + o_s1), (const uint8_t*)(d_blob + o_bytes), d_coef, d_status, (uint32_t)s);
     tm.end("jpeg_decode B: entropy", (double)(blob - o_bytes));
     tm.begin();
     hipLaunchKernelGGL(jpegdec_idct_kernel, dim3((max_blk + JD_THREADS - 1) / JD_THREADS, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, d_tab,

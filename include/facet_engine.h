@@ -339,14 +339,15 @@ int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int 
 /* Status of a file. 0: decoded (or decodable). Positive: a kind of file left to the caller's own decoder, nothing was attempted.
  * Negative: a corrupt stream. */
 #define FE_JPEG_OK 0
-#define FE_JPEG_PROGRESSIVE 1        /* SOF2 */
+#define FE_JPEG_PROGRESSIVE 1        /* SOF2; as a flag of the _ex entry points: decode such files too */
 #define FE_JPEG_ARITHMETIC 2         /* arithmetic coding */
 #define FE_JPEG_PRECISION 3          /* 12-bit samples */
 #define FE_JPEG_COMPONENTS 4         /* 4 components (CMYK / YCCK) or 2 */
 #define FE_JPEG_ADOBE_RGB 5          /* 3 components stored as RGB (Adobe transform 0) */
 #define FE_JPEG_SAMPLING 6           /* sampling other than luma 1x1 / 2x1 / 2x2 with chroma 1x1 (4:4:0, 4:1:1, ...) */
 #define FE_JPEG_MULTISCAN 7          /* baseline file with more than one scan */
-#define FE_JPEG_OTHER 8              /* lossless / hierarchical frame, DNL, an EXIF / XMP block only Pillow should judge */
+#define FE_JPEG_OTHER 8              /* lossless / hierarchical frame, DNL, an EXIF / XMP block only Pillow should judge; with
+                                      * FE_JPEG_PROGRESSIVE: a progression that is out of order, incomplete or longer than 32 scans, DQT between scans */
 #define FE_JPEG_BAD_MARKER (-1)      /* not a JPEG file, a marker segment that makes no sense, a table that is missing */
 #define FE_JPEG_BAD_HUFFMAN (-2)     /* a table that is no prefix code, a code that is in no table, a run past the block */
 #define FE_JPEG_PREMATURE_END (-3)   /* the file or a segment ends before its data does */
@@ -365,6 +366,18 @@ int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info);
  * every image got a status. Temporaries come from the context's workspace, in as many chunks as it takes. */
 int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation,
                    int dst_on_device, uint8_t* dst, int32_t* status);
+/* The same with flags. 0: exactly fe_jpeg_probe / fe_jpeg_decode. FE_JPEG_PROGRESSIVE: a progressive Huffman file (SOF2) gets status 0
+ * instead of 1 when libjpeg decodes it without inter-block smoothing, which is when its scans obey jdphuff.c's parameter rules, follow the
+ * normal progression (a coefficient's first scan has Ah = 0, every later one Ah = the Al before it) and are complete (every coefficient of
+ * every component down to Al = 0), in at most 32 scans and with no DQT behind the first SOS; any other progressive file gets
+ * FE_JPEG_OTHER or a negative status. progressive: the frame is SOF2 (set only with the flag); scans: the scans read, 0 for a baseline
+ * file. The entropy stage runs once per scan over that scan's restart intervals and with that scan's tables, in file order; the
+ * transform and colour stages, and therefore the pixels, are those of a baseline file. Progressive and baseline files of one output
+ * size may share a call. */
+typedef struct { int32_t width, height, components, hsamp, vsamp, restart_interval, orientation, status, progressive, scans; } fe_jpeg_info_ex;
+int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info);
+int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation,
+                      int dst_on_device, int flags, uint8_t* dst, int32_t* status);
 
 /* ---- image-level entry points (uint8 HWC images in, per-image results out) ------------------------------ */
 /* CLIP from raw RGB images: open_clip eval transform on the GPU (PIL-bicubic shorter side -> 224, center crop 224,
