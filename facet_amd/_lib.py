@@ -37,7 +37,7 @@ class EngineError(RuntimeError):
 
 class EngineCapacityError(EngineError):
     """The batch did not fit (device memory, arena, KV cache): FE_ERR_CAPACITY, raised by the padded-batch image path only
-    (vlm_preprocess_rgb, vlm_encode_preprocessed, vlm_prefill with pad). Fewer images at a time may fit. jpeg_encode raises it when the
+    (vlm_preprocess_rgb, vlm_encode_preprocessed, vlm_prefill with pad). Fewer images at a time may fit. jpeg_encode / face_thumbnails raise it when the
     caller's `cap` is too small for an image."""
 
 
@@ -173,6 +173,8 @@ SIGNATURES = {
     "fe_jpeg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_thumbnail_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fe_face_thumbnails": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "fe_jpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_jpeg_probe_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
@@ -1209,6 +1211,29 @@ class Engine:
         self._ck(self.lib.fe_thumbnail_jpeg(self.h, p, n, h, w, 1 if bgr else 0, dev, oh, ow, fx, fy,
                                             rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None, box.ctypes.data_as(C.c_void_p),
                                             1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths)
+
+    def face_thumbnails(self, images, img_index, crops, out_sizes, quality=85, cap=None):
+        """BGR uint8 [n,h,w,3] (or device tuple) -> list of bytes, one per face: crops int [m,4] (x0,y0,x1,y1 exclusive, inside the image,
+        not empty) of images img_index [m], each resized to out_sizes [m,2] = (ow, oh) with PIL's BOX filter and saved as the JPEG
+        `Image.fromarray(crop[:, :, ::-1]).resize((ow, oh), Image.BOX).save(buf, "JPEG", quality=quality)` writes (fe_face_thumbnails;
+        facet_amd.face.face_thumbnail_plan gives the rectangle and size of a face box). cap as in jpeg_encode, against
+        fe_jpeg_bound(max oh, max ow)."""
+        p, n, h, w, dev, keep = self._img_ptr(images)
+        idx = np.ascontiguousarray(img_index, dtype=np.int32).reshape(-1)
+        m = idx.shape[0]
+        if m == 0:
+            return []
+        r = np.ascontiguousarray(crops, dtype=np.int32).reshape(m, 4)
+        sz = np.ascontiguousarray(out_sizes, dtype=np.int32).reshape(m, 2)
+        if cap is None:
+            cap = self.jpeg_bound(max(1, int(sz[:, 1].max())), max(1, int(sz[:, 0].max())))
+        cap = int(cap)
+        out = np.empty((m, cap), np.uint8)
+        lengths = np.zeros(m, np.int32)
+        self._ck(self.lib.fe_face_thumbnails(self.h, p, n, h, w, dev, m, idx.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
+                                             sz.ctypes.data_as(C.c_void_p), int(quality), out.ctypes.data_as(C.c_void_p), cap,
+                                             lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)
 
     @staticmethod

@@ -19,7 +19,7 @@ as the last step, from the multi-pass metrics mapping (multi_pass.py:713-752); `
 narrower mapping of the single-pass path (batch_processor.py:272-296).
 
 Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P + SAMP-Net), fe_image_stats (technical scans),
-fe_face_analyze + fe_roi_laplacian (through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
+fe_face_analyze + fe_roi_laplacian (+ fe_face_thumbnails with `gpu_thumbnails=True`; through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
 fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_subject_region (with `subject_region=True`).
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
@@ -97,7 +97,7 @@ class BatchScorer:
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
         _resident (process_files): (device_ptr, n, h, w) of an RGB batch that is already on the device, handed over - it is freed here -
-        with images_rgb None; the pixels are fetched only when a stage that works on host arrays (faces, the VLM analyzer) is on."""
+        with images_rgb None; the pixels are fetched only when a stage that works on host arrays (face thumbnails cut by Pillow, the VLM analyzer) is on."""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -111,7 +111,8 @@ class BatchScorer:
             # one upload; the BGR copy the reference keeps as img_cv is made on the device, and every engine call reads the resident batch
             if _resident is None:
                 e.h2d(d_rgb, imgs)
-            elif (self.face_analyzer is not None and self.face_analyzer.available) or self.vlm_composition is not None:
+            elif (self.face_analyzer is not None and self.face_analyzer.available and not getattr(self.face_analyzer, 'gpu_thumbnails', False)) \
+                    or self.vlm_composition is not None:      # face thumbnails cut on the engine need no host pixels
                 imgs = np.empty((n, h, w, 3), np.uint8)
                 e.d2h(imgs, d_rgb)
             d_bgr = e.dev_alloc(n * h * w * 3)
@@ -122,7 +123,8 @@ class BatchScorer:
                 tech_ = TechnicalAnalyzer.analyze_batch(eng, bgr_dev, self.shadow_threshold, self.highlight_threshold, self.mono_threshold)
                 faces_ = None
                 if self.face_analyzer is not None and self.face_analyzer.available:
-                    faces_ = self.face_analyzer.analyze_faces_batch([imgs[i][..., ::-1] for i in range(n)], resident=bgr_dev)
+                    faces_ = self.face_analyzer.analyze_faces_batch([imgs[i][..., ::-1] for i in range(n)] if imgs is not None else None,
+                                                                    resident=bgr_dev)
                 lines_ = leading_lines
                 if lines_ is None and self.detect_lines:      # CompositionAnalyzer.detect_leading_lines (multi_pass.py:702-705), batched
                     from .composition import score_lines

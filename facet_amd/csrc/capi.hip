@@ -1345,6 +1345,43 @@ size_t fe_jpeg_bound(int h, int w) { return (h > 0 && w > 0) ? jpeg_bound(h, w) 
   }                                               \
   return FE_OK;
 
+/* face thumbnails: m crops of a BGR batch, each BOX-resized to its own size and encoded (reference analyzers/face.py:43-82) */
+int fe_face_thumbnails(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int m, const int32_t* img_index, const int32_t* crops,
+                       const int32_t* out_sizes, int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  if (!ctx) return FE_ERR_INVALID;
+  char msg[200] = "";
+  if (!(bgr && n > 0 && h > 0 && w > 0 && h <= 65535 && w <= 65535 && m >= 0 && (m == 0 || (img_index && crops && out_sizes && out && lengths))))
+    snprintf(msg, sizeof msg, "face_thumbnails: bad arguments");
+  else if (quality < 1 || quality > 100)
+    snprintf(msg, sizeof msg, "face_thumbnails: quality %d (1 .. 100)", quality);
+  for (int f = 0; f < m && !msg[0]; ++f) {
+    const int32_t* r = crops + 4 * f;
+    const int32_t ow = out_sizes[2 * f], oh = out_sizes[2 * f + 1];
+    if (img_index[f] < 0 || img_index[f] >= n) snprintf(msg, sizeof msg, "face_thumbnails: face %d refers to image %d of %d", f, img_index[f], n);
+    else if (r[0] < 0 || r[1] < 0 || r[2] > w || r[3] > h || r[0] >= r[2] || r[1] >= r[3])
+      snprintf(msg, sizeof msg, "face_thumbnails: crop %d = [%d,%d,%d,%d] is empty or leaves the %dx%d image", f, r[0], r[1], r[2], r[3], w, h);
+    else if (ow < 1 || oh < 1 || ow > FE_FACE_THUMB_MAX_SIDE || oh > FE_FACE_THUMB_MAX_SIDE)
+      snprintf(msg, sizeof msg, "face_thumbnails: output size %d x %d of face %d (1 .. %d)", ow, oh, f, FE_FACE_THUMB_MAX_SIDE);
+  }
+  if (msg[0]) { ctx->c.err = msg; return FE_ERR_INVALID; }
+  if (m == 0) return FE_OK;
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  C.arena.reset();
+  const uint8_t* d_img = bgr;
+  if (!on_device) {
+    uint8_t* d = (uint8_t*)C.arena.alloc((size_t)n * h * w * 3);
+    FE_HIP(hipMemcpyAsync(d, bgr, (size_t)n * h * w * 3, hipMemcpyHostToDevice, C.stream));
+    d_img = d;
+  }
+  if (!face_thumbnails(C, d_img, n, h, w, m, img_index, crops, out_sizes, quality, out, cap, lengths)) {
+    char b[200];
+    snprintf(b, sizeof(b), "face_thumbnails: a face needs more than the %zu bytes of its output row (fe_jpeg_bound(max oh, max ow) always fits)", cap);
+    throw ThumbOverflow(b);
+  }
+  FE_THUMB_END(ctx)
+}
+
 /* what Pillow's `Image.save(buf, "JPEG", quality=q)` writes for each RGB (bgr = 1: B,G,R bytes) image of the batch */
 int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int quality, uint8_t* out, size_t cap,
                    int32_t* lengths) {

@@ -214,6 +214,11 @@ size_t jpeg_bound(int h, int w);                          // bytes no encode of 
 size_t jpeg_scratch_bytes(int h, int w);      // arena bytes per image of launch_jpeg_encode
 // d_out [n][cap]; d_lengths [n]: bytes written, or < 0 when the image needs more than cap (nothing is stored past cap)
 void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, int quality, uint8_t* d_out, size_t cap, int32_t* d_lengths);
+// face thumbnails (kernels_face_thumb.hip): m crops of a resident BGR batch, each BOX-resized to its own size and encoded; out [m][cap] and
+// lengths [m] are host buffers with fe_jpeg_encode's contract, the index / rectangle / size arrays are host arrays the caller has checked.
+// Returns false when a row was too small for its face.
+bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes,
+                     int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
 // ---- JPEG decode: file bytes -> resident uint8 batch, Pillow's pixels (kernels_jpeg_dec.hip, jpeg_dec_core.h) ----
 void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]);      // the fields of fe_jpeg_info_ex, host only

@@ -231,7 +231,8 @@ __global__ __launch_bounds__(JP_SCAN) void jpeg_stuff_kernel(const uint32_t* __r
 
 size_t jpeg_bound(int h, int w) { return encode_bound(h, w); }
 
-static const Tables* jpeg_tables(Ctx& c, int h, int w, int quality) {
+// also used by kernels_face_thumb.hip, which patches the size fields of the header per image
+const Tables* jpeg_tables(Ctx& c, int h, int w, int quality) {
   const auto key = std::make_tuple(h, w, quality);
   auto it = c.jpeg_cache.find(key);
   if (it != c.jpeg_cache.end()) return (const Tables*)it->second;

@@ -8,12 +8,15 @@ What runs where:
   GPU (engine): SCRFD preprocessing (cv2.resize + canvas + blob), detector graph, threshold/decode; for ALL faces of a batch
       in one call each: similarity-warped 112x112 crops + ArcFace graph, 192x192 crops + 2d106 landmark graph
       (fe_face_detect / fe_face_crops_run, include/facet_engine.h). The reference runs these per image and per face.
+      With `gpu_thumbnails=True` (batch path): the JPEG thumbnails of all accepted faces of a batch in one call (fe_face_thumbnails).
   host (here): sort + NMS over the few candidates, 5-point similarity estimate, landmark back-projection, the reference's own
-      post-processing (gray / Laplacian variance on small ROIs, EAR, aggregation) and JPEG thumbnails.
+      post-processing (gray / Laplacian variance on small ROIs, EAR, aggregation) and, by default and for single images, the JPEG
+      thumbnails (Pillow).
 The three networks are the reference's own files: <root>/models/buffalo_l/{det_10g,2d106det,w600k_r50}.onnx (insightface's
 layout, root='~/.insightface' at face.py:34), parsed by the engine's ONNX runtime; `models=` passes bytes directly (tests use
 standins.synthetic_onnx). insightface internals follow the published package [DEP-KNOWLEDGE]; cv2 is not importable here, so
-gray/Laplacian are restated in numpy and thumbnails are encoded with Pillow (not bit-identical to cv2.imencode).
+gray/Laplacian are restated in numpy and thumbnails are Pillow's BOX resize + JPEG (parity with cv2's INTER_AREA + cv2.imencode is
+unpinned); the engine's thumbnails are byte for byte the Pillow ones.
 """
 import io
 import os
@@ -106,6 +109,50 @@ def laplacian_var(gray):
     p = np.pad(p, ((0, 0), (1, 1)), mode="reflect" if g.shape[1] > 1 else "edge")      # length-1 axis repeats its only sample
     lap = p[:-2, 1:-1] + p[2:, 1:-1] + p[1:-1, :-2] + p[1:-1, 2:] - 4.0 * g
     return float(lap.var())
+
+
+def face_thumbnail_plan(bbox, h, w, size=128, padding=0.3):
+    """Crop rectangle and thumbnail size of a face box in an h x w image: (x0, y0, x1, y1, ow, oh), or None where
+    FaceAnalyzer._crop_face_thumbnail returns None (empty crop, an output side of 0, a box that is no number). The box is truncated
+    with int(), grown by int(padding * its size) on every side and clipped as numpy clips the slice (a negative upper bound counts
+    from the far edge); the longer edge becomes `size`, the shorter what int() leaves (reference analyzers/face.py:52-76)."""
+    try:
+        left, top, right, bottom = (int(v) for v in bbox)
+        grow_x, grow_y = int((right - left) * padding), int((bottom - top) * padding)
+        y0, y1, _ = slice(max(0, top - grow_y), min(h, bottom + grow_y)).indices(h)
+        x0, x1, _ = slice(max(0, left - grow_x), min(w, right + grow_x)).indices(w)
+        if y1 <= y0 or x1 <= x0:
+            return None
+        factor = size / max(y1 - y0, x1 - x0)
+        ow, oh = int((x1 - x0) * factor), int((y1 - y0) * factor)
+    except (ValueError, OverflowError, ZeroDivisionError, TypeError):
+        return None
+    if ow < 1 or oh < 1:
+        return None
+    return x0, y0, x1, y1, ow, oh
+
+
+def face_thumbnails(engine, batch, boxes_per_image, size=128, quality=85, padding=0.3):
+    """JPEG thumbnails of face boxes on the engine: batch = BGR uint8 [n,h,w,3] or (device_ptr, n, h, w); boxes_per_image = one list
+    of (x1, y1, x2, y2) boxes per image. Returns a list per image of bytes | None, each what FaceAnalyzer(thumbnail_size=size,
+    thumbnail_quality=quality)._crop_face_thumbnail(image, box, padding) returns, for all boxes in one fe_face_thumbnails call."""
+    if isinstance(batch, tuple):
+        _, n, h, w = batch
+    else:
+        batch = np.ascontiguousarray(batch, dtype=np.uint8)
+        n, h, w = batch.shape[:3]
+    assert len(boxes_per_image) == n
+    out = [[None] * len(boxes) for boxes in boxes_per_image]
+    where, idx, crops, sizes = [], [], [], []
+    for i, boxes in enumerate(boxes_per_image):
+        for j, box in enumerate(boxes):
+            plan = face_thumbnail_plan(box, h, w, size, padding)
+            if plan is not None:
+                where.append((i, j)); idx.append(i); crops.append(plan[:4]); sizes.append(plan[4:])
+    if where:
+        for (i, j), blob in zip(where, engine.face_thumbnails(batch, idx, crops, sizes, int(quality))):
+            out[i][j] = blob
+    return out
 
 
 class _GraphsHandle:
@@ -272,8 +319,10 @@ class FaceAnalyzer:
     RIGHT_EYE_INDICES = [89, 93, 91, 92, 95, 94]
 
     def __init__(self, device='cuda', min_confidence=0.7, min_face_size=30, thumbnail_size=128, thumbnail_quality=85,
-                 blink_ear_threshold=0.21, min_faces_for_group=4, engine=None, models=None, root='~/.insightface'):
+                 blink_ear_threshold=0.21, min_faces_for_group=4, engine=None, models=None, root='~/.insightface', gpu_thumbnails=False):
         self.available = False
+        # analyze_faces_batch cuts, resizes and encodes the thumbnails of a batch on the engine (fe_face_thumbnails): the same bytes
+        self.gpu_thumbnails = gpu_thumbnails
         self.min_confidence = min_confidence
         self.min_face_size = min_face_size
         self.thumbnail_size = thumbnail_size
@@ -295,20 +344,16 @@ class FaceAnalyzer:
     def _crop_face_thumbnail(self, img_cv, bbox, padding=0.3):
         """JPEG bytes of the face box grown by `padding` of its size on every side (clipped to the image) and scaled so its longer edge
         is `thumbnail_size` - the arithmetic of the reference's helper (analyzers/face.py:52-82: int() truncation of the box, of the
-        padding and of the scaled size), with Pillow doing the resampling and encoding (cv2 is not available: pixels are close to,
-        not identical with, the reference's INTER_AREA + cv2.imencode bytes)."""
+        padding and of the scaled size; face_thumbnail_plan), with Pillow doing the resampling and encoding (cv2 is not available: pixels
+        are close to, not identical with, the reference's INTER_AREA + cv2.imencode bytes). The oracle of fe_face_thumbnails."""
         try:
             from PIL import Image
-            left, top, right, bottom = (int(v) for v in bbox)
-            grow_x, grow_y = int((right - left) * padding), int((bottom - top) * padding)
-            rows = slice(max(0, top - grow_y), min(img_cv.shape[0], bottom + grow_y))
-            cols = slice(max(0, left - grow_x), min(img_cv.shape[1], right + grow_x))
-            crop = img_cv[rows, cols]
-            if crop.size == 0:
+            plan = face_thumbnail_plan(bbox, img_cv.shape[0], img_cv.shape[1], self.thumbnail_size, padding)
+            if plan is None:
                 return None
-            factor = self.thumbnail_size / max(crop.shape[0], crop.shape[1])
-            size = (int(crop.shape[1] * factor), int(crop.shape[0] * factor))            # PIL takes (width, height)
-            thumb = Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).resize(size, Image.BOX)
+            x0, y0, x1, y1, ow, oh = plan
+            crop = img_cv[y0:y1, x0:x1]
+            thumb = Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).resize((ow, oh), Image.BOX)      # PIL takes (width, height)
             out = io.BytesIO()
             thumb.save(out, format='JPEG', quality=int(self.thumbnail_quality))
             return out.getvalue()
@@ -329,7 +374,10 @@ class FaceAnalyzer:
     def analyze_faces_batch(self, images, resident=None):
         """Same-sized BGR images -> list of analyze_faces dicts, with every network run once per batch. resident: optional
         (device_ptr, n, h, w) of the same BGR batch already in device memory - then `images` (any per-image array-likes, e.g.
-        reversed-channel views of an RGB batch) are only read for the thumbnails of the faces found."""
+        reversed-channel views of an RGB batch) are only read for the thumbnails of the faces found, and with `gpu_thumbnails` not at
+        all: `images` may then be None."""
+        if resident is not None and self.gpu_thumbnails:
+            images = [np.broadcast_to(np.uint8(0), (resident[2], resident[3], 3))] * resident[1]      # only their shape is read
         if not self.available or images is None or len(images) == 0:
             return [self._zeros() for _ in (images if images is not None else [])]
         e = self.face_app.engine
@@ -346,20 +394,30 @@ class FaceAnalyzer:
             else:
                 dev = resident
             per_image = self.face_app.get_batch(dev)
-            # first pass only records which ROIs the reference logic looks at; one engine call scans them all
+            # first pass only records which ROIs the reference logic looks at and which faces it accepts; one engine call scans all ROIs
             wanted = []
-            for i, faces in enumerate(per_image):
-                self._post(faces, arr[i], lambda x1, y1, x2, y2, i=i: (wanted.append((i, x1, y1, x2, y2)), (0.0, 0.0))[1], thumbnails=False)
+            first = [self._post(faces, arr[i], lambda x1, y1, x2, y2, i=i: (wanted.append((i, x1, y1, x2, y2)), (0.0, 0.0))[1], thumbnails=False)
+                     for i, faces in enumerate(per_image)]
             table = {}
             if wanted:
                 st = e.roi_laplacian(dev, [r[0] for r in wanted], [r[1:] for r in wanted])
                 for r, (ls, lss, gs, cnt) in zip(wanted, st):
                     mean = ls / cnt
                     table[r] = (lss / cnt - mean * mean, gs / cnt)
+            thumbs = None
+            if self.gpu_thumbnails:      # and one more cuts the thumbnails of the accepted faces from the resident batch
+                thumbs = face_thumbnails(e, dev, [[f['bbox'] for f in r['face_details']] for r in first], self.thumbnail_size,
+                                         self.thumbnail_quality)
         finally:
             if d is not None:
                 e.dev_free(d)
-        return [self._post(faces, arr[i], lambda x1, y1, x2, y2, i=i: table[(i, x1, y1, x2, y2)]) for i, faces in enumerate(per_image)]
+        out = [self._post(faces, arr[i], lambda x1, y1, x2, y2, i=i: table[(i, x1, y1, x2, y2)], thumbnails=thumbs is None)
+               for i, faces in enumerate(per_image)]
+        if thumbs is not None:
+            for r, blobs in zip(out, thumbs):
+                for f, blob in zip(r['face_details'], blobs):
+                    f['thumbnail'] = blob
+        return out
 
     @staticmethod
     def _roi_numpy(img_cv):

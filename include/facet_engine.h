@@ -36,7 +36,7 @@ enum fe_status {
   FE_ERR_NOT_LOADED = -3, /* model weights not committed */
   FE_ERR_CAPACITY = -4   /* the batch does not fit (device memory, arena, KV cache): returned by fe_vlm_preprocess_rgb,
                             fe_vlm_encode_preprocessed, fe_vlm3_encode_images and fe_vlm_prefill_images_padded - retry with fewer images - and by
-                            fe_jpeg_encode / fe_thumbnail_jpeg when an output row is too small for its image */
+                            fe_jpeg_encode / fe_thumbnail_jpeg / fe_face_thumbnails when an output row is too small for its image */
 };
 
 /* Model slots (reference names: models/model_manager.py:393-437 'topiq','clip','samp_net',...). */
@@ -334,6 +334,23 @@ int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr
  * for (w, h, size). out / cap / lengths as fe_jpeg_encode, with cap against fe_jpeg_bound(oh, ow). */
 int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int oh, int ow, int fx, int fy,
                       const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths);
+
+/* Face thumbnails (reference analyzers/face.py:43-82, as facet_amd.face.FaceAnalyzer._crop_face_thumbnail states it with Pillow): for
+ * each of m faces the rectangle crops[f] = (x0, y0, x1, y1; exclusive ends, inside the image, not empty) of image img_index[f] of the
+ * BGR batch is taken as an image of its own, resized to out_sizes[f] = (ow, oh) with PIL's BOX filter (libImaging/Resample.c: horizontal
+ * pass into uint8, then vertical; the filter support is clamped to the crop, not to the photo; up- and downscale) and saved as the RGB
+ * JPEG of fe_jpeg_encode. Byte-exact with `Image.fromarray(crop[:, :, ::-1]).resize((ow, oh), Image.BOX).save(buf, "JPEG",
+ * quality=quality)`. facet_amd.face.face_thumbnail_plan gives rectangle and size for a face box. All faces of a call share three or four
+ * launches; the encoder is one workgroup per face. Faces whose output has at most FE_FACE_THUMB_FUSED_SIDE x FE_FACE_THUMB_FUSED_SIDE
+ * pixels (384 blocks) keep coefficients, code lengths and the bit buffer in LDS; larger outputs (up to FE_FACE_THUMB_MAX_SIDE a side) run
+ * the same workgroup-per-face kernel over arena scratch and give the same bytes. out [m][cap] / lengths [m] are host buffers with
+ * fe_jpeg_encode's contract: FE_ERR_CAPACITY and minus the bytes needed when a row is too small, nothing stored past a row, and
+ * cap = fe_jpeg_bound(max oh, max ow) always fits. m == 0 returns FE_OK; a bad index, rectangle, size or quality returns FE_ERR_INVALID
+ * with a message and launches nothing. A host batch (on_device = 0) is uploaded whole and has to fit the arena. */
+#define FE_FACE_THUMB_FUSED_SIDE 128
+#define FE_FACE_THUMB_MAX_SIDE 8192
+int fe_face_thumbnails(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int m, const int32_t* img_index,
+                       const int32_t* crops, const int32_t* out_sizes, int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
 /* ---- JPEG decode: file bytes -> uint8 batch, Pillow's pixels -------------------------------------------- */
 /* Status of a file. 0: decoded (or decodable). Positive: a kind of file left to the caller's own decoder, nothing was attempted.
