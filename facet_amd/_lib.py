@@ -180,6 +180,11 @@ SIGNATURES = {
     "fe_jpeg_probe_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "fe_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
+    "fe_jpeg_scaled_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fe_jpeg_decode_scaled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    "fe_jpeg_thumbnail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
     "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1213,6 +1218,33 @@ class Engine:
                                             1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)
 
+    def jpeg_thumbnail(self, blobs, scale, plan, quality=80, progressive=False, cap=None):
+        """JPEG files (a list of bytes) of one size -> (list of bytes, status int32 [n]): what `Image.open(f)`,
+        `thumbnail((size, size), LANCZOS)`, `save(buf, "JPEG", quality=quality)` writes for each, with (scale, plan) =
+        facet_amd.thumbnail.thumbnail_plan_jpeg(W, H, size) (fe_jpeg_thumbnail). Scaled decode, reduce, resize and encode run back to back
+        on the device. A file with a non-zero status (jpeg_decode's codes) gives b"". cap as in jpeg_encode, against the plan's size."""
+        if scale not in (1, 2, 4, 8):
+            raise ValueError(f"jpeg_thumbnail: scale {scale!r} (1, 2, 4 or 8)")
+        blobs = [bytes(b) for b in blobs]
+        n = len(blobs)
+        if n == 0:
+            return [], np.zeros(0, np.int32)
+        ptrs = (C.c_char_p * n)(*blobs)
+        lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+        ow, oh = plan.size
+        fx, fy = plan.factors
+        rbox = np.asarray(plan.reduce_box, dtype=np.int32).reshape(4) if plan.reduce_box is not None else None
+        box = np.asarray(plan.resize_box, dtype=np.float32).reshape(4)
+        cap = self.jpeg_bound(oh, ow) if cap is None else int(cap)
+        out = np.empty((n, cap), np.uint8)
+        lengths = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        self._ck(self.lib.fe_jpeg_thumbnail(self.h, ptrs, lens, n, int(plan.src_h), int(plan.src_w), int(scale), FE_JPEG_PROGRESSIVE if progressive else 0,
+                                            oh, ow, fx, fy, rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None,
+                                            box.ctypes.data_as(C.c_void_p), 1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap,
+                                            lengths.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths), status
+
     def face_thumbnails(self, images, img_index, crops, out_sizes, quality=85, cap=None):
         """BGR uint8 [n,h,w,3] (or device tuple) -> list of bytes, one per face: crops int [m,4] (x0,y0,x1,y1 exclusive, inside the image,
         not empty) of images img_index [m], each resized to out_sizes [m,2] = (ow, oh) with PIL's BOX filter and saved as the JPEG
@@ -1256,13 +1288,25 @@ class Engine:
             raise EngineError("fe_jpeg_probe failed")
         return dict(zip(("width", "height", "components", "hsamp", "vsamp", "restart_interval", "orientation", "status"), (int(v) for v in info)))
 
-    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False, progressive=False):
+    @staticmethod
+    def jpeg_scaled_size(h, w, scale):
+        """(h, w) of an H x W file decoded at 1/scale: ceil(H / scale), ceil(W / scale) (fe_jpeg_scaled_size). Host only."""
+        sh, sw = C.c_int32(), C.c_int32()
+        if load_library().fe_jpeg_scaled_size(int(h), int(w), int(scale), C.byref(sh), C.byref(sw)) != 0:
+            raise ValueError(f"jpeg_scaled_size: {h} x {w} at scale {scale} (a positive size; scale 1, 2, 4 or 8)")
+        return sh.value, sw.value
+
+    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False, progressive=False, scale=1):
         """JPEG files (a list of bytes) whose decoded size is h x w -> (pixels, status). pixels: uint8 [n,h,w,3], what Pillow's
         `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives (apply_orientation=False: without the transpose; bgr: B,G,R bytes),
         a host array, or with device=True a (device_ptr, n, h, w) tuple whose buffer the caller releases with dev_free (device=<pointer>
         decodes into the caller's own buffer). status: int32 [n], 0 where the image was decoded; the slot of any other image is left as it
         was (zeros in a host array allocated here, undefined in a device buffer allocated here). progressive=True (fe_jpeg_decode_ex):
-        progressive files that jpeg_probe(blob, progressive=True) gives status 0 are decoded too, in the same call as baseline ones."""
+        progressive files that jpeg_probe(blob, progressive=True) gives status 0 are decoded too, in the same call as baseline ones.
+        scale = 2, 4 or 8 (fe_jpeg_decode_scaled): the decode at 1/scale that `im.draft()` switches on, the pixels of the drafted image;
+        h, w are then the scaled size, jpeg_scaled_size(H, W, scale), exchanged for orientations 5 .. 8 like the full size."""
+        if scale not in (1, 2, 4, 8):
+            raise ValueError(f"jpeg_decode: scale {scale!r} (1, 2, 4 or 8)")
         blobs = [bytes(b) for b in blobs]
         n = len(blobs)
         if n == 0:
@@ -1272,7 +1316,10 @@ class Engine:
         status = np.zeros(n, np.int32)
         def call(on_device, dst):
             head = (self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, on_device)
-            if progressive:
+            if scale != 1:
+                self._ck(self.lib.fe_jpeg_decode_scaled(self.h, ptrs, lens, n, int(h), int(w), int(scale), *head[6:],
+                                                        FE_JPEG_PROGRESSIVE if progressive else 0, dst, status.ctypes.data_as(C.c_void_p)))
+            elif progressive:
                 self._ck(self.lib.fe_jpeg_decode_ex(*head, FE_JPEG_PROGRESSIVE, dst, status.ctypes.data_as(C.c_void_p)))
             else:
                 self._ck(self.lib.fe_jpeg_decode(*head, dst, status.ctypes.data_as(C.c_void_p)))

@@ -1433,7 +1433,7 @@ int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, i
                    uint8_t* dst, int32_t* status) {
   FE_API_BEGIN(ctx)
   FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0, "bad arguments");
-  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, 0, dst, status);
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, 1, bgr, apply_orientation, dst_on_device, 0, dst, status);
   FE_API_END(ctx)
 }
 
@@ -1441,8 +1441,85 @@ int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len
                       int flags, uint8_t* dst, int32_t* status) {
   FE_API_BEGIN(ctx)
   FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~FE_JPEG_PROGRESSIVE), "bad arguments");
-  jpeg_decode_batch(ctx->c, data, len, n, h, w, bgr, apply_orientation, dst_on_device, flags, dst, status);
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, 1, bgr, apply_orientation, dst_on_device, flags, dst, status);
   FE_API_END(ctx)
+}
+
+static bool jpeg_scale_ok(int scale) { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
+
+int fe_jpeg_scaled_size(int h, int w, int scale, int32_t* sh, int32_t* sw) {
+  if (!sh || !sw || h <= 0 || w <= 0 || !jpeg_scale_ok(scale)) return FE_ERR_INVALID;
+  int a, b;
+  jpeg_scaled_size(h, w, scale, &a, &b);
+  *sh = a; *sw = b;
+  return FE_OK;
+}
+
+/* libjpeg's 1/scale decode, which is what Pillow's JpegImageFile.draft() switches on: scale 1 is fe_jpeg_decode_ex */
+int fe_jpeg_decode_scaled(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int bgr, int apply_orientation,
+                          int dst_on_device, int flags, uint8_t* dst, int32_t* status) {
+  if (!ctx) return FE_ERR_INVALID;
+  if (!jpeg_scale_ok(scale)) {
+    ctx->c.err = "jpeg_decode_scaled: scale " + std::to_string(scale) + " (1, 2, 4 or 8)";
+    return FE_ERR_INVALID;
+  }
+  FE_API_BEGIN(ctx)
+  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~FE_JPEG_PROGRESSIVE), "bad arguments");
+  jpeg_decode_batch(ctx->c, data, len, n, h, w, scale, bgr, apply_orientation, dst_on_device, flags, dst, status);
+  FE_API_END(ctx)
+}
+
+/* stored JPEG bytes -> smaller JPEG bytes: `Image.open(f)`, `thumbnail((size, size), LANCZOS)`, `save("JPEG", quality)` (reference
+ * db/maintenance.py:182-272, api/routers/thumbnails.py:54-64) as scaled decode -> reduce -> boxed LANCZOS -> encode on one resident buffer */
+int fe_jpeg_thumbnail(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int flags, int oh, int ow, int fx,
+                      int fy, const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths,
+                      int32_t* status) {
+  if (!ctx) return FE_ERR_INVALID;
+  if (!jpeg_scale_ok(scale)) {
+    ctx->c.err = "jpeg_thumbnail: scale " + std::to_string(scale) + " (1, 2, 4 or 8)";
+    return FE_ERR_INVALID;
+  }
+  FE_API_BEGIN(ctx)
+  FE_CHECK(data && len && out && lengths && status && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1 && !(flags & ~FE_JPEG_PROGRESSIVE),
+           "bad arguments");
+  FE_CHECK((fx == 1 && fy == 1) || reduce_box, "jpeg_thumbnail: reduce factors without a reduce box");
+  ThumbPlan p;
+  p.oh = oh; p.ow = ow; p.fx = fx; p.fy = fy; p.tall = tall;
+  for (int i = 0; i < 4; ++i) { p.rbox[i] = reduce_box ? reduce_box[i] : 0; p.box[i] = resize_box[i]; }
+  Ctx& C = ctx->c;
+  struct DevBuf {
+    uint8_t* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+  } px;                                                      // the decoded batch: outside the arena, which both stages recycle
+  const size_t per = (size_t)h * w * 3;
+  FE_HIP(hipMalloc((void**)&px.p, (size_t)n * per));
+  jpeg_decode_batch(C, data, len, n, h, w, scale, 0, 0, 1, flags, px.p, status);      // no EXIF transpose: Image.open + thumbnail does none
+  std::vector<int> good;
+  for (int i = 0; i < n; ++i) {
+    lengths[i] = 0;
+    if (status[i] == 0) good.push_back(i);
+  }
+  const int ng = (int)good.size();
+  for (int k = 0; k < ng; ++k)                               // close the holes files with a status left: slot good[k] >= k moves down to k
+    if (good[k] != k) FE_HIP(hipMemcpyAsync(px.p + (size_t)k * per, px.p + (size_t)good[k] * per, per, hipMemcpyDeviceToDevice, C.stream));
+  auto spread = [&]() {                                      // rows and lengths 0 .. ng - 1 back to their files' places, last first
+    for (int k = ng - 1; k >= 0; --k) {
+      if (good[k] == k) continue;
+      if (lengths[k] > 0 && (size_t)lengths[k] <= cap) memmove(out + (size_t)good[k] * cap, out + (size_t)k * cap, (size_t)lengths[k]);
+      lengths[good[k]] = lengths[k];
+      lengths[k] = 0;
+    }
+  };
+  if (ng) {
+    try {
+      thumbnail_run(ctx, px.p, ng, h, w, 0, 1, &p, quality, out, cap, lengths);
+    } catch (const ThumbOverflow&) {
+      spread();
+      throw;
+    }
+    spread();
+  }
+  FE_THUMB_END(ctx)
 }
 
 // uint8 images -> the model's normalised NHWC4 input, preprocessing exactly like the reference's PIL/torchvision path

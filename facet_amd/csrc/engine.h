@@ -222,7 +222,8 @@ bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, c
 
 // ---- JPEG decode: file bytes -> resident uint8 batch, Pillow's pixels (kernels_jpeg_dec.hip, jpeg_dec_core.h) ----
 void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]);      // the fields of fe_jpeg_info_ex, host only
-void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device, int flags,
+void jpeg_scaled_size(int h, int w, int scale, int* sh, int* sw);                  // ceil(h / scale), ceil(w / scale): what a scaled decode gives
+void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int bgr, int apply_orientation, int dst_on_device, int flags,
                        uint8_t* dst, int32_t* status);
 
 // ---- perceptual hash + all-pairs Hamming search (kernels_phash.hip) ------------------------------------

@@ -436,6 +436,222 @@ FE_JHD bool idct_block(const int16_t* coef, const uint16_t* q, uint8_t* out, siz
   return wide == 0;
 }
 
+// ---- scaled decode: libjpeg's scale_num / scale_denom = 1 / scale, which is what Pillow's JpegImageFile.draft() asks for ------------------
+// jdmaster.c: the image shrinks to ceil(w / scale) x ceil(h / scale) by transforming every luma block into 8 / scale samples a side
+// instead of 8. A chroma component doubles its own transform size while that still divides the sampling ratio in both directions, so
+// subsampled chroma is scaled up by its IDCT instead of by the upsampler:
+//   scale   4:4:4 / gray   4:2:2 (Y, C, upsampling)        4:2:0 (Y, C, upsampling)
+//     2     4              4, 4, h2v1 fancy                 4, 8, none
+//     4     2              2, 2, h2v1 fancy                 2, 4, none
+//     8     1              1, 1, h2v1 replicated            1, 2, none
+// (jdsample.c switches the triangle filter off when the smallest transform is 1 x 1, and as ever for a component no wider than 2 samples.)
+// The h2v2 upsamplers are never reached at scale > 1 with the samplings parse() takes.
+// The reduced transforms are jidctred.c's: jpeg_idct_islow's fixed point (CONST_BITS 13, PASS1_BITS 2) over the coefficients that survive.
+// 4x4 skips row 4 and column 4 of the block, 2x2 reads rows / columns 0, 1, 3, 5, 7 only, 1x1 is the DC term.
+// Range rule, as idct_block's: libjpeg-turbo's SIMD 4x4 and 2x2 keep dequantised and first-pass values in 16 bits and saturate the
+// samples, the C code wraps 32-bit sums and masks into its table, so a block with a dequantised coefficient (of those the transform
+// reads) or a first-pass value outside int16, or a sample before the table outside [-512, 511], is reported (ST_BAD_COEFFICIENT). The 1x1
+// transform exists in C only and int16 * uint16 cannot wrap: it reports nothing.
+constexpr int UP_NONE = 0, UP_H2V1_FANCY = 1, UP_H2V1_REPLICATE = 2;
+
+struct ScaledGeom {
+  int scale, ow, oh;                   // output size before any EXIF transpose: ceil(w / scale), ceil(h / scale)
+  int ss[3];                           // samples a side that a block of each component becomes
+  int pack[3];                         // horizontally adjacent blocks one work item transforms, so that it stores whole dwords
+  int gw[3];                           // work items per block row: ceil(bw / pack)
+  uint32_t grp_off[4];                 // first work item of each component; [3]: their number
+  int stride[3];                       // bytes per plane row: bw * ss rounded up to a dword
+  uint32_t plane_off[3], plane_bytes;  // a plane is [bh * ss][stride], 16-byte aligned; never more than DecGeom's plane_bytes
+  int cw;                              // real width of a chroma plane (jdmaster.c downsampled_width)
+  int up;                              // UP_*
+};
+
+FE_JHD ScaledGeom make_scaled_geom(const DecGeom& g, int scale) {
+  ScaledGeom s;
+  s.scale = scale;
+  s.ow = (g.w + scale - 1) / scale; s.oh = (g.h + scale - 1) / scale;
+  const int mn = 8 / scale;
+  uint32_t p = 0, n = 0;
+  for (int c = 0; c < 3; ++c) {
+    int ss = mn;
+    const int ch = c ? 1 : g.hs, cv = c ? 1 : g.vs;        // this component's sampling factors
+    while (ss < 8 && (g.hs * mn) % (ch * ss * 2) == 0 && (g.vs * mn) % (cv * ss * 2) == 0) ss *= 2;
+    s.ss[c] = ss;
+    s.pack[c] = ss >= 4 ? 1 : 4 / ss;
+    s.gw[c] = (g.bw[c] + s.pack[c] - 1) / s.pack[c];
+    s.grp_off[c] = n;
+    n += (uint32_t)s.gw[c] * (uint32_t)g.bh[c];
+    s.stride[c] = (g.bw[c] * ss + 3) & ~3;
+    s.plane_off[c] = p;
+    p += ((uint32_t)s.stride[c] * (uint32_t)(g.bh[c] * ss) + 15u) & ~15u;
+  }
+  s.grp_off[3] = n; s.plane_bytes = p;
+  const int in_group = s.ss[1] / mn;                       // chroma samples per output group, against hs luma ones
+  s.up = (g.ncomp == 1 || in_group == g.hs) ? UP_NONE : (mn > 1 ? UP_H2V1_FANCY : UP_H2V1_REPLICATE);
+  s.cw = (g.w * s.ss[1] + g.hs * 8 - 1) / (g.hs * 8);
+  return s;
+}
+
+// 8 coefficients of one block row
+FE_JHD void load_coef_row(const int16_t* p, int32_t* r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 u = *reinterpret_cast<const uint4*>(p);       // a block is 128 bytes, 16-byte aligned
+  const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { r[2 * j] = (int16_t)(wds[j] & 0xFFFFu); r[2 * j + 1] = (int16_t)(wds[j] >> 16); }
+#else
+  for (int j = 0; j < 8; ++j) r[j] = p[j];
+#endif
+}
+
+FE_JHD void store4(uint8_t* p, uint32_t v) {                // p is 4-byte aligned
+#if defined(__HIP_DEVICE_COMPILE__)
+  *reinterpret_cast<uint32_t*>(p) = v;
+#else
+  for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i));
+#endif
+}
+
+// jidctred.c jpeg_idct_4x4's 1-D step on d[0 .. 7] without d[4] -> 4 values scaled up by 2^14
+FE_JHD void idct4_1d(const int32_t* d, int32_t* o) {
+  const int32_t tmp0 = wshl(d[0], 14);
+  const int32_t tmp2 = wadd(wmul(d[2], 15137), wmul(d[6], -6270));
+  const int32_t tmp10 = wadd(tmp0, tmp2), tmp12 = wsub(tmp0, tmp2);
+  const int32_t a = wadd(wadd(wmul(d[7], -1730), wmul(d[5], 11893)), wadd(wmul(d[3], -17799), wmul(d[1], 8697)));
+  const int32_t b = wadd(wadd(wmul(d[7], -4176), wmul(d[5], -4926)), wadd(wmul(d[3], 7373), wmul(d[1], 20995)));
+  o[0] = wadd(tmp10, b); o[3] = wsub(tmp10, b);
+  o[1] = wadd(tmp12, a); o[2] = wsub(tmp12, a);
+}
+
+// jpeg_idct_2x2's: d[0], d[1], d[3], d[5], d[7] -> 2 values scaled up by 2^15
+FE_JHD void idct2_1d(const int32_t* d, int32_t* o) {
+  const int32_t tmp10 = wshl(d[0], 15);
+  const int32_t t = wadd(wadd(wmul(d[7], -5906), wmul(d[5], 6967)), wadd(wmul(d[3], -10426), wmul(d[1], 29692)));
+  o[0] = wadd(tmp10, t); o[1] = wsub(tmp10, t);
+}
+
+// coef, q: natural order. out: 4 rows of 4 samples, one dword each. false: outside the range stated above.
+FE_JHD bool idct_4x4(const int16_t* coef, const uint16_t* q, uint32_t* out) {
+  int32_t ws[4][8];                      // [output row][column]
+  int32_t in[8][8];
+  uint32_t wide = 0;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    if (r == 4) continue;
+    load_coef_row(coef + 8 * r, in[r]);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c == 4) continue;
+      in[r][c] = wmul(in[r][c], q[8 * r + c]);
+      wide |= (uint32_t)wadd(in[r][c], 32768) >> 16;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    if (c == 4) continue;
+    const int32_t d[8] = {in[0][c], in[1][c], in[2][c], in[3][c], 0, in[5][c], in[6][c], in[7][c]};
+    int32_t o[4];
+    idct4_1d(d, o);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ws[r][c] = wdescale(o[r], 12);     // CONST_BITS - PASS1_BITS + 1
+      wide |= (uint32_t)wadd(ws[r][c], 32768) >> 16;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    ws[r][4] = 0;
+    int32_t o[4];
+    idct4_1d(ws[r], o);
+    uint32_t v4 = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int32_t v = wdescale(o[c], 19);      // CONST_BITS + PASS1_BITS + 3 + 1
+      wide |= (uint32_t)wadd(v, 512) >> 10;
+      v4 |= (uint32_t)idct_range_limit(v) << (8 * c);
+    }
+    out[r] = v4;
+  }
+  return wide == 0;
+}
+
+// out: samples (0,0), (0,1), (1,0), (1,1) in the bytes of one word, lowest first
+FE_JHD bool idct_2x2(const int16_t* coef, const uint16_t* q, uint32_t* out) {
+  constexpr int used[5] = {0, 1, 3, 5, 7};
+  int32_t in[8][8];
+  int32_t ws[2][8];
+  uint32_t wide = 0;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const int r = used[i];
+    load_coef_row(coef + 8 * r, in[r]);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const int c = used[j];
+      in[r][c] = wmul(in[r][c], q[8 * r + c]);
+      wide |= (uint32_t)wadd(in[r][c], 32768) >> 16;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int c = used[j];
+    const int32_t d[8] = {in[0][c], in[1][c], 0, in[3][c], 0, in[5][c], 0, in[7][c]};
+    int32_t o[2];
+    idct2_1d(d, o);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      ws[r][c] = wdescale(o[r], 13);     // CONST_BITS - PASS1_BITS + 2
+      wide |= (uint32_t)wadd(ws[r][c], 32768) >> 16;
+    }
+  }
+  uint32_t v4 = 0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    ws[r][2] = ws[r][4] = ws[r][6] = 0;
+    int32_t o[2];
+    idct2_1d(ws[r], o);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int32_t v = wdescale(o[c], 20);      // CONST_BITS + PASS1_BITS + 3 + 2
+      wide |= (uint32_t)wadd(v, 512) >> 10;
+      v4 |= (uint32_t)idct_range_limit(v) << (8 * (2 * r + c));
+    }
+  }
+  *out = v4;
+  return wide == 0;
+}
+
+// jpeg_idct_1x1
+FE_JHD uint8_t idct_1x1(int16_t dc, uint16_t q0) { return idct_range_limit(wdescale(wmul(dc, q0), 3)); }
+
+// One work item of the scaled transform: blocks gx * pack .. of a block row whose first block is at `row` (bw blocks of 64 coefficients),
+// each transformed into ss x ss samples of the plane rows starting at `out` (the block row's first sample). Blocks past bw give zero
+// bytes inside the row's padding, so every store is a whole dword.
+FE_JHD bool idct_group(const int16_t* row, int gx, int bw, int ss, const uint16_t* q, uint8_t* out, size_t stride) {
+  if (ss == 8) return idct_block(row + (size_t)gx * 64, q, out + (size_t)gx * 8, stride);
+  if (ss == 4) {
+    uint32_t v[4];
+    const bool ok = idct_4x4(row + (size_t)gx * 64, q, v);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) store4(out + r * stride + (size_t)gx * 4, v[r]);
+    return ok;
+  }
+  if (ss == 2) {
+    uint32_t v[2] = {0, 0};
+    bool ok = true;
+    for (int j = 0; j < 2; ++j)
+      if (2 * gx + j < bw) ok &= idct_2x2(row + (size_t)(2 * gx + j) * 64, q, v + j);
+    store4(out + (size_t)gx * 4, (v[0] & 0xFFFFu) | (v[1] << 16));
+    store4(out + stride + (size_t)gx * 4, (v[0] >> 16) | (v[1] & 0xFFFF0000u));
+    return ok;
+  }
+  uint32_t v = 0;
+  for (int j = 0; j < 4; ++j)
+    if (4 * gx + j < bw) v |= (uint32_t)idct_1x1(row[(size_t)(4 * gx + j) * 64], q[0]) << (8 * j);
+  store4(out + (size_t)gx * 4, v);
+  return true;
+}
+
 // ---- upsampling (jdsample.c with do_fancy_upsampling) + jdcolor.c ---------------------------------------------------------------------
 // Chroma sample for pixel (x, y) of a component subsampled hs x vs; p: its plane, stride bytes per row; cw x ch: its real extent.
 // A component no wider than 2 samples is replicated (jinit_upsampler takes the fancy routines for downsampled_width > 2 only).
@@ -476,6 +692,21 @@ FE_JHD void pixel_rgb(const uint8_t* planes, const DecGeom& g, int x, int y, uin
   const int cb = chroma_at(planes + g.plane_off[1], g.bw[1] * 8, g.cw, g.ch, g.hs, g.vs, x, y);
   const int cr = chroma_at(planes + g.plane_off[2], g.bw[2] * 8, g.cw, g.ch, g.hs, g.vs, x, y);
   ycc_to_rgb(yv, cb, cr, rgb, rgb + 1, rgb + 2);
+}
+
+// pixel (x, y) of the ceil(w / scale) x ceil(h / scale) image from the planes of the scaled transform
+FE_JHD void pixel_rgb_scaled(const uint8_t* planes, const DecGeom& g, const ScaledGeom& s, int x, int y, uint8_t* rgb) {
+  const int yv = planes[s.plane_off[0] + (size_t)y * s.stride[0] + x];
+  if (g.ncomp == 1) { rgb[0] = rgb[1] = rgb[2] = (uint8_t)yv; return; }
+  int cc[2];
+#pragma unroll
+  for (int c = 1; c < 3; ++c) {
+    const uint8_t* p = planes + s.plane_off[c];
+    if (s.up == UP_NONE) cc[c - 1] = p[(size_t)y * s.stride[c] + x];
+    else if (s.up == UP_H2V1_REPLICATE) cc[c - 1] = p[(size_t)y * s.stride[c] + (x >> 1)];
+    else cc[c - 1] = chroma_at(p, s.stride[c], s.cw, 0, 2, 1, x, y);
+  }
+  ycc_to_rgb(yv, cc[0], cc[1], rgb, rgb + 1, rgb + 2);
 }
 
 // where pixel (x, y) of a w x h image lands under EXIF orientation o (ImageOps.exif_transpose): pixel index in the output, whose width is
@@ -912,16 +1143,18 @@ inline void build_tables(const Parsed& P, DecTables& T) {
 }
 
 // The whole decode of one parsed file on the host, stage by stage as the kernels run it. buf: the file copied into a 16-byte aligned
-// buffer padded to a multiple of 16 bytes. out: [oh][ow][3] with (oh, ow) = (height, width), exchanged for orientations 5 .. 8 when
-// apply_orientation. Returns the status; out is written only for 0. An incomplete progression has its scans run and its blocks transformed
-// all the same, so that a stream that is corrupt as well is reported as that; it keeps ST_OTHER when nothing is found.
-inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int apply_orientation, uint8_t* out) {
+// buffer padded to a multiple of 16 bytes. scale: 1, 2, 4 or 8, which the caller has checked. out:
+// [oh][ow][3] with (oh, ow) = (ceil(height / scale), ceil(width / scale)), exchanged for orientations 5 .. 8 when apply_orientation.
+// Returns the status; out is written only for 0. An incomplete progression has its scans run and its blocks transformed all the same, so
+// that a stream that is corrupt as well is reported as that; it keeps ST_OTHER when nothing is found.
+inline int32_t decode_host_scaled(const Parsed& P, const uint8_t* buf, int scale, int bgr, int apply_orientation, uint8_t* out) {
   if (P.status != ST_OK && !P.incomplete) return P.status;
   const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+  const ScaledGeom sg = make_scaled_geom(g, scale);
   DecTables* T = new DecTables;
   build_tables(P, *T);
   std::vector<int16_t> coef((size_t)g.nblk * 64, 0);
-  std::vector<uint8_t> planes(g.plane_bytes);
+  std::vector<uint8_t> planes(scale == 1 ? g.plane_bytes : sg.plane_bytes);
   uint8_t td[3], ta[3];
   for (int c = 0; c < 3; ++c) { td[c] = P.comp[c].td; ta[c] = P.comp[c].ta; }
   const uint32_t mcus = (uint32_t)g.mw * g.mh, per = P.ri ? (uint32_t)P.ri : mcus;
@@ -944,7 +1177,7 @@ inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int app
     const uint32_t m0 = (uint32_t)k * per;
     st = decode_segment(br, g, T->huff, td, ta, m0, mcus - m0 < per ? mcus - m0 : per, coef.data(), kNatural);
   }
-  if (st == ST_OK) {
+  if (st == ST_OK && scale == 1) {
     for (int c = 0; c < g.ncomp; ++c)
       for (int by = 0; by < g.bh[c]; ++by)
         for (int bx = 0; bx < g.bw[c]; ++bx)
@@ -952,19 +1185,33 @@ inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int app
                           planes.data() + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, (size_t)g.bw[c] * 8))
             st = ST_BAD_COEFFICIENT;
   }
+  if (st == ST_OK && scale != 1) {
+    for (int c = 0; c < g.ncomp; ++c)
+      for (int by = 0; by < g.bh[c]; ++by)
+        for (int gx = 0; gx < sg.gw[c]; ++gx)
+          if (!idct_group(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c]) * 64, gx, g.bw[c], sg.ss[c], T->q[P.comp[c].tq],
+                          planes.data() + sg.plane_off[c] + (size_t)by * sg.ss[c] * sg.stride[c], (size_t)sg.stride[c]))
+            st = ST_BAD_COEFFICIENT;
+  }
   if (st == ST_OK && P.incomplete) st = ST_OTHER;
   if (st == ST_OK) {
     const int o = apply_orientation ? P.orientation : 1;
-    for (int y = 0; y < g.h; ++y)
-      for (int x = 0; x < g.w; ++x) {
+    const int ow = scale == 1 ? g.w : sg.ow, oh = scale == 1 ? g.h : sg.oh;
+    for (int y = 0; y < oh; ++y)
+      for (int x = 0; x < ow; ++x) {
         uint8_t rgb[3];
-        pixel_rgb(planes.data(), g, x, y, rgb);
-        uint8_t* p = out + oriented_index(o, g.w, g.h, x, y) * 3;
+        if (scale == 1) pixel_rgb(planes.data(), g, x, y, rgb);
+        else pixel_rgb_scaled(planes.data(), g, sg, x, y, rgb);
+        uint8_t* p = out + oriented_index(o, ow, oh, x, y) * 3;
         p[0] = rgb[bgr ? 2 : 0]; p[1] = rgb[1]; p[2] = rgb[bgr ? 0 : 2];
       }
   }
   delete T;
   return st;
+}
+
+inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int apply_orientation, uint8_t* out) {
+  return decode_host_scaled(P, buf, 1, bgr, apply_orientation, out);
 }
 }  // namespace jpegdec
 }  // namespace fe

@@ -10,6 +10,10 @@
 //   C idct:    one lane per block: dequantise, integer slow IDCT, 8 rows of 8 samples into the component's plane (padded to the block grid)
 //   D colour:  one lane per 4 pixels of a row: triangle-filter upsampling, YCbCr -> RGB, store as RGB or BGR at the address the EXIF
 //              orientation gives (all 8 cases; there is no transpose pass)
+// A scaled decode (fe_jpeg_decode_scaled, scale 2 / 4 / 8: libjpeg's 1/scale, which Pillow's draft() asks for) shares A and B and has a
+// stage C of its own: a block becomes 4 x 4, 2 x 2 or 1 x 1 samples (chroma up to twice the luma's size, jpeg_dec_core.h's table), the
+// planes are laid out per component, and a lane takes one block, two 2 x 2 blocks or four 1 x 1 blocks so that it stores whole dwords.
+// Stage D is the same kernel instantiated over that layout.
 // A segment's error (bad code, data that ends early) and a block outside the range honest coefficients reach become the image's negative
 // status by atomicMin; stage D leaves the slot of such an image untouched.
 #include <chrono>
@@ -128,37 +132,68 @@ __global__ __launch_bounds__(JD_THREADS) void jpegdec_idct_kernel(const DevImage
     atomicMin(status + blockIdx.y, (int32_t)ST_BAD_COEFFICIENT);
 }
 
-// dst [slots][oh][ow][3]. A lane takes pixels 4 t .. 4 t + 3 of a source row. Where the destination keeps the source's row direction
+// Stage C of a scaled decode. Work items are numbered per component (ScaledGeom.grp_off); item (by, gx) of a component transforms blocks
+// gx * pack .. gx * pack + pack - 1 of block row by into the rows by * ss .. of that component's plane (idct_group).
+__global__ __launch_bounds__(JD_THREADS) void jpegdec_idct_scaled_kernel(const DevImage* __restrict__ imgs, const DecTables* __restrict__ tabs,
+                                                                         const int16_t* __restrict__ coef, uint8_t* __restrict__ planes,
+                                                                         int32_t* __restrict__ status, int scale) {
+  __shared__ uint16_t q[4][64];
+  const DevImage im = imgs[blockIdx.y];
+  const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  const ScaledGeom sg = make_scaled_geom(g, scale);
+  if (blockIdx.x * JD_THREADS >= sg.grp_off[3]) return;      // uniform over the workgroup
+  (&q[0][0])[threadIdx.x] = (&tabs[blockIdx.y].q[0][0])[threadIdx.x];
+  __syncthreads();
+  const uint32_t i = blockIdx.x * JD_THREADS + threadIdx.x;
+  if (i >= sg.grp_off[3]) return;
+  const int c = (g.ncomp == 3 && i >= sg.grp_off[1]) ? (i >= sg.grp_off[2] ? 2 : 1) : 0;
+  const uint32_t li = i - sg.grp_off[c];
+  const uint32_t by = li / (uint32_t)sg.gw[c], gx = li % (uint32_t)sg.gw[c];
+  const int16_t* row = coef + im.coef_off + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c]) * 64;
+  uint8_t* out = planes + im.plane_off + sg.plane_off[c] + (size_t)by * sg.ss[c] * sg.stride[c];
+  if (!idct_group(row, (int)gx, g.bw[c], sg.ss[c], q[im.tq[c] & 3], out, (size_t)sg.stride[c]))
+    atomicMin(status + blockIdx.y, (int32_t)ST_BAD_COEFFICIENT);
+}
+
+// dst [slots][oh][ow][3]. A lane takes pixels 4 t .. 4 t + 3 of a source row. SCALED: the source is the ceil(w / scale) x ceil(h / scale)
+// image in ScaledGeom's planes; otherwise scale is 1 and unused. Where the destination keeps the source's row direction
 // (orientation 1 or 4) and rows are a whole number of dwords, the 12 bytes go out as three dwords; otherwise byte by byte.
+template <bool SCALED>
 __global__ __launch_bounds__(JD_THREADS) void jpegdec_colour_kernel(const DevImage* __restrict__ imgs, const uint8_t* __restrict__ planes,
                                                                     const int32_t* __restrict__ status, uint8_t* __restrict__ dst, int oh, int ow,
-                                                                    int bgr, int apply_orientation, int dst_aligned) {
+                                                                    int bgr, int apply_orientation, int dst_aligned, int scale) {
   const DevImage im = imgs[blockIdx.y];
   if (status[blockIdx.y] != 0) return;
-  const int w4 = (im.w + 3) >> 2;
+  const int sw = SCALED ? (im.w + scale - 1) / scale : im.w, sh = SCALED ? (im.h + scale - 1) / scale : im.h;
+  const int w4 = (sw + 3) >> 2;
   const uint32_t i = blockIdx.x * JD_THREADS + threadIdx.x;
-  if (i >= (uint32_t)w4 * (uint32_t)im.h) return;
+  if (i >= (uint32_t)w4 * (uint32_t)sh) return;
   const int y = (int)(i / (uint32_t)w4), x0 = (int)(i % (uint32_t)w4) * 4;
   const DecGeom g = make_dec_geom(im.w, im.h, im.ncomp, im.hs, im.vs);
+  ScaledGeom sg;
+  if constexpr (SCALED) sg = make_scaled_geom(g, scale);
   const uint8_t* pl = planes + im.plane_off;
   const int o = apply_orientation ? im.orientation : 1;
   uint8_t* out = dst + (size_t)im.slot * oh * ow * 3;
   const int ir = bgr ? 2 : 0, ib = bgr ? 0 : 2;
   uint8_t px[12];
-  const int nx = min(4, im.w - x0);
+  const int nx = min(4, sw - x0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     uint8_t rgb[3] = {0, 0, 0};
-    if (j < nx) pixel_rgb(pl, g, x0 + j, y, rgb);
+    if (j < nx) {
+      if constexpr (SCALED) pixel_rgb_scaled(pl, g, sg, x0 + j, y, rgb);
+      else pixel_rgb(pl, g, x0 + j, y, rgb);
+    }
     px[3 * j + ir] = rgb[0]; px[3 * j + 1] = rgb[1]; px[3 * j + ib] = rgb[2];
   }
-  if ((o == 1 || o == 4) && dst_aligned && (im.w & 3) == 0) {
-    uint32_t* p = reinterpret_cast<uint32_t*>(out + oriented_index(o, im.w, im.h, x0, y) * 3);
+  if ((o == 1 || o == 4) && dst_aligned && (sw & 3) == 0) {
+    uint32_t* p = reinterpret_cast<uint32_t*>(out + oriented_index(o, sw, sh, x0, y) * 3);
 #pragma unroll
     for (int j = 0; j < 3; ++j) p[j] = px[4 * j] | ((uint32_t)px[4 * j + 1] << 8) | ((uint32_t)px[4 * j + 2] << 16) | ((uint32_t)px[4 * j + 3] << 24);
   } else {
     for (int j = 0; j < nx; ++j) {
-      uint8_t* p = out + oriented_index(o, im.w, im.h, x0 + j, y) * 3;
+      uint8_t* p = out + oriented_index(o, sw, sh, x0 + j, y) * 3;
       p[0] = px[3 * j]; p[1] = px[3 * j + 1]; p[2] = px[3 * j + 2];
     }
   }
@@ -196,10 +231,15 @@ void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]) {
   out[0] = P.width; out[1] = P.height; out[2] = P.ncomp; out[3] = P.hs; out[4] = P.vs; out[5] = P.ri; out[6] = P.orientation; out[7] = P.status;
 }
 
-// dst: [n][h][w][3] on the device or on the host; status: host [n]. See fe_jpeg_decode.
-void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
-                       int flags, uint8_t* dst, int32_t* status) {
+void jpeg_scaled_size(int h, int w, int scale, int* sh, int* sw) {
+  *sh = (h + scale - 1) / scale; *sw = (w + scale - 1) / scale;
+}
+
+// dst: [n][h][w][3] on the device or on the host; status: host [n]. scale: 1, 2, 4 or 8; h, w are the scaled size. See fe_jpeg_decode_scaled.
+void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int bgr, int apply_orientation,
+                       int dst_on_device, int flags, uint8_t* dst, int32_t* status) {
   FE_CHECK(n > 0 && h > 0 && w > 0 && h <= 65535 && w <= 65535, "jpeg_decode: bad shape %d x %d x %d", n, h, w);
+  FE_CHECK(scale == 1 || scale == 2 || scale == 4 || scale == 8, "jpeg_decode: scale %d (1, 2, 4, 8)", scale);
   const auto t_parse = std::chrono::steady_clock::now();
   std::vector<Parsed> parsed((size_t)n);
   std::vector<int> todo;
@@ -209,7 +249,9 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     parse(data[i], len[i], P, flags);
     if (P.status == ST_OK || P.incomplete) {
       const bool swap = apply_orientation && P.orientation >= 5;
-      if ((swap ? P.width : P.height) != h || (swap ? P.height : P.width) != w) { P.status = ST_BAD_DIMENSIONS; P.incomplete = false; }
+      int sh, sw;
+      jpeg_scaled_size(P.height, P.width, scale, &sh, &sw);
+      if ((swap ? sw : sh) != h || (swap ? sh : sw) != w) { P.status = ST_BAD_DIMENSIONS; P.incomplete = false; }
     }
     status[i] = P.status;
     if (P.status == ST_OK || P.incomplete) todo.push_back(i);      // an incomplete progression has its scans run: it may be corrupt as well
@@ -269,7 +311,7 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
     HuffDec* h_pool = (HuffDec*)(hb + o_pool);
     int32_t* h_st0 = (int32_t*)(hb + o_st0);                 // what each image's status starts from
     size_t coef_el = 0, plane_b = 0, seg_at = 0, byte_at = 0, scan_at = 0, pool_at = 0;
-    uint32_t max_groups = 0, max_blk = 1;
+    uint32_t max_groups = 0, max_blk = 1;                    // max_blk: work items of stage C, which are blocks at scale 1
     uint32_t scan_groups[MAX_SCANS] = {};                    // [s]: workgroups per image of the launch for scan s, 0: no image has one
     bool held_back = false;
     for (int k = 0; k < nd; ++k) {
@@ -311,7 +353,7 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
       coef_el += (size_t)g.nblk * 64;
       plane_b += up256(g.plane_bytes);
       max_groups = std::max(max_groups, (D.nseg + JD_WAVE - 1) / JD_WAVE);
-      max_blk = std::max(max_blk, g.nblk);
+      max_blk = std::max(max_blk, scale == 1 ? g.nblk : make_scaled_geom(g, scale).grp_off[3]);
     }
     memset(hb + o_bytes + byte_at, 0, 16);
     FE_CHECK(max_groups <= 65535, "jpeg_decode: an image has too many restart intervals");
@@ -340,13 +382,22 @@ void jpeg_decode_batch(Ctx& c, const uint8_t* const* data, const size_t* len, in
                          (const uint32_t*)(d_blob + o_s1), (const uint8_t*)(d_blob + o_bytes), d_coef, d_status, (uint32_t)s);
     tm.end("jpeg_decode B: entropy", (double)(blob - o_bytes));
     tm.begin();
-    hipLaunchKernelGGL(jpegdec_idct_kernel, dim3((max_blk + JD_THREADS - 1) / JD_THREADS, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, d_tab,
-                       (const int16_t*)d_coef, d_planes, d_status);
+    if (scale == 1)
+      hipLaunchKernelGGL(jpegdec_idct_kernel, dim3((max_blk + JD_THREADS - 1) / JD_THREADS, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, d_tab,
+                         (const int16_t*)d_coef, d_planes, d_status);
+    else
+      hipLaunchKernelGGL(jpegdec_idct_scaled_kernel, dim3((max_blk + JD_THREADS - 1) / JD_THREADS, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img,
+                         d_tab, (const int16_t*)d_coef, d_planes, d_status, scale);
     tm.end("jpeg_decode C: idct", (double)coef_el * 2);
     tm.begin();
     const unsigned quads = (unsigned)(((size_t)((std::max(h, w) + 3) / 4) * std::max(h, w) + JD_THREADS - 1) / JD_THREADS);      // either orientation
-    hipLaunchKernelGGL(jpegdec_colour_kernel, dim3(quads, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, (const uint8_t*)d_planes,
-                       (const int32_t*)d_status, d_out, h, w, bgr ? 1 : 0, apply_orientation ? 1 : 0, (int)(((uintptr_t)d_out & 3) == 0 && (out_b & 3) == 0));
+    const int aligned = (int)(((uintptr_t)d_out & 3) == 0 && (out_b & 3) == 0);
+    if (scale == 1)
+      hipLaunchKernelGGL(jpegdec_colour_kernel<false>, dim3(quads, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, (const uint8_t*)d_planes,
+                         (const int32_t*)d_status, d_out, h, w, bgr ? 1 : 0, apply_orientation ? 1 : 0, aligned, 1);
+    else
+      hipLaunchKernelGGL(jpegdec_colour_kernel<true>, dim3(quads, (unsigned)nd), dim3(JD_THREADS), 0, c.stream, d_img, (const uint8_t*)d_planes,
+                         (const int32_t*)d_status, d_out, h, w, bgr ? 1 : 0, apply_orientation ? 1 : 0, aligned, scale);
     tm.end("jpeg_decode D: colour", (double)nd * out_b);
     FE_HIP(hipGetLastError());
     st_host.resize((size_t)nd);

@@ -39,11 +39,17 @@ def read_blob(path_or_blob):
         return f.read()
 
 
-def pillow_image(blob):
-    """utils/image_loading.py:100-103 on the file's bytes -> PIL RGB image, or None where the reference gives up."""
+def pillow_image(blob, scale=1):
+    """utils/image_loading.py:100-103 on the file's bytes -> PIL RGB image, or None where the reference gives up. scale 2, 4, 8: a JPEG
+    file is drafted to that scale first (what JpegImageFile.draft() sets when it chooses it); other formats have no draft mode."""
     from PIL import Image, ImageOps
     try:
         im = Image.open(io.BytesIO(blob))
+        if scale != 1 and im.format == 'JPEG' and len(im.tile) == 1 and not im.decoderconfig:
+            w, h = im.size
+            im._size = (-(-w // scale), -(-h // scale))
+            im.tile = [im.tile[0]._replace(extents=(0, 0) + im.size)]
+            im.decoderconfig = (scale, 0)
         im = ImageOps.exif_transpose(im)
         if im.mode != 'RGB':
             im = im.convert('RGB')
@@ -54,16 +60,19 @@ def pillow_image(blob):
         return None
 
 
-def pillow_rgb(blob):
-    im = pillow_image(blob)
+def pillow_rgb(blob, scale=1):
+    im = pillow_image(blob, scale)
     return None if im is None else np.asarray(im, dtype=np.uint8)
 
 
-def decode_groups(engine, blobs, device=False, progressive=False):
+def decode_groups(engine, blobs, device=False, progressive=False, scale=1):
     """Probe every file, group the decodable ones by output size and decode each group with one fe_jpeg_decode. progressive: a file the
     probe calls progressive (status 1) is probed again for the progressive decoder and, when that takes it, joins the group of its size.
     -> (groups, rest): groups = [(indices, pixels)], pixels a uint8 [k,h,w,3] array or with device=True a (device_ptr, k, h, w) tuple the
-    caller frees, holding exactly the images of `indices` in that order; rest = the indices left for Pillow."""
+    caller frees, holding exactly the images of `indices` in that order; rest = the indices left for Pillow. scale 2, 4, 8: the decode
+    at 1/scale (Engine.jpeg_decode's scale), grouped by scaled size."""
+    if scale not in (1, 2, 4, 8):
+        raise ValueError(f"decode_groups: scale {scale!r} (1, 2, 4 or 8)")
     sizes, rest = {}, []
     for i, b in enumerate(blobs):
         info = engine.jpeg_probe(b)
@@ -72,12 +81,14 @@ def decode_groups(engine, blobs, device=False, progressive=False):
         if info['status'] != 0:
             rest.append(i)
             continue
-        h, w = info['height'], info['width']
+        h, w = -(-info['height'] // scale), -(-info['width'] // scale)
         if info['orientation'] >= 5:
             h, w = w, h
         sizes.setdefault((h, w), []).append(i)
     groups = []
     flag = dict(progressive=True) if progressive else {}
+    if scale != 1:
+        flag['scale'] = scale
     for (h, w), idx in sizes.items():
         px, status = engine.jpeg_decode([blobs[i] for i in idx], h, w, device=device, **flag)
         good = [k for k in range(len(idx)) if status[k] == 0]
@@ -97,17 +108,18 @@ def decode_groups(engine, blobs, device=False, progressive=False):
     return groups, sorted(rest)
 
 
-def decode_jpegs(engine, blobs, progressive=False):
+def decode_jpegs(engine, blobs, progressive=False, scale=1):
     """The RGB pixels of every file (bytes), as uint8 [h,w,3] arrays in input order: what load_image_from_path's pil_img holds, None
-    where it fails. progressive: decode complete progressive files on the GPU too; the result is the same either way."""
+    where it fails. progressive: decode complete progressive files on the GPU too; the result is the same either way. scale 2, 4, 8:
+    the pixels of the file drafted to 1/scale (libjpeg's scaled decode), from the GPU or from Pillow alike; grayscale comes back as RGB."""
     blobs = [bytes(b) for b in blobs]
     out = [None] * len(blobs)
-    groups, rest = decode_groups(engine, blobs, device=False, progressive=progressive)
+    groups, rest = decode_groups(engine, blobs, device=False, progressive=progressive, scale=scale)
     for idx, px in groups:
         for k, i in enumerate(idx):
             out[i] = px[k]
     for i in rest:
-        out[i] = pillow_rgb(blobs[i])
+        out[i] = pillow_rgb(blobs[i], scale)
     return out
 
 

@@ -36,7 +36,7 @@ enum fe_status {
   FE_ERR_NOT_LOADED = -3, /* model weights not committed */
   FE_ERR_CAPACITY = -4   /* the batch does not fit (device memory, arena, KV cache): returned by fe_vlm_preprocess_rgb,
                             fe_vlm_encode_preprocessed, fe_vlm3_encode_images and fe_vlm_prefill_images_padded - retry with fewer images - and by
-                            fe_jpeg_encode / fe_thumbnail_jpeg / fe_face_thumbnails when an output row is too small for its image */
+                            fe_jpeg_encode / fe_thumbnail_jpeg / fe_jpeg_thumbnail / fe_face_thumbnails when an output row is too small for its image */
 };
 
 /* Model slots (reference names: models/model_manager.py:393-437 'topiq','clip','samp_net',...). */
@@ -395,6 +395,26 @@ typedef struct { int32_t width, height, components, hsamp, vsamp, restart_interv
 int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info);
 int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation,
                       int dst_on_device, int flags, uint8_t* dst, int32_t* status);
+/* The decode at 1/scale that Pillow's `JpegImageFile.draft()` switches on (libjpeg's scale_num / scale_denom), which `Image.thumbnail`
+ * calls first on an image that comes from a JPEG file. scale: 1, 2, 4 or 8, anything else returns FE_ERR_INVALID and launches nothing;
+ * scale 1 is fe_jpeg_decode_ex bit for bit. h, w: the scaled size, ceil(H / scale) x ceil(W / scale) (fe_jpeg_scaled_size), exchanged
+ * after the EXIF transpose as in fe_jpeg_decode. The pixels are those of `im.draft(None, ...); im.convert('RGB')` once draft() has chosen
+ * this scale: luma blocks go through libjpeg's 4x4 / 2x2 / 1x1 inverse transforms (jidctred.c), and a subsampled chroma component is
+ * scaled up by a transform up to twice that size instead of by the upsampler (jdmaster.c), so this is not the full decode followed by a
+ * reduce. Entropy stage, parser, flags and status codes are fe_jpeg_decode_ex's; progressive files under the flag take the same stages. */
+int fe_jpeg_scaled_size(int h, int w, int scale, int32_t* scaled_h, int32_t* scaled_w);
+int fe_jpeg_decode_scaled(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int bgr,
+                          int apply_orientation, int dst_on_device, int flags, uint8_t* dst, int32_t* status);
+/* Stored JPEG bytes -> smaller JPEG bytes (reference db/maintenance.py:182-272 export_viewer_db, api/routers/thumbnails.py:54-64
+ * _resize_thumbnail): `Image.open(f)`, `img.thumbnail((size, size), LANCZOS)`, `img.save(buf, "JPEG", quality=quality)` for n files of
+ * one source size, as fe_jpeg_decode_scaled (no EXIF transpose: Image.open + thumbnail does none) -> reduce -> boxed LANCZOS resize ->
+ * encode on one resident buffer. scale and the plan (oh .. tall, fe_thumbnail_jpeg's arguments) are
+ * facet_amd.thumbnail.thumbnail_plan_jpeg's for (W, H, size); h, w the scaled size the plan is stated on. flags: fe_jpeg_decode_ex's.
+ * status [n]: the decode's; a file with a non-zero status gets lengths[i] = 0 and its row is left alone. out / cap / lengths otherwise as
+ * fe_thumbnail_jpeg, FE_ERR_CAPACITY included. */
+int fe_jpeg_thumbnail(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int flags, int oh, int ow,
+                      int fx, int fy, const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap,
+                      int32_t* lengths, int32_t* status);
 
 /* ---- image-level entry points (uint8 HWC images in, per-image results out) ------------------------------ */
 /* CLIP from raw RGB images: open_clip eval transform on the GPU (PIL-bicubic shorter side -> 224, center crop 224,
