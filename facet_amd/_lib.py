@@ -93,6 +93,9 @@ SIGNATURES = {
     "fe_op_adaptive_avgpool": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _f32p]),
     "fe_op_layernorm": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_float, _f32p]),
+    "fe_op_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "fe_op_mha": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
+                            C.c_int, _f32p]),
     "fe_op_vlm_select": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
@@ -537,6 +540,39 @@ class Engine:
         rows, d = x.shape
         y = np.empty_like(x)
         self._ck(self.lib.fe_op_layernorm(self.h, xp, rows, d, gp, bp, eps, y.ctypes.data_as(_f32p)))
+        return y
+
+    def attention(self, q, k, v, bv=None, causal=False, form=0):
+        """Test hook of the fused head_dim-64 attention kernels: q [B, Lq, H*64], k / v [B, Lk, H*64], bv [H*64] ->
+        softmax(q k^T) v + bv per head (q as the kernel receives it, already scaled). form 1: the split-f16 kernel (f16 precision)."""
+        q, qp = _f32(q)
+        k, kp = _f32(k)
+        v, vp = _f32(v)
+        B, Lq, d = q.shape
+        Lk = k.shape[1]
+        assert d % 64 == 0 and k.shape == (B, Lk, d) and v.shape == (B, Lk, d)
+        bv, bp = _f32(np.zeros(d, np.float32) if bv is None else bv)
+        assert bv.shape == (d,)
+        o = np.empty((B, Lq, d), np.float32)
+        self._ck(self.lib.fe_op_attention(self.h, qp, kp, vp, bp, B, d // 64, Lq, Lk, int(causal), int(form), o.ctypes.data_as(_f32p)))
+        return o
+
+    def mha(self, x_q, x_kv, heads, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, res=None, causal=False):
+        """Test hook of the nn.MultiheadAttention wiring (batch_first): x_q [B, Lq, d], x_kv [B, Lk, d] -> res + out_proj(attention)."""
+        x_q, qp = _f32(x_q)
+        x_kv, kp = _f32(x_kv)
+        B, Lq, d = x_q.shape
+        Lk = x_kv.shape[1]
+        assert x_kv.shape == (B, Lk, d)
+        w = [_f32(a) for a in (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias)]
+        assert w[0][0].shape == (3 * d, d) and w[1][0].shape == (3 * d,) and w[2][0].shape == (d, d) and w[3][0].shape == (d,)
+        rp = None
+        if res is not None:
+            res, rp = _f32(res)
+            assert res.shape == x_q.shape
+        y = np.empty((B, Lq, d), np.float32)
+        self._ck(self.lib.fe_op_mha(self.h, qp, kp, B, Lq, Lk, d, int(heads), w[0][1], w[1][1], w[2][1], w[3][1], rp, int(causal),
+                                    y.ctypes.data_as(_f32p)))
         return y
 
     def set_conv_variant(self, v):

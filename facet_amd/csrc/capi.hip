@@ -713,6 +713,114 @@ int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g
   FE_API_END(ctx)
 }
 
+// Test hook of the fused head_dim-64 attention kernels, launched alone: o = softmax(q k^T) v + bv per (batch, head), q taken as the
+// kernel receives it (already scaled). v is transposed on the host into the kernel's V^T layout [B][d][roundup32(Lk)], zero padded.
+// form 0: the kernel of the context's precision (operands rounded on upload); form 1: the split-f16 kernel on hi | lo pairs.
+int fe_op_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, const float* bv, int B, int H, int Lq, int Lk, int causal,
+                    int form, float* o) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(q && k && v && bv && o && B > 0 && H > 0 && Lq > 0 && Lk > 0 && (form == 0 || form == 1), "bad attention arguments");
+  FE_CHECK(form == 0 || C.precision == PREC_F16, "fe_op_attention: the split form (form 1) runs on f16 pairs - set f16 precision");
+  FE_CHECK(form == 0 || !causal, "fe_op_attention: the split form (form 1) has no causal mask");
+  C.arena.reset();
+  const int d = H * 64, Lp = (Lk + 31) / 32 * 32;
+  const size_t nq = (size_t)B * Lq * d, nk = (size_t)B * Lk * d, nv = (size_t)B * d * Lp;
+  std::vector<float> vt(nv, 0.f);
+  for (int b = 0; b < B; ++b)
+    for (int j = 0; j < Lk; ++j)
+      for (int c = 0; c < d; ++c) vt[((size_t)b * d + c) * Lp + j] = v[((size_t)b * Lk + j) * d + c];
+  auto up = [&](const float* src, size_t n) {
+    float* p = C.arena.array<float>(n);
+    FE_HIP(hipMemcpyAsync(p, src, n * sizeof(float), hipMemcpyHostToDevice, C.stream));
+    return p;
+  };
+  float *dq = up(q, nq), *dk = up(k, nk), *dvt = up(vt.data(), nv), *dbv = up(bv, d);
+  if (form == 1) {
+    f16* q2 = C.arena.array<f16>(2 * nq);      // rows [hi d | lo d]
+    f16* k2 = C.arena.array<f16>(2 * nk);
+    f16* v2 = C.arena.array<f16>(2 * nv);      // rows [hi Lp | lo Lp]: V^T hi and lo interleaved by row, row stride 2 Lp
+    f16* o2 = C.arena.array<f16>(2 * nq);
+    float* o32 = C.arena.array<float>(2 * nq);
+    launch_split_hi_lo(dq, q2, (size_t)B * Lq, d, C.stream);
+    launch_split_hi_lo(dk, k2, (size_t)B * Lk, d, C.stream);
+    launch_split_hi_lo(dvt, v2, (size_t)B * d, Lp, C.stream);
+    launch_attention_split(q2, k2, 2 * d, d, v2, v2 + Lp, 2 * Lp, o2, 2 * d, d, B, H, Lq, Lk, d, C.stream);
+    launch_convert(o2, o32, 2 * nq, C.stream);
+    std::vector<float> pair(2 * nq);
+    FE_HIP(hipMemcpyAsync(pair.data(), o32, 2 * nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    for (size_t row = 0; row < (size_t)B * Lq; ++row)
+      for (int c = 0; c < d; ++c) o[row * d + c] = (pair[row * 2 * d + c] + pair[row * 2 * d + d + c]) + bv[c];
+    return FE_OK;
+  }
+  auto half_op = [&](auto* tag) {
+    typedef std::remove_pointer_t<decltype(tag)> E;
+    E *hq = C.arena.array<E>(nq), *hk = C.arena.array<E>(nk), *hv = C.arena.array<E>(nv), *ho = C.arena.array<E>(nq);
+    launch_convert(dq, hq, nq, C.stream);
+    launch_convert(dk, hk, nk, C.stream);
+    launch_convert(dvt, hv, nv, C.stream);
+    launch_attention(hq, d, hk, d, hv, Lp, dbv, ho, d, B, H, Lq, Lk, d, causal ? 1 : 0, C.stream);
+    launch_convert(ho, dq, nq, C.stream);      // dq is free again: the fp32 copy of the output
+    return dq;
+  };
+  float* dout;
+  if (C.precision == PREC_BF16) {
+    dout = half_op((bf16*)nullptr);
+  } else if (C.precision == PREC_F16) {
+    dout = half_op((f16*)nullptr);
+  } else {
+    dout = C.arena.array<float>(nq);
+    launch_attention(dq, d, dk, d, dvt, Lp, dbv, dout, d, B, H, Lq, Lk, d, causal ? 1 : 0, C.stream);
+  }
+  FE_HIP(hipMemcpyAsync(o, dout, nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+
+// Test hook of the attention wiring (build_mha + mha_forward in engine.hip) with nn.MultiheadAttention's parameters: the q / k
+// projections with the folded 1/sqrt(head_dim), the role-swapped V^T GEMM, the kernel (or the unfused route for head_dim != 64), the
+// out-projection and the residual, in the context's precision.
+int fe_op_mha(fe_ctx* ctx, const float* x_q, const float* x_kv, int B, int Lq, int Lk, int d, int heads, const float* in_proj_weight,
+              const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* res, int causal, float* y) {
+  FE_API_BEGIN(ctx)
+  Ctx& C = ctx->c;
+  FE_CHECK(x_q && x_kv && in_proj_weight && in_proj_bias && out_proj_weight && out_proj_bias && y && B > 0 && Lq > 0 && Lk > 0 && d > 0 && heads > 0,
+           "bad mha arguments");
+  C.arena.reset();
+  DeviceWeights dw;
+  dw.prec = C.precision;
+  WeightStore ws;
+  const int64_t s_in[2] = {3 * d, d}, s_out[2] = {d, d}, s_inb[1] = {3 * d}, s_outb[1] = {d};
+  ws.set("a.in_proj_weight", in_proj_weight, s_in, 2);
+  ws.set("a.in_proj_bias", in_proj_bias, s_inb, 1);
+  ws.set("a.out_proj.weight", out_proj_weight, s_out, 2);
+  ws.set("a.out_proj.bias", out_proj_bias, s_outb, 1);
+  const MHAW m = build_mha(dw, ws, "a", heads);
+  const size_t nq = (size_t)B * Lq * d, nk = (size_t)B * Lk * d;
+  auto up = [&](const float* src, size_t n) {
+    float* p = C.arena.array<float>(n);
+    FE_HIP(hipMemcpyAsync(p, src, n * sizeof(float), hipMemcpyHostToDevice, C.stream));
+    return p;
+  };
+  float *dq = up(x_q, nq), *dkv = up(x_kv, nk), *dres = res ? up(res, nq) : nullptr, *dy = C.arena.array<float>(nq);
+  auto half_op = [&](auto* tag) {
+    typedef std::remove_pointer_t<decltype(tag)> E;
+    E *hq = C.arena.array<E>(nq), *hkv = C.arena.array<E>(nk), *hres = res ? C.arena.array<E>(nq) : nullptr, *hy = C.arena.array<E>(nq);
+    launch_convert(dq, hq, nq, C.stream);
+    launch_convert(dkv, hkv, nk, C.stream);
+    if (res) launch_convert(dres, hres, nq, C.stream);
+    mha_forward<E, E>(C, m, hq, d, hkv, d, B, Lq, Lk, hres, d, hy, d, causal != 0);
+    launch_convert(hy, dy, nq, C.stream);
+  };
+  if (C.precision == PREC_BF16) half_op((bf16*)nullptr);
+  else if (C.precision == PREC_F16) half_op((f16*)nullptr);
+  else mha_forward<float, float>(C, m, dq, d, dkv, d, B, Lq, Lk, dres, d, dy, d, causal != 0);
+  FE_HIP(hipMemcpyAsync(y, dy, nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_API_END(ctx)
+}
+
 // Bring-up hook: the VLM decoder's greedy selection (vlm_select) on caller logits [rows][vocab], rounded to bf16 first as in the decoder.
 // ids [rows]; logprobs [rows] (nullable: the plain kernels) the log-probability of each chosen id.
 int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs) {

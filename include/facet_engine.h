@@ -248,6 +248,20 @@ int fe_op_maxpool2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int
 int fe_op_bilinear(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_adaptive_avgpool(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g, const float* b, float eps, float* y);
+/* test hook of the fused head_dim-64 attention kernels, launched alone (kernels_attn.hip, kernels_attn_bf16.hip, kernels_attn_split.hip):
+   q [B][Lq][H*64], k / v [B][Lk][H*64], bv [H*64] -> o [B][Lq][H*64] = softmax(q k^T) v + bv per (batch, head), the semantics of
+   torch.nn.functional.scaled_dot_product_attention with scale = 1 (q is passed as the kernel receives it: the caller has applied any
+   scaling); causal: key j is visible to query i only if j <= i. form 0: the kernel of the context's precision, operands rounded to it on
+   upload. form 1: the split-f16 kernel on hi | lo pairs of the fp32 operands (f16 precision only, no causal mask; hi + lo + bv returned). */
+int fe_op_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, const float* bv, int B, int H, int Lq, int Lk,
+                    int causal, int form, float* o);
+/* test hook of the attention wiring around those kernels (torch.nn.MultiheadAttention, batch_first): x_q [B][Lq][d], x_kv [B][Lk][d],
+   in_proj_weight [3d][d], in_proj_bias [3d], out_proj_weight [d][d], out_proj_bias [d], res [B][Lq][d] (NULL: none) ->
+   y [B][Lq][d] = res + out_proj(attention(q, k, v)) in the context's precision. head_dim = d / heads; 64 runs the fused kernel, any other
+   value the unfused route, which exists for fp32 without a causal mask (anything else is an error). */
+int fe_op_mha(fe_ctx* ctx, const float* x_q, const float* x_kv, int B, int Lq, int Lk, int d, int heads, const float* in_proj_weight,
+              const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* res, int causal,
+              float* y);
 /* test hook of the VLM decoder's greedy selection: logits [rows][vocab] (rows <= 65535) are rounded to bf16 as in the decoder; ids [rows] =
    argmax (first index on ties), logprobs [rows] (NULL: not computed) = the log-probability of that id. */
 int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs);
