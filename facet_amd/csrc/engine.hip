@@ -863,7 +863,7 @@ void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, 
     raw_gemm(c, p, 2.0 * B * d * (double)d * Lk);
   }
   if (flash) {
-    // fused QK^T -> online softmax -> PV (kernels_attn.hip / kernels_attn_bf16.hip); scores never touch HBM
+    // fused QK^T -> online softmax -> PV (kernels_attn.hip); scores never touch HBM
     launch_attention(Q, d, K, d, Vt, Lp, m.bv, O, d, B, H, Lq, Lk, d, causal ? 1 : 0, c.stream);
     c.flops_accum += 4.0 * B * H * (double)Lq * Lk * hd;
     if (half) c.flops_half += 4.0 * B * H * (double)Lq * Lk * hd;

@@ -392,12 +392,12 @@ void launch_tap_gather(const T* z, int ldz, int n, int h, int w, int kh, int kw,
 // fused attention, head_dim 64 (kernels_attn.hip): o = softmax(q k^T) v + bv per (batch, head)
 void launch_attention(const float* q, int ldq, const float* k, int ldk, const float* vt, int lp, const float* bv, float* o,
                       int ldo, int B, int H, int Lq, int Lk, int dmodel, int causal, hipStream_t s);
-// 2-byte twins (kernels_attn_bf16.hip): bf16 or fp16 Q / K / V^T / O, fp32 softmax and accumulation
+// 2-byte forms (kernels_attn.hip, AttnHalf): bf16 or fp16 Q / K / V^T / O, fp32 softmax and accumulation
 void launch_attention(const bf16* q, int ldq, const bf16* k, int ldk, const bf16* vt, int lp, const float* bv, bf16* o,
                       int ldo, int B, int H, int Lq, int Lk, int dmodel, int causal, hipStream_t s);
 void launch_attention(const f16* q, int ldq, const f16* k, int ldk, const f16* vt, int lp, const float* bv, f16* o,
                       int ldo, int B, int H, int Lq, int Lk, int dmodel, int causal, hipStream_t s);
-// split-operand attention (kernels_attn_split.hip): q / k rows [.][ld] with hi at column c and lo at lo_off + c, V^T as two planes,
+// split-operand attention (kernels_attn.hip, AttnSplit): q / k rows [.][ld] with hi at column c and lo at lo_off + c, V^T as two planes,
 // output rows [.][ldo] as hi | lo (o_lo_off)
 void launch_attention_split(const f16* q, const f16* k, int ld, int lo_off, const f16* vt_hi, const f16* vt_lo, int lp, f16* o, int ldo, int o_lo_off,
                             int B, int H, int Lq, int Lk, int dmodel, hipStream_t s);

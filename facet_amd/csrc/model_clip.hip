@@ -316,7 +316,7 @@ __global__ void clip_v_transpose_kernel(const f16* __restrict__ src, int ld, int
 }
 
 // Every tensor between two layers is either the fp32 token stream or an fp16 PAIR (hi | lo): LayerNorm writes pairs, the fused q|k|v
-// projection and c_fc write pairs from their epilogues, attention (kernels_attn_split.hip) reads and writes pairs, out_proj and c_proj
+// projection and c_fc write pairs from their epilogues, attention (kernels_attn.hip, AttnSplit) reads and writes pairs, out_proj and c_proj
 // add into the fp32 stream. No activation is ever rounded to a single fp16.
 void clip_forward_split3(Ctx& c, const ClipModel& m, const Tensor& x, float* feat) {
   FE_CHECK(m.split3, "clip: the tower was not committed under FE_PRECISION_SPLIT3");

@@ -248,7 +248,7 @@ int fe_op_maxpool2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int
 int fe_op_bilinear(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_adaptive_avgpool(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g, const float* b, float eps, float* y);
-/* test hook of the fused head_dim-64 attention kernels, launched alone (kernels_attn.hip, kernels_attn_bf16.hip, kernels_attn_split.hip):
+/* test hook of the fused head_dim-64 attention kernels, launched alone (kernels_attn.hip: fp32, bf16 / f16 and split-f16 policies):
    q [B][Lq][H*64], k / v [B][Lk][H*64], bv [H*64] -> o [B][Lq][H*64] = softmax(q k^T) v + bv per (batch, head), the semantics of
    torch.nn.functional.scaled_dot_product_attention with scale = 1 (q is passed as the kernel receives it: the caller has applied any
    scaling); causal: key j is visible to query i only if j <= i. form 0: the kernel of the context's precision, operands rounded to it on
