@@ -183,6 +183,7 @@ SIGNATURES = {
     "fe_jpeg_probe_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "fe_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
+    "fe_jpeg_entropy_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fe_jpeg_scaled_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_jpeg_decode_scaled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p]),
@@ -203,6 +204,7 @@ FE_CONTOUR_FIELDS = 8      # long longs per contour record
 FE_SIM_FUSED, FE_SIM_COSINE = 0, 1
 FE_SIM_K_MAX = 32
 FE_JPEG_PROGRESSIVE = 1    # flag of fe_jpeg_probe_ex / fe_jpeg_decode_ex (and the status of a progressive file without it)
+FE_JPEG_FLAG_PARALLEL = 0x100      # flag of the decode entry points: baseline segments decoded by one lane per 128-byte subsequence
 FE_SIM_NO_DATE = -(1 << 63)
 
 
@@ -1254,11 +1256,12 @@ class Engine:
                                             1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)
 
-    def jpeg_thumbnail(self, blobs, scale, plan, quality=80, progressive=False, cap=None):
+    def jpeg_thumbnail(self, blobs, scale, plan, quality=80, progressive=False, cap=None, parallel_entropy=False):
         """JPEG files (a list of bytes) of one size -> (list of bytes, status int32 [n]): what `Image.open(f)`,
         `thumbnail((size, size), LANCZOS)`, `save(buf, "JPEG", quality=quality)` writes for each, with (scale, plan) =
         facet_amd.thumbnail.thumbnail_plan_jpeg(W, H, size) (fe_jpeg_thumbnail). Scaled decode, reduce, resize and encode run back to back
-        on the device. A file with a non-zero status (jpeg_decode's codes) gives b"". cap as in jpeg_encode, against the plan's size."""
+        on the device. A file with a non-zero status (jpeg_decode's codes) gives b"". cap as in jpeg_encode, against the plan's size.
+        parallel_entropy: as in jpeg_decode; the bytes do not depend on it."""
         if scale not in (1, 2, 4, 8):
             raise ValueError(f"jpeg_thumbnail: scale {scale!r} (1, 2, 4 or 8)")
         blobs = [bytes(b) for b in blobs]
@@ -1275,8 +1278,8 @@ class Engine:
         out = np.empty((n, cap), np.uint8)
         lengths = np.zeros(n, np.int32)
         status = np.zeros(n, np.int32)
-        self._ck(self.lib.fe_jpeg_thumbnail(self.h, ptrs, lens, n, int(plan.src_h), int(plan.src_w), int(scale), FE_JPEG_PROGRESSIVE if progressive else 0,
-                                            oh, ow, fx, fy, rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None,
+        self._ck(self.lib.fe_jpeg_thumbnail(self.h, ptrs, lens, n, int(plan.src_h), int(plan.src_w), int(scale),
+                                            (FE_JPEG_PROGRESSIVE if progressive else 0) | (FE_JPEG_FLAG_PARALLEL if parallel_entropy else 0), oh, ow, fx, fy, rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None,
                                             box.ctypes.data_as(C.c_void_p), 1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap,
                                             lengths.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths), status
@@ -1332,7 +1335,16 @@ class Engine:
             raise ValueError(f"jpeg_scaled_size: {h} x {w} at scale {scale} (a positive size; scale 1, 2, 4 or 8)")
         return sh.value, sw.value
 
-    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False, progressive=False, scale=1):
+    def jpeg_entropy_stats(self):
+        """What the entropy stage of this engine's last jpeg_decode / jpeg_thumbnail call did (fe_jpeg_entropy_stats): dict(
+        parallel_segments, subsequences, max_rounds, redone) = segments decoded by one lane per subsequence, those subsequences, the most
+        rounds any segment needed to settle its entry states, images decoded again by the serial kernel after an error. All zero for
+        a call without parallel_entropy."""
+        out = (C.c_int32 * 4)()
+        self._ck(self.lib.fe_jpeg_entropy_stats(self.h, out))
+        return dict(zip(("parallel_segments", "subsequences", "max_rounds", "redone"), (int(v) for v in out)))
+
+    def jpeg_decode(self, blobs, h, w, bgr=False, apply_orientation=True, device=False, progressive=False, scale=1, parallel_entropy=False):
         """JPEG files (a list of bytes) whose decoded size is h x w -> (pixels, status). pixels: uint8 [n,h,w,3], what Pillow's
         `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives (apply_orientation=False: without the transpose; bgr: B,G,R bytes),
         a host array, or with device=True a (device_ptr, n, h, w) tuple whose buffer the caller releases with dev_free (device=<pointer>
@@ -1340,7 +1352,10 @@ class Engine:
         was (zeros in a host array allocated here, undefined in a device buffer allocated here). progressive=True (fe_jpeg_decode_ex):
         progressive files that jpeg_probe(blob, progressive=True) gives status 0 are decoded too, in the same call as baseline ones.
         scale = 2, 4 or 8 (fe_jpeg_decode_scaled): the decode at 1/scale that `im.draft()` switches on, the pixels of the drafted image;
-        h, w are then the scaled size, jpeg_scaled_size(H, W, scale), exchanged for orientations 5 .. 8 like the full size."""
+        h, w are then the scaled size, jpeg_scaled_size(H, W, scale), exchanged for orientations 5 .. 8 like the full size.
+        parallel_entropy=True (FE_JPEG_FLAG_PARALLEL): a baseline file's entropy-coded segments of at least 256 bytes are decoded by one
+        lane per 128 bytes instead of one lane per segment, which is what a file without restart markers needs; pixels and statuses do
+        not depend on it, and jpeg_entropy_stats() tells what it did."""
         if scale not in (1, 2, 4, 8):
             raise ValueError(f"jpeg_decode: scale {scale!r} (1, 2, 4 or 8)")
         blobs = [bytes(b) for b in blobs]
@@ -1350,13 +1365,14 @@ class Engine:
         ptrs = (C.c_char_p * n)(*blobs)
         lens = (C.c_size_t * n)(*[len(b) for b in blobs])
         status = np.zeros(n, np.int32)
+        flags = (FE_JPEG_PROGRESSIVE if progressive else 0) | (FE_JPEG_FLAG_PARALLEL if parallel_entropy else 0)
         def call(on_device, dst):
             head = (self.h, ptrs, lens, n, int(h), int(w), 1 if bgr else 0, 1 if apply_orientation else 0, on_device)
             if scale != 1:
-                self._ck(self.lib.fe_jpeg_decode_scaled(self.h, ptrs, lens, n, int(h), int(w), int(scale), *head[6:],
-                                                        FE_JPEG_PROGRESSIVE if progressive else 0, dst, status.ctypes.data_as(C.c_void_p)))
-            elif progressive:
-                self._ck(self.lib.fe_jpeg_decode_ex(*head, FE_JPEG_PROGRESSIVE, dst, status.ctypes.data_as(C.c_void_p)))
+                self._ck(self.lib.fe_jpeg_decode_scaled(self.h, ptrs, lens, n, int(h), int(w), int(scale), *head[6:], flags, dst,
+                                                        status.ctypes.data_as(C.c_void_p)))
+            elif flags:
+                self._ck(self.lib.fe_jpeg_decode_ex(*head, flags, dst, status.ctypes.data_as(C.c_void_p)))
             else:
                 self._ck(self.lib.fe_jpeg_decode(*head, dst, status.ctypes.data_as(C.c_void_p)))
         if device is False or device is None:

@@ -247,17 +247,18 @@ class BatchScorer:
                 out[i] = r
         return out
 
-    def process_files(self, paths_or_blobs, exif=None, leading_lines=None, progressive=False):
+    def process_files(self, paths_or_blobs, exif=None, leading_lines=None, progressive=False, parallel_entropy=False):
         """Image FILES (paths, or the files' bytes) instead of decoded arrays: the reference's `_load_images` + batch step. JPEG files the
         engine decodes (facet_amd.image_loading) are decoded on the device per output size and scored from that resident batch, with no
         copy of the pixels down and up again; every other file is opened with Pillow as load_image_from_path does and goes through
         process_images. Results come back in input order; a file the reference could not load gives None. progressive=True: complete
-        progressive files join the resident batch of their size instead of going through Pillow; the records are the same either way."""
+        progressive files join the resident batch of their size instead of going through Pillow; the records are the same either way.
+        parallel_entropy=True: the decoder works inside a file's entropy-coded segments in parallel (Engine.jpeg_decode); the same records again."""
         from .image_loading import decode_groups, pillow_rgb, read_blob
         blobs = [read_blob(p) for p in paths_or_blobs]
         out = [None] * len(blobs)
         e = self.engine
-        groups, rest = decode_groups(e, blobs, device=True, progressive=progressive)
+        groups, rest = decode_groups(e, blobs, device=True, progressive=progressive, parallel_entropy=parallel_entropy)
         for idx, dev in groups:
             res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
                                      leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev)

@@ -1514,7 +1514,7 @@ int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int 
 
 /* ---- JPEG decode: what `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives, from the file's bytes ---- */
 int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info) {
-  if (!info || (flags & ~FE_JPEG_PROGRESSIVE)) return FE_ERR_INVALID;
+  if (!info || (flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL))) return FE_ERR_INVALID;      // the parser has no use for the second
   try {
     int32_t v[10];
     static const uint8_t none[1] = {0};
@@ -1548,9 +1548,16 @@ int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, i
 int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
                       int flags, uint8_t* dst, int32_t* status) {
   FE_API_BEGIN(ctx)
-  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~FE_JPEG_PROGRESSIVE), "bad arguments");
+  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)), "bad arguments");
   jpeg_decode_batch(ctx->c, data, len, n, h, w, 1, bgr, apply_orientation, dst_on_device, flags, dst, status);
   FE_API_END(ctx)
+}
+
+/* what the entropy stage of the context's last decode call did; read back with that call's statuses, so nothing is waited for here */
+int fe_jpeg_entropy_stats(fe_ctx* ctx, int32_t out[4]) {
+  if (!ctx || !out) return FE_ERR_INVALID;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->c.jpeg_entropy_stats[k];
+  return FE_OK;
 }
 
 static bool jpeg_scale_ok(int scale) { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
@@ -1572,7 +1579,7 @@ int fe_jpeg_decode_scaled(fe_ctx* ctx, const uint8_t* const* data, const size_t*
     return FE_ERR_INVALID;
   }
   FE_API_BEGIN(ctx)
-  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~FE_JPEG_PROGRESSIVE), "bad arguments");
+  FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)), "bad arguments");
   jpeg_decode_batch(ctx->c, data, len, n, h, w, scale, bgr, apply_orientation, dst_on_device, flags, dst, status);
   FE_API_END(ctx)
 }
@@ -1588,7 +1595,7 @@ int fe_jpeg_thumbnail(fe_ctx* ctx, const uint8_t* const* data, const size_t* len
     return FE_ERR_INVALID;
   }
   FE_API_BEGIN(ctx)
-  FE_CHECK(data && len && out && lengths && status && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1 && !(flags & ~FE_JPEG_PROGRESSIVE),
+  FE_CHECK(data && len && out && lengths && status && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)),
            "bad arguments");
   FE_CHECK((fx == 1 && fy == 1) || reduce_box, "jpeg_thumbnail: reduce factors without a reduce box");
   ThumbPlan p;

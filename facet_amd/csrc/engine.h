@@ -288,6 +288,7 @@ struct Ctx {
   std::map<std::tuple<int, int, int>, void*> jpeg_cache;               // (h, w, quality) -> jpeg::Tables on the device
   void* jpegdec_stage = nullptr;      // pinned host block of fe_jpeg_decode's single upload; grows, never shrinks
   size_t jpegdec_stage_cap = 0;
+  int32_t jpeg_entropy_stats[4] = {0, 0, 0, 0};      // of the last jpeg_decode_batch: fe_jpeg_entropy_stats
   WeightStore staging[8];
   std::unique_ptr<struct TopiqModel> topiq;
   std::unique_ptr<struct U2NetPModel> u2netp;

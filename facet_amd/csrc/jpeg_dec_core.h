@@ -12,6 +12,7 @@
 #pragma once
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "jpeg_core.h"
@@ -199,6 +200,177 @@ FE_JHD int decode_segment(BitReader& br, const DecGeom& g, const HuffDec* huff, 
   return 0;
 }
 
+// ---- decoding inside one segment in parallel: self-synchronising Huffman decoding ------------------------------------------------------
+// (Weissenberger & Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018.) A baseline segment is cut into subsequences of S raw
+// bytes, S a power of two >= 16; a cut that lands on the stuffed 0x00 behind a 0xFF moves one byte on, which is exact because inside a
+// segment a 0xFF is always followed by its stuffed zero and is never one itself. A lane decodes the symbols (a Huffman code with its
+// extra bits) that START inside its subsequence, from an entry state: where in the MCU and in the block the decoder is, and at which bit.
+//   step 1  every subsequence but the last is decoded from its first bit as if a block of component 0 began there; subsequence 0 really
+//           does. Nothing is stored but the exit: the state at the first symbol that starts at or behind the next subsequence's first byte.
+//   step 2  rounds: subsequence i is decoded again from the exit of i - 1 as the previous round left it, unless that is the entry it was last
+//           decoded from. After round r the exits of 0 .. r are the true ones, by induction from subsequence 0, so at most as many rounds
+//           as subsequences are run and what stands then is right: there is nothing to fall back from. A round that changes nothing ends it.
+//   step 3  exclusive prefix sums over the blocks each subsequence completed and over the DC differences it decoded per component give
+//           every subsequence the index of its first block in scan order and its entry predictions.
+//   step 4  every subsequence decodes from its true entry and stores coefficients: a block that straddles a cut is written by two lanes,
+//           to different int16 elements.
+// Positions are kept in raw-byte terms: an exit is the number of (destuffed) bits behind the first byte of the next subsequence, which
+// is a raw offset fixed by the cut, so two passes that stop at the same bit state the same number whatever their readers prefetched.
+// A code in no table or a run past 63 in steps 1 and 2 is what a wrong guess looks like, not an error: the pass drops one bit, or ends
+// the block at 63, and goes on, because any rule that is a function of the bits keeps the induction and this one lets a lane that guessed
+// the component wrong find its way into step with the true decoder inside its own subsequence (giving up instead left a three-component
+// file without restart markers one round per subsequence). Step 4 starts from true states, so there the same conditions are
+// decode_segment's errors; the caller then zeroes the image and decodes it again with decode_segment for its exact status.
+// SUB_INVALID is the exit of a pass that has not run; no pass starts from it.
+// The exit of the last subsequence has no reader, so steps 1 and 2 leave it out.
+constexpr uint32_t SUB_INVALID = 0xFFFFFFFFu;
+constexpr uint32_t SUB_BYTES = 128;    // the device's S
+// The most bits an exit can lie behind its cut: the longest symbol is a 16-bit code with 15 extra bits, and the symbol that crosses the cut
+// began at least one bit in front of it. (The one-bit drop of a speculative pass is shorter.)
+constexpr uint32_t SUB_MAX_PAST = 16 + 15 - 1;
+
+FE_JHD uint32_t sub_count(uint32_t seg_bytes, uint32_t S) { return (seg_bytes + S - 1) / S; }
+
+// raw offset of subsequence i's first byte; i * S is inside the segment [s0, s1)
+FE_JHD uint32_t sub_start(const uint8_t* bytes, uint32_t s0, uint32_t i, uint32_t S) {
+  const uint32_t c = s0 + i * S;
+  return (i && bytes[c] == 0 && bytes[c - 1] == 255) ? c + 1 : c;
+}
+
+// BitReader that knows where the bit it hands out next lies relative to raw offset `limit`, a data byte or the segment's end
+struct SubReader : BitReader {
+  uint32_t limit, loaded, mark;        // loaded: bits taken into acc so far; mark: `loaded` when the byte at `limit` came in
+  FE_JHD void start(const uint8_t* b, uint32_t from, uint32_t stop, uint32_t lim) {
+    init(b, from, stop);
+    limit = lim; loaded = 0; mark = SUB_INVALID;
+  }
+  FE_JHD void fill_marked() {          // BitReader::fill
+    while (nbits <= 56) {
+      uint32_t b = 0;
+      if (pos >= limit && mark == SUB_INVALID) mark = loaded;
+      if (pos < end) {
+        b = byte_at(pos++);
+        if (b == 255u) ++pos;
+      } else {
+        pad += 8;
+      }
+      acc = (acc << 8) | b;
+      nbits += 8;
+      loaded += 8;
+    }
+  }
+  FE_JHD bool behind() const { return mark != SUB_INVALID && loaded - (uint32_t)nbits >= mark; }      // after fill_marked()
+  FE_JHD uint32_t past() const { return loaded - (uint32_t)nbits - mark; }
+};
+
+// entry / exit state: bits behind the subsequence's first byte << 16 | block within the MCU << 8 | zigzag index (0: a DC code is next)
+FE_JHD uint32_t sub_state(uint32_t bits, int b, int k) { return (bits << 16) | ((uint32_t)b << 8) | (uint32_t)k; }
+
+struct SubResult {
+  uint32_t exit;                       // SUB_INVALID: the pass did not reach its limit (step 4: ended with its blocks or an error)
+  uint32_t nblk;                       // blocks whose last symbol it decoded
+  int32_t dc[3];                       // sums of the DC differences it decoded, wrapping as decode_block's pred does
+  int32_t err;                         // WRITE: 0, ST_BAD_HUFFMAN or ST_PREMATURE_END
+};
+
+// One pass over subsequence i of nsub of the segment [s0, s1) from `entry`. WRITE = false: steps 1 and 2. WRITE = true: step 4, which
+// stores into coef (the image's buffer, zero on entry) for blocks first_blk .. of the segment's nmcu MCUs from mcu0 on, with predictions
+// pred_in, stops at the segment's last block and, in the last subsequence, has no other end: it then runs until the MCU in which the
+// data ran out. Every loop is bounded: a symbol takes at least one bit, so a pass with a limit sees at most 8 S + 32 of them, and the
+// one without ends with its blocks or with the first MCU that consumed padding.
+template <bool WRITE>
+FE_JHD void sub_pass(const uint8_t* bytes, uint32_t s0, uint32_t s1, uint32_t S, uint32_t i, uint32_t nsub, uint32_t entry, const DecGeom& g,
+                     const HuffDec* huff, const uint8_t* td, const uint8_t* ta, uint32_t first_blk, const int32_t* pred_in, uint32_t mcu0,
+                     uint32_t nmcu, int16_t* coef, const uint8_t* nat, SubResult& R) {
+  R.exit = SUB_INVALID; R.nblk = 0; R.dc[0] = R.dc[1] = R.dc[2] = 0; R.err = 0;
+  const int eb = (int)((entry >> 8) & 255u), ek = (int)(entry & 255u);
+  if (entry == SUB_INVALID || (entry >> 16) > SUB_MAX_PAST || ek >= 64 || eb >= (g.ncomp == 1 ? 1 : g.hs * g.vs + 2)) {
+    if (WRITE) R.err = ST_BAD_HUFFMAN;       // no converged exit looks like this: step 4 never writes nothing without saying so
+    return;
+  }
+  const int nl = g.ncomp == 1 ? 1 : g.hs * g.vs, bpm = g.ncomp == 1 ? 1 : nl + 2;      // luma blocks, all blocks of an MCU
+  const uint32_t total = nmcu * (uint32_t)bpm;
+  const bool last = i + 1 == nsub;
+  int b = eb, k = ek;
+  uint32_t blk = first_blk;
+  int pred[3] = {0, 0, 0}, mx = 0, my = 0;
+  int16_t* p = coef;
+  auto block_at = [&]() {              // WRITE: block b of MCU (mx, my)
+    const int c = b < nl ? 0 : b - nl + 1;
+    const int ch = c ? 1 : g.hs, cv = c ? 1 : g.vs, by = c ? 0 : b / g.hs, bx = c ? 0 : b % g.hs;
+    return coef + (size_t)(g.blk_off[c] + (uint32_t)(my * cv + by) * g.bw[c] + (uint32_t)(mx * ch + bx)) * 64;
+  };
+  if (WRITE) {
+    if (blk >= total) return;
+    b = (int)(blk % (uint32_t)bpm);    // the entry's, restated from the block index so that every address follows from blk < total alone
+    const uint32_t m = mcu0 + blk / (uint32_t)bpm;
+    my = (int)(m / (uint32_t)g.mw); mx = (int)(m % (uint32_t)g.mw);
+    pred[0] = pred_in[0]; pred[1] = pred_in[1]; pred[2] = pred_in[2];
+    p = block_at();
+  }
+  SubReader br;
+  br.start(bytes, sub_start(bytes, s0, i, S), s1, last ? (WRITE ? SUB_INVALID : s1) : sub_start(bytes, s0, i + 1, S));
+  br.fill_marked();
+  br.skip((int)(entry >> 16));
+  const uint32_t cap = (WRITE && last) ? SUB_INVALID : 8 * S + 64;
+  for (uint32_t it = 0; it < cap; ++it) {
+    br.fill_marked();
+    if (br.behind()) { R.exit = sub_state(br.past(), b, k); return; }
+    const int c = b < nl ? 0 : b - nl + 1;
+    if (k == 0) {
+      int s = decode_symbol(br, huff[td[c] & 3]);
+      if (s < 0 || s > 15) {
+        if (WRITE) { R.err = ST_BAD_HUFFMAN; return; }
+        br.skip(1); continue;
+      }
+      if (s) {
+        const int r = (int)br.peek(s);
+        br.skip(s);
+        s = huff_extend(r, s);
+      }
+      R.dc[c] = (int32_t)((uint32_t)R.dc[c] + (uint32_t)s);
+      if (WRITE) {
+        pred[c] = (int32_t)((uint32_t)pred[c] + (uint32_t)s);
+        p[0] = (int16_t)pred[c];
+      }
+      k = 1;
+      continue;
+    }
+    int s = decode_symbol(br, huff[4 + (ta[c] & 3)]);
+    if (s < 0) {
+      if (WRITE) { R.err = ST_BAD_HUFFMAN; return; }
+      br.skip(1); continue;
+    }
+    const int r = s >> 4;
+    s &= 15;
+    if (s) {
+      k += r;
+      const int v = (int)br.peek(s);
+      br.skip(s);
+      if (k >= 64) {
+        if (WRITE) { R.err = ST_BAD_HUFFMAN; return; }
+        k = 63;
+      }
+      if (WRITE) p[nat[k]] = (int16_t)huff_extend(v, s);
+      ++k;
+    } else {
+      k = r == 15 ? k + 16 : 64;       // ZRL, which may run off the block's end as in decode_block; anything else is EOB
+    }
+    if (k < 64) continue;
+    k = 0;                             // the block is complete
+    ++R.nblk;
+    if (++b == bpm) b = 0;
+    if (WRITE) {
+      if (b == 0) {
+        if (br.overread()) { R.err = ST_PREMATURE_END; return; }
+        if (++mx == g.mw) { mx = 0; ++my; }
+      }
+      if (++blk >= total) return;
+      p = block_at();
+    }
+  }
+}
+
 // ---- dequantise + jidctint.c jpeg_idct_islow ------------------------------------------------------------------------------------------
 // Two's complement arithmetic that wraps: coefficients a hostile stream chose may overflow 32 bits, which must stay defined behaviour.
 FE_JHD int32_t wmul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
@@ -212,6 +384,7 @@ FE_JHD int32_t wdescale(int32_t x, int n) { return wadd(x, 1 << (n - 1)) >> n; }
 // tables, the restart interval and the segments are the scan's; quantisation tables, geometry and orientation stay the image's.
 constexpr int MAX_SCANS = 32;          // libjpeg's default scripts have 10 (colour) and 6 (gray)
 constexpr int FLAG_PROGRESSIVE = 1;    // parse(): take SOF2 files
+constexpr int FLAG_PARALLEL = 0x100;   // the decode: baseline segments of at least two subsequences one lane per subsequence; parse() ignores it
 
 struct ScanDesc {
   uint32_t seg_first, nseg;            // this scan's rows of the segment offset arrays
@@ -1142,6 +1315,42 @@ inline void build_tables(const Parsed& P, DecTables& T) {
   }
 }
 
+// Stages C and D on the host: the coefficients of a parsed file -> out. st: what the entropy stage gave; returns the image's status.
+inline int32_t finish_host(const Parsed& P, const DecGeom& g, const ScaledGeom& sg, const DecTables& T, const std::vector<int16_t>& coef, int32_t st,
+                           int scale, int bgr, int apply_orientation, uint8_t* out) {
+  std::vector<uint8_t> planes(scale == 1 ? g.plane_bytes : sg.plane_bytes);
+  if (st == ST_OK && scale == 1) {
+    for (int c = 0; c < g.ncomp; ++c)
+      for (int by = 0; by < g.bh[c]; ++by)
+        for (int bx = 0; bx < g.bw[c]; ++bx)
+          if (!idct_block(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c] + bx) * 64, T.q[P.comp[c].tq],
+                          planes.data() + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, (size_t)g.bw[c] * 8))
+            st = ST_BAD_COEFFICIENT;
+  }
+  if (st == ST_OK && scale != 1) {
+    for (int c = 0; c < g.ncomp; ++c)
+      for (int by = 0; by < g.bh[c]; ++by)
+        for (int gx = 0; gx < sg.gw[c]; ++gx)
+          if (!idct_group(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c]) * 64, gx, g.bw[c], sg.ss[c], T.q[P.comp[c].tq],
+                          planes.data() + sg.plane_off[c] + (size_t)by * sg.ss[c] * sg.stride[c], (size_t)sg.stride[c]))
+            st = ST_BAD_COEFFICIENT;
+  }
+  if (st == ST_OK && P.incomplete) st = ST_OTHER;
+  if (st == ST_OK) {
+    const int o = apply_orientation ? P.orientation : 1;
+    const int ow = scale == 1 ? g.w : sg.ow, oh = scale == 1 ? g.h : sg.oh;
+    for (int y = 0; y < oh; ++y)
+      for (int x = 0; x < ow; ++x) {
+        uint8_t rgb[3];
+        if (scale == 1) pixel_rgb(planes.data(), g, x, y, rgb);
+        else pixel_rgb_scaled(planes.data(), g, sg, x, y, rgb);
+        uint8_t* p = out + oriented_index(o, ow, oh, x, y) * 3;
+        p[0] = rgb[bgr ? 2 : 0]; p[1] = rgb[1]; p[2] = rgb[bgr ? 0 : 2];
+      }
+  }
+  return st;
+}
+
 // The whole decode of one parsed file on the host, stage by stage as the kernels run it. buf: the file copied into a 16-byte aligned
 // buffer padded to a multiple of 16 bytes. scale: 1, 2, 4 or 8, which the caller has checked. out:
 // [oh][ow][3] with (oh, ow) = (ceil(height / scale), ceil(width / scale)), exchanged for orientations 5 .. 8 when apply_orientation.
@@ -1154,7 +1363,6 @@ inline int32_t decode_host_scaled(const Parsed& P, const uint8_t* buf, int scale
   DecTables* T = new DecTables;
   build_tables(P, *T);
   std::vector<int16_t> coef((size_t)g.nblk * 64, 0);
-  std::vector<uint8_t> planes(scale == 1 ? g.plane_bytes : sg.plane_bytes);
   uint8_t td[3], ta[3];
   for (int c = 0; c < 3; ++c) { td[c] = P.comp[c].td; ta[c] = P.comp[c].ta; }
   const uint32_t mcus = (uint32_t)g.mw * g.mh, per = P.ri ? (uint32_t)P.ri : mcus;
@@ -1177,41 +1385,109 @@ inline int32_t decode_host_scaled(const Parsed& P, const uint8_t* buf, int scale
     const uint32_t m0 = (uint32_t)k * per;
     st = decode_segment(br, g, T->huff, td, ta, m0, mcus - m0 < per ? mcus - m0 : per, coef.data(), kNatural);
   }
-  if (st == ST_OK && scale == 1) {
-    for (int c = 0; c < g.ncomp; ++c)
-      for (int by = 0; by < g.bh[c]; ++by)
-        for (int bx = 0; bx < g.bw[c]; ++bx)
-          if (!idct_block(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c] + bx) * 64, T->q[P.comp[c].tq],
-                          planes.data() + g.plane_off[c] + ((size_t)by * 8 * g.bw[c] + bx) * 8, (size_t)g.bw[c] * 8))
-            st = ST_BAD_COEFFICIENT;
-  }
-  if (st == ST_OK && scale != 1) {
-    for (int c = 0; c < g.ncomp; ++c)
-      for (int by = 0; by < g.bh[c]; ++by)
-        for (int gx = 0; gx < sg.gw[c]; ++gx)
-          if (!idct_group(coef.data() + ((size_t)g.blk_off[c] + (size_t)by * g.bw[c]) * 64, gx, g.bw[c], sg.ss[c], T->q[P.comp[c].tq],
-                          planes.data() + sg.plane_off[c] + (size_t)by * sg.ss[c] * sg.stride[c], (size_t)sg.stride[c]))
-            st = ST_BAD_COEFFICIENT;
-  }
-  if (st == ST_OK && P.incomplete) st = ST_OTHER;
-  if (st == ST_OK) {
-    const int o = apply_orientation ? P.orientation : 1;
-    const int ow = scale == 1 ? g.w : sg.ow, oh = scale == 1 ? g.h : sg.oh;
-    for (int y = 0; y < oh; ++y)
-      for (int x = 0; x < ow; ++x) {
-        uint8_t rgb[3];
-        if (scale == 1) pixel_rgb(planes.data(), g, x, y, rgb);
-        else pixel_rgb_scaled(planes.data(), g, sg, x, y, rgb);
-        uint8_t* p = out + oriented_index(o, ow, oh, x, y) * 3;
-        p[0] = rgb[bgr ? 2 : 0]; p[1] = rgb[1]; p[2] = rgb[bgr ? 0 : 2];
-      }
-  }
+  st = finish_host(P, g, sg, *T, coef, st, scale, bgr, apply_orientation, out);
   delete T;
   return st;
 }
 
 inline int32_t decode_host(const Parsed& P, const uint8_t* buf, int bgr, int apply_orientation, uint8_t* out) {
   return decode_host_scaled(P, buf, 1, bgr, apply_orientation, out);
+}
+
+// Steps 1 to 4 of the parallel decode over one segment with the lanes as loops, in the order of the kernels: every pass of a round reads
+// what the round before left. rounds: the largest count so far. Returns 0 or an error of step 4.
+inline int32_t decode_segment_parallel(const uint8_t* buf, uint32_t s0, uint32_t s1, uint32_t S, const DecGeom& g, const HuffDec* huff,
+                                       const uint8_t* td, const uint8_t* ta, uint32_t mcu0, uint32_t nmcu, int16_t* coef, uint32_t& rounds) {
+  const uint32_t n = sub_count(s1 - s0, S);
+  std::vector<uint32_t> cur(n, SUB_INVALID), nxt(n, SUB_INVALID), entry(n, 0), first(n, 0);
+  std::vector<int32_t> dc[3] = {std::vector<int32_t>(n, 0), std::vector<int32_t>(n, 0), std::vector<int32_t>(n, 0)};
+  SubResult R;
+  auto sync_pass = [&](uint32_t i, uint32_t e) {
+    sub_pass<false>(buf, s0, s1, S, i, n, e, g, huff, td, ta, 0, nullptr, 0, 0, nullptr, nullptr, R);
+    entry[i] = e; first[i] = R.nblk;
+    for (int c = 0; c < 3; ++c) dc[c][i] = R.dc[c];
+  };
+  for (uint32_t i = 0; i + 1 < n; ++i) {                     // step 1
+    sync_pass(i, 0);
+    cur[i] = R.exit;
+  }
+  uint32_t ran = 0;
+  for (bool changed = true; changed && ran < n; ++ran) {   // step 2
+    changed = false;
+    nxt[0] = cur[0];
+    for (uint32_t i = 1; i + 1 < n; ++i) {
+      if (cur[i - 1] == entry[i]) { nxt[i] = cur[i]; continue; }
+      sync_pass(i, cur[i - 1]);
+      nxt[i] = R.exit;
+      changed |= nxt[i] != cur[i];
+    }
+    cur.swap(nxt);
+  }
+  if (ran > rounds) rounds = ran;
+  uint32_t blocks = 0;                                       // step 3
+  int32_t pred[3] = {0, 0, 0};
+  for (uint32_t i = 0; i < n; ++i) {
+    if (i) entry[i] = cur[i - 1];
+    const uint32_t nb = i + 1 < n ? first[i] : 0;
+    first[i] = blocks;
+    blocks += nb;
+    for (int c = 0; c < 3; ++c) {
+      const int32_t d = i + 1 < n ? dc[c][i] : 0;
+      dc[c][i] = pred[c];
+      pred[c] = (int32_t)((uint32_t)pred[c] + (uint32_t)d);
+    }
+  }
+  int32_t err = 0;
+  for (uint32_t i = 0; i < n; ++i) {                         // step 4
+    const int32_t pin[3] = {dc[0][i], dc[1][i], dc[2][i]};
+    sub_pass<true>(buf, s0, s1, S, i, n, entry[i], g, huff, td, ta, first[i], pin, mcu0, nmcu, coef, kNatural, R);
+    if (R.err && !err) err = R.err;
+  }
+  return err;
+}
+
+struct ParallelStats { uint32_t segments = 0, subsequences = 0, rounds = 0, redone = 0; };
+
+// decode_host for a baseline file with every segment of at least two subsequences of S bytes decoded in parallel and the others by
+// decode_segment; an image in which either met an error is zeroed and decoded again as decode_host decodes it, so status and pixels are
+// decode_host's for every file.
+inline int32_t decode_host_parallel(const Parsed& P, const uint8_t* buf, uint32_t S, int bgr, int apply_orientation, uint8_t* out, ParallelStats& ps) {
+  if (P.status != ST_OK || P.progressive) return decode_host(P, buf, bgr, apply_orientation, out);
+  const DecGeom g = make_dec_geom(P.width, P.height, P.ncomp, P.hs, P.vs);
+  const ScaledGeom sg = make_scaled_geom(g, 1);
+  DecTables* T = new DecTables;
+  build_tables(P, *T);
+  std::vector<int16_t> coef((size_t)g.nblk * 64, 0);
+  uint8_t td[3], ta[3];
+  for (int c = 0; c < 3; ++c) { td[c] = P.comp[c].td; ta[c] = P.comp[c].ta; }
+  const uint32_t mcus = (uint32_t)g.mw * g.mh, per = P.ri ? (uint32_t)P.ri : mcus;
+  int32_t st = ST_OK, perr = 0;
+  for (size_t k = 0; k < P.seg_start.size(); ++k) {
+    const uint32_t m0 = (uint32_t)k * per, nm = mcus - m0 < per ? mcus - m0 : per, nsub = sub_count(P.seg_end[k] - P.seg_start[k], S);
+    if (nsub >= 2) {
+      ++ps.segments; ps.subsequences += nsub;
+      const int32_t e = decode_segment_parallel(buf, P.seg_start[k], P.seg_end[k], S, g, T->huff, td, ta, m0, nm, coef.data(), ps.rounds);
+      if (e && !perr) perr = e;
+    } else if (st == ST_OK) {
+      BitReader br;
+      br.init(buf, P.seg_start[k], P.seg_end[k]);
+      st = decode_segment(br, g, T->huff, td, ta, m0, nm, coef.data(), kNatural);
+    }
+  }
+  if (perr || st != ST_OK) {                                 // whichever decoder met the error, as the kernels do
+    ++ps.redone;
+    std::fill(coef.begin(), coef.end(), (int16_t)0);
+    st = ST_OK;
+    for (size_t k = 0; k < P.seg_start.size() && st == ST_OK; ++k) {
+      BitReader br;
+      br.init(buf, P.seg_start[k], P.seg_end[k]);
+      const uint32_t m0 = (uint32_t)k * per;
+      st = decode_segment(br, g, T->huff, td, ta, m0, mcus - m0 < per ? mcus - m0 : per, coef.data(), kNatural);
+    }
+  }
+  st = finish_host(P, g, sg, *T, coef, st, 1, bgr, apply_orientation, out);
+  delete T;
+  return st;
 }
 }  // namespace jpegdec
 }  // namespace fe

@@ -3,7 +3,8 @@
     decode_jpegs(engine, blobs)            -> [uint8 [h,w,3] | None]   RGB pixels of each file, in input order
     load_image_from_path(engine, path)     -> (pil_img, img_cv)        the reference's signature, for one file
     decode_groups(engine, blobs, device)   -> the resident batches BatchScorer.process_files scores, and what is left for Pillow
-Each takes progressive=False; True sends complete progressive files through the GPU decoder as well.
+Each takes progressive=False; True sends complete progressive files through the GPU decoder as well. Each takes parallel_entropy=False;
+True decodes a baseline file's long entropy-coded segments with one GPU lane per 128 bytes instead of one per segment (Engine.jpeg_decode).
 
 The reference opens every file with `Image.open`, `ImageOps.exif_transpose` and `convert('RGB')` (:100-103). `fe_jpeg_decode` gives those
 pixels for baseline Huffman JPEG files (YCbCr 4:4:4 / 4:2:2 / 4:2:0 or grayscale, one scan, any tables, with or without restart markers,
@@ -65,12 +66,12 @@ def pillow_rgb(blob, scale=1):
     return None if im is None else np.asarray(im, dtype=np.uint8)
 
 
-def decode_groups(engine, blobs, device=False, progressive=False, scale=1):
+def decode_groups(engine, blobs, device=False, progressive=False, scale=1, parallel_entropy=False):
     """Probe every file, group the decodable ones by output size and decode each group with one fe_jpeg_decode. progressive: a file the
     probe calls progressive (status 1) is probed again for the progressive decoder and, when that takes it, joins the group of its size.
     -> (groups, rest): groups = [(indices, pixels)], pixels a uint8 [k,h,w,3] array or with device=True a (device_ptr, k, h, w) tuple the
     caller frees, holding exactly the images of `indices` in that order; rest = the indices left for Pillow. scale 2, 4, 8: the decode
-    at 1/scale (Engine.jpeg_decode's scale), grouped by scaled size."""
+    at 1/scale (Engine.jpeg_decode's scale), grouped by scaled size. parallel_entropy: Engine.jpeg_decode's; the pixels do not depend on it."""
     if scale not in (1, 2, 4, 8):
         raise ValueError(f"decode_groups: scale {scale!r} (1, 2, 4 or 8)")
     sizes, rest = {}, []
@@ -89,6 +90,8 @@ def decode_groups(engine, blobs, device=False, progressive=False, scale=1):
     flag = dict(progressive=True) if progressive else {}
     if scale != 1:
         flag['scale'] = scale
+    if parallel_entropy:
+        flag['parallel_entropy'] = True
     for (h, w), idx in sizes.items():
         px, status = engine.jpeg_decode([blobs[i] for i in idx], h, w, device=device, **flag)
         good = [k for k in range(len(idx)) if status[k] == 0]
@@ -108,13 +111,14 @@ def decode_groups(engine, blobs, device=False, progressive=False, scale=1):
     return groups, sorted(rest)
 
 
-def decode_jpegs(engine, blobs, progressive=False, scale=1):
+def decode_jpegs(engine, blobs, progressive=False, scale=1, parallel_entropy=False):
     """The RGB pixels of every file (bytes), as uint8 [h,w,3] arrays in input order: what load_image_from_path's pil_img holds, None
     where it fails. progressive: decode complete progressive files on the GPU too; the result is the same either way. scale 2, 4, 8:
-    the pixels of the file drafted to 1/scale (libjpeg's scaled decode), from the GPU or from Pillow alike; grayscale comes back as RGB."""
+    the pixels of the file drafted to 1/scale (libjpeg's scaled decode), from the GPU or from Pillow alike; grayscale comes back as RGB.
+    parallel_entropy: the GPU decodes inside a file's entropy-coded segments in parallel; the result is the same either way."""
     blobs = [bytes(b) for b in blobs]
     out = [None] * len(blobs)
-    groups, rest = decode_groups(engine, blobs, device=False, progressive=progressive, scale=scale)
+    groups, rest = decode_groups(engine, blobs, device=False, progressive=progressive, scale=scale, parallel_entropy=parallel_entropy)
     for idx, px in groups:
         for k, i in enumerate(idx):
             out[i] = px[k]
@@ -123,7 +127,7 @@ def decode_jpegs(engine, blobs, progressive=False, scale=1):
     return out
 
 
-def load_image_from_path(engine, photo_path, progressive=False):
+def load_image_from_path(engine, photo_path, progressive=False, parallel_entropy=False):
     """(pil_img, img_cv): PIL RGB image and BGR array of one file, (None, None) on error - utils/image_loading.py:44-112 for non-RAW files."""
     from PIL import Image
     try:
@@ -133,7 +137,7 @@ def load_image_from_path(engine, photo_path, progressive=False):
     except Exception as e:
         print(f"Error loading image {photo_path}: {e}")
         return None, None
-    rgb = decode_jpegs(engine, [blob], progressive=progressive)[0]
+    rgb = decode_jpegs(engine, [blob], progressive=progressive, parallel_entropy=parallel_entropy)[0]
     if rgb is None:
         return None, None
     return Image.fromarray(rgb), np.ascontiguousarray(rgb[..., ::-1])

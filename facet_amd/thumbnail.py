@@ -162,13 +162,13 @@ def _probe(engine, blob, progressive):
     return info
 
 
-def resize_thumbnails(engine, blobs, size, quality=80, progressive=False):
+def resize_thumbnails(engine, blobs, size, quality=80, progressive=False, parallel_entropy=False):
     """JPEG files (bytes) -> list of bytes in input order: `Image.open(f)`, `thumbnail((size, size), LANCZOS)`, `save(buf, "JPEG",
     quality=quality)` of each, byte for byte, None where Pillow raises. Three-component files the decoder takes are grouped by source
     size and go through fe_jpeg_thumbnail; everything else - grayscale (Pillow keeps mode L and writes a one-component file), CMYK,
     progressive files without progressive=True, files with a comment segment (Pillow copies it), corrupt files - goes through that same
     Pillow recipe, so the bytes never depend on which side did the work. Unlike resize_thumbnail, a file that already fits is encoded
-    again, as Pillow's three calls would."""
+    again, as Pillow's three calls would. parallel_entropy: Engine.jpeg_thumbnail's, for the files the engine takes; the bytes are the same."""
     blobs = [bytes(b) for b in blobs]
     out = [None] * len(blobs)
     groups, rest = {}, []
@@ -180,7 +180,8 @@ def resize_thumbnails(engine, blobs, size, quality=80, progressive=False):
             groups.setdefault((info['width'], info['height']), []).append(i)
     for (w, h), idx in groups.items():
         scale, plan = thumbnail_plan_jpeg(w, h, size)
-        rows, status = engine.jpeg_thumbnail([blobs[i] for i in idx], scale, plan, quality=quality, progressive=progressive)
+        flag = dict(parallel_entropy=True) if parallel_entropy else {}
+        rows, status = engine.jpeg_thumbnail([blobs[i] for i in idx], scale, plan, quality=quality, progressive=progressive, **flag)
         for k, i in enumerate(idx):
             if status[k] == 0:
                 out[i] = rows[k]
@@ -203,16 +204,16 @@ def _jpeg_size(engine, blob):
     return Image.open(io.BytesIO(blob)).size
 
 
-def resize_thumbnail(engine, thumbnail_bytes, size):
+def resize_thumbnail(engine, thumbnail_bytes, size, parallel_entropy=False):
     """The reference's `_resize_thumbnail(thumbnail_bytes, size)` (api/routers/thumbnails.py:54-64) plus the engine: the same bytes
     object when the image is already small enough, else its JPEG at quality 80 with the longer side `size`. Raises where Pillow raises."""
     if max(_jpeg_size(engine, thumbnail_bytes)) <= size:
         return thumbnail_bytes
-    got = resize_thumbnails(engine, [thumbnail_bytes], size)[0]
+    got = resize_thumbnails(engine, [thumbnail_bytes], size, parallel_entropy=parallel_entropy)[0]
     return got if got is not None else pillow_resize_thumbnail(thumbnail_bytes, size)      # raises Pillow's error
 
 
-def downsize_thumbnails(engine, rows, thumbnail_size=320):
+def downsize_thumbnails(engine, rows, thumbnail_size=320, parallel_entropy=False):
     """The body of both loops of the reference's export_viewer_db (db/maintenance.py:182-272) without the database: rows = (key, blob)
     pairs -> yields (new_bytes, key), in input order, for the rows whose image is larger than thumbnail_size; a None blob and a row
     Pillow cannot read are skipped silently."""
@@ -225,6 +226,6 @@ def downsize_thumbnails(engine, rows, thumbnail_size=320):
                 todo.append((key, bytes(blob)))
         except Exception:
             pass      # skip corrupt thumbnails
-    for (key, _), new in zip(todo, resize_thumbnails(engine, [b for _, b in todo], thumbnail_size)):
+    for (key, _), new in zip(todo, resize_thumbnails(engine, [b for _, b in todo], thumbnail_size, parallel_entropy=parallel_entropy)):
         if new is not None:
             yield new, key

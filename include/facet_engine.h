@@ -409,6 +409,19 @@ typedef struct { int32_t width, height, components, hsamp, vsamp, restart_interv
 int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info);
 int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation,
                       int dst_on_device, int flags, uint8_t* dst, int32_t* status);
+/* A second flag bit of fe_jpeg_decode_ex, fe_jpeg_decode_scaled and fe_jpeg_thumbnail, alone or with FE_JPEG_PROGRESSIVE; fe_jpeg_probe_ex
+ * accepts and ignores it. Without it the entropy stage gives a lane to every restart interval, so a file without restart markers is
+ * decoded by one lane. With it, every baseline entropy-coded segment (the whole scan, or one restart interval) of at least two
+ * subsequences of 128 bytes is decoded by one lane per subsequence: self-synchronising Huffman decoding (Weissenberger & Schmidt, ICPP
+ * 2018), in which every lane first decodes from a guessed state, takes over its left neighbour's exit state round by round until no
+ * state changes, and then decodes once more for real. Shorter segments and the scans of progressive files keep the lane per segment.
+ * Pixels, bytes and statuses never depend on the flag: an image in which the parallel decode met an error is decoded again by the serial
+ * kernel inside the same call. */
+#define FE_JPEG_FLAG_PARALLEL 0x100
+/* The entropy stage of the context's last fe_jpeg_decode* / fe_jpeg_thumbnail call: out[0] segments decoded in parallel, out[1] their
+ * subsequences, out[2] the most rounds any segment took, out[3] images decoded again by the serial kernel. All zero without
+ * FE_JPEG_FLAG_PARALLEL. The numbers came back with that call's statuses: this waits for nothing. */
+int fe_jpeg_entropy_stats(fe_ctx* ctx, int32_t out[4]);
 /* The decode at 1/scale that Pillow's `JpegImageFile.draft()` switches on (libjpeg's scale_num / scale_denom), which `Image.thumbnail`
  * calls first on an image that comes from a JPEG file. scale: 1, 2, 4 or 8, anything else returns FE_ERR_INVALID and launches nothing;
  * scale 1 is fe_jpeg_decode_ex bit for bit. h, w: the scaled size, ceil(H / scale) x ceil(W / scale) (fe_jpeg_scaled_size), exchanged

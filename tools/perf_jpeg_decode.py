@@ -1,7 +1,8 @@
 """fe_jpeg_decode rates (profiles/jpeg_decode_perf.txt).
 usage: perf_jpeg_decode.py
   256 x 1024x1024 photo-like files at quality 85, 4:2:0 and 4:2:2, without restart markers and with one per MCU row, and the same
-  sources saved with progressive=True (decoded with FE_JPEG_PROGRESSIVE: one entropy pass per scan); the files are in host memory, the
+  sources saved with progressive=True (decoded with FE_JPEG_PROGRESSIVE: one entropy pass per scan); every baseline configuration a
+  second time with parallel_entropy=True (FE_JPEG_FLAG_PARALLEL: a lane per 128-byte subsequence); the files are in host memory, the
   pixels stay on the device. Per configuration: median of 7 calls (min, max), images/s, and from one profiled call the
   time of each stage (host parse, the upload, entropy, IDCT, colour). Before the GPU is opened: Pillow's decode of the same files on this
   host, one process alone and 16 side by side; afterwards the upload of the decoded pixels, which the CPU route also pays."""
@@ -82,18 +83,28 @@ if __name__ == "__main__":
                   f"{N / max(secs):6.0f} images/s", flush=True)
     e = Engine(0, arena_bytes=8 << 30)
     d = e.dev_alloc(N * HW * HW * 3)
+    rounds = 0
     for label, blobs in files.items():
-        kw = {"progressive": True} if label.startswith("prog") else {}
-        _, status = e.jpeg_decode(blobs, HW, HW, device=d, **kw)
-        assert not status.any(), status
-        med, lo, hi = stats_ms(lambda: e.jpeg_decode(blobs, HW, HW, device=d, **kw))
-        print(f"fe_jpeg_decode {label:18s}: median {med:8.2f} ms (min {lo:.2f}, max {hi:.2f}) for {N} x {HW}x{HW} q{QUALITY}, files in host memory, "
-              f"pixels left on the device = {med * 1e3 / N:7.1f} us/image, {N / med * 1e3:7.0f} images/s", flush=True)
-        e.profile_enable(True)
-        e.jpeg_decode(blobs, HW, HW, device=d, **kw)
-        recs = e.profile_records()
-        e.profile_enable(False)
-        print("    stages of one call: " + "; ".join(f"{r['name'].split(': ')[1]} {r['ms']:.2f} ms" for r in recs), flush=True)
+        # a baseline configuration a second time with FE_JPEG_FLAG_PARALLEL; the scans of a progressive file stay a lane per segment
+        for par in ((False,) if label.startswith("prog") else (False, True)):
+            kw = {"progressive": True} if label.startswith("prog") else ({"parallel_entropy": True} if par else {})
+            name = label + (" parallel" if par else "")
+            _, status = e.jpeg_decode(blobs, HW, HW, device=d, **kw)
+            assert not status.any(), status
+            med, lo, hi = stats_ms(lambda: e.jpeg_decode(blobs, HW, HW, device=d, **kw))
+            print(f"fe_jpeg_decode {name:22s}: median {med:8.2f} ms (min {lo:.2f}, max {hi:.2f}) for {N} x {HW}x{HW} q{QUALITY}, files in host memory, "
+                  f"pixels left on the device = {med * 1e3 / N:7.1f} us/image, {N / med * 1e3:7.0f} images/s", flush=True)
+            e.profile_enable(True)
+            e.jpeg_decode(blobs, HW, HW, device=d, **kw)
+            recs = e.profile_records()
+            e.profile_enable(False)
+            print("    stages of one call: " + "; ".join(f"{r['name'].split(': ')[1]} {r['ms']:.2f} ms" for r in recs), flush=True)
+            if par:
+                st = e.jpeg_entropy_stats()
+                rounds = max(rounds, st["max_rounds"])
+                print(f"    parallel entropy: {st['parallel_segments']} segments, {st['subsequences']} subsequences, most rounds of a segment "
+                      f"{st['max_rounds']}, images decoded again {st['redone']}", flush=True)
+    print(f"parallel entropy: most rounds of any segment over all configurations {rounds}", flush=True)
     px = np.random.default_rng(0).integers(0, 256, (N, HW, HW, 3), dtype=np.uint8)
     med, lo, hi = stats_ms(lambda: e.h2d(d, px))
     print(f"upload of {N} decoded images ({px.nbytes / 1e6:.0f} MB, pageable host memory): median {med:.2f} ms (min {lo:.2f}, max {hi:.2f}) = "

@@ -3,7 +3,8 @@ usage: perf_thumbnail_transcode.py [out.txt]
   512 thumbnails as Pillow writes them (256 of 640x427 and 256 of 427x640, photo-like, quality 80) to the sizes 320, 160 (draft() keeps
   scale 1) and 100 (scale 2). Per size: resize_thumbnails over all 512 (two fe_jpeg_thumbnail calls, grouping and the Python bytes
   objects included), median of 7 (min, max), and from one profiled call per source shape the time of each stage (host parse, upload,
-  entropy, IDCT, colour, then reduce / resize / encode as one remainder). Before the GPU is opened: the reference's Pillow recipe on this
+  entropy, IDCT, colour, then reduce / resize / encode as one remainder), first with the lane-per-segment entropy stage and then with
+  parallel_entropy=True (FE_JPEG_FLAG_PARALLEL), whose rows carry that name. Before the GPU is opened: the reference's Pillow recipe on this
   host, one process alone and 16 side by side. The table goes to stdout and, when a path is given, into that file as well."""
 import io
 import os
@@ -86,26 +87,34 @@ if __name__ == "__main__":
             say(f"Pillow -> {size:3d} (draft scale {draft_scale(640, 427, size)}): one process alone {one * 1e3:6.2f} ms/file ({1 / one:5.0f} files/s); "
                 f"16 processes side by side, 32 files each: slowest loop {max(secs):.3f} s = {N / max(secs):6.0f} files/s")
     e = Engine(0, arena_bytes=4 << 30)
-    for size in TARGETS:
-        got = resize_thumbnails(e, files, size)
-        assert got[:4] == [pillow_resize_thumbnail(b, size) for b in files[:4]], "not Pillow's bytes"
-        med, lo, hi = stats_ms(lambda: resize_thumbnails(e, files, size))
-        say(f"resize_thumbnails -> {size:3d} (draft scale {draft_scale(640, 427, size)}): median {med:8.2f} ms (min {lo:.2f}, max {hi:.2f}) for {N} files, "
-            f"{sum(len(b) for b in got) / 1e6:.2f} MB of JPEG back = {med * 1e3 / N:7.1f} us/file, {N / med * 1e3:7.0f} files/s")
-        for (w, h) in SHAPES:
-            group = [b for i, b in enumerate(files) if SHAPES[i % 2] == (w, h)]
-            scale, plan = thumbnail_plan_jpeg(w, h, size)
-            t0 = time.perf_counter()
-            e.jpeg_thumbnail(group, scale, plan)
-            plain = (time.perf_counter() - t0) * 1e3
-            e.profile_enable(True)
-            e.jpeg_thumbnail(group, scale, plan)
-            recs = e.profile_records()
-            e.profile_enable(False)
-            dec = [r for r in recs if r["name"].startswith("jpeg_decode")]
-            say(f"    fe_jpeg_thumbnail {w}x{h} -> {plan.size[0]}x{plan.size[1]}, {len(group)} files, one call {plain:.2f} ms; decode stages: "
-                + "; ".join(f"{r['name'].split(': ')[1]} {r['ms']:.2f} ms" for r in dec)
-                + f"; reduce + resize + encode + copies back: the remaining {plain - sum(r['ms'] for r in dec):.2f} ms")
+    for par in (False, True):            # the lane-per-segment entropy stage, then FE_JPEG_FLAG_PARALLEL: one lane per 128-byte subsequence
+        kw, tag = (dict(parallel_entropy=True), " parallel_entropy") if par else ({}, "")
+        rounds = redone = 0
+        for size in TARGETS:
+            got = resize_thumbnails(e, files, size, **kw)
+            assert got[:4] == [pillow_resize_thumbnail(b, size) for b in files[:4]], "not Pillow's bytes"
+            med, lo, hi = stats_ms(lambda: resize_thumbnails(e, files, size, **kw))
+            say(f"resize_thumbnails{tag} -> {size:3d} (draft scale {draft_scale(640, 427, size)}): median {med:8.2f} ms (min {lo:.2f}, max {hi:.2f}) for {N} files, "
+                f"{sum(len(b) for b in got) / 1e6:.2f} MB of JPEG back = {med * 1e3 / N:7.1f} us/file, {N / med * 1e3:7.0f} files/s")
+            for (w, h) in SHAPES:
+                group = [b for i, b in enumerate(files) if SHAPES[i % 2] == (w, h)]
+                scale, plan = thumbnail_plan_jpeg(w, h, size)
+                t0 = time.perf_counter()
+                e.jpeg_thumbnail(group, scale, plan, **kw)
+                plain = (time.perf_counter() - t0) * 1e3
+                e.profile_enable(True)
+                e.jpeg_thumbnail(group, scale, plan, **kw)
+                recs = e.profile_records()
+                e.profile_enable(False)
+                st = e.jpeg_entropy_stats()
+                rounds, redone = max(rounds, st['max_rounds']), redone + st['redone']
+                dec = [r for r in recs if r["name"].startswith("jpeg_decode")]
+                say(f"    fe_jpeg_thumbnail{tag} {w}x{h} -> {plan.size[0]}x{plan.size[1]}, {len(group)} files, one call {plain:.2f} ms; decode stages: "
+                    + "; ".join(f"{r['name'].split(': ')[1]} {r['ms']:.2f} ms" for r in dec)
+                    + f"; reduce + resize + encode + copies back: the remaining {plain - sum(r['ms'] for r in dec):.2f} ms")
+        if par:
+            say(f"parallel_entropy: {st['parallel_segments']} segments / {st['subsequences']} subsequences in the last call, "
+                f"most rounds of any segment in the profiled calls {rounds}, images decoded again by the serial kernel {redone}")
     e.close()
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
