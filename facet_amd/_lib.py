@@ -16,7 +16,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACET_AMD_LIB") or os.path.join(_HERE, "libfacet_engine.so")   # env: developer A/B builds only
 
 FE_MODEL_TOPIQ, FE_MODEL_CLIP, FE_MODEL_SAMP, FE_MODEL_U2NETP, FE_MODEL_AESTHETIC, FE_MODEL_VLM = range(6)
-FE_MODEL_SCRFD, FE_MODEL_ARCFACE = 5, 6
 FE_RECORD_FLOATS = 789
 FE_GRAPH_FACE_DET, FE_GRAPH_FACE_LMK, FE_GRAPH_FACE_REC = 0, 1, 2
 FE_FACE_FLOATS = 739

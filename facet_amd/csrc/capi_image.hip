@@ -1,0 +1,511 @@
+// C ABI: image-level work without a model - PIL resize and reduce, thumbnails, JPEG encode / probe / decode, pHash, statistics, lines,
+// contours, subject region.
+#include "capi_internal.h"
+#include "lines_host.h"
+#include <thread>
+
+namespace {
+// What fe_resize_u8, fe_resize_u8_box and fe_reduce_u8 do around their launch: a host batch goes through the arena, in and out.
+template <class Launch>
+void resize_staged(Ctx& C, const uint8_t* src, size_t in_b, uint8_t* dst, size_t out_b, int on_device, Launch&& launch) {
+  C.arena.reset();
+  const uint8_t* d_in = resident(C, src, in_b, on_device);
+  uint8_t* d_out = on_device ? dst : (uint8_t*)C.arena.alloc(out_b);
+  launch(d_in, d_out);
+  if (!on_device) FE_HIP(hipMemcpyAsync(dst, d_out, out_b, hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+}
+
+// ---- thumbnails: reduce -> boxed LANCZOS resize -> baseline JPEG, one chain on the device ----------------------------------------
+struct ThumbPlan { int oh, ow, fx, fy; int rbox[4]; float box[4]; int tall; };
+ThumbPlan make_thumb_plan(int oh, int ow, int fx, int fy, const int32_t* reduce_box, const float* resize_box, int tall) {
+  ThumbPlan p;
+  p.oh = oh; p.ow = ow; p.fx = fx; p.fy = fy; p.tall = tall;
+  for (int i = 0; i < 4; ++i) { p.rbox[i] = reduce_box ? reduce_box[i] : 0; p.box[i] = resize_box[i]; }
+  return p;
+}
+// plan NULL: the images are encoded as they are. out [n][cap] and lengths [n] are host buffers.
+void thumbnail_run(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, const ThumbPlan* plan, int quality,
+                   uint8_t* out, size_t cap, int32_t* lengths) {
+  Ctx& C = ctx->c;
+  int rh = h, rw = w, oh = h, ow = w;
+  bool do_reduce = false, do_resize = false;
+  if (plan) {
+    oh = plan->oh; ow = plan->ow;
+    do_reduce = plan->fx > 1 || plan->fy > 1;
+    if (do_reduce) {
+      FE_CHECK(plan->rbox[0] >= 0 && plan->rbox[1] >= 0 && plan->rbox[2] <= w && plan->rbox[3] <= h && plan->rbox[0] < plan->rbox[2] && plan->rbox[1] < plan->rbox[3],
+               "thumbnail: reduce box outside the image or empty");
+      rw = (plan->rbox[2] - plan->rbox[0] + plan->fx - 1) / plan->fx;
+      rh = (plan->rbox[3] - plan->rbox[1] + plan->fy - 1) / plan->fy;
+    }
+    do_resize = oh != rh || ow != rw || plan->box[0] != 0.0f || plan->box[1] != 0.0f || plan->box[2] != (float)rw || plan->box[3] != (float)rh;
+  }
+  FE_CHECK(oh > 0 && ow > 0 && oh <= 65535 && ow <= 65535, "thumbnail: bad output size %d x %d", ow, oh);
+  const size_t dcap = std::min(cap, jpeg_bound(oh, ow));      // no encode is longer, so the device rows need not be
+  const size_t per_in = (size_t)h * w * 3;
+  const size_t per = (do_reduce ? (size_t)rh * rw * 3 : 0) + (do_resize ? (size_t)rh * ow * 3 + (size_t)rw * oh * 3 + (size_t)oh * ow * 3 : 0) +
+                     jpeg_scratch_bytes(oh, ow) + dcap + 2048;
+  const size_t budget = std::min<size_t>((size_t)1 << 30, C.arena.capacity() - C.arena.capacity() / 8);
+  int mb = (int)std::max<size_t>(1, std::min<size_t>(256, budget / per));
+  if (!on_device) mb = (int)std::max<size_t>(1, std::min<size_t>(mb, ((size_t)1 << 30) / per_in));
+  std::vector<int32_t> lens(n);
+  ImageStager st(ctx, img, n, per_in, mb, on_device);
+  bool overflow = false;
+  for (int k = 0; k < st.chunks(); ++k) {
+    const int i0 = k * mb, nb = st.count(k);
+    C.arena.reset();
+    const uint8_t* cur = st.get(k);
+    if (do_reduce) {
+      uint8_t* d = (uint8_t*)C.arena.alloc((size_t)nb * rh * rw * 3);
+      reduce_u8(C, cur, nb, h, w, plan->fx, plan->fy, plan->rbox, d);
+      cur = d;
+    }
+    if (do_resize) {
+      uint8_t* d = (uint8_t*)C.arena.alloc((size_t)nb * oh * ow * 3);
+      if (plan->tall) {      // Image.resize's two calls for images more than 100 times taller than wide: rows first, then columns
+        uint8_t* mid = (uint8_t*)C.arena.alloc((size_t)nb * oh * rw * 3);
+        const float b1[4] = {0.0f, plan->box[1], (float)rw, plan->box[3]}, b2[4] = {plan->box[0], 0.0f, plan->box[2], (float)oh};
+        resize_u8_box(C, cur, nb, rh, rw, oh, rw, FE_FILTER_LANCZOS, b1, mid);
+        resize_u8_box(C, mid, nb, oh, rw, oh, ow, FE_FILTER_LANCZOS, b2, d);
+      } else {
+        resize_u8_box(C, cur, nb, rh, rw, oh, ow, FE_FILTER_LANCZOS, plan->box, d);
+      }
+      cur = d;
+    }
+    uint8_t* d_out = (uint8_t*)C.arena.alloc((size_t)nb * dcap);
+    int32_t* d_len = (int32_t*)C.arena.alloc((size_t)nb * sizeof(int32_t));
+    launch_jpeg_encode(C, cur, nb, oh, ow, bgr ? 1 : 0, quality, d_out, dcap, d_len);
+    st.done(k);
+    FE_HIP(hipMemcpyAsync(lens.data() + i0, d_len, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    for (int i = 0; i < nb; ++i) {
+      const int32_t len = lens[i0 + i];
+      lengths[i0 + i] = len;
+      if (len <= 0 || (size_t)len > cap) { overflow = true; continue; }
+      FE_HIP(hipMemcpyAsync(out + (size_t)(i0 + i) * cap, d_out + (size_t)i * dcap, (size_t)len, hipMemcpyDeviceToHost, C.stream));
+    }
+    FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next chunk
+  }
+  if (overflow) {
+    char b[160];
+    snprintf(b, sizeof(b), "jpeg: an image needs more than the %zu bytes of its output row (fe_jpeg_bound(%d, %d) = %zu always fits)", cap, oh, ow, jpeg_bound(oh, ow));
+    throw CapacityError(b);
+  }
+}
+
+bool jpeg_scale_ok(int scale) { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
+
+// the two division tables of cv2's 8-bit HSV conversion, made once per context (fe_image_stats, fe_subject_region)
+void ensure_hsv_tables(fe_ctx* ctx) {
+  if (ctx->hsv_sdiv) return;
+  std::vector<int> sd, hd;
+  cv_hsv_tables(sd, hd);
+  FE_HIP(hipMalloc((void**)&ctx->hsv_sdiv, 256 * sizeof(int)));
+  ctx->misc_allocs.push_back(ctx->hsv_sdiv);
+  FE_HIP(hipMalloc((void**)&ctx->hsv_hdiv, 256 * sizeof(int)));
+  ctx->misc_allocs.push_back(ctx->hsv_hdiv);
+  FE_HIP(hipMemcpy(ctx->hsv_sdiv, sd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
+  FE_HIP(hipMemcpy(ctx->hsv_hdiv, hd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
+}
+
+// Brings the contour records of one micro-batch to the host: counts [nb] exact; records [nb][max_contours][8], per image the first
+// max_contours in descending start_index order. The device list holds every qualifying contour (its capacity is the largest number
+// of components an image can have), in the order the walks finished, so the order is made here.
+void collect_contours(fe_ctx* ctx, const ContourScratch& sc, int nb, int h, int w, int max_contours, long long* records, int* counts) {
+  Ctx& C = ctx->c;
+  const int cap = contour_work_cap(h, w);
+  std::vector<int> found(nb), listed(nb);
+  int err = 0;
+  FE_HIP(hipMemcpyAsync(found.data(), sc.rec_count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipMemcpyAsync(listed.data(), sc.work_count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipMemcpyAsync(&err, sc.error, sizeof(int), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+  FE_CHECK(!(err & 1), "contours: a border walk did not close within 8 * pixels + 8 steps");
+  FE_CHECK(!(err & 2), "contours: more component roots than an image can hold");
+  std::vector<std::vector<long long>> got(nb);
+  for (int i = 0; i < nb; ++i) {
+    FE_CHECK(found[i] >= 0 && found[i] <= listed[i] && listed[i] <= cap, "contours: inconsistent counts (%d of %d, room %d)", found[i], listed[i], cap);
+    counts[i] = found[i];
+  }
+  for (int i = 0; i < nb; ++i) {      // nothing below throws while a copy into `got` is in flight
+    if (!found[i]) continue;
+    got[i].resize((size_t)found[i] * FE_CONTOUR_RECORD);
+    FE_HIP(hipMemcpyAsync(got[i].data(), sc.recs + (size_t)i * cap * FE_CONTOUR_RECORD, got[i].size() * sizeof(long long), hipMemcpyDeviceToHost,
+                          C.stream));
+  }
+  FE_HIP(hipStreamSynchronize(C.stream));
+  struct Rec { long long f[FE_CONTOUR_RECORD]; };
+  for (int i = 0; i < nb; ++i) {
+    if (!found[i]) continue;
+    Rec* r = reinterpret_cast<Rec*>(got[i].data());
+    std::sort(r, r + found[i], [](const Rec& a, const Rec& b) { return a.f[0] > b.f[0]; });
+    const size_t keep = (size_t)std::min(found[i], max_contours);
+    memcpy(records + (size_t)i * max_contours * FE_CONTOUR_RECORD, r, keep * sizeof(Rec));
+  }
+}
+
+// images per micro-batch such that `per_image` bytes each fit the arena with room to spare
+int contour_microbatch(fe_ctx* ctx, int n, size_t per_image) {
+  const size_t room = ctx->c.arena.capacity() / 8 * 7;
+  FE_CHECK(per_image + 4096 <= room, "contours: one image needs %zu bytes of workspace, the arena holds %zu", per_image, ctx->c.arena.capacity());
+  return (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)64, room / (per_image + 4096)}));
+}
+}  // namespace
+
+extern "C" {
+
+// device u8 batch -> device u8 batch resized like PIL (+ crop)
+int fe_resize_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, int ow, int filter, int on_device,
+                 uint8_t* dst) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(src && dst && n > 0, "bad arguments");
+    resize_staged(C, src, (size_t)n * h * w * 3, dst, (size_t)n * oh * ow * 3, on_device,
+                  [&](const uint8_t* d_in, uint8_t* d_out) { resize_u8(C, d_in, n, h, w, oh, ow, filter, 0, oh, 0, ow, d_out); });
+  });
+}
+
+/* PIL `resize((ow, oh), filter, box)` with a fractional source box (x0, y0, x1, y1); box NULL = the whole image */
+int fe_resize_u8_box(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int oh, int ow, int filter, const float* box, int on_device,
+                     uint8_t* dst) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(src && dst && n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "bad arguments");
+    const float whole[4] = {0.0f, 0.0f, (float)w, (float)h};
+    resize_staged(C, src, (size_t)n * h * w * 3, dst, (size_t)n * oh * ow * 3, on_device,
+                  [&](const uint8_t* d_in, uint8_t* d_out) { resize_u8_box(C, d_in, n, h, w, oh, ow, filter, box ? box : whole, d_out); });
+  });
+}
+
+/* PIL `reduce((fx, fy), box)`: dst [n, ceil(bh / fy), ceil(bw / fx), 3]; box (x0, y0, x1, y1) in pixels, NULL = the whole image */
+int fe_reduce_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w, int fx, int fy, const int32_t* box, int on_device, uint8_t* dst) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(src && dst && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1, "bad arguments");
+    const int b[4] = {box ? box[0] : 0, box ? box[1] : 0, box ? box[2] : w, box ? box[3] : h};
+    FE_CHECK(b[0] >= 0 && b[1] >= 0 && b[2] <= w && b[3] <= h && b[0] < b[2] && b[1] < b[3], "reduce: box outside the image or empty");
+    const int ow = (b[2] - b[0] + fx - 1) / fx, oh = (b[3] - b[1] + fy - 1) / fy;
+    resize_staged(C, src, (size_t)n * h * w * 3, dst, (size_t)n * oh * ow * 3, on_device,
+                  [&](const uint8_t* d_in, uint8_t* d_out) { reduce_u8(C, d_in, n, h, w, fx, fy, b, d_out); });
+  });
+}
+
+size_t fe_jpeg_bound(int h, int w) { return (h > 0 && w > 0) ? jpeg_bound(h, w) : 0; }
+
+/* what Pillow's `Image.save(buf, "JPEG", quality=q)` writes for each RGB (bgr = 1: B,G,R bytes) image of the batch */
+int fe_jpeg_encode(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int quality, uint8_t* out, size_t cap,
+                   int32_t* lengths) {
+  return fe_api(ctx, OnError::Capacity, [&] {
+    FE_CHECK(img && out && lengths && n > 0 && h > 0 && w > 0, "bad arguments");
+    thumbnail_run(ctx, img, n, h, w, bgr, on_device, nullptr, quality, out, cap, lengths);
+  });
+}
+
+/* the reference's generate_photo_thumbnail (utils/image_transforms.py:32-50) for a batch, with the plan of facet_amd.thumbnail.thumbnail_plan */
+int fe_thumbnail_jpeg(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, int oh, int ow, int fx, int fy,
+                      const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  return fe_api(ctx, OnError::Capacity, [&] {
+    FE_CHECK(img && out && lengths && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1, "bad arguments");
+    FE_CHECK((fx == 1 && fy == 1) || reduce_box, "thumbnail: reduce factors without a reduce box");
+    const ThumbPlan p = make_thumb_plan(oh, ow, fx, fy, reduce_box, resize_box, tall);
+    thumbnail_run(ctx, img, n, h, w, bgr, on_device, &p, quality, out, cap, lengths);
+  });
+}
+
+/* ---- JPEG decode: what `ImageOps.exif_transpose(Image.open(f)).convert('RGB')` gives, from the file's bytes ---- */
+int fe_jpeg_probe_ex(const uint8_t* data, size_t len, int flags, fe_jpeg_info_ex* info) {
+  if (!info || (flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL))) return FE_ERR_INVALID;      // the parser has no use for the second
+  try {
+    int32_t v[10];
+    static const uint8_t none[1] = {0};
+    jpeg_probe(data ? data : none, data ? len : 0, flags, v);
+    info->width = v[0]; info->height = v[1]; info->components = v[2]; info->hsamp = v[3]; info->vsamp = v[4];
+    info->restart_interval = v[5]; info->orientation = v[6]; info->status = v[7]; info->progressive = v[8]; info->scans = v[9];
+  } catch (const std::exception&) {
+    return FE_ERR_RUNTIME;
+  }
+  return FE_OK;
+}
+
+int fe_jpeg_probe(const uint8_t* data, size_t len, fe_jpeg_info* info) {
+  if (!info) return FE_ERR_INVALID;
+  fe_jpeg_info_ex x;
+  const int rc = fe_jpeg_probe_ex(data, len, 0, &x);
+  if (rc != FE_OK) return rc;
+  info->width = x.width; info->height = x.height; info->components = x.components; info->hsamp = x.hsamp; info->vsamp = x.vsamp;
+  info->restart_interval = x.restart_interval; info->orientation = x.orientation; info->status = x.status;
+  return FE_OK;
+}
+
+int fe_jpeg_decode(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                   uint8_t* dst, int32_t* status) {
+  return fe_api(ctx, [&] {
+    FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0, "bad arguments");
+    jpeg_decode_batch(ctx->c, data, len, n, h, w, 1, bgr, apply_orientation, dst_on_device, 0, dst, status);
+  });
+}
+
+int fe_jpeg_decode_ex(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int bgr, int apply_orientation, int dst_on_device,
+                      int flags, uint8_t* dst, int32_t* status) {
+  return fe_api(ctx, [&] {
+    FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)), "bad arguments");
+    jpeg_decode_batch(ctx->c, data, len, n, h, w, 1, bgr, apply_orientation, dst_on_device, flags, dst, status);
+  });
+}
+
+/* what the entropy stage of the context's last decode call did; read back with that call's statuses, so nothing is waited for here */
+int fe_jpeg_entropy_stats(fe_ctx* ctx, int32_t out[4]) {
+  if (!ctx || !out) return FE_ERR_INVALID;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->c.jpeg_entropy_stats[k];
+  return FE_OK;
+}
+
+int fe_jpeg_scaled_size(int h, int w, int scale, int32_t* sh, int32_t* sw) {
+  if (!sh || !sw || h <= 0 || w <= 0 || !jpeg_scale_ok(scale)) return FE_ERR_INVALID;
+  int a, b;
+  jpeg_scaled_size(h, w, scale, &a, &b);
+  *sh = a; *sw = b;
+  return FE_OK;
+}
+
+/* libjpeg's 1/scale decode, which is what Pillow's JpegImageFile.draft() switches on: scale 1 is fe_jpeg_decode_ex */
+int fe_jpeg_decode_scaled(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int bgr, int apply_orientation,
+                          int dst_on_device, int flags, uint8_t* dst, int32_t* status) {
+  return fe_api(ctx, [&] {
+    if (!jpeg_scale_ok(scale)) {
+      ctx->c.err = "jpeg_decode_scaled: scale " + std::to_string(scale) + " (1, 2, 4 or 8)";
+      return FE_ERR_INVALID;
+    }
+    FE_CHECK(data && len && dst && status && n > 0 && h > 0 && w > 0 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)), "bad arguments");
+    jpeg_decode_batch(ctx->c, data, len, n, h, w, scale, bgr, apply_orientation, dst_on_device, flags, dst, status);
+    return FE_OK;
+  });
+}
+
+/* stored JPEG bytes -> smaller JPEG bytes: `Image.open(f)`, `thumbnail((size, size), LANCZOS)`, `save("JPEG", quality)` (reference
+ * db/maintenance.py:182-272, api/routers/thumbnails.py:54-64) as scaled decode -> reduce -> boxed LANCZOS -> encode on one resident buffer */
+int fe_jpeg_thumbnail(fe_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, int h, int w, int scale, int flags, int oh, int ow, int fx,
+                      int fy, const int32_t* reduce_box, const float* resize_box, int tall, int quality, uint8_t* out, size_t cap, int32_t* lengths,
+                      int32_t* status) {
+  return fe_api(ctx, OnError::Capacity, [&] {
+    if (!jpeg_scale_ok(scale)) {
+      ctx->c.err = "jpeg_thumbnail: scale " + std::to_string(scale) + " (1, 2, 4 or 8)";
+      return FE_ERR_INVALID;
+    }
+    FE_CHECK(data && len && out && lengths && status && resize_box && n > 0 && h > 0 && w > 0 && fx >= 1 && fy >= 1 && !(flags & ~(FE_JPEG_PROGRESSIVE | FE_JPEG_FLAG_PARALLEL)),
+             "bad arguments");
+    FE_CHECK((fx == 1 && fy == 1) || reduce_box, "jpeg_thumbnail: reduce factors without a reduce box");
+    const ThumbPlan p = make_thumb_plan(oh, ow, fx, fy, reduce_box, resize_box, tall);
+    Ctx& C = ctx->c;
+    struct DevBuf {
+      uint8_t* p = nullptr;
+      ~DevBuf() { if (p) (void)hipFree(p); }
+    } px;                                                      // the decoded batch: outside the arena, which both stages recycle
+    const size_t per = (size_t)h * w * 3;
+    FE_HIP(hipMalloc((void**)&px.p, (size_t)n * per));
+    jpeg_decode_batch(C, data, len, n, h, w, scale, 0, 0, 1, flags, px.p, status);      // no EXIF transpose: Image.open + thumbnail does none
+    std::vector<int> good;
+    for (int i = 0; i < n; ++i) {
+      lengths[i] = 0;
+      if (status[i] == 0) good.push_back(i);
+    }
+    const int ng = (int)good.size();
+    for (int k = 0; k < ng; ++k)                               // close the holes files with a status left: slot good[k] >= k moves down to k
+      if (good[k] != k) FE_HIP(hipMemcpyAsync(px.p + (size_t)k * per, px.p + (size_t)good[k] * per, per, hipMemcpyDeviceToDevice, C.stream));
+    auto spread = [&]() {                                      // rows and lengths 0 .. ng - 1 back to their files' places, last first
+      for (int k = ng - 1; k >= 0; --k) {
+        if (good[k] == k) continue;
+        if (lengths[k] > 0 && (size_t)lengths[k] <= cap) memmove(out + (size_t)good[k] * cap, out + (size_t)k * cap, (size_t)lengths[k]);
+        lengths[good[k]] = lengths[k];
+        lengths[k] = 0;
+      }
+    };
+    if (ng) {
+      try {
+        thumbnail_run(ctx, px.p, ng, h, w, 0, 1, &p, quality, out, cap, lengths);
+      } catch (const CapacityError&) {
+        spread();
+        throw;
+      }
+      spread();
+    }
+    return FE_OK;
+  });
+}
+
+/* External contours of binary images: labelling, RETR_EXTERNAL test and border sums on the device (kernels_contours.hip) */
+int fe_external_contours(fe_ctx* ctx, const uint8_t* binary, int n, int h, int w, int on_device, long long min_twice_area, int max_contours,
+                         long long* records, int* counts) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(binary && records && counts && n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 30) && max_contours > 0 && min_twice_area >= 0,
+             "bad arguments");
+    const size_t npx = (size_t)h * w;
+    const int mb = contour_microbatch(ctx, n, contour_scratch_bytes(1, h, w));
+    ImageStager st(ctx, binary, n, npx, mb, on_device);
+    for (int k = 0; k < st.chunks(); ++k) {
+      const int i0 = k * mb, nb = st.count(k);
+      C.arena.reset();
+      const uint8_t* d_in = st.get(k);
+      ContourScratch sc;
+      contour_scratch_carve(sc, C.arena.alloc(contour_scratch_bytes(nb, h, w)), nb, h, w);
+      launch_external_contours(d_in, nb, h, w, 0, min_twice_area, sc, C.stream);
+      st.done(k);
+      collect_contours(ctx, sc, nb, h, w, max_contours, records + (size_t)i0 * max_contours * FE_CONTOUR_RECORD, counts + i0);
+    }
+  });
+}
+
+/* Subject region (reference analyzers/composition.py:16-93): median thresholds, Canny, hysteresis, external contours - all on the device */
+int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int max_contours, long long* records, int* counts,
+                      int* thresholds, uint8_t* edges_out) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(bgr && records && counts && n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 30) && max_contours > 0, "bad arguments");
+    ensure_hsv_tables(ctx);
+    const size_t npx = (size_t)h * w, per = npx * 3;
+    const long long min_twice_area = ((long long)npx + 4999) / 5000;      // smallest a with a * 5000 >= h * w  (area > h * w * 0.0001, not strict)
+    const size_t per_image = contour_scratch_bytes(1, h, w) + 8 * npx + stats_accum_bytes(1) + FE_STATS_COUNT * sizeof(double) + 2048;
+    const int mb = contour_microbatch(ctx, n, per_image);
+    ImageStager st(ctx, bgr, n, per, mb, on_device);
+    for (int k = 0; k < st.chunks(); ++k) {
+      const int i0 = k * mb, nb = st.count(k);
+      C.arena.reset();
+      const uint8_t* d_in = st.get(k);
+      uint8_t* d_gray = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+      void* d_acc = C.arena.alloc(stats_accum_bytes(nb));
+      double* d_stats = (double*)C.arena.alloc((size_t)nb * FE_STATS_COUNT * sizeof(double));
+      int* d_thr = (int*)C.arena.alloc((size_t)nb * 2 * sizeof(int));
+      void* d_grad = C.arena.alloc((size_t)nb * npx * 4);
+      void* d_mag = C.arena.alloc((size_t)nb * npx * 2);
+      uint8_t* d_map = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+      ContourScratch sc;
+      contour_scratch_carve(sc, C.arena.alloc(contour_scratch_bytes(nb, h, w)), nb, h, w);
+      // gray and its histogram come from the statistics pass, so the conversion exists once
+      launch_image_stats(d_in, nb, h, w, d_gray, nullptr, ctx->hsv_sdiv, ctx->hsv_hdiv, d_acc, d_stats, C.stream);
+      st.done(k);
+      launch_median_thresholds(d_stats, nb, (long long)npx, d_thr, C.stream);
+      launch_canny_map_gray(d_gray, nb, h, w, d_thr, d_grad, d_mag, d_map, C.stream);
+      launch_external_contours(d_map, nb, h, w, 1, min_twice_area, sc, C.stream);
+      if (thresholds) FE_HIP(hipMemcpyAsync(thresholds + (size_t)i0 * 2, d_thr, (size_t)nb * 2 * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+      if (edges_out) FE_HIP(hipMemcpyAsync(edges_out + (size_t)i0 * npx, sc.edge, (size_t)nb * npx, hipMemcpyDeviceToHost, C.stream));
+      collect_contours(ctx, sc, nb, h, w, max_contours, records + (size_t)i0 * max_contours * FE_CONTOUR_RECORD, counts + i0);
+    }
+  });
+}
+
+/* Per-image technical statistics of a BGR batch (reference analyzers/image_cache.py:28-33 + analyzers/technical.py) */
+int fe_image_stats(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, double* stats, uint8_t* gray_out, uint8_t* hsv_out) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(bgr && stats && n > 0 && h > 0 && w > 0, "bad arguments");
+    ensure_hsv_tables(ctx);
+    const size_t per = (size_t)h * w * 3, npx = (size_t)h * w;
+    // two blocks per image in pass 1: large chunks keep all 256 CUs busy (the footprint is only ~2-5 bytes per pixel)
+    const int mb = std::max(1, std::max(ctx->microbatch, 256));
+    ImageStager st(ctx, bgr, n, per, mb, on_device);
+    for (int k = 0; k < st.chunks(); ++k) {
+      const int i0 = k * mb, nb = st.count(k);
+      C.arena.reset();
+      const uint8_t* d_in = st.get(k);
+      uint8_t* d_gray = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+      uint8_t* d_hsv = hsv_out ? (uint8_t*)C.arena.alloc((size_t)nb * per) : nullptr;
+      void* d_acc = C.arena.alloc(stats_accum_bytes(nb));
+      double* d_out = (double*)C.arena.alloc((size_t)nb * FE_STATS_COUNT * sizeof(double));
+      launch_image_stats(d_in, nb, h, w, d_gray, d_hsv, ctx->hsv_sdiv, ctx->hsv_hdiv, d_acc, d_out, C.stream);
+      st.done(k);
+      FE_HIP(hipMemcpyAsync(stats + (size_t)i0 * FE_STATS_COUNT, d_out, (size_t)nb * FE_STATS_COUNT * sizeof(double), hipMemcpyDeviceToHost, C.stream));
+      if (gray_out) FE_HIP(hipMemcpyAsync(gray_out + (size_t)i0 * npx, d_gray, (size_t)nb * npx, hipMemcpyDeviceToHost, C.stream));
+      if (hsv_out) FE_HIP(hipMemcpyAsync(hsv_out + (size_t)i0 * per, d_hsv, (size_t)nb * per, hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next micro-batch
+    }
+  });
+}
+
+/* RGB <-> BGR copy of a packed uint8 batch into device memory */
+int fe_swap_rb_u8(fe_ctx* ctx, const uint8_t* src, int on_device, size_t pixels, uint8_t* dst_device) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(src && dst_device && pixels > 0, "bad arguments");
+    if (on_device) {
+      FE_CHECK(src != dst_device, "swap_rb: in-place is not supported");
+      launch_swap_rb_u8(src, dst_device, pixels, C.stream);
+    } else {                                   // stage through the destination: upload, then swap each pixel's ends in a second buffer-free pass
+      C.arena.reset();
+      launch_swap_rb_u8(upload(C, src, pixels * 3), dst_device, pixels, C.stream);
+    }
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+/* Leading lines (reference analyzers/composition.py:191-261): blur + Canny map on the GPU, hysteresis + probabilistic Hough per image on host threads */
+int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int canny_low, int canny_high, int threshold,
+                     int min_line_length, int max_line_gap, int max_lines, int* lines, int* counts, uint8_t* edges_out) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(bgr && n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 30), "bad arguments");
+    FE_CHECK((lines != nullptr) == (counts != nullptr) && (lines || edges_out), "pass lines AND counts, and / or edges_out");
+    FE_CHECK(!lines || max_lines > 0, "max_lines must be positive");
+    FE_CHECK(canny_low >= 0 && canny_high >= canny_low && threshold > 0 && min_line_length >= 0 && max_line_gap >= 0, "bad thresholds");
+    const size_t npx = (size_t)h * w, per = npx * 3;
+    const int mb = std::max(1, std::min(n, 64));
+    const int threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<uint8_t> scratch;
+    if (!edges_out) scratch.resize((size_t)mb * npx);
+    ImageStager st(ctx, bgr, n, per, mb, on_device);
+    for (int k = 0; k < st.chunks(); ++k) {
+      const int i0 = k * mb, nb = st.count(k);
+      C.arena.reset();
+      const uint8_t* d_in = st.get(k);
+      uint8_t* d_blur = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+      void* d_grad = C.arena.alloc((size_t)nb * npx * 4);
+      void* d_mag = C.arena.alloc((size_t)nb * npx * 2);
+      uint8_t* d_map = (uint8_t*)C.arena.alloc((size_t)nb * npx);
+      launch_canny_map(d_in, nb, h, w, canny_low, canny_high, d_blur, d_grad, d_mag, d_map, C.stream);
+      st.done(k);
+      uint8_t* maps = edges_out ? edges_out + (size_t)i0 * npx : scratch.data();
+      FE_HIP(hipMemcpyAsync(maps, d_map, (size_t)nb * npx, hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+      lines_host_stage(maps, nb, h, w, threshold, min_line_length, max_line_gap, max_lines, lines ? lines + (size_t)i0 * max_lines * 4 : nullptr,
+                       counts ? counts + i0 : nullptr, threads);
+    }
+  });
+}
+
+/* imagehash.phash (hash_size 8, highfreq_factor 4) of every image of an RGB / BGR batch (reference batch_processor.py:216) */
+int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, uint64_t* hashes, uint8_t* small_out, double* dct_out) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(img && hashes && n > 0 && h > 0 && w > 0, "bad arguments");
+    if (!ctx->phash_cos) {
+      double tab[8 * 32];
+      phash_cos_table(tab);
+      FE_HIP(hipMalloc((void**)&ctx->phash_cos, sizeof(tab)));
+      ctx->misc_allocs.push_back(ctx->phash_cos);
+      FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    const size_t per = (size_t)h * w * 3;
+    // chunks of up to 256 images whatever the model micro-batch (a wave per row: large chunks fill the chip, scratch is 32 B per
+    // row), but at most 1 GiB of pixels: host input is staged through two device buffers of one chunk each
+    const int mb = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1 << 30) / per));
+    ImageStager st(ctx, img, n, per, mb, on_device);
+    for (int k = 0; k < st.chunks(); ++k) {
+      const int i0 = k * mb, nb = st.count(k);
+      C.arena.reset();
+      const uint8_t* d_in = st.get(k);
+      uint8_t* d_tmp = (uint8_t*)C.arena.alloc(phash_tmp_bytes(nb, h));
+      uint64_t* d_hash = (uint64_t*)C.arena.alloc((size_t)nb * sizeof(uint64_t));
+      uint8_t* d_small = small_out ? (uint8_t*)C.arena.alloc((size_t)nb * 1024) : nullptr;
+      double* d_dct = dct_out ? (double*)C.arena.alloc((size_t)nb * 64 * sizeof(double)) : nullptr;
+      launch_phash(C, d_in, nb, h, w, bgr ? 1 : 0, d_tmp, ctx->phash_cos, d_hash, d_small, d_dct);
+      st.done(k);
+      FE_HIP(hipMemcpyAsync(hashes + i0, d_hash, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, C.stream));
+      if (small_out) FE_HIP(hipMemcpyAsync(small_out + (size_t)i0 * 1024, d_small, (size_t)nb * 1024, hipMemcpyDeviceToHost, C.stream));
+      if (dct_out) FE_HIP(hipMemcpyAsync(dct_out + (size_t)i0 * 64, d_dct, (size_t)nb * 64 * sizeof(double), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next micro-batch
+    }
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,189 @@
+// What the translation units of the C ABI (capi.hip, capi_<domain>.hip) share: the context, the entry-point guard, the staging helpers.
+#pragma once
+#include "../../include/facet_engine.h"
+#include "engine.h"
+#include "onnx_graph.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <stdexcept>
+#include <tuple>
+#include <type_traits>
+
+using namespace fe;
+
+// Below the first group, each group of fields is kept by the one file named above it; fe_destroy (capi.hip) releases them all.
+struct fe_ctx {
+  Ctx c;
+  int microbatch = 8;
+  hipEvent_t t0 = nullptr, t1 = nullptr;   // capi.hip: fe_timer_*, fe_bench_conv
+  // double-buffered H2D staging of uint8 micro-batches on a copy stream (host-buffer entry points): the copy of
+  // micro-batch k+1 is issued right after the kernels of micro-batch k were queued, so PCIe overlaps compute (ImageStager)
+  hipStream_t copy_stream = nullptr;
+  uint8_t* stage_buf[2] = {nullptr, nullptr};
+  size_t stage_cap[2] = {0, 0};
+  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
+  // capi_face.hip: device copies of OpenCV's interpolation tables (built once / per size)
+  short* warp_wtab = nullptr;
+  struct CvResizeTab { int* ofs; short* coef; };
+  std::map<std::tuple<int, int, int>, CvResizeTab> cvresize;   // (src, dst, clamp) -> tables
+  // capi_image.hip
+  int* hsv_sdiv = nullptr; int* hsv_hdiv = nullptr;   // cv2 HSV division tables
+  double* phash_cos = nullptr;                        // DCT-II cosine table of fe_phash
+  std::vector<void*> misc_allocs;                     // these tables and capi_face.hip's, for fe_destroy
+  // capi_models.hip
+  float* clip_in = nullptr;  // preprocessed CLIP crops waiting for a full tower batch (ClipBatcher)
+  size_t clip_in_cap = 0;
+  float* samp_in = nullptr;  // same for the SAMP-Net / U2-Net-P crops (SampBatcher)
+  size_t samp_in_cap = 0;
+  float* d_rec = nullptr;   // interleaved ensemble records of the host-output entry point
+  size_t d_rec_cap = 0;
+  int ensemble_mask = 7;    // models fe_ensemble_score runs when loaded: 1 topiq | 2 clip | 4 samp (fe_ensemble_select)
+  // capi_models.hip and capi_face.hip, through out_buf()
+  float* d_out = nullptr;   // persistent device staging for per-image results
+  size_t d_out_cap = 0;
+  float* out_buf(size_t floats) {
+    if (floats > d_out_cap) {
+      if (d_out) (void)hipFree(d_out);
+      d_out = nullptr; d_out_cap = 0;
+      FE_HIP(hipMalloc((void**)&d_out, floats * sizeof(float)));
+      d_out_cap = floats;
+    }
+    return d_out;
+  }
+};
+
+// Walks a uint8 image batch micro-batch by micro-batch. Device-resident input: pointer arithmetic. Host input: ping-pong
+// device buffers filled on the copy stream; get(k) makes the compute stream wait for chunk k, done(k) marks its last
+// consumer and starts the copy of chunk k+1 (which then runs under the kernels just queued for chunk k).
+class ImageStager {
+ public:
+  ImageStager(fe_ctx* ctx, const uint8_t* imgs, int n, size_t per_image, int mb, int on_device)
+      : x_(ctx), imgs_(imgs), n_(n), per_(per_image), mb_(mb), dev_(on_device) {
+    if (!dev_) {
+      if (!x_->copy_stream) {
+        FE_HIP(hipStreamCreateWithFlags(&x_->copy_stream, hipStreamNonBlocking));
+        for (int i = 0; i < 2; ++i) {
+          FE_HIP(hipEventCreateWithFlags(&x_->ev_copied[i], hipEventDisableTiming));
+          FE_HIP(hipEventCreateWithFlags(&x_->ev_consumed[i], hipEventDisableTiming));
+        }
+      }
+      const size_t need = (size_t)std::min(mb_, n_) * per_;
+      for (int i = 0; i < 2; ++i)
+        if (x_->stage_cap[i] < need) {
+          FE_HIP(hipStreamSynchronize(x_->c.stream));
+          if (x_->stage_buf[i]) FE_HIP(hipFree(x_->stage_buf[i]));
+          x_->stage_buf[i] = nullptr; x_->stage_cap[i] = 0;
+          FE_HIP(hipMalloc((void**)&x_->stage_buf[i], need));
+          x_->stage_cap[i] = need;
+        }
+      issue(0);
+    }
+  }
+  int chunks() const { return (n_ + mb_ - 1) / mb_; }
+  int count(int k) const { return std::min(mb_, n_ - k * mb_); }
+  const uint8_t* get(int k) {
+    if (dev_) return imgs_ + (size_t)k * mb_ * per_;
+    FE_HIP(hipStreamWaitEvent(x_->c.stream, x_->ev_copied[k & 1], 0));
+    return x_->stage_buf[k & 1];
+  }
+  void done(int k) {
+    if (dev_) return;
+    FE_HIP(hipEventRecord(x_->ev_consumed[k & 1], x_->c.stream));
+    consumed_[k & 1] = true;
+    if (k + 1 < chunks()) issue(k + 1);
+  }
+ private:
+  void issue(int k) {
+    const int b = k & 1;
+    if (consumed_[b]) FE_HIP(hipStreamWaitEvent(x_->copy_stream, x_->ev_consumed[b], 0));
+    FE_HIP(hipMemcpyAsync(x_->stage_buf[b], imgs_ + (size_t)k * mb_ * per_, (size_t)count(k) * per_, hipMemcpyHostToDevice,
+                          x_->copy_stream));
+    FE_HIP(hipEventRecord(x_->ev_copied[b], x_->copy_stream));
+  }
+  fe_ctx* x_; const uint8_t* imgs_; int n_; size_t per_; int mb_, dev_;
+  bool consumed_[2] = {false, false};
+};
+
+// ---- the guard of every entry point that takes a context -------------------------------------------------------------------------
+// On the error path nothing may stay in flight: queued async copies read the caller's host buffers and write into host
+// vectors local to the entry point, both of which die when it returns.
+inline void fe_drain(fe_ctx* ctx) {
+  if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+  if (ctx->c.stream) (void)hipStreamSynchronize(ctx->c.stream);
+}
+
+// thrown by the JPEG writers when an output row is too small for its image
+struct CapacityError : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// Which failures of an entry point are FE_ERR_CAPACITY; every other exception is FE_ERR_RUNTIME.
+enum class OnError {
+  Runtime,       // none
+  Capacity,      // a thrown CapacityError (the thumbnail and JPEG encode entry points)
+  VlmCapacity    // a failure to fit (arena, device memory, KV-cache capacity) by its message: the padded-batch image path of the VLM
+                 // families, so a caller can retry with fewer images
+};
+inline bool vlm_capacity_error(const char* msg) {
+  return strstr(msg, "arena exhausted") || strstr(msg, "out of memory") || strstr(msg, "do not fit") || strstr(msg, "max_seq <= 8192");
+}
+
+// Runs `body` as the entry point's work. A null context is FE_ERR_INVALID. Every entry point re-selects the context's device: the
+// calling thread may share the process with torch / RCCL. body returns nothing (FE_OK) or an fe_status (an early `return FE_OK;`, or
+// FE_ERR_NOT_LOADED / FE_ERR_INVALID after storing the message in ctx->c.err). An exception leaves what() in ctx->c.err, drains the
+// streams and returns the code `policy` gives it.
+template <class F>
+int fe_api(fe_ctx* ctx, OnError policy, F&& body) {
+  if (!ctx) return FE_ERR_INVALID;
+  try {
+    (void)hipSetDevice(ctx->c.device);
+    if constexpr (std::is_void_v<decltype(body())>) {
+      body();
+      return FE_OK;
+    } else {
+      return body();
+    }
+  } catch (const std::exception& e) {
+    ctx->c.err = e.what();
+    fe_drain(ctx);
+    const bool capacity = (policy == OnError::Capacity && dynamic_cast<const CapacityError*>(&e)) ||
+                          (policy == OnError::VlmCapacity && vlm_capacity_error(e.what()));
+    return capacity ? FE_ERR_CAPACITY : FE_ERR_RUNTIME;
+  }
+}
+template <class F>
+int fe_api(fe_ctx* ctx, F&& body) { return fe_api(ctx, OnError::Runtime, body); }
+
+// ---- host data into the arena ---------------------------------------------------------------------------------------------------
+// n elements of a host array into the arena, copied on the stream (src == nullptr: nothing, nullptr)
+template <class T>
+T* upload(Ctx& C, const T* src, size_t n) {
+  if (!src) return nullptr;
+  T* d = (T*)C.arena.alloc(n * sizeof(T));
+  FE_HIP(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, C.stream));
+  return d;
+}
+// p itself when it is device memory, its arena copy otherwise
+template <class T>
+const T* resident(Ctx& C, const T* p, size_t n, int on_device) { return on_device ? p : upload(C, p, n); }
+
+// host fp32 NCHW -> arena NHWC tensor of element type T with cpad channels, and back (synchronises)
+template <class T = float>
+TensorT<T> upload_nchw(Ctx& c, const float* x, int n, int ch, int h, int w, int cpad) {
+  const size_t elems = (size_t)n * ch * h * w;
+  float* tmp = (float*)c.arena.alloc(elems * sizeof(float));
+  FE_HIP(hipMemcpyAsync(tmp, x, elems * sizeof(float), hipMemcpyHostToDevice, c.stream));
+  TensorT<T> t = c.arena.tensor_t<T>(n, h, w, cpad);
+  launch_nchw_to_nhwc(tmp, t.p, n, ch, h, w, cpad, c.stream);
+  return t;
+}
+template <class T>
+void download_nchw(Ctx& c, const TensorT<T>& t, int ch, float* y) {
+  const size_t elems = (size_t)t.n * ch * t.h * t.w;
+  float* tmp = (float*)c.arena.alloc(elems * sizeof(float));
+  launch_nhwc_to_nchw(t.p, t.ld, tmp, t.n, ch, t.h, t.w, c.stream);
+  FE_HIP(hipMemcpyAsync(y, tmp, elems * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+  FE_HIP(hipStreamSynchronize(c.stream));
+}
+
+// capi_graph.hip: the loaded graph of a slot, or an exception that names the slot
+GraphSlot& graph_slot(fe_ctx* ctx, int slot);

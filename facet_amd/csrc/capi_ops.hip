@@ -1,0 +1,290 @@
+// C ABI: single operators and kernels launched alone, the test hooks of the suite.
+#include "capi_internal.h"
+
+extern "C" {
+
+int fe_op_conv2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const float* weight, int cout, int kh, int kw,
+                 const float* scale, const float* shift, const float* res, int res_after_act, int stride, int pad,
+                 int dil, int act, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && weight && y && n > 0 && c > 0 && h > 0 && w > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && dil > 0,
+             "bad conv arguments");
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = C.precision;      // FE_PRECISION_BF16: the same op on the bf16 kernel (inputs rounded to bf16 on upload, fp32 back)
+    WeightStore ws;
+    const int64_t wshape[4] = {cout, c, kh, kw};
+    ws.set("w.weight", weight, wshape, 4);
+    ConvW cw = build_conv(dw, ws, "w", "", false);
+    std::vector<float> v;
+    if (scale) { v.assign(scale, scale + cout); cw.scale = dw.upload(v); }
+    if (shift) { v.assign(shift, shift + cout); cw.shift = dw.upload(v); }
+    const int ho = conv_out_dim(h, kh, stride, pad, dil), wo = conv_out_dim(w, kw, stride, pad, dil);
+    FE_CHECK(ho > 0 && wo > 0, "conv output is empty");
+    auto half_op = [&](auto* tag) {      // the same op on the 2-byte kernel (inputs rounded on upload, fp32 back)
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      FE_CHECK(cw.wh, "fe_op_conv2d(2-byte): Cin must be a multiple of 8 (16 for spatial kernels)");
+      TensorT<E> xt = upload_nchw<E>(C, x, n, c, h, w, cw.CinPadH);
+      ConvOptsT<E> o;
+      o.sh = o.sw = stride; o.ph = o.pw = pad; o.dh = o.dw = dil; o.act = act; o.res_after_act = res_after_act;
+      TensorT<E> rt;
+      if (C.res32) {
+        // FE_PRECISION_RES32: the fp32-stream form of the layer - residual read as fp32, result written both as fp32 rows (returned)
+        // and as 2-byte rows, which must be the rounding of the fp32 ones (checked here: this entry point is the kernels' test hook)
+        Tensor r32, y32 = C.arena.tensor(n, ho, wo, cout);
+        if (res) { r32 = upload_nchw(C, res, n, cout, ho, wo, cout); o.res32 = &r32; }
+        o.y32 = &y32;
+        TensorT<E> yt = C.arena.tensor_t<E>(n, ho, wo, cout);
+        conv_forward(C, cw, xt, yt, o);
+        download_nchw(C, y32, cout, y);
+        std::vector<float> y16((size_t)n * cout * ho * wo);
+        download_nchw(C, yt, cout, y16.data());
+        for (size_t i = 0; i < y16.size(); ++i) {
+          const float a = std::fmin(std::fmax(y[i], -65504.f), 65504.f);
+          FE_CHECK(std::fabs(y16[i] - a) <= std::fabs(a) * (PrecOf<E>::value == PREC_F16 ? 4.9e-4f : 3.95e-3f) + 6.2e-5f,
+                   "fe_op_conv2d(res32): 2-byte output %g is not the rounding of the fp32 output %g at %zu", y16[i], y[i], i);
+        }
+        return;
+      }
+      if (res) { rt = upload_nchw<E>(C, res, n, cout, ho, wo, cout); o.res = &rt; }
+      TensorT<E> yt = conv_new(C, cw, xt, o);
+      download_nchw(C, yt, cout, y);
+    };
+    if (C.precision == PREC_BF16) {
+      half_op((bf16*)nullptr);
+    } else if (C.precision == PREC_F16) {
+      half_op((f16*)nullptr);
+    } else {
+      Tensor xt = upload_nchw(C, x, n, c, h, w, cw.CinPad);
+      ConvOpts o;
+      o.sh = o.sw = stride; o.ph = o.pw = pad; o.dh = o.dw = dil; o.act = act; o.res_after_act = res_after_act;
+      Tensor rt;
+      if (res) { rt = upload_nchw(C, res, n, cout, ho, wo, cout); o.res = &rt; }
+      Tensor yt = conv_new(C, cw, xt, o);
+      download_nchw(C, yt, cout, y);
+    }
+  });
+}
+
+int fe_op_topiq_gate64(fe_ctx* ctx, const float* x, int n, int h, int w, const float* w0, const float* b0, const float* w2, const float* b2,
+                       const float* w4, float b4, const float* wx, const float* bx, int wblk_act, int gate_act, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && w0 && b0 && w2 && b2 && w4 && wx && bx && y && n > 0 && h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0, "bad gate64 arguments");
+    FE_CHECK(C.precision == PREC_BF16 || C.precision == PREC_F16, "fe_op_topiq_gate64: the fused gate exists for the 2-byte element types only");
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = C.precision;
+    GatedConvW g;
+    build_gate64_fragments(dw, g, w0, b0, w2, b2, w4, b4, wx, bx);
+    auto run = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      TensorT<E> xt = upload_nchw<E>(C, x, n, 64, h, w, 64);
+      TensorT<E> yt = C.arena.tensor_t<E>(n, h / 16, w / 16, 64);
+      launch_topiq_gate64(xt, yt, g.fused, g.fused_bias, wblk_act, gate_act, C.stream);
+      download_nchw(C, yt, 64, y);
+    };
+    if (C.precision == PREC_BF16) run((bf16*)nullptr); else run((f16*)nullptr);
+  });
+}
+
+int fe_op_conv3x3_c64(fe_ctx* ctx, const float* x, int n, int h, int w, const float* w2, const float* scale2, const float* shift2, int act2,
+                      const float* w3, const float* scale3, const float* shift3, const float* res, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && w2 && y && n > 0 && h > 0 && w > 0 && (!w3 || res), "bad conv3x3_c64 arguments");
+    FE_CHECK(C.precision == PREC_BF16 || C.precision == PREC_F16, "fe_op_conv3x3_c64: the halo-tiled kernel exists for the 2-byte element types only");
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = C.precision;
+    void *f2 = nullptr, *f3 = nullptr;
+    build_c64_fragments(dw, w2, w3, &f2, &f3);
+    std::vector<float> v;
+    auto up = [&](const float* a, int cnt) -> float* { if (!a) return nullptr; v.assign(a, a + cnt); return dw.upload(v); };
+    float *s2 = up(scale2, 64), *h2 = up(shift2, 64), *s3 = up(scale3, 256), *h3 = up(shift3, 256);
+    const int cout = w3 ? 256 : 64;
+    auto run = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      TensorT<E> xt = upload_nchw<E>(C, x, n, 64, h, w, 64);
+      TensorT<E> yt = C.arena.tensor_t<E>(n, h, w, cout);
+      TensorT<E> rt;
+      if (w3) rt = upload_nchw<E>(C, res, n, 256, h, w, 256);
+      launch_conv3x3_c64(xt, yt, w3 ? &rt : nullptr, f2, f3, s2, h2, s3, h3, act2, C.stream);
+      download_nchw(C, yt, cout, y);
+    };
+    if (C.precision == PREC_BF16) run((bf16*)nullptr); else run((f16*)nullptr);
+  });
+}
+
+int fe_op_maxpool2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int k, int stride, int pad, int ceil_mode,
+                    float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    C.arena.reset();
+    Tensor xt = upload_nchw(C, x, n, c, h, w, c);
+    auto od = [&](int in) {
+      int o = ceil_mode ? (in + 2 * pad - k + stride - 1) / stride + 1 : (in + 2 * pad - k) / stride + 1;
+      if (ceil_mode && (o - 1) * stride >= in + pad) --o;
+      return o;
+    };
+    Tensor yt = C.arena.tensor(n, od(h), od(w), c);
+    launch_maxpool(xt, yt, k, stride, pad, C.stream);
+    download_nchw(C, yt, c, y);
+  });
+}
+
+int fe_op_bilinear(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    C.arena.reset();
+    Tensor xt = upload_nchw(C, x, n, c, h, w, c);
+    Tensor yt = C.arena.tensor(n, ho, wo, c);
+    launch_bilinear(xt, yt, C.stream);
+    download_nchw(C, yt, c, y);
+  });
+}
+
+int fe_op_adaptive_avgpool(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    C.arena.reset();
+    Tensor xt = upload_nchw(C, x, n, c, h, w, c);
+    Tensor yt = C.arena.tensor(n, ho, wo, c);
+    launch_adaptive_avgpool(xt, yt, C.stream);
+    download_nchw(C, yt, c, y);
+  });
+}
+
+int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g, const float* b, float eps, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    C.arena.reset();
+    const size_t n = (size_t)rows * d;
+    float* dx = upload(C, x, n);
+    float* dy = C.arena.array<float>(n);
+    float* dg = upload(C, g, (size_t)d);
+    float* db = upload(C, b, (size_t)d);
+    launch_layernorm(dx, d, dy, d, dg, db, rows, d, eps, C.stream);
+    FE_HIP(hipMemcpyAsync(y, dy, n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+// Test hook of the fused head_dim-64 attention kernels, launched alone: o = softmax(q k^T) v + bv per (batch, head), q taken as the
+// kernel receives it (already scaled). v is transposed on the host into the kernel's V^T layout [B][d][roundup32(Lk)], zero padded.
+// form 0: the kernel of the context's precision (operands rounded on upload); form 1: the split-f16 kernel on hi | lo pairs.
+int fe_op_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, const float* bv, int B, int H, int Lq, int Lk, int causal,
+                    int form, float* o) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(q && k && v && bv && o && B > 0 && H > 0 && Lq > 0 && Lk > 0 && (form == 0 || form == 1), "bad attention arguments");
+    FE_CHECK(form == 0 || C.precision == PREC_F16, "fe_op_attention: the split form (form 1) runs on f16 pairs - set f16 precision");
+    FE_CHECK(form == 0 || !causal, "fe_op_attention: the split form (form 1) has no causal mask");
+    C.arena.reset();
+    const int d = H * 64, Lp = (Lk + 31) / 32 * 32;
+    const size_t nq = (size_t)B * Lq * d, nk = (size_t)B * Lk * d, nv = (size_t)B * d * Lp;
+    std::vector<float> vt(nv, 0.f);
+    for (int b = 0; b < B; ++b)
+      for (int j = 0; j < Lk; ++j)
+        for (int c = 0; c < d; ++c) vt[((size_t)b * d + c) * Lp + j] = v[((size_t)b * Lk + j) * d + c];
+    float *dq = upload(C, q, nq), *dk = upload(C, k, nk), *dvt = upload(C, vt.data(), nv), *dbv = upload(C, bv, (size_t)d);
+    if (form == 1) {
+      f16* q2 = C.arena.array<f16>(2 * nq);      // rows [hi d | lo d]
+      f16* k2 = C.arena.array<f16>(2 * nk);
+      f16* v2 = C.arena.array<f16>(2 * nv);      // rows [hi Lp | lo Lp]: V^T hi and lo interleaved by row, row stride 2 Lp
+      f16* o2 = C.arena.array<f16>(2 * nq);
+      float* o32 = C.arena.array<float>(2 * nq);
+      launch_split_hi_lo(dq, q2, (size_t)B * Lq, d, C.stream);
+      launch_split_hi_lo(dk, k2, (size_t)B * Lk, d, C.stream);
+      launch_split_hi_lo(dvt, v2, (size_t)B * d, Lp, C.stream);
+      launch_attention_split(q2, k2, 2 * d, d, v2, v2 + Lp, 2 * Lp, o2, 2 * d, d, B, H, Lq, Lk, d, C.stream);
+      launch_convert(o2, o32, 2 * nq, C.stream);
+      std::vector<float> pair(2 * nq);
+      FE_HIP(hipMemcpyAsync(pair.data(), o32, 2 * nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+      for (size_t row = 0; row < (size_t)B * Lq; ++row)
+        for (int c = 0; c < d; ++c) o[row * d + c] = (pair[row * 2 * d + c] + pair[row * 2 * d + d + c]) + bv[c];
+      return FE_OK;
+    }
+    auto half_op = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      E *hq = C.arena.array<E>(nq), *hk = C.arena.array<E>(nk), *hv = C.arena.array<E>(nv), *ho = C.arena.array<E>(nq);
+      launch_convert(dq, hq, nq, C.stream);
+      launch_convert(dk, hk, nk, C.stream);
+      launch_convert(dvt, hv, nv, C.stream);
+      launch_attention(hq, d, hk, d, hv, Lp, dbv, ho, d, B, H, Lq, Lk, d, causal ? 1 : 0, C.stream);
+      launch_convert(ho, dq, nq, C.stream);      // dq is free again: the fp32 copy of the output
+      return dq;
+    };
+    float* dout;
+    if (C.precision == PREC_BF16) {
+      dout = half_op((bf16*)nullptr);
+    } else if (C.precision == PREC_F16) {
+      dout = half_op((f16*)nullptr);
+    } else {
+      dout = C.arena.array<float>(nq);
+      launch_attention(dq, d, dk, d, dvt, Lp, dbv, dout, d, B, H, Lq, Lk, d, causal ? 1 : 0, C.stream);
+    }
+    FE_HIP(hipMemcpyAsync(o, dout, nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    return FE_OK;
+  });
+}
+
+// Test hook of the attention wiring (build_mha + mha_forward in engine.hip) with nn.MultiheadAttention's parameters: the q / k
+// projections with the folded 1/sqrt(head_dim), the role-swapped V^T GEMM, the kernel (or the unfused route for head_dim != 64), the
+// out-projection and the residual, in the context's precision.
+int fe_op_mha(fe_ctx* ctx, const float* x_q, const float* x_kv, int B, int Lq, int Lk, int d, int heads, const float* in_proj_weight,
+              const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* res, int causal, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x_q && x_kv && in_proj_weight && in_proj_bias && out_proj_weight && out_proj_bias && y && B > 0 && Lq > 0 && Lk > 0 && d > 0 && heads > 0,
+             "bad mha arguments");
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = C.precision;
+    WeightStore ws;
+    const int64_t s_in[2] = {3 * d, d}, s_out[2] = {d, d}, s_inb[1] = {3 * d}, s_outb[1] = {d};
+    ws.set("a.in_proj_weight", in_proj_weight, s_in, 2);
+    ws.set("a.in_proj_bias", in_proj_bias, s_inb, 1);
+    ws.set("a.out_proj.weight", out_proj_weight, s_out, 2);
+    ws.set("a.out_proj.bias", out_proj_bias, s_outb, 1);
+    const MHAW m = build_mha(dw, ws, "a", heads);
+    const size_t nq = (size_t)B * Lq * d, nk = (size_t)B * Lk * d;
+    float *dq = upload(C, x_q, nq), *dkv = upload(C, x_kv, nk), *dres = upload(C, res, nq), *dy = C.arena.array<float>(nq);
+    auto half_op = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      E *hq = C.arena.array<E>(nq), *hkv = C.arena.array<E>(nk), *hres = res ? C.arena.array<E>(nq) : nullptr, *hy = C.arena.array<E>(nq);
+      launch_convert(dq, hq, nq, C.stream);
+      launch_convert(dkv, hkv, nk, C.stream);
+      if (res) launch_convert(dres, hres, nq, C.stream);
+      mha_forward<E, E>(C, m, hq, d, hkv, d, B, Lq, Lk, hres, d, hy, d, causal != 0);
+      launch_convert(hy, dy, nq, C.stream);
+    };
+    if (C.precision == PREC_BF16) half_op((bf16*)nullptr);
+    else if (C.precision == PREC_F16) half_op((f16*)nullptr);
+    else mha_forward<float, float>(C, m, dq, d, dkv, d, B, Lq, Lk, dres, d, dy, d, causal != 0);
+    FE_HIP(hipMemcpyAsync(y, dy, nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+// Bring-up hook: the VLM decoder's greedy selection (vlm_select) on caller logits [rows][vocab], rounded to bf16 first as in the decoder.
+// ids [rows]; logprobs [rows] (nullable: the plain kernels) the log-probability of each chosen id.
+int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(logits && ids && rows > 0 && rows <= 65535 && vocab > 0, "bad arguments (1 <= rows <= 65535, vocab > 0)");
+    C.arena.reset();
+    float* d_lg = upload(C, logits, (size_t)rows * vocab);
+    int* d_ids = (int*)C.arena.alloc((size_t)rows * sizeof(int));
+    float* d_lp = logprobs ? (float*)C.arena.alloc((size_t)rows * sizeof(float)) : nullptr;
+    vlm_select(C, d_lg, rows, vocab, d_ids, d_lp);
+    FE_HIP(hipMemcpyAsync(ids, d_ids, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+    if (d_lp) FE_HIP(hipMemcpyAsync(logprobs, d_lp, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+}  // extern "C"

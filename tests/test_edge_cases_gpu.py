@@ -29,6 +29,16 @@ def test_not_loaded_and_bad_arguments_return_errors_not_crashes(engine):
         engine.conv2d(np.zeros((1, 8, 4, 4), np.float32), np.zeros((8, 8, 7, 7), np.float32))  # empty output
 
 
+def test_a_failed_check_outside_the_vlm_path_is_a_runtime_error_by_number(engine):
+    """An FE_CHECK that fails in an entry point without a capacity rule returns FE_ERR_RUNTIME (-2) with its text and launches nothing."""
+    src, dst = np.zeros((1, 4, 4, 3), np.uint8), np.full((1, 2, 2, 3), 0xA5, np.uint8)
+    box = np.array([0, 0, 5, 4], np.int32)                                              # one column past the image
+    rc = engine.lib.fe_reduce_u8(engine.h, src.ctypes.data_as(C.c_void_p), 1, 4, 4, 2, 2, box.ctypes.data_as(C.c_void_p), 0,
+                                 dst.ctypes.data_as(C.c_void_p))
+    assert rc == -2 and b"reduce: box outside the image or empty" in engine.lib.fe_last_error(engine.h)
+    assert (dst == 0xA5).all()
+
+
 def test_arena_exhaustion_is_a_clean_error_and_recoverable():
     small = Engine(0, arena_bytes=64 << 20)
     small.load_weights(FE_MODEL_TOPIQ, synthetic_state_dict("topiq", 3))

@@ -79,7 +79,7 @@ def test_samp_images_bgr_flag_and_clip_images(engine, all_loaded):
 
 
 def test_crop_gathering_across_microbatches_is_order_preserving():
-    """CLIP and SAMP crops are gathered across micro-batches and run in larger chunks (ClipBatcher / SampBatcher in capi.hip): with
+    """CLIP and SAMP crops are gathered across micro-batches and run in larger chunks (ClipBatcher / SampBatcher in capi_models.hip): with
     70 images, 16 per micro-batch, the towers run on a full chunk plus a remainder that was shifted inside the gather buffer.
     Every image must get its own result: compare with one-image calls."""
     from facet_amd import Engine

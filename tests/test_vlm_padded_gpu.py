@@ -9,6 +9,7 @@ left-padded batch with its attention mask, the call models/vlm_tagger.py:327-368
     the pad token id changes nothing; no NaN anywhere;
   * VLMTagger.tag_batch on three PIL photos of different sizes returns the tags the reference's ids decode to.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -128,6 +129,20 @@ def test_right_padding_is_rejected(eng):
     am = np.array([[1, 1, 1, 0], [1, 1, 1, 1]], np.int32)
     with pytest.raises(ValueError):
         eng.vlm_generate(np.ones((2, 4), np.int32), 2, position_ids=np.zeros((3, 2, 4), np.int32), attention_mask=am)
+
+
+def test_a_prompt_longer_than_the_cache_is_a_capacity_error_by_number(eng):
+    """fe_vlm_prefill_images_padded with one position more than max_seq: refused by the entry point's own check, whose text carries one
+    of the strings the padded path reports as FE_ERR_CAPACITY (-4) and not as FE_ERR_RUNTIME; nothing is launched or written."""
+    eng.load_weights(FE_MODEL_VLM, synthetic_state_dict("qwen2_5_vl_text_tiny", 12))
+    n_seq, L = 2, 5
+    i32p = C.POINTER(C.c_int32)
+    ids, pos, pad = np.ones((n_seq, L), np.int32), np.zeros((3, n_seq, L), np.int32), np.zeros(n_seq, np.int32)
+    nxt = np.full(n_seq, -7, np.int32)
+    rc = eng.lib.fe_vlm_prefill_images_padded(eng.h, ids.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), n_seq, L, L - 1, pad.ctypes.data_as(i32p),
+                                              None, 0, nxt.ctypes.data_as(i32p), None)
+    assert rc == -4 and b"max_seq <= 8192" in eng.lib.fe_last_error(eng.h)
+    assert (nxt == -7).all()
 
 
 def test_tag_batch_on_photos_of_different_sizes(eng):
