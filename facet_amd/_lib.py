@@ -30,6 +30,9 @@ PRECISION_NAME = {0: "f32", 1: "bf16", 2: "f16", 1 | FE_PRECISION_RES32: "bf16+r
 ACT = {"none": 0, None: 0, "relu": 1, "gelu": 2, "sigmoid": 3, "softplus": 5}
 
 
+VLM_WEIGHT_FORMATS = {"bf16": 0, "fp8": 1}      # FE_VLM_WEIGHTS_BF16 / FE_VLM_WEIGHTS_E4M3
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -116,6 +119,8 @@ SIGNATURES = {
     "fe_tag_similarities": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.c_int, _f32p]),
     "fe_vlm_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int)]),
     "fe_vlm_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "fe_vlm_set_weight_format": (C.c_int, [C.c_void_p, C.c_int]),
+    "fe_vlm_weight_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "fe_vlm_prefill": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_decode_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_vision_configure": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -736,6 +741,22 @@ class Engine:
         """Geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (transformers Qwen2_5_VLTextConfig; defaults = Qwen2.5-VL-7B)."""
         ms = (C.c_int * 3)(*[int(v) for v in mrope_section])
         self._ck(self.lib.fe_vlm_configure(self.h, int(n_heads), int(n_kv_heads), int(head_dim), float(rope_theta), float(rms_eps), ms))
+
+    def vlm_weight_format(self, fmt="bf16"):
+        """Storage of the decoder's Linear weights (q|k|v, o, gate, up, down of every layer, lm_head) built by the NEXT
+        load_weights(FE_MODEL_VLM, ...): "bf16" (default, the reference's dtype) or "fp8" - OCP e4m3 codes with one power-of-two scale
+        per output row (facet_amd.weights.quantize_e4m3_rows), half the bytes a decode step streams. Activations, attention, the KV
+        cache, the embedding table and the vision tower stay bf16."""
+        if fmt not in VLM_WEIGHT_FORMATS:
+            raise ValueError(f"vlm_weight_format {fmt!r}: one of {sorted(VLM_WEIGHT_FORMATS)}")
+        self._ck(self.lib.fe_vlm_set_weight_format(self.h, VLM_WEIGHT_FORMATS[fmt]))
+
+    def vlm_weight_info(self):
+        """The loaded decoder's weight storage (fe_vlm_weight_info): format "bf16" / "fp8", the stored bytes of the matrices a decode step
+        streams (layer projections + lm_head), the bytes of their row scales, the number of quantised rows."""
+        d = (C.c_int64 * 4)()
+        self._ck(self.lib.fe_vlm_weight_info(self.h, d))
+        return dict(format={v: k for k, v in VLM_WEIGHT_FORMATS.items()}[int(d[0])], weight_bytes=int(d[1]), scale_bytes=int(d[2]), quantized_rows=int(d[3]))
 
     def vlm_vision_configure(self, n_heads=16, fullatt_block_indexes=(7, 15, 23, 31)):
         """Vision-tower geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (Qwen2_5_VLVisionConfig; defaults = Qwen2.5-VL-7B)."""

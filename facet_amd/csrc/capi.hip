@@ -261,7 +261,8 @@ int fe_weights_commit(fe_ctx* ctx, int model) {
       ctx->c.samp = std::move(m);
     } else if (model == FE_MODEL_VLM) {
       auto m = std::make_unique<VlmModel>();
-      build_vlm(*m, ws, ctx->c.vlm_cfg);      // always bf16: the precision the reference loads it in (models/vlm_tagger.py:155-156)
+      // bf16 arithmetic always: the precision the reference loads it in (models/vlm_tagger.py:155-156); the weights' storage is the caller's choice
+      build_vlm(*m, ws, ctx->c.vlm_cfg, ctx->c.vlm_weight_format);
       ctx->c.vlm = std::move(m);
     } else {
       throw Error("fe_weights_commit: model " + std::to_string(model) + " not implemented");

@@ -263,6 +263,22 @@ int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, flo
     g.qwen3 = false; g.qwen2 = false; g.n_deepstack = 0;      // (the Qwen2.5-VL family: what a context builds unless fe_vlm2_ / fe_vlm3_configure said otherwise)
   });
 }
+int fe_vlm_set_weight_format(fe_ctx* ctx, int format) {
+  return fe_api(ctx, [&] {
+    FE_CHECK(format == FE_VLM_WEIGHTS_BF16 || format == FE_VLM_WEIGHTS_E4M3, "vlm_set_weight_format: %d (FE_VLM_WEIGHTS_BF16 or FE_VLM_WEIGHTS_E4M3)", format);
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    ctx->c.vlm_weight_format = format;
+  });
+}
+int fe_vlm_weight_info(fe_ctx* ctx, int64_t* info4) {
+  return fe_api(ctx, [&] {
+    if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+    FE_CHECK(info4, "bad arguments");
+    const VlmModel& m = *ctx->c.vlm;
+    info4[0] = m.weight_format; info4[1] = m.weight_bytes; info4[2] = m.scale_bytes; info4[3] = m.quant_rows;
+    return FE_OK;
+  });
+}
 // ---- Qwen3-VL: the same decoder entry points serve the family the next commit builds --------------------------------------------------------
 int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads,
                       const int* deepstack_indexes, int n_deepstack) {

@@ -298,6 +298,7 @@ struct Ctx {
   std::unique_ptr<struct ClipTextModel> clip_text;
   std::unique_ptr<struct VlmModel> vlm;
   VlmConfig vlm_cfg;          // read by the next fe_weights_commit(FE_MODEL_VLM) (fe_vlm_configure)
+  int vlm_weight_format = 0;  // FE_VLM_WEIGHTS_* of the next fe_weights_commit(FE_MODEL_VLM) (fe_vlm_set_weight_format)
   std::unique_ptr<GraphSlot> graphs[8];   // ONNX graphs (face detector / landmarks / recognition, ...)
   ~Ctx();
 };
@@ -439,6 +440,10 @@ struct VlmModel {
   ConvW lm_head;
   std::vector<VlmLayerW> layers;
   int vocab = 0, hidden = 0, inter = 0;
+  // storage of the decoder's Linear weights (FE_VLM_WEIGHTS_*), and of the matrices a decode step streams (layer projections + lm_head):
+  // their stored bytes, the bytes of their row scales, the quantised rows (fe_vlm_weight_info)
+  int weight_format = 0;
+  int64_t weight_bytes = 0, scale_bytes = 0, quant_rows = 0;
   VlmVisionW vis;
   bf16* img_embeds = nullptr; int img_rows = 0, img_cap = 0;      // merged image embeddings of the last fe_vlm_encode_images (device)
   // contiguous KV cache: per layer [n_seq][n_kv_heads][max_seq][128] keys (rotated) and values
@@ -462,7 +467,7 @@ struct VlmModel {
   void release_cache();
   ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); if (ds_feats) (void)hipFree(ds_feats); }
 };
-void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg);
+void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int weight_format = 0);
 void build_vlm_vision(VlmModel& m, const WeightStore& ws);
 void build_vlm_ln_vision(VlmModel& m, const WeightStore& ws);      // the family: m.cfg.qwen3, else Qwen2-VL
 // pieces shared by the three towers (model_vlm_vision.hip), hd = head_dim 64 or 80

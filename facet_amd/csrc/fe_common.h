@@ -294,6 +294,10 @@ struct ConvW {
   int KpH = 0, cb = 0, CinPadH = 0;   // CinPadH: input channels the bf16 kernel reads per pixel (Cin rounded up to 8)
   void* wtap_h = nullptr;  // tap-decomposed form for Cout <= 2 spatial kernels, [KH*KW*Cout rounded to 8][KpTH]
   int KpTH = 0;
+  // e4m3 form (VLM decoder Linears committed under FE_VLM_WEIGHTS_E4M3, model_vlm.hip): [Cout][KpH] codes in plain K order, zero codes
+  // past Cin, and one power-of-two scale per row; such a layer has no wh. (Not `scale`: that is an epilogue vector of the conv kernels.)
+  uint8_t* w8 = nullptr;
+  float* w8_scale = nullptr;  // [Cout]
 };
 
 template <class T>

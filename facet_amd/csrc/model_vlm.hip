@@ -11,7 +11,10 @@
 // accumulation inside every contraction. Parity: tests/test_vlm_gpu.py against vectors of the reference's own model class
 // (tests/golden/make_vlm_golden.py) - pinned.
 // Not in this slice: the vision tower (window attention, patch merger) and fp8 attention; image tokens enter as rows of `embeds`.
+// Weight storage: bf16, or (FE_VLM_WEIGHTS_E4M3) e4m3 rows with one power-of-two scale each (fp8_core.h) for the Linear layers - the
+// same arithmetic on other weight values, see "e4m3 weights" below.
 #include "engine.h"
+#include "fp8_core.h"
 #include "vlm_attn_tile.h"
 #include <type_traits>
 #include <cmath>
@@ -294,8 +297,107 @@ __global__ __launch_bounds__(256) void vlm_gemv_kernel(const bf16* __restrict__ 
     }
   }
 }
+// ---- e4m3 weights (FE_VLM_WEIGHTS_E4M3): a Linear layer is [Cout][KpH] codes (ConvW.w8) and [Cout] scales 2^e (ConvW.w8_scale), the format
+// of fp8_core.h. Layout along K: PLAIN order, one byte per element, rows padded with zero codes to KpH (a multiple of 64) - code k of a
+// row multiplies activation k. v_cvt_scalef32_pk_bf16_fp8 (scale 1) widens two neighbouring codes of a 32-bit word to a packed bf16 pair
+// exactly (4 significant bits into 8), element 0 from the lower byte: 16 codes of a 16-byte load become the 8 pairs that face the 8
+// dwords of 16 activations, with no permutation. The products and the fp32 sums are then those of the bf16 kernels; the row scale
+// multiplies the fp32 sum (exact: a power of two) before the bias.
+typedef __bf16 vlm_bf2 __attribute__((ext_vector_type(2)));
+template <bool HI>
+__device__ __forceinline__ unsigned vlm_e4m3_pair(const unsigned word) {
+  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(word, 1.0f, HI));
+}
+// 16 codes (K order) -> 16 bf16 (K order): lo = elements 0 .. 7, hi = 8 .. 15
+__device__ __forceinline__ void vlm_e4m3_widen16(const uint4 c, uint4& lo, uint4& hi) {
+  lo.x = vlm_e4m3_pair<false>(c.x); lo.y = vlm_e4m3_pair<true>(c.x); lo.z = vlm_e4m3_pair<false>(c.y); lo.w = vlm_e4m3_pair<true>(c.y);
+  hi.x = vlm_e4m3_pair<false>(c.z); hi.y = vlm_e4m3_pair<true>(c.z); hi.z = vlm_e4m3_pair<false>(c.w); hi.w = vlm_e4m3_pair<true>(c.w);
+}
+// vlm_gemv_kernel on e4m3 rows: N * K bytes per launch. A lane takes 16 codes per 16-byte load, so a wave covers 1024 columns of K and the
+// four waves 4096 per step; K % 16 == 0. The conversion is 8 instructions per 16 weights of a column, shared by the M rows: against the
+// 16 M dot instructions of those weights it leaves the 2- and 4-row steps where the bf16 kernel has them.
+template <int MR, class TO>
+__global__ __launch_bounds__(256) void vlm_gemv_e4m3_kernel(const bf16* __restrict__ x, int ldx, const uint8_t* __restrict__ w, int ldw, const float* __restrict__ wscale,
+                                                            const float* __restrict__ bias, TO* __restrict__ y, int ldy, int M, int N, int K) {
+  __shared__ float red[4][MR][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * 2;
+  const bool two = n0 + 1 < N;
+  const uint8_t* w0 = w + (size_t)n0 * ldw;
+  const uint8_t* w1 = w + (size_t)(two ? n0 + 1 : n0) * ldw;
+  float a0[MR], a1[MR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) { a0[m] = 0.f; a1[m] = 0.f; }
+  auto dot8 = [](const uint4 p, const uint4 q, float acc) __attribute__((always_inline)) {
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.x), __builtin_bit_cast(vlm_bf2, q.x), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.y), __builtin_bit_cast(vlm_bf2, q.y), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.z), __builtin_bit_cast(vlm_bf2, q.z), acc, false);
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.w), __builtin_bit_cast(vlm_bf2, q.w), acc, false);
+  };
+  auto fma16 = [&](const uint4 ca, const uint4 cb, const int k) __attribute__((always_inline)) {
+    uint4 al, ah, bl, bh;
+    vlm_e4m3_widen16(ca, al, ah);
+    vlm_e4m3_widen16(cb, bl, bh);
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      if (m < M) {
+        const uint4 xl = *reinterpret_cast<const uint4*>(x + (size_t)m * ldx + k), xh = *reinterpret_cast<const uint4*>(x + (size_t)m * ldx + k + 8);
+        a0[m] = dot8(xh, ah, dot8(xl, al, a0[m]));
+        a1[m] = dot8(xh, bh, dot8(xl, bl, a1[m]));
+      }
+    }
+  };
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));      // weights are read once per step: streamed past the caches
+  auto ldw16 = [](const uint8_t* ptr) __attribute__((always_inline)) {
+    const v4u a = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(ptr));
+    return make_uint4(a[0], a[1], a[2], a[3]);
+  };
+  int k = wave * 1024 + lane * 16;
+  for (; k + 3 * 4096 < K; k += 4 * 4096) {      // four steps per trip, their eight weight loads issued before the first is used
+    uint4 wa[4], wb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { wa[j] = ldw16(w0 + k + 4096 * j); wb[j] = ldw16(w1 + k + 4096 * j); }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) fma16(wa[j], wb[j], k + 4096 * j);
+  }
+  for (; k + 4096 < K; k += 2 * 4096) {
+    const uint4 p0 = ldw16(w0 + k), q0 = ldw16(w1 + k), p1 = ldw16(w0 + k + 4096), q1 = ldw16(w1 + k + 4096);
+    fma16(p0, q0, k); fma16(p1, q1, k + 4096);
+  }
+  for (; k < K; k += 4096) fma16(ldw16(w0 + k), ldw16(w1 + k), k);
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a0[m] += __shfl_xor(a0[m], o); a1[m] += __shfl_xor(a1[m], o); }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int m = 0; m < MR; ++m) { red[wave][m][0] = a0[m]; red[wave][m][1] = a1[m]; }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 2 * MR) {
+    const int m = t >> 1, c = t & 1;
+    if (m < M && (c == 0 || two)) {
+      const float v = ((red[0][m][c] + red[1][m][c]) + (red[2][m][c] + red[3][m][c])) * wscale[n0 + c] + (bias ? bias[n0 + c] : 0.f);
+      stf(y + (size_t)m * ldy + n0 + c, v);
+    }
+  }
+}
+// the e4m3 GEMV takes a layer whose K is a multiple of 16 (a lane's 16-byte load); vlm_linear sends other shapes through the bf16 scratch
+static bool vlm_e4m3_gemv_ok(const ConvW& w) { return w.CinPadH % 16 == 0; }
 template <class TO>
 static void vlm_gemv(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy) {
+  if (w.w8) {
+    FE_CHECK(w.w8_scale && vlm_e4m3_gemv_ok(w) && w.KpH % 16 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv(e4m3): unsupported layer");
+    const int K = w.CinPadH, blocks = (w.Cout + 1) / 2;
+#define VLM_GEMV8(MR) hipLaunchKernelGGL((vlm_gemv_e4m3_kernel<MR, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const uint8_t*)w.w8, w.KpH, (const float*)w.w8_scale, (const float*)w.shift, y, ldy, M, w.Cout, K)
+    if (M == 1) VLM_GEMV8(1); else if (M == 2) VLM_GEMV8(2); else VLM_GEMV8(4);
+#undef VLM_GEMV8
+    FE_HIP(hipGetLastError());
+    c.flops_accum += 2.0 * M * (double)w.Cin * w.Cout;
+    return;
+  }
   FE_CHECK(w.wh && w.hprec == PREC_BF16 && w.KpH % 8 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv: unsupported layer");
   const int K = w.CinPadH, blocks = (w.Cout + 1) / 2;
   if (M == 1) hipLaunchKernelGGL((vlm_gemv_kernel<1, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, (const float*)w.shift, y, ldy, M, w.Cout, K);
@@ -320,33 +422,45 @@ static void vlm_gemv(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* 
 constexpr int VLM_G32_XP = 272;      // bytes per staged activation row: 128 elements + 16 (conflict-free 16-byte reads at stride 1 row)
 // (w2 / part2: a second weight matrix of the same shape on the same activations - the gate and up projections of the MLP as ONE launch:
 // workgroup columns [cols1, 2 cols1) take it)
-__global__ __launch_bounds__(256) void vlm_gemm32_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ w, int ldw, float* __restrict__ part, int M, int N,
-                                                         int K, int stages_per_wg, const bf16* __restrict__ w2, float* __restrict__ part2, int cols1) {
+// WT = uint8_t: e4m3 rows (see "e4m3 weights" above; wscale / wscale2 their row scales). A stage of a tile is then 32 rows x 128 bytes:
+// FOUR loads per lane, each 8 rows x 128 contiguous bytes per instruction (whole sectors, once), half the bytes of the bf16 stage. The
+// codes are widened on the way into the SAME wave-private LDS image (16 codes = the two neighbouring 16-byte slots 2 p and 2 p + 1 of
+// the row; under the XOR the second is the first's address ^ 16, and the 8-lane groups of two neighbouring rows cover the 16 slots of a
+// 256-byte bank line between them), so the fragment reads and the bf16 MFMA below do not know the difference. Each accumulator row is
+// multiplied by its scale before the partial sums are stored (exact, a power of two: the sum over the splits is the scaled sum), which
+// leaves the finishing passes as they are. K % 128 == 0 as for bf16.
+template <class WT>
+__global__ __launch_bounds__(256) void vlm_gemm32_kernel(const bf16* __restrict__ x, int ldx, const WT* __restrict__ w, int ldw, float* __restrict__ part, int M, int N,
+                                                         int K, int stages_per_wg, const WT* __restrict__ w2, float* __restrict__ part2, int cols1,
+                                                         const float* __restrict__ wscale, const float* __restrict__ wscale2) {
+  constexpr bool F8 = sizeof(WT) == 1;
+  constexpr int NP = F8 ? 4 : 8;      // 16-byte weight pieces per lane and stage
   __shared__ __attribute__((aligned(16))) char ws[4][32 * 256];
   __shared__ __attribute__((aligned(16))) char xs[2][32 * VLM_G32_XP];
   const bf16* const tag = nullptr;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
   const int ntiles = (N + 31) / 32;
   int bx = blockIdx.x;
-  if (bx >= cols1) { bx -= cols1; w = w2; part = part2; }
+  if (bx >= cols1) { bx -= cols1; w = w2; part = part2; wscale = wscale2; }
   const int nt = min(bx * 4 + wave, ntiles - 1);      // a workgroup's waves past the last tile repeat it (and do not store)
   const int n0 = nt * 32;
   const int nst = K / 128;
   const int s0 = blockIdx.y * stages_per_wg, s1 = min(s0 + stages_per_wg, nst);
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   // weight piece i of a stage: row 4 i + lane / 16 of the tile, 16 bytes at 16 (lane % 16) of the row's 256
-  const int wrow = lane >> 4, wpc = lane & 15;
-  const bf16* wsrc[8];
-  int wdst[8];
+  // (e4m3: row 8 i + lane / 8, 16 codes at 16 (lane % 8) of the row's 128, bound for the image's slots 2 (lane % 8) and 2 (lane % 8) + 1)
+  const int wrow = F8 ? lane >> 3 : lane >> 4, wpc = F8 ? lane & 7 : lane & 15;
+  const WT* wsrc[NP];
+  int wdst[NP];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = 4 * i + wrow, nr = min(n0 + row, N - 1);      // rows past N: a valid row, dropped at the store
-    wsrc[i] = w + (size_t)nr * ldw + wpc * 8;
-    wdst[i] = row * 256 + ((wpc ^ (row & 15)) << 4);
+  for (int i = 0; i < NP; ++i) {
+    const int row = (F8 ? 8 : 4) * i + wrow, nr = min(n0 + row, N - 1);      // rows past N: a valid row, dropped at the store
+    wsrc[i] = w + (size_t)nr * ldw + wpc * (F8 ? 16 : 8);
+    wdst[i] = row * 256 + (((F8 ? 2 * wpc : wpc) ^ (row & 15)) << 4);
   }
-  auto fetch_w = [&](const int st, v4u (&dst)[8]) __attribute__((always_inline)) {
+  auto fetch_w = [&](const int st, v4u (&dst)[NP]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) dst[i] = *reinterpret_cast<const v4u*>(wsrc[i] + (size_t)st * 128);
+    for (int i = 0; i < NP; ++i) dst[i] = *reinterpret_cast<const v4u*>(wsrc[i] + (size_t)st * 128);
   };
   // activation piece i (of 2) of a stage: row (t + 256 i) / 16, 16 bytes at 16 ((t + 256 i) % 16)
   auto stage_x = [&](const int st, char* dst) __attribute__((always_inline)) {
@@ -361,7 +475,7 @@ __global__ __launch_bounds__(256) void vlm_gemm32_kernel(const bf16* __restrict_
   fe_f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  v4u wr[2][8];
+  v4u wr[2][NP];
   char* const wl = ws[wave];
   if (s0 < s1) { fetch_w(s0, wr[0]); stage_x(s0, xs[0]); }
   __syncthreads();
@@ -373,7 +487,16 @@ __global__ __launch_bounds__(256) void vlm_gemm32_kernel(const bf16* __restrict_
       if (cur < s1) {
         if (cur + 1 < s1) fetch_w(cur + 1, wr[u ^ 1]);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<v4u*>(wl + wdst[i]) = wr[u][i];
+        for (int i = 0; i < NP; ++i) {
+          if constexpr (F8) {
+            uint4 lo, hi;
+            vlm_e4m3_widen16(make_uint4(wr[u][i][0], wr[u][i][1], wr[u][i][2], wr[u][i][3]), lo, hi);
+            *reinterpret_cast<uint4*>(wl + wdst[i]) = lo;
+            *reinterpret_cast<uint4*>(wl + (wdst[i] ^ 16)) = hi;
+          } else {
+            *reinterpret_cast<v4u*>(wl + wdst[i]) = wr[u][i];
+          }
+        }
         if (cur + 1 < s1) stage_x(cur + 1, xs[u ^ 1]);      // the other buffer: its readers passed the barrier one stage ago
         const char* const xb = xs[u] + r * VLM_G32_XP + 64 * h;
 #pragma unroll
@@ -394,7 +517,7 @@ __global__ __launch_bounds__(256) void vlm_gemm32_kernel(const bf16* __restrict_
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int nn = (e & 3) + 8 * (e >> 2) + 4 * h;
-      if (n0 + nn < N) out[nn] = acc[e];
+      if (n0 + nn < N) out[nn] = F8 ? acc[e] * wscale[n0 + nn] : acc[e];
     }
   }
 }
@@ -414,8 +537,11 @@ __global__ void vlm_gemm32_finish_kernel(const float* __restrict__ part, int spl
 static int vlm_gemm32_partials(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float** part, const ConvW* w2 = nullptr, float** part2 = nullptr,
                                float* direct = nullptr) {
   const int K = w.CinPadH, N = w.Cout;
-  FE_CHECK(w.wh && w.hprec == PREC_BF16 && !w.scale && K % 128 == 0 && w.KpH % 8 == 0 && ldx % 8 == 0 && M >= 1 && M <= 32, "vlm_gemm32: unsupported layer");
-  FE_CHECK(!w2 || (w2->wh && w2->hprec == PREC_BF16 && !w2->scale && w2->CinPadH == K && w2->Cout == N && w2->KpH == w.KpH && part2), "vlm_gemm32: the paired matrix differs in shape");
+  const bool f8 = w.w8 != nullptr;
+  FE_CHECK((f8 ? w.w8_scale && w.KpH % 16 == 0 : w.wh && w.hprec == PREC_BF16 && w.KpH % 8 == 0) && !w.scale && K % 128 == 0 && ldx % 8 == 0 && M >= 1 && M <= 32,
+           "vlm_gemm32: unsupported layer");
+  FE_CHECK(!w2 || ((f8 ? w2->w8 && w2->w8_scale : w2->wh && w2->hprec == PREC_BF16) && !w2->scale && w2->CinPadH == K && w2->Cout == N && w2->KpH == w.KpH && part2),
+           "vlm_gemm32: the paired matrix differs in shape or format");
   const int ntiles = (N + 31) / 32, cols = (ntiles + 3) / 4, nst = K / 128, allcols = w2 ? 2 * cols : cols;
   // ~3 workgroups per CU stream from all of HBM; the partial sums of a split cost 4 M N bytes each way: no more splits than that needs,
   // and at least 4 stages per workgroup
@@ -424,8 +550,13 @@ static int vlm_gemm32_partials(Ctx& c, const ConvW& w, const bf16* x, int ldx, i
   splits = (nst + per - 1) / per;
   *part = splits == 1 && direct ? direct : c.arena.array<float>((size_t)splits * M * N);
   if (w2) *part2 = c.arena.array<float>((size_t)splits * M * N);
-  hipLaunchKernelGGL(vlm_gemm32_kernel, dim3(allcols, splits), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, *part, M, N, K, per,
-                     w2 ? (const bf16*)w2->wh : (const bf16*)nullptr, w2 ? *part2 : (float*)nullptr, cols);
+  if (f8)
+    hipLaunchKernelGGL(vlm_gemm32_kernel<uint8_t>, dim3(allcols, splits), dim3(256), 0, c.stream, x, ldx, (const uint8_t*)w.w8, w.KpH, *part, M, N, K, per,
+                       w2 ? (const uint8_t*)w2->w8 : (const uint8_t*)nullptr, w2 ? *part2 : (float*)nullptr, cols, (const float*)w.w8_scale,
+                       w2 ? (const float*)w2->w8_scale : (const float*)nullptr);
+  else
+    hipLaunchKernelGGL(vlm_gemm32_kernel<bf16>, dim3(allcols, splits), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, *part, M, N, K, per,
+                       w2 ? (const bf16*)w2->wh : (const bf16*)nullptr, w2 ? *part2 : (float*)nullptr, cols, (const float*)nullptr, (const float*)nullptr);
   FE_HIP(hipGetLastError());
   const double fl = 2.0 * M * (double)w.Cin * N * (w2 ? 2 : 1);
   c.flops_accum += fl; c.flops_half += fl;
@@ -516,9 +647,45 @@ __global__ void vlm_finish_silu_mul_kernel(const float* __restrict__ pg, const f
     st4(hout + 4 * i, make_float4(f(g.x, u.x), f(g.y, u.y), f(g.z, u.z), f(g.w, u.w)));
   }
 }
+// e4m3 rows -> a bf16 matrix [Cout][KpH] in the layout of ConvW.wh: decode(code) * 2^e, exactly a bf16 value (fp8_core.h), so the shared
+// layer wrappers then compute what they compute for a bf16 model loaded with the dequantised weights. One thread per 16 codes.
+__global__ void vlm_e4m3_dequant_kernel(const uint8_t* __restrict__ w8, const float* __restrict__ wscale, bf16* __restrict__ out, size_t n16, int kp16) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) {
+    const float sc = wscale[i / kp16];
+    uint4 lo, hi;
+    vlm_e4m3_widen16(*reinterpret_cast<const uint4*>(w8 + i * 16), lo, hi);
+    // the scaled value has at most 4 significant bits and a normal exponent: the upper 16 bits of the fp32 product ARE its bf16 form
+    auto sc2 = [sc](const unsigned u) { return (__float_as_uint(__uint_as_float(u << 16) * sc) >> 16) | (__float_as_uint(__uint_as_float(u & 0xFFFF0000u) * sc) & 0xFFFF0000u); };
+    uint4* o = reinterpret_cast<uint4*>(out + i * 16);
+    o[0] = make_uint4(sc2(lo.x), sc2(lo.y), sc2(lo.z), sc2(lo.w));
+    o[1] = make_uint4(sc2(hi.x), sc2(hi.y), sc2(hi.z), sc2(hi.w));
+  }
+}
+// the bf16 view of an e4m3 layer, in arena scratch (the CALLER rewinds): for more than 32 rows (prefill; decode beyond 32 sequences, which
+// this extra pass makes slower than a bf16 model's) and for the shapes the e4m3 kernels do not take
+static ConvW vlm_e4m3_widen(Ctx& c, const ConvW& w) {
+  FE_CHECK(w.w8 && w.w8_scale && w.KpH % 16 == 0, "vlm: layer has no e4m3 rows");
+  ConvW t = w;
+  const size_t n = (size_t)w.Cout * w.KpH;
+  bf16* wide = c.arena.array<bf16>(n);
+  hipLaunchKernelGGL(vlm_e4m3_dequant_kernel, dim3(grid_n(n / 16)), dim3(256), 0, c.stream, (const uint8_t*)w.w8, (const float*)w.w8_scale, wide, n / 16, w.KpH / 16);
+  FE_HIP(hipGetLastError());
+  t.wh = wide; t.hprec = PREC_BF16; t.w8 = nullptr; t.w8_scale = nullptr;
+  return t;
+}
 // y = x W^T (+ b) in bf16 for any row count: the streaming GEMV for up to 4 rows, the weight-streaming matrix-core GEMM up to 32, the
-// shared layer wrapper above that
+// shared layer wrapper above that (an e4m3 layer: the same choice among its own kernels, the wrapper on its bf16 scratch)
 static void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy) {
+  if (w.w8) {
+    if (M <= 4 && !vlm_uses_gemm32(w, M) && vlm_e4m3_gemv_ok(w)) vlm_gemv(c, w, x, ldx, M, y, ldy);
+    else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy);
+    else {
+      const size_t mark = c.arena.mark();
+      linear_forward(c, vlm_e4m3_widen(c, w), x, ldx, M, y, ldy, ACT_NONE);
+      c.arena.rewind(mark);
+    }
+    return;
+  }
   if (M <= 4 && !vlm_uses_gemm32(w, M)) vlm_gemv(c, w, x, ldx, M, y, ldy);
   else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy);
   else linear_forward(c, w, x, ldx, M, y, ldy, ACT_NONE);
@@ -804,7 +971,48 @@ bf16* upload_bf16(DeviceWeights& dw, const std::vector<float>& v) {
   return (bf16*)dw.upload_raw(h.data(), h.size() * sizeof(uint16_t));
 }
 
-void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
+// FE_VLM_WEIGHTS_E4M3: a Linear weight [N][K] (+ bias) as the e4m3 form of ConvW - every row rounded to bf16 as the bf16 commit does, then
+// quantised by fp8_core.h; no bf16 copy goes to the device. `name` is the tensor in the error of a NaN / Inf weight.
+static ConvW pack_linear_e4m3(DeviceWeights& dw, const HostTensor& W, const std::vector<float>* bias, const std::string& name) {
+  FE_CHECK(W.shape.size() == 2, "vlm: %s is not a matrix", name.c_str());
+  ConvW c;
+  c.Cout = (int)W.shape[0]; c.Cin = (int)W.shape[1];
+  c.CinPad = (c.Cin + 3) & ~3; c.K = c.CinPad; c.Kp = (c.K + CONV_KALIGN - 1) / CONV_KALIGN * CONV_KALIGN;
+  c.CinPadH = (c.Cin + 7) & ~7; c.cb = 32;
+  c.KpH = (c.CinPadH + CONV_KALIGN_H - 1) / CONV_KALIGN_H * CONV_KALIGN_H;
+  FE_CHECK(!bias || (int)bias->size() == c.Cout, "vlm: %s bias size", name.c_str());
+  std::vector<uint8_t> codes((size_t)c.Cout * c.KpH, 0);
+  std::vector<float> scales((size_t)c.Cout), row((size_t)c.Cin);
+  for (int n = 0; n < c.Cout; ++n) {
+    for (int k = 0; k < c.Cin; ++k) {
+      const uint32_t u = (uint32_t)f32_to_bf16_bits(W.data[(size_t)n * c.Cin + k]) << 16;
+      memcpy(&row[k], &u, 4);
+    }
+    int e = 0;
+    FE_CHECK(fp8::quantize_row(row.data(), (size_t)c.Cin, codes.data() + (size_t)n * c.KpH, &e), "vlm: %s holds a NaN or Inf (row %d): not quantised to e4m3", name.c_str(), n);
+    scales[n] = fp8::row_scale(e);
+  }
+  c.w8 = (uint8_t*)dw.upload_raw(codes.data(), codes.size());
+  c.w8_scale = dw.upload(scales);
+  if (bias) c.shift = dw.upload(*bias);
+  return c;
+}
+// a Linear of the decoder in the model's weight format (e4m3: `name` for the error message; bf16: build_linear_rows on all rows)
+static ConvW vlm_pack_linear(VlmModel& m, const HostTensor& W, const HostTensor* bias, const std::string& name) {
+  if (m.weight_format == FE_VLM_WEIGHTS_E4M3) return pack_linear_e4m3(m.dw, W, bias ? &bias->data : nullptr, name);
+  return build_linear_rows(m.dw, W, bias, 0, (int)W.shape[0]);
+}
+
+void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int weight_format) {
+  FE_CHECK(weight_format == FE_VLM_WEIGHTS_BF16 || weight_format == FE_VLM_WEIGHTS_E4M3, "vlm: weight format %d", weight_format);
+  m.weight_format = weight_format;
+  const bool f8 = weight_format == FE_VLM_WEIGHTS_E4M3;
+  // (e4m3: the parts of a fused q|k|v are checked under their own names before they are concatenated)
+  auto finite = [&](const HostTensor& t, const std::string& name) {
+    if (!f8) return;
+    for (const float v : t.data) FE_CHECK(std::isfinite(v), "vlm: %s.weight holds a NaN or Inf: not quantised to e4m3", name.c_str());
+  };
+  auto linear = [&](const std::string& prefix) { return f8 ? vlm_pack_linear(m, ws.get(prefix + ".weight"), nullptr, prefix + ".weight") : build_linear(m.dw, ws, prefix, false); };
   m.cfg = cfg;
   m.dw.prec = PREC_BF16;
   m.dw.half_only = true;      // 7.6 G parameters: no fp32 / Winograd copies beside the bf16 ones
@@ -836,19 +1044,20 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
         FE_CHECK(!ws.has(L + ".self_attn." + n + ".bias"), "vlm (qwen3): layer %d %s carries a bias", i, n);
         const HostTensor& a = ws.get(L + ".self_attn." + n + ".weight");
         FE_CHECK((int)a.shape[1] == m.hidden, "vlm: %s input width", n);
+        finite(a, L + ".self_attn." + n);
         W.data.insert(W.data.end(), a.data.begin(), a.data.end());
       }
       FE_CHECK((int64_t)W.data.size() == W.shape[0] * W.shape[1], "vlm: layer %d q/k/v shapes do not match %d heads / %d kv heads of 128", i, cfg.n_heads, cfg.n_kv_heads);
-      w.qkv = build_linear_rows(m.dw, W, nullptr, 0, qd + 2 * kd);
+      w.qkv = vlm_pack_linear(m, W, nullptr, L + ".self_attn.q|k|v_proj.weight");
       const HostTensor& qn = ws.get(L + ".self_attn.q_norm.weight");
       const HostTensor& kn = ws.get(L + ".self_attn.k_norm.weight");
       FE_CHECK(qn.numel() == 128 && kn.numel() == 128, "vlm (qwen3): layer %d q_norm / k_norm must have 128 weights", i);
       w.qn = upload_bf16(m.dw, qn.data);
       w.kn = upload_bf16(m.dw, kn.data);
-      w.o = build_linear(m.dw, ws, L + ".self_attn.o_proj", false);
-      w.gate = build_linear(m.dw, ws, L + ".mlp.gate_proj", false);
-      w.up = build_linear(m.dw, ws, L + ".mlp.up_proj", false);
-      w.down = build_linear(m.dw, ws, L + ".mlp.down_proj", false);
+      w.o = linear(L + ".self_attn.o_proj");
+      w.gate = linear(L + ".mlp.gate_proj");
+      w.up = linear(L + ".mlp.up_proj");
+      w.down = linear(L + ".mlp.down_proj");
       w.ln1 = upload_bf16(m.dw, ws.get(L + ".input_layernorm.weight").data);
       w.ln2 = upload_bf16(m.dw, ws.get(L + ".post_attention_layernorm.weight").data);
       m.layers.push_back(w);
@@ -861,29 +1070,40 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg) {
       const HostTensor& a = ws.get(L + ".self_attn." + n + ".weight");
       const HostTensor& bb = ws.get(L + ".self_attn." + n + ".bias");
       FE_CHECK((int)a.shape[1] == m.hidden, "vlm: %s input width", n);
+      finite(a, L + ".self_attn." + n);
       W.data.insert(W.data.end(), a.data.begin(), a.data.end());
       Bv.data.insert(Bv.data.end(), bb.data.begin(), bb.data.end());
     }
     FE_CHECK((int64_t)W.data.size() == W.shape[0] * W.shape[1], "vlm: layer %d q/k/v shapes do not match %d heads / %d kv heads of 128", i, cfg.n_heads, cfg.n_kv_heads);
-    w.qkv = build_linear_rows(m.dw, W, &Bv, 0, qd + 2 * kd);
-    w.o = build_linear(m.dw, ws, L + ".self_attn.o_proj", false);
-    w.gate = build_linear(m.dw, ws, L + ".mlp.gate_proj", false);
-    w.up = build_linear(m.dw, ws, L + ".mlp.up_proj", false);
-    w.down = build_linear(m.dw, ws, L + ".mlp.down_proj", false);
+    w.qkv = vlm_pack_linear(m, W, &Bv, L + ".self_attn.q|k|v_proj.weight");
+    w.o = linear(L + ".self_attn.o_proj");
+    w.gate = linear(L + ".mlp.gate_proj");
+    w.up = linear(L + ".mlp.up_proj");
+    w.down = linear(L + ".mlp.down_proj");
     w.ln1 = upload_bf16(m.dw, ws.get(L + ".input_layernorm.weight").data);
     w.ln2 = upload_bf16(m.dw, ws.get(L + ".post_attention_layernorm.weight").data);
     m.layers.push_back(w);
   }
   FE_CHECK(!m.layers.empty(), "vlm: no decoder layers found");
   m.norm = upload_bf16(m.dw, ws.get(P + "norm.weight").data);
-  if (tied) {
+  if (tied && f8) {      // the lookup keeps the bf16 table (looked-up rows are the original ones); the head is an e4m3 copy of it
+    m.embed = upload_bf16(m.dw, E.data);
+    m.lm_head = vlm_pack_linear(m, E, nullptr, P + "embed_tokens.weight");
+  } else if (tied) {
     m.lm_head = build_linear_rows(m.dw, E, nullptr, 0, m.vocab);
     FE_CHECK(m.lm_head.wh && m.lm_head.hprec == PREC_BF16, "vlm: tied lm_head needs the bf16 form");
     if (m.lm_head.KpH == m.hidden) m.embed = (bf16*)m.lm_head.wh;      // one device copy: rows [vocab][hidden], row-major
     else m.embed = upload_bf16(m.dw, E.data);
   } else {
-    m.lm_head = build_linear(m.dw, ws, "lm_head", false);
+    m.lm_head = linear("lm_head");
   }
+  m.weight_bytes = m.scale_bytes = m.quant_rows = 0;
+  auto count = [&](const ConvW& w) {
+    m.weight_bytes += (int64_t)w.Cout * w.KpH * (w.w8 ? 1 : 2);
+    if (w.w8) { m.scale_bytes += 4 * (int64_t)w.Cout; m.quant_rows += w.Cout; }
+  };
+  for (const VlmLayerW& w : m.layers) { count(w.qkv); count(w.o); count(w.gate); count(w.up); count(w.down); }
+  count(m.lm_head);
   FE_CHECK(cfg.n_deepstack <= (int)m.layers.size(), "vlm: %d DeepStack levels for %zu decoder layers", cfg.n_deepstack, m.layers.size());
   m.inter = m.layers[0].gate.Cout;
   // inv_freq as Qwen2_5_VLRotaryEmbedding.compute_default_rope_parameters: 1 / base^(2i / dim), fp32
@@ -1052,8 +1272,9 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   else
     hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)B * 64)), dim3(256), 0, c.stream, (const bf16*)last, d, (const bf16*)m.norm, lastn, d, B, d, g.rms_eps);
   float* lg = logits_dev ? logits_dev : c.arena.array<float>((size_t)B * m.vocab);
-  if (B <= 4 && !vlm_uses_gemm32(m.lm_head, B)) vlm_gemv(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
+  if (B <= 4 && !vlm_uses_gemm32(m.lm_head, B) && (!m.lm_head.w8 || vlm_e4m3_gemv_ok(m.lm_head))) vlm_gemv(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
   else if (B <= 32 && d % 128 == 0) vlm_gemm32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
+  else if (m.lm_head.w8) linear_forward_f32(c, vlm_e4m3_widen(c, m.lm_head), (const bf16*)lastn, d, B, lg, m.vocab, ACT_NONE);      // (scratch: rewound below)
   else linear_forward_f32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab, ACT_NONE);
   vlm_select(c, lg, B, m.vocab, next_dev, lp_dev);
   m.cur_len = Lk;

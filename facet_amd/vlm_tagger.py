@@ -312,6 +312,10 @@ class VLMTagger:
         self.tokens = dict(QWEN3_VL_TOKENS if self.family == "qwen3" else QWEN2_5_VL_TOKENS, **(special_tokens or {}))
         self.batch_size = model_config.get("vlm_batch_size", 4 if self.family == "qwen3" else 2)
         self.valid_tags = set(scoring_config.get_tag_vocabulary().keys()) if scoring_config else set()
+        # "bf16" (the reference's dtype) or "fp8": the decoder's Linear weights as e4m3 rows (Engine.vlm_weight_format)
+        self.weight_format = model_config.get("weight_format", "bf16")
+        if self.weight_format not in ("bf16", "fp8"):
+            raise ValueError(f"weight_format {self.weight_format!r}: 'bf16' or 'fp8'")
         self._prompt = None
 
     # -- lifecycle (ModelManager calls load / unload around a pass) ------------------------------------------------------------------
@@ -323,6 +327,7 @@ class VLMTagger:
         if state_dict is None:
             raise FileNotFoundError("no checkpoint: pass the model's state dict (the reference downloads it with from_pretrained, "
                                     "models/vlm_tagger.py:170-176; there is no network here)")
+        self.engine.vlm_weight_format(self.weight_format)      # read by the commit below
         if self.family == "qwen3":      # Qwen3VLForConditionalGeneration: geometry = Engine.vlm3_configure's arguments (default Qwen3-VL-2B)
             self.engine.vlm3_configure(**dict(geometry or QWEN3_VL_2B))
             self.engine.load_weights(FE_MODEL_VLM, state_dict)

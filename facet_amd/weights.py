@@ -444,6 +444,56 @@ def synthetic_images(seed, n, h, w):
     return np.random.default_rng(seed).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
 
 
+# ---------------------------------------------------------------------------------------------------
+# e4m3 weight rows of the VLM decoders (Engine.vlm_weight_format("fp8")): facet_amd/csrc/fp8_core.h restated in numpy
+# ---------------------------------------------------------------------------------------------------
+
+def _round_bf16(w):
+    """float32 -> the nearest-even bfloat16 value, as float32 (what the engine stores for a Linear weight)."""
+    u = np.ascontiguousarray(w, np.float32).view(np.uint32)          # (finite inputs: the sum below stays inside 32 bits)
+    return ((u + np.uint32(0x7FFF) + ((u >> 16) & 1)) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def _e4m3_values():
+    c = np.arange(256)
+    E, m = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(E == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (E.astype(np.float64) - 10))
+    v[(E == 15) & ((c & 7) == 7)] = np.nan
+    return np.where(c & 0x80, -v, v).astype(np.float32)
+
+
+def quantize_e4m3_rows(w):
+    """w [N, K] float -> (codes uint8 [N, K], exponents int8 [N]): what a commit under vlm_weight_format("fp8") stores for a Linear
+    weight. w is rounded to bf16 first, as the engine does; row n then gets the smallest exponent e_n with max|w[n]| * 2^-e_n <= 448
+    (frexp; 0 for a zero row; clamped to >= -117) and codes w[n] * 2^-e_n rounded to nearest-even OCP e4m3. NaN / Inf raise."""
+    w = np.asarray(w, np.float32)
+    if w.ndim != 2:
+        raise ValueError("quantize_e4m3_rows takes a [rows, K] matrix")
+    if not np.isfinite(w).all() or not np.isfinite(w := _round_bf16(w)).all():
+        raise ValueError("quantize_e4m3_rows: NaN or Inf in the weight")
+    a = np.abs(w).max(1) if w.shape[1] else np.zeros(w.shape[0], np.float32)
+    f, x = np.frexp(a)                                  # a = f * 2^x, f in [0.5, 1); 448 = 0.875 * 2^9
+    e = np.where(a > 0, np.where(f <= 0.875, x - 9, x - 8), 0)
+    e = np.maximum(e, -117).astype(np.int32)
+    s = np.ldexp(w, -e[:, None])                        # float32, exact; |s| <= 448 by the choice of e
+    u = s.view(np.uint32)
+    sign = ((u >> 24) & 0x80).astype(np.uint8)
+    u = u & 0x7FFFFFFF
+    # nearest even at 3 mantissa bits on the fp32 bit pattern (e4m3's exponent field is fp32's minus 120); below 2^-6 the grid has step
+    # 2^-9, which is the ulp of 2^14 + |s| in fp32 (the addition rounds to nearest even)
+    normal = (((u + 0x7FFFF + ((u >> 20) & 1)) >> 20) - (120 << 3)).astype(np.uint8)
+    sub = ((u.view(np.float32) + np.float32(16384.0)).view(np.uint32) - 0x46800000).astype(np.uint8)
+    codes = np.where(u < 0x3C800000, sub, normal) | sign
+    return codes, e.astype(np.int8)
+
+
+def dequantize_e4m3_rows(codes, exponents):
+    """(codes uint8 [N, K], exponents int8 [N]) -> float32 [N, K]: decode(code) * 2^e, every value exactly a bf16 value."""
+    codes = np.asarray(codes, np.uint8)
+    e = np.asarray(exponents).astype(np.int32)
+    return np.ldexp(_e4m3_values()[codes], e[:, None])          # float32: exact, the result is a bf16 value
+
+
 def checkpoint_or_synthetic(kind, weights_path, synthetic, seed, loader):
     """The state dict the drop-in wrappers load. A real checkpoint path wins. Without one the reference would download the weights
     (pyiqa / open_clip / the aesthetic head, models/pyiqa_scorer.py:108, model_manager.py:140, processing/scorer.py:560-577) and fail

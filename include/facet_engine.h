@@ -84,8 +84,9 @@ int fe_model_precision(fe_ctx* ctx, int model); /* enum fe_precision value of a 
 /* ---- VLM tagger (BASELINE configs[4]), slice 1: the text decoder --------------------------------------------
  * Reference: models/vlm_tagger.py loads transformers' Qwen2_5_VLForConditionalGeneration in bfloat16 (:155-184) and calls
  * generate(**inputs, max_new_tokens=..., do_sample=False) (:250-259, :355-360). FE_MODEL_VLM takes that class's state dict (tensor
- * names model.language_model.* and lm_head.weight; model.visual.* is ignored in this slice) and always runs in bf16, with the
- * rounding points of the bf16 torch modules. Token ids in, token ids out: tokenizer, chat template and tag parsing stay on the host
+ * names model.language_model.* and lm_head.weight; model.visual.* is ignored in this slice) and computes in bf16, with the
+ * rounding points of the bf16 torch modules; the decoder's Linear weights are stored as bf16 too unless fe_vlm_set_weight_format
+ * asked for e4m3 rows (below), which changes the weights' values and nothing else. Token ids in, token ids out: tokenizer, chat template and tag parsing stay on the host
  * (facet_amd/vlm_tagger.py). fe_vlm_configure gives the geometry the tensor shapes do not determine (defaults = Qwen2.5-VL-7B:
  * 28 heads, 4 KV heads, head_dim 128, rope_theta 1e6, rms eps 1e-6, mrope_section 16/24/24) and is read by the NEXT
  * fe_weights_commit(FE_MODEL_VLM).
@@ -95,6 +96,19 @@ int fe_model_precision(fe_ctx* ctx, int model); /* enum fe_precision value of a 
  * ties, as torch.argmax) and, when `logits` is not NULL, those logits [n_seq][vocab]. fe_vlm_decode_step appends one token per
  * sequence (tokens [n_seq], position_ids [3][n_seq]). dims: vocab, hidden, layers, heads, kv_heads, intermediate, max_seq, cur_len. */
 int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section);
+/* Storage of the decoder's Linear weights (all three families), read by the NEXT fe_weights_commit(FE_MODEL_VLM); any other value is an
+ * error. FE_VLM_WEIGHTS_E4M3: q|k|v, o, gate, up, down of every layer and lm_head are kept as OCP e4m3 codes with one power-of-two scale
+ * per output row (row n: the smallest e with max|w[n]| * 2^-e <= 448, e >= -117; code = w * 2^-e rounded to nearest even, from the
+ * bf16-rounded weight) and no bf16 copy of them is uploaded: a decode step streams half the bytes. Every dequantised value is exactly a
+ * bf16 value, so the model is the bf16 model on those weights: activations, attention, the KV cache, norms, biases, the embedding table
+ * (a tied checkpoint keeps its bf16 table for the lookup beside the e4m3 head) and the vision tower are untouched. Up to 32 rows the
+ * projections read the codes directly; above that (prefill, more than 32 sequences) each matrix is widened to a bf16 scratch in the arena
+ * first - one extra pass, so decode beyond 32 sequences is slower than with bf16 weights. A NaN or Inf weight fails the commit.
+ * fe_vlm_weight_info: info4 = the loaded model's format, the stored bytes of the matrices a decode step streams (layer projections +
+ * lm_head), the bytes of their row scales, the number of quantised rows. */
+enum fe_vlm_weights { FE_VLM_WEIGHTS_BF16 = 0, FE_VLM_WEIGHTS_E4M3 = 1 };
+int fe_vlm_set_weight_format(fe_ctx* ctx, int format);
+int fe_vlm_weight_info(fe_ctx* ctx, int64_t* info4);
 /* Vision tower (slice 2; built when the FE_MODEL_VLM checkpoint carries model.visual.*): geometry the tensor shapes do not determine
  * (defaults = Qwen2.5-VL-7B: 16 heads of 80, full attention in blocks 7 / 15 / 23 / 31, every other block inside 112-pixel windows), read
  * by the NEXT fe_weights_commit(FE_MODEL_VLM).

@@ -3,6 +3,13 @@
   python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32] [--vision N] [--from-rgb N] [--pad P]
   python tools/perf_vlm.py --family qwen3 [--prompt 512] [--new 32] [--batches 1,4,32] [--vision N]
   python tools/perf_vlm.py --scores [--layers 4] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 7]
+  python tools/perf_vlm.py --weights bf16,fp8 [--family qwen2_5|qwen3|qwen2] [--layers 8] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 5]
+
+--weights: one column per weight format (Engine.vlm_weight_format) of the chosen family's decoder - qwen3 / qwen2 at full depth, qwen2_5 at
+--layers layers of the 7B geometry. Every format's engine is loaded with the same seeded weights; the formats are timed alternately,
+--reps times each, per batch: prefill tokens/s (device timer) and the device-resident decode loop (fe_vlm_generate; host clock around the
+call, which ends in a synchronise) as median ms/step with the spread of the repetitions, tokens/s, and the fraction of the 8 TB/s HBM peak
+that the bytes of fe_vlm_weight_info (weights + row scales, streamed once per step) amount to at that time.
 
 --scores: the device-resident decode loop with the chosen tokens' log-probs (fe_vlm_generate_scored) against the plain loop
 (fe_vlm_generate) at the 7B geometry, same prefill, --reps alternating repetitions of each; prints the median ms/step of both and the
@@ -40,7 +47,8 @@ ap.add_argument("--pad", type=int, default=0, help="also time decode steps with 
 ap.add_argument("--family", default="qwen2_5", choices=("qwen2_5", "qwen3", "qwen2"))
 ap.add_argument("--qwen25-layers", type=int, default=4, help="--family qwen3: layers of the Qwen2.5-VL-7B decoder timed at batch 4 for comparison")
 ap.add_argument("--scores", action="store_true", help="time fe_vlm_generate_scored against fe_vlm_generate (ms/step) and stop")
-ap.add_argument("--reps", type=int, default=7, help="--scores: alternating repetitions of each loop")
+ap.add_argument("--reps", type=int, default=7, help="--scores / --weights: alternating repetitions of each loop")
+ap.add_argument("--weights", default=None, help="comma-separated weight formats (bf16, fp8): one column per format, then stop")
 a = ap.parse_args()
 
 
@@ -60,6 +68,59 @@ def decode_rate(e, B, L, new, V):
     return t_pre, t_dec, (t_all - t_pre) / new
 
 
+def weights_table():
+    from facet_amd.weights import qwen2_vl_text_spec, qwen3_vl_text_spec
+    from facet_amd.vlm_composition import QWEN2_VL_2B
+    from facet_amd.vlm_tagger import QWEN3_VL_2B
+    fmts = a.weights.split(",")
+    if a.family == "qwen3":
+        spec, V, what = qwen3_vl_text_spec(), 151936, "Qwen3-VL-2B decoder, 28 layers (full depth), tied head"
+        conf = lambda e: e.vlm3_configure(**QWEN3_VL_2B)
+    elif a.family == "qwen2":
+        spec, V, what = qwen2_vl_text_spec(), 151936, "Qwen2-VL-2B decoder, 28 layers (full depth), tied head"
+        conf = lambda e: e.vlm2_configure(**QWEN2_VL_2B)
+    else:
+        spec, V = qwen2_5_vl_text_spec(hidden=3584, layers=a.layers, heads=28, kv_heads=4, inter=18944, vocab=152064), 152064
+        what = f"Qwen2.5-VL-7B decoder geometry, {a.layers} of 28 layers + lm_head"
+        conf = lambda e: e.vlm_configure(28, 4, 128, 1e6, 1e-6, (16, 24, 24))
+    sd = synthetic_state_dict(None, 3, spec=spec)
+    eng, info = {}, {}
+    for f in fmts:
+        e = Engine(0, arena_bytes=24 << 30)
+        conf(e)
+        e.vlm_weight_format(f)
+        t0 = time.time(); e.load_weights(FE_MODEL_VLM, sd)
+        eng[f], info[f] = e, e.vlm_weight_info()
+        print(f"{f}: committed in {time.time() - t0:.0f} s: {info[f]}", flush=True)
+    del sd
+    L, new = a.prompt, a.new
+    print(f"{what}; prompt {L}, {new} decode steps per call, median (min..max) of {a.reps} alternating calls per format", flush=True)
+    for B in [int(b) for b in a.batches.split(",")]:
+        p = np.random.default_rng(B).integers(0, V, (B, L)).astype(np.int32)
+        pre, dec = {f: [] for f in fmts}, {f: [] for f in fmts}
+        for r in range(a.reps + 1):                      # (the first round warms up: graph capture, first-use attributes)
+            for f in fmts:
+                e = eng[f]
+                e.timer_start(); e.vlm_prefill(p, max_seq=L + new + 8); t_pre = e.timer_stop()
+                e.sync()
+                t0 = time.perf_counter(); e.vlm_generate(p, new + 1); t_all = (time.perf_counter() - t0) * 1e3
+                if r:
+                    pre[f].append(t_pre); dec[f].append((t_all - t_pre) / new)
+        for f in fmts:
+            t, tp = float(np.median(dec[f])), float(np.median(pre[f]))
+            by = info[f]["weight_bytes"] + info[f]["scale_bytes"]
+            print(f"{a.family} {f:4s} B={B:3d}: prefill {B * L / tp * 1e3:9.0f} tok/s ({tp:.2f} ms) | decode {t:7.4f} ms/step ({min(dec[f]):.4f}..{max(dec[f]):.4f}) = "
+                  f"{B / t * 1e3:8.0f} tok/s | {by / 1e9:.3f} GB per step = {by / t / 1e6:6.0f} GB/s = {by / t / 1e6 / 8000:.3f} of HBM peak", flush=True)
+        if len(fmts) > 1:
+            t0 = float(np.median(dec[fmts[0]]))
+            print("    decode ms/step " + ", ".join(f"{f} / {fmts[0]} = {float(np.median(dec[f])) / t0:.3f}" for f in fmts[1:]), flush=True)
+    for e in eng.values():
+        e.close()
+
+
+if a.weights:
+    weights_table()
+    sys.exit(0)
 if a.family == "qwen2":
     # Qwen2-VL-2B (the composition model) at full depth: tower at 1296 and 5120 patches, prefill, decode ms/step at the --batches, and the
     # stop-at-EOS loop against the full one at 256 steps when every row finishes by step 64. Every figure beside its HBM-bound estimate.
