@@ -1,6 +1,7 @@
 // Engine runtime: weight packing, conv/linear wrappers and the ResNet graphs.
 #include "engine.h"
 #include "onnx_graph.h"
+#include "wino64_maps.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -140,6 +141,14 @@ ConvW pack_conv(DeviceWeights& dw, const HostTensor& w, const std::vector<float>
       }
     c.wino = dw.upload(U);
     c.wino_m = wino_form;
+  }
+  if (!skip_f32 && dw.prec == PREC_F32 && c.KH == 3 && c.KW == 3 && c.CinPad >= 56 && c.CinPad <= 64 && c.Cout > 32 && c.Cout <= 64 && c.Cout % 4 == 0) {
+    // in-register F(2x2,3x3) (kernels_wino64.hip): U in matrix-fragment order, 262 KB per layer; channels past Cin are zero rows of U.
+    // The kernel always walks 64 input channels and 64 output rows: fewer than 56 / 33 of them would issue no fewer matrix instructions
+    // than the direct kernel. (Stride and activation, which also decide the route, are not known at pack time.)
+    std::vector<float> U(w64::U_FLOATS);
+    w64::pack_u(w.data.data(), c.Cout, c.Cin, U.data());
+    c.wino64 = dw.upload(U);
   }
   if (scale) c.scale = dw.upload(*scale);
   if (shift) c.shift = dw.upload(*shift);
@@ -336,13 +345,45 @@ void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, cons
       return;
     }
   }
+  // In-register Winograd F(2x2,3x3) for the 3x3 stride-1 layers over (up to) 64 packed input channels, which the three-launch forms
+  // above leave to the direct kernel: one launch, 16/36 of the direct kernel's multiplies. Epilogues with an erf or exp per output (GELU,
+  // sigmoid, ...) stay on the direct kernel: measured slower here (profiles/wino64_perf.txt).
+  static const bool no_wino64 = getenv("FE_NO_WINO64") != nullptr;
+  if (w.wino64 && !no_wino64 && p.variant == 0 && (o.act == ACT_NONE || o.act == ACT_RELU || o.act == ACT_PRELU) && o.sh == 1 && o.sw == 1 && o.ph == 1 && o.pw == 1 && o.dh == 1 && o.dw == 1 && !o.gate && y.h == x.h &&
+      y.w == x.w && (((uintptr_t)x.p | (uintptr_t)y.p | (uintptr_t)(o.res ? o.res->p : nullptr)) & 15) == 0 && x.ld % 4 == 0 && y.ld % 4 == 0 &&
+      (!o.res || o.res->ld % 4 == 0) && (unsigned long long)x.h * x.w * x.ld * 4ull < 0xF0000000ull) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c.profile) {
+      FE_HIP(hipEventCreate(&e0)); FE_HIP(hipEventCreate(&e1));
+      FE_HIP(hipEventRecord(e0, c.stream));
+    }
+    launch_wino64(x, y, w.wino64, w.scale, w.shift, w.slope, o.act, o.res, o.res_after_act, c.stream);
+    const double direct = 2.0 * p.M * (double)(9 * w.Cin) * (w.CoutAlg ? w.CoutAlg : p.Cout);
+    if (c.profile) {
+      FE_HIP(hipEventRecord(e1, c.stream));
+      FE_HIP(hipEventSynchronize(e1));
+      float ms = 0.f;
+      FE_HIP(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+      char nm[128];
+      snprintf(nm, sizeof nm, "wino64 3x3 M=%d K=%d N=%d", p.M, p.K, p.Cout);
+      const double bytes = 4.0 * ((double)x.pixels() * x.c + (double)y.pixels() * y.c * (o.res ? 2 : 1) + (double)w64::U_FLOATS);
+      c.timings.push_back({nm, direct, bytes, ms});
+    }
+    const double tiles = (double)x.n * ((x.h + 1) / 2) * ((x.w + 1) / 2);
+    c.flops_accum += direct;
+    c.flops_saved += direct - 2.0 * 16.0 * tiles * 64.0 * w.Cout;
+    return;
+  }
   // Split-K for few-row, long-K products (ArcFace's 25088 -> 512 embedding layer on a handful of faces; SAMP-Net's eight pattern layers,
   // K = 2592 .. 7524 -> 1024, at micro-batches above 32 rows: SAMP stage 3290 -> 3330 images/s): a single tile row would walk K
   // serially on Cout/64 CUs. K is cut into equal slices that run as ONE batched launch into [splits][M][Cout] partials, which
   // splitk_reduce sums in a fixed order and finishes with the epilogue.
   static const bool no_splitk = getenv("FE_NO_SPLITK") != nullptr;
+  // (A/B hook; 4096 until round 3)
+  static const int splitk_min = getenv("FE_SPLITK_MIN") ? atoi(getenv("FE_SPLITK_MIN")) : 2048;
   if (!no_splitk && w.KH == 1 && w.KW == 1 && o.sh == 1 && o.sw == 1 && o.ph == 0 && o.pw == 0 && !o.gate && p.variant == 0 && p.M <= 256 &&
-      w.CinPad >= (getenv("FE_SPLITK_MIN") ? atoi(getenv("FE_SPLITK_MIN")) : 2048) && w.K == w.CinPad &&      // (A/B hook; 4096 until round 3) (size_t)((p.M + 127) / 128) * ((w.Cout + 63) / 64) < 64 &&
+      w.CinPad >= splitk_min && w.K == w.CinPad && (size_t)((p.M + 127) / 128) * ((w.Cout + 63) / 64) < 64 &&
       (o.act == ACT_NONE || o.act == ACT_RELU || o.act == ACT_PRELU)) {
     int splits = 0;
     for (int s = 64; s >= 2; --s)

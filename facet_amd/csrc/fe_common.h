@@ -284,6 +284,7 @@ struct ConvW {
   float* wtap = nullptr;
   int wino_m = 0;          // 2 or 4: which Winograd form `wino` holds (F(2x2,3x3): 16 planes, F(4x4,3x3): 36 planes)
   float* wino = nullptr;   // 3x3 convs with Cin >= 256 also carry Winograd F(2x2,3x3) weights U[16][Cout][Cin]
+  float* wino64 = nullptr; // fp32 3x3 layers with 56 .. 64 packed input and 36 .. 64 output channels also carry the U fragments of kernels_wino64.hip
   float* wstem = nullptr;  // 7x7 or 3x3, Cin <= 3, Cout 32|64 stems also carry the [taps][Cout][4] layout of kernels_stem.hip
   float* wn16 = nullptr;   // fp32 3x3 layers with 16 output channels and 16 / 32 / 64 input channels also carry the layout of kernels_n16.hip
   int KpT = 0;
@@ -324,6 +325,9 @@ void launch_wino_output(const float* Mb, const Tensor& y, int th, int tw, const 
 void launch_wino4_input(const Tensor& x, int th, int tw, float* V, hipStream_t s);     // F(4x4,3x3): [36][tiles][C] planes
 void launch_wino4_output(const float* Mb, const Tensor& y, int th, int tw, const float* scale, const float* shift, int act, const float* slope,
                          const Tensor* res, int res_after_act, hipStream_t s);
+// in-register Winograd F(2x2,3x3) for up to 64 -> 64 channels in one launch (kernels_wino64.hip); U: w64::pack_u (wino64_maps.h)
+void launch_wino64(const Tensor& x, const Tensor& y, const float* U, const float* scale, const float* shift, const float* slope, int act,
+                   const Tensor* res, int res_after_act, hipStream_t s);
 template <class TO>   // TO = float | bf16: the stem always reads fp32 NHWC4 pixels; it can hand bf16 activations to the bf16 path
 bool launch_stem(const float* x, int ldx, int N, int H, int W, const float* wstem, const float* scale, const float* shift, const float* slope,
                  int Cout, int k, int stride, int act, TO* y, int ldy, int Ho, int Wo, hipStream_t s);   // kernels_stem.hip; false = shape not handled
