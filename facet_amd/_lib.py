@@ -31,6 +31,7 @@ ACT = {"none": 0, None: 0, "relu": 1, "gelu": 2, "sigmoid": 3, "softplus": 5}
 
 
 VLM_WEIGHT_FORMATS = {"bf16": 0, "fp8": 1}      # FE_VLM_WEIGHTS_BF16 / FE_VLM_WEIGHTS_E4M3
+VLM_KV_FORMATS = {"bf16": 0, "fp8": 1, "bf16_e4m3": 2}      # FE_VLM_KV_BF16 / FE_VLM_KV_E4M3 / FE_VLM_KV_BF16_E4M3
 
 
 class EngineError(RuntimeError):
@@ -99,6 +100,8 @@ SIGNATURES = {
     "fe_op_mha": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                             C.c_int, _f32p]),
     "fe_op_vlm_select": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
+    "fe_op_vlm_decode_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                             _f32p, _f32p, _f32p]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
     "fe_topiq_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -121,6 +124,9 @@ SIGNATURES = {
     "fe_vlm_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "fe_vlm_set_weight_format": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_vlm_weight_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "fe_vlm_set_kv_format": (C.c_int, [C.c_void_p, C.c_int]),
+    "fe_vlm_kv_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "fe_vlm_kv_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     "fe_vlm_prefill": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_decode_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_vlm_vision_configure": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -757,6 +763,49 @@ class Engine:
         d = (C.c_int64 * 4)()
         self._ck(self.lib.fe_vlm_weight_info(self.h, d))
         return dict(format={v: k for k, v in VLM_WEIGHT_FORMATS.items()}[int(d[0])], weight_bytes=int(d[1]), scale_bytes=int(d[2]), quantized_rows=int(d[3]))
+
+    def vlm_kv_format(self, fmt="bf16"):
+        """Storage of the decoder's KV cache, read by the NEXT prefill (fe_vlm_set_kv_format); independent of vlm_weight_format. "bf16"
+        (default), "fp8" - every cache row (the 128 values of one sequence, KV head and position, K and V separately) as OCP e4m3 codes
+        with one power-of-two scale, the row rule of facet_amd.weights.quantize_e4m3_rows: 264 bytes per token, KV head and layer instead
+        of 512, read directly by the decode attention - or "bf16_e4m3": a bf16 cache holding dequantize(quantize(row)), the arithmetic of
+        "fp8" at the storage of "bf16" (for tests and accuracy studies). A change of format drops the live cache."""
+        if fmt not in VLM_KV_FORMATS:
+            raise ValueError(f"vlm_kv_format {fmt!r}: one of {sorted(VLM_KV_FORMATS)}")
+        self._ck(self.lib.fe_vlm_set_kv_format(self.h, VLM_KV_FORMATS[fmt]))
+
+    def vlm_kv_info(self):
+        """fe_vlm_kv_info: the format of the next prefill's cache, the bytes one token of one sequence takes in it over all layers, the
+        bytes allocated for the live cache (0 before a prefill) and its max_seq."""
+        d = (C.c_int64 * 4)()
+        self._ck(self.lib.fe_vlm_kv_info(self.h, d))
+        return dict(format={v: k for k, v in VLM_KV_FORMATS.items()}[int(d[0])], bytes_per_token=int(d[1]), allocated_bytes=int(d[2]), max_seq=int(d[3]))
+
+    def vlm_kv_rows(self, layer, seq, kv_head, pos0=0, n=None):
+        """Rows pos0 .. pos0 + n - 1 (n None: up to the cache length) of the live cache of (layer, sequence, KV head), dequantised:
+        (k, v) float32 [n, 128] (fe_vlm_kv_rows)."""
+        if n is None:
+            n = self.vlm_dims()["cur_len"] - int(pos0)
+        k, v = np.empty((int(n), 128), np.float32), np.empty((int(n), 128), np.float32)
+        self._ck(self.lib.fe_vlm_kv_rows(self.h, int(layer), int(seq), int(kv_head), int(pos0), int(n), k.ctypes.data_as(_f32p), v.ctypes.data_as(_f32p)))
+        return k, v
+
+    def vlm_decode_attention(self, q, k, v, pad=None, kv_format="bf16", len_from_device=False):
+        """The decode attention of the VLM decoders launched alone (fe_op_vlm_decode_attention): q [B, nh, 128], k / v [B, nkv, Lk, 128]
+        (rounded to bf16), pad int [B] (left padding; None: zeros), the cache built in kv_format by the engine's own fill pass ->
+        (out [B, nh, 128], k_image, v_image [B, nkv, Lk, 128]: the dequantised cache rows)."""
+        if kv_format not in VLM_KV_FORMATS:
+            raise ValueError(f"kv_format {kv_format!r}: one of {sorted(VLM_KV_FORMATS)}")
+        (q, qp), (k, kp), (v, vp) = _f32(q), _f32(k), _f32(v)
+        B, nh, _ = q.shape
+        _, nkv, Lk, _ = k.shape
+        assert q.shape == (B, nh, 128) and k.shape == (B, nkv, Lk, 128) and v.shape == k.shape, (q.shape, k.shape, v.shape)
+        pd, pdp = self._i32(np.zeros(B, np.int32) if pad is None else pad)
+        assert pd.shape == (B,), pd.shape
+        out, ki, vi = np.empty_like(q), np.empty_like(k), np.empty_like(v)
+        self._ck(self.lib.fe_op_vlm_decode_attention(self.h, qp, kp, vp, B, nh, nkv, Lk, pdp, VLM_KV_FORMATS[kv_format], int(bool(len_from_device)),
+                                                     out.ctypes.data_as(_f32p), ki.ctypes.data_as(_f32p), vi.ctypes.data_as(_f32p)))
+        return out, ki, vi
 
     def vlm_vision_configure(self, n_heads=16, fullatt_block_indexes=(7, 15, 23, 31)):
         """Vision-tower geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (Qwen2_5_VLVisionConfig; defaults = Qwen2.5-VL-7B)."""

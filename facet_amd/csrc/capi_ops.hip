@@ -1,5 +1,6 @@
 // C ABI: single operators and kernels launched alone, the test hooks of the suite.
 #include "capi_internal.h"
+#include "fp8_core.h"
 
 extern "C" {
 
@@ -284,6 +285,62 @@ int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int3
     FE_HIP(hipMemcpyAsync(ids, d_ids, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, C.stream));
     if (d_lp) FE_HIP(hipMemcpyAsync(logprobs, d_lp, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, C.stream));
     FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+// Test hook of the VLM decode attention (vlm_decode_attention in model_vlm.hip, with the cache built by vlm_kv_fill), launched alone.
+int fe_op_vlm_decode_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int nkv, int Lk, const int32_t* pad, int kv_format,
+                               int len_from_device, float* out, float* k_image, float* v_image) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(q && k && v && pad && out && B > 0 && nkv > 0 && nh > 0 && nh % nkv == 0 && nh / nkv <= 8 && Lk > 0 && Lk <= 8192, "bad decode attention arguments");
+    FE_CHECK(kv_format == FE_VLM_KV_BF16 || kv_format == FE_VLM_KV_E4M3 || kv_format == FE_VLM_KV_BF16_E4M3, "fe_op_vlm_decode_attention: kv format %d", kv_format);
+    for (int b = 0; b < B; ++b) FE_CHECK(pad[b] >= 0 && pad[b] < Lk, "fe_op_vlm_decode_attention: pad %d of %d keys", pad[b], Lk);
+    C.arena.reset();
+    // graph-replay form: the grid covers a cache longer than Lk (whole chunks past the length, and one that starts inside it)
+    const int max_seq = len_from_device ? Lk + 2 * 128 + 37 : Lk;
+    const size_t nq = (size_t)B * nh * 128, rows = (size_t)B * nkv * Lk, nk = rows * 128, crow = (size_t)B * nkv * max_seq;
+    float *dq = upload(C, q, nq), *dk = upload(C, k, nk), *dv = upload(C, v, nk);
+    int* dpad = upload(C, pad, (size_t)B);
+    bf16 *hq = C.arena.array<bf16>(nq), *hk = C.arena.array<bf16>(nk), *hv = C.arena.array<bf16>(nk), *ho = C.arena.array<bf16>(nq);
+    launch_convert(dq, hq, nq, C.stream);
+    launch_convert(dk, hk, nk, C.stream);
+    launch_convert(dv, hv, nk, C.stream);
+    const bool f8 = kv_format == FE_VLM_KV_E4M3;
+    VlmKv kv;
+    kv.format = kv_format; kv.max_seq = max_seq;
+    kv.k = (bf16*)C.arena.alloc(crow * 128 * (f8 ? 1 : sizeof(bf16)));
+    kv.v = (bf16*)C.arena.alloc(crow * 128 * (f8 ? 1 : sizeof(bf16)));
+    if (f8) { kv.ks = C.arena.array<float>(crow); kv.vs = C.arena.array<float>(crow); }
+    vlm_kv_fill(C, kv, hk, hv, B * nkv, Lk);
+    int* dlen = nullptr;
+    if (len_from_device) { const int last = Lk - 1; dlen = upload(C, &last, 1); FE_HIP(hipStreamSynchronize(C.stream)); }
+    const int nsplit = (max_seq + 127) / 128;
+    float *po = C.arena.array<float>(nq * nsplit), *pm = C.arena.array<float>((size_t)B * nh * nsplit), *pl = C.arena.array<float>((size_t)B * nh * nsplit);
+    vlm_decode_attention(C, kv, hq, B, nh, nkv, Lk, dlen, dpad, po, pm, pl, nsplit, ho);
+    launch_convert(ho, dq, nq, C.stream);      // dq is free again: the fp32 copy of the output
+    FE_HIP(hipMemcpyAsync(out, dq, nq * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    // the cache rows as the kernel read them, dequantised on the host (fp8_core.h)
+    for (int which = 0; which < 2; ++which) {
+      float* img = which ? v_image : k_image;
+      if (!img) continue;
+      const bf16* src = which ? kv.v : kv.k;
+      const size_t esz = f8 ? 1 : sizeof(uint16_t);
+      std::vector<uint8_t> raw(crow * 128 * esz);
+      std::vector<float> sc(f8 ? crow : 0);
+      FE_HIP(hipMemcpyAsync(raw.data(), src, raw.size(), hipMemcpyDeviceToHost, C.stream));
+      if (f8) FE_HIP(hipMemcpyAsync(sc.data(), which ? kv.vs : kv.ks, crow * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+      for (size_t r = 0; r < rows; ++r) {
+        const size_t cr = (r / Lk) * max_seq + r % Lk;
+        for (int d = 0; d < 128; ++d) {
+          if (f8) img[r * 128 + d] = fp8::e4m3_decode(raw[cr * 128 + d]) * sc[cr];
+          else { uint16_t h; memcpy(&h, &raw[(cr * 128 + d) * 2], 2); const uint32_t u = (uint32_t)h << 16; memcpy(&img[r * 128 + d], &u, 4); }
+        }
+      }
+    }
+    return FE_OK;
   });
 }
 

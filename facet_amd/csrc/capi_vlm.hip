@@ -1,5 +1,6 @@
 // C ABI: the three VLM families (Qwen2.5-VL, Qwen2-VL, Qwen3-VL) - configure, preprocess, vision encode, prefill, decode.
 #include "capi_internal.h"
+#include "fp8_core.h"
 
 namespace {
 // ---- the blocks every vision encode entry point repeats ----
@@ -279,6 +280,58 @@ int fe_vlm_weight_info(fe_ctx* ctx, int64_t* info4) {
     return FE_OK;
   });
 }
+int fe_vlm_set_kv_format(fe_ctx* ctx, int format) {
+  return fe_api(ctx, [&] {
+    FE_CHECK(format == FE_VLM_KV_BF16 || format == FE_VLM_KV_E4M3 || format == FE_VLM_KV_BF16_E4M3,
+             "vlm_set_kv_format: %d (FE_VLM_KV_BF16, FE_VLM_KV_E4M3 or FE_VLM_KV_BF16_E4M3)", format);
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    ctx->c.vlm_kv_format = format;
+    // a live cache in another format is gone: decode calls fail until the next prefill
+    if (ctx->c.vlm && ctx->c.vlm->cache_B > 0 && ctx->c.vlm->kv_format != format) {
+      FE_HIP(hipStreamSynchronize(ctx->c.stream));
+      ctx->c.vlm->release_cache();
+    }
+  });
+}
+int fe_vlm_kv_info(fe_ctx* ctx, int64_t* info4) {
+  return fe_api(ctx, [&] {
+    if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+    FE_CHECK(info4, "bad arguments");
+    const VlmModel& m = *ctx->c.vlm;
+    info4[0] = ctx->c.vlm_kv_format; info4[1] = m.kv_token_bytes(ctx->c.vlm_kv_format); info4[2] = m.cache_bytes; info4[3] = m.max_seq;
+    return FE_OK;
+  });
+}
+int fe_vlm_kv_rows(fe_ctx* ctx, int layer, int seq, int kv_head, int pos0, int n, float* k, float* v) {
+  return fe_api(ctx, [&] {
+    if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
+    Ctx& C = ctx->c;
+    const VlmModel& m = *C.vlm;
+    FE_CHECK(m.cache_B > 0 && m.cur_len > 0, "kv_rows: call fe_vlm_prefill first");
+    FE_CHECK(k && v && layer >= 0 && layer < (int)m.layers.size() && seq >= 0 && seq < m.cache_B && kv_head >= 0 && kv_head < m.cfg.n_kv_heads && pos0 >= 0 && n > 0 &&
+             pos0 + n <= m.cur_len, "kv_rows: layer %d, sequence %d, kv head %d, positions %d .. %d outside the live cache (%d positions)", layer, seq, kv_head, pos0,
+             pos0 + n - 1, m.cur_len);
+    const size_t row0 = ((size_t)seq * m.cfg.n_kv_heads + kv_head) * m.max_seq + pos0, cnt = (size_t)n * 128;
+    for (int which = 0; which < 2; ++which) {
+      float* out = which ? v : k;
+      const bf16* src = which ? m.vcache[layer] : m.kcache[layer];
+      if (m.kv_format == FE_VLM_KV_E4M3) {      // codes and scales to the host, decoded by fp8_core.h
+        std::vector<uint8_t> codes(cnt);
+        std::vector<float> sc((size_t)n);
+        FE_HIP(hipMemcpyAsync(codes.data(), (const uint8_t*)src + row0 * 128, cnt, hipMemcpyDeviceToHost, C.stream));
+        FE_HIP(hipMemcpyAsync(sc.data(), (which ? m.vscale[layer] : m.kscale[layer]) + row0, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+        FE_HIP(hipStreamSynchronize(C.stream));
+        for (size_t i = 0; i < cnt; ++i) out[i] = fp8::e4m3_decode(codes[i]) * sc[i / 128];
+      } else {
+        std::vector<uint16_t> h(cnt);
+        FE_HIP(hipMemcpyAsync(h.data(), src + row0 * 128, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost, C.stream));
+        FE_HIP(hipStreamSynchronize(C.stream));
+        for (size_t i = 0; i < cnt; ++i) { const uint32_t u = (uint32_t)h[i] << 16; memcpy(&out[i], &u, 4); }
+      }
+    }
+    return FE_OK;
+  });
+}
 // ---- Qwen3-VL: the same decoder entry points serve the family the next commit builds --------------------------------------------------------
 int fe_vlm3_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, float rope_theta, float rms_eps, const int* mrope_section, int vis_heads,
                       const int* deepstack_indexes, int n_deepstack) {
@@ -353,7 +406,7 @@ int fe_vlm_prefill(fe_ctx* ctx, const int32_t* tokens, const int32_t* position_i
   return fe_api(ctx, [&] {
     if (!ctx->c.vlm) { ctx->c.err = "vlm weights not loaded"; return FE_ERR_NOT_LOADED; }
     FE_CHECK(tokens && position_ids && next_tokens && n_seq > 0 && len > 0 && max_seq >= len && max_seq <= 8192, "bad arguments (max_seq <= 8192)");
-    ctx->c.vlm->reserve_cache(n_seq, max_seq);
+    ctx->c.vlm->reserve_cache(n_seq, max_seq, ctx->c.vlm_kv_format);
     ctx->c.vlm->cur_len = 0;
     vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits);
     return FE_OK;
@@ -368,7 +421,7 @@ int fe_vlm_prefill_images(fe_ctx* ctx, const int32_t* tokens, const int32_t* pos
     FE_CHECK(n_image_rows == 0 || (image_rows && n_image_rows == m.img_rows), "prefill_images: %d placeholder rows but the last fe_vlm_encode_images left %d embeddings",
              n_image_rows, m.img_rows);
     for (int i = 0; i < n_image_rows; ++i) FE_CHECK(image_rows[i] >= 0 && image_rows[i] < n_seq * len, "prefill_images: row index out of range");
-    m.reserve_cache(n_seq, max_seq);
+    m.reserve_cache(n_seq, max_seq, ctx->c.vlm_kv_format);
     m.cur_len = 0;
     vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits, image_rows, n_image_rows);
     return FE_OK;
@@ -385,7 +438,7 @@ int fe_vlm_prefill_images_padded(fe_ctx* ctx, const int32_t* tokens, const int32
              n_image_rows, m.img_rows);
     for (int i = 0; i < n_image_rows; ++i)
       FE_CHECK(image_rows[i] >= 0 && image_rows[i] < n_seq * len && image_rows[i] % len >= pad[image_rows[i] / len], "prefill_images_padded: row index %d out of range or in the pad", image_rows[i]);
-    m.reserve_cache(n_seq, max_seq);
+    m.reserve_cache(n_seq, max_seq, ctx->c.vlm_kv_format);
     m.cur_len = 0;
     vlm_step(ctx, tokens, position_ids, n_seq, len, next_tokens, logits, image_rows, n_image_rows, pad);
     return FE_OK;

@@ -298,6 +298,7 @@ struct Ctx {
   std::unique_ptr<struct ClipTextModel> clip_text;
   std::unique_ptr<struct VlmModel> vlm;
   VlmConfig vlm_cfg;          // read by the next fe_weights_commit(FE_MODEL_VLM) (fe_vlm_configure)
+  int vlm_kv_format = 0;      // FE_VLM_KV_* of the next prefill's cache (fe_vlm_set_kv_format)
   int vlm_weight_format = 0;  // FE_VLM_WEIGHTS_* of the next fe_weights_commit(FE_MODEL_VLM) (fe_vlm_set_weight_format)
   std::unique_ptr<GraphSlot> graphs[8];   // ONNX graphs (face detector / landmarks / recognition, ...)
   ~Ctx();
@@ -447,7 +448,12 @@ struct VlmModel {
   VlmVisionW vis;
   bf16* img_embeds = nullptr; int img_rows = 0, img_cap = 0;      // merged image embeddings of the last fe_vlm_encode_images (device)
   // contiguous KV cache: per layer [n_seq][n_kv_heads][max_seq][128] keys (rotated) and values
+  // kv_format (FE_VLM_KV_*, fe_vlm_set_kv_format; model_vlm.hip "KV-cache formats"): under FE_VLM_KV_E4M3 kcache / vcache hold the code arrays
+  // ([n_seq][n_kv_heads][max_seq][128] uint8) and kscale / vscale the row scales ([n_seq][n_kv_heads][max_seq] fp32)
   std::vector<bf16*> kcache, vcache;
+  std::vector<float*> kscale, vscale;
+  int kv_format = 0;
+  int64_t cache_bytes = 0;      // allocated for K / V rows and scales, all layers
   int cache_B = 0, max_seq = 0, cur_len = 0;
   // left padding of every sequence (device int [cache_B]): set by each prefill (zeros unless fe_vlm_prefill_images_padded), read by the
   // attention kernels of the prefill and of every later decode step (a captured decode graph holds the pointer)
@@ -463,8 +469,9 @@ struct VlmModel {
   VlmLnVisionW vis_ln;
   bf16* ds_feats = nullptr; int ds_n = 0, ds_cap = 0;
   const int* ds_slot = nullptr;
-  void reserve_cache(int B, int max_seq);
+  void reserve_cache(int B, int max_seq, int kv_format = 0);      // a change of shape or format releases the cache first
   void release_cache();
+  int64_t kv_token_bytes(int format) const;      // bytes one token of one sequence takes over all layers
   ~VlmModel() { release_cache(); if (img_embeds) (void)hipFree(img_embeds); if (pre_pv) (void)hipFree(pre_pv); if (ds_feats) (void)hipFree(ds_feats); }
 };
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int weight_format = 0);
@@ -503,6 +510,15 @@ void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, in
 void vlm_embed(Ctx& c, const VlmModel& m, const int* tok_dev, int rows, bf16* x);
 void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev = nullptr,
                  float* lp_dev = nullptr);
+// One layer's KV cache in its format (E4M3: k / v are the code arrays, ks / vs the row scales; else ks = vs = nullptr)
+struct VlmKv { int format = 0; bf16* k = nullptr; bf16* v = nullptr; float* ks = nullptr; float* vs = nullptr; int max_seq = 0; };
+// bf16 rows ksrc / vsrc [n][L][128] (n = sequences x KV heads) -> positions 0 .. L - 1 of the cache, in its format
+void vlm_kv_fill(Ctx& c, const VlmKv& kv, const bf16* ksrc, const bf16* vsrc, int n, int L);
+// decode attention of one query row per head over the cache (+ the merge of the key chunks): q / out [B][nh * 128]; Lk keys by value or
+// (len_dev != nullptr) *len_dev + 1 of them, the grid then covering max_seq; pad: device [B]. po / pm / pl: arena scratch for nsplit chunks
+// ([B * nh * nsplit * 128], [B * nh * nsplit] twice), nsplit = ceil((len_dev ? max_seq : Lk) / 128).
+void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh, int nkv, int Lk, const int* len_dev, const int* pad, float* po, float* pm,
+                          float* pl, int nsplit, bf16* out);
 // fe_vlm_generate_until: the stop rule of a decode loop. fin_dev [B]: -1 while a sequence runs, else the EOS id it emitted (set by the
 // caller for sequences whose first token already is one); live_dev [1]: the count of running sequences after the last step, read by the
 // host after every `poll` steps. steps_run: out, the steps executed.

@@ -10,7 +10,9 @@
 // weight multiply, both products of the rotary embedding, SiLU before the gate multiply, each residual sum, the logits), fp32
 // accumulation inside every contraction. Parity: tests/test_vlm_gpu.py against vectors of the reference's own model class
 // (tests/golden/make_vlm_golden.py) - pinned.
-// Not in this slice: the vision tower (window attention, patch merger) and fp8 attention; image tokens enter as rows of `embeds`.
+// Not in this slice: the vision tower (window attention, patch merger) and fp8 matrix-core attention; image tokens enter as rows of `embeds`.
+// KV-cache storage: bf16, or (FE_VLM_KV_E4M3) e4m3 rows with one power-of-two scale each, read by a decode attention kernel of their own -
+// see "KV-cache formats" below.
 // Weight storage: bf16, or (FE_VLM_WEIGHTS_E4M3) e4m3 rows with one power-of-two scale each (fp8_core.h) for the Linear layers - the
 // same arithmetic on other weight values, see "e4m3 weights" below.
 #include "engine.h"
@@ -59,15 +61,69 @@ __global__ void vlm_rmsnorm_kernel(const bf16* __restrict__ x, int ldx, const bf
   }
 }
 
+// ---- KV-cache formats (FE_VLM_KV_*, fe_vlm_set_kv_format) --------------------------------------------------------------------------------
+// One cache row = the 128 values of one (sequence, KV head, position), K and V separately. FE_VLM_KV_E4M3 stores it as 128 OCP e4m3 codes
+// and the fp32 scale 2^e of fp8_core.h's row rule (codes [B][nkv][max_seq][128] uint8, scales [B][nkv][max_seq]): 132 bytes instead of 256.
+// Every dequantised value is exactly a bf16 value, so the engine under it is the bf16 engine whose cache rows were replaced by
+// dequantize(quantize(row)); FE_VLM_KV_BF16_E4M3 stores exactly those rows in a bf16 cache (the arithmetic of the format at the storage of
+// bf16: it separates what the format costs from what the e4m3 kernels do, for tests and accuracy studies).
+// The store of one row held by a wave, lane l owning dims l and l + 64 (the layout of both rope kernels): the row maximum is a wave
+// reduction over the magnitudes' bit patterns (monotone for non-negative floats; a NaN or Inf sorts above every finite value), then
+// row_exponent / e4m3_encode of fp8_core.h, so the bits are the host's. A row with a NaN or Inf becomes NaN codes with scale 1.
+// `cache` is the bf16 cache, or (E4M3) the code array; `ri` the row index (b * nkv + head) * max_seq + position.
+template <int KV>
+__device__ __forceinline__ void vlm_kv_store_row(bf16* __restrict__ cache, float* __restrict__ scales, const size_t ri, const int lane, const bf16 r1, const bf16 r2) {
+  if constexpr (KV == FE_VLM_KV_BF16) {
+    bf16* dst = cache + ri * 128;
+    dst[lane] = r1; dst[lane + 64] = r2;
+  } else {
+    const float x1 = (float)r1, x2 = (float)r2;
+    uint32_t a = max(fp8::f32_bits(x1) & 0x7FFFFFFFu, fp8::f32_bits(x2) & 0x7FFFFFFFu);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = max(a, (uint32_t)__shfl_xor((int)a, o));
+    const bool finite = a < 0x7F800000u;
+    const int e = finite ? fp8::row_exponent(fp8::bits_f32(a)) : 0;
+    const float inv = fp8::row_scale(-e), sc = fp8::row_scale(e);
+    const uint8_t c1 = finite ? fp8::e4m3_encode(x1 * inv) : (uint8_t)0x7F, c2 = finite ? fp8::e4m3_encode(x2 * inv) : (uint8_t)0x7F;
+    if constexpr (KV == FE_VLM_KV_E4M3) {
+      uint8_t* dst = reinterpret_cast<uint8_t*>(cache) + ri * 128;
+      dst[lane] = c1; dst[lane + 64] = c2;
+      if (lane == 0) scales[ri] = sc;
+    } else {      // the image of the row, exactly bf16 values
+      bf16* dst = cache + ri * 128;
+      dst[lane] = (bf16)(fp8::e4m3_decode(c1) * sc); dst[lane + 64] = (bf16)(fp8::e4m3_decode(c2) * sc);
+    }
+  }
+}
+// rows [n][L][128] bf16 (a prefill's K or V of one layer, n = sequences x KV heads) -> positions 0 .. L - 1 of a cache in format KV. One
+// wave per row. The prefill under the e4m3 formats attends to the unquantised rows and fills the cache with this pass.
+template <int KV>
+__global__ void vlm_kv_fill_kernel(const bf16* __restrict__ ksrc, const bf16* __restrict__ vsrc, bf16* __restrict__ kc, bf16* __restrict__ vc, float* __restrict__ ksc,
+                                   float* __restrict__ vsc, int n, int L, int max_seq) {
+  const int lane = threadIdx.x & 63;
+  const size_t total = (size_t)2 * n * L, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+  for (size_t wv = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < total; wv += nwaves) {
+    const bool isv = wv >= (size_t)n * L;
+    const size_t r = isv ? wv - (size_t)n * L : wv;
+    const bf16* src = (isv ? vsrc : ksrc) + r * 128;
+    const size_t ri = (r / L) * max_seq + r % L;
+    vlm_kv_store_row<KV>(isv ? vc : kc, isv ? vsc : ksc, ri, lane, src[lane], src[lane + 64]);
+  }
+}
+
 // Multimodal rotary embedding on the q and k heads of a fused QKV row block + the KV-cache append.
 //   qkv: [rows][(nh + 2 nkv) * 128]; pos: [3][rows] (temporal, height, width position of every token; equal for text tokens)
 //   q_out: [rows][nh * 128]; kc / vc: cache [B][nkv][max_seq][128], row `row` = (b, t) lands at position start + t.
 // Dimension i of a head takes frequency i % 64 and the position component of its section (sections doubled over the two halves:
 // [16, 24, 24, 16, 24, 24]); cos / sin are rounded to bf16 and x*cos, rotate_half(x)*sin and their sum are each rounded to bf16, as
 // apply_multimodal_rotary_pos_emb does on bf16 tensors. One thread per (row, head, pair d < 64).
+// KV: the cache format. A wave covers exactly one (row, head) per loop trip (64 lanes = the 64 pairs), so under the e4m3 formats the append
+// quantises the row in place (vlm_kv_store_row; ksc / vsc: the scale arrays of FE_VLM_KV_E4M3, kc / vc then the code arrays). The bf16
+// instantiation is the code this kernel was before the formats.
+template <int KV>
 __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, bf16* __restrict__ q_out,
                                       bf16* __restrict__ kc, bf16* __restrict__ vc, int rows, int L, int nh, int nkv, int s0, int s1, int start, int max_seq,
-                                      const int* __restrict__ start_dev) {
+                                      const int* __restrict__ start_dev, float* __restrict__ ksc, float* __restrict__ vsc) {
   if (start_dev) start = *start_dev;      // decode steps replayed from a captured graph: the cache length lives in device memory
   const int heads = nh + 2 * nkv;
   const size_t total = (size_t)rows * heads * 64;
@@ -76,6 +132,10 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
     const bf16* src = qkv + ((size_t)row * heads + hd) * 128;
     const int b = row / L, t = row - b * L;
     if (hd >= nh + nkv) {      // V: plain copy into the cache
+      if constexpr (KV != FE_VLM_KV_BF16) {
+        vlm_kv_store_row<KV>(vc, vsc, ((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t, d, src[d], src[d + 64]);
+        continue;
+      }
       bf16* dst = vc + (((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t) * 128;
       dst[d] = src[d]; dst[d + 64] = src[d + 64];
       continue;
@@ -86,6 +146,12 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
     const float x1 = (float)src[d], x2 = (float)src[d + 64];
     const bf16 o1 = (bf16)((float)(bf16)(x1 * c) + (float)(bf16)(-x2 * s));
     const bf16 o2 = (bf16)((float)(bf16)(x2 * c) + (float)(bf16)(x1 * s));
+    if constexpr (KV != FE_VLM_KV_BF16) {
+      if (hd >= nh) {      // (wave-uniform)
+        vlm_kv_store_row<KV>(kc, ksc, ((size_t)b * nkv + (hd - nh)) * max_seq + start + t, d, o1, o2);
+        continue;
+      }
+    }
     bf16* dst = hd < nh ? q_out + ((size_t)row * nh + hd) * 128 : kc + (((size_t)b * nkv + (hd - nh)) * max_seq + start + t) * 128;
     dst[d] = o1; dst[d + 64] = o2;
   }
@@ -97,9 +163,12 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
 //   norm: the fp32 sum of squares over the wave, n = bf16(x * rsqrt(mean + eps)), y = bf16(w * n)   (Qwen3VLTextRMSNorm on a bf16 tensor)
 //   rope: frequency j takes the height position when j % 3 == 1 and j < 3 s1, the width position when j % 3 == 2 and j < 3 s2, the temporal
 //         one otherwise (apply_interleaved_mrope); cos / sin rounded to bf16, products and sum rounded as vlm_rope_cache_kernel does
+// KV, ksc, vsc: the cache format, as in vlm_rope_cache_kernel
+template <int KV>
 __global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, const bf16* __restrict__ qn,
                                           const bf16* __restrict__ kn, bf16* __restrict__ q_out, bf16* __restrict__ kc, bf16* __restrict__ vc, int rows, int L, int nh,
-                                          int nkv, int s1, int s2, int start, int max_seq, const int* __restrict__ start_dev, float eps) {
+                                          int nkv, int s1, int s2, int start, int max_seq, const int* __restrict__ start_dev, float eps, float* __restrict__ ksc,
+                                          float* __restrict__ vsc) {
   if (start_dev) start = *start_dev;      // decode steps replayed from a captured graph: the cache length lives in device memory
   const int lane = threadIdx.x & 63;
   const int heads = nh + 2 * nkv;
@@ -114,8 +183,7 @@ __global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const in
     const int b = row / L, t = row - b * L;
     const bf16 r1 = src[lane], r2 = src[lane + 64];
     if (hd >= nh + nkv) {      // V: plain copy into the cache (wave-uniform branch)
-      bf16* dst = vc + (((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t) * 128;
-      dst[lane] = r1; dst[lane + 64] = r2;
+      vlm_kv_store_row<KV>(vc, vsc, ((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t, lane, r1, r2);
       continue;
     }
     const float x1 = (float)r1, x2 = (float)r2;
@@ -129,7 +197,11 @@ __global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const in
     const float c = (float)(bf16)cosf(ang), s = (float)(bf16)sinf(ang);
     const bf16 o1 = (bf16)((float)(bf16)(y1 * c) + (float)(bf16)(-y2 * s));
     const bf16 o2 = (bf16)((float)(bf16)(y2 * c) + (float)(bf16)(y1 * s));
-    bf16* dst = hd < nh ? q_out + ((size_t)row * nh + hd) * 128 : kc + (((size_t)b * nkv + (hd - nh)) * max_seq + start + t) * 128;
+    if (hd >= nh) {      // (wave-uniform)
+      vlm_kv_store_row<KV>(kc, ksc, ((size_t)b * nkv + (hd - nh)) * max_seq + start + t, lane, o1, o2);
+      continue;
+    }
+    bf16* dst = q_out + ((size_t)row * nh + hd) * 128;
     dst[lane] = o1; dst[lane + 64] = o2;
   }
 }
@@ -949,6 +1021,129 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16*
     po[(((size_t)b * nh + head0 + g) * nsplit + sp) * 128 + dm] = (part[0][g][dm] + part[1][g][dm]) + (part[2][g][dm] + part[3][g][dm]);
   }
 }
+// vlm_attn_decode_gqa_kernel on an FE_VLM_KV_E4M3 cache: the same grid, chunks, pad / len_dev handling and po / pm / pl outputs (and
+// vlm_attn_combine_kernel after it), half the K / V bytes. A key row is 128 contiguous codes: 16 lanes per key with 8 codes each (8-byte
+// loads, 512 contiguous bytes per wave instruction), widened by v_cvt_scalef32_pk_f32_fp8 (gfx950: the OCP reading, scale 1). The K scale
+// multiplies the score and the V scale the bf16-rounded probability, both exactly (powers of two): this is the bf16 kernel's arithmetic on
+// the dequantised rows, with the products and sums in its order. q stays bf16, accumulation fp32. Both kernels are bound by the vector ALU,
+// not by the K / V bytes (G = 7, 32 sequences x 1716 keys: the bf16 kernel 40 us, 2.8 TB/s), so the dot products and the P V sums here are
+// explicit fused multiply-adds - the file is compiled without contraction, which costs the bf16 kernel a multiply and an add per term:
+// 1892 against 2777 vector instructions at G = 7, 34 us (profiles/vlm_fp8_kv_perf.txt).
+__device__ __forceinline__ void vlm_e4m3_unpack8(const uint2 c, float v[8]) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  const f2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.x, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.x, 1.0f, true);
+  const f2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.y, 1.0f, false), e = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.y, 1.0f, true);
+  v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1]; v[4] = d[0]; v[5] = d[1]; v[6] = e[0]; v[7] = e[1];
+}
+template <int G>
+__global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const bf16* __restrict__ q, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc,
+                                                                       const float* __restrict__ ksc, const float* __restrict__ vsc, float* __restrict__ po,
+                                                                       float* __restrict__ pm, float* __restrict__ pl, int nh, int nkv, int Lk, int max_seq, float scale,
+                                                                       const int* __restrict__ len_dev, int nsplit, const int* __restrict__ pad) {
+  __shared__ float sc[G][VLM_DEC_CHUNK];      // scores, then probabilities times the V scales
+  __shared__ float part[4][G][128];
+  if (len_dev) Lk = *len_dev + 1;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int bk = blockIdx.x, sp = blockIdx.y;
+  const int b = bk / nkv, kvh = bk - b * nkv, head0 = kvh * G;
+  const int k0 = sp * VLM_DEC_CHUNK, k1 = min(k0 + VLM_DEC_CHUNK, Lk);
+  const int padb = pad[b];      // keys below it are left padding
+  if (k0 >= Lk || k1 <= padb) {      // a chunk past the cache length or wholly in the pad: neutral element of the merge
+    if (t < G) { pm[((size_t)b * nh + head0 + t) * nsplit + sp] = -INFINITY; pl[((size_t)b * nh + head0 + t) * nsplit + sp] = 0.f; }
+    return;
+  }
+  const size_t row0 = ((size_t)b * nkv + kvh) * max_seq;
+  const uint8_t* const K = kc + row0 * 128;
+  const uint8_t* const V = vc + row0 * 128;
+  const float* const KS = ksc + row0;
+  const float* const VS = vsc + row0;
+  // ---- scores: 16 lanes per key (8 codes each), 4 keys per wave instruction, 32 keys per wave ----------------------------------------------
+  {
+    const int sub = lane & 15, kk = lane >> 4;
+    float qf[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) h_unpack8_bf16(*reinterpret_cast<const uint4*>(q + ((size_t)b * nh + head0 + g) * 128 + 8 * sub), qf[g]);
+    uint2 kr[8];
+    float ks[8];
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int key = min(k0 + wave * 32 + it * 4 + kk, k1 - 1);
+      kr[it] = *reinterpret_cast<const uint2*>(K + (size_t)key * 128 + 8 * sub);
+      ks[it] = KS[key];
+    }
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int kl = wave * 32 + it * 4 + kk;
+      float kf[8];
+      vlm_e4m3_unpack8(kr[it], kf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float a = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a = __builtin_fmaf(kf[e], qf[g][e], a);
+        a = vlm_row16_sum(a);
+        if (sub == 0) sc[g][kl] = (k0 + kl < k1 && k0 + kl >= padb) ? (a * ks[it]) * scale : -INFINITY;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- softmax pieces per head: wave w takes heads w, w + 4; 2 keys per lane ---------------------------------------------------------------
+  for (int g = wave; g < G; g += 4) {
+    const float s0 = sc[g][lane], s1 = sc[g][64 + lane];
+    float mx = fmaxf(s0, s1);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    // probabilities as bf16 (the P operand of the reference's P V product), then times the key's V scale: p * (2^e * code) = (p * 2^e) * code
+    const float e0 = (float)(bf16)__expf(s0 - mx) * VS[min(k0 + lane, k1 - 1)], e1 = (float)(bf16)__expf(s1 - mx) * VS[min(k0 + 64 + lane, k1 - 1)];
+    float sum = __expf(s0 - mx) + __expf(s1 - mx);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    sc[g][lane] = e0; sc[g][64 + lane] = e1;
+    if (lane == 0) { pm[((size_t)b * nh + head0 + g) * nsplit + sp] = mx; pl[((size_t)b * nh + head0 + g) * nsplit + sp] = sum; }
+  }
+  __syncthreads();
+  // ---- O partials: the same 16-lanes-per-row pattern on V: lane (sub, kk) accumulates dims 8 sub .. 8 sub + 7 over keys 32 wave + 4 it + kk
+  // for every head; the four kk groups are then added with two shuffles ------------------------------------------------------------------
+  {
+    const int sub = lane & 15, kk = lane >> 4;
+    uint2 vr[8];
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int key = k0 + wave * 32 + it * 4 + kk;
+      vr[it] = *reinterpret_cast<const uint2*>(V + (size_t)min(key, k1 - 1) * 128 + 8 * sub);
+    }
+    float a[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[g][e] = 0.f;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int kl = wave * 32 + it * 4 + kk;      // probabilities of keys past the chunk's end are zero
+      float vf[8];
+      vlm_e4m3_unpack8(vr[it], vf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float pj = sc[g][kl];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[g][e] = __builtin_fmaf(pj, vf[e], a[g][e]);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float v = a[g][e];
+        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+        if (kk == 0) part[wave][g][8 * sub + e] = v;
+      }
+  }
+  __syncthreads();
+  for (int i = t; i < G * 128; i += 256) {
+    const int g = i >> 7, dm = i & 127;
+    po[(((size_t)b * nh + head0 + g) * nsplit + sp) * 128 + dm] = (part[0][g][dm] + part[1][g][dm]) + (part[2][g][dm] + part[3][g][dm]);
+  }
+}
 __global__ void vlm_attn_combine_kernel(const float* __restrict__ po, const float* __restrict__ pm, const float* __restrict__ pl, bf16* __restrict__ o, int nsplit) {
   const int bh = blockIdx.x, t = threadIdx.x;      // 128 threads: one per output dimension
   float M = -INFINITY;
@@ -1114,17 +1309,31 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int wei
   else build_vlm_vision(m, ws);
 }
 
-void VlmModel::reserve_cache(int B, int max_seq_) {
-  const size_t per = (size_t)B * cfg.n_kv_heads * max_seq_ * 128;
-  if (B == cache_B && max_seq_ == max_seq && !kcache.empty()) return;
+int64_t VlmModel::kv_token_bytes(int format) const {
+  return (int64_t)layers.size() * cfg.n_kv_heads * 2 * (format == FE_VLM_KV_E4M3 ? 128 + 4 : 256);
+}
+void VlmModel::reserve_cache(int B, int max_seq_, int format) {
+  FE_CHECK(format == FE_VLM_KV_BF16 || format == FE_VLM_KV_E4M3 || format == FE_VLM_KV_BF16_E4M3, "vlm: kv format %d", format);
+  const size_t rows = (size_t)B * cfg.n_kv_heads * max_seq_;
+  if (B == cache_B && max_seq_ == max_seq && format == kv_format && !kcache.empty()) return;
   release_cache();
+  kv_format = format;
+  const bool f8 = format == FE_VLM_KV_E4M3;
   for (size_t i = 0; i < layers.size(); ++i) {
     void *k = nullptr, *v = nullptr;
-    FE_HIP(hipMalloc(&k, per * sizeof(bf16)));
+    FE_HIP(hipMalloc(&k, rows * 128 * (f8 ? 1 : sizeof(bf16))));
     kcache.push_back((bf16*)k);
-    FE_HIP(hipMalloc(&v, per * sizeof(bf16)));
+    FE_HIP(hipMalloc(&v, rows * 128 * (f8 ? 1 : sizeof(bf16))));
     vcache.push_back((bf16*)v);
+    if (f8) {
+      void *ks = nullptr, *vs = nullptr;
+      FE_HIP(hipMalloc(&ks, rows * sizeof(float)));
+      kscale.push_back((float*)ks);
+      FE_HIP(hipMalloc(&vs, rows * sizeof(float)));
+      vscale.push_back((float*)vs);
+    }
   }
+  cache_bytes = (int64_t)layers.size() * 2 * rows * (f8 ? 128 + 4 : 256);
   FE_HIP(hipMalloc((void**)&pad, (size_t)B * sizeof(int)));
   FE_HIP(hipMemset(pad, 0, (size_t)B * sizeof(int)));
   FE_HIP(hipMalloc((void**)&last_lp, (size_t)B * sizeof(float)));
@@ -1134,11 +1343,54 @@ void VlmModel::reserve_cache(int B, int max_seq_) {
 void VlmModel::release_cache() {
   for (bf16* p : kcache) (void)hipFree(p);
   for (bf16* p : vcache) (void)hipFree(p);
+  for (float* p : kscale) (void)hipFree(p);
+  for (float* p : vscale) (void)hipFree(p);
   if (pad) (void)hipFree(pad);
   if (last_lp) (void)hipFree(last_lp);
   pad = nullptr; last_lp = nullptr;
-  kcache.clear(); vcache.clear();
-  cache_B = 0; max_seq = 0; cur_len = 0;
+  kcache.clear(); vcache.clear(); kscale.clear(); vscale.clear();
+  cache_B = 0; max_seq = 0; cur_len = 0; cache_bytes = 0;
+}
+
+void vlm_kv_fill(Ctx& c, const VlmKv& kv, const bf16* ksrc, const bf16* vsrc, int n, int L) {
+  FE_CHECK(n > 0 && L > 0 && L <= kv.max_seq && kv.k && kv.v && (kv.format != FE_VLM_KV_E4M3 || (kv.ks && kv.vs)), "vlm_kv_fill: %d rows of %d do not fit the cache", L, kv.max_seq);
+  const dim3 grid(grid_n((size_t)2 * n * L * 64)), block(256);
+#define VLM_FILL(F) hipLaunchKernelGGL(vlm_kv_fill_kernel<F>, grid, block, 0, c.stream, ksrc, vsrc, kv.k, kv.v, kv.ks, kv.vs, n, L, kv.max_seq)
+  if (kv.format == FE_VLM_KV_E4M3) VLM_FILL(FE_VLM_KV_E4M3);
+  else if (kv.format == FE_VLM_KV_BF16_E4M3) VLM_FILL(FE_VLM_KV_BF16_E4M3);
+  else VLM_FILL(FE_VLM_KV_BF16);
+#undef VLM_FILL
+  FE_HIP(hipGetLastError());
+}
+
+void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh, int nkv, int Lk, const int* len_dev, const int* pad, float* po, float* pm,
+                          float* pl, int nsplit, bf16* out) {
+  const int G = nh / nkv;
+  const float scale = 1.0f / sqrtf(128.f);
+  FE_CHECK(nkv > 0 && nh % nkv == 0 && Lk > 0 && Lk <= kv.max_seq && nsplit == ((len_dev ? kv.max_seq : Lk) + VLM_DEC_CHUNK - 1) / VLM_DEC_CHUNK, "vlm decode attention: bad shape");
+  const bool f8 = kv.format == FE_VLM_KV_E4M3;
+  FE_CHECK(!f8 || (kv.ks && kv.vs), "vlm decode attention: an e4m3 cache without scales");
+#define VLM_DEC_LAUNCH(GG)                                                                                                                            \
+  if (f8)                                                                                                                                             \
+    hipLaunchKernelGGL(vlm_attn_decode_gqa_e4m3_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, q, (const uint8_t*)kv.k, (const uint8_t*)kv.v, \
+                       (const float*)kv.ks, (const float*)kv.vs, po, pm, pl, nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad);                   \
+  else                                                                                                                                                \
+    hipLaunchKernelGGL(vlm_attn_decode_gqa_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, q, (const bf16*)kv.k, (const bf16*)kv.v, po, pm, pl, \
+                       nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad)
+  switch (G) {
+    case 1: VLM_DEC_LAUNCH(1); break;
+    case 2: VLM_DEC_LAUNCH(2); break;
+    case 3: VLM_DEC_LAUNCH(3); break;
+    case 4: VLM_DEC_LAUNCH(4); break;
+    case 5: VLM_DEC_LAUNCH(5); break;
+    case 6: VLM_DEC_LAUNCH(6); break;
+    case 7: VLM_DEC_LAUNCH(7); break;
+    case 8: VLM_DEC_LAUNCH(8); break;
+    default: FE_CHECK(false, "vlm decode attention: %d query heads per KV head (1 .. 8 are built)", G);
+  }
+#undef VLM_DEC_LAUNCH
+  hipLaunchKernelGGL(vlm_attn_combine_kernel, dim3(B * nh), dim3(128), 0, c.stream, (const float*)po, (const float*)pm, (const float*)pl, out, nsplit);
+  FE_HIP(hipGetLastError());
 }
 
 
@@ -1177,6 +1429,12 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   bf16* gg = c.arena.array<bf16>((size_t)rows * m.inter);
   bf16* uu = c.arena.array<bf16>((size_t)rows * m.inter);
   const float scale = 1.0f / sqrtf(128.f);
+  FE_CHECK(m.kcache.size() == m.layers.size() && (m.kv_format != FE_VLM_KV_E4M3 || m.kscale.size() == m.layers.size()), "vlm: no KV cache");
+  const bool f8kv = m.kv_format == FE_VLM_KV_E4M3;
+  // (e4m3 formats: a prefill's own K / V, see the layer loop; every prefill entry point starts at position 0)
+  FE_CHECK(m.kv_format == FE_VLM_KV_BF16 || L == 1 || start == 0, "vlm: a prefill under an e4m3 KV format starts at position 0 (cache holds %d)", start);
+  bf16* const pk = m.kv_format != FE_VLM_KV_BF16 && L > 1 ? c.arena.array<bf16>((size_t)B * nkv * L * 128) : nullptr;
+  bf16* const pv = pk ? c.arena.array<bf16>((size_t)B * nkv * L * 128) : nullptr;
   // decode attention: keys split over workgroups, merged by a second launch (graph replay: the grid covers the whole cache)
   const int nsplit = L == 1 ? ((len_dev ? m.max_seq : Lk) + VLM_DEC_CHUNK - 1) / VLM_DEC_CHUNK : 0;
   float* po = nsplit ? c.arena.array<float>((size_t)B * nh * nsplit * 128) : nullptr;
@@ -1193,34 +1451,35 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   for (size_t li = 0; li < m.layers.size(); ++li) {
     const VlmLayerW& w = m.layers[li];
     vlm_linear(c, w.qkv, (const bf16*)n, d, rows, qkv, qkvd);
-    if (g.qwen3)
-      hipLaunchKernelGGL(vlm3_qk_rope_cache_kernel, dim3(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), dim3(256), 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq,
-                         (const bf16*)w.qn, (const bf16*)w.kn, qr, m.kcache[li], m.vcache[li], rows, L, nh, nkv, g.mrope[1], g.mrope[2], start, m.max_seq,
-                         L == 1 ? len_dev : (const int*)nullptr, g.rms_eps);
-    else
-    hipLaunchKernelGGL(vlm_rope_cache_kernel, dim3(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), dim3(256), 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, qr,
-                       m.kcache[li], m.vcache[li], rows, L, nh, nkv, g.mrope[0], g.mrope[1], start, m.max_seq, L == 1 ? len_dev : (const int*)nullptr);
+    // e4m3 formats, prefill: the rope kernel writes the prompt's K / V as bf16 rows into scratch ([B][nkv][L][128], the bf16 instantiation
+    // with max_seq = L), the prefill attention runs over that scratch unchanged, and vlm_kv_fill leaves the quantised rows in the cache.
+    // Decode steps (L == 1) quantise in the rope kernel itself: no launch is added to a step.
+    VlmKv kv{m.kv_format, m.kcache[li], m.vcache[li], f8kv ? m.kscale[li] : (float*)nullptr, f8kv ? m.vscale[li] : (float*)nullptr, m.max_seq};
+    const bool staged = pk != nullptr;
+    bf16* const rk = staged ? pk : kv.k;
+    bf16* const rv = staged ? pv : kv.v;
+    const int rseq = staged ? L : m.max_seq;
+    const dim3 rgrid(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), rblock(256);
+    const int* const rlen = L == 1 ? len_dev : (const int*)nullptr;
+#define VLM_ROPE(F)                                                                                                                                                \
+  do {                                                                                                                                                             \
+    if (g.qwen3)                                                                                                                                                   \
+      hipLaunchKernelGGL(vlm3_qk_rope_cache_kernel<F>, rgrid, rblock, 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, (const bf16*)w.qn,             \
+                         (const bf16*)w.kn, qr, rk, rv, rows, L, nh, nkv, g.mrope[1], g.mrope[2], start, rseq, rlen, g.rms_eps, kv.ks, kv.vs);                   \
+    else                                                                                                                                                           \
+      hipLaunchKernelGGL(vlm_rope_cache_kernel<F>, rgrid, rblock, 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, qr, rk, rv, rows, L, nh, nkv,      \
+                         g.mrope[0], g.mrope[1], start, rseq, rlen, kv.ks, kv.vs);                                                                                 \
+  } while (0)
+    if (staged || m.kv_format == FE_VLM_KV_BF16) VLM_ROPE(FE_VLM_KV_BF16);
+    else if (m.kv_format == FE_VLM_KV_E4M3) VLM_ROPE(FE_VLM_KV_E4M3);
+    else VLM_ROPE(FE_VLM_KV_BF16_E4M3);
+#undef VLM_ROPE
     if (L == 1) {
-      const int G = nh / nkv;
-#define VLM_DEC_LAUNCH(GG)                                                                                                                            \
-  hipLaunchKernelGGL(vlm_attn_decode_gqa_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, (const bf16*)qr, (const bf16*)m.kcache[li],       \
-                     (const bf16*)m.vcache[li], po, pm, pl, nh, nkv, Lk, m.max_seq, scale, len_dev, nsplit, (const int*)m.pad)
-      switch (G) {
-        case 1: VLM_DEC_LAUNCH(1); break;
-        case 2: VLM_DEC_LAUNCH(2); break;
-        case 3: VLM_DEC_LAUNCH(3); break;
-        case 4: VLM_DEC_LAUNCH(4); break;
-        case 5: VLM_DEC_LAUNCH(5); break;
-        case 6: VLM_DEC_LAUNCH(6); break;
-        case 7: VLM_DEC_LAUNCH(7); break;
-        case 8: VLM_DEC_LAUNCH(8); break;
-        default: FE_CHECK(false, "vlm decode attention: %d query heads per KV head (1 .. 8 are built)", G);
-      }
-#undef VLM_DEC_LAUNCH
-      hipLaunchKernelGGL(vlm_attn_combine_kernel, dim3(B * nh), dim3(128), 0, c.stream, (const float*)po, (const float*)pm, (const float*)pl, ao, nsplit);
+      vlm_decode_attention(c, kv, (const bf16*)qr, B, nh, nkv, Lk, len_dev, (const int*)m.pad, po, pm, pl, nsplit, ao);
     } else {
-      VlmAttnParams ap{qr, qd, m.kcache[li], m.vcache[li], ao, qd, B, nh, nkv, L, Lk, m.max_seq, start, scale, m.pad};
+      VlmAttnParams ap{qr, qd, rk, rv, ao, qd, B, nh, nkv, L, Lk, rseq, start, scale, m.pad};
       hipLaunchKernelGGL(vlm_attn_prefill_kernel, dim3((L + 127) / 128, B * nh), dim3(256), 0, c.stream, ap);
+      if (staged) vlm_kv_fill(c, kv, (const bf16*)pk, (const bf16*)pv, B * nkv, L);
     }
     FE_HIP(hipGetLastError());
     c.flops_accum += 4.0 * B * nh * (double)L * (start + (L + 1) * 0.5) * 128;

@@ -153,7 +153,7 @@ class ModelManager:
                 raise FileNotFoundError("no checkpoint: pass the model's state dict as qwen2_vl.state_dict (the reference downloads it with "
                                         "from_pretrained, models/model_manager.py:111-117; there is no network here)")
             proc = q.get('processor') or Qwen2VLProcessor(q.get('encode'), q.get('decode'), **{k: q[k] for k in ('min_pixels', 'max_pixels', 'special_tokens') if k in q})
-            return {'model': Qwen2VLModel(self.engine, q['state_dict'], q.get('geometry'), q.get('weight_format', 'bf16')).to(self.device), 'processor': proc}
+            return {'model': Qwen2VLModel(self.engine, q['state_dict'], q.get('geometry'), q.get('weight_format', 'bf16'), q.get('kv_format', 'bf16')).to(self.device), 'processor': proc}
         raise KeyError(f"model '{name}' is not served by the engine (hot-path models: {HOT_PATH_MODELS})")
 
     @staticmethod

@@ -42,17 +42,21 @@ class Qwen2VLModel:
     """The engine-backed stand-in for the loaded `Qwen2VLForConditionalGeneration`: holds the state dict on the host and commits it to
     the engine (`to`) or drops the device copy (`cpu`), the two moves ModelManager makes between passes."""
 
-    def __init__(self, engine, state_dict, geometry=None, weight_format="bf16"):
+    def __init__(self, engine, state_dict, geometry=None, weight_format="bf16", kv_format="bf16"):
         self.engine, self.state_dict, self.geometry = engine, state_dict, dict(geometry or QWEN2_VL_2B)
         if weight_format not in ("bf16", "fp8"):
             raise ValueError(f"weight_format {weight_format!r}: 'bf16' or 'fp8'")
         self.weight_format = weight_format      # "fp8": the decoder's Linear weights as e4m3 rows (Engine.vlm_weight_format)
+        if kv_format not in ("bf16", "fp8", "bf16_e4m3"):
+            raise ValueError(f"kv_format {kv_format!r}: 'bf16', 'fp8' or 'bf16_e4m3'")
+        self.kv_format = kv_format              # "fp8": the decoder's KV cache as e4m3 rows (Engine.vlm_kv_format)
         self.loaded = False
 
     def to(self, device=None):
         if not self.loaded:
             self.engine.vlm2_configure(**self.geometry)
             self.engine.vlm_weight_format(self.weight_format)
+            self.engine.vlm_kv_format(self.kv_format)
             self.engine.load_weights(FE_MODEL_VLM, self.state_dict)
             self.loaded = True
         return self

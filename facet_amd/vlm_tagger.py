@@ -316,6 +316,10 @@ class VLMTagger:
         self.weight_format = model_config.get("weight_format", "bf16")
         if self.weight_format not in ("bf16", "fp8"):
             raise ValueError(f"weight_format {self.weight_format!r}: 'bf16' or 'fp8'")
+        # "bf16", "fp8" (the decoder's KV cache as e4m3 rows read by the decode attention) or "bf16_e4m3" (Engine.vlm_kv_format)
+        self.kv_format = model_config.get("kv_format", "bf16")
+        if self.kv_format not in ("bf16", "fp8", "bf16_e4m3"):
+            raise ValueError(f"kv_format {self.kv_format!r}: 'bf16', 'fp8' or 'bf16_e4m3'")
         self._prompt = None
 
     # -- lifecycle (ModelManager calls load / unload around a pass) ------------------------------------------------------------------
@@ -328,6 +332,7 @@ class VLMTagger:
             raise FileNotFoundError("no checkpoint: pass the model's state dict (the reference downloads it with from_pretrained, "
                                     "models/vlm_tagger.py:170-176; there is no network here)")
         self.engine.vlm_weight_format(self.weight_format)      # read by the commit below
+        self.engine.vlm_kv_format(self.kv_format)              # read by every prefill
         if self.family == "qwen3":      # Qwen3VLForConditionalGeneration: geometry = Engine.vlm3_configure's arguments (default Qwen3-VL-2B)
             self.engine.vlm3_configure(**dict(geometry or QWEN3_VL_2B))
             self.engine.load_weights(FE_MODEL_VLM, state_dict)

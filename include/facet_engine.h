@@ -109,6 +109,26 @@ int fe_vlm_configure(fe_ctx* ctx, int n_heads, int n_kv_heads, int head_dim, flo
 enum fe_vlm_weights { FE_VLM_WEIGHTS_BF16 = 0, FE_VLM_WEIGHTS_E4M3 = 1 };
 int fe_vlm_set_weight_format(fe_ctx* ctx, int format);
 int fe_vlm_weight_info(fe_ctx* ctx, int64_t* info4);
+/* Storage of the decoders' KV cache (all three families), per context, read by the NEXT prefill; an unknown code is an error that leaves the
+ * state unchanged. A change of format releases the cache: a decode call before a new prefill then fails ("call fe_vlm_prefill first").
+ * One cache row is the 128 values of one (sequence, KV head, position), K and V separately.
+ *   FE_VLM_KV_BF16 (default): bf16 rows.
+ *   FE_VLM_KV_E4M3: 128 OCP e4m3 codes and one fp32 scale 2^e per row, by the row rule of the e4m3 weights above (the smallest e with
+ *     max|row| * 2^-e <= 448, e >= -117; codes rounded to nearest even; nothing saturates): 2 * (128 + 4) bytes per token, KV head and
+ *     layer instead of 512. The decode attention (fe_vlm_decode_step, fe_vlm_generate*) reads the codes directly, q and the probabilities
+ *     stay bf16 and the sums fp32; the scales multiply scores and probabilities exactly. A prefill attends to its own unquantised K / V
+ *     (its logits and first tokens are those of FE_VLM_KV_BF16, bit for bit) and leaves dequantize(quantize(row)) of every row in the
+ *     cache. Every dequantised value is exactly a bf16 value: the engine is the bf16 engine on those cache rows. A row holding a NaN or
+ *     Inf becomes NaN codes and propagates. Not built: fp8 matrix-core attention, a quantised q, a quantised prefill attention.
+ *   FE_VLM_KV_BF16_E4M3: a bf16 cache whose rows are replaced by dequantize(quantize(row)) - the arithmetic of FE_VLM_KV_E4M3 at the storage
+ *     of FE_VLM_KV_BF16, for tests and accuracy studies (what the format costs, apart from what the e4m3 kernels do).
+ * fe_vlm_kv_info: info4 = the format of the next prefill, the bytes one token of one sequence takes over all layers in that format, the
+ * bytes allocated for the live cache (0 before a prefill), its max_seq. Needs a loaded model.
+ * fe_vlm_kv_rows: positions pos0 .. pos0 + n - 1 of (layer, seq, kv_head) of the live cache, dequantised, as float k / v [n][128]. */
+enum fe_vlm_kv { FE_VLM_KV_BF16 = 0, FE_VLM_KV_E4M3 = 1, FE_VLM_KV_BF16_E4M3 = 2 };
+int fe_vlm_set_kv_format(fe_ctx* ctx, int format);
+int fe_vlm_kv_info(fe_ctx* ctx, int64_t* info4);
+int fe_vlm_kv_rows(fe_ctx* ctx, int layer, int seq, int kv_head, int pos0, int n, float* k, float* v);
 /* Vision tower (slice 2; built when the FE_MODEL_VLM checkpoint carries model.visual.*): geometry the tensor shapes do not determine
  * (defaults = Qwen2.5-VL-7B: 16 heads of 80, full attention in blocks 7 / 15 / 23 / 31, every other block inside 112-pixel windows), read
  * by the NEXT fe_weights_commit(FE_MODEL_VLM).
@@ -279,6 +299,13 @@ int fe_op_mha(fe_ctx* ctx, const float* x_q, const float* x_kv, int B, int Lq, i
 /* test hook of the VLM decoder's greedy selection: logits [rows][vocab] (rows <= 65535) are rounded to bf16 as in the decoder; ids [rows] =
    argmax (first index on ties), logprobs [rows] (NULL: not computed) = the log-probability of that id. */
 int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int32_t* ids, float* logprobs);
+/* Test hook of the VLM decode attention, launched alone (no model): q [B][nh][128], k / v [B][nkv][Lk][128] are rounded to bf16, a cache of
+ * Lk rows is built in kv_format (FE_VLM_KV_*) by the engine's own fill pass, and one decode-attention + merge launch pair runs over it with
+ * the left padding pad [B] (keys below pad[b] are masked; pad[b] < Lk). len_from_device: Lk reaches the kernel through a device word and
+ * the grid covers a larger max_seq, as a replayed decode graph has it. out [B][nh][128]; k_image / v_image [B][nkv][Lk][128] (nullable):
+ * the dequantised cache rows. nh / nkv in 1 .. 8. */
+int fe_op_vlm_decode_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int nkv, int Lk, const int32_t* pad, int kv_format,
+                               int len_from_device, float* out, float* k_image, float* v_image);
 
 /* developer hook: force a tile variant of the contraction kernel for every later launch (0 = automatic choice) */
 int fe_set_conv_variant(fe_ctx* ctx, int variant);

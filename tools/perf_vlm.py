@@ -3,13 +3,18 @@
   python tools/perf_vlm.py [--layers 28] [--prompt 512] [--new 32] [--batches 1,8,32] [--vision N] [--from-rgb N] [--pad P]
   python tools/perf_vlm.py --family qwen3 [--prompt 512] [--new 32] [--batches 1,4,32] [--vision N]
   python tools/perf_vlm.py --scores [--layers 4] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 7]
-  python tools/perf_vlm.py --weights bf16,fp8 [--family qwen2_5|qwen3|qwen2] [--layers 8] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 5]
+  python tools/perf_vlm.py --weights bf16,fp8 [--kv bf16,fp8] [--family qwen2_5|qwen3|qwen2] [--layers 8] [--prompt 512] [--new 32] [--batches 1,4,32] [--reps 5]
 
 --weights: one column per weight format (Engine.vlm_weight_format) of the chosen family's decoder - qwen3 / qwen2 at full depth, qwen2_5 at
 --layers layers of the 7B geometry. Every format's engine is loaded with the same seeded weights; the formats are timed alternately,
 --reps times each, per batch: prefill tokens/s (device timer) and the device-resident decode loop (fe_vlm_generate; host clock around the
 call, which ends in a synchronise) as median ms/step with the spread of the repetitions, tokens/s, and the fraction of the 8 TB/s HBM peak
 that the bytes of fe_vlm_weight_info (weights + row scales, streamed once per step) amount to at that time.
+
+--kv: crossed with --weights (bf16 alone when that is not given), one column per (weight format, KV-cache format) pair
+(Engine.vlm_kv_format: bf16, fp8, bf16_e4m3); the pairs are timed alternately like the weight formats. Each row also gives the K / V bytes
+a decode step reads at the middle of the call (fe_vlm_kv_info's bytes per token x sequences x cached tokens) beside the weight bytes; the
+HBM fraction is of their sum.
 
 --scores: the device-resident decode loop with the chosen tokens' log-probs (fe_vlm_generate_scored) against the plain loop
 (fe_vlm_generate) at the 7B geometry, same prefill, --reps alternating repetitions of each; prints the median ms/step of both and the
@@ -49,6 +54,7 @@ ap.add_argument("--qwen25-layers", type=int, default=4, help="--family qwen3: la
 ap.add_argument("--scores", action="store_true", help="time fe_vlm_generate_scored against fe_vlm_generate (ms/step) and stop")
 ap.add_argument("--reps", type=int, default=7, help="--scores / --weights: alternating repetitions of each loop")
 ap.add_argument("--weights", default=None, help="comma-separated weight formats (bf16, fp8): one column per format, then stop")
+ap.add_argument("--kv", default=None, help="comma-separated KV-cache formats (bf16, fp8, bf16_e4m3), crossed with --weights")
 a = ap.parse_args()
 
 
@@ -72,7 +78,10 @@ def weights_table():
     from facet_amd.weights import qwen2_vl_text_spec, qwen3_vl_text_spec
     from facet_amd.vlm_composition import QWEN2_VL_2B
     from facet_amd.vlm_tagger import QWEN3_VL_2B
-    fmts = a.weights.split(",")
+    fmts = (a.weights or "bf16").split(",")
+    kvs = a.kv.split(",") if a.kv else [None]
+    cols = [(f, kv) for f in fmts for kv in kvs]
+    name = lambda c: c[0] if c[1] is None else f"{c[0]}/kv-{c[1]}"
     if a.family == "qwen3":
         spec, V, what = qwen3_vl_text_spec(), 151936, "Qwen3-VL-2B decoder, 28 layers (full depth), tied head"
         conf = lambda e: e.vlm3_configure(**QWEN3_VL_2B)
@@ -85,40 +94,49 @@ def weights_table():
         conf = lambda e: e.vlm_configure(28, 4, 128, 1e6, 1e-6, (16, 24, 24))
     sd = synthetic_state_dict(None, 3, spec=spec)
     eng, info = {}, {}
-    for f in fmts:
+    for c in cols:                                       # one engine per column: no column pays for another's cache or scratch
         e = Engine(0, arena_bytes=24 << 30)
         conf(e)
-        e.vlm_weight_format(f)
+        e.vlm_weight_format(c[0])
+        if c[1] is not None:
+            e.vlm_kv_format(c[1])
         t0 = time.time(); e.load_weights(FE_MODEL_VLM, sd)
-        eng[f], info[f] = e, e.vlm_weight_info()
-        print(f"{f}: committed in {time.time() - t0:.0f} s: {info[f]}", flush=True)
+        eng[c], info[c] = e, e.vlm_weight_info()
+        print(f"{name(c)}: committed in {time.time() - t0:.0f} s: {info[c]}", flush=True)
     del sd
     L, new = a.prompt, a.new
     print(f"{what}; prompt {L}, {new} decode steps per call, median (min..max) of {a.reps} alternating calls per format", flush=True)
     for B in [int(b) for b in a.batches.split(",")]:
         p = np.random.default_rng(B).integers(0, V, (B, L)).astype(np.int32)
-        pre, dec = {f: [] for f in fmts}, {f: [] for f in fmts}
+        pre, dec, kvinfo = {c: [] for c in cols}, {c: [] for c in cols}, {}
         for r in range(a.reps + 1):                      # (the first round warms up: graph capture, first-use attributes)
-            for f in fmts:
-                e = eng[f]
+            for c in cols:
+                e = eng[c]
                 e.timer_start(); e.vlm_prefill(p, max_seq=L + new + 8); t_pre = e.timer_stop()
                 e.sync()
                 t0 = time.perf_counter(); e.vlm_generate(p, new + 1); t_all = (time.perf_counter() - t0) * 1e3
+                if c[1] is not None:
+                    kvinfo[c] = e.vlm_kv_info()
                 if r:
-                    pre[f].append(t_pre); dec[f].append((t_all - t_pre) / new)
-        for f in fmts:
-            t, tp = float(np.median(dec[f])), float(np.median(pre[f]))
-            by = info[f]["weight_bytes"] + info[f]["scale_bytes"]
-            print(f"{a.family} {f:4s} B={B:3d}: prefill {B * L / tp * 1e3:9.0f} tok/s ({tp:.2f} ms) | decode {t:7.4f} ms/step ({min(dec[f]):.4f}..{max(dec[f]):.4f}) = "
-                  f"{B / t * 1e3:8.0f} tok/s | {by / 1e9:.3f} GB per step = {by / t / 1e6:6.0f} GB/s = {by / t / 1e6 / 8000:.3f} of HBM peak", flush=True)
-        if len(fmts) > 1:
-            t0 = float(np.median(dec[fmts[0]]))
-            print("    decode ms/step " + ", ".join(f"{f} / {fmts[0]} = {float(np.median(dec[f])) / t0:.3f}" for f in fmts[1:]), flush=True)
+                    pre[c].append(t_pre); dec[c].append((t_all - t_pre) / new)
+        for c in cols:
+            t, tp = float(np.median(dec[c])), float(np.median(pre[c]))
+            by = info[c]["weight_bytes"] + info[c]["scale_bytes"]
+            kvtxt = ""
+            if c[1] is not None:
+                kvb = kvinfo[c]["bytes_per_token"] * B * (L + new // 2)
+                kvtxt = f"weights + {kvb / 1e9:.3f} GB of K/V ({kvinfo[c]['bytes_per_token']} B per token, {kvinfo[c]['allocated_bytes'] / 1e9:.3f} GB allocated) = "
+                by += kvb
+            print(f"{a.family} {name(c):4s} B={B:3d}: prefill {B * L / tp * 1e3:9.0f} tok/s ({tp:.2f} ms) | decode {t:7.4f} ms/step ({min(dec[c]):.4f}..{max(dec[c]):.4f}) = "
+                  f"{B / t * 1e3:8.0f} tok/s | {kvtxt}{by / 1e9:.3f} GB per step = {by / t / 1e6:6.0f} GB/s = {by / t / 1e6 / 8000:.3f} of HBM peak", flush=True)
+        if len(cols) > 1:
+            t0 = float(np.median(dec[cols[0]]))
+            print("    decode ms/step " + ", ".join(f"{name(c)} / {name(cols[0])} = {float(np.median(dec[c])) / t0:.3f}" for c in cols[1:]), flush=True)
     for e in eng.values():
         e.close()
 
 
-if a.weights:
+if a.weights or a.kv:
     weights_table()
     sys.exit(0)
 if a.family == "qwen2":
