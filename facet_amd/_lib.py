@@ -102,6 +102,8 @@ SIGNATURES = {
     "fe_op_vlm_select": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_op_vlm_decode_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                              _f32p, _f32p, _f32p]),
+    "fe_op_vlm_linear": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_float,
+                                   C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.POINTER(C.c_int32)]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
     "fe_topiq_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -806,6 +808,47 @@ class Engine:
         self._ck(self.lib.fe_op_vlm_decode_attention(self.h, qp, kp, vp, B, nh, nkv, Lk, pdp, VLM_KV_FORMATS[kv_format], int(bool(len_from_device)),
                                                      out.ctypes.data_as(_f32p), ki.ctypes.data_as(_f32p), vi.ctypes.data_as(_f32p)))
         return out, ki, vi
+
+    VLM_LINEAR_ROUTES = {"linear": 0, "logits": 1, "add_rmsnorm": 2, "silu_mul": 3}
+    VLM_LINEAR_KERNELS = {"auto": 0, "gemv": 1, "gemm32": 2}
+    VLM_LINEAR_FAMILIES = {1: "gemv", 2: "gemm32", 3: "wrapper"}
+
+    def vlm_linear(self, x, w, bias=None, weight_format="bf16", route="linear", kernel="auto", w2=None, xres=None, g=None, eps=1e-6,
+                   slot=None, ds=None):
+        """A decode projection of the VLM decoders launched alone (fe_op_vlm_linear), on weights packed as a model's are and freed on return.
+        x [M, ldx] (ldx >= K, ldx % 8 == 0), w [N, K], bias [N] or None; weight_format "bf16" / "fp8". route:
+          "linear"       y = bf16(x w^T + bias)                         -> (y, info)
+          "logits"       y = x w^T + bias in fp32 (the lm_head's form)  -> (y, info)
+          "add_rmsnorm"  r = bf16(xres + bf16(x w^T)) (+ ds[slot[m]] where slot[m] >= 0), n = RMSNorm(r, eps) * g  -> (r, n, info)
+          "silu_mul"     h = bf16(silu(bf16(x w^T))) * bf16(x w2^T), one launch for both products  -> (h, info)
+        kernel: "auto" (the decoder's choice), "gemv" or "gemm32" (forced; a shape it does not take raises EngineError). info: dict(family
+        "gemv" / "gemm32" / "wrapper", mr, splits, direct). All results float32 [M, N]."""
+        (x, xp), (w, wp) = _f32(x), _f32(w)
+        M, ldx = x.shape
+        N, Kw = w.shape
+        assert ldx >= Kw and ldx % 8 == 0, (ldx, Kw)
+        null, nulli = C.cast(None, _f32p), C.cast(None, C.POINTER(C.c_int32))
+
+        def opt(a, shape):
+            if a is None:
+                return None, null
+            a, p = _f32(a)
+            assert a.shape == shape, (a.shape, shape)
+            return a, p
+        b, bp = opt(bias, (N,))
+        w2a, w2p = opt(w2, (N, Kw))
+        xr, xrp = opt(xres, (M, N))
+        ga, gp = opt(g, (N,))
+        dsa, dsp = opt(ds, (0 if ds is None else len(ds), N))
+        sl, slp = (None, nulli) if slot is None else self._i32(slot)
+        assert sl is None or sl.shape == (M,), sl.shape
+        y, y2 = np.empty((M, N), np.float32), np.empty((M, N), np.float32)
+        info = (C.c_int32 * 4)()
+        self._ck(self.lib.fe_op_vlm_linear(self.h, xp, M, ldx, wp, bp, N, Kw, VLM_WEIGHT_FORMATS[weight_format], w2p, xrp, gp, float(eps), slp, dsp,
+                                           0 if dsa is None else dsa.shape[0], self.VLM_LINEAR_ROUTES[route], self.VLM_LINEAR_KERNELS[kernel],
+                                           y.ctypes.data_as(_f32p), y2.ctypes.data_as(_f32p), info))
+        d = dict(family=self.VLM_LINEAR_FAMILIES.get(int(info[0]), int(info[0])), mr=int(info[1]), splits=int(info[2]), direct=bool(info[3]))
+        return (y, y2, d) if route == "add_rmsnorm" else (y, d)
 
     def vlm_vision_configure(self, n_heads=16, fullatt_block_indexes=(7, 15, 23, 31)):
         """Vision-tower geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (Qwen2_5_VLVisionConfig; defaults = Qwen2.5-VL-7B)."""

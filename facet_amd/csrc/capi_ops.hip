@@ -344,4 +344,68 @@ int fe_op_vlm_decode_attention(fe_ctx* ctx, const float* q, const float* k, cons
   });
 }
 
+// Test hook of the VLM decode projections (vlm_linear, vlm_logits and the fused steps of vlm_forward in model_vlm.hip), launched alone on
+// weights packed as build_vlm packs them. The weights live in a DeviceWeights of the call: freed when it returns, on every path.
+int fe_op_vlm_linear(fe_ctx* ctx, const float* x, int M, int ldx, const float* w, const float* bias, int N, int K, int weight_format, const float* w2,
+                     const float* xres, const float* g, float eps, const int32_t* slot, const float* ds, int n_ds, int route, int kernel, float* y,
+                     float* y2, int32_t* info) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && w && y && info && M > 0 && M <= 4096 && N > 0 && K > 0 && ldx >= K && ldx % 8 == 0, "bad vlm linear arguments");
+    FE_CHECK(weight_format == FE_VLM_WEIGHTS_BF16 || weight_format == FE_VLM_WEIGHTS_E4M3, "fe_op_vlm_linear: weight format %d", weight_format);
+    FE_CHECK(route >= 0 && route <= 3 && kernel >= VLM_LIN_AUTO && kernel <= VLM_LIN_FORCE_GEMM32, "fe_op_vlm_linear: route %d, kernel %d", route, kernel);
+    FE_CHECK(route < 2 || (!bias && N % 4 == 0 && kernel != VLM_LIN_FORCE_GEMV), "fe_op_vlm_linear: the fused routes take the GEMM, no bias and N %% 4 == 0");
+    FE_CHECK(route != 2 || (xres && g && y2 && !slot == !ds && (!ds || n_ds > 0)), "fe_op_vlm_linear: route 2 takes xres, g, y2 and slot with ds");
+    FE_CHECK(route != 3 || w2, "fe_op_vlm_linear: route 3 takes w2");
+    if (route == 2 && slot)
+      for (int m = 0; m < M; ++m) FE_CHECK(slot[m] >= -1 && slot[m] < n_ds, "fe_op_vlm_linear: slot %d of %d rows", slot[m], n_ds);
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = PREC_BF16; dw.half_only = true;      // as build_vlm
+    const size_t mn = (size_t)M * N;
+    auto pack = [&](const float* src, const HostTensor* b) {
+      HostTensor W;
+      W.shape = {N, K};
+      W.data.assign(src, src + (size_t)N * K);
+      return vlm_pack_linear(dw, weight_format, W, b, "w");
+    };
+    HostTensor Bv;
+    if (bias) { Bv.shape = {N}; Bv.data.assign(bias, bias + N); }
+    const ConvW cw = pack(w, bias ? &Bv : nullptr);
+    auto to_bf16 = [&](const float* src, size_t n) {
+      float* d32 = upload(C, src, n);
+      bf16* d16 = C.arena.array<bf16>(n);
+      launch_convert(d32, d16, n, C.stream);
+      return d16;
+    };
+    const bf16* hx = to_bf16(x, (size_t)M * ldx);
+    float* out32 = C.arena.array<float>(mn);
+    bf16* out16 = C.arena.array<bf16>(mn);
+    VlmLinearInfo li;
+    if (route == 0) {
+      vlm_linear(C, cw, hx, ldx, M, out16, N, kernel, &li);
+      launch_convert(out16, out32, mn, C.stream);
+    } else if (route == 1) {
+      vlm_logits(C, cw, hx, ldx, M, out32, N, kernel, &li);
+    } else if (route == 2) {
+      bf16* hres = to_bf16(xres, mn);
+      const bf16* hg = to_bf16(g, (size_t)N);
+      const bf16* hds = ds ? to_bf16(ds, (size_t)n_ds * N) : nullptr;
+      const int* dslot = ds ? upload(C, slot, (size_t)M) : nullptr;
+      li = VlmLinearInfo{VLM_LIN_GEMM32, 0, vlm_proj_add_rmsnorm(C, cw, hx, ldx, M, hres, hg, out16, eps, dslot, hds), 0};
+      float* n32 = C.arena.array<float>(mn);
+      launch_convert(out16, n32, mn, C.stream);
+      launch_convert(hres, out32, mn, C.stream);
+      FE_HIP(hipMemcpyAsync(y2, n32, mn * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    } else {
+      const ConvW cw2 = pack(w2, nullptr);
+      li = VlmLinearInfo{VLM_LIN_GEMM32, 0, vlm_gate_up_silu_mul(C, cw, cw2, hx, ldx, M, out16), 0};
+      launch_convert(out16, out32, mn, C.stream);
+    }
+    FE_HIP(hipMemcpyAsync(y, out32, mn * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    info[0] = li.family; info[1] = li.mr; info[2] = li.splits; info[3] = li.direct;
+  });
+}
+
 }  // extern "C"

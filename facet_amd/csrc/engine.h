@@ -519,6 +519,23 @@ void vlm_kv_fill(Ctx& c, const VlmKv& kv, const bf16* ksrc, const bf16* vsrc, in
 // ([B * nh * nsplit * 128], [B * nh * nsplit] twice), nsplit = ceil((len_dev ? max_seq : Lk) / 128).
 void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh, int nkv, int Lk, const int* len_dev, const int* pad, float* po, float* pm,
                           float* pl, int nsplit, bf16* out);
+// ---- the decode projections launched alone (fe_op_vlm_linear): the decoder's own choice among its kernels, or a forced one
+enum VlmLinearForce : int { VLM_LIN_AUTO = 0, VLM_LIN_FORCE_GEMV = 1, VLM_LIN_FORCE_GEMM32 = 2 };
+enum VlmLinearFamily : int { VLM_LIN_GEMV = 1, VLM_LIN_GEMM32 = 2, VLM_LIN_WRAPPER = 3 };
+// what ran: the family, the GEMV's row template MR, the GEMM's K splits, and whether its single split was written straight to the output
+struct VlmLinearInfo { int family = 0, mr = 0, splits = 0, direct = 0; };
+// a decoder Linear [N][K] (+ bias) in a weight format (FE_VLM_WEIGHTS_*), as build_vlm packs it; `name`: the tensor in an error message
+ConvW vlm_pack_linear(DeviceWeights& dw, int weight_format, const HostTensor& W, const HostTensor* bias, const std::string& name);
+// y = x W^T (+ b) in bf16 for any row count (a forced kernel runs under its own checks, whatever the row count)
+void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy, int force = VLM_LIN_AUTO, VlmLinearInfo* info = nullptr);
+// the fp32 logits of the lm_head: lg [M][ldy]
+void vlm_logits(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float* lg, int ldy, int force = VLM_LIN_AUTO, VlmLinearInfo* info = nullptr);
+// the fused steps of a 4 .. 32-row layer; each leaves its split sums in arena scratch (the CALLER rewinds) and returns the split count
+//   x = bf16(x + bf16(a W^T)) (+ the DeepStack rows ds[slot[row]] where slot is given), n = RMSNorm(x) ln   (ln == nullptr: the sum only)
+int vlm_proj_add_rmsnorm(Ctx& c, const ConvW& w, const bf16* a, int lda, int rows, bf16* x, const bf16* ln, bf16* n, float eps, const int* slot,
+                         const bf16* ds);
+//   h = bf16(silu(bf16(n Wg^T))) * bf16(n Wu^T), both products from one launch
+int vlm_gate_up_silu_mul(Ctx& c, const ConvW& gate, const ConvW& up, const bf16* n, int ldn, int rows, bf16* h);
 // fe_vlm_generate_until: the stop rule of a decode loop. fin_dev [B]: -1 while a sequence runs, else the EOS id it emitted (set by the
 // caller for sequences whose first token already is one); live_dev [1]: the count of running sequences after the last step, read by the
 // host after every `poll` steps. steps_run: out, the steps executed.

@@ -459,7 +459,8 @@ __global__ __launch_bounds__(256) void vlm_gemv_e4m3_kernel(const bf16* __restri
 // the e4m3 GEMV takes a layer whose K is a multiple of 16 (a lane's 16-byte load); vlm_linear sends other shapes through the bf16 scratch
 static bool vlm_e4m3_gemv_ok(const ConvW& w) { return w.CinPadH % 16 == 0; }
 template <class TO>
-static void vlm_gemv(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy) {
+static void vlm_gemv(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy, VlmLinearInfo* info = nullptr) {
+  if (info) *info = VlmLinearInfo{VLM_LIN_GEMV, M == 1 ? 1 : M == 2 ? 2 : 4, 0, 0};
   if (w.w8) {
     FE_CHECK(w.w8_scale && vlm_e4m3_gemv_ok(w) && w.KpH % 16 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv(e4m3): unsupported layer");
     const int K = w.CinPadH, blocks = (w.Cout + 1) / 2;
@@ -635,12 +636,13 @@ static int vlm_gemm32_partials(Ctx& c, const ConvW& w, const bf16* x, int ldx, i
   return splits;
 }
 template <class TO>
-static void vlm_gemm32(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy) {
+static void vlm_gemm32(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy, VlmLinearInfo* info = nullptr) {
   const size_t mark = c.arena.mark();
   float* part = nullptr;
   float* direct = nullptr;
   if constexpr (std::is_same<TO, float>::value) { if (!w.shift && ldy == w.Cout) direct = y; }
   const int splits = vlm_gemm32_partials(c, w, x, ldx, M, &part, nullptr, nullptr, direct), N = w.Cout;
+  if (info) *info = VlmLinearInfo{VLM_LIN_GEMM32, 0, splits, direct && part == direct};
   if (!(direct && part == direct)) {
     hipLaunchKernelGGL((vlm_gemm32_finish_kernel<TO>), dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, c.stream, (const float*)part, splits, M, N,
                        (const float*)w.shift, y, ldy);
@@ -747,20 +749,60 @@ static ConvW vlm_e4m3_widen(Ctx& c, const ConvW& w) {
 }
 // y = x W^T (+ b) in bf16 for any row count: the streaming GEMV for up to 4 rows, the weight-streaming matrix-core GEMM up to 32, the
 // shared layer wrapper above that (an e4m3 layer: the same choice among its own kernels, the wrapper on its bf16 scratch)
-static void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy) {
+// (force, the test hook's: that kernel under its own checks; info: what ran)
+void vlm_linear(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy, int force, VlmLinearInfo* info) {
+  if (force == VLM_LIN_FORCE_GEMV) { vlm_gemv(c, w, x, ldx, M, y, ldy, info); return; }
+  if (force == VLM_LIN_FORCE_GEMM32) { vlm_gemm32(c, w, x, ldx, M, y, ldy, info); return; }
   if (w.w8) {
-    if (M <= 4 && !vlm_uses_gemm32(w, M) && vlm_e4m3_gemv_ok(w)) vlm_gemv(c, w, x, ldx, M, y, ldy);
-    else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy);
+    if (M <= 4 && !vlm_uses_gemm32(w, M) && vlm_e4m3_gemv_ok(w)) vlm_gemv(c, w, x, ldx, M, y, ldy, info);
+    else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy, info);
     else {
       const size_t mark = c.arena.mark();
       linear_forward(c, vlm_e4m3_widen(c, w), x, ldx, M, y, ldy, ACT_NONE);
       c.arena.rewind(mark);
+      if (info) *info = VlmLinearInfo{VLM_LIN_WRAPPER, 0, 0, 0};
     }
     return;
   }
-  if (M <= 4 && !vlm_uses_gemm32(w, M)) vlm_gemv(c, w, x, ldx, M, y, ldy);
-  else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy);
-  else linear_forward(c, w, x, ldx, M, y, ldy, ACT_NONE);
+  if (M <= 4 && !vlm_uses_gemm32(w, M)) vlm_gemv(c, w, x, ldx, M, y, ldy, info);
+  else if (vlm_uses_gemm32(w, M)) vlm_gemm32(c, w, x, ldx, M, y, ldy, info);
+  else {
+    linear_forward(c, w, x, ldx, M, y, ldy, ACT_NONE);
+    if (info) *info = VlmLinearInfo{VLM_LIN_WRAPPER, 0, 0, 0};
+  }
+}
+// the fp32 logits of the lm_head (hidden = w.Cin): the same three families, the wrapper's e4m3 scratch left in the arena (the CALLER rewinds)
+void vlm_logits(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float* lg, int ldy, int force, VlmLinearInfo* info) {
+  if (force == VLM_LIN_FORCE_GEMV) { vlm_gemv(c, w, x, ldx, M, lg, ldy, info); return; }
+  if (force == VLM_LIN_FORCE_GEMM32) { vlm_gemm32(c, w, x, ldx, M, lg, ldy, info); return; }
+  if (M <= 4 && !vlm_uses_gemm32(w, M) && (!w.w8 || vlm_e4m3_gemv_ok(w))) { vlm_gemv(c, w, x, ldx, M, lg, ldy, info); return; }
+  if (M <= 32 && w.Cin % 128 == 0) { vlm_gemm32(c, w, x, ldx, M, lg, ldy, info); return; }
+  if (w.w8) linear_forward_f32(c, vlm_e4m3_widen(c, w), x, ldx, M, lg, ldy, ACT_NONE);
+  else linear_forward_f32(c, w, x, ldx, M, lg, ldy, ACT_NONE);
+  if (info) *info = VlmLinearInfo{VLM_LIN_WRAPPER, 0, 0, 0};
+}
+// The fused steps of a 4 .. 32-row layer (engine.h): the split sums of the weight-streaming GEMM are taken by the pass that follows the
+// projection instead of a finishing launch of their own.
+int vlm_proj_add_rmsnorm(Ctx& c, const ConvW& w, const bf16* a, int lda, int rows, bf16* x, const bf16* ln, bf16* n, float eps, const int* slot,
+                         const bf16* ds) {
+  FE_CHECK(w.Cout % 4 == 0 && !w.shift && (!ds || slot), "vlm_proj_add_rmsnorm: unsupported layer");
+  float* part = nullptr;
+  const int sp = vlm_gemm32_partials(c, w, a, lda, rows, &part);
+  const int d = w.Cout;
+  if (ds) hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<true>, dim3(rows), dim3(1024), 0, c.stream, (const float*)part, sp, rows, d, (const float*)nullptr, x, ln, n, eps, slot, ds);
+  else hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)part, sp, rows, d, (const float*)nullptr, x, ln, n, eps,
+                          (const int*)nullptr, (const bf16*)nullptr);
+  FE_HIP(hipGetLastError());
+  return sp;
+}
+int vlm_gate_up_silu_mul(Ctx& c, const ConvW& gate, const ConvW& up, const bf16* n, int ldn, int rows, bf16* h) {
+  FE_CHECK(gate.Cout % 4 == 0 && !gate.shift && !up.shift, "vlm_gate_up_silu_mul: unsupported layer");
+  float *pg = nullptr, *pu = nullptr;
+  const int sg = vlm_gemm32_partials(c, gate, n, ldn, rows, &pg, &up, &pu);      // gate and up: one launch
+  const size_t mn4 = (size_t)rows * gate.Cout / 4;
+  hipLaunchKernelGGL(vlm_finish_silu_mul_kernel, dim3(grid_n(mn4)), dim3(256), 0, c.stream, (const float*)pg, (const float*)pu, sg, mn4, h);
+  FE_HIP(hipGetLastError());
+  return sg;
 }
 
 // device-resident decode state (graph replay): after a step, the chosen tokens become the next step's input, every position and the
@@ -1193,9 +1235,9 @@ static ConvW pack_linear_e4m3(DeviceWeights& dw, const HostTensor& W, const std:
   return c;
 }
 // a Linear of the decoder in the model's weight format (e4m3: `name` for the error message; bf16: build_linear_rows on all rows)
-static ConvW vlm_pack_linear(VlmModel& m, const HostTensor& W, const HostTensor* bias, const std::string& name) {
-  if (m.weight_format == FE_VLM_WEIGHTS_E4M3) return pack_linear_e4m3(m.dw, W, bias ? &bias->data : nullptr, name);
-  return build_linear_rows(m.dw, W, bias, 0, (int)W.shape[0]);
+ConvW vlm_pack_linear(DeviceWeights& dw, int weight_format, const HostTensor& W, const HostTensor* bias, const std::string& name) {
+  if (weight_format == FE_VLM_WEIGHTS_E4M3) return pack_linear_e4m3(dw, W, bias ? &bias->data : nullptr, name);
+  return build_linear_rows(dw, W, bias, 0, (int)W.shape[0]);
 }
 
 void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int weight_format) {
@@ -1207,7 +1249,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int wei
     if (!f8) return;
     for (const float v : t.data) FE_CHECK(std::isfinite(v), "vlm: %s.weight holds a NaN or Inf: not quantised to e4m3", name.c_str());
   };
-  auto linear = [&](const std::string& prefix) { return f8 ? vlm_pack_linear(m, ws.get(prefix + ".weight"), nullptr, prefix + ".weight") : build_linear(m.dw, ws, prefix, false); };
+  auto linear = [&](const std::string& prefix) { return f8 ? vlm_pack_linear(m.dw, m.weight_format, ws.get(prefix + ".weight"), nullptr, prefix + ".weight") : build_linear(m.dw, ws, prefix, false); };
   m.cfg = cfg;
   m.dw.prec = PREC_BF16;
   m.dw.half_only = true;      // 7.6 G parameters: no fp32 / Winograd copies beside the bf16 ones
@@ -1243,7 +1285,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int wei
         W.data.insert(W.data.end(), a.data.begin(), a.data.end());
       }
       FE_CHECK((int64_t)W.data.size() == W.shape[0] * W.shape[1], "vlm: layer %d q/k/v shapes do not match %d heads / %d kv heads of 128", i, cfg.n_heads, cfg.n_kv_heads);
-      w.qkv = vlm_pack_linear(m, W, nullptr, L + ".self_attn.q|k|v_proj.weight");
+      w.qkv = vlm_pack_linear(m.dw, m.weight_format, W, nullptr, L + ".self_attn.q|k|v_proj.weight");
       const HostTensor& qn = ws.get(L + ".self_attn.q_norm.weight");
       const HostTensor& kn = ws.get(L + ".self_attn.k_norm.weight");
       FE_CHECK(qn.numel() == 128 && kn.numel() == 128, "vlm (qwen3): layer %d q_norm / k_norm must have 128 weights", i);
@@ -1270,7 +1312,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int wei
       Bv.data.insert(Bv.data.end(), bb.data.begin(), bb.data.end());
     }
     FE_CHECK((int64_t)W.data.size() == W.shape[0] * W.shape[1], "vlm: layer %d q/k/v shapes do not match %d heads / %d kv heads of 128", i, cfg.n_heads, cfg.n_kv_heads);
-    w.qkv = vlm_pack_linear(m, W, &Bv, L + ".self_attn.q|k|v_proj.weight");
+    w.qkv = vlm_pack_linear(m.dw, m.weight_format, W, &Bv, L + ".self_attn.q|k|v_proj.weight");
     w.o = linear(L + ".self_attn.o_proj");
     w.gate = linear(L + ".mlp.gate_proj");
     w.up = linear(L + ".mlp.up_proj");
@@ -1283,7 +1325,7 @@ void build_vlm(VlmModel& m, const WeightStore& ws, const VlmConfig& cfg, int wei
   m.norm = upload_bf16(m.dw, ws.get(P + "norm.weight").data);
   if (tied && f8) {      // the lookup keeps the bf16 table (looked-up rows are the original ones); the head is an e4m3 copy of it
     m.embed = upload_bf16(m.dw, E.data);
-    m.lm_head = vlm_pack_linear(m, E, nullptr, P + "embed_tokens.weight");
+    m.lm_head = vlm_pack_linear(m.dw, m.weight_format, E, nullptr, P + "embed_tokens.weight");
   } else if (tied) {
     m.lm_head = build_linear_rows(m.dw, E, nullptr, 0, m.vocab);
     FE_CHECK(m.lm_head.wh && m.lm_head.hprec == PREC_BF16, "vlm: tied lm_head needs the bf16 form");
@@ -1493,18 +1535,9 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
                        vlm_uses_gemm32(w.down, rows) && !w.o.shift && !w.gate.shift && !w.up.shift && !w.down.shift && w.gate.KpH == w.up.KpH;
     if (fused) {
       const size_t pm = c.arena.mark();
-      float *po_ = nullptr, *pg = nullptr, *pu = nullptr, *pd = nullptr;
-      int sp = vlm_gemm32_partials(c, w.o, (const bf16*)ao, qd, rows, &po_);
-      hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)po_, sp, rows, d, (const float*)nullptr, x, (const bf16*)w.ln2, n, g.rms_eps,
-                         (const int*)nullptr, (const bf16*)nullptr);
-      const int sg = vlm_gemm32_partials(c, w.gate, (const bf16*)n, d, rows, &pg, &w.up, &pu);      // gate and up: one launch
-      const size_t mn4 = (size_t)rows * m.inter / 4;
-      hipLaunchKernelGGL(vlm_finish_silu_mul_kernel, dim3(grid_n(mn4)), dim3(256), 0, c.stream, (const float*)pg, (const float*)pu, sg, mn4, gg);
-      sp = vlm_gemm32_partials(c, w.down, (const bf16*)gg, m.inter, rows, &pd);
-      if (ds) hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<true>, dim3(rows), dim3(1024), 0, c.stream, (const float*)pd, sp, rows, d, (const float*)nullptr, x, next_ln, n, g.rms_eps, m.ds_slot, ds);
-      else hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)pd, sp, rows, d, (const float*)nullptr, x, next_ln, n, g.rms_eps,
-                              (const int*)nullptr, (const bf16*)nullptr);
-      FE_HIP(hipGetLastError());
+      vlm_proj_add_rmsnorm(c, w.o, (const bf16*)ao, qd, rows, x, (const bf16*)w.ln2, n, g.rms_eps, nullptr, nullptr);
+      vlm_gate_up_silu_mul(c, w.gate, w.up, (const bf16*)n, d, rows, gg);
+      vlm_proj_add_rmsnorm(c, w.down, (const bf16*)gg, m.inter, rows, x, next_ln, n, g.rms_eps, ds ? m.ds_slot : (const int*)nullptr, ds);
       c.arena.rewind(pm);
       continue;
     }
@@ -1531,10 +1564,7 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   else
     hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)B * 64)), dim3(256), 0, c.stream, (const bf16*)last, d, (const bf16*)m.norm, lastn, d, B, d, g.rms_eps);
   float* lg = logits_dev ? logits_dev : c.arena.array<float>((size_t)B * m.vocab);
-  if (B <= 4 && !vlm_uses_gemm32(m.lm_head, B) && (!m.lm_head.w8 || vlm_e4m3_gemv_ok(m.lm_head))) vlm_gemv(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
-  else if (B <= 32 && d % 128 == 0) vlm_gemm32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);
-  else if (m.lm_head.w8) linear_forward_f32(c, vlm_e4m3_widen(c, m.lm_head), (const bf16*)lastn, d, B, lg, m.vocab, ACT_NONE);      // (scratch: rewound below)
-  else linear_forward_f32(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab, ACT_NONE);
+  vlm_logits(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);      // (scratch: rewound below)
   vlm_select(c, lg, B, m.vocab, next_dev, lp_dev);
   m.cur_len = Lk;
   c.arena.rewind(mark);

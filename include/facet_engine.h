@@ -306,6 +306,21 @@ int fe_op_vlm_select(fe_ctx* ctx, const float* logits, int rows, int vocab, int3
  * the dequantised cache rows. nh / nkv in 1 .. 8. */
 int fe_op_vlm_decode_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int nkv, int Lk, const int32_t* pad, int kv_format,
                                int len_from_device, float* out, float* k_image, float* v_image);
+/* Test hook of the VLM decode projections, launched alone (no model): x [M][ldx] (ldx >= K, a multiple of 8), w [N][K] and w2 (nullable,
+ * route 3) are rounded to bf16; the weights are packed in weight_format (FE_VLM_WEIGHTS_*) by the functions that build a model and freed
+ * before the call returns. bias [N] is nullable. route:
+ *   0  the decoder's Linear: y [M][N] = bf16(x W^T + bias)
+ *   1  the logits form of the lm_head: y [M][N] = x W^T + bias in fp32 (a single K split without bias is written straight to y)
+ *   2  o / down projection fused with what follows it: y [M][N] = bf16(xres + bf16(x W^T)) (+ ds [n_ds][N] rows where slot [M] >= 0, both
+ *      nullable), y2 [M][N] = RMSNorm(y, eps) * g (g [N]); N % 4 == 0, no bias
+ *   3  gate | up in one launch fused with the SwiGLU product: y [M][N] = bf16(silu(bf16(x W^T))) * bf16(x W2^T); N % 4 == 0, no bias
+ * kernel: 0 what the decoder picks for this shape, 1 the streaming GEMV (M <= 4), 2 the weight-streaming GEMM (M <= 32, K % 128 == 0);
+ * routes 2 and 3 are the GEMM's. A forced kernel runs under its own checks: a shape it does not take is FE_ERR_RUNTIME.
+ * info [4] (out): the family that ran (1 GEMV, 2 GEMM, 3 the shared layer wrapper, for e4m3 on its bf16 scratch), the GEMV's row
+ * template (1, 2 or 4), the GEMM's K splits, 1 if the single split was written straight to y. */
+int fe_op_vlm_linear(fe_ctx* ctx, const float* x, int M, int ldx, const float* w, const float* bias, int N, int K, int weight_format, const float* w2,
+                     const float* xres, const float* g, float eps, const int32_t* slot, const float* ds, int n_ds, int route, int kernel, float* y,
+                     float* y2, int32_t* info);
 
 /* developer hook: force a tile variant of the contraction kernel for every later launch (0 = automatic choice) */
 int fe_set_conv_variant(fe_ctx* ctx, int variant);
