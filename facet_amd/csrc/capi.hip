@@ -56,6 +56,13 @@ void fe_destroy(fe_ctx* ctx) {
     if (ctx->ev_consumed[i]) (void)hipEventDestroy(ctx->ev_consumed[i]);
   }
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
+  if (ctx->side.stream) {
+    (void)hipStreamSynchronize(ctx->side.stream);
+    (void)hipStreamDestroy(ctx->side.stream);
+  }
+  for (hipEvent_t e : {ctx->side.ev_start, ctx->side.ev_join, ctx->side.ev_read[0], ctx->side.ev_read[1]})
+    if (e) (void)hipEventDestroy(e);
+  ctx->side.arena.release();
   for (void* q : ctx->misc_allocs) (void)hipFree(q);
   if (ctx->clip_in) (void)hipFree(ctx->clip_in);
   if (ctx->samp_in) (void)hipFree(ctx->samp_in);

@@ -39,6 +39,13 @@ struct fe_ctx {
   float* d_rec = nullptr;   // interleaved ensemble records of the host-output entry point
   size_t d_rec_cap = 0;
   int ensemble_mask = 7;    // models fe_ensemble_score runs when loaded: 1 topiq | 2 clip | 4 samp (fe_ensemble_select)
+  // the side lane of ensemble_run: a second stream with an arena of its own, on which the 224^2 models run beside TOPIQ. Created on
+  // first use; idle whenever ensemble_run is not on the stack (it joins before it returns)
+  struct SideLane {
+    hipStream_t stream = nullptr;
+    Arena arena;
+    hipEvent_t ev_start = nullptr, ev_join = nullptr, ev_read[2] = {nullptr, nullptr};   // ev_read: its last read of a ping-pong buffer
+  } side;
   // capi_models.hip and capi_face.hip, through out_buf()
   float* d_out = nullptr;   // persistent device staging for per-image results
   size_t d_out_cap = 0;
@@ -61,24 +68,27 @@ class ImageStager {
   ImageStager(fe_ctx* ctx, const uint8_t* imgs, int n, size_t per_image, int mb, int on_device)
       : x_(ctx), imgs_(imgs), n_(n), per_(per_image), mb_(mb), dev_(on_device) {
     if (!dev_) {
-      if (!x_->copy_stream) {
-        FE_HIP(hipStreamCreateWithFlags(&x_->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-          FE_HIP(hipEventCreateWithFlags(&x_->ev_copied[i], hipEventDisableTiming));
-          FE_HIP(hipEventCreateWithFlags(&x_->ev_consumed[i], hipEventDisableTiming));
-        }
-      }
-      const size_t need = (size_t)std::min(mb_, n_) * per_;
-      for (int i = 0; i < 2; ++i)
-        if (x_->stage_cap[i] < need) {
-          FE_HIP(hipStreamSynchronize(x_->c.stream));
-          if (x_->stage_buf[i]) FE_HIP(hipFree(x_->stage_buf[i]));
-          x_->stage_buf[i] = nullptr; x_->stage_cap[i] = 0;
-          FE_HIP(hipMalloc((void**)&x_->stage_buf[i], need));
-          x_->stage_cap[i] = need;
-        }
+      prepare(x_, (size_t)std::min(mb_, n_) * per_);
       issue(0);
     }
+  }
+  // the copy stream, its events and two staging buffers of at least `need` bytes (ensemble_run issues its copies itself)
+  static void prepare(fe_ctx* x, size_t need) {
+    if (!x->copy_stream) {
+      FE_HIP(hipStreamCreateWithFlags(&x->copy_stream, hipStreamNonBlocking));
+      for (int i = 0; i < 2; ++i) {
+        FE_HIP(hipEventCreateWithFlags(&x->ev_copied[i], hipEventDisableTiming));
+        FE_HIP(hipEventCreateWithFlags(&x->ev_consumed[i], hipEventDisableTiming));
+      }
+    }
+    for (int i = 0; i < 2; ++i)
+      if (x->stage_cap[i] < need) {
+        FE_HIP(hipStreamSynchronize(x->c.stream));
+        if (x->stage_buf[i]) FE_HIP(hipFree(x->stage_buf[i]));
+        x->stage_buf[i] = nullptr; x->stage_cap[i] = 0;
+        FE_HIP(hipMalloc((void**)&x->stage_buf[i], need));
+        x->stage_cap[i] = need;
+      }
   }
   int chunks() const { return (n_ + mb_ - 1) / mb_; }
   int count(int k) const { return std::min(mb_, n_ - k * mb_); }
@@ -108,10 +118,30 @@ class ImageStager {
 // ---- the guard of every entry point that takes a context -------------------------------------------------------------------------
 // On the error path nothing may stay in flight: queued async copies read the caller's host buffers and write into host
 // vectors local to the entry point, both of which die when it returns.
+// The side lane's kernels also run in an arena that the next call recycles. (By the time an exception reaches the guard, LaneScope has
+// put the main stream and arena back into the Ctx.)
 inline void fe_drain(fe_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+  if (ctx->side.stream) (void)hipStreamSynchronize(ctx->side.stream);
   if (ctx->c.stream) (void)hipStreamSynchronize(ctx->c.stream);
 }
+
+// While it lives, the Ctx enqueues on the side lane: c.stream and c.arena are the side lane's, and the main pair waits in ctx->side.
+// The model code reads both members of the Ctx it is handed; all enqueueing happens on one host thread in program order.
+class LaneScope {
+ public:
+  explicit LaneScope(fe_ctx* ctx, bool on_side) : x_(on_side ? ctx : nullptr) { flip(); }
+  ~LaneScope() { flip(); }
+  LaneScope(const LaneScope&) = delete;
+  LaneScope& operator=(const LaneScope&) = delete;
+ private:
+  void flip() {
+    if (!x_) return;
+    std::swap(x_->c.stream, x_->side.stream);
+    x_->c.arena.swap(x_->side.arena);
+  }
+  fe_ctx* x_;
+};
 
 // thrown by the JPEG writers when an output row is too small for its image
 struct CapacityError : std::runtime_error { using std::runtime_error::runtime_error; };

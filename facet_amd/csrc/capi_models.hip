@@ -1,5 +1,6 @@
 // C ABI: the scoring models - TOPIQ, U2-Net-P + SAMP-Net, CLIP image and text, the aesthetic head, tag similarities, the ensemble.
 #include "capi_internal.h"
+#include "ensemble_plan.h"
 
 namespace {
 const float kImagenetMean[3] = {0.485f, 0.456f, 0.406f};
@@ -125,18 +126,6 @@ void compact_crops(float* buf, size_t per, int c, int left, hipStream_t s) {
     FE_HIP(hipMemcpyAsync(buf + (size_t)done * per, buf + (size_t)(c + done) * per, (size_t)n * per * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
 }
-int clip_tower_chunk(const ClipModel& m, int n) {
-  if (n <= 40) return n;
-  const int hi = std::min(n, 128), lo = std::max(32, hi - 40), ntile = std::max(1, m.width / 128);
-  int best = hi;
-  double best_eff = 0.0;
-  for (int c = hi; c >= lo; --c) {
-    const long wgs = (((long)c * m.tokens + 127) / 128) * ntile;
-    const double eff = (double)wgs / (double)(((wgs + 255) / 256) * 256);
-    if (eff > best_eff + 1e-9) { best_eff = eff; best = c; }
-  }
-  return best;
-}
 void clip_tower(Ctx& C, const Tensor& x, float* feat) {   // in the precision the tower was committed under
   const bool r32 = C.clip->dw.res32;      // fp32 token stream around the 2-byte GEMMs
   if (C.clip->split3) { clip_forward_split3(C, *C.clip, x, feat); return; }
@@ -144,6 +133,9 @@ void clip_tower(Ctx& C, const Tensor& x, float* feat) {   // in the precision th
   else if (C.clip->dw.prec == PREC_F16) { if (r32) clip_forward<f16, float>(C, *C.clip, x, feat); else clip_forward<f16>(C, *C.clip, x, feat); }
   else clip_forward<float>(C, *C.clip, x, feat);
 }
+// Both batchers enqueue on ctx->c.stream and take scratch from ctx->c.arena as they find them at the call (the main pair, or the side
+// lane's under a LaneScope). stage / run / compact are the three steps; push / finish sequence them for the single-model entry points,
+// ensemble_run follows its plan (ensemble_plan.h), which sequences them the same way.
 class ClipBatcher {
  public:
   ClipBatcher(fe_ctx* ctx, int n_total, int max_push, float* d_feat, float* d_norm, float* d_aes)
@@ -152,7 +144,7 @@ class ClipBatcher {
     hw_ = m.patch_size * (int)std::lround(std::sqrt((double)(m.tokens - 1)));
     od_ = m.out_dim;
     per_ = (size_t)hw_ * hw_ * 4;
-    chunk_ = clip_tower_chunk(m, n_total);
+    chunk_ = clip_tower_chunk(m.width, m.tokens, n_total);
     const size_t need = (size_t)(chunk_ + max_push) * per_;
     if (ctx->clip_in_cap < need) {
       FE_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -162,30 +154,39 @@ class ClipBatcher {
       ctx->clip_in_cap = need;
     }
   }
-  // xt: dense NHWC4 crops of one micro-batch (arena memory; copied out before the arena is recycled)
-  void push(const Tensor& xt) {
+  int chunk() const { return chunk_; }
+  // xt: dense NHWC4 crops of one micro-batch (arena memory; copied out before the arena is recycled) -> slots [slot, slot + xt.n)
+  void stage(const Tensor& xt, int slot) {
     FE_CHECK(xt.c == 4 && xt.ld == 4 && xt.h == hw_ && xt.w == hw_, "clip batcher: crop layout");
-    FE_HIP(hipMemcpyAsync(x_->clip_in + (size_t)count_ * per_, xt.p, (size_t)xt.n * per_ * sizeof(float), hipMemcpyDeviceToDevice, x_->c.stream));
-    count_ += xt.n;
-    while (count_ >= chunk_) run(chunk_);
+    FE_CHECK((size_t)(slot + xt.n) * per_ <= x_->clip_in_cap, "clip batcher: slot %d + %d past the staging buffer", slot, xt.n);
+    FE_HIP(hipMemcpyAsync(x_->clip_in + (size_t)slot * per_, xt.p, (size_t)xt.n * per_ * sizeof(float), hipMemcpyDeviceToDevice, x_->c.stream));
   }
-  void finish() {
-    while (count_ > 0) run(std::min(count_, chunk_));
-  }
- private:
-  void run(int c) {
+  // tower, L2 normalise and aesthetic head on slots [0, c): the results of images [done, done + c)
+  void run(int c, int done) {
     Ctx& C = x_->c;
     const size_t mark = C.arena.mark();
     Tensor x;
     x.p = x_->clip_in; x.n = c; x.h = hw_; x.w = hw_; x.c = 4; x.ld = 4;
-    clip_tower(C, x, feat_ + (size_t)done_ * od_);
-    if (norm_) l2_normalize(C, feat_ + (size_t)done_ * od_, norm_ + (size_t)done_ * od_, c, od_);
-    if (aes_) aesthetic_forward(C, *C.aesthetic, feat_ + (size_t)done_ * od_, c, aes_ + done_);
+    clip_tower(C, x, feat_ + (size_t)done * od_);
+    if (norm_) l2_normalize(C, feat_ + (size_t)done * od_, norm_ + (size_t)done * od_, c, od_);
+    if (aes_) aesthetic_forward(C, *C.aesthetic, feat_ + (size_t)done * od_, c, aes_ + done);
     C.arena.rewind(mark);
-    const int left = count_ - c;
-    compact_crops(x_->clip_in, per_, c, left, C.stream);
+  }
+  void compact(int c, int left) { compact_crops(x_->clip_in, per_, c, left, x_->c.stream); }
+  void push(const Tensor& xt) {
+    stage(xt, count_);
+    count_ += xt.n;
+    while (count_ >= chunk_) consume(chunk_);
+  }
+  void finish() {
+    while (count_ > 0) consume(std::min(count_, chunk_));
+  }
+ private:
+  void consume(int c) {
+    run(c, done_);
+    compact(c, count_ - c);
     done_ += c;
-    count_ = left;
+    count_ -= c;
   }
   fe_ctx* x_;
   float *feat_, *norm_, *aes_;
@@ -195,11 +196,13 @@ class ClipBatcher {
 // SAMP-Net + U2-Net-P see 224^2 crops too, and most of their ~130 convolutions run on 7x7 .. 56x56 maps: at 32 images per launch
 // they are launch- and tile-quantisation-bound (tools/samp_mb_sweep.py: 2216 img/s at 32 per launch, 2903 at 128). Crops are
 // collected across micro-batches like the CLIP ones; the chunk is bounded by what the arena can hold (~150 MB per image).
+// The chunk is sized from the arena of the Ctx at construction: construct it outside any LaneScope, so the policy follows the main arena.
+constexpr size_t kSampBytesPerImage = (size_t)150 << 20;
 class SampBatcher {
  public:
   SampBatcher(fe_ctx* ctx, int n_total, int max_push, float* pw, float* at, float* sd) : x_(ctx), pw_(pw), at_(at), sd_(sd) {
     const size_t room = ctx->c.arena.capacity() > ((size_t)8 << 30) ? ctx->c.arena.capacity() - ((size_t)8 << 30) : ctx->c.arena.capacity() / 4;
-    const int fit = (int)std::min<size_t>(128, std::max<size_t>(1, room / ((size_t)150 << 20)));
+    const int fit = (int)std::min<size_t>(128, std::max<size_t>(1, room / kSampBytesPerImage));
     chunk_ = std::max(1, std::min(n_total, std::max(fit, std::min(max_push, 32))));
     per_ = (size_t)224 * 224 * 4;
     const size_t need = (size_t)(chunk_ + max_push) * per_;
@@ -211,27 +214,35 @@ class SampBatcher {
       ctx->samp_in_cap = need;
     }
   }
-  void push(const Tensor& xt) {
+  int chunk() const { return chunk_; }
+  void stage(const Tensor& xt, int slot) {
     FE_CHECK(xt.c == 4 && xt.ld == 4 && xt.h == 224 && xt.w == 224, "samp batcher: crop layout");
-    FE_HIP(hipMemcpyAsync(x_->samp_in + (size_t)count_ * per_, xt.p, (size_t)xt.n * per_ * sizeof(float), hipMemcpyDeviceToDevice, x_->c.stream));
-    count_ += xt.n;
-    while (count_ >= chunk_) run(chunk_);
+    FE_CHECK((size_t)(slot + xt.n) * per_ <= x_->samp_in_cap, "samp batcher: slot %d + %d past the staging buffer", slot, xt.n);
+    FE_HIP(hipMemcpyAsync(x_->samp_in + (size_t)slot * per_, xt.p, (size_t)xt.n * per_ * sizeof(float), hipMemcpyDeviceToDevice, x_->c.stream));
   }
-  void finish() {
-    while (count_ > 0) run(std::min(count_, chunk_));
-  }
- private:
-  void run(int c) {
+  void run(int c, int done) {
     Ctx& C = x_->c;
     const size_t mark = C.arena.mark();
     Tensor x;
     x.p = x_->samp_in; x.n = c; x.h = 224; x.w = 224; x.c = 4; x.ld = 4;
-    samp_chunk(x_, x, true, pw_ + (size_t)done_ * 8, at_ + (size_t)done_ * 6, sd_ + (size_t)done_ * 5, nullptr);
+    samp_chunk(x_, x, true, pw_ + (size_t)done * 8, at_ + (size_t)done * 6, sd_ + (size_t)done * 5, nullptr);
     C.arena.rewind(mark);
-    const int left = count_ - c;
-    compact_crops(x_->samp_in, per_, c, left, C.stream);
+  }
+  void compact(int c, int left) { compact_crops(x_->samp_in, per_, c, left, x_->c.stream); }
+  void push(const Tensor& xt) {
+    stage(xt, count_);
+    count_ += xt.n;
+    while (count_ >= chunk_) consume(chunk_);
+  }
+  void finish() {
+    while (count_ > 0) consume(std::min(count_, chunk_));
+  }
+ private:
+  void consume(int c) {
+    run(c, done_);
+    compact(c, count_ - c);
     done_ += c;
-    count_ = left;
+    count_ -= c;
   }
   fe_ctx* x_;
   float *pw_, *at_, *sd_;
@@ -255,8 +266,41 @@ __global__ void records_interleave_kernel(const float* __restrict__ planes, size
   rec[(size_t)img * ld + f] = v;
 }
 
+// The side lane's stream, events and an arena of at least `need` bytes. false: something could not be had (device memory, most
+// likely) and the call runs on the one lane; that is no error.
+bool side_lane_ready(fe_ctx* ctx, size_t need) {
+  auto& s = ctx->side;
+  try {
+    if (!s.stream) FE_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&s.ev_start, &s.ev_join, &s.ev_read[0], &s.ev_read[1]})
+      if (!*e) FE_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (s.arena.capacity() < need) {
+      FE_HIP(hipStreamSynchronize(s.stream));
+      s.arena.init(need);
+    }
+    return true;
+  } catch (const std::exception&) {
+    (void)hipGetLastError();
+    return false;
+  }
+}
+// Scratch of the side lane: the larger of its two models on a chunk (each step resets the arena, and they alternate on the one stream)
+// plus the 224^2 preprocessing of a micro-batch. CLIP: ~13 token-stream-sized buffers of 257 x 1024 x 4 B per image in either
+// precision, taken as 32 MB. Never more than the main arena, in which the one-lane path runs the same steps.
+size_t side_arena_bytes(fe_ctx* ctx, int mb, int h, int w, int clip_chunk, int samp_chunk) {
+  const size_t tower = std::max((size_t)clip_chunk * ((size_t)32 << 20), (size_t)samp_chunk * kSampBytesPerImage);
+  const size_t ow = w <= h ? 224 : (size_t)(224.0 * w / h) + 1;
+  const size_t pre = (size_t)mb * ((size_t)h * ow * 3 + (size_t)224 * 224 * (3 + 16) + 1024);
+  return std::min(ctx->c.arena.capacity(), tower + pre + ((size_t)64 << 20));
+}
+
 // Runs every selected model over the batch and leaves the interleaved records in device memory d_rec [n][ld].
+// With a 224^2 model selected the call runs on two lanes: TOPIQ on the context's stream and arena, SAMP (and a 2-byte CLIP tower) on
+// the side lane beside it (ensemble_plan.h has the schedule and its edges; DESIGN.md section 5 the reasons). One lane when
+// per-launch profiling is on (event pairs with a sync mean nothing across lanes), when the side arena could not be allocated, and
+// when FE_NO_OVERLAP is in the environment (A/B hook, read per call). Both ways every launch has the same arguments.
 int ensemble_run(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, int on_device, float* d_rec, int ld) {
+  using namespace fe::plan;
   Ctx& C = ctx->c;
   const size_t per = (size_t)h * w * 3;
   // SoA planes on the device (every plane 16-B aligned), interleaved into records by a last small kernel
@@ -264,7 +308,6 @@ int ensemble_run(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, int on_de
   const size_t o_aes = n4, o_pw = 2 * n4, o_at = o_pw + 8 * n4, o_sd = o_at + 6 * n4, o_emb = o_sd + 5 * n4,
                o_feat = o_emb + 768 * n4, total = o_feat + 768 * n4;
   float* d_pl = ctx->out_buf(total);
-  FE_HIP(hipMemsetAsync(d_pl, 0, total * sizeof(float), C.stream));
   const int sel = ctx->ensemble_mask;
   const bool do_topiq = (sel & 1) && C.topiq && C.topiq->has_head, do_clip = (sel & 2) && C.clip, do_samp = (sel & 4) && C.samp && C.u2netp;
   float* p_topiq = d_pl;  float* p_aes = d_pl + o_aes;  float* p_pw = d_pl + o_pw;  float* p_at = d_pl + o_at;
@@ -273,35 +316,83 @@ int ensemble_run(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, int on_de
   if (do_clip) tower = std::make_unique<ClipBatcher>(ctx, n, ctx->microbatch, d_feat, p_emb, C.aesthetic ? p_aes : nullptr);
   std::unique_ptr<SampBatcher> samp;
   if (do_samp) samp = std::make_unique<SampBatcher>(ctx, n, ctx->microbatch, p_pw, p_at, p_sd);
-  ImageStager st(ctx, rgb, n, per, ctx->microbatch, on_device);
-  for (int k = 0; k < st.chunks(); ++k) {
-    const int i0 = k * ctx->microbatch, nb = st.count(k);
-    C.arena.reset();
-    const uint8_t* d_in = st.get(k);
-    if (do_topiq) {
-      const size_t mark = C.arena.mark();
-      topiq_chunk_score(ctx, d_in, nb, h, w, p_topiq + i0);
-      C.arena.rewind(mark);
-    }
-    if (do_clip) {
-      const size_t mark = C.arena.mark();
-      Tensor xt = preprocess_square224(C, d_in, nb, h, w, FE_FILTER_BICUBIC, true, kClipMean, kClipStd, 0);
-      tower->push(xt);   // the ViT tower runs once enough crops have gathered for full rounds of workgroups
-      C.arena.rewind(mark);
-    }
-    if (do_samp) {
-      const size_t mark = C.arena.mark();
-      Tensor xt = preprocess_square224(C, d_in, nb, h, w, FE_FILTER_BILINEAR, false, kImagenetMean, kImagenetStd, 0);
-      samp->push(xt);    // U2-Net-P + SAMP-Net run once enough crops have gathered
-      C.arena.rewind(mark);
-    }
-    st.done(k);
+  if (!on_device) ImageStager::prepare(ctx, (size_t)std::min(ctx->microbatch, n) * per);
+
+  Shape sh;
+  sh.n = n; sh.mb = ctx->microbatch; sh.on_device = on_device != 0;
+  sh.topiq = do_topiq; sh.clip = do_clip; sh.samp = do_samp;
+  sh.clip_chunk = tower ? tower->chunk() : 1;
+  sh.samp_chunk = samp ? samp->chunk() : 1;
+  // An fp32 CLIP tower stays on the main lane: its GEMMs and TOPIQ's want the same matrix pipes, and beside TOPIQ it measured 0 to -0.2 %
+  // (profiles/overlap_perf.txt: topiq_clip, and CLIP alone on the side lane of the full workload). A 2-byte tower rides the side lane with
+  // SAMP: under the parity and bf16 policies the pairing is worth 5 %. Keyed on the precision the model was committed under.
+  sh.clip_side = do_clip && C.clip->dw.prec != PREC_F32;
+  if (const char* v = getenv("FE_OVERLAP_LANES")) {   // A/B hook, read per call: "clip" / "samp" = only that model on the side lane; "both"; "samp_first"
+    sh.samp_side = strcmp(v, "clip") != 0;
+    sh.clip_side = strcmp(v, "samp") != 0;
+    sh.samp_first = strcmp(v, "samp_first") == 0;
   }
-  if (tower) tower->finish();
-  if (samp) samp->finish();
-  const size_t work = (size_t)n * FE_RECORD_FLOATS;
-  hipLaunchKernelGGL(records_interleave_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, C.stream, d_pl, n4, n, d_rec, ld);
-  FE_HIP(hipGetLastError());
+  const bool side_clip = do_clip && sh.clip_side, side_samp = do_samp && sh.samp_side;
+  sh.overlap = (side_clip || side_samp) && !C.profile && getenv("FE_NO_OVERLAP") == nullptr &&
+               side_lane_ready(ctx, side_arena_bytes(ctx, std::min(ctx->microbatch, n), h, w, side_clip ? sh.clip_chunk : 0, side_samp ? sh.samp_chunk : 0));
+
+  // the streams and events by the plan's names, read before any LaneScope swaps the Ctx's members
+  const hipStream_t lane[N_LANES] = {C.stream, ctx->side.stream, ctx->copy_stream};
+  hipEvent_t event[N_EVENTS];
+  event[EV_START] = ctx->side.ev_start; event[EV_JOIN] = ctx->side.ev_join;
+  for (int b = 0; b < 2; ++b) {
+    event[EV_COPIED0 + b] = ctx->ev_copied[b]; event[EV_CONSUMED0 + b] = ctx->ev_consumed[b]; event[EV_SIDE_READ0 + b] = ctx->side.ev_read[b];
+  }
+  auto input = [&](int k) { return on_device ? rgb + (size_t)k * ctx->microbatch * per : (const uint8_t*)ctx->stage_buf[k & 1]; };
+  for (const Op& o : build(sh)) {
+    LaneScope scope(ctx, o.lane == LANE_SIDE);
+    switch (o.kind) {
+      case OP_CLEAR:
+        FE_HIP(hipMemsetAsync(d_pl, 0, total * sizeof(float), lane[LANE_MAIN]));
+        break;
+      case OP_COPY_IN:
+        FE_HIP(hipMemcpyAsync(ctx->stage_buf[o.mb & 1], rgb + (size_t)o.img0 * per, (size_t)o.count * per, hipMemcpyHostToDevice, lane[LANE_COPY]));
+        break;
+      case OP_RECORD:
+        FE_HIP(hipEventRecord(event[o.event], lane[o.lane]));
+        break;
+      case OP_WAIT:
+        FE_HIP(hipStreamWaitEvent(lane[o.lane], event[o.event], 0));
+        break;
+      case OP_TOPIQ:
+        C.arena.reset();
+        topiq_chunk_score(ctx, input(o.mb), o.count, h, w, p_topiq + o.img0);
+        break;
+      case OP_CLIP_PRE:
+        C.arena.reset();
+        tower->stage(preprocess_square224(C, input(o.mb), o.count, h, w, FE_FILTER_BICUBIC, true, kClipMean, kClipStd, 0), o.slot);
+        break;
+      case OP_CLIP_TOWER:   // the ViT tower runs once enough crops have gathered for full rounds of workgroups
+        C.arena.reset();
+        tower->run(o.count, o.img0);
+        break;
+      case OP_CLIP_COMPACT:
+        tower->compact(o.count, o.left);
+        break;
+      case OP_SAMP_PRE:
+        C.arena.reset();
+        samp->stage(preprocess_square224(C, input(o.mb), o.count, h, w, FE_FILTER_BILINEAR, false, kImagenetMean, kImagenetStd, 0), o.slot);
+        break;
+      case OP_SAMP_NETS:    // U2-Net-P + SAMP-Net run once enough crops have gathered
+        C.arena.reset();
+        samp->run(o.count, o.img0);
+        break;
+      case OP_SAMP_COMPACT:
+        samp->compact(o.count, o.left);
+        break;
+      case OP_INTERLEAVE: {
+        const size_t work = (size_t)n * FE_RECORD_FLOATS;
+        hipLaunchKernelGGL(records_interleave_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, lane[LANE_MAIN], d_pl, n4, n, d_rec, ld);
+        FE_HIP(hipGetLastError());
+        break;
+      }
+    }
+  }
   return (do_topiq ? 1 : 0) | (do_clip ? 2 : 0) | (do_samp ? 4 : 0);
 }
 }  // namespace
@@ -462,7 +553,7 @@ int fe_clip_encode_image(fe_ctx* ctx, const float* x, int n, int on_device, floa
     const size_t per = (size_t)3 * hw * hw;
     float* d_out = ctx->out_buf((size_t)n * (2 * od + 1));
     float* d_feat = d_out; float* d_norm = d_out + (size_t)n * od; float* d_aes = d_out + (size_t)n * 2 * od;
-    const int step = clip_tower_chunk(*C.clip, n);   // inputs are already 224^2: batch the tower for full rounds of workgroups
+    const int step = clip_tower_chunk(C.clip->width, C.clip->tokens, n);   // inputs are already 224^2: batch the tower for full rounds of workgroups
     for (int i0 = 0; i0 < n; i0 += step) {
       const int nb = std::min(step, n - i0);
       C.arena.reset();

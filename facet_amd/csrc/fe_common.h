@@ -11,6 +11,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace fe {
@@ -208,6 +209,7 @@ class Arena {
   void rewind(size_t m) { off_ = m; }
   size_t capacity() const { return cap_; }
   size_t high_water() const { return high_; }
+  void swap(Arena& o) { std::swap(base_, o.base_); std::swap(cap_, o.cap_); std::swap(off_, o.off_); std::swap(high_, o.high_); }
   void* alloc(size_t bytes) {
     size_t a = (off_ + 255) & ~(size_t)255;
     FE_CHECK(a + bytes <= cap_, "arena exhausted: need %zu at %zu of %zu", bytes, a, cap_);
