@@ -104,6 +104,11 @@ SIGNATURES = {
                                              _f32p, _f32p, _f32p]),
     "fe_op_vlm_linear": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_float,
                                    C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.POINTER(C.c_int32)]),
+    "fe_op_vlm_rope_cache": (C.c_int, [C.c_void_p, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, _f32p, _f32p, C.c_float] + [C.c_int] * 12 +
+                             [_f32p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f32p, _f32p]),
+    "fe_op_vlm_rows": (C.c_int, [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_float, C.c_int, C.c_int, _f32p, _f32p]),
+    "fe_op_vlm_vis_rope": (C.c_int, [C.c_void_p, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
     "fe_topiq_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -849,6 +854,85 @@ class Engine:
                                            y.ctypes.data_as(_f32p), y2.ctypes.data_as(_f32p), info))
         d = dict(family=self.VLM_LINEAR_FAMILIES.get(int(info[0]), int(info[0])), mr=int(info[1]), splits=int(info[2]), direct=bool(info[3]))
         return (y, y2, d) if route == "add_rmsnorm" else (y, d)
+
+    VLM_ROPE_FAMILIES = {"qwen2_5": 0, "qwen3": 1}
+
+    def vlm_rope_cache(self, qkv, pos, inv_freq, nh, nkv, B, L, sections, family="qwen2_5", qn=None, kn=None, eps=1e-6, start=0,
+                       start_from_device=False, max_seq=None, kv_format="bf16", max_blocks=0, fill=0xA5):
+        """The rotary embedding + KV-cache append of the VLM decoders launched alone (fe_op_vlm_rope_cache). qkv [B * L, (nh + 2 nkv) * 128]
+        (rounded to bf16), pos int [3, B * L], inv_freq [64]; sections: the two section sizes the family reads ("qwen2_5": temporal and
+        height of the chunked form; "qwen3": height and width of the interleaved one, with qn / kn [128] and eps). Both caches (and the
+        scale arrays of "fp8") are filled with the byte `fill` before the launch.
+        -> (q [B * L, nh * 128] float32, k_raw, v_raw [B, nkv, max_seq, 128] as stored: uint16 bf16 bit patterns, or uint8 e4m3 codes,
+        k_scale, v_scale [B, nkv, max_seq] float32 for "fp8", else None)."""
+        (qkv, qp), (fr, fp) = _f32(qkv), _f32(inv_freq)
+        pos, pp = self._i32(pos)
+        rows, heads = B * L, nh + 2 * nkv
+        max_seq = start + L if max_seq is None else int(max_seq)
+        assert qkv.shape == (rows, heads * 128) and pos.shape == (3, rows) and fr.shape == (64,), (qkv.shape, pos.shape, fr.shape)
+        null = C.cast(None, _f32p)
+        (qn, qnp), (kn, knp) = ((None, null), (None, null)) if qn is None else (_f32(qn), _f32(kn))
+        assert qn is None or (qn.shape == (128,) and kn.shape == (128,))
+        f8 = kv_format == "fp8"
+        q = np.empty((rows, nh * 128), np.float32)
+        k = np.empty((B, nkv, max_seq, 128), np.uint8 if f8 else np.uint16)
+        v = np.empty_like(k)
+        ks, vs = (np.empty((B, nkv, max_seq), np.float32), np.empty((B, nkv, max_seq), np.float32)) if f8 else (None, None)
+        u8 = C.POINTER(C.c_uint8)
+        self._ck(self.lib.fe_op_vlm_rope_cache(self.h, qp, pp, fp, self.VLM_ROPE_FAMILIES[family], qnp, knp, float(eps), int(sections[0]), int(sections[1]),
+                                               int(B), int(L), int(nh), int(nkv), int(start), int(bool(start_from_device)), max_seq,
+                                               VLM_KV_FORMATS[kv_format], int(max_blocks), int(fill), q.ctypes.data_as(_f32p), k.ctypes.data_as(u8),
+                                               v.ctypes.data_as(u8), ks.ctypes.data_as(_f32p) if f8 else null, vs.ctypes.data_as(_f32p) if f8 else null))
+        return q, k, v, ks, vs
+
+    VLM_ROWS_ROUTES = {"rmsnorm": 0, "add": 1, "add_rmsnorm": 2, "add_rmsnorm_no_w": 3, "add_rmsnorm_ds": 4, "few_rows_rmsnorm": 5, "silu_mul": 6}
+
+    def vlm_rows(self, route, x, y=None, w=None, slot=None, ds=None, eps=1e-6, d=None, ldy=None, alias=False, max_blocks=0):
+        """A row pass of the VLM decoders launched alone (fe_op_vlm_rows); inputs are rounded to bf16, results are float32 bf16 values.
+          "rmsnorm"           x [rows, ldx], d <= ldx values per row normed, w [d] -> n [rows, ldy] (columns past d keep 768)
+          "add"               -> bf16(x + y)
+          "add_rmsnorm"       -> (r, n): r = bf16(x + y), n = RMSNorm(r) w
+          "add_rmsnorm_no_w"  -> r
+          "add_rmsnorm_ds"    -> (r, n) with r = bf16(r + ds[slot[row]]) on rows whose slot >= 0, before the norm
+          "few_rows_rmsnorm"  -> (x, n), rows <= 64
+          "silu_mul"          -> bf16(bf16(silu(x)) y); alias: written over x's buffer"""
+        r = self.VLM_ROWS_ROUTES[route]
+        x, xp = _f32(x)
+        rows, ldx = x.shape
+        d = ldx if d is None else int(d)
+        ldy = d if ldy is None else int(ldy)
+        null, nulli = C.cast(None, _f32p), C.cast(None, C.POINTER(C.c_int32))
+
+        def opt(a, shape):
+            if a is None:
+                return None, null
+            a, p = _f32(a)
+            assert a.shape == shape, (a.shape, shape)
+            return a, p
+        ya, yp = opt(y, (rows, d))
+        wa, wp = opt(w, (d,))
+        dsa, dsp = opt(ds, (0 if ds is None else len(ds), d))
+        sl, slp = (None, nulli) if slot is None else self._i32(slot)
+        assert sl is None or sl.shape == (rows,), sl.shape
+        gives_x, gives_n = route != "rmsnorm", wa is not None
+        ox = np.empty((rows, d), np.float32) if gives_x else None
+        on = np.empty((rows, ldy), np.float32) if gives_n else None
+        self._ck(self.lib.fe_op_vlm_rows(self.h, r, xp, yp, wp, slp, dsp, 0 if dsa is None else dsa.shape[0], rows, d, ldx, ldy, float(eps), int(bool(alias)),
+                                         int(max_blocks), ox.ctypes.data_as(_f32p) if gives_x else null, on.ctypes.data_as(_f32p) if gives_n else null))
+        if gives_x and gives_n:
+            return ox, on
+        return ox if gives_x else on
+
+    def vlm_vis_rope(self, qkv, pos, inv_freq, hd, heads, max_blocks=0):
+        """The 2-D rotary embedding of the vision towers launched alone (fe_op_vlm_vis_rope): qkv [rows, 3 * heads * hd] (rounded to bf16), pos
+        int [rows, 2], inv_freq [hd / 4] -> (q, k) float32 [rows, heads * hd]."""
+        (qkv, qp), (fr, fp) = _f32(qkv), _f32(inv_freq)
+        pos, pp = self._i32(pos)
+        rows = qkv.shape[0]
+        assert qkv.shape == (rows, 3 * heads * hd) and pos.shape == (rows, 2) and fr.shape == (hd // 4,), (qkv.shape, pos.shape, fr.shape)
+        q, k = np.empty((rows, heads * hd), np.float32), np.empty((rows, heads * hd), np.float32)
+        self._ck(self.lib.fe_op_vlm_vis_rope(self.h, qp, pp, fp, int(hd), rows, int(heads), int(max_blocks), q.ctypes.data_as(_f32p), k.ctypes.data_as(_f32p)))
+        return q, k
 
     def vlm_vision_configure(self, n_heads=16, fullatt_block_indexes=(7, 15, 23, 31)):
         """Vision-tower geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (Qwen2_5_VLVisionConfig; defaults = Qwen2.5-VL-7B)."""

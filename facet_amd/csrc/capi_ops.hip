@@ -408,4 +408,135 @@ int fe_op_vlm_linear(fe_ctx* ctx, const float* x, int M, int ldx, const float* w
   });
 }
 
+// ---- test hooks of the VLM decoders' row passes: each runs the launch function vlm_forward (or a vision tower) calls, alone ----------------
+// n host floats -> bf16 in the arena
+static bf16* vlm_hook_bf16(Ctx& C, const float* src, size_t n) {
+  if (!src) return nullptr;
+  float* d32 = upload(C, src, n);
+  bf16* d16 = C.arena.array<bf16>(n);
+  launch_convert(d32, d16, n, C.stream);
+  return d16;
+}
+// n bf16 values in device memory -> host floats (queued on the stream; the caller synchronises)
+static void vlm_hook_f32(Ctx& C, const bf16* src, size_t n, float* dst) {
+  if (!dst) return;
+  float* d32 = C.arena.array<float>(n);
+  launch_convert(src, d32, n, C.stream);
+  FE_HIP(hipMemcpyAsync(dst, d32, n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+}
+
+int fe_op_vlm_rope_cache(fe_ctx* ctx, const float* qkv, const int32_t* pos, const float* inv_freq, int family, const float* qn, const float* kn, float eps,
+                         int sa, int sb, int B, int L, int nh, int nkv, int start, int start_from_device, int max_seq, int kv_format, int max_blocks, int fill,
+                         float* q_out, uint8_t* k_raw, uint8_t* v_raw, float* k_scale, float* v_scale) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(qkv && pos && inv_freq && q_out && k_raw && v_raw && B > 0 && L > 0 && nh > 0 && nkv > 0 && (size_t)B * L * (nh + 2 * nkv) <= (1u << 20),
+             "bad rope arguments");
+    FE_CHECK(family == 0 || (family == 1 && qn && kn), "fe_op_vlm_rope_cache: family %d (0 Qwen2.5-VL, 1 Qwen3-VL with qn and kn)", family);
+    FE_CHECK(kv_format == FE_VLM_KV_BF16 || kv_format == FE_VLM_KV_E4M3 || kv_format == FE_VLM_KV_BF16_E4M3, "fe_op_vlm_rope_cache: kv format %d", kv_format);
+    FE_CHECK(sa >= 0 && sb >= 0 && sa + sb <= 64 && fill >= 0 && fill <= 255 && max_blocks >= 0, "fe_op_vlm_rope_cache: sections %d, %d, fill %d", sa, sb, fill);
+    // (the launch function checks a start passed by value; the one the kernel reads from device memory is checked here)
+    FE_CHECK(max_seq > 0 && max_seq <= 8192 && start >= 0 && start + L <= max_seq, "fe_op_vlm_rope_cache: positions %d .. %d of a cache of %d", start, start + L - 1,
+             max_seq);
+    const bool f8 = kv_format == FE_VLM_KV_E4M3;
+    FE_CHECK(!f8 || (k_scale && v_scale), "fe_op_vlm_rope_cache: the e4m3 format returns its scales");
+    C.arena.reset();
+    const size_t rows = (size_t)B * L, crow = (size_t)B * nkv * max_seq, cbytes = crow * 128 * (f8 ? 1 : sizeof(bf16));
+    const bf16* hqkv = vlm_hook_bf16(C, qkv, rows * (nh + 2 * nkv) * 128);
+    const int* dpos = upload(C, pos, 3 * rows);
+    const float* dfreq = upload(C, inv_freq, (size_t)64);
+    VlmKv kv;
+    kv.format = kv_format; kv.max_seq = max_seq;
+    kv.k = (bf16*)C.arena.alloc(cbytes);
+    kv.v = (bf16*)C.arena.alloc(cbytes);
+    FE_HIP(hipMemsetAsync(kv.k, fill, cbytes, C.stream));
+    FE_HIP(hipMemsetAsync(kv.v, fill, cbytes, C.stream));
+    if (f8) {
+      kv.ks = C.arena.array<float>(crow); kv.vs = C.arena.array<float>(crow);
+      FE_HIP(hipMemsetAsync(kv.ks, fill, crow * sizeof(float), C.stream));
+      FE_HIP(hipMemsetAsync(kv.vs, fill, crow * sizeof(float), C.stream));
+    }
+    bf16* hq = C.arena.array<bf16>(rows * nh * 128);
+    VlmRope r;
+    r.qwen3 = family == 1;
+    r.qn = vlm_hook_bf16(C, r.qwen3 ? qn : nullptr, 128); r.kn = vlm_hook_bf16(C, r.qwen3 ? kn : nullptr, 128); r.eps = eps;
+    if (r.qwen3) { r.s1 = sa; r.s2 = sb; } else { r.s0 = sa; r.s1 = sb; r.s2 = 64 - sa - sb; }
+    r.B = B; r.L = L; r.nh = nh; r.nkv = nkv; r.max_blocks = max_blocks;
+    if (start_from_device) { r.start = 0; r.start_dev = upload(C, &start, 1); FE_HIP(hipStreamSynchronize(C.stream)); }
+    else r.start = start;
+    vlm_rope_cache(C, r, kv, hqkv, dpos, dfreq, hq);
+    vlm_hook_f32(C, hq, rows * nh * 128, q_out);
+    FE_HIP(hipMemcpyAsync(k_raw, kv.k, cbytes, hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipMemcpyAsync(v_raw, kv.v, cbytes, hipMemcpyDeviceToHost, C.stream));
+    if (f8) {
+      FE_HIP(hipMemcpyAsync(k_scale, kv.ks, crow * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipMemcpyAsync(v_scale, kv.vs, crow * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    }
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+int fe_op_vlm_rows(fe_ctx* ctx, int route, const float* x, const float* y, const float* w, const int32_t* slot, const float* ds, int n_ds, int rows, int d,
+                   int ldx, int ldy, float eps, int alias, int max_blocks, float* out_x, float* out_n) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    enum { RMSNORM = 0, ADD = 1, ADD_NORM = 2, ADD_NORM_NO_W = 3, ADD_NORM_DS = 4, FEW_ROWS = 5, SILU_MUL = 6 };
+    FE_CHECK(route >= RMSNORM && route <= SILU_MUL && x && rows > 0 && rows <= 65536 && d > 0 && d <= 65536 && d % 4 == 0 && max_blocks >= 0, "bad vlm rows arguments");
+    FE_CHECK(route == RMSNORM ? (ldx >= d && ldy >= d && ldx <= 2 * d + 64 && ldy <= 2 * d + 64) : (ldx == d && ldy == d), "fe_op_vlm_rows: strides %d, %d of %d values", ldx,
+             ldy, d);
+    const bool takes_y = route != RMSNORM && route != FEW_ROWS, takes_w = route == RMSNORM || route == ADD_NORM || route == ADD_NORM_DS || route == FEW_ROWS;
+    const bool gives_x = route != RMSNORM;
+    FE_CHECK(!takes_y == !y && !takes_w == !w && !gives_x == !out_x && !takes_w == !out_n, "fe_op_vlm_rows: route %d takes other operands", route);
+    FE_CHECK(route == ADD_NORM_DS ? (slot && ds && n_ds > 0) : (!slot && !ds), "fe_op_vlm_rows: slot and ds belong to route %d", (int)ADD_NORM_DS);
+    if (route == ADD_NORM_DS)
+      for (int m = 0; m < rows; ++m) FE_CHECK(slot[m] >= -1 && slot[m] < n_ds, "fe_op_vlm_rows: slot %d of %d rows", slot[m], n_ds);
+    FE_CHECK(route != FEW_ROWS || rows <= 64, "fe_op_vlm_rows: the few-rows form takes up to 64 rows");
+    C.arena.reset();
+    const size_t n = (size_t)rows * d;
+    bf16* hx = vlm_hook_bf16(C, x, (size_t)rows * ldx);
+    const bf16* hy = vlm_hook_bf16(C, y, n);
+    const bf16* hw = vlm_hook_bf16(C, w, (size_t)d);
+    const bf16* hds = vlm_hook_bf16(C, ds, (size_t)(ds ? n_ds : 0) * d);
+    const int* dslot = slot ? upload(C, slot, (size_t)rows) : nullptr;
+    bf16* hn = nullptr;
+    if (takes_w) {      // the columns past d of a padded output keep the fill
+      const size_t no = (size_t)rows * ldy;
+      std::vector<float> pad(no, 768.f);      // (a bf16 value)
+      hn = vlm_hook_bf16(C, pad.data(), no);
+      FE_HIP(hipStreamSynchronize(C.stream));      // (pad dies with this block)
+    }
+    const bf16* hout = hx;
+    if (route == RMSNORM) vlm_rmsnorm(C, hx, ldx, hw, hn, ldy, rows, d, eps, max_blocks);
+    else if (route == ADD) vlm_add(C, hx, hy, n, max_blocks);
+    else if (route == FEW_ROWS) vlm_few_rows_rmsnorm(C, hx, hw, hn, rows, d, eps);
+    else if (route == SILU_MUL) {
+      bf16* hh = alias ? hx : C.arena.array<bf16>(n);
+      vlm_silu_mul(C, hx, hy, hh, n, max_blocks);
+      hout = hh;
+    } else vlm_add_rmsnorm(C, hx, hy, hw, hn, rows, d, eps, dslot, hds, max_blocks);
+    if (gives_x) vlm_hook_f32(C, hout, n, out_x);
+    if (takes_w) vlm_hook_f32(C, hn, (size_t)rows * ldy, out_n);
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+int fe_op_vlm_vis_rope(fe_ctx* ctx, const float* qkv, const int32_t* pos, const float* inv_freq, int hd, int rows, int heads, int max_blocks, float* q_out,
+                       float* k_out) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(qkv && pos && inv_freq && q_out && k_out && (hd == 64 || hd == 80) && rows > 0 && rows <= 65536 && heads > 0 && heads <= 64 && max_blocks >= 0,
+             "bad vision rope arguments (hd 64 or 80)");
+    C.arena.reset();
+    const size_t n = (size_t)rows * heads * hd;
+    const bf16* hqkv = vlm_hook_bf16(C, qkv, 3 * n);
+    const int* dpos = upload(C, pos, (size_t)2 * rows);
+    const float* dfreq = upload(C, inv_freq, (size_t)(hd / 4));
+    bf16 *hq = C.arena.array<bf16>(n), *hk = C.arena.array<bf16>(n);
+    vlm_vis_rope(C, hd, hqkv, dpos, dfreq, hq, hk, rows, heads, max_blocks);
+    vlm_hook_f32(C, hq, n, q_out);
+    vlm_hook_f32(C, hk, n, k_out);
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
 }  // extern "C"

@@ -479,7 +479,8 @@ void build_vlm_vision(VlmModel& m, const WeightStore& ws);
 void build_vlm_ln_vision(VlmModel& m, const WeightStore& ws);      // the family: m.cfg.qwen3, else Qwen2-VL
 // pieces shared by the three towers (model_vlm_vision.hip), hd = head_dim 64 or 80
 //   2-D rotary embedding on the q / k thirds of fused qkv rows [rows][3 * heads * hd] -> q_out / k_out [rows][heads * hd]
-void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads);
+void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads,
+                  int max_blocks = 0);      // (max_blocks: see vlm_grid)
 //   non-causal attention inside the segments cu [n_seg + 1] (longest: max_seg rows), v = the V third of the fused qkv rows
 void vlm_vis_attention(Ctx& c, int hd, const bf16* q, const bf16* k, const bf16* qkv, bf16* o, const int* cu, int n_seg, int max_seg, int heads);
 //   the hd / 4 frequencies of VisionRotaryEmbedding(hd / 2)
@@ -503,9 +504,34 @@ void vlm_patchify16(Ctx& c, const uint8_t* img, int oh, int ow, const float* lut
 // row kernels and helpers shared by the decoder and the vision towers (model_vlm.hip)
 inline int grid_n(size_t n, int per = 256) { size_t g = (n + per - 1) / per; return (int)(g > 65535 * 4 ? 65535 * 4 : (g ? g : 1)); }      // grid-stride launches
 bf16* upload_bf16(DeviceWeights& dw, const std::vector<float>& v);
-void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps);
-void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n);
-void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n);
+// max_blocks of the row passes below (the fe_op_vlm_* test hooks; vlm_forward and the towers pass 0 = grid_n's own cap): at most that many
+// 256-thread workgroups for the same work, so the later trips of the grid-stride loops run at small shapes. grid x block stays a multiple
+// of 64 (a wave stays on one row, or one (row, head)).
+int vlm_grid(size_t n_threads, int max_blocks);
+// y = RMSNorm(x) w, rows of d values at strides ldx / ldy (d, ldx, ldy multiples of 4)
+void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps, int max_blocks = 0);
+void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n, int max_blocks = 0);
+void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n, int max_blocks = 0);      // h may be g
+// x = bf16(x + y) (+ the DeepStack rows ds[slot[row]] where ds is given and slot[row] >= 0), n = RMSNorm(x) w   (w == nullptr: the sum only)
+void vlm_add_rmsnorm(Ctx& c, bf16* x, const bf16* y, const bf16* w, bf16* n, int rows, int d, float eps, const int* slot = nullptr, const bf16* ds = nullptr,
+                     int max_blocks = 0);
+// n = RMSNorm(x) w for up to 64 rows, one 1024-thread workgroup per row (the finishing pass of the fused steps with no split sums to take:
+// x is rewritten with its own bits)
+void vlm_few_rows_rmsnorm(Ctx& c, bf16* x, const bf16* w, bf16* n, int rows, int d, float eps);
+// The rotary embedding of the q and k heads of fused rows qkv [B * L][(nh + 2 nkv) * 128] + the KV-cache append at positions start .. start + L - 1
+// (start_dev != nullptr: the start is read from device memory instead, the form a captured decode graph replays). qwen3: q / k RMSNorm with
+// qn / kn [128] and eps, then the interleaved M-RoPE with sections (.., s1, s2); else the chunked one with sections (s0, s1, ..).
+// pos: device [3][B * L]; inv_freq: device [64]; q_out [B * L][nh * 128]; kv: the cache and its format (struct VlmKv below).
+struct VlmKv;
+struct VlmRope {
+  bool qwen3 = false;
+  const bf16* qn = nullptr; const bf16* kn = nullptr; float eps = 0.f;
+  int s0 = 0, s1 = 0, s2 = 0;
+  int B = 0, L = 0, nh = 0, nkv = 0;
+  int start = 0; const int* start_dev = nullptr;
+  int max_blocks = 0;
+};
+void vlm_rope_cache(Ctx& c, const VlmRope& r, const VlmKv& kv, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out);
 void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, int d);
 void vlm_embed(Ctx& c, const VlmModel& m, const int* tok_dev, int rows, bf16* x);
 void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int* next_dev, float* logits_dev, const int* len_dev = nullptr,

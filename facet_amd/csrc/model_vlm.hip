@@ -42,7 +42,8 @@ __global__ void vlm_embed_kernel(const int* __restrict__ tok, const bf16* __rest
 }
 
 // transformers' RMSNorm in bf16: x32 = float(x); y = w * bf16(x32 * rsqrt(mean(x32^2) + eps)), the product rounded to bf16.
-// One wave per row; d % 8 == 0.
+// One wave per row; d, ldx and ldy multiples of 4: a lane moves 4 values (8 bytes) at a time, the last trip over a row may be partial
+// (vlm_rmsnorm checks it).
 __global__ void vlm_rmsnorm_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ w, bf16* __restrict__ y, int ldy, int rows, int d, float eps) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -1436,16 +1437,65 @@ void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh,
 }
 
 
-void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps) {
-  hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, ldx, w, y, ldy, rows, d, eps);
+// ---- the launches of the row passes (engine.h): vlm_forward, the vision towers and the fe_op_vlm_* test hooks all come through here ------
+int vlm_grid(size_t n_threads, int max_blocks) {
+  int g = grid_n(n_threads);
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
+  // (the wave-per-row kernels derive row and lane from the global thread index)
+  FE_CHECK(max_blocks >= 0 && ((size_t)g * 256) % 64 == 0, "vlm: a launch of %d workgroups (max_blocks %d) does not keep a wave on one row", g, max_blocks);
+  return g;
+}
+void vlm_rmsnorm(Ctx& c, const bf16* x, int ldx, const bf16* w, bf16* y, int ldy, int rows, int d, float eps, int max_blocks) {
+  FE_CHECK(rows > 0 && d > 0 && d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, "vlm_rmsnorm: %d rows of %d values at strides %d, %d (multiples of 4)",
+           rows, d, ldx, ldy);
+  hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(vlm_grid((size_t)rows * 64, max_blocks)), dim3(256), 0, c.stream, x, ldx, w, y, ldy, rows, d, eps);
   FE_HIP(hipGetLastError());
 }
-void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n) {
-  hipLaunchKernelGGL(vlm_add_kernel, dim3(grid_n(n / 4)), dim3(256), 0, c.stream, x, y, n / 4);
+void vlm_add(Ctx& c, bf16* x, const bf16* y, size_t n, int max_blocks) {
+  FE_CHECK(n % 4 == 0, "vlm_add: %zu values (a multiple of 4)", n);
+  hipLaunchKernelGGL(vlm_add_kernel, dim3(vlm_grid(n / 4, max_blocks)), dim3(256), 0, c.stream, x, y, n / 4);
   FE_HIP(hipGetLastError());
 }
-void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n) {
-  hipLaunchKernelGGL(vlm_silu_mul_kernel, dim3(grid_n(n / 4)), dim3(256), 0, c.stream, g, u, h, n / 4);
+void vlm_silu_mul(Ctx& c, const bf16* g, const bf16* u, bf16* h, size_t n, int max_blocks) {
+  FE_CHECK(n % 4 == 0, "vlm_silu_mul: %zu values (a multiple of 4)", n);
+  hipLaunchKernelGGL(vlm_silu_mul_kernel, dim3(vlm_grid(n / 4, max_blocks)), dim3(256), 0, c.stream, g, u, h, n / 4);
+  FE_HIP(hipGetLastError());
+}
+void vlm_add_rmsnorm(Ctx& c, bf16* x, const bf16* y, const bf16* w, bf16* n, int rows, int d, float eps, const int* slot, const bf16* ds, int max_blocks) {
+  FE_CHECK(rows > 0 && d > 0 && d % 4 == 0 && (!ds || slot) && (!w || n), "vlm_add_rmsnorm: %d rows of %d values (a multiple of 4)", rows, d);
+  const dim3 grid(vlm_grid((size_t)rows * 64, max_blocks));
+  if (ds) hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<true>, grid, dim3(256), 0, c.stream, x, y, w, n, rows, d, eps, slot, ds);
+  else hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<false>, grid, dim3(256), 0, c.stream, x, y, w, n, rows, d, eps, (const int*)nullptr, (const bf16*)nullptr);
+  FE_HIP(hipGetLastError());
+}
+void vlm_few_rows_rmsnorm(Ctx& c, bf16* x, const bf16* w, bf16* n, int rows, int d, float eps) {
+  FE_CHECK(rows > 0 && rows <= 64 && d > 0 && d % 4 == 0 && w && n, "vlm_few_rows_rmsnorm: %d rows (1 .. 64) of %d values (a multiple of 4)", rows, d);
+  hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)nullptr, 0, rows, d, (const float*)nullptr, x, w, n, eps,
+                     (const int*)nullptr, (const bf16*)nullptr);
+  FE_HIP(hipGetLastError());
+}
+void vlm_rope_cache(Ctx& c, const VlmRope& r, const VlmKv& kv, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out) {
+  const int rows = r.B * r.L;
+  FE_CHECK(r.B > 0 && r.L > 0 && r.nh > 0 && r.nkv > 0 && qkv && pos && inv_freq && q_out && kv.k && kv.v, "vlm_rope_cache: %d x %d rows, %d + 2 x %d heads", r.B, r.L,
+           r.nh, r.nkv);
+  FE_CHECK(r.start_dev || (r.start >= 0 && r.start + r.L <= kv.max_seq), "vlm_rope_cache: positions %d .. %d do not fit the cache (%d)", r.start, r.start + r.L - 1,
+           kv.max_seq);
+  FE_CHECK(kv.format != FE_VLM_KV_E4M3 || (kv.ks && kv.vs), "vlm_rope_cache: an e4m3 cache without scales");
+  FE_CHECK(!r.qwen3 || (r.qn && r.kn), "vlm_rope_cache: the Qwen3 form takes q / k norm weights");
+  const dim3 grid(vlm_grid((size_t)rows * (r.nh + 2 * r.nkv) * 64, r.max_blocks)), block(256);
+#define VLM_ROPE(F)                                                                                                                                                \
+  do {                                                                                                                                                             \
+    if (r.qwen3)                                                                                                                                                   \
+      hipLaunchKernelGGL(vlm3_qk_rope_cache_kernel<F>, grid, block, 0, c.stream, qkv, pos, inv_freq, r.qn, r.kn, q_out, kv.k, kv.v, rows, r.L, r.nh, r.nkv, r.s1,  \
+                         r.s2, r.start, kv.max_seq, r.start_dev, r.eps, kv.ks, kv.vs);                                                                             \
+    else                                                                                                                                                           \
+      hipLaunchKernelGGL(vlm_rope_cache_kernel<F>, grid, block, 0, c.stream, qkv, pos, inv_freq, q_out, kv.k, kv.v, rows, r.L, r.nh, r.nkv, r.s0, r.s1, r.start,   \
+                         kv.max_seq, r.start_dev, kv.ks, kv.vs);                                                                                                   \
+  } while (0)
+  if (kv.format == FE_VLM_KV_BF16) VLM_ROPE(FE_VLM_KV_BF16);
+  else if (kv.format == FE_VLM_KV_E4M3) VLM_ROPE(FE_VLM_KV_E4M3);
+  else VLM_ROPE(FE_VLM_KV_BF16_E4M3);
+#undef VLM_ROPE
   FE_HIP(hipGetLastError());
 }
 void vlm_put_rows(Ctx& c, bf16* x, const bf16* rows, const int* index, int n, int d) {
@@ -1485,11 +1535,8 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   // (few rows: one 1024-thread workgroup per row - the wave-per-row kernel walks a 3584-wide row in 14 dependent steps, 11 us for 32 rows;
   // with no split sums to take, the finishing pass is x = bf16(x + 0), n = RMSNorm(x) w)
   const bool few_rows = rows <= 64 && d % 4 == 0;
-  if (few_rows)
-    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(rows), dim3(1024), 0, c.stream, (const float*)nullptr, 0, rows, d, (const float*)nullptr, x, (const bf16*)m.layers[0].ln1, n, g.rms_eps,
-                       (const int*)nullptr, (const bf16*)nullptr);
-  else
-    hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, (const bf16*)x, d, (const bf16*)m.layers[0].ln1, n, d, rows, d, g.rms_eps);
+  if (few_rows) vlm_few_rows_rmsnorm(c, x, (const bf16*)m.layers[0].ln1, n, rows, d, g.rms_eps);
+  else vlm_rmsnorm(c, (const bf16*)x, d, (const bf16*)m.layers[0].ln1, n, d, rows, d, g.rms_eps);
   for (size_t li = 0; li < m.layers.size(); ++li) {
     const VlmLayerW& w = m.layers[li];
     vlm_linear(c, w.qkv, (const bf16*)n, d, rows, qkv, qkvd);
@@ -1498,24 +1545,16 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
     // Decode steps (L == 1) quantise in the rope kernel itself: no launch is added to a step.
     VlmKv kv{m.kv_format, m.kcache[li], m.vcache[li], f8kv ? m.kscale[li] : (float*)nullptr, f8kv ? m.vscale[li] : (float*)nullptr, m.max_seq};
     const bool staged = pk != nullptr;
-    bf16* const rk = staged ? pk : kv.k;
-    bf16* const rv = staged ? pv : kv.v;
-    const int rseq = staged ? L : m.max_seq;
-    const dim3 rgrid(grid_n((size_t)rows * (nh + 2 * nkv) * 64)), rblock(256);
-    const int* const rlen = L == 1 ? len_dev : (const int*)nullptr;
-#define VLM_ROPE(F)                                                                                                                                                \
-  do {                                                                                                                                                             \
-    if (g.qwen3)                                                                                                                                                   \
-      hipLaunchKernelGGL(vlm3_qk_rope_cache_kernel<F>, rgrid, rblock, 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, (const bf16*)w.qn,             \
-                         (const bf16*)w.kn, qr, rk, rv, rows, L, nh, nkv, g.mrope[1], g.mrope[2], start, rseq, rlen, g.rms_eps, kv.ks, kv.vs);                   \
-    else                                                                                                                                                           \
-      hipLaunchKernelGGL(vlm_rope_cache_kernel<F>, rgrid, rblock, 0, c.stream, (const bf16*)qkv, pos, (const float*)m.inv_freq, qr, rk, rv, rows, L, nh, nkv,      \
-                         g.mrope[0], g.mrope[1], start, rseq, rlen, kv.ks, kv.vs);                                                                                 \
-  } while (0)
-    if (staged || m.kv_format == FE_VLM_KV_BF16) VLM_ROPE(FE_VLM_KV_BF16);
-    else if (m.kv_format == FE_VLM_KV_E4M3) VLM_ROPE(FE_VLM_KV_E4M3);
-    else VLM_ROPE(FE_VLM_KV_BF16_E4M3);
-#undef VLM_ROPE
+    const VlmKv rkv = staged ? VlmKv{FE_VLM_KV_BF16, pk, pv, nullptr, nullptr, L} : kv;
+    bf16* const rk = rkv.k;
+    bf16* const rv = rkv.v;
+    const int rseq = rkv.max_seq;
+    VlmRope rope;
+    rope.qwen3 = g.qwen3; rope.qn = (const bf16*)w.qn; rope.kn = (const bf16*)w.kn; rope.eps = g.rms_eps;
+    rope.s0 = g.mrope[0]; rope.s1 = g.mrope[1]; rope.s2 = g.mrope[2];
+    rope.B = B; rope.L = L; rope.nh = nh; rope.nkv = nkv;
+    rope.start = start; rope.start_dev = L == 1 ? len_dev : (const int*)nullptr;
+    vlm_rope_cache(c, rope, rkv, (const bf16*)qkv, pos, (const float*)m.inv_freq, qr);
     if (L == 1) {
       vlm_decode_attention(c, kv, (const bf16*)qr, B, nh, nkv, Lk, len_dev, (const int*)m.pad, po, pm, pl, nsplit, ao);
     } else {
@@ -1542,27 +1581,20 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
       continue;
     }
     vlm_linear(c, w.o, (const bf16*)ao, qd, rows, br, d);
-    hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<false>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, (const bf16*)w.ln2, n, rows, d, g.rms_eps,
-                       (const int*)nullptr, (const bf16*)nullptr);
+    vlm_add_rmsnorm(c, x, (const bf16*)br, (const bf16*)w.ln2, n, rows, d, g.rms_eps);
     vlm_linear(c, w.gate, (const bf16*)n, d, rows, gg, m.inter);
     vlm_linear(c, w.up, (const bf16*)n, d, rows, uu, m.inter);
-    hipLaunchKernelGGL(vlm_silu_mul_kernel, dim3(grid_n((size_t)rows * m.inter / 4)), dim3(256), 0, c.stream, (const bf16*)gg, (const bf16*)uu, gg, (size_t)rows * m.inter / 4);
+    vlm_silu_mul(c, (const bf16*)gg, (const bf16*)uu, gg, (size_t)rows * m.inter);
     vlm_linear(c, w.down, (const bf16*)gg, m.inter, rows, br, d);
     // x += down(...) and, in the same launch, the next layer's input norm (none after the last layer)
-    if (ds) hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<true>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps, m.ds_slot, ds);
-    else hipLaunchKernelGGL(vlm_add_rmsnorm_kernel<false>, dim3(grid_n((size_t)rows * 64)), dim3(256), 0, c.stream, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps,
-                            (const int*)nullptr, (const bf16*)nullptr);
-    FE_HIP(hipGetLastError());
+    vlm_add_rmsnorm(c, x, (const bf16*)br, next_ln, n, rows, d, g.rms_eps, ds ? m.ds_slot : (const int*)nullptr, ds);
   }
   // final norm + lm_head on the last position of every sequence
   bf16* last = c.arena.array<bf16>((size_t)B * d);
   bf16* lastn = c.arena.array<bf16>((size_t)B * d);
   hipLaunchKernelGGL(vlm_last_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, c.stream, (const bf16*)x, last, B, L, d);
-  if (B <= 64 && d % 4 == 0)
-    hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel<false>, dim3(B), dim3(1024), 0, c.stream, (const float*)nullptr, 0, B, d, (const float*)nullptr, last, (const bf16*)m.norm, lastn, g.rms_eps,
-                       (const int*)nullptr, (const bf16*)nullptr);
-  else
-    hipLaunchKernelGGL(vlm_rmsnorm_kernel, dim3(grid_n((size_t)B * 64)), dim3(256), 0, c.stream, (const bf16*)last, d, (const bf16*)m.norm, lastn, d, B, d, g.rms_eps);
+  if (B <= 64 && d % 4 == 0) vlm_few_rows_rmsnorm(c, last, (const bf16*)m.norm, lastn, B, d, g.rms_eps);
+  else vlm_rmsnorm(c, (const bf16*)last, d, (const bf16*)m.norm, lastn, d, B, d, g.rms_eps);
   float* lg = logits_dev ? logits_dev : c.arena.array<float>((size_t)B * m.vocab);
   vlm_logits(c, m.lm_head, (const bf16*)lastn, d, B, lg, m.vocab);      // (scratch: rewound below)
   vlm_select(c, lg, B, m.vocab, next_dev, lp_dev);

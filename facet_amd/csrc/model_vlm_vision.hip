@@ -168,9 +168,9 @@ float* vlm_vis_inv_freq(DeviceWeights& dw, int hd) {
   for (int i = 0; i < hd / 4; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)(hd / 2));
   return dw.upload(inv);
 }
-void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads) {
+void vlm_vis_rope(Ctx& c, int hd, const bf16* qkv, const int* pos, const float* inv_freq, bf16* q_out, bf16* k_out, int rows, int heads, int max_blocks) {
   vis_check_hd(hd);
-  const dim3 grid(grid_n((size_t)rows * 2 * heads * (hd / 2)));
+  const dim3 grid(vlm_grid((size_t)rows * 2 * heads * (hd / 2), max_blocks));
   if (hd == 80) hipLaunchKernelGGL(vlm_vis_rope_kernel<80>, grid, dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads);
   else hipLaunchKernelGGL(vlm_vis_rope_kernel<64>, grid, dim3(256), 0, c.stream, qkv, pos, inv_freq, q_out, k_out, rows, heads);
   FE_HIP(hipGetLastError());

@@ -321,6 +321,37 @@ int fe_op_vlm_decode_attention(fe_ctx* ctx, const float* q, const float* k, cons
 int fe_op_vlm_linear(fe_ctx* ctx, const float* x, int M, int ldx, const float* w, const float* bias, int N, int K, int weight_format, const float* w2,
                      const float* xres, const float* g, float eps, const int32_t* slot, const float* ds, int n_ds, int route, int kernel, float* y,
                      float* y2, int32_t* info);
+/* Test hooks of the VLM decoders' row passes, launched alone (no model) through the functions vlm_forward launches them with. fp32 inputs are
+ * rounded to bf16 on the device; fp32 outputs hold bf16 values. max_blocks (all three): 0 = the launch of production, else at most that
+ * many 256-thread workgroups, so the later trips of the grid-stride loops run at small shapes.
+ *
+ * fe_op_vlm_rope_cache: rotary embedding of the q and k heads + the KV-cache append. qkv [B * L][(nh + 2 nkv) * 128], pos [3][B * L],
+ * inv_freq [64]. family 0: Qwen2.5-VL, chunked sections (sa, sb, 64 - sa - sb) over (temporal, height, width); family 1: Qwen3-VL, q / k
+ * RMSNorm with qn / kn [128] and eps, then the interleaved form where frequency j takes the height position if j % 3 == 1 and j < 3 sa, the
+ * width position if j % 3 == 2 and j < 3 sb. The caches [B][nkv][max_seq][128] (and, FE_VLM_KV_E4M3, both scale arrays [B][nkv][max_seq])
+ * are filled with the byte `fill` first; rows start .. start + L - 1 are then written (start_from_device: the kernel reads start from a
+ * device word, as a replayed decode graph has it). Out: q_out [B * L][nh * 128]; k_raw / v_raw the WHOLE caches as stored - bf16 bit
+ * patterns (2 bytes per value) or e4m3 codes (1 byte); k_scale / v_scale the whole scale arrays (FE_VLM_KV_E4M3 only, else ignored).
+ *
+ * fe_op_vlm_rows, rows of d values (d % 4 == 0), route:
+ *   0  rmsnorm           out_n [rows][ldy] = RMSNorm(x [rows][ldx], eps) * w [d]; columns d .. ldy - 1 keep the value 768
+ *   1  add               out_x [rows][d] = bf16(x + y)
+ *   2  add_rmsnorm       out_x = bf16(x + y), out_n = RMSNorm(out_x, eps) * w
+ *   3  add_rmsnorm, w == NULL (the last layer's form): out_x only
+ *   4  add_rmsnorm with the DeepStack sum: rows with slot [rows] >= 0 take out_x = bf16(bf16(x + y) + ds [n_ds][d] row slot) first
+ *   5  few_rows_rmsnorm  the one-workgroup-per-row form of rows <= 64: out_x = x, out_n = RMSNorm(x, eps) * w
+ *   6  silu_mul          out_x = bf16(bf16(silu(x)) * y); alias != 0: written over the gate's own buffer, as vlm_forward calls it
+ * ldx = ldy = d except for route 0. Unused inputs and outputs may be NULL.
+ *
+ * fe_op_vlm_vis_rope: the 2-D rotary embedding of the vision towers. qkv [rows][3 * heads * hd], hd 64 or 80, pos [rows][2] (row, column),
+ * inv_freq [hd / 4] -> q_out, k_out [rows][heads * hd]. */
+int fe_op_vlm_rope_cache(fe_ctx* ctx, const float* qkv, const int32_t* pos, const float* inv_freq, int family, const float* qn, const float* kn, float eps,
+                         int sa, int sb, int B, int L, int nh, int nkv, int start, int start_from_device, int max_seq, int kv_format, int max_blocks, int fill,
+                         float* q_out, uint8_t* k_raw, uint8_t* v_raw, float* k_scale, float* v_scale);
+int fe_op_vlm_rows(fe_ctx* ctx, int route, const float* x, const float* y, const float* w, const int32_t* slot, const float* ds, int n_ds, int rows, int d,
+                   int ldx, int ldy, float eps, int alias, int max_blocks, float* out_x, float* out_n);
+int fe_op_vlm_vis_rope(fe_ctx* ctx, const float* qkv, const int32_t* pos, const float* inv_freq, int hd, int rows, int heads, int max_blocks, float* q_out,
+                       float* k_out);
 
 /* developer hook: force a tile variant of the contraction kernel for every later launch (0 = automatic choice) */
 int fe_set_conv_variant(fe_ctx* ctx, int variant);
