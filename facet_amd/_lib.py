@@ -27,7 +27,8 @@ PRECISION = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16":
              "bf16+r32": 1 | FE_PRECISION_RES32, "f16+r32": 2 | FE_PRECISION_RES32, "f16x3": 2 | FE_PRECISION_RES32 | FE_PRECISION_SPLIT3}
 PRECISION_NAME = {0: "f32", 1: "bf16", 2: "f16", 1 | FE_PRECISION_RES32: "bf16+r32", 2 | FE_PRECISION_RES32: "f16+r32",
                   2 | FE_PRECISION_RES32 | FE_PRECISION_SPLIT3: "f16x3"}
-ACT = {"none": 0, None: 0, "relu": 1, "gelu": 2, "sigmoid": 3, "softplus": 5}
+ACT = {"none": 0, None: 0, "relu": 1, "gelu": 2, "sigmoid": 3, "softplus": 5, "quickgelu": 6}
+ELEM = {"f32": 0, "bf16": 1, "f16": 2}      # FE_ELEM_*
 
 
 VLM_WEIGHT_FORMATS = {"bf16": 0, "fp8": 1}      # FE_VLM_WEIGHTS_BF16 / FE_VLM_WEIGHTS_E4M3
@@ -96,6 +97,10 @@ SIGNATURES = {
     "fe_op_adaptive_avgpool": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _f32p]),
     "fe_op_layernorm": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_float, _f32p]),
+    "fe_op_plane": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _f32p] + [C.c_int] * 14 + [C.c_float, C.c_float, _f32p]),
+    "fe_op_rowpass": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p] + [C.c_int] * 6 + [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, _f32p]),
+    "fe_op_gemm_skinny": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_int,
+                                    C.c_int, C.c_float, _f32p]),
     "fe_op_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "fe_op_mha": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                             C.c_int, _f32p]),
@@ -559,6 +564,67 @@ class Engine:
         rows, d = x.shape
         y = np.empty_like(x)
         self._ck(self.lib.fe_op_layernorm(self.h, xp, rows, d, gp, bp, eps, y.ctypes.data_as(_f32p)))
+        return y
+
+    PLANE_ROUTES = {"maxpool": 0, "bilinear": 1, "adaptive_avgpool": 2}
+
+    def plane(self, route, x, elem="f32", ho=None, wo=None, k=0, stride=0, pad=0, ceil_mode=False, ctot_in=None, c0_in=0, ctot_out=None, c0_out=0,
+              poison=3e4, fill=-7.0):
+        """A pooling / resampling kernel launched alone on element type `elem` (fe_op_plane): x [n, c, h, w] sits at channels c0_in .. of a
+        device tensor of ctot_in channels (the others hold `poison`), the result is written to channels c0_out .. of a tensor of ctot_out
+        channels prefilled with `fill` -> that WHOLE tensor [n, ctot_out, ho, wo]. "maxpool" takes k, stride, pad, ceil_mode (ho / wo
+        default to torch's output size), the other two ho and wo."""
+        x, xp = _f32(x)
+        n, c, h, w = x.shape
+        if route == "maxpool":
+            def od(i):
+                o = (-(-(i + 2 * pad - k) // stride) if ceil_mode else (i + 2 * pad - k) // stride) + 1
+                return o - 1 if ceil_mode and (o - 1) * stride >= i + pad else o
+            ho, wo = od(h) if ho is None else ho, od(w) if wo is None else wo
+        ctot_in = c0_in + c if ctot_in is None else int(ctot_in)
+        ctot_out = c0_out + c if ctot_out is None else int(ctot_out)
+        y = np.empty((n, ctot_out, int(ho), int(wo)), np.float32)
+        self._ck(self.lib.fe_op_plane(self.h, self.PLANE_ROUTES[route], ELEM[elem], xp, n, c, h, w, ctot_in, int(c0_in), ctot_out, int(c0_out), int(k), int(stride),
+                                      int(pad), int(bool(ceil_mode)), int(ho), int(wo), float(poison), float(fill), y.ctypes.data_as(_f32p)))
+        return y
+
+    ROWPASS_ROUTES = {"layernorm": 0, "layernorm_split": 1, "softmax_rows": 2, "softmax_rows_pad": 3, "add_rows_bcast": 4, "split_hi_lo": 5, "convert": 6}
+
+    def rowpass(self, route, x, d=None, elem_in="f32", elem_out=None, g=None, b=None, ldy=None, eps=1e-5, off_x=0, off_y=None, off_gb=0, fill=-7.0):
+        """A row kernel launched alone on explicit element types (fe_op_rowpass): x [rows, ldx] whole (d <= ldx values a row are used),
+        -> the WHOLE output [rows, ldy]. "layernorm" / "layernorm_split": g, b [d]; "add_rows_bcast": g = pos [L, d]; the in-place routes
+        ("softmax_rows", "softmax_rows_pad", "add_rows_bcast") run on a copy of x, the others write a buffer prefilled with `fill`.
+        off_x / off_y / off_gb: elements added to the device base of x / the output / g and b (0 .. 3)."""
+        r = self.ROWPASS_ROUTES[route]
+        x, xp = _f32(x)
+        rows, ldx = x.shape
+        d = ldx if d is None else int(d)
+        in_place = route in ("softmax_rows", "softmax_rows_pad", "add_rows_bcast")
+        elem_out = elem_in if elem_out is None else elem_out
+        ldy = (ldx if in_place else 2 * d if route in ("layernorm_split", "split_hi_lo") else d) if ldy is None else int(ldy)
+        off_y = off_x if off_y is None else int(off_y)
+        null = C.cast(None, _f32p)
+        (g, gp), (b, bp) = ((None, null) if g is None else _f32(g)), ((None, null) if b is None else _f32(b))
+        L = g.shape[0] if route == "add_rows_bcast" else 0
+        assert g is None or g.shape == ((L, d) if L else (d,)), g.shape
+        assert b is None or b.shape == (d,), b.shape
+        y = np.empty((rows, ldy), np.float32)
+        self._ck(self.lib.fe_op_rowpass(self.h, r, ELEM[elem_in], ELEM[elem_out], xp, rows, d, ldx, ldy, int(off_x), off_y, gp, bp, int(off_gb), L, float(eps),
+                                        float(fill), y.ctypes.data_as(_f32p)))
+        return y
+
+    def gemm_skinny(self, x, w, K, types=("f32", "f32", "f32"), scale=None, shift=None, act=None, ldy=None, fill=-7.0):
+        """The skinny GEMM launched alone (fe_op_gemm_skinny): x [M, ldx], w [N, ldw], the first K columns of both are contracted; types =
+        (activations, weights, output) -> the WHOLE output [M, ldy] (columns >= N keep `fill`)."""
+        (x, xp), (w, wp) = _f32(x), _f32(w)
+        (M, ldx), (N, ldw) = x.shape, w.shape
+        ldy = N if ldy is None else int(ldy)
+        null = C.cast(None, _f32p)
+        (scale, sp), (shift, hp) = ((None, null) if scale is None else _f32(scale)), ((None, null) if shift is None else _f32(shift))
+        assert (scale is None or scale.shape == (N,)) and (shift is None or shift.shape == (N,))
+        y = np.empty((M, ldy), np.float32)
+        self._ck(self.lib.fe_op_gemm_skinny(self.h, ELEM[types[0]], ELEM[types[1]], ELEM[types[2]], xp, M, int(K), ldx, wp, N, ldw, sp, hp, ACT[act], ldy,
+                                            float(fill), y.ctypes.data_as(_f32p)))
         return y
 
     def attention(self, q, k, v, bv=None, causal=False, form=0):

@@ -2,6 +2,73 @@
 #include "capi_internal.h"
 #include "fp8_core.h"
 
+// ---- staging of the element-typed test hooks (fe_op_plane, fe_op_rowpass, fe_op_gemm_skinny) ---------------------------------------------
+// n host floats -> n values of type E in the arena, rounded on the device; the array starts `off` elements past a 256-byte boundary
+template <class E>
+static E* hook_up(Ctx& C, const float* src, size_t n, int off = 0) {
+  if (!src) return nullptr;
+  if constexpr (std::is_same_v<E, float>) {
+    float* d = C.arena.array<float>(n + off) + off;
+    FE_HIP(hipMemcpyAsync(d, src, n * sizeof(float), hipMemcpyHostToDevice, C.stream));
+    return d;
+  } else {
+    const float* d32 = upload(C, src, n);
+    E* d = C.arena.array<E>(n + off) + off;
+    launch_convert(d32, d, n, C.stream);
+    return d;
+  }
+}
+// n values of `fill`, placed the same way
+template <class E>
+static E* hook_filled(Ctx& C, size_t n, float fill, int off = 0) {
+  const std::vector<float> v(n, fill);
+  E* d = hook_up<E>(C, v.data(), n, off);
+  FE_HIP(hipStreamSynchronize(C.stream));      // (v dies with this block)
+  return d;
+}
+// n values of type E in device memory -> host floats (synchronises)
+template <class E>
+static void hook_down(Ctx& C, const E* src, size_t n, float* dst) {
+  const float* d32;
+  if constexpr (std::is_same_v<E, float>) {
+    d32 = src;
+  } else {
+    float* t = C.arena.array<float>(n);
+    launch_convert(src, t, n, C.stream);
+    d32 = t;
+  }
+  FE_HIP(hipMemcpyAsync(dst, d32, n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));
+}
+template <class TI, class TO>
+static void hook_layernorm(Ctx& C, const float* x, int rows, int d, int ldx, int ldy, int off_x, int off_y, const float* g, const float* b, int off_gb,
+                           float eps, float fill, float* y) {
+  const size_t ny = (size_t)rows * ldy;
+  const TI* dx = hook_up<TI>(C, x, (size_t)rows * ldx, off_x);
+  TO* dy = hook_filled<TO>(C, ny, fill, off_y);
+  const float *dg = hook_up<float>(C, g, (size_t)d, off_gb), *db = hook_up<float>(C, b, (size_t)d, off_gb);
+  launch_layernorm(dx, ldx, dy, ldy, dg, db, rows, d, eps, C.stream);
+  hook_down(C, dy, ny, y);
+}
+template <class TI, class TO>
+static void hook_convert(Ctx& C, const float* x, size_t n, float fill, float* y) {
+  const TI* dx = hook_up<TI>(C, x, n);
+  TO* dy = hook_filled<TO>(C, n, fill);
+  launch_convert(dx, dy, n, C.stream);
+  hook_down(C, dy, n, y);
+}
+template <class TI, class TW, class TO>
+static void hook_gemm_skinny(Ctx& C, const float* x, int M, int K, int ldx, const float* w, int N, int ldw, const float* scale, const float* shift, int act,
+                             int ldy, float fill, float* y) {
+  const size_t ny = (size_t)M * ldy;
+  const TI* dx = hook_up<TI>(C, x, (size_t)M * ldx);
+  const TW* dw = hook_up<TW>(C, w, (size_t)N * ldw);
+  const float *ds = hook_up<float>(C, scale, (size_t)N), *dh = hook_up<float>(C, shift, (size_t)N);
+  TO* dy = hook_filled<TO>(C, ny, fill);
+  launch_gemm_skinny(dx, ldx, dw, ldw, ds, dh, dy, ldy, M, N, K, act, C.stream);
+  hook_down(C, dy, ny, y);
+}
+
 extern "C" {
 
 int fe_op_conv2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const float* weight, int cout, int kh, int kw,
@@ -169,6 +236,133 @@ int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g
     launch_layernorm(dx, d, dy, d, dg, db, rows, d, eps, C.stream);
     FE_HIP(hipMemcpyAsync(y, dy, n * sizeof(float), hipMemcpyDeviceToHost, C.stream));
     FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+// ---- test hooks of kernels_misc.hip on explicit element types (independent of the context's precision): upload, launch, download ----------
+int fe_op_plane(fe_ctx* ctx, int route, int elem, const float* x, int n, int c, int h, int w, int ctot_in, int c0_in, int ctot_out, int c0_out,
+                int k, int stride, int pad, int ceil_mode, int ho, int wo, float poison, float fill, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    enum { MAXPOOL = 0, BILINEAR = 1, AVGPOOL = 2 };
+    FE_CHECK(x && y && route >= MAXPOOL && route <= AVGPOOL && n > 0 && c > 0 && h > 0 && w > 0 && ho > 0 && wo > 0, "bad plane arguments");
+    FE_CHECK(c0_in >= 0 && c0_in + c <= ctot_in && c0_out >= 0 && c0_out + c <= ctot_out, "fe_op_plane: channels %d + %d of %d, %d + %d of %d", c0_in, c, ctot_in,
+             c0_out, c, ctot_out);
+    FE_CHECK((size_t)n * ctot_in * h * w <= (1u << 24) && (size_t)n * ctot_out * ho * wo <= (1u << 24), "fe_op_plane: up to 2^24 values a tensor");
+    if (route == MAXPOOL) {
+      FE_CHECK(k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k, "fe_op_plane: max pool k %d stride %d pad %d", k, stride, pad);
+      auto od = [&](int in) {
+        int o = ceil_mode ? (in + 2 * pad - k + stride - 1) / stride + 1 : (in + 2 * pad - k) / stride + 1;
+        if (ceil_mode && (o - 1) * stride >= in + pad) --o;
+        return o;
+      };
+      FE_CHECK(ho == od(h) && wo == od(w), "fe_op_plane: max pool output %d x %d, expected %d x %d", ho, wo, od(h), od(w));
+    }
+    C.arena.reset();
+    const size_t hw = (size_t)h * w;
+    std::vector<float> xin((size_t)n * ctot_in * hw, poison);
+    const std::vector<float> yin((size_t)n * ctot_out * ho * wo, fill);
+    for (int img = 0; img < n; ++img)
+      for (int ch = 0; ch < c; ++ch) memcpy(&xin[((size_t)img * ctot_in + c0_in + ch) * hw], x + ((size_t)img * c + ch) * hw, hw * sizeof(float));
+    auto run = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> E;
+      const TensorT<E> xt = upload_nchw<E>(C, xin.data(), n, ctot_in, h, w, ctot_in);
+      const TensorT<E> yt = upload_nchw<E>(C, yin.data(), n, ctot_out, ho, wo, ctot_out);
+      const TensorT<E> xv = xt.slice(c0_in, c), yv = yt.slice(c0_out, c);
+      if (route == MAXPOOL) launch_maxpool(xv, yv, k, stride, pad, C.stream);
+      else if (route == BILINEAR) launch_bilinear(xv, yv, C.stream);
+      else launch_adaptive_avgpool(xv, yv, C.stream);
+      download_nchw(C, yt, ctot_out, y);
+    };
+    if (elem == FE_ELEM_F32) run((float*)nullptr);
+    else if (elem == FE_ELEM_BF16) run((bf16*)nullptr);
+    else if (elem == FE_ELEM_F16) run((f16*)nullptr);
+    else FE_CHECK(false, "fe_op_plane: element type %d", elem);
+  });
+}
+
+int fe_op_rowpass(fe_ctx* ctx, int route, int elem_in, int elem_out, const float* x, int rows, int d, int ldx, int ldy, int off_x, int off_y,
+                  const float* g, const float* b, int off_gb, int L, float eps, float fill, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    enum { LAYERNORM = 0, LAYERNORM_SPLIT = 1, SOFTMAX = 2, SOFTMAX_PAD = 3, ADD_ROWS = 4, SPLIT_HI_LO = 5, CONVERT = 6 };
+    const int F = FE_ELEM_F32, B = FE_ELEM_BF16, H = FE_ELEM_F16;
+    FE_CHECK(x && y && route >= LAYERNORM && route <= CONVERT && rows > 0 && d > 0 && ldx >= d && ldy >= d, "bad rowpass arguments");
+    FE_CHECK((size_t)rows * ldx <= (1u << 24) && (size_t)rows * ldy <= (1u << 24), "fe_op_rowpass: up to 2^24 values an array");
+    FE_CHECK(off_x >= 0 && off_x <= 3 && off_y >= 0 && off_y <= 3 && off_gb >= 0 && off_gb <= 3, "fe_op_rowpass: offsets %d, %d, %d (0 .. 3)", off_x, off_y, off_gb);
+    const bool in_place = route == SOFTMAX || route == SOFTMAX_PAD || route == ADD_ROWS;
+    FE_CHECK(!in_place || (ldy == ldx && off_y == off_x && elem_in == elem_out), "fe_op_rowpass: route %d runs in place (one stride, offset and type)", route);
+    FE_CHECK((route == LAYERNORM || route == LAYERNORM_SPLIT) ? (g && b) : route == ADD_ROWS ? (g && !b && L > 0) : (!g && !b), "fe_op_rowpass: g / b of route %d", route);
+    auto pair = [&](int a, int o) { return elem_in == a && elem_out == o; };
+    const size_t nx = (size_t)rows * ldx, ny = (size_t)rows * ldy;
+    C.arena.reset();
+    if (route == LAYERNORM) {
+      if (pair(F, F)) hook_layernorm<float, float>(C, x, rows, d, ldx, ldy, off_x, off_y, g, b, off_gb, eps, fill, y);
+      else if (pair(B, B)) hook_layernorm<bf16, bf16>(C, x, rows, d, ldx, ldy, off_x, off_y, g, b, off_gb, eps, fill, y);
+      else if (pair(H, H)) hook_layernorm<f16, f16>(C, x, rows, d, ldx, ldy, off_x, off_y, g, b, off_gb, eps, fill, y);
+      else if (pair(F, B)) hook_layernorm<float, bf16>(C, x, rows, d, ldx, ldy, off_x, off_y, g, b, off_gb, eps, fill, y);
+      else if (pair(F, H)) hook_layernorm<float, f16>(C, x, rows, d, ldx, ldy, off_x, off_y, g, b, off_gb, eps, fill, y);
+      else FE_CHECK(false, "fe_op_rowpass: no LayerNorm from element type %d to %d", elem_in, elem_out);
+    } else if (route == LAYERNORM_SPLIT) {
+      FE_CHECK(pair(F, H) && ldy >= 2 * d, "fe_op_rowpass: layernorm_split is f32 -> f16 with ldy >= 2 d");
+      const float* dx = hook_up<float>(C, x, nx, off_x);
+      f16* dy = hook_filled<f16>(C, ny, fill, off_y);
+      const float *dg = hook_up<float>(C, g, (size_t)d, off_gb), *db = hook_up<float>(C, b, (size_t)d, off_gb);
+      launch_layernorm_split(dx, ldx, dy, ldy, dg, db, rows, d, eps, C.stream);
+      hook_down(C, dy, ny, y);
+    } else if (route == SOFTMAX || route == SOFTMAX_PAD) {
+      FE_CHECK(pair(F, F), "fe_op_rowpass: the softmax kernels are fp32");
+      float* dy = hook_up<float>(C, x, nx, off_x);
+      if (route == SOFTMAX) launch_softmax_rows(dy, ldx, rows, d, C.stream);
+      else launch_softmax_rows_pad(dy, ldx, rows, d, C.stream);
+      hook_down(C, dy, nx, y);
+    } else if (route == ADD_ROWS) {
+      const float* dpos = hook_up<float>(C, g, (size_t)L * d, off_gb);
+      auto run = [&](auto* tag) {
+        typedef std::remove_pointer_t<decltype(tag)> E;
+        E* dy = hook_up<E>(C, x, nx, off_x);
+        launch_add_rows_bcast(dy, ldx, dpos, rows, L, d, C.stream);
+        hook_down(C, dy, nx, y);
+      };
+      if (elem_in == F) run((float*)nullptr);
+      else if (elem_in == B) run((bf16*)nullptr);
+      else if (elem_in == H) run((f16*)nullptr);
+      else FE_CHECK(false, "fe_op_rowpass: element type %d", elem_in);
+    } else if (route == SPLIT_HI_LO) {
+      FE_CHECK(pair(F, H) && ldx == d && ldy == 2 * d && off_x == 0 && off_y == 0, "fe_op_rowpass: split_hi_lo is dense f32 [rows][d] -> f16 [rows][2 d]");
+      const float* dx = hook_up<float>(C, x, nx);
+      f16* dy = hook_filled<f16>(C, ny, fill);
+      launch_split_hi_lo(dx, dy, (size_t)rows, d, C.stream);
+      hook_down(C, dy, ny, y);
+    } else {
+      FE_CHECK(ldx == d && ldy == d && off_x == 0 && off_y == 0, "fe_op_rowpass: convert takes dense arrays");
+      if (pair(F, B)) hook_convert<float, bf16>(C, x, nx, fill, y);
+      else if (pair(B, F)) hook_convert<bf16, float>(C, x, nx, fill, y);
+      else if (pair(F, H)) hook_convert<float, f16>(C, x, nx, fill, y);
+      else if (pair(H, F)) hook_convert<f16, float>(C, x, nx, fill, y);
+      else FE_CHECK(false, "fe_op_rowpass: no conversion from element type %d to %d", elem_in, elem_out);
+    }
+  });
+}
+
+int fe_op_gemm_skinny(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
+                      const float* scale, const float* shift, int act, int ldy, float fill, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    const int F = FE_ELEM_F32, B = FE_ELEM_BF16, H = FE_ELEM_F16;
+    FE_CHECK(x && w && y && M > 0 && M <= 32 && N > 0 && N <= 65536 && K > 0 && K <= 65536 && ldx >= K && ldx <= 2 * K + 64 && ldw >= K && ldw <= 2 * K + 64 && ldy >= N &&
+             ldy <= 2 * N + 64, "bad skinny GEMM arguments");
+    FE_CHECK(act >= ACT_NONE && act <= ACT_QUICKGELU && act != ACT_PRELU, "fe_op_gemm_skinny: activation %d", act);
+    auto is = [&](int a, int b, int c) { return ti == a && tw == b && to == c; };
+    C.arena.reset();
+    if (is(F, F, F)) hook_gemm_skinny<float, float, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(B, B, B)) hook_gemm_skinny<bf16, bf16, bf16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(B, B, F)) hook_gemm_skinny<bf16, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(H, H, H)) hook_gemm_skinny<f16, f16, f16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(H, H, F)) hook_gemm_skinny<f16, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(F, B, F)) hook_gemm_skinny<float, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else if (is(F, H, F)) hook_gemm_skinny<float, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    else FE_CHECK(false, "fe_op_gemm_skinny: no kernel for element types (%d, %d, %d)", ti, tw, to);
   });
 }
 

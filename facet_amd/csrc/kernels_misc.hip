@@ -359,6 +359,11 @@ __global__ void conv_narrow_kernel(const ConvParams p) {
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
   const int HoWo = p.Ho * p.Wo;
+  // weight row of each accumulator: the packed weights hold exactly Cout rows, so the accumulators past Cout (CO = 4 serves Cout 2 and 3)
+  // read the last row again instead of the memory behind it; their sums are never stored
+  size_t wrow[CO];
+#pragma unroll
+  for (int o = 0; o < CO; ++o) wrow[o] = (size_t)(o < p.Cout ? o : p.Cout - 1) * p.ldw;
   for (long long m4 = wave * 4; m4 < p.M; m4 += nwaves * 4) {
     const long long m = m4 + grp;
     const bool mv = m < p.M;
@@ -381,7 +386,7 @@ __global__ void conv_narrow_kernel(const ConvParams p) {
           if (!ok) xv = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
           for (int o = 0; o < CO; ++o) {
-            const float4 wv = *reinterpret_cast<const float4*>(wp + (size_t)o * p.ldw + c);
+            const float4 wv = *reinterpret_cast<const float4*>(wp + wrow[o] + c);
             acc[o] += xv.x * wv.x + xv.y * wv.y + xv.z * wv.z + xv.w * wv.w;
           }
         }
@@ -394,10 +399,8 @@ __global__ void conv_narrow_kernel(const ConvParams p) {
       if (sub == 0 && mv && o < p.Cout) {
         v = v * (p.scale ? p.scale[o] : 1.f) + (p.shift ? p.shift[o] : 0.f);
         if (p.res && !p.res_after_act) v += p.res[(size_t)m * p.ldr + o];
-        if (p.act == ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (p.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-        else if (p.act == ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
-        else if (p.act == ACT_PRELU) v = v > 0.f ? v : v * p.slope[o];
+        if (p.act == ACT_PRELU) v = v > 0.f ? v : v * p.slope[o];
+        else v = fe_apply_act(v, p.act);      // (softplus and quick-GELU included: launch_conv sends every activation here)
         if (p.res && p.res_after_act) v += p.res[(size_t)m * p.ldr + o];
         p.y[(size_t)m * p.ldy + o] = v;
       }

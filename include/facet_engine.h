@@ -282,6 +282,41 @@ int fe_op_maxpool2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int
 int fe_op_bilinear(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_adaptive_avgpool(fe_ctx* ctx, const float* x, int n, int c, int h, int w, int ho, int wo, float* y);
 int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g, const float* b, float eps, float* y);
+/* Test hooks of the pooling, resampling, row and small-GEMM kernels (kernels_misc.hip), launched alone through the launch functions the
+ * models call, on explicit element types (FE_ELEM_*) whatever the context's precision is: fp32 host data is rounded to the element type on
+ * the device, results come back as fp32. Upload, launch and download only.
+ *
+ * fe_op_plane, route 0 maxpool (k, stride, pad, ceil_mode; ho / wo must be torch's output size), 1 bilinear (align_corners = False),
+ * 2 adaptive_avgpool: x [n][c][h][w] is placed at channels c0_in .. c0_in + c - 1 of an NHWC device tensor of ctot_in channels whose other
+ * channels hold `poison`; the kernel writes the view c0_out .. c0_out + c - 1 of a tensor of ctot_out channels prefilled with `fill`.
+ * y [n][ctot_out][ho][wo]: the WHOLE output tensor.
+ *
+ * fe_op_rowpass, rows of d values, route:
+ *   0  layernorm         y [rows][ldy] = LayerNorm(x [rows][ldx], eps) * g [d] + b [d]; (elem_in, elem_out) one of (f32, f32), (bf16, bf16),
+ *                        (f16, f16), (f32, bf16), (f32, f16)
+ *   1  layernorm_split   f32 -> f16, d in {256, 512, 768, 1024}, ldy >= 2 d: columns 0 .. d - 1 the f16 rounding hi of the result, d .. 2 d - 1
+ *                        the rounding lo of (result - hi)
+ *   2  softmax_rows      f32, in place on a copy of x [rows][ldx] (ldy == ldx): columns >= d are left alone
+ *   3  softmax_rows_pad  the same, columns d .. ldx - 1 zeroed
+ *   4  add_rows_bcast    in place on a copy of x [rows][ldx] (elem_in == elem_out, ldy == ldx): row r += g [L][d] row r % L
+ *   5  split_hi_lo       f32 [rows][d] -> f16 [rows][2 d] (ldx == d, ldy == 2 d), hi | lo as route 1
+ *   6  convert           [rows][d] dense (ldx == ldy == d); (f32, bf16), (bf16, f32), (f32, f16), (f16, f32)
+ * x is the whole [rows][ldx] array; the output buffer [rows][ldy] is prefilled with `fill` (routes 0, 1, 5, 6) or is the copy of x, and is
+ * returned whole in y. off_x / off_y (0 .. 3 elements) are added to the device base of x / y and off_gb (0 .. 3 floats) to that of g and b,
+ * which decides the vector or scalar form of a launch. Any other pair of element types is an error.
+ *
+ * fe_op_gemm_skinny: y [M][ldy] (prefilled with `fill`) = act(x [M][ldx] . w [N][ldw]^T * scale [N] + shift [N]) over K columns, M <= 32,
+ * scale / shift nullable; (ti, tw, to) one of (f32, f32, f32), (bf16, bf16, bf16), (bf16, bf16, f32), (f16, f16, f16), (f16, f16, f32),
+ * (f32, bf16, f32), (f32, f16, f32). */
+#define FE_ELEM_F32 0
+#define FE_ELEM_BF16 1
+#define FE_ELEM_F16 2
+int fe_op_plane(fe_ctx* ctx, int route, int elem, const float* x, int n, int c, int h, int w, int ctot_in, int c0_in, int ctot_out, int c0_out,
+                int k, int stride, int pad, int ceil_mode, int ho, int wo, float poison, float fill, float* y);
+int fe_op_rowpass(fe_ctx* ctx, int route, int elem_in, int elem_out, const float* x, int rows, int d, int ldx, int ldy, int off_x, int off_y,
+                  const float* g, const float* b, int off_gb, int L, float eps, float fill, float* y);
+int fe_op_gemm_skinny(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
+                      const float* scale, const float* shift, int act, int ldy, float fill, float* y);
 /* test hook of the fused head_dim-64 attention kernels, launched alone (kernels_attn.hip: fp32, bf16 / f16 and split-f16 policies):
    q [B][Lq][H*64], k / v [B][Lk][H*64], bv [H*64] -> o [B][Lq][H*64] = softmax(q k^T) v + bv per (batch, head), the semantics of
    torch.nn.functional.scaled_dot_product_attention with scale = 1 (q is passed as the kernel receives it: the caller has applied any
