@@ -45,7 +45,9 @@ class EngineCapacityError(EngineError):
     caller's `cap` is too small for an image."""
 
 
+FE_ERR_INVALID = -1
 FE_ERR_CAPACITY = -4
+FE_MIXED_CLIP, FE_MIXED_SAMP = 0, 1      # fe_preprocess224_mixed modes
 
 
 _lib = None
@@ -163,6 +165,8 @@ SIGNATURES = {
                                                C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _f32p]),
     "fe_ensemble_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
                                     C.POINTER(C.c_int)]),
+    "fe_ensemble_score_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, _f32p, C.POINTER(C.c_int)]),
+    "fe_preprocess224_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, _u8p]),
     "fe_u2netp_saliency": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     "fe_samp_forward": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "fe_onnx_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _i64p,
@@ -390,7 +394,9 @@ class Engine:
 
     def _ck(self, rc):
         if rc != 0:
-            raise (EngineCapacityError if rc == FE_ERR_CAPACITY else EngineError)((self.lib.fe_last_error(self.h) or b"?").decode())
+            err = (EngineCapacityError if rc == FE_ERR_CAPACITY else EngineError)((self.lib.fe_last_error(self.h) or b"?").decode())
+            err.status = rc      # the fe_status code (include/facet_engine.h)
+            raise err
 
     # -- misc -------------------------------------------------------------------------------
     def sync(self):
@@ -799,6 +805,42 @@ class Engine:
         mask = C.c_int(0)
         self._ck(self.lib.fe_ensemble_score(self.h, p, n, h, w, dev, rec.ctypes.data_as(_f32p), C.byref(mask)))
         return rec, mask.value
+
+    @staticmethod
+    def _img_list(images):
+        """A list of uint8 [h, w, 3] arrays (host), or (device_pointers, sizes) with sizes [(h, w), ...] -> the pointer array, the int32
+        [n][2] sizes, n, on_device and what must stay alive for the call."""
+        if isinstance(images, tuple):
+            ptrs, sizes = images
+            vals = [p.value if isinstance(p, C.c_void_p) else (None if p is None else int(p)) for p in ptrs]
+            hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(len(vals), 2))
+            return (C.c_void_p * len(vals))(*vals), hw, len(vals), 1, None
+        arrs = []
+        for i, a in enumerate(images):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint8)
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError(f"image {i}: expected [h,w,3], got {a.shape}")
+            arrs.append(a)
+        hw = np.ascontiguousarray(np.array([(0, 0) if a is None else a.shape[:2] for a in arrs], dtype=np.int32).reshape(len(arrs), 2))
+        return (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs]), hw, len(arrs), 0, arrs
+
+    def ensemble_score_mixed(self, images):
+        """ensemble_score for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for
+        resident images. -> (records float32 [n, 789] in input order, models_run bitmask). include/facet_engine.h fe_ensemble_score_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        rec = np.empty((n, FE_RECORD_FLOATS), np.float32)
+        mask = C.c_int(0)
+        self._ck(self.lib.fe_ensemble_score_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, rec.ctypes.data_as(_f32p), C.byref(mask)))
+        return rec, mask.value
+
+    def preprocess224_mixed(self, images, mode):
+        """The 224 x 224 uint8 crops the mixed-size call feeds CLIP (mode 'clip' / 0) or SAMP-Net (mode 'samp' / 1): [n, 224, 224, 3], Pillow's bytes."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        crops = np.empty((n, 224, 224, 3), np.uint8)
+        m = {"clip": FE_MIXED_CLIP, "samp": FE_MIXED_SAMP}.get(mode, mode)
+        self._ck(self.lib.fe_preprocess224_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(m), crops.ctypes.data_as(_u8p)))
+        return crops
 
     def ensemble_select(self, models=7):
         """Which loaded models ensemble_score runs: 1 topiq | 2 clip (+ aesthetic) | 4 samp."""

@@ -22,12 +22,19 @@ Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P +
 fe_face_analyze + fe_roi_laplacian (+ fe_face_thumbnails with `gpu_thumbnails=True`; through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
 fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_subject_region (with `subject_region=True`).
 
+Mixed sizes: `process_images` / `process_files` take a chunk of photos of any sizes. By default the chunk is cut into one process_batch
+per distinct shape. `mixed_sizes=True` uploads the chunk once and scores all of it with ONE fe_ensemble_score_mixed call (CLIP and SAMP
+crops gather across shapes into the towers' usual chunks; TOPIQ runs per shape group inside that call); statistics, faces, lines,
+pHash, thumbnails and the subject region still run per shape group on the resident pixels, and the dicts come back in input order
+with the same keys.
+
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
 context on the same GPU (`aux_engine=`, and build the FaceAnalyzer on it): those calls then run on a worker thread beside
 fe_ensemble_score - ctypes drops the GIL, the hardware queues interleave the two streams - and the step costs max(models, rest)
 instead of their sum. Results are identical to the single-context path (tests/test_batch_gpu.py).
 """
+import ctypes
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -71,7 +78,10 @@ class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
                  aux_engine=None, phash=False, vlm_composition=None, thumbnails=False, thumbnail_size=640, thumbnail_quality=80,
-                 subject_region=False):
+                 subject_region=False, mixed_sizes=False):
+        # process_images / process_files: one fe_ensemble_score_mixed call for the whole chunk instead of one fe_ensemble_score per distinct
+        # shape (module docstring, "Mixed sizes"). Off by default.
+        self.mixed_sizes = mixed_sizes
         # multi-pass placement (multi_pass.py:685-701): get_placement_data(None, w, h, config, img_cv) - the subject box detected from the
         # resident BGR copy (fe_subject_region) is what power_point_score and the rule-based comp_score are computed from, faces or not
         self.subject_region = subject_region
@@ -92,12 +102,14 @@ class BatchScorer:
         self.tag_threshold, self.max_tags = tag_threshold, max_tags           # utils/tags.py:50-51 defaults
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
-    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None):
+    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
         _resident (process_files): (device_ptr, n, h, w) of an RGB batch that is already on the device, handed over - it is freed here -
-        with images_rgb None; the pixels are fetched only when a stage that works on host arrays (face thumbnails cut by Pillow, the VLM analyzer) is on."""
+        with images_rgb None; the pixels are fetched only when a stage that works on host arrays (face thumbnails cut by Pillow, the VLM analyzer) is on.
+        _records (the mixed-size path): (records [n, 789], mask) of these images, computed by the caller - the ensemble call is skipped.
+        _borrowed: the resident batch stays the caller's and is not freed here."""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -143,7 +155,10 @@ class BatchScorer:
                     subjects_ = CompositionAnalyzer.detect_subject_region_batch(eng, bgr_dev)
                 return tech_, faces_, lines_, hashes_, thumbs_, subjects_
 
-            if self._pool is not None:
+            if _records is not None:
+                rec, mask = _records
+                tech, faces, leading_lines, hashes, thumbs, subjects = rest(self.aux_engine if self._pool is not None else e)
+            elif self._pool is not None:
                 fut = self._pool.submit(rest, self.aux_engine)      # fe_swap_rb_u8 has synchronised: the BGR copy is complete
                 try:
                     rec, mask = e.ensemble_score(rgb_dev)
@@ -153,7 +168,8 @@ class BatchScorer:
                 rec, mask = e.ensemble_score(rgb_dev)
                 tech, faces, leading_lines, hashes, thumbs, subjects = rest(e)
         finally:
-            e.dev_free(d_rgb)
+            if not _borrowed:
+                e.dev_free(d_rgb)
             if d_bgr is not None:
                 e.dev_free(d_bgr)
         tags = None
@@ -240,12 +256,68 @@ class BatchScorer:
                 raise ValueError(f"image {i}: expected [h,w,3], got {a.shape}")
             groups.setdefault(a.shape, []).append(i)
         out = [None] * len(arrs)
+        if self.mixed_sizes and arrs:
+            return self._process_images_mixed(arrs, groups, exif, leading_lines)
         for idx in groups.values():
             res = self.process_batch(np.stack([arrs[i] for i in idx]), exif=[exif[i] for i in idx] if exif else None,
                                      leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None)
             for i, r in zip(idx, res):
                 out[i] = r
         return out
+
+    def _process_images_mixed(self, arrs, groups, exif, leading_lines, out=None, index=None):
+        """The chunk goes up once, into one allocation in which every shape group lies back to back (256-byte aligned), and through
+        _process_mixed. index: the callers' indices of arrs (process_files), default 0 .. len(arrs) - 1."""
+        e = self.engine
+        index = list(range(len(arrs))) if index is None else index
+        out = [None] * len(arrs) if out is None else out
+        at, starts = 0, []
+        for (h, w, _), idx in groups.items():
+            starts.append(at)
+            at += -(-(len(idx) * h * w * 3) // 256) * 256
+        d_all = e.dev_alloc(at)
+        try:
+            entries = []
+            for ((h, w, _), idx), a0 in zip(groups.items(), starts):
+                dev = ctypes.c_void_p(d_all.value + a0)
+                e.h2d(dev, np.stack([arrs[i] for i in idx]))
+                entries.append(([index[i] for i in idx], (dev, len(idx), h, w), False))
+            self._process_mixed(entries, out, exif, leading_lines)
+        finally:
+            e.dev_free(d_all)
+        return out
+
+    def _process_mixed(self, entries, out, exif, leading_lines):
+        """entries: [(indices into out, (device_ptr, k, h, w), owned)] - resident RGB batches of one shape each. One ensemble_score_mixed call
+        over every image of every entry, by pointers into the resident batches; then process_batch per entry for the stages that run per
+        shape, with its records handed in. An owned batch is freed by process_batch (or here, when the ensemble call fails)."""
+        e = self.engine
+        order, ptrs, sizes = [], [], []
+        for idx, (p, k, h, w), _ in entries:
+            base = p.value if isinstance(p, ctypes.c_void_p) else int(p)
+            for j, i in enumerate(idx):
+                order.append(i); ptrs.append(base + j * h * w * 3); sizes.append((h, w))
+        by_input = sorted(range(len(order)), key=lambda r: order[r])      # the call sees the images in input order
+        try:
+            rec, mask = e.ensemble_score_mixed(([ptrs[r] for r in by_input], [sizes[r] for r in by_input]))
+        except Exception:
+            for _, dev, owned in entries:
+                if owned:
+                    e.dev_free(dev[0])
+            raise
+        row = {order[r]: q for q, r in enumerate(by_input)}
+        for n_done, (idx, dev, owned) in enumerate(entries):
+            try:
+                res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
+                                         leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev,
+                                         _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned)
+            except Exception:
+                for _, dev2, owned2 in entries[n_done + 1:]:
+                    if owned2:
+                        e.dev_free(dev2[0])
+                raise
+            for i, r in zip(idx, res):
+                out[i] = r
 
     def process_files(self, paths_or_blobs, exif=None, leading_lines=None, progressive=False, parallel_entropy=False):
         """Image FILES (paths, or the files' bytes) instead of decoded arrays: the reference's `_load_images` + batch step. JPEG files the
@@ -259,6 +331,8 @@ class BatchScorer:
         out = [None] * len(blobs)
         e = self.engine
         groups, rest = decode_groups(e, blobs, device=True, progressive=progressive, parallel_entropy=parallel_entropy)
+        if self.mixed_sizes:
+            return self._process_files_mixed(blobs, groups, rest, out, exif, leading_lines)
         for idx, dev in groups:
             res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
                                      leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev)
@@ -272,6 +346,42 @@ class BatchScorer:
                                       leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None)
             for i, r in zip(idx, res):
                 out[i] = r
+        return out
+
+    def _process_files_mixed(self, blobs, groups, rest, out, exif, leading_lines):
+        """process_files with mixed_sizes: the decode groups' resident buffers and one upload of the files Pillow opened go through a single
+        ensemble_score_mixed call."""
+        from .image_loading import pillow_rgb
+        e = self.engine
+        entries = [(idx, dev, True) for idx, dev in groups]
+        arrs = [(i, pillow_rgb(blobs[i])) for i in rest]
+        arrs = [(i, np.ascontiguousarray(a, dtype=np.uint8)) for i, a in arrs if a is not None]
+        d_all = None
+        try:
+            if arrs:
+                shapes = {}
+                for r, (_, a) in enumerate(arrs):
+                    shapes.setdefault(a.shape, []).append(r)
+                at, starts = 0, []
+                for (h, w, _), rs in shapes.items():
+                    starts.append(at)
+                    at += -(-(len(rs) * h * w * 3) // 256) * 256
+                try:
+                    d_all = e.dev_alloc(at)
+                    for ((h, w, _), rs), a0 in zip(shapes.items(), starts):
+                        dev = ctypes.c_void_p(d_all.value + a0)
+                        e.h2d(dev, np.stack([arrs[r][1] for r in rs]))
+                        entries.append(([arrs[r][0] for r in rs], (dev, len(rs), h, w), False))
+                except Exception:
+                    for _, dev, owned in entries:
+                        if owned:
+                            e.dev_free(dev[0])
+                    raise
+            if entries:
+                self._process_mixed(entries, out, exif, leading_lines)
+        finally:
+            if d_all is not None:
+                e.dev_free(d_all)
         return out
 
     @staticmethod

@@ -50,6 +50,7 @@ void fe_destroy(fe_ctx* ctx) {
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->d_out) (void)hipFree(ctx->d_out);
   if (ctx->d_rec) (void)hipFree(ctx->d_rec);
+  if (ctx->mixed_buf) (void)hipFree(ctx->mixed_buf);
   for (int i = 0; i < 2; ++i) {
     if (ctx->stage_buf[i]) (void)hipFree(ctx->stage_buf[i]);
     if (ctx->ev_copied[i]) (void)hipEventDestroy(ctx->ev_copied[i]);

@@ -38,6 +38,8 @@ struct fe_ctx {
   size_t samp_in_cap = 0;
   float* d_rec = nullptr;   // interleaved ensemble records of the host-output entry point
   size_t d_rec_cap = 0;
+  void* mixed_buf = nullptr;   // descriptors and table pool of the mixed-size call on the stack (fe_ensemble_score_mixed,
+  size_t mixed_cap = 0;        // fe_preprocess224_mixed); grows to the largest call, never per image size
   int ensemble_mask = 7;    // models fe_ensemble_score runs when loaded: 1 topiq | 2 clip | 4 samp (fe_ensemble_select)
   // the side lane of ensemble_run: a second stream with an arena of its own, on which the 224^2 models run beside TOPIQ. Created on
   // first use; idle whenever ensemble_run is not on the stack (it joins before it returns)

@@ -1,6 +1,7 @@
 // C ABI: the scoring models - TOPIQ, U2-Net-P + SAMP-Net, CLIP image and text, the aesthetic head, tag similarities, the ensemble.
 #include "capi_internal.h"
 #include "ensemble_plan.h"
+#include "resize_mixed_core.h"
 
 namespace {
 const float kImagenetMean[3] = {0.485f, 0.456f, 0.406f};
@@ -173,6 +174,12 @@ class ClipBatcher {
     C.arena.rewind(mark);
   }
   void compact(int c, int left) { compact_crops(x_->clip_in, per_, c, left, x_->c.stream); }
+  // slots [slot, slot + count) themselves, for a producer that writes the normalised crops in place (the mixed-size preprocessing)
+  float* slots(int slot, int count) {
+    FE_CHECK(hw_ == 224, "clip batcher: in-place crops are 224 x 224");
+    FE_CHECK(slot >= 0 && count > 0 && (size_t)(slot + count) * per_ <= x_->clip_in_cap, "clip batcher: slot %d + %d past the staging buffer", slot, count);
+    return x_->clip_in + (size_t)slot * per_;
+  }
   void push(const Tensor& xt) {
     stage(xt, count_);
     count_ += xt.n;
@@ -229,6 +236,10 @@ class SampBatcher {
     C.arena.rewind(mark);
   }
   void compact(int c, int left) { compact_crops(x_->samp_in, per_, c, left, x_->c.stream); }
+  float* slots(int slot, int count) {
+    FE_CHECK(slot >= 0 && count > 0 && (size_t)(slot + count) * per_ <= x_->samp_in_cap, "samp batcher: slot %d + %d past the staging buffer", slot, count);
+    return x_->samp_in + (size_t)slot * per_;
+  }
   void push(const Tensor& xt) {
     stage(xt, count_);
     count_ += xt.n;
@@ -388,6 +399,251 @@ int ensemble_run(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, int on_de
       case OP_INTERLEAVE: {
         const size_t work = (size_t)n * FE_RECORD_FLOATS;
         hipLaunchKernelGGL(records_interleave_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, lane[LANE_MAIN], d_pl, n4, n, d_rec, ld);
+        FE_HIP(hipGetLastError());
+        break;
+      }
+    }
+  }
+  return (do_topiq ? 1 : 0) | (do_clip ? 2 : 0) | (do_samp ? 4 : 0);
+}
+
+// ---- images of mixed sizes --------------------------------------------------------------------------------------------------------
+// records_interleave_kernel for a mixed call: the planes are in position order, pos [n] = position of input image i.
+__global__ void records_interleave_mixed_kernel(const float* __restrict__ planes, size_t n4, int n, const int32_t* __restrict__ pos,
+                                                float* __restrict__ rec, int ld) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n * FE_RECORD_FLOATS) return;
+  const int img = (int)(i / FE_RECORD_FLOATS), f = (int)(i - (size_t)img * FE_RECORD_FLOATS);
+  const size_t p = (size_t)pos[img];
+  const size_t o_aes = n4, o_pw = 2 * n4, o_at = o_pw + 8 * n4, o_sd = o_at + 6 * n4, o_emb = o_sd + 5 * n4;
+  float v;
+  if (f == 0) v = planes[p];
+  else if (f == 1) v = planes[o_aes + p];
+  else if (f < 10) v = planes[o_pw + p * 8 + (f - 2)];
+  else if (f < 16) v = planes[o_at + p * 6 + (f - 10)];
+  else if (f < 21) v = planes[o_sd + p * 5 + (f - 16)];
+  else v = planes[o_emb + p * 768 + (f - 21)];
+  rec[(size_t)img * ld + f] = v;
+}
+
+// Puts the scoped resize tables into the Ctx for the lifetime of a mixed call
+struct ScopedTables {
+  Ctx& c;
+  ScopedTables(Ctx& ctx, const std::map<std::tuple<int, int, int>, ResizeCoeffsDev>* t) : c(ctx) { c.resize_scoped = t; }
+  ~ScopedTables() { c.resize_scoped = nullptr; }
+};
+
+// Per-image argument checks of the mixed entry points. FE_OK, or FE_ERR_INVALID with the index of the offending image in the message.
+int mixed_check_images(fe_ctx* ctx, const char* what, const uint8_t* const* images, const int32_t* hw, int n, int min_side) {
+  char b[160];
+  if (!images || !hw || n <= 0) { ctx->c.err = std::string(what) + ": bad arguments (null list or n <= 0)"; return FE_ERR_INVALID; }
+  for (int i = 0; i < n; ++i) {
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!images[i]) { snprintf(b, sizeof b, "%s: image %d is a null pointer", what, i); ctx->c.err = b; return FE_ERR_INVALID; }
+    if (h < min_side || w < min_side || (size_t)h * (size_t)w > ((size_t)1 << 28)) {
+      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); each side must be at least %d", what, i, h, w, min_side);
+      ctx->c.err = b;
+      return FE_ERR_INVALID;
+    }
+  }
+  return FE_OK;
+}
+
+// ensemble_run for images of mixed sizes: the same plan over cut_mixed's micro-batches (ensemble_plan.h), the 224^2 crops from the
+// descriptor-driven kernels (resize_mixed_core.h) straight into the batchers' slots. Descriptors, the table pool (LANCZOS tables of
+// TOPIQ's > 1024 cap included) and the position map go up once, into ctx->mixed_buf: nothing is allocated or cached per image size.
+int ensemble_run_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, float* d_rec, int ld) {
+  using namespace fe::plan;
+  Ctx& C = ctx->c;
+  const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
+  const size_t o_aes = n4, o_pw = 2 * n4, o_at = o_pw + 8 * n4, o_sd = o_at + 6 * n4, o_emb = o_sd + 5 * n4,
+               o_feat = o_emb + 768 * n4, total = o_feat + 768 * n4;
+  float* d_pl = ctx->out_buf(total);
+  const int sel = ctx->ensemble_mask;
+  const bool do_topiq = (sel & 1) && C.topiq && C.topiq->has_head, do_clip = (sel & 2) && C.clip, do_samp = (sel & 4) && C.samp && C.u2netp;
+  float* p_topiq = d_pl;  float* p_aes = d_pl + o_aes;  float* p_pw = d_pl + o_pw;  float* p_at = d_pl + o_at;
+  float* p_sd = d_pl + o_sd;  float* p_emb = d_pl + o_emb;  float* d_feat = d_pl + o_feat;
+  std::unique_ptr<ClipBatcher> tower;
+  if (do_clip) tower = std::make_unique<ClipBatcher>(ctx, n, ctx->microbatch, d_feat, p_emb, C.aesthetic ? p_aes : nullptr);
+  std::unique_ptr<SampBatcher> samp;
+  if (do_samp) samp = std::make_unique<SampBatcher>(ctx, n, ctx->microbatch, p_pw, p_at, p_sd);
+
+  // the cuts: positions, micro-batches, and where every image lies inside its micro-batch
+  std::vector<uintptr_t> addr(n);
+  for (int i = 0; i < n; ++i) addr[i] = (uintptr_t)images[i];
+  const MixedCuts mc = cut_mixed(hw, n, ctx->microbatch, do_topiq, on_device ? addr.data() : nullptr);
+  const int chunks = (int)mc.cuts.size();
+  std::vector<int> first(chunks + 1, 0), cut_of(n);
+  std::vector<size_t> off(n), bytes(n);
+  size_t stage_need = 0;
+  for (int k = 0; k < chunks; ++k) {
+    first[k + 1] = first[k] + mc.cuts[k].count;
+    size_t run = 0;
+    for (int p = first[k]; p < first[k + 1]; ++p) {
+      const int i = mc.order[p];
+      cut_of[p] = k; off[p] = run; bytes[p] = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+      run += bytes[p];
+    }
+    if (!on_device || mc.cuts[k].gather) stage_need = std::max(stage_need, run);
+  }
+  if (stage_need) ImageStager::prepare(ctx, stage_need);
+
+  // descriptors per mode in position order, the pool, TOPIQ's LANCZOS tables, the position map: one blob
+  MixedTables tables;
+  std::vector<MixedDesc> desc[2];
+  std::vector<size_t> inter_need[2];
+  std::vector<int> max_nr[2];
+  const bool mode_on[2] = {do_clip, do_samp};
+  size_t max_inter = 0;
+  for (int m = 0; m < 2; ++m) {
+    if (!mode_on[m]) continue;
+    desc[m].resize(n); inter_need[m].assign(chunks, 0); max_nr[m].assign(chunks, 0);
+    for (int p = 0; p < n; ++p) {
+      const int i = mc.order[p], k = cut_of[p];
+      MixedDesc& d = desc[m][p];
+      FE_CHECK(tables.describe(m, hw[2 * i], hw[2 * i + 1], d), "ensemble_score_mixed: image %d (%d x %d) cannot be resampled to 224 x 224", i, hw[2 * i], hw[2 * i + 1]);
+      d.src = on_device ? images[i] : (const uint8_t*)ctx->stage_buf[k & 1] + off[p];
+      d.slot = p - first[k];
+      FE_CHECK(inter_need[m][k] + MixedTables::inter_bytes(d) < ((size_t)1 << 32), "ensemble_score_mixed: intermediates of a micro-batch exceed 4 GiB");
+      d.inter = (uint32_t)inter_need[m][k];
+      inter_need[m][k] += MixedTables::inter_bytes(d);
+      if (d.ksize_h) max_nr[m][k] = std::max(max_nr[m][k], (int)d.nr);
+      max_inter = std::max(max_inter, inter_need[m][k]);
+    }
+  }
+  struct Lz { std::tuple<int, int, int> key; size_t kk, bounds; int ksize; };
+  std::vector<Lz> lz;
+  if (do_topiq) {
+    std::map<std::tuple<int, int, int>, int> have;
+    for (int k = 0; k < chunks; ++k) {
+      const int i = mc.order[first[k]], h = hw[2 * i], w = hw[2 * i + 1], long_edge = std::max(h, w);
+      if (long_edge <= 1024) continue;
+      const double sc = 1024.0 / long_edge;      // topiq_backbone_chunk's arithmetic
+      const int nw = (int)(w * sc), nh = (int)(h * sc);
+      for (const auto& ax : {std::make_pair(w, nw), std::make_pair(h, nh)}) {
+        const auto key = std::make_tuple(ax.first, ax.second, (int)FE_FILTER_LANCZOS);
+        if (ax.first == ax.second || ax.second < 1 || !have.emplace(key, 1).second) continue;
+        ResizeCoeffs rc;
+        build_resize_coeffs(ax.first, ax.second, FE_FILTER_LANCZOS, rc);
+        Lz e{key, tables.pool.size(), tables.pool.size() + rc.kk.size(), rc.ksize};
+        tables.pool.insert(tables.pool.end(), rc.kk.begin(), rc.kk.end());
+        tables.pool.insert(tables.pool.end(), rc.bounds.begin(), rc.bounds.end());
+        lz.push_back(e);
+      }
+    }
+  }
+  const size_t desc_bytes = (size_t)n * sizeof(MixedDesc), pool_bytes = tables.pool.size() * sizeof(int32_t), pos_bytes = (size_t)n * sizeof(int32_t);
+  const size_t o_pool = 2 * desc_bytes, o_pos = o_pool + pool_bytes, blob_bytes = o_pos + pos_bytes;
+  std::vector<uint8_t> blob(blob_bytes, 0);
+  for (int m = 0; m < 2; ++m)
+    if (mode_on[m]) memcpy(blob.data() + m * desc_bytes, desc[m].data(), desc_bytes);
+  if (pool_bytes) memcpy(blob.data() + o_pool, tables.pool.data(), pool_bytes);
+  {
+    int32_t* pos = (int32_t*)(blob.data() + o_pos);
+    for (int p = 0; p < n; ++p) pos[mc.order[p]] = p;
+  }
+  if (ctx->mixed_cap < blob_bytes) {
+    fe_drain(ctx);
+    if (ctx->mixed_buf) FE_HIP(hipFree(ctx->mixed_buf));
+    ctx->mixed_buf = nullptr; ctx->mixed_cap = 0;
+    FE_HIP(hipMalloc(&ctx->mixed_buf, blob_bytes + blob_bytes / 2));
+    ctx->mixed_cap = blob_bytes + blob_bytes / 2;
+  }
+  uint8_t* d_blob = (uint8_t*)ctx->mixed_buf;
+  FE_HIP(hipMemcpyAsync(d_blob, blob.data(), blob_bytes, hipMemcpyHostToDevice, C.stream));
+  FE_HIP(hipStreamSynchronize(C.stream));      // the blob is host memory of this frame; the stream is idle between calls
+  const MixedDesc* d_desc[2] = {(const MixedDesc*)d_blob, (const MixedDesc*)(d_blob + desc_bytes)};
+  int32_t* d_pool = (int32_t*)(d_blob + o_pool);
+  const int32_t* d_pos = (const int32_t*)(d_blob + o_pos);
+  std::map<std::tuple<int, int, int>, ResizeCoeffsDev> lanczos;
+  for (const Lz& e : lz) {
+    ResizeCoeffsDev t;
+    t.kk = d_pool + e.kk; t.bounds = d_pool + e.bounds; t.ksize = e.ksize;
+    lanczos.emplace(e.key, t);
+  }
+  ScopedTables scoped(C, &lanczos);
+
+  Shape sh;
+  sh.n = n; sh.mb = ctx->microbatch; sh.on_device = on_device != 0;
+  sh.topiq = do_topiq; sh.clip = do_clip; sh.samp = do_samp;
+  sh.clip_chunk = tower ? tower->chunk() : 1;
+  sh.samp_chunk = samp ? samp->chunk() : 1;
+  sh.clip_side = do_clip && C.clip->dw.prec != PREC_F32;      // as in ensemble_run
+  if (const char* v = getenv("FE_OVERLAP_LANES")) {
+    sh.samp_side = strcmp(v, "clip") != 0;
+    sh.clip_side = strcmp(v, "samp") != 0;
+    sh.samp_first = strcmp(v, "samp_first") == 0;
+  }
+  const bool side_clip = do_clip && sh.clip_side, side_samp = do_samp && sh.samp_side;
+  // side arena: the larger tower chunk plus the intermediates of the largest micro-batch of the call, in steps of 64 MiB so that calls
+  // whose sizes differ a little do not each regrow it
+  const size_t inter_room = (max_inter + (((size_t)64 << 20) - 1)) & ~(((size_t)64 << 20) - 1);
+  const size_t side_need = std::min(C.arena.capacity(), std::max((size_t)(side_clip ? sh.clip_chunk : 0) * ((size_t)32 << 20),
+                                                                 (size_t)(side_samp ? sh.samp_chunk : 0) * kSampBytesPerImage) + inter_room + ((size_t)64 << 20));
+  sh.overlap = (side_clip || side_samp) && !C.profile && getenv("FE_NO_OVERLAP") == nullptr && side_lane_ready(ctx, side_need);
+
+  const hipStream_t lane[N_LANES] = {C.stream, ctx->side.stream, ctx->copy_stream};
+  hipEvent_t event[N_EVENTS];
+  event[EV_START] = ctx->side.ev_start; event[EV_JOIN] = ctx->side.ev_join;
+  for (int b = 0; b < 2; ++b) {
+    event[EV_COPIED0 + b] = ctx->ev_copied[b]; event[EV_CONSUMED0 + b] = ctx->ev_consumed[b]; event[EV_SIDE_READ0 + b] = ctx->side.ev_read[b];
+  }
+  auto crops = [&](const Op& o, int m, float* out, const float* mean, const float* stdv) {
+    uint8_t* scratch = inter_need[m][o.mb] ? (uint8_t*)C.arena.alloc(inter_need[m][o.mb]) : nullptr;
+    resize_mixed224(C, d_desc[m] + o.img0, o.count, max_nr[m][o.mb], d_pool, scratch, nullptr, out, mean, stdv);
+  };
+  for (const Op& o : build(sh, mc.cuts)) {
+    LaneScope scope(ctx, o.lane == LANE_SIDE);
+    switch (o.kind) {
+      case OP_CLEAR:
+        FE_HIP(hipMemsetAsync(d_pl, 0, total * sizeof(float), lane[LANE_MAIN]));
+        break;
+      case OP_COPY_IN:      // image by image: the host images lie anywhere
+        for (int p = o.img0; p < o.img0 + o.count; ++p)
+          FE_HIP(hipMemcpyAsync(ctx->stage_buf[o.mb & 1] + off[p], images[mc.order[p]], bytes[p], hipMemcpyHostToDevice, lane[LANE_COPY]));
+        break;
+      case OP_GATHER:
+        for (int p = o.img0; p < o.img0 + o.count; ++p)
+          FE_HIP(hipMemcpyAsync(ctx->stage_buf[o.mb & 1] + off[p], images[mc.order[p]], bytes[p], hipMemcpyDeviceToDevice, lane[LANE_MAIN]));
+        break;
+      case OP_RECORD:
+        FE_HIP(hipEventRecord(event[o.event], lane[o.lane]));
+        break;
+      case OP_WAIT:
+        FE_HIP(hipStreamWaitEvent(lane[o.lane], event[o.event], 0));
+        break;
+      case OP_TOPIQ: {
+        const int i = mc.order[o.img0];
+        const uint8_t* in = (!on_device || mc.cuts[o.mb].gather) ? (const uint8_t*)ctx->stage_buf[o.mb & 1] : images[i];
+        C.arena.reset();
+        topiq_chunk_score(ctx, in, o.count, hw[2 * i], hw[2 * i + 1], p_topiq + o.img0);
+        break;
+      }
+      case OP_CLIP_PRE:
+        C.arena.reset();
+        crops(o, MIXED_CLIP, tower->slots(o.slot, o.count), kClipMean, kClipStd);
+        break;
+      case OP_CLIP_TOWER:
+        C.arena.reset();
+        tower->run(o.count, o.img0);
+        break;
+      case OP_CLIP_COMPACT:
+        tower->compact(o.count, o.left);
+        break;
+      case OP_SAMP_PRE:
+        C.arena.reset();
+        crops(o, MIXED_SAMP, samp->slots(o.slot, o.count), kImagenetMean, kImagenetStd);
+        break;
+      case OP_SAMP_NETS:
+        C.arena.reset();
+        samp->run(o.count, o.img0);
+        break;
+      case OP_SAMP_COMPACT:
+        samp->compact(o.count, o.left);
+        break;
+      case OP_INTERLEAVE: {
+        const size_t work = (size_t)n * FE_RECORD_FLOATS;
+        hipLaunchKernelGGL(records_interleave_mixed_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, lane[LANE_MAIN], d_pl, n4, n, d_pos, d_rec, ld);
         FE_HIP(hipGetLastError());
         break;
       }
@@ -725,6 +981,79 @@ int fe_ensemble_score_dev(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, 
     const int ran = ensemble_run(ctx, rgb, n, h, w, on_device, d_records, ld_records);
     FE_HIP(hipStreamSynchronize(ctx->c.stream));
     if (models_run) *models_run = ran;
+  });
+}
+
+// fe_ensemble_score on a list of images that each have their own size (include/facet_engine.h has the contract, ensemble_run_mixed the schedule).
+int fe_ensemble_score_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, float* records,
+                            int* models_run) {
+  return fe_api(ctx, [&]() -> int {
+    Ctx& C = ctx->c;
+    if (!records) { C.err = "fe_ensemble_score_mixed: bad arguments (null records)"; return FE_ERR_INVALID; }
+    if (const int rc = mixed_check_images(ctx, "fe_ensemble_score_mixed", images, hw, n, 32)) return rc;
+    const size_t floats = (size_t)n * FE_RECORD_FLOATS;
+    if (floats > ctx->d_rec_cap) {
+      if (ctx->d_rec) FE_HIP(hipFree(ctx->d_rec));
+      ctx->d_rec = nullptr; ctx->d_rec_cap = 0;
+      FE_HIP(hipMalloc((void**)&ctx->d_rec, floats * sizeof(float)));
+      ctx->d_rec_cap = floats;
+    }
+    const int ran = ensemble_run_mixed(ctx, images, hw, n, on_device, ctx->d_rec, FE_RECORD_FLOATS);
+    FE_HIP(hipMemcpyAsync(records, ctx->d_rec, floats * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    if (models_run) *models_run = ran;
+    return FE_OK;
+  });
+}
+
+// The mixed-size preprocessing kernels alone: uint8 crops to the host. Works through the list in pieces of fe_set_microbatch images, each with
+// its descriptors, table pool, (host input) images and intermediates in the arena.
+int fe_preprocess224_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int mode, uint8_t* crops) {
+  return fe_api(ctx, [&]() -> int {
+    Ctx& C = ctx->c;
+    if (!crops || (mode != FE_MIXED_CLIP && mode != FE_MIXED_SAMP)) { C.err = "fe_preprocess224_mixed: bad arguments (null crops, or mode not 0 / 1)"; return FE_ERR_INVALID; }
+    if (const int rc = mixed_check_images(ctx, "fe_preprocess224_mixed", images, hw, n, 1)) return rc;
+    const size_t crop_bytes = (size_t)kMixedSide * kMixedSide * 3;
+    for (int i0 = 0; i0 < n; i0 += ctx->microbatch) {
+      const int nb = std::min(ctx->microbatch, n - i0);
+      C.arena.reset();
+      MixedTables tables;
+      std::vector<MixedDesc> desc(nb);
+      size_t inter = 0, src_bytes = 0;
+      int max_nr = 0;
+      for (int j = 0; j < nb; ++j) {
+        const int i = i0 + j;
+        MixedDesc& d = desc[j];
+        FE_CHECK(tables.describe(mode, hw[2 * i], hw[2 * i + 1], d), "preprocess224_mixed: image %d (%d x %d) cannot be resampled to 224 x 224", i, hw[2 * i], hw[2 * i + 1]);
+        d.slot = j;
+        FE_CHECK(inter + MixedTables::inter_bytes(d) < ((size_t)1 << 32), "preprocess224_mixed: intermediates exceed 4 GiB");
+        d.inter = (uint32_t)inter;
+        inter += MixedTables::inter_bytes(d);
+        if (d.ksize_h) max_nr = std::max(max_nr, (int)d.nr);
+        src_bytes += (size_t)d.h * d.w * 3;
+      }
+      if (on_device) {
+        for (int j = 0; j < nb; ++j) desc[j].src = images[i0 + j];
+      } else {
+        uint8_t* d_src = (uint8_t*)C.arena.alloc(src_bytes);
+        size_t at = 0;
+        for (int j = 0; j < nb; ++j) {
+          const size_t b = (size_t)desc[j].h * desc[j].w * 3;
+          FE_HIP(hipMemcpyAsync(d_src + at, images[i0 + j], b, hipMemcpyHostToDevice, C.stream));
+          desc[j].src = d_src + at;
+          at += b;
+        }
+      }
+      if (tables.pool.empty()) tables.pool.push_back(0);      // every image 224 x 224: no pass, but the kernel still takes a pool
+      const MixedDesc* d_desc = upload(C, desc.data(), desc.size());
+      const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());
+      uint8_t* d_inter = inter ? (uint8_t*)C.arena.alloc(inter) : nullptr;
+      uint8_t* d_crops = (uint8_t*)C.arena.alloc((size_t)nb * crop_bytes);
+      resize_mixed224(C, d_desc, nb, max_nr, d_pool, d_inter, d_crops, nullptr, nullptr, nullptr);
+      FE_HIP(hipMemcpyAsync(crops + (size_t)i0 * crop_bytes, d_crops, (size_t)nb * crop_bytes, hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));      // descriptors and pool are host memory of this iteration
+    }
+    return FE_OK;
   });
 }
 

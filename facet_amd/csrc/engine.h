@@ -206,6 +206,10 @@ void resize_u8(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow
                int cw, uint8_t* d_dst);
 // PIL `resize((ow, oh), filter, box)`: box = (x0, y0, x1, y1) in source pixels, fractional; the support is clamped to the image, not the box
 void resize_u8_box(Ctx& c, const uint8_t* d_src, int n, int h, int w, int oh, int ow, int filter, const float box[4], uint8_t* d_dst);
+// 224 x 224 crops of a list of images of any sizes, one launch per pass (kernels_resize_mixed.hip; descriptors and pool: resize_mixed_core.h)
+struct MixedDesc;
+void resize_mixed224(Ctx& c, const MixedDesc* d_desc, int count, int max_nr, const int32_t* d_pool, uint8_t* d_scratch, uint8_t* out_u8,
+                     float* out_f, const float mean[3], const float stdv[3]);
 
 // ---- thumbnails: Pillow's box reduce + baseline JPEG encoder (kernels_jpeg.hip, jpeg_core.h) ------------
 // PIL `reduce((fx, fy), box)`: d_dst [n][ceil(bh / fy)][ceil(bw / fx)][3]
@@ -283,6 +287,9 @@ struct Ctx {
   size_t topiq_f32_below = 0;   // 2-byte TOPIQ: images with fewer pixels run on the model's fp32 weights (fe_topiq_f32_below; 0 = never)
 
   std::map<std::tuple<int, int, int>, ResizeCoeffsDev> resize_cache;  // (in, out, filter) -> device tables
+  // tables of the call on the stack, looked up before resize_cache (nullptr outside such a call): the mixed-size ensemble call keeps the
+  // LANCZOS tables of its shapes in call-scoped memory, so a library of distinct sizes leaves nothing behind
+  const std::map<std::tuple<int, int, int>, ResizeCoeffsDev>* resize_scoped = nullptr;
   // (in, out, filter, bits of box start, bits of box end) -> device tables of a boxed resize
   std::map<std::tuple<int, int, int, uint32_t, uint32_t>, ResizeCoeffsDev> resize_box_cache;
   std::map<std::tuple<int, int, int>, void*> jpeg_cache;               // (h, w, quality) -> jpeg::Tables on the device

@@ -10,71 +10,23 @@
 // Here the coefficient tables are built on the host with the same double arithmetic and the two passes run as HIP
 // kernels with the same int32 arithmetic, so results are bit-exact (tests/test_resize_gpu.py compares with PIL itself).
 #include "engine.h"
+#include "resize_coeffs.h"
 #include <cmath>
 #include <cstring>
 
 namespace fe {
 
-static double filt_bilinear(double x) { if (x < 0.0) x = -x; return x < 1.0 ? 1.0 - x : 0.0; }
-static double filt_bicubic(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-static double sinc_filter(double x) { if (x == 0.0) return 1.0; x = x * M_PI; return std::sin(x) / x; }
-static double filt_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc_filter(x) * sinc_filter(x / 3) : 0.0; }
-
-constexpr int PRECISION_BITS = 32 - 8 - 2;
+constexpr int PRECISION_BITS = kResizePrecisionBits;
 
 void build_resize_coeffs(int in_size, int out_size, int filter, ResizeCoeffs& rc) {
   build_resize_coeffs(in_size, 0.0f, (float)in_size, out_size, filter, rc);
 }
 
-// Resample.c precompute_coeffs: in0 / in1 are C floats there too, their difference is taken in float
+// Resample.c precompute_coeffs (resize_coeffs.h holds the arithmetic, shared with the mixed-size path and the CPU harnesses)
 void build_resize_coeffs(int in_size, float in0, float in1, int out_size, int filter, ResizeCoeffs& rc) {
-  double (*f)(double);
-  double fsupport;
-  switch (filter) {
-    case FE_FILTER_BILINEAR: f = filt_bilinear; fsupport = 1.0; break;
-    case FE_FILTER_BICUBIC: f = filt_bicubic; fsupport = 2.0; break;
-    case FE_FILTER_LANCZOS: f = filt_lanczos; fsupport = 3.0; break;
-    default: throw Error("resize: unknown filter " + std::to_string(filter));
-  }
-  double scale, filterscale;
-  filterscale = scale = (double)(in1 - in0) / out_size;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = fsupport * filterscale;
-  const int ksize = (int)std::ceil(support) * 2 + 1;
-  rc.ksize = ksize;
+  rc.ksize = pil_resize_coeffs(in_size, in0, in1, out_size, filter, rc.kk, rc.bounds);
+  if (rc.ksize == 0) throw Error("resize: unknown filter " + std::to_string(filter));
   rc.out = out_size;
-  rc.kk.assign((size_t)out_size * ksize, 0);
-  rc.bounds.assign((size_t)out_size * 2, 0);
-  std::vector<double> k(ksize);
-  for (int xx = 0; xx < out_size; ++xx) {
-    const double center = in0 + (xx + 0.5) * scale;
-    double ww = 0.0;
-    const double ss = 1.0 / filterscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    for (int x = 0; x < xmax; ++x) {
-      const double w = f((x + xmin - center + 0.5) * ss);
-      k[x] = w;
-      ww += w;
-    }
-    for (int x = 0; x < xmax; ++x)
-      if (ww != 0.0) k[x] /= ww;
-    for (int x = 0; x < xmax; ++x) {
-      const double v = k[x];
-      rc.kk[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
-    }
-    rc.bounds[xx * 2] = xmin;
-    rc.bounds[xx * 2 + 1] = xmax;
-  }
 }
 
 __device__ __forceinline__ uint8_t clip8(int v) {
@@ -151,6 +103,10 @@ const ResizeCoeffsDev& upload_resize_coeffs(Ctx& c, const std::tuple<int, int, i
 
 static const ResizeCoeffsDev& coeffs_dev(Ctx& c, int in_size, int out_size, int filter) {
   const auto key = std::make_tuple(in_size, out_size, filter);
+  if (c.resize_scoped) {
+    auto sc = c.resize_scoped->find(key);
+    if (sc != c.resize_scoped->end()) return sc->second;
+  }
   auto it = c.resize_cache.find(key);
   if (it != c.resize_cache.end()) return it->second;
   ResizeCoeffs rc;

@@ -602,6 +602,26 @@ int fe_ensemble_select(fe_ctx* ctx, int models);
 int fe_ensemble_score_dev(fe_ctx* ctx, const uint8_t* rgb, int n, int h, int w, int on_device, float* d_records, int ld_records,
                           int* models_run);
 
+/* fe_ensemble_score for a chunk of photos as a library holds them: every image has its own size. images[i] points to image i as
+ * [h][w][3] RGB with (h, w) = hw[i] (hw is [n][2]); all pointers are host pointers (on_device = 0) or all device pointers, at any
+ * alignment and anywhere relative to each other. records [n][FE_RECORD_FLOATS] (host) come back in input order; fields, models_run and
+ * fe_ensemble_select as for fe_ensemble_score. Every image needs h >= 32 and w >= 32: a bad size or a null pointer returns
+ * FE_ERR_INVALID, the message names the index of the image, nothing is launched.
+ * Schedule: with TOPIQ selected the images are grouped by shape (order of first appearance, input order within a group) and cut into
+ * micro-batches of at most fe_set_microbatch images of one shape; TOPIQ runs per micro-batch as in fe_ensemble_score (LANCZOS cap per
+ * shape), in place when the images of a device micro-batch lie back to back, from a gathered copy otherwise. Without TOPIQ the
+ * micro-batches are plain slices of the list. Either way the 224 x 224 CLIP and SAMP crops of a micro-batch come from one launch per
+ * resampling pass over per-image descriptors, whatever the sizes, and gather across micro-batches - so across shapes - into the towers'
+ * usual chunks. All coefficient tables of the call live in one call-scoped pool: no device allocation per image size, nothing cached. */
+int fe_ensemble_score_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, float* records,
+                            int* models_run);
+/* The preprocessing kernels of fe_ensemble_score_mixed alone. mode FE_MIXED_CLIP: PIL BICUBIC, shorter side to 224, centre crop (open_clip's
+ * eval transform); FE_MIXED_SAMP: PIL BILINEAR to 224 x 224 (torchvision Resize((224, 224))). crops [n][224][224][3] uint8 on the host,
+ * byte for byte what Pillow gives. images / hw / on_device as above; any h, w >= 1. */
+#define FE_MIXED_CLIP 0
+#define FE_MIXED_SAMP 1
+int fe_preprocess224_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int mode, uint8_t* crops);
+
 /* ---- ONNX-subset graph runtime --------------------------------------------------------------------------------
  * Replaces the onnxruntime InferenceSessions that insightface.app.FaceAnalysis(name='buffalo_l') opens for the reference
  * (analyzers/face.py:30-38: det_10g.onnx, 2d106det.onnx, w600k_r50.onnx; invoked through face_app.get at :99). The
