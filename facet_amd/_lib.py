@@ -89,6 +89,8 @@ SIGNATURES = {
     "fe_model_loaded": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_op_conv2d": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int,
                                C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "fe_op_gate_rowpool": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, _f32p, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int)]),
     "fe_op_topiq_gate64": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float,
                                      _f32p, _f32p, C.c_int, C.c_int, _f32p]),
     "fe_op_conv3x3_c64": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p,
@@ -510,6 +512,30 @@ class Engine:
         self._ck(self.lib.fe_op_conv2d(self.h, xp, n, c, h, ww, wp, cout, kh, kw, sp, hp, rp, int(res_after_act),
                                        stride, pad, dil, ACT[act], y.ctypes.data_as(_f32p)))
         return y
+
+    def gate_rowpool(self, x, weight, bias, gate, th, tw, act="gelu", fused=True, ldx=None):
+        """Test hook of the pooled gate of the fp32 TOPIQ head: x [n, cin, h, w], weight [cout, cin], bias [cout] or None, gate [n, h, w] ->
+        (mean over the adaptive th x tw windows of act(weight x + bias) * gate as [n, cout, th, tw], whether the row-pooling route ran).
+        fused=False forces the plain conv + adaptive pool; ldx > cin places the input rows in a wider NHWC buffer."""
+        x = np.asarray(x, np.float32)
+        n, cin, h, w = x.shape
+        ldx = cin if ldx is None else int(ldx)
+        xr = np.full((n, h, w, ldx), 3e4, np.float32)
+        xr[..., :cin] = x.transpose(0, 2, 3, 1)
+        xr, xp = _f32(xr)
+        weight, wp = _f32(weight)
+        cout = weight.shape[0]
+        assert weight.shape == (cout, cin)
+        bp = None
+        if bias is not None:
+            bias, bp = _f32(bias)
+        gate, gp = _f32(gate)
+        assert gate.shape == (n, h, w)
+        y = np.empty((n, th, tw, cout), np.float32)
+        routed = C.c_int(0)
+        self._ck(self.lib.fe_op_gate_rowpool(self.h, xp, n, h, w, cin, ldx, wp, bp, cout, gp, ACT[act], th, tw, int(bool(fused)),
+                                             y.ctypes.data_as(_f32p), C.byref(routed)))
+        return np.ascontiguousarray(y.transpose(0, 3, 1, 2)), bool(routed.value)
 
     def topiq_gate64(self, x, w0, b0, w2, b2, w4, b4, wx, bx, wblk_act="gelu", gate_act="gelu"):
         """Test hook of the fused gate + 16x16 pool of TOPIQ's 64-channel level (2-byte precisions): x [n, 64, h, w]."""

@@ -135,6 +135,35 @@ int fe_op_conv2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const 
   });
 }
 
+int fe_op_gate_rowpool(fe_ctx* ctx, const float* x, int n, int h, int w, int cin, int ldx, const float* weight, const float* bias, int cout,
+                       const float* gate, int act, int th, int tw, int fused, float* y, int* routed) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && weight && gate && y && n > 0 && h > 0 && w > 0 && cin > 0 && ldx >= cin && cout > 0 && th > 0 && tw > 0 && th <= h && tw <= w,
+             "bad gate_rowpool arguments");
+    FE_CHECK(C.precision == PREC_F32, "fe_op_gate_rowpool: fp32 contexts only");
+    C.arena.reset();
+    DeviceWeights dw;
+    dw.prec = PREC_F32;
+    HostTensor W, B;
+    W.shape = {cout, cin}; W.data.assign(weight, weight + (size_t)cout * cin);
+    if (bias) { B.shape = {cout}; B.data.assign(bias, bias + cout); }
+    ConvW cw = build_linear_rows(dw, W, bias ? &B : nullptr, 0, cout);
+    FE_CHECK(cw.CinPad <= ldx, "fe_op_gate_rowpool: ldx below the packed channel count %d", cw.CinPad);
+    Tensor xt = C.arena.tensor(n, h, w, ldx);
+    FE_HIP(hipMemcpyAsync(xt.p, x, xt.numel() * sizeof(float), hipMemcpyHostToDevice, C.stream));
+    Tensor gt = C.arena.tensor(n, h, w, 1);
+    FE_HIP(hipMemcpyAsync(gt.p, gate, gt.numel() * sizeof(float), hipMemcpyHostToDevice, C.stream));
+    ConvOpts og; og.act = act; og.gate = &gt;
+    int took = 0;
+    Tensor pooled = topiq_gate_pool(C, cw, xt.slice(0, cw.CinPad), og, th, tw, fused != 0, &took);
+    FE_CHECK(pooled.h == th && pooled.w == tw && pooled.ld == cout, "fe_op_gate_rowpool: unexpected result shape");
+    FE_HIP(hipMemcpyAsync(y, pooled.p, pooled.numel() * sizeof(float), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));
+    if (routed) *routed = took;
+  });
+}
+
 int fe_op_topiq_gate64(fe_ctx* ctx, const float* x, int n, int h, int w, const float* w0, const float* b0, const float* w2, const float* b2,
                        const float* w4, float b4, const float* wx, const float* bx, int wblk_act, int gate_act, float* y) {
   return fe_api(ctx, [&] {

@@ -149,6 +149,8 @@ inline TensorT<T> mat_view(const T* p, int rows, int cols, int ld) {
 void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, const ConvOpts& o);
 void conv_forward(Ctx& c, const ConvW& w, const TensorH& x, const TensorH& y, const ConvOptsT<bf16>& o);
 void conv_forward(Ctx& c, const ConvW& w, const TensorF16& x, const TensorF16& y, const ConvOptsT<f16>& o);
+// fp32: whether this layer can run with the row-pooling epilogue (ConvOpts::pool_kw = kw, ConvOpts::pool); conv_forward asserts it
+bool conv_rowpool_ok(const Ctx& c, const ConvW& w, const Tensor& x, const ConvOpts& o, int kw);
 // Allocates the output from the arena with the standard conv output size.
 template <class T>
 TensorT<T> conv_new(Ctx& c, const ConvW& w, const TensorT<T>& x, const ConvOptsT<T>& o);
@@ -579,6 +581,10 @@ void vlm_select(Ctx& c, float* lg, int B, int vocab, int* next_dev, float* lp_de
 
 void build_topiq_head(TopiqModel& m, const WeightStore& ws);
 // feats: the 5 pyramid levels for nb images; scores_dev: device [nb]
+// The pooled gate of one pyramid level, fp32: adaptive_avgpool(act(split_x1(f)) * gate) as [n][th][tw][Cout] from the arena. With
+// `rowpool`, and where the windows tile the map in widths of 2, 4, 8 or 16, the conv pools rows in its epilogue and a finishing pass adds
+// the window's rows (no full-size tensor; *fused = 1); otherwise the conv writes full size and launch_adaptive_avgpool reads it back.
+Tensor topiq_gate_pool(Ctx& c, const ConvW& split_x1, const Tensor& f, const ConvOpts& og, int th, int tw, bool rowpool, int* fused = nullptr);
 template <class T>
 void topiq_head_forward(Ctx& c, TopiqModel& m, const std::vector<TensorT<T>>& feats, float* scores_dev);
 // fp32 view of an activation vector: the pointer itself for fp32, an arena copy for bf16

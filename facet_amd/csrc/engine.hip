@@ -253,6 +253,22 @@ LayerNormW build_ln(DeviceWeights& dw, const WeightStore& ws, const std::string&
   return l;
 }
 
+// Whether conv_forward can run this (1x1, gated) layer with the row-pooling epilogue of the LDS-DMA kernel (ConvOpts::pool_kw): the shape
+// rules of the epilogue plus everything that sends the layer to one of that kernel's scalar-offset 1x1 tiles (launch_conv).
+bool conv_rowpool_ok(const Ctx& c, const ConvW& w, const Tensor& x, const ConvOpts& o, int kw) {
+  auto al16 = [](const void* ptr) { return ((uintptr_t)ptr & 15) == 0; };
+  if (kw != 2 && kw != 4 && kw != 8 && kw != 16) return false;
+  if (w.KH != 1 || w.KW != 1 || o.sh != 1 || o.sw != 1 || o.ph != 0 || o.pw != 0 || o.res || !o.gate || o.act == ACT_PRELU) return false;
+  if (x.w % kw != 0 || x.c != w.CinPad || w.CinPad % 32 != 0 || w.Kp != w.CinPad || w.Cout <= 32 || w.Cout % 4 != 0) return false;
+  if (c.force_variant != 0 || getenv("FE_NO_DMA")) return false;
+  if (!al16(x.p) || x.ld % 4 != 0 || (w.scale && !al16(w.scale)) || (w.shift && !al16(w.shift))) return false;
+  if (o.gate && o.gate->c != 1 && (o.gate->ld % 4 != 0 || !al16(o.gate->p))) return false;
+  // operands the kernel reaches through 32-bit buffer offsets, whole or by image groups (conv_split_by_images)
+  const unsigned long long img = (unsigned long long)x.h * x.w * (unsigned long long)(x.ld > w.Cout ? x.ld : w.Cout) * 4;
+  const unsigned long long wspan = (unsigned long long)w.Cout * w.Kp * 4;
+  return img < 0xF0000000ull && wspan < 0xFFFFFF00ull && x.pixels() < (1ull << 31);
+}
+
 void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, const ConvOpts& o) {
   FE_CHECK(x.c == w.CinPad, "conv: input channels %d != packed Cin %d", x.c, w.CinPad);
   FE_CHECK(y.c == w.Cout && y.n == x.n, "conv: output view mismatch (c=%d Cout=%d)", y.c, w.Cout);
@@ -279,6 +295,12 @@ void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, cons
   FE_CHECK(y.pixels() < (1ull << 31), "conv: M too large");
   p.act = o.act; p.res_after_act = o.res_after_act;
   p.variant = c.force_variant;
+  if (o.pool_kw) {      // row-pooling epilogue: y carries the conv's output shape only, the sums go to o.pool
+    FE_CHECK(conv_rowpool_ok(c, w, x, o, o.pool_kw), "conv: the row-pooling epilogue does not apply to this layer (kw=%d)", o.pool_kw);
+    FE_CHECK(o.pool && o.pool->p && o.pool->n == x.n && o.pool->h == x.h && o.pool->w * o.pool_kw == x.w && o.pool->c == w.Cout, "conv: pool view mismatch");
+    p.pool_kw = o.pool_kw; p.pool = o.pool->p; p.ldp = o.pool->ld;
+    p.y = nullptr; p.ldy = w.Cout;
+  }
   if (w.wtap && o.act != ACT_PRELU && o.sh == 1 && o.sw == 1 && !o.res && !o.gate && p.variant == 0 && y.h == x.h && y.w == x.w) {
     // narrow spatial conv (Cout <= 2): 1x1 conv to per-tap partials on the matrix cores + a gather-sum pass
     const int T = w.KH * w.KW * w.Cout, Tp = (T + 3) & ~3;
@@ -442,8 +464,9 @@ void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, cons
     FE_HIP(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     char nm[128];
-    snprintf(nm, sizeof nm, "conv%dx%d s%d d%d M=%d K=%d N=%d", w.KH, w.KW, o.sh, o.dh, p.M, p.K, p.Cout);
-    double bytes = 4.0 * ((double)x.pixels() * x.c + (double)y.pixels() * y.c * (o.res ? 2 : 1) + (double)w.Cout * w.K);
+    int nn = snprintf(nm, sizeof nm, "conv%dx%d s%d d%d M=%d K=%d N=%d", w.KH, w.KW, o.sh, o.dh, p.M, p.K, p.Cout);
+    if (o.pool_kw && nn > 0 && nn < (int)sizeof nm) snprintf(nm + nn, sizeof nm - nn, " +rowpool kw=%d", o.pool_kw);
+    double bytes = 4.0 * ((double)x.pixels() * x.c + (double)y.pixels() * y.c * (o.res ? 2 : 1) / (o.pool_kw ? o.pool_kw : 1) + (double)w.Cout * w.K);
     c.timings.push_back({nm, 2.0 * p.M * (double)(w.KH * w.KW * w.Cin) * (w.CoutAlg ? w.CoutAlg : p.Cout), bytes, ms});
   } else {
     launch();

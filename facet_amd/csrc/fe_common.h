@@ -270,6 +270,11 @@ struct ConvParamsT {
   int a_wrap;                       // 2-byte GEMM form: > 0 = the A row holds only a_wrap * 32 columns and is read again from column 0 after them
   int split_lo_off;                 // 2-byte fp32-stream forms: > 0 = split-pair output, hi at column c and lo = round(v - hi) at column split_lo_off + c of y
   int exact_act;                    // 2-byte fp32-stream forms: erf GELU instead of the tanh form (results that are NOT rounded to 2 bytes)
+  // fp32 LDS-DMA kernel, row-pooling epilogue (1x1, stride 1, no padding, W % pool_kw == 0): pool_kw in {2, 4, 8, 16} = each aligned group
+  // of pool_kw consecutive output pixels is summed (after activation and gate) into one row of `pool` [N][H][W / pool_kw][Cout]; `y` is
+  // neither written nor needed (may be null). 0 = off.
+  int pool_kw;
+  T* pool; int ldp;
 };
 using ConvParams = ConvParamsT<float>;
 using ConvParamsH = ConvParamsT<bf16>;
@@ -314,6 +319,10 @@ struct ConvOptsT {
   // output view passed to conv_forward may then carry a null pointer: fp32 output only)
   const TensorT<float>* res32 = nullptr;
   const TensorT<float>* y32 = nullptr;
+  // fp32 only: row-pooling epilogue (ConvParamsT::pool_kw). `pool` is the [N][H][W / pool_kw][Cout] partial tensor; the output view given
+  // to conv_forward then only carries the shape (null pointer).
+  int pool_kw = 0;
+  const TensorT<T>* pool = nullptr;
 };
 using ConvOpts = ConvOptsT<float>;
 
@@ -363,6 +372,7 @@ inline bool conv_split_by_images(const ConvParamsT<T>& p, Launch&& launch) {
     if (p.res32) q.res32 = p.res32 + opix * p.ldr32;
     if (p.res) q.res = p.res + opix * p.ldr;
     if (p.gate) q.gate = p.gate + opix * p.ldg;
+    if (p.pool_kw) q.pool = p.pool + opix / p.pool_kw * p.ldp;      // Wo % pool_kw == 0: an image starts a group
     launch(q);
   }
   return true;
@@ -387,6 +397,9 @@ template <class T> void launch_maxpool(const TensorT<T>& x, const TensorT<T>& y,
 template <class T> void launch_bilinear(const TensorT<T>& x, const TensorT<T>& y, hipStream_t s);
 // adaptive average pool NHWC -> NHWC (torch semantics: start=floor(i*H/Ho), end=ceil((i+1)*H/Ho))
 template <class T> void launch_adaptive_avgpool(const TensorT<T>& x, const TensorT<T>& y, hipStream_t s);
+// finishes the row-pooling epilogue of the gated 1x1 conv: part [n][h][wo][c] holds sums over W / wo pixels of a row; y [n][ho][wo][c] =
+// (sum of the h / ho rows of a window, top to bottom) / (window size). h % ho == 0; 16-B aligned views.
+void launch_rowpool_finish(const Tensor& part, const Tensor& y, int kw, hipStream_t s);
 void launch_convert(const float* x, bf16* y, size_t n, hipStream_t s);
 void launch_convert(const bf16* x, float* y, size_t n, hipStream_t s);
 void launch_convert(const float* x, f16* y, size_t n, hipStream_t s);

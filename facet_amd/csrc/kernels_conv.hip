@@ -297,7 +297,7 @@ static void launch_forced(const ConvParams& q, hipStream_t s) {
 double conv_flops(const ConvParams& p) { return 2.0 * (double)p.M * p.K * p.Cout; }
 
 void launch_conv(const ConvParams& p, hipStream_t s) {
-  FE_CHECK(p.x && p.w && p.y && p.ldy >= p.Cout && p.ldx >= p.Cin, "conv: null operand or row stride below the channel count");
+  FE_CHECK(p.x && p.w && (p.y || p.pool_kw) && p.ldy >= p.Cout && p.ldx >= p.Cin, "conv: null operand or row stride below the channel count");
   FE_CHECK(p.Cin % 4 == 0 && p.ldx % 4 == 0, "conv: Cin=%d ldx=%d must be multiples of 4", p.Cin, p.ldx);
   FE_CHECK(((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.w & 15) == 0, "conv: x/w must be 16-B aligned");
   FE_CHECK(p.Kp % CONV_KALIGN == 0 && p.Kp >= p.K, "conv: bad Kp=%d K=%d", p.Kp, p.K);
@@ -321,15 +321,18 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
   // Tile choice: 128x128 for wide outputs, 256x64 / 256x32 for narrow ones; problems too small to give every
   // CU a 128x128 tile drop to 64x64 tiles (4x the workgroups).
   // forced variants (tests / tools): 1-7 register-staged tiles, 11-18 LDS-DMA tiles, 21/22 lean LDS-DMA tiles
+  static const bool no_dma = getenv("FE_NO_DMA") != nullptr;
+  const unsigned long long xspan = ((unsigned long long)p.N * p.H * p.W - 1) * (unsigned long long)p.ldx * 4 + (unsigned long long)p.Cin * 4;
+  const unsigned long long wspan = ((unsigned long long)p.Cout - 1) * (unsigned long long)q.ldw * 4 + (unsigned long long)p.Kp * 4;
+  const bool dma = !no_dma && p.Cin % 16 == 0 && p.KH * p.KW < 64 && xspan < 0xFFFFFF00ull && wspan < 0xFFFFFF00ull;
+  // the row-pooling epilogue exists in the LDS-DMA kernel's 1x1 tiles only (conv_rowpool_ok, engine.hip, is the callers' test)
+  FE_CHECK(!p.pool_kw || (dma && q.variant == 0 && p.Cout > 32 && q.vec_epi), "conv: the row-pooling epilogue is not available for this problem");
   if (q.variant > 10 && q.variant < 40) { launch_conv_dma(q, q.variant > 20 ? q.variant : q.variant - 10, s); return; }
   if (q.variant > 0) { launch_forced(q, s); return; }
   // the narrow kernel reads weights in plain (tap, ci) order; pack_conv blocks K by 16 channels once Cin % 16 == 0 and there
   // is more than one tap, so those go to the matrix-core path below (256x32 tile)
   if (p.Cout <= 4 && q.batch <= 1 && !p.gate && q.variant == 0 && (p.Cin % 16 != 0 || p.KH * p.KW == 1)) { launch_conv_narrow(q, s); return; }
-  static const bool no_dma = getenv("FE_NO_DMA") != nullptr;
-  const unsigned long long xspan = ((unsigned long long)p.N * p.H * p.W - 1) * (unsigned long long)p.ldx * 4 + (unsigned long long)p.Cin * 4;
-  const unsigned long long wspan = ((unsigned long long)p.Cout - 1) * (unsigned long long)q.ldw * 4 + (unsigned long long)p.Kp * 4;
-  if (!no_dma && p.Cin % 16 == 0 && p.KH * p.KW < 64 && xspan < 0xFFFFFF00ull && wspan < 0xFFFFFF00ull) {
+  if (dma) {
     // Tile choice = wave-quantisation model: workgroups are dealt round-robin over the 256 CUs and the ones resident on
     // a CU share its matrix pipes, so a launch lasts ~ ceil(WGs / 256) tiles per CU x (tile area / tile efficiency).
     // Measured relative efficiencies on the ResNet/ViT shapes (tools/conv_bench.py; re-scanned in round 2): 128x128 1.00, 128x64 1.05, 64x64 0.93;
@@ -351,6 +354,7 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         if (cost < best) { best = cost; tile = cs[i].tile; }
       }
     }
+    if (q.pool_kw && tile == 1) tile = 7;      // the row-pooling epilogue has no 128x128 form (the default efficiencies never pick it for these layers)
     launch_conv_dma(q, tile, s);
     return;
   }

@@ -25,6 +25,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // MODE 0: 3-slab ring + double-buffered fragments (3 waves/SIMD for 64x64 wave tiles).
 // MODE 1: lean - 2 slabs, one fragment set, register budget of 128 so FOUR waves/SIMD are resident.
 // MODE 2: MODE 0 with a PReLU epilogue (per-channel slopes); separate instantiation so the hot tiles keep their registers.
+// MODE 3: MODE 0 with the row-pooling epilogue (ConvParams::pool_kw): groups of consecutive output pixels summed, no full-size output.
 // ONE_TAP: 1x1 kernels (GEMMs) with Cin % 32 == 0 - no tap masks, the K offset of a slab is the scalar offset of the buffer load.
 template <int WGM, int WGN, int TM, int TN, int MODE = 0, bool ONE_TAP = false>
 __global__ __launch_bounds__(256, (MODE == 1 ? 4 : (TM * TN >= 8 ? 2 : (TM * TN >= 4 ? 3 : 4)))) void conv_dma_kernel(ConvParams p, const int ntiles) {
@@ -414,6 +415,86 @@ __global__ __launch_bounds__(256, (MODE == 1 ? 4 : (TM * TN >= 8 ? 2 : (TM * TN 
 #undef FE_READ_FRAGS
   __syncthreads();   // all fragment reads retired before the epilogue reuses the slabs as staging
 
+  if constexpr (MODE == 3) {
+  // ---- row-pooling epilogue (the gated 1x1 layers of the TOPIQ head): scale / shift / activation / gate per row as below, then each aligned
+  // group of p.pool_kw consecutive rows is summed and ONE float4 per group goes to p.pool; the full-size output is never written.
+    // The launcher guarantees p.vec_epi, a 1x1 stride-1 problem and W % pool_kw == 0 with pool_kw in {2, 4, 8, 16}: a group lies in one image
+    // row and in one 32-row slab of a wave (slabs start at multiples of 32). The finished rows go back to the wave's staging region, where
+    // every output lane adds its pool_kw rows in ascending order: a fixed order, no atomics. Rows >= M enter as zeros. Narrow wave tiles only
+    // (TN = 1, the 128x64 and 64x64 blocks these layers run on); the per-element arithmetic is that of their plain epilogue below, so both
+    // routes pool the same values.
+    static_assert(TN == 1, "row-pooling epilogue: narrow wave tiles only");
+    constexpr int WC = TN * 32, ES = WC + 4, LPR = WC / 4, RPI = 64 / LPR, NIT = 32 / RPI;
+    float* E = smem + wave * 32 * ES;
+    const int lr = lane / LPR, lc = (lane % LPR) * 4;
+    const int colb = n0 + wn * WC + lc;
+    const int colc = colb < p.Cout ? colb : 0;
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sf = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (p.scale) sc = *reinterpret_cast<const float4*>(p.scale + colc);
+    if (p.shift) sf = *reinterpret_cast<const float4*>(p.shift + colc);
+    const int act = p.act;
+    const int kwp = p.pool_kw;
+    auto row_of = [&](int i, int it) { return m0 + wm * TM * 32 + i * 32 + lr + it * RPI; };
+    auto fetch_gate = [&](int m) -> float4 {
+      const int mc = m < p.M ? m : p.M - 1;
+      if (!p.gate) return make_float4(1.f, 1.f, 1.f, 1.f);
+      if (p.gate_c1) { const float g = p.gate[(size_t)mc * p.ldg]; return make_float4(g, g, g, g); }
+      return *reinterpret_cast<const float4*>(p.gate + (size_t)mc * p.ldg + colc);
+    };
+    auto finish_row = [&](int m, int erow, const float4 gu) {
+      float4 v = *reinterpret_cast<const float4*>(&E[erow * ES + lc]);
+      v.x = v.x * sc.x + sf.x; v.y = v.y * sc.y + sf.y; v.z = v.z * sc.z + sf.z; v.w = v.w * sc.w + sf.w;
+      v.x = apply_act_d(v.x, act); v.y = apply_act_d(v.y, act); v.z = apply_act_d(v.z, act); v.w = apply_act_d(v.w, act);
+      if (p.gate) { v.x *= gu.x; v.y *= gu.y; v.z *= gu.z; v.w *= gu.w; }
+      if (m >= p.M) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(&E[erow * ES + lc]) = v;
+    };
+    // one output = (group, 4 channels); KW rows read first, then added first row to last
+    auto sum_groups = [&](int i, auto kwc) {
+      constexpr int KW = decltype(kwc)::value;
+      constexpr int NOUT = (32 / KW) * LPR;      // float4 outputs of a 32-row slab
+  #pragma unroll
+      for (int o0 = 0; o0 < NOUT; o0 += 64) {
+        const int o = o0 + lane;
+        const int grp = o / LPR, c4 = (o % LPR) * 4;
+        const int col = n0 + wn * WC + c4;
+        const int mg = m0 + wm * TM * 32 + i * 32 + grp * KW;      // first row of the group
+        if (o < NOUT) {
+          float4 rv[KW];
+  #pragma unroll
+          for (int k = 0; k < KW; ++k) rv[k] = *reinterpret_cast<const float4*>(&E[(grp * KW + k) * ES + c4]);
+          float4 a = rv[0];
+  #pragma unroll
+          for (int k = 1; k < KW; ++k) { a.x += rv[k].x; a.y += rv[k].y; a.z += rv[k].z; a.w += rv[k].w; }
+          if (col < p.Cout && mg < p.M) *reinterpret_cast<float4*>(p.pool + (size_t)(mg / KW) * p.ldp + col) = a;
+        }
+      }
+    };
+  #pragma unroll
+    for (int i = 0; i < TM; ++i) {
+  #pragma unroll
+      for (int j = 0; j < TN; ++j)
+  #pragma unroll
+        for (int e = 0; e < 16; ++e) E[((e & 3) + 8 * (e >> 2) + 4 * h) * ES + j * 32 + r] = acc[i][j][e];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      float4 gv[NIT];      // every gate row of the slab requested before the first activation
+  #pragma unroll
+      for (int it = 0; it < NIT; ++it) gv[it] = fetch_gate(row_of(i, it));
+  #pragma unroll
+      for (int it = 0; it < NIT; ++it) finish_row(row_of(i, it), lr + it * RPI, gv[it]);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (kwp == 16) sum_groups(i, std::integral_constant<int, 16>{});
+      else if (kwp == 8) sum_groups(i, std::integral_constant<int, 8>{});
+      else if (kwp == 4) sum_groups(i, std::integral_constant<int, 4>{});
+      else sum_groups(i, std::integral_constant<int, 2>{});
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();      // the group reads retire before the next slab's accumulators overwrite the region
+    }
+    return;
+  }
+
   // Two epilogue forms. Narrow wave tiles (TN = 1: the tiles of the HBM-bound short-K layers) keep the fully unrolled, branch-free
   // row code with every residual row requested up front - measured 64.6 vs 55.1 TFLOP/s on the K = 64 -> 256 expand against the
   // rolled form (hipcc drains the outstanding loads at the scalar branches the rolled form has per row). Wide wave tiles take the
@@ -658,6 +739,18 @@ void launch_conv_dma(const ConvParams& p0, int tile, hipStream_t s) {
   p.x_span = (unsigned)xs; p.w_span = (unsigned)ws;
   p.unit_stride = (p.KH == 1 && p.KW == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.Ho == p.H && p.Wo == p.W &&
                    (long long)p.N * p.H * p.W == (long long)p.M) ? 1 : 0;
+  if (p.pool_kw) {      // row-pooling epilogue: the narrow-wave 1x1 tiles launch_conv picks for Cout > 32, in their scalar-offset (ONE_TAP) form
+    const int kw = p.pool_kw;
+    FE_CHECK(kw == 2 || kw == 4 || kw == 8 || kw == 16, "conv_dma: pool_kw=%d is not one of 2, 4, 8, 16", kw);
+    FE_CHECK(p.unit_stride && p.W % kw == 0 && p.Cin % 32 == 0 && p.Kp == p.Cin, "conv_dma: the row-pooling epilogue needs a 1x1 stride-1 conv with Cin %% 32 == 0 and W %% pool_kw == 0");
+    FE_CHECK(p.vec_epi && p.batch <= 1 && !p.res && p.act != ACT_PRELU, "conv_dma: the row-pooling epilogue takes the vector epilogue's alignment, no residual, no PReLU");
+    FE_CHECK(p.pool && ((uintptr_t)p.pool & 15) == 0 && p.ldp % 4 == 0 && p.ldp >= p.Cout, "conv_dma: bad pool view");
+    switch (tile) {
+      case 7: launch_dma_variant<2, 2, 2, 1, 3, true>(p, s); return;
+      case 4: launch_dma_variant<2, 2, 1, 1, 3, true>(p, s); return;
+      default: FE_CHECK(false, "conv_dma: no row-pooling form of tile %d", tile);
+    }
+  }
   if (p.act == ACT_PRELU) {
     FE_CHECK(p.slope, "conv_dma: PReLU without slopes");
     switch (tile) {

@@ -323,6 +323,37 @@ void launch_adaptive_avgpool(const TensorT<T>& x, const TensorT<T>& y, hipStream
   FE_HIP(hipGetLastError());
 }
 
+// Second half of the pooled gate of the TOPIQ head (fp32): the gated 1x1 conv's row-pooling epilogue (kernels_conv_dma.hip) left
+// part[n][h][wo][c] = sums over the kw pixels of a window row; this adds the kh = h / ho rows of a window top to bottom and divides by the
+// window size like adaptive_avgpool_vec4_kernel. 4 channels per thread.
+__global__ void rowpool_finish_kernel(const float* __restrict__ part, int ldp, float* __restrict__ y, int ldy, int n, int kh, int c4, int ho, int wo,
+                                      float d) {
+  const size_t total = (size_t)n * ho * wo * c4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % c4) * 4;
+    size_t pix = i / c4;
+    const int ow = pix % wo; pix /= wo;      // pix = img * ho + oh
+    const float* row = part + (pix * kh * wo + ow) * (size_t)ldp + ch;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int iy = 0; iy < kh; ++iy) {
+      const float4 a = ld4(row + (size_t)iy * wo * ldp);
+      acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w;
+    }
+    st4(y + (pix * wo + ow) * (size_t)ldy + ch, make_float4(acc.x / d, acc.y / d, acc.z / d, acc.w / d));
+  }
+}
+void launch_rowpool_finish(const Tensor& part, const Tensor& y, int kw, hipStream_t s) {
+  FE_CHECK(part.c == y.c && part.n == y.n && part.w == y.w && y.h > 0 && part.h % y.h == 0 && kw > 0, "rowpool_finish: shape mismatch");
+  FE_CHECK(part.c % 4 == 0 && part.ld % 4 == 0 && y.ld % 4 == 0 && vec4_ok(part.p, y.p), "rowpool_finish: views must be 16-byte aligned");
+  const int kh = part.h / y.h;
+  const size_t work = y.pixels() * (size_t)(y.c / 4);
+  size_t g = (work + 255) / 256;
+  if (g > 8192) g = 8192;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL(rowpool_finish_kernel, dim3((unsigned)g), dim3(256), 0, s, part.p, part.ld, y.p, y.ld, part.n, kh, part.c / 4, y.h, y.w, (float)(kh * kw));
+  FE_HIP(hipGetLastError());
+}
+
 // ---- elementwise ---------------------------------------------------------------------------------------
 __global__ void sigmoid_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, size_t pixels, int c) {
   const size_t total = pixels * c;

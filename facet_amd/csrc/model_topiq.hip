@@ -186,6 +186,32 @@ static void dec_forward(Ctx& c, const DecLayerW& w, T* tgt, const T* memory, int
   c.arena.rewind(mark);
 }
 
+Tensor topiq_gate_pool(Ctx& c, const ConvW& split_x1, const Tensor& f, const ConvOpts& og, int th, int tw, bool rowpool, int* fused) {
+  if (fused) *fused = 0;
+  const int kw = (tw > 0 && f.w % tw == 0) ? f.w / tw : 0;
+  if (rowpool && f.h > th && f.w > tw && th > 0 && f.h % th == 0 && kw && conv_rowpool_ok(c, split_x1, f, og, kw)) {
+    Tensor pooled = c.arena.tensor(f.n, th, tw, split_x1.Cout);
+    const size_t mark = c.arena.mark();
+    Tensor part = c.arena.tensor(f.n, f.h, tw, split_x1.Cout);
+    Tensor shape = f;      // the conv's output shape; nothing is written at full size
+    shape.p = nullptr; shape.c = split_x1.Cout; shape.ld = split_x1.Cout;
+    ConvOpts o = og;
+    o.pool_kw = kw; o.pool = &part;
+    conv_forward(c, split_x1, f, shape, o);
+    launch_rowpool_finish(part, pooled, kw, c.stream);
+    c.arena.rewind(mark);
+    if (fused) *fused = 1;
+    return pooled;
+  }
+  Tensor gated = conv_new(c, split_x1, f, og);
+  if (gated.h > th && gated.w > tw) {
+    Tensor pooled = c.arena.tensor(f.n, th, tw, gated.c);
+    launch_adaptive_avgpool(gated, pooled, c.stream);
+    return pooled;
+  }
+  return gated;
+}
+
 // T = activation type (float | bf16). With bf16 the head stays bf16 up to the token mean; the MOS MLP (LayerNorm - Linear - GELU -
 // LayerNorm - Linear - GELU - Linear on one 256-vector per image) always runs in fp32 on the fp32 copies of its weights.
 template <class T>
@@ -259,11 +285,22 @@ void topiq_head_forward(Ctx& c, TopiqModel& m, const std::vector<TensorT<T>>& fe
     ConvOptsT<T> o4; o4.act = ACT_SIGMOID; o4.ph = o4.pw = 1;
     TensorT<T> wc = conv_new(c, g.w4, wb, o4);
     ConvOptsT<T> og; og.act = m.gate_act; og.gate = &wc;   // act(x1) * weight
-    TensorT<T> gated = conv_new(c, g.split_x1, f, og);
-    if (gated.h > th && gated.w > tw) {
-      TensorT<T> pooled = c.arena.tensor_t<T>(B, th, tw, gated.c);
-      launch_adaptive_avgpool(gated, pooled, c.stream);
-      gated = pooled;
+    TensorT<T> gated;
+    if constexpr (sizeof(T) == 4) {
+      // fp32: the pool's row sums come out of the gated conv's epilogue where the windows tile the map (topiq_gate_pool)
+      const bool no_rowpool = getenv("FE_NO_GATE_ROWPOOL") != nullptr;      // A/B hook, read per call like FE_NO_FUSED_GATE
+      // Maps under 1 MiB per image keep the two launches: their full-size tensor never leaves the caches, so there is no traffic to save,
+      // and the scores of small images keep their bits (the two routes add a window in different orders). Per image, not per batch, so
+      // the route of an image does not depend on what it is batched with.
+      const bool large = (size_t)f.h * f.w * g.split_x1.Cout * sizeof(float) >= ((size_t)1 << 20);
+      gated = topiq_gate_pool(c, g.split_x1, f, og, th, tw, !no_rowpool && large);
+    } else {
+      gated = conv_new(c, g.split_x1, f, og);
+      if (gated.h > th && gated.w > tw) {
+        TensorT<T> pooled = c.arena.tensor_t<T>(B, th, tw, gated.c);
+        launch_adaptive_avgpool(gated, pooled, c.stream);
+        gated = pooled;
+      }
     }
     FE_CHECK(gated.h == th && gated.w == tw, "topiq head: level %d is %dx%d, expected %dx%d", i, gated.h, gated.w, th, tw);
     TensorT<T> t = mat_view(tok[i], B * L, d, d);

@@ -270,6 +270,13 @@ int fe_op_conv2d(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const 
 int fe_op_topiq_gate64(fe_ctx* ctx, const float* x, int n, int h, int w, const float* w0, const float* b0, const float* w2,
                        const float* b2, const float* w4, float b4, const float* wx, const float* bx, int wblk_act,
                        int gate_act, float* y);
+/* test hook of the pooled gate of the fp32 TOPIQ head (topiq_gate_pool): x [n][h][w][ldx] (NHWC rows of ldx >= cin floats, the first cin used),
+   weight [cout][cin], bias [cout] or NULL, gate [n][h][w] ->
+   y [n][th][tw][cout] = adaptive_avgpool( act(weight x + bias) * gate ). fused != 0: routed like the head (the gated 1x1 conv's row-pooling
+   epilogue + finishing pass where the windows tile the map in widths 2 / 4 / 8 / 16, else the two plain launches); fused == 0: always the
+   plain conv + adaptive pool. *routed (may be NULL) = 1 when the row-pooling route ran. fp32 contexts only. */
+int fe_op_gate_rowpool(fe_ctx* ctx, const float* x, int n, int h, int w, int cin, int ldx, const float* weight, const float* bias, int cout,
+                       const float* gate, int act, int th, int tw, int fused, float* y, int* routed);
 /* test hook of the halo-tiled 3x3 convolution 64 -> 64 (stride 1, padding 1; kernels_c64.hip; 2-byte precisions only): x [n][64][h][w],
    w2 [64][64][3][3], y = act2(conv(x, w2) * scale2 + shift2) [n][64][h][w]; with w3 [256][64] (then res [n][256][h][w] too, act2 = ReLU):
    y = relu((w3 . relu(conv * scale2 + shift2)) * scale3 + shift3 + res) [n][256][h][w] - the tail of a ResNet-50 layer1 bottleneck.
