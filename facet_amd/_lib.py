@@ -91,6 +91,7 @@ SIGNATURES = {
                                C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "fe_op_gate_rowpool": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, _f32p, C.c_int,
                                      C.c_int, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int)]),
+    "fe_op_wino64": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p]),
     "fe_op_topiq_gate64": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float,
                                      _f32p, _f32p, C.c_int, C.c_int, _f32p]),
     "fe_op_conv3x3_c64": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p,
@@ -536,6 +537,26 @@ class Engine:
         self._ck(self.lib.fe_op_gate_rowpool(self.h, xp, n, h, w, cin, ldx, wp, bp, cout, gp, ACT[act], th, tw, int(bool(fused)),
                                              y.ctypes.data_as(_f32p), C.byref(routed)))
         return np.ascontiguousarray(y.transpose(0, 3, 1, 2)), bool(routed.value)
+
+    def wino64_conv(self, x, w, scale=None, shift=None, res=None, res_after_act=False, act=None):
+        """Test hook of the in-register Winograd kernel (fp32 3x3, stride 1, padding 1, up to 64 -> 64 channels, both multiples of 4), launched
+        alone whatever conv2d's routing would choose: act = None, "relu" or "gelu"."""
+        x, xp = _f32(x)
+        w, wp = _f32(w)
+        n, c, h, ww = x.shape
+        cout = w.shape[0]
+        assert w.shape == (cout, c, 3, 3)
+        y = np.empty((n, cout, h, ww), np.float32)
+        sp = hp = rp = None
+        if scale is not None:
+            scale, sp = _f32(scale)
+        if shift is not None:
+            shift, hp = _f32(shift)
+        if res is not None:
+            res, rp = _f32(res)
+            assert res.shape == y.shape
+        self._ck(self.lib.fe_op_wino64(self.h, xp, n, c, h, ww, wp, cout, sp, hp, rp, int(res_after_act), ACT[act], y.ctypes.data_as(_f32p)))
+        return y
 
     def topiq_gate64(self, x, w0, b0, w2, b2, w4, b4, wx, bx, wblk_act="gelu", gate_act="gelu"):
         """Test hook of the fused gate + 16x16 pool of TOPIQ's 64-channel level (2-byte precisions): x [n, 64, h, w]."""

@@ -1,6 +1,7 @@
 // C ABI: single operators and kernels launched alone, the test hooks of the suite.
 #include "capi_internal.h"
 #include "fp8_core.h"
+#include "wino64_maps.h"
 
 // ---- staging of the element-typed test hooks (fe_op_plane, fe_op_rowpass, fe_op_gemm_skinny) ---------------------------------------------
 // n host floats -> n values of type E in the arena, rounded on the device; the array starts `off` elements past a 256-byte boundary
@@ -161,6 +162,26 @@ int fe_op_gate_rowpool(fe_ctx* ctx, const float* x, int n, int h, int w, int cin
     FE_HIP(hipMemcpyAsync(y, pooled.p, pooled.numel() * sizeof(float), hipMemcpyDeviceToHost, C.stream));
     FE_HIP(hipStreamSynchronize(C.stream));
     if (routed) *routed = took;
+  });
+}
+
+int fe_op_wino64(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const float* weight, int cout, const float* scale, const float* shift,
+                 const float* res, int res_after_act, int act, float* y) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(x && weight && y && n > 0 && h > 0 && w > 0 && c > 0 && c <= 64 && c % 4 == 0 && cout > 0 && cout <= 64 && cout % 4 == 0, "bad wino64 arguments");
+    FE_CHECK(C.precision == PREC_F32, "fe_op_wino64: fp32 contexts only");
+    C.arena.reset();
+    std::vector<float> U(w64::U_FLOATS);
+    w64::pack_u(weight, cout, c, U.data());
+    const float* dU = upload(C, U.data(), U.size());
+    const float *ds = upload(C, scale, (size_t)cout), *dh = upload(C, shift, (size_t)cout);
+    Tensor xt = upload_nchw(C, x, n, c, h, w, c);
+    Tensor rt;
+    if (res) rt = upload_nchw(C, res, n, cout, h, w, cout);
+    Tensor yt = C.arena.tensor(n, h, w, cout);
+    launch_wino64(xt, yt, dU, ds, dh, nullptr, act, res ? &rt : nullptr, res_after_act, C.stream);
+    download_nchw(C, yt, cout, y);      // synchronises: U is read by then
   });
 }
 

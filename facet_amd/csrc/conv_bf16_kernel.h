@@ -763,6 +763,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 ? 1 : (TM * TN >= 8
             if constexpr (S32) { if (p.res32) rs_ = p.res32[(size_t)m * p.ldr32 + col]; }
             if (!p.res_after_act) v += rs_;
             if constexpr (MODE == 2) v = v > 0.f ? v : v * p.slope[col];
+            else if (p.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));      // (ocml's erff, as before fe_erf: rare, and the 2-byte results keep their bits)
             else v = fe_apply_act(v, p.act);
             if (p.res_after_act) v += rs_;
             if (p.gate) v *= (float)p.gate[(size_t)m * p.ldg + (p.gate_c1 ? 0 : col)];

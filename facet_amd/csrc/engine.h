@@ -124,6 +124,13 @@ void linear_forward(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16*
                     const bf16* res = nullptr, int ldr = 0);
 void linear_forward(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, f16* y, int ldy, int act,
                     const f16* res = nullptr, int ldr = 0);
+// fp32 rows that are the tokens of B images, L each (the transformer layers of the TOPIQ head). linear_forward picks its few-row kernel by
+// the row count, so an image's route - and the last bits of its score - would depend on what it is batched with; here the route follows L:
+// images of at most 32 tokens take the few-row kernel in chunks of 32 rows whatever B is (a row's sum does not depend on its chunk), larger
+// ones never reach it.
+void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act);
+template <class T>
+inline void linear_tokens(Ctx& c, const ConvW& w, const T* x, int ldx, int B, int L, T* y, int ldy, int act) { linear_forward(c, w, x, ldx, B * L, y, ldy, act); }
 // 2-byte operand rows, fp32 residual rows (nullable) and fp32 result rows (the projections that write an fp32 token stream)
 void linear_forward_s32(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float* y, int ldy, int act, const float* res = nullptr, int ldr = 0);
 void linear_forward_s32(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, float* y, int ldy, int act, const float* res = nullptr, int ldr = 0);
@@ -151,6 +158,9 @@ void conv_forward(Ctx& c, const ConvW& w, const TensorH& x, const TensorH& y, co
 void conv_forward(Ctx& c, const ConvW& w, const TensorF16& x, const TensorF16& y, const ConvOptsT<f16>& o);
 // fp32: whether this layer can run with the row-pooling epilogue (ConvOpts::pool_kw = kw, ConvOpts::pool); conv_forward asserts it
 bool conv_rowpool_ok(const Ctx& c, const ConvW& w, const Tensor& x, const ConvOpts& o, int kw);
+// fp32: the layer on the in-register Winograd kernel (3x3, stride 1, pad 1, a packed ConvW::wino64 operand), with its profile record
+// "wino64 3x3 M= K= N=" and FLOP accounting. false = not launched: the layer or the views do not fit. The caller decides on the activation.
+bool conv_wino64(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, const ConvOpts& o);
 // Allocates the output from the arena with the standard conv output size.
 template <class T>
 TensorT<T> conv_new(Ctx& c, const ConvW& w, const TensorT<T>& x, const ConvOptsT<T>& o);

@@ -269,6 +269,40 @@ bool conv_rowpool_ok(const Ctx& c, const ConvW& w, const Tensor& x, const ConvOp
   return img < 0xF0000000ull && wspan < 0xFFFFFF00ull && x.pixels() < (1ull << 31);
 }
 
+// The in-register Winograd F(2x2,3x3) kernel (kernels_wino64.hip) for a 3x3 stride-1 pad-1 layer with a packed wino64 operand: the launch,
+// its profile record and the executed-FLOP accounting. Returns false, with nothing launched, where the layer or its views do not fit the
+// kernel. Which activations go this way is the caller's rule (conv_forward: none / ReLU / PReLU; the TOPIQ fp32 head: GELU on large maps).
+bool conv_wino64(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, const ConvOpts& o) {
+  if (!(w.wino64 && c.force_variant == 0 && w.KH == 3 && w.KW == 3 && o.sh == 1 && o.sw == 1 && o.ph == 1 && o.pw == 1 && o.dh == 1 && o.dw == 1 && !o.gate && !o.pool_kw &&
+        x.c == w.CinPad && y.c == w.Cout && y.n == x.n && y.h == x.h && y.w == x.w &&
+        (((uintptr_t)x.p | (uintptr_t)y.p | (uintptr_t)(o.res ? o.res->p : nullptr)) & 15) == 0 && x.ld % 4 == 0 && y.ld % 4 == 0 &&
+        (!o.res || o.res->ld % 4 == 0) && (unsigned long long)x.h * x.w * x.ld * 4ull < 0xF0000000ull && y.pixels() < (1ull << 31)))
+    return false;
+  const int M = (int)y.pixels();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (c.profile) {
+    FE_HIP(hipEventCreate(&e0)); FE_HIP(hipEventCreate(&e1));
+    FE_HIP(hipEventRecord(e0, c.stream));
+  }
+  launch_wino64(x, y, w.wino64, w.scale, w.shift, w.slope, o.act, o.res, o.res_after_act, c.stream);
+  const double direct = 2.0 * M * (double)(9 * w.Cin) * (w.CoutAlg ? w.CoutAlg : w.Cout);
+  if (c.profile) {
+    FE_HIP(hipEventRecord(e1, c.stream));
+    FE_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    FE_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    char nm[128];
+    snprintf(nm, sizeof nm, "wino64 3x3 M=%d K=%d N=%d", M, w.K, w.Cout);
+    const double bytes = 4.0 * ((double)x.pixels() * x.c + (double)y.pixels() * y.c * (o.res ? 2 : 1) + (double)w64::U_FLOATS);
+    c.timings.push_back({nm, direct, bytes, ms});
+  }
+  const double tiles = (double)x.n * ((x.h + 1) / 2) * ((x.w + 1) / 2);
+  c.flops_accum += direct;
+  c.flops_saved += direct - 2.0 * 16.0 * tiles * 64.0 * w.Cout;
+  return true;
+}
+
 void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, const ConvOpts& o) {
   FE_CHECK(x.c == w.CinPad, "conv: input channels %d != packed Cin %d", x.c, w.CinPad);
   FE_CHECK(y.c == w.Cout && y.n == x.n, "conv: output view mismatch (c=%d Cout=%d)", y.c, w.Cout);
@@ -368,35 +402,10 @@ void conv_forward(Ctx& c, const ConvW& w, const Tensor& x, const Tensor& y, cons
     }
   }
   // In-register Winograd F(2x2,3x3) for the 3x3 stride-1 layers over (up to) 64 packed input channels, which the three-launch forms
-  // above leave to the direct kernel: one launch, 16/36 of the direct kernel's multiplies. Epilogues with an erf or exp per output (GELU,
-  // sigmoid, ...) stay on the direct kernel: measured slower here (profiles/wino64_perf.txt).
+  // above leave to the direct kernel (conv_wino64 above). Epilogues with an erf or exp per output (GELU, sigmoid, ...) stay on the direct
+  // kernel here; the TOPIQ fp32 head sends its large GELU layers to conv_wino64 itself (model_topiq.hip).
   static const bool no_wino64 = getenv("FE_NO_WINO64") != nullptr;
-  if (w.wino64 && !no_wino64 && p.variant == 0 && (o.act == ACT_NONE || o.act == ACT_RELU || o.act == ACT_PRELU) && o.sh == 1 && o.sw == 1 && o.ph == 1 && o.pw == 1 && o.dh == 1 && o.dw == 1 && !o.gate && y.h == x.h &&
-      y.w == x.w && (((uintptr_t)x.p | (uintptr_t)y.p | (uintptr_t)(o.res ? o.res->p : nullptr)) & 15) == 0 && x.ld % 4 == 0 && y.ld % 4 == 0 &&
-      (!o.res || o.res->ld % 4 == 0) && (unsigned long long)x.h * x.w * x.ld * 4ull < 0xF0000000ull) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c.profile) {
-      FE_HIP(hipEventCreate(&e0)); FE_HIP(hipEventCreate(&e1));
-      FE_HIP(hipEventRecord(e0, c.stream));
-    }
-    launch_wino64(x, y, w.wino64, w.scale, w.shift, w.slope, o.act, o.res, o.res_after_act, c.stream);
-    const double direct = 2.0 * p.M * (double)(9 * w.Cin) * (w.CoutAlg ? w.CoutAlg : p.Cout);
-    if (c.profile) {
-      FE_HIP(hipEventRecord(e1, c.stream));
-      FE_HIP(hipEventSynchronize(e1));
-      float ms = 0.f;
-      FE_HIP(hipEventElapsedTime(&ms, e0, e1));
-      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-      char nm[128];
-      snprintf(nm, sizeof nm, "wino64 3x3 M=%d K=%d N=%d", p.M, p.K, p.Cout);
-      const double bytes = 4.0 * ((double)x.pixels() * x.c + (double)y.pixels() * y.c * (o.res ? 2 : 1) + (double)w64::U_FLOATS);
-      c.timings.push_back({nm, direct, bytes, ms});
-    }
-    const double tiles = (double)x.n * ((x.h + 1) / 2) * ((x.w + 1) / 2);
-    c.flops_accum += direct;
-    c.flops_saved += direct - 2.0 * 16.0 * tiles * 64.0 * w.Cout;
-    return;
-  }
+  if (!no_wino64 && (o.act == ACT_NONE || o.act == ACT_RELU || o.act == ACT_PRELU) && conv_wino64(c, w, x, y, o)) return;
   // Split-K for few-row, long-K products (ArcFace's 25088 -> 512 embedding layer on a handful of faces; SAMP-Net's eight pattern layers,
   // K = 2592 .. 7524 -> 1024, at micro-batches above 32 rows: SAMP stage 3290 -> 3330 images/s): a single tile row would walk K
   // serially on Cout/64 CUs. K is cut into equal slices that run as ONE batched launch into [splits][M][Cout] partials, which
@@ -899,6 +908,12 @@ void linear_forward_res(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, f1
 void linear_forward_res(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float* y, int ldy, int act, const float* res, int ldr) { linear_forward_s32(c, w, x, ldx, M, y, ldy, act, res, ldr); }
 void linear_forward_res(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, float* y, int ldy, int act, const float* res, int ldr) { linear_forward_s32(c, w, x, ldx, M, y, ldy, act, res, ldr); }
 
+void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act) {
+  const int rows = B * L;
+  if (L > 32 || rows <= 32) { linear_forward(c, w, x, ldx, rows, y, ldy, act); return; }
+  for (int m0 = 0; m0 < rows; m0 += 32) linear_forward(c, w, x + (size_t)m0 * ldx, ldx, std::min(32, rows - m0), y + (size_t)m0 * ldy, ldy, act);
+}
+
 template <class T, class RT>
 void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, int ldkv, int B, int Lq, int Lk,
                  const RT* res, int ldr, RT* y, int ldy, bool causal) {
@@ -915,8 +930,8 @@ void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, 
   FE_CHECK(flash || !half, "attention(bf16) needs head_dim 64");
   T* S = flash ? nullptr : c.arena.array<T>((size_t)B * H * Lq * Lp);
   T* O = c.arena.array<T>((size_t)B * Lq * d);
-  linear_forward(c, m.q, q_in, ldq, B * Lq, Q, d, ACT_NONE);
-  linear_forward(c, m.k, kv_in, ldkv, B * Lk, K, d, ACT_NONE);
+  linear_tokens(c, m.q, q_in, ldq, B, Lq, Q, d, ACT_NONE);      // (fp32: the route follows the image, not the batch)
+  linear_tokens(c, m.k, kv_in, ldkv, B, Lk, K, d, ACT_NONE);
   if (Lp != Lk) FE_HIP(hipMemsetAsync(Vt, 0, (size_t)B * d * Lp * sizeof(T), c.stream));
   {  // V^T[b] [d][Lk] = Wv [d][d] . X_b^T : the token matrix plays the weight operand
     ConvParamsT<T> p{};

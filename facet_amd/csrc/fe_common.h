@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fe_check.h"
+#include "erf_core.h"
 #include <cstdint>
 #include <cstdio>
 #include <atomic>
@@ -46,7 +47,7 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SIGMOID = 3, ACT_
 // Softplus follows torch.nn.Softplus(beta=1, threshold=20): x above the threshold passes through.
 __device__ __forceinline__ float fe_apply_act(float v, int act) {
   if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+  if (act == ACT_GELU) return fe_gelu_erf(v);      // branch-free erf, <= 2 ulp (erf_core.h)
   if (act == ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
   if (act == ACT_SOFTPLUS) return v > 20.f ? v : log1pf(expf(v));
   if (act == ACT_QUICKGELU) return v / (1.f + __expf(-1.702f * v));
@@ -57,7 +58,7 @@ __device__ __forceinline__ float fe_rcp_fast(float x) { return __builtin_amdgcn_
 
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute): ~12 instructions against ocml's erff (~40 with its branches). The GELU
 // built on it is within 1e-7 * |x| of the erf form - used where a result is NOT rounded to 2 bytes afterwards but fp32's last bits do
-// not matter either (the split-pair and fp32-stream epilogues of the 2-byte kernels; the fp32 kernels keep erff).
+// not matter either (the split-pair and fp32-stream epilogues of the 2-byte kernels; the fp32 kernels use fe_erf, erf_core.h).
 __device__ __forceinline__ float fe_erf_as(float x) {
   const float ax = fabsf(x);
   const float t = fe_rcp_fast(1.0f + 0.3275911f * ax);

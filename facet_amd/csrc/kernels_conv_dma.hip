@@ -651,7 +651,7 @@ __global__ __launch_bounds__(256, (MODE == 1 ? 4 : (TM * TN >= 8 ? 2 : (TM * TN 
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
       } else if (act == ACT_GELU) {
   #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = 0.5f * v[e] * (1.f + erff(v[e] * 0.70710678118654752440f));
+        for (int e = 0; e < 4; ++e) v[e] = fe_gelu_erf(v[e]);
       } else if (act == ACT_SIGMOID) {
   #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = 1.f / (1.f + __expf(-v[e]));

@@ -7,7 +7,7 @@
 //   * a wave holds all 16 planes of its 32 tiles x 32 channels as accumulators (256 registers, one wave per SIMD);
 //   * input transform in-lane: a lane reads the 4 x 4 patch of its tile for its channel pair from the LDS patch (16 8-byte reads per two
 //     K-steps), forms the 16 plane values with adds, and issues 16 matrix instructions per K-step into 16 independent accumulators;
-//   * output transform in-lane, then scale / shift / residual / ReLU or PReLU (fe_apply_act, as the direct kernel) and 16-byte stores;
+//   * output transform in-lane, then scale / shift / residual / ReLU, PReLU or GELU (fe_apply_act, as the direct kernel) and 16-byte stores;
 //   * persistent workgroups, one per CU; the K loop runs in stages of 8 input channels (4 K-steps). A stage's patch chunk (11.5 KB) sits
 //     in LDS, double buffered: the next one - of this block or the next block - is fetched into registers under the current stage's
 //     matrix instructions and stored behind them;
@@ -32,8 +32,10 @@ struct W64Params {
 
 constexpr int W64_PATCH_FLOATS = w64::CHUNK_UNITS * 2;
 
-// A: the activation - ACT_NONE, ACT_RELU or ACT_PRELU. With one wave per SIMD nothing hides the epilogue's vector work behind another wave's
-// matrix instructions: an erf or exp per output (GELU, sigmoid) made the kernel slower than the direct one, so conv_forward keeps those there.
+// A: the activation - ACT_NONE, ACT_RELU, ACT_PRELU or ACT_GELU. With one wave per SIMD nothing hides the epilogue's vector work behind another
+// wave's matrix instructions. ocml's erff or an exp with its division per output (GELU, sigmoid) made the kernel slower than the direct one, so
+// conv_forward keeps those there; with the branch-free fe_erf (erf_core.h) the GELU form is the faster one on large maps, and the TOPIQ fp32 head
+// calls it for its 64 -> 64 layers (conv_wino64, engine.hip; profiles/erf_gelu_perf.txt).
 template <int A>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino64_kernel(const W64Params p) {
   using namespace w64;
@@ -212,7 +214,7 @@ void launch_wino64(const Tensor& x, const Tensor& y, const float* U, const float
            x.w, x.c, y.h, y.w, y.c);
   FE_CHECK(x.ld % 4 == 0 && y.ld % 4 == 0 && (((uintptr_t)x.p | (uintptr_t)y.p | (uintptr_t)U) & 15) == 0, "wino64: operands must be 16-byte aligned");
   FE_CHECK(!res || (res->ld % 4 == 0 && ((uintptr_t)res->p & 15) == 0 && res->c == y.c && res->pixels() == y.pixels()), "wino64: residual view");
-  FE_CHECK(act == ACT_NONE || act == ACT_RELU || (act == ACT_PRELU && slope), "wino64: activation %d (PReLU needs slopes)", act);
+  FE_CHECK(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU || (act == ACT_PRELU && slope), "wino64: activation %d (PReLU needs slopes)", act);
   FE_CHECK((unsigned long long)x.h * x.w * x.ld * 4ull < 0xF0000000ull, "wino64: one image must stay below 4 GiB (32-bit buffer offsets)");
   W64Params p{};
   p.x = x.p; p.ldx = x.ld; p.cin = x.c; p.N = x.n; p.H = x.h; p.W = x.w;
@@ -227,6 +229,7 @@ void launch_wino64(const Tensor& x, const Tensor& y, const float* U, const float
   const int grid = p.nblocks < 256 ? p.nblocks : 256;      // one workgroup per CU
   if (act == ACT_NONE) hipLaunchKernelGGL(wino64_kernel<ACT_NONE>, dim3(grid), dim3(256), 0, s, p);
   else if (act == ACT_RELU) hipLaunchKernelGGL(wino64_kernel<ACT_RELU>, dim3(grid), dim3(256), 0, s, p);
+  else if (act == ACT_GELU) hipLaunchKernelGGL(wino64_kernel<ACT_GELU>, dim3(grid), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(wino64_kernel<ACT_PRELU>, dim3(grid), dim3(256), 0, s, p);
   FE_HIP(hipGetLastError());
 }

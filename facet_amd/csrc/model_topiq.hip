@@ -163,7 +163,7 @@ static void enc_forward(Ctx& c, const EncLayerW& e, T* x, T* y, int B, int L) {
   ln(c, e.n1, x, n, rows);
   mha_forward<T>(c, e.attn, n, d, n, d, B, L, L, x, d, a, d);
   ln(c, e.n2, a, n, rows);
-  linear_forward(c, e.lin1, n, d, rows, hbuf, ff, ACT_GELU);
+  linear_tokens(c, e.lin1, n, d, B, L, hbuf, ff, ACT_GELU);
   linear_forward(c, e.lin2, hbuf, ff, rows, y, d, ACT_NONE, a, d);
   c.arena.rewind(mark);
 }
@@ -181,7 +181,7 @@ static void dec_forward(Ctx& c, const DecLayerW& w, T* tgt, const T* memory, int
   ln(c, w.n1, (const T*)tgt, t2, B * Lq);
   mha_forward<T>(c, w.cross, t2, d, mem, d, B, Lq, Lk, tgt, d, a, d);
   ln(c, w.n3, (const T*)a, t2, B * Lq);
-  linear_forward(c, w.lin1, t2, d, B * Lq, hbuf, ff, ACT_GELU);
+  linear_tokens(c, w.lin1, t2, d, B, Lq, hbuf, ff, ACT_GELU);
   linear_forward(c, w.lin2, hbuf, ff, B * Lq, tgt, d, ACT_NONE, a, d);
   c.arena.rewind(mark);
 }
@@ -278,6 +278,18 @@ void topiq_head_forward(Ctx& c, TopiqModel& m, const std::vector<TensorT<T>>& fe
           c.timings.push_back({nm, flops, 2.0 * (double)wa.pixels() * 128, ms});
         }
         c.flops_accum += flops; c.flops_half += flops;
+        tiled = true;
+      }
+    }
+    if constexpr (sizeof(T) == 4) {
+      // fp32: the in-register Winograd kernel with the GELU epilogue (conv_forward keeps GELU layers on the direct kernel), on maps of at
+      // least 1 MiB per image: measured faster there (profiles/erf_gelu_perf.txt). Per image, not per batch, as the row-pool route below:
+      // an image's route does not depend on what it is batched with, and the scores of small images keep their bits.
+      const bool no_head_wino64 = getenv("FE_NO_HEAD_WINO64") != nullptr || getenv("FE_NO_WINO64") != nullptr;      // A/B hooks, read per call
+      const bool large = (size_t)wa.h * wa.w * g.w2.Cout * sizeof(float) >= ((size_t)1 << 20);
+      if (g.w2.wino64 && m.wblk_act == ACT_GELU && large && !no_head_wino64) {
+        wb = c.arena.tensor(wa.n, wa.h, wa.w, g.w2.Cout);
+        if (!conv_wino64(c, g.w2, wa, wb, o2)) conv_forward(c, g.w2, wa, wb, o2);      // (views that do not fit the kernel)
         tiled = true;
       }
     }

@@ -277,6 +277,12 @@ int fe_op_topiq_gate64(fe_ctx* ctx, const float* x, int n, int h, int w, const f
    plain conv + adaptive pool. *routed (may be NULL) = 1 when the row-pooling route ran. fp32 contexts only. */
 int fe_op_gate_rowpool(fe_ctx* ctx, const float* x, int n, int h, int w, int cin, int ldx, const float* weight, const float* bias, int cout,
                        const float* gate, int act, int th, int tw, int fused, float* y, int* routed);
+/* test hook of the in-register Winograd F(2x2,3x3) kernel (kernels_wino64.hip; fp32 contexts only), launched alone, whatever route
+   fe_op_conv2d would choose: x [n][c][h][w] with c <= 64, weight [cout][c][3][3] with cout <= 64 (c and cout multiples of 4), stride 1,
+   padding 1; y = act(conv * scale + shift [+ res]) [+ res when res_after_act] as [n][cout][h][w]. scale / shift / res may be NULL;
+   act = FE_ACT_NONE, FE_ACT_RELU or FE_ACT_GELU. */
+int fe_op_wino64(fe_ctx* ctx, const float* x, int n, int c, int h, int w, const float* weight, int cout, const float* scale, const float* shift,
+                 const float* res, int res_after_act, int act, float* y);
 /* test hook of the halo-tiled 3x3 convolution 64 -> 64 (stride 1, padding 1; kernels_c64.hip; 2-byte precisions only): x [n][64][h][w],
    w2 [64][64][3][3], y = act2(conv(x, w2) * scale2 + shift2) [n][64][h][w]; with w3 [256][64] (then res [n][256][h][w] too, act2 = ReLU):
    y = relu((w3 . relu(conv * scale2 + shift2)) * scale3 + shift3 + res) [n][256][h][w] - the tail of a ResNet-50 layer1 bottleneck.
