@@ -48,6 +48,7 @@ class EngineCapacityError(EngineError):
 FE_ERR_INVALID = -1
 FE_ERR_CAPACITY = -4
 FE_MIXED_CLIP, FE_MIXED_SAMP = 0, 1      # fe_preprocess224_mixed modes
+FE_ORDER_BGR, FE_ORDER_RGB = 0, 1        # fe_image_stats_mixed: byte order of a pixel
 
 
 _lib = None
@@ -188,6 +189,8 @@ SIGNATURES = {
     "fe_face_analyze": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                   C.c_int, _f32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fe_image_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "fe_image_stats_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "fe_set_stats_segment": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_roi_laplacian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double)]),
     "fe_cv_resize_linear_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -1456,6 +1459,22 @@ class Engine:
                                          gray.ctypes.data_as(C.c_void_p) if want_gray else None,
                                          hsv.ctypes.data_as(C.c_void_p) if want_hsv else None))
         return stats, gray, hsv
+
+    def image_stats_mixed(self, images, order='bgr'):
+        """image_stats for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for resident
+        images, any h, w >= 1. order 'bgr' / 'rgb' (or FE_ORDER_*): the byte order of a pixel. -> stats float64 [n, 264] in input order,
+        every double equal to image_stats's for that image. include/facet_engine.h fe_image_stats_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        stats = np.empty((n, FE_STATS_DOUBLES), np.float64)
+        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
+        self._ck(self.lib.fe_image_stats_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o),
+                                               stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return stats
+
+    def set_stats_segment(self, pixels=0):
+        """Pixels per segment of image_stats_mixed's first pass: 0 = the default, else a multiple of 4096 (>= 4096). The records do not
+        depend on it."""
+        self._ck(self.lib.fe_set_stats_segment(self.h, int(pixels)))
 
     def roi_laplacian(self, images, img_index, rois):
         """rois int [m,4] (x1,y1,x2,y2 exclusive, clipped) -> float64 [m,4]: sum lap, sum lap^2, sum gray, pixel count."""

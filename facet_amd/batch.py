@@ -24,9 +24,10 @@ fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_sub
 
 Mixed sizes: `process_images` / `process_files` take a chunk of photos of any sizes. By default the chunk is cut into one process_batch
 per distinct shape. `mixed_sizes=True` uploads the chunk once and scores all of it with ONE fe_ensemble_score_mixed call (CLIP and SAMP
-crops gather across shapes into the towers' usual chunks; TOPIQ runs per shape group inside that call); statistics, faces, lines,
-pHash, thumbnails and the subject region still run per shape group on the resident pixels, and the dicts come back in input order
-with the same keys.
+crops gather across shapes into the towers' usual chunks; TOPIQ runs per shape group inside that call) and computes the technical
+statistics of all of it with ONE fe_image_stats_mixed call on the RGB pixels; faces, lines, pHash, thumbnails and the subject region
+still run per shape group on a BGR copy of the resident pixels (made only when one of them is on), and the dicts come back in input
+order with the same keys.
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -102,14 +103,16 @@ class BatchScorer:
         self.tag_threshold, self.max_tags = tag_threshold, max_tags           # utils/tags.py:50-51 defaults
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
-    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False):
+    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False, _tech=None):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
         _resident (process_files): (device_ptr, n, h, w) of an RGB batch that is already on the device, handed over - it is freed here -
         with images_rgb None; the pixels are fetched only when a stage that works on host arrays (face thumbnails cut by Pillow, the VLM analyzer) is on.
         _records (the mixed-size path): (records [n, 789], mask) of these images, computed by the caller - the ensemble call is skipped.
-        _borrowed: the resident batch stays the caller's and is not freed here."""
+        _borrowed: the resident batch stays the caller's and is not freed here.
+        _tech (the mixed-size path): the technical dicts of these images (TechnicalAnalyzer.analyze_mixed), computed by the caller - the
+        statistics call is skipped, and the BGR copy is made only when a stage that reads it is on."""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -127,14 +130,20 @@ class BatchScorer:
                     or self.vlm_composition is not None:      # face thumbnails cut on the engine need no host pixels
                 imgs = np.empty((n, h, w, 3), np.uint8)
                 e.d2h(imgs, d_rgb)
-            d_bgr = e.dev_alloc(n * h * w * 3)
-            e.swap_rb(d_rgb, n * h * w, d_bgr)
-            rgb_dev, bgr_dev = (d_rgb, n, h, w), (d_bgr, n, h, w)
+            faces_on = self.face_analyzer is not None and self.face_analyzer.available
+            bgr_dev = None
+            if _tech is None or faces_on or (leading_lines is None and self.detect_lines) or self.phash or self.thumbnails or self.subject_region:
+                d_bgr = e.dev_alloc(n * h * w * 3)
+                e.swap_rb(d_rgb, n * h * w, d_bgr)
+                bgr_dev = (d_bgr, n, h, w)
+            rgb_dev = (d_rgb, n, h, w)
 
             def rest(eng):      # everything that is not a model of the ensemble; reads the BGR copy only
-                tech_ = TechnicalAnalyzer.analyze_batch(eng, bgr_dev, self.shadow_threshold, self.highlight_threshold, self.mono_threshold)
+                tech_ = _tech
+                if tech_ is None:
+                    tech_ = TechnicalAnalyzer.analyze_batch(eng, bgr_dev, self.shadow_threshold, self.highlight_threshold, self.mono_threshold)
                 faces_ = None
-                if self.face_analyzer is not None and self.face_analyzer.available:
+                if faces_on:
                     faces_ = self.face_analyzer.analyze_faces_batch([imgs[i][..., ::-1] for i in range(n)] if imgs is not None else None,
                                                                     resident=bgr_dev)
                 lines_ = leading_lines
@@ -289,17 +298,32 @@ class BatchScorer:
 
     def _process_mixed(self, entries, out, exif, leading_lines):
         """entries: [(indices into out, (device_ptr, k, h, w), owned)] - resident RGB batches of one shape each. One ensemble_score_mixed call
-        over every image of every entry, by pointers into the resident batches; then process_batch per entry for the stages that run per
-        shape, with its records handed in. An owned batch is freed by process_batch (or here, when the ensemble call fails)."""
+        and one analyze_mixed call over every image of every entry, by pointers into the resident batches (the second on the aux engine's
+        worker beside the first when there is one); then process_batch per entry for the stages that run per shape, with its records and
+        technical dicts handed in. An owned batch is freed by process_batch (or here, when the ensemble call fails)."""
         e = self.engine
         order, ptrs, sizes = [], [], []
         for idx, (p, k, h, w), _ in entries:
             base = p.value if isinstance(p, ctypes.c_void_p) else int(p)
             for j, i in enumerate(idx):
                 order.append(i); ptrs.append(base + j * h * w * 3); sizes.append((h, w))
-        by_input = sorted(range(len(order)), key=lambda r: order[r])      # the call sees the images in input order
+        by_input = sorted(range(len(order)), key=lambda r: order[r])      # the calls see the images in input order
+        resident = ([ptrs[r] for r in by_input], [sizes[r] for r in by_input])
+
+        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels
+            return TechnicalAnalyzer.analyze_mixed(eng, resident, self.shadow_threshold, self.highlight_threshold, self.mono_threshold, order='rgb')
+
         try:
-            rec, mask = e.ensemble_score_mixed(([ptrs[r] for r in by_input], [sizes[r] for r in by_input]))
+            if self._pool is not None:      # beside the ensemble call, on the aux context (module docstring, "Overlap")
+                e.sync()                    # whatever filled the resident batches on this context's stream is complete
+                fut = self._pool.submit(stats, self.aux_engine)
+                try:
+                    rec, mask = e.ensemble_score_mixed(resident)
+                finally:
+                    tech = fut.result()      # also on error: the worker must be done before the buffers go
+            else:
+                rec, mask = e.ensemble_score_mixed(resident)
+                tech = stats(e)
         except Exception:
             for _, dev, owned in entries:
                 if owned:
@@ -310,7 +334,7 @@ class BatchScorer:
             try:
                 res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
                                          leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev,
-                                         _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned)
+                                         _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned, _tech=[tech[row[i]] for i in idx])
             except Exception:
                 for _, dev2, owned2 in entries[n_done + 1:]:
                     if owned2:

@@ -423,6 +423,84 @@ int fe_image_stats(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_
   });
 }
 
+/* The records of fe_image_stats for a list of images of any sizes: the plan of stats_plan.h, chunk by chunk */
+int fe_image_stats_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, double* stats) {
+  return fe_api(ctx, OnError::Capacity, [&]() -> int {
+    namespace sp = fe::stats_plan;
+    Ctx& C = ctx->c;
+    char b[200];
+    if (!images || !hw || !stats || n <= 0) { C.err = "fe_image_stats_mixed: bad arguments (null list, null stats or n <= 0)"; return FE_ERR_INVALID; }
+    if (order != FE_ORDER_BGR && order != FE_ORDER_RGB) {
+      snprintf(b, sizeof b, "fe_image_stats_mixed: order %d is neither FE_ORDER_BGR (0) nor FE_ORDER_RGB (1)", order);
+      C.err = b;
+      return FE_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) {
+      const int h = hw[2 * i], w = hw[2 * i + 1];
+      if (!images[i]) { snprintf(b, sizeof b, "fe_image_stats_mixed: image %d is a null pointer", i); C.err = b; return FE_ERR_INVALID; }
+      if (h < 1 || w < 1 || (size_t)h * (size_t)w >= ((size_t)1 << 31)) {
+        snprintf(b, sizeof b, "fe_image_stats_mixed: image %d is %d x %d (h x w); each side must be at least 1 and h * w below 2^31", i, h, w);
+        C.err = b;
+        return FE_ERR_INVALID;
+      }
+    }
+    const sp::Plan plan = sp::build(hw, n, !on_device, ctx->stats_segment ? ctx->stats_segment : sp::kDefaultSegment, C.arena.capacity());
+    if (plan.bad_image >= 0) {
+      const int i = plan.bad_image;
+      snprintf(b, sizeof b, "fe_image_stats_mixed: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", i, hw[2 * i], hw[2 * i + 1],
+               plan.bad_bytes, C.arena.capacity());
+      throw CapacityError(b);
+    }
+    ensure_hsv_tables(ctx);
+    std::vector<uint8_t> blob;
+    for (const sp::Chunk& ck : plan.chunks) {
+      const sp::Layout& L = ck.lay;
+      C.arena.reset();
+      uint8_t* base = (uint8_t*)C.arena.alloc(L.total);
+      blob.assign(L.blob_bytes, 0);
+      sp::ImageDesc* im = (sp::ImageDesc*)blob.data();
+      for (int k = 0; k < ck.count; ++k) {
+        const int i = ck.first + k;
+        const uint8_t* src = images[i];
+        if (!on_device) {      // the host images lie anywhere: one copy each, to a 256-byte boundary of the stage region
+          uint8_t* d = base + L.stage + ck.stage_off[k];
+          FE_HIP(hipMemcpyAsync(d, src, (size_t)hw[2 * i] * hw[2 * i + 1] * 3, hipMemcpyHostToDevice, C.stream));
+          src = d;
+        }
+        im[k] = sp::ImageDesc{src, base + L.gray + ck.gray_off[k], hw[2 * i], hw[2 * i + 1], ck.nseg[k], 0};
+      }
+      memcpy(blob.data() + L.blob_segs, ck.segs.data(), ck.segs.size() * sizeof(sp::SegDesc));
+      memcpy(blob.data() + L.blob_strips, ck.strips.data(), ck.strips.size() * sizeof(sp::StripDesc));
+      if (!ck.multi.empty()) memcpy(blob.data() + L.blob_multi, ck.multi.data(), ck.multi.size() * sizeof(int32_t));
+      uint8_t* d_blob = base + L.blob;
+      FE_HIP(hipMemcpyAsync(d_blob, blob.data(), L.blob_bytes, hipMemcpyHostToDevice, C.stream));
+      double* d_out = (double*)(base + L.records);
+      launch_image_stats_mixed((const sp::ImageDesc*)d_blob, ck.count, (const sp::SegDesc*)(d_blob + L.blob_segs), (int)ck.segs.size(),
+                               (const sp::StripDesc*)(d_blob + L.blob_strips), (int)ck.strips.size(), (const int32_t*)(d_blob + L.blob_multi),
+                               (int)ck.multi.size(), order == FE_ORDER_RGB, ctx->hsv_sdiv, ctx->hsv_hdiv, base + L.accum, L.zero_bytes,
+                               (unsigned int*)(base + L.hist), d_out, C.stream);
+      FE_HIP(hipMemcpyAsync(stats + (size_t)ck.first * FE_STATS_COUNT, d_out, (size_t)ck.count * FE_STATS_COUNT * sizeof(double), hipMemcpyDeviceToHost,
+                            C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));   // the arena and the blob are recycled by the next chunk
+    }
+    return FE_OK;
+  });
+}
+
+int fe_set_stats_segment(fe_ctx* ctx, int pixels) {
+  return fe_api(ctx, [&]() -> int {
+    if (pixels != 0 && (pixels < fe::stats_plan::kSegmentUnit || pixels % fe::stats_plan::kSegmentUnit != 0)) {
+      char b[160];
+      snprintf(b, sizeof b, "fe_set_stats_segment: %d pixels (0 for the default, or a multiple of %d that is at least %d)", pixels,
+               fe::stats_plan::kSegmentUnit, fe::stats_plan::kSegmentUnit);
+      ctx->c.err = b;
+      return FE_ERR_INVALID;
+    }
+    ctx->stats_segment = pixels;
+    return FE_OK;
+  });
+}
+
 /* RGB <-> BGR copy of a packed uint8 batch into device memory */
 int fe_swap_rb_u8(fe_ctx* ctx, const uint8_t* src, int on_device, size_t pixels, uint8_t* dst_device) {
   return fe_api(ctx, [&] {

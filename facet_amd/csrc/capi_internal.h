@@ -30,6 +30,7 @@ struct fe_ctx {
   // capi_image.hip
   int* hsv_sdiv = nullptr; int* hsv_hdiv = nullptr;   // cv2 HSV division tables
   double* phash_cos = nullptr;                        // DCT-II cosine table of fe_phash
+  int stats_segment = 0;                              // fe_set_stats_segment: pixels per pass-1 segment of fe_image_stats_mixed, 0 = default
   std::vector<void*> misc_allocs;                     // these tables and capi_face.hip's, for fe_destroy
   // capi_models.hip
   float* clip_in = nullptr;  // preprocessed CLIP crops waiting for a full tower batch (ClipBatcher)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "fe_check.h"
 #include "erf_core.h"
+#include "stats_plan.h"
 #include <cstdint>
 #include <cstdio>
 #include <atomic>
@@ -484,6 +485,11 @@ size_t stats_accum_bytes(int n);
 void launch_image_stats(const uint8_t* bgr, int n, int h, int w, uint8_t* gray, uint8_t* hsv_out, const int* sdiv, const int* hdiv, void* accum,
                         double* out, hipStream_t s);
 void cv_hsv_tables(std::vector<int>& sdiv, std::vector<int>& hdiv);
+// One chunk of a mixed-size statistics call (stats_plan.h has the plan and the descriptor types). zero: device block of zero_bytes that
+// starts with the chunk's n accumulators and holds its n hue-saturation histograms at ghist; out: device [n][FE_STATS_COUNT] doubles.
+void launch_image_stats_mixed(const stats_plan::ImageDesc* images, int n, const stats_plan::SegDesc* segs, int n_segs,
+                              const stats_plan::StripDesc* strips, int n_strips, const int32_t* multi, int n_multi, int rgb, const int* sdiv,
+                              const int* hdiv, void* zero, size_t zero_bytes, unsigned int* ghist, double* out, hipStream_t s);
 // rois: device int [m][4] = x1,y1,x2,y2 (already clipped to the image, x2/y2 exclusive); out: device double [m][4]
 void launch_roi_laplacian(const uint8_t* bgr, int h, int w, const int* img_of, const int* rois, int m, double* out, hipStream_t s);
 // kernels_lines.hip: Gaussian 5x5 + Canny non-maximum-suppression map on the GPU (host stage: lines_host.h)

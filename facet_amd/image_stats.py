@@ -48,6 +48,14 @@ class ImageCache:
         shape = images[2:4] if isinstance(images, tuple) else np.asarray(images).shape[1:3]
         return [cls(_record=st[i], _shape=shape, _gray=None if g is None else g[i], _hsv=None if hv is None else hv[i]) for i in range(st.shape[0])]
 
+    @classmethod
+    def from_mixed(cls, engine, images, order='bgr'):
+        """images: a list of uint8 [h,w,3] arrays of any sizes, or (device_pointers, sizes) -> list[ImageCache] in input order, one engine
+        call (fe_image_stats_mixed). order: 'bgr' or 'rgb', the byte order of the pixels. No planes are kept."""
+        st = engine.image_stats_mixed(images, order=order)
+        shapes = images[1] if isinstance(images, tuple) else [np.asarray(a).shape[:2] for a in images]
+        return [cls(_record=st[i], _shape=shapes[i]) for i in range(st.shape[0])]
+
     # -- order statistics of the gray plane from its histogram ---------------------------------------------------------
     def _order_stat(self, k):
         if self._cum is None:
@@ -174,9 +182,19 @@ class TechnicalAnalyzer:
     @staticmethod
     def analyze_batch(engine, images, shadow_threshold=0.15, highlight_threshold=0.10, mono_threshold=0.1):
         """The seven dicts multi_pass.py:425-444 computes per image, for a whole BGR batch with one engine call."""
+        return TechnicalAnalyzer._dicts(ImageCache.from_batch(engine, images), shadow_threshold, highlight_threshold, mono_threshold)
+
+    @staticmethod
+    def analyze_mixed(engine, images, shadow_threshold=0.15, highlight_threshold=0.10, mono_threshold=0.1, order='bgr'):
+        """analyze_batch for images that each have their own size (a list of arrays, or (device_pointers, sizes)), in input order, with
+        one engine call; order 'bgr' or 'rgb' is the byte order of the pixels."""
+        return TechnicalAnalyzer._dicts(ImageCache.from_mixed(engine, images, order), shadow_threshold, highlight_threshold, mono_threshold)
+
+    @staticmethod
+    def _dicts(caches, shadow_threshold, highlight_threshold, mono_threshold):
         T = TechnicalAnalyzer
         out = []
-        for c in ImageCache.from_batch(engine, images):
+        for c in caches:
             out.append({'sharpness': T.get_sharpness_data(True, c), 'color': T.get_color_harmony_data(True, c),
                         'histogram': T.get_histogram_data(True, shadow_threshold, highlight_threshold, c),
                         'mono': T.detect_monochrome(True, mono_threshold, c), 'dynamic_range': T.get_dynamic_range(True, c),

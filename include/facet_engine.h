@@ -704,6 +704,22 @@ int fe_cv_resize_linear_u8(fe_ctx* ctx, const uint8_t* src, int n, int h, int w,
 #define FE_STATS_DOUBLES 264
 int fe_image_stats(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, double* stats, uint8_t* gray_out,
                    uint8_t* hsv_out);
+/* The records of fe_image_stats for a list of images that each have their own size, in a fixed number of launches per chunk of the list:
+ * every image's pixels are cut into segments that are spread over the device, so one large photo uses as many workgroups as its size
+ * warrants. images [n] pointers to uint8 [h][w][3] images, hw [n][2] = h, w, on_device: as for fe_ensemble_score_mixed; device images may
+ * sit at any byte alignment. Any h, w >= 1 with h * w < 2^31. order: the three bytes of a pixel are B,G,R (FE_ORDER_BGR, what
+ * fe_image_stats takes) or R,G,B (FE_ORDER_RGB): an RGB batch needs no BGR copy. stats [n][FE_STATS_DOUBLES] (host) in input order, every
+ * double equal to fe_image_stats's for that image, [260] included. Host images are staged chunk by chunk through the arena, device images
+ * are read in place. There are no gray / HSV plane outputs: fe_image_stats is the call for those.
+ * A null pointer, a bad size or a bad order returns FE_ERR_INVALID, the message names the index of the image, nothing is launched. An
+ * image whose own scratch (its pixels when they are staged, h * w gray bytes, 184 320 bytes of histogram, its descriptors) exceeds the
+ * arena returns FE_ERR_CAPACITY, the message names its index, nothing is launched. */
+#define FE_ORDER_BGR 0
+#define FE_ORDER_RGB 1
+int fe_image_stats_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, double* stats);
+/* Pixels per segment of fe_image_stats_mixed's first pass: 0 = the default, otherwise a multiple of 4096 that is at least 4096 (anything
+ * else returns FE_ERR_INVALID and changes nothing). The records do not depend on it. */
+int fe_set_stats_segment(fe_ctx* ctx, int pixels);
 
 /* Laplacian statistics of m rectangular ROIs: what analyzers/face.py:160-176 (eye regions) and :272-279
  * (face crop) compute with cv2.cvtColor(roi, BGR2GRAY) + cv2.Laplacian(gray, CV_64F).var() + np.mean(gray) per face on the CPU.

@@ -4,8 +4,14 @@ mixed_sizes off (one process_batch and one fe_ensemble_score per distinct shape:
 (TOPIQ deselected: the reference's single-pass mode). Prints images/s and the device memory in use before the first and after the
 first and the last chunk of a row. Rows of 1, 2 and 16 shapes repeat their chunk (the second run is timed); the row of 256 shapes runs
 three chunks of 256 shapes each that no earlier chunk had (the last is timed), which is what a library of distinct sizes does to the
-per-size tables. usage: perf_mixed.py [n] [chunks_of_256]     (written to profiles/mixed_sizes_perf.txt)"""
-import os, sys, time
+per-size tables. usage: perf_mixed.py [n] [chunks_of_256] [--mixed-only] [--policies f32,parity]     (written to profiles/mixed_sizes_perf.txt)
+
+perf_mixed.py --stats [--repeats R]: the technical statistics alone (written to profiles/mixed_stats_perf.txt). For the same chunk over 1, 16
+and 256 shapes, resident as RGB: the per-shape-group path as process_batch does it (per group a device allocation, fe_swap_rb_u8,
+fe_image_stats on the BGR copy, the frees), fe_image_stats alone on a BGR copy made beforehand, and one fe_image_stats_mixed call on the
+RGB pixels at the default segment size and at 65 536, 262 144 and 1 048 576 pixels; then one 6000 x 4000 image alone. Every figure is
+the median of R calls after one warm-up call, with the fastest and the slowest beside it."""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -15,8 +21,15 @@ from facet_amd.batch import BatchScorer
 from facet_amd.precision import describe, load_models
 from facet_amd.weights import synthetic_state_dict
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-fresh_chunks = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+ap = argparse.ArgumentParser()
+ap.add_argument("n", nargs="?", type=int, default=256)
+ap.add_argument("chunks_of_256", nargs="?", type=int, default=3)
+ap.add_argument("--mixed-only", action="store_true", help="skip the rows with mixed_sizes off")
+ap.add_argument("--policies", default="f32,parity")
+ap.add_argument("--stats", action="store_true", help="the statistics table instead of the process_images table")
+ap.add_argument("--repeats", type=int, default=7)
+args = ap.parse_args()
+n, fresh_chunks = args.n, args.chunks_of_256
 rng = np.random.default_rng(3)
 yy, xx = np.mgrid[:1400, :1400].astype(np.float32)
 field = np.clip(np.stack([120 + 70 * np.sin(xx / (40.0 + 9 * c)) * np.cos(yy / (55.0 - 7 * c)) for c in range(3)], -1)
@@ -43,11 +56,72 @@ def used_mib():
     return (total - free) / 2**20
 
 
+def timed(call, repeats):
+    """Milliseconds of `call` (which returns after the engine stream has drained): median, fastest, slowest of `repeats` after one warm-up."""
+    call()
+    ts = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        call()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return f"{np.median(ts):9.2f} ({min(ts):.2f} .. {max(ts):.2f})"
+
+
+def stats_rows(e, label, imgs, repeats):
+    """imgs go up once, grouped by shape as _process_images_mixed lays them out; every path reads the resident RGB pixels."""
+    groups = {}
+    for i, a in enumerate(imgs):
+        groups.setdefault(a.shape[:2], []).append(i)
+    bufs, ptrs, sizes = [], [None] * len(imgs), [a.shape[:2] for a in imgs]
+    for (h, w), idx in groups.items():
+        d = e.dev_alloc(len(idx) * h * w * 3)
+        e.h2d(d, np.stack([imgs[i] for i in idx]))
+        bufs.append((d, len(idx), h, w))
+        for j, i in enumerate(idx):
+            ptrs[i] = d.value + j * h * w * 3
+
+    def per_group():
+        for d, k, h, w in bufs:
+            d_bgr = e.dev_alloc(k * h * w * 3)
+            try:
+                e.swap_rb(d, k * h * w, d_bgr)
+                e.image_stats((d_bgr, k, h, w))
+            finally:
+                e.dev_free(d_bgr)
+
+    print(f"{label:22} {'per group: alloc + swap + fe_image_stats':42} {timed(per_group, repeats)}", flush=True)
+    bgr = []
+    for d, k, h, w in bufs:
+        d_bgr = e.dev_alloc(k * h * w * 3)
+        e.swap_rb(d, k * h * w, d_bgr)
+        bgr.append((d_bgr, k, h, w))
+    print(f"{label:22} {'per group: fe_image_stats alone (BGR ready)':42} {timed(lambda: [e.image_stats(b) for b in bgr], repeats)}", flush=True)
+    for b in bgr:
+        e.dev_free(b[0])
+    for seg in (0, 65536, 262144, 1048576):
+        e.set_stats_segment(seg)
+        what = f"fe_image_stats_mixed, segment {seg if seg else 'default'}"
+        print(f"{label:22} {what:42} {timed(lambda: e.image_stats_mixed((ptrs, sizes), order='rgb'), repeats)}", flush=True)
+    e.set_stats_segment(0)
+    for b in bufs:
+        e.dev_free(b[0])
+
+
+if args.stats:
+    e = Engine(0, arena_bytes=4 << 30)
+    print(f"{n} images per chunk, sides 776 .. 1280, resident RGB; milliseconds per chunk: median (fastest .. slowest) of {args.repeats} calls after a warm-up")
+    for n_shapes in (1, 16, 256):
+        shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+        stats_rows(e, f"{n} images, {n_shapes} shapes", chunk(shapes), args.repeats)
+    stats_rows(e, "1 image 4000 x 6000", [np.ascontiguousarray(np.tile(field, (3, 5, 1))[:4000, :6000])], args.repeats)
+    e.close()
+    sys.exit(0)
+
 sds = {m: synthetic_state_dict(m, 4) for m in ("topiq", "clip", "u2netp", "samp_net")}
 aes = synthetic_state_dict("aesthetic", 4)
 print(f"{n} images per chunk, sides 776 .. 1280; images/s of process_images (upload included); device MiB in use: before / after first chunk / after last chunk")
 print(f"{'policy':8} {'mask':>4} {'shapes':>6} {'mixed_sizes':>11} {'images/s':>9} {'MiB before':>11} {'first':>9} {'last':>9}")
-for policy in ("f32", "parity"):
+for policy in args.policies.split(","):
     e = Engine(0, arena_bytes=(4 + 2 * 32) << 30)      # bench.py's arena for micro-batch 32 at 1024 x 1024
     load_models(e, policy, sds)
     e.load_weights(FE_MODEL_AESTHETIC, aes)
@@ -58,7 +132,7 @@ for policy in ("f32", "parity"):
     for mask in (7, 6):
         e.ensemble_select(mask)
         for n_shapes in (1, 2, 16, 256):
-            for mixed in (False, True):
+            for mixed in ((True,) if args.mixed_only else (False, True)):
                 bs = BatchScorer(e, mixed_sizes=mixed)
                 before = used_mib()
                 runs = fresh_chunks if n_shapes == 256 else 2
