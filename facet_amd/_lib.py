@@ -48,7 +48,10 @@ class EngineCapacityError(EngineError):
 FE_ERR_INVALID = -1
 FE_ERR_CAPACITY = -4
 FE_MIXED_CLIP, FE_MIXED_SAMP = 0, 1      # fe_preprocess224_mixed modes
-FE_ORDER_BGR, FE_ORDER_RGB = 0, 1        # fe_image_stats_mixed: byte order of a pixel
+FE_ORDER_BGR, FE_ORDER_RGB = 0, 1        # fe_image_stats_mixed / fe_phash_mixed / fe_thumbnail_jpeg_mixed: byte order of a pixel
+# fe_thumb_plan (include/facet_engine.h), 52 bytes
+THUMB_PLAN_DTYPE = np.dtype([('oh', '<i4'), ('ow', '<i4'), ('fx', '<i4'), ('fy', '<i4'), ('reduce_box', '<i4', (4,)), ('resize_box', '<f4', (4,)),
+                             ('tall', '<i4')])
 
 
 _lib = None
@@ -202,6 +205,10 @@ SIGNATURES = {
     "fe_subject_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_phash_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_thumbnail_jpeg_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    "fe_resize_cache_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "fe_resize_u8_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "fe_reduce_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "fe_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int]),
@@ -1568,6 +1575,28 @@ class Engine:
                                    lo.ctypes.data_as(C.c_void_p) if want_dct else None))
         return (hashes, small, lo) if (want_small or want_dct) else hashes
 
+    def phash_mixed(self, images, order='rgb', want_small=False, want_dct=False):
+        """phash for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for resident
+        images. order 'rgb' / 'bgr' (or FE_ORDER_*): the byte order of a pixel. -> uint64 [n] in input order, every hash (and, with
+        want_small / want_dct, every byte and double of `small` and `lo`) equal to phash's for that image alone. Nothing is cached per
+        size. include/facet_engine.h fe_phash_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        hashes = np.empty((n,), np.uint64)
+        small = np.empty((n, 32, 32), np.uint8) if want_small else None
+        lo = np.empty((n, 8, 8), np.float64) if want_dct else None
+        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
+        self._ck(self.lib.fe_phash_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o), hashes.ctypes.data_as(C.c_void_p),
+                                         small.ctypes.data_as(C.c_void_p) if want_small else None,
+                                         lo.ctypes.data_as(C.c_void_p) if want_dct else None))
+        return (hashes, small, lo) if (want_small or want_dct) else hashes
+
+    def resize_cache_entries(self):
+        """How many per-size resampling tables the context holds (fe_resize_cache_entries): phash / thumbnail_jpeg / resize calls add to
+        it with every new size, the mixed-size calls never do."""
+        v = C.c_int32(0)
+        self._ck(self.lib.fe_resize_cache_entries(self.h, C.byref(v)))
+        return v.value
+
     def resize_u8_box(self, imgs, oh, ow, box, filter="lanczos"):
         """PIL `resize((ow, oh), filter, box)` of a uint8 [n,h,w,3] batch; box = (x0, y0, x1, y1) in source pixels, fractional."""
         a = np.ascontiguousarray(imgs, dtype=np.uint8)
@@ -1624,6 +1653,44 @@ class Engine:
         self._ck(self.lib.fe_thumbnail_jpeg(self.h, p, n, h, w, 1 if bgr else 0, dev, oh, ow, fx, fy,
                                             rbox.ctypes.data_as(C.c_void_p) if rbox is not None else None, box.ctypes.data_as(C.c_void_p),
                                             1 if plan.tall else 0, int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths)
+
+    @staticmethod
+    def thumb_plans(plans, sizes):
+        """ThumbnailPlan tuples (facet_amd.thumbnail.thumbnail_plan) of images of the given (h, w) sizes -> the fe_thumb_plan array
+        (numpy, THUMB_PLAN_DTYPE) fe_thumbnail_jpeg_mixed takes."""
+        arr = np.zeros(len(plans), THUMB_PLAN_DTYPE)
+        for i, (p, (h, w)) in enumerate(zip(plans, sizes)):
+            if (p.src_w, p.src_h) != (int(w), int(h)):
+                raise ValueError(f"thumbnail_jpeg_mixed: plan {i} is for a {p.src_w} x {p.src_h} image, image {i} is {w} x {h}")
+            arr[i] = (p.size[1], p.size[0], p.factors[0], p.factors[1], p.reduce_box if p.reduce_box is not None else (0, 0, 0, 0), p.resize_box,
+                      1 if p.tall else 0)
+        return arr
+
+    def thumbnail_jpeg_mixed(self, images, plans, quality=80, order='rgb', cap=None):
+        """thumbnail_jpeg for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for
+        resident images, and one plan per image (facet_amd.thumbnail.thumbnail_plan(w, h, size)). order 'rgb' / 'bgr' (or FE_ORDER_*).
+        -> list of bytes in input order, each what thumbnail_jpeg writes for that image alone. Nothing is cached per size. cap: bytes of
+        room per image (default: fe_jpeg_bound of the largest thumbnail, which always fits); when an image needs more the
+        EngineCapacityError carries `lengths` (int32 [n]: bytes written, or minus the bytes needed) and `rows` (bytes, or None for an image
+        that did not fit). include/facet_engine.h fe_thumbnail_jpeg_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        if len(plans) != n:
+            raise ValueError(f"thumbnail_jpeg_mixed: {len(plans)} plans for {n} images")
+        arr = self.thumb_plans(plans, hw)
+        if cap is None:
+            cap = self.jpeg_bound(max(int(arr['oh'].max()), 1), max(int(arr['ow'].max()), 1)) if n else 1
+        cap = int(cap)
+        out = np.empty((n, cap), np.uint8)
+        lengths = np.zeros(n, np.int32)
+        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
+        try:
+            self._ck(self.lib.fe_thumbnail_jpeg_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o), arr.ctypes.data_as(C.c_void_p),
+                                                      int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
+        except EngineCapacityError as err:
+            err.lengths = lengths
+            err.rows = [out[i, :int(l)].tobytes() if 0 < l <= cap else None for i, l in enumerate(lengths)]
+            raise
         return self._jpeg_rows(out, lengths)
 
     def jpeg_thumbnail(self, blobs, scale, plan, quality=80, progressive=False, cap=None, parallel_entropy=False):

@@ -25,9 +25,11 @@ fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_sub
 Mixed sizes: `process_images` / `process_files` take a chunk of photos of any sizes. By default the chunk is cut into one process_batch
 per distinct shape. `mixed_sizes=True` uploads the chunk once and scores all of it with ONE fe_ensemble_score_mixed call (CLIP and SAMP
 crops gather across shapes into the towers' usual chunks; TOPIQ runs per shape group inside that call) and computes the technical
-statistics of all of it with ONE fe_image_stats_mixed call on the RGB pixels; faces, lines, pHash, thumbnails and the subject region
-still run per shape group on a BGR copy of the resident pixels (made only when one of them is on), and the dicts come back in input
-order with the same keys.
+statistics of all of it with ONE fe_image_stats_mixed call on the RGB pixels. With `thumbnails=True` the thumbnails of the whole chunk come
+from ONE fe_thumbnail_jpeg_mixed call and, with `phash=True` as well, its hashes from ONE fe_phash_mixed call, both on the RGB pixels and
+both without a per-size table left in the context; faces, lines and the subject region still run per shape group on a BGR copy of the
+resident pixels (made only when one of them is on - or pHash without thumbnails, which keeps its per-group fe_phash), and the dicts come
+back in input order with the same keys and values.
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -103,7 +105,8 @@ class BatchScorer:
         self.tag_threshold, self.max_tags = tag_threshold, max_tags           # utils/tags.py:50-51 defaults
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
-    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False, _tech=None):
+    def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False, _tech=None, _hashes=None,
+                      _thumbs=None):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
@@ -112,7 +115,9 @@ class BatchScorer:
         _records (the mixed-size path): (records [n, 789], mask) of these images, computed by the caller - the ensemble call is skipped.
         _borrowed: the resident batch stays the caller's and is not freed here.
         _tech (the mixed-size path): the technical dicts of these images (TechnicalAnalyzer.analyze_mixed), computed by the caller - the
-        statistics call is skipped, and the BGR copy is made only when a stage that reads it is on."""
+        statistics call is skipped, and the BGR copy is made only when a stage that reads it is on.
+        _hashes / _thumbs (the mixed-size path): the phash strings / thumbnail bytes of these images (fe_phash_mixed, fe_thumbnail_jpeg_mixed),
+        computed by the caller - that stage is skipped and asks for no BGR copy."""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -132,7 +137,8 @@ class BatchScorer:
                 e.d2h(imgs, d_rgb)
             faces_on = self.face_analyzer is not None and self.face_analyzer.available
             bgr_dev = None
-            if _tech is None or faces_on or (leading_lines is None and self.detect_lines) or self.phash or self.thumbnails or self.subject_region:
+            if _tech is None or faces_on or (leading_lines is None and self.detect_lines) or (self.phash and _hashes is None) or \
+                    (self.thumbnails and _thumbs is None) or self.subject_region:
                 d_bgr = e.dev_alloc(n * h * w * 3)
                 e.swap_rb(d_rgb, n * h * w, d_bgr)
                 bgr_dev = (d_bgr, n, h, w)
@@ -150,12 +156,12 @@ class BatchScorer:
                 if lines_ is None and self.detect_lines:      # CompositionAnalyzer.detect_leading_lines (multi_pass.py:702-705), batched
                     from .composition import score_lines
                     lines_ = [score_lines(l, h, w)['leading_lines_score'] for l in eng.leading_lines(bgr_dev)]
-                hashes_ = None
-                if self.phash:      # the same bytes as the PIL image, in B,G,R order
+                hashes_ = _hashes
+                if self.phash and hashes_ is None:      # the same bytes as the PIL image, in B,G,R order
                     from .phash import phash_batch
                     hashes_ = phash_batch(eng, bgr_dev, bgr=True)
-                thumbs_ = None
-                if self.thumbnails:
+                thumbs_ = _thumbs
+                if self.thumbnails and thumbs_ is None:
                     from .thumbnail import thumbnails
                     thumbs_ = thumbnails(eng, bgr_dev, self.thumbnail_size, self.thumbnail_quality, bgr=True)
                 subjects_ = None
@@ -310,8 +316,19 @@ class BatchScorer:
         by_input = sorted(range(len(order)), key=lambda r: order[r])      # the calls see the images in input order
         resident = ([ptrs[r] for r in by_input], [sizes[r] for r in by_input])
 
-        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels
-            return TechnicalAnalyzer.analyze_mixed(eng, resident, self.shadow_threshold, self.highlight_threshold, self.mono_threshold, order='rgb')
+        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels; then the index columns
+            tech_ = TechnicalAnalyzer.analyze_mixed(eng, resident, self.shadow_threshold, self.highlight_threshold, self.mono_threshold, order='rgb')
+            hashes_ = thumbs_ = None
+            # Indexing (thumbnails on, the reference's two columns per photo): one fe_thumbnail_jpeg_mixed and, with phash on, one
+            # fe_phash_mixed over the whole chunk, R,G,B read in place, so neither asks process_batch for a BGR copy. pHash without
+            # thumbnails keeps its per-group fe_phash on the BGR copy: tests/test_stats_mixed_gpu.py pins that configuration's calls.
+            if self.thumbnails:
+                from .thumbnail import thumbnails_mixed
+                thumbs_ = thumbnails_mixed(eng, resident, self.thumbnail_size, self.thumbnail_quality, order='rgb')
+                if self.phash:
+                    from .phash import phash_mixed, to_hex
+                    hashes_ = to_hex(phash_mixed(eng, resident, order='rgb'))
+            return tech_, hashes_, thumbs_
 
         try:
             if self._pool is not None:      # beside the ensemble call, on the aux context (module docstring, "Overlap")
@@ -320,10 +337,10 @@ class BatchScorer:
                 try:
                     rec, mask = e.ensemble_score_mixed(resident)
                 finally:
-                    tech = fut.result()      # also on error: the worker must be done before the buffers go
+                    tech, hashes, thumbs = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score_mixed(resident)
-                tech = stats(e)
+                tech, hashes, thumbs = stats(e)
         except Exception:
             for _, dev, owned in entries:
                 if owned:
@@ -334,7 +351,9 @@ class BatchScorer:
             try:
                 res = self.process_batch(None, exif=[exif[i] for i in idx] if exif else None,
                                          leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev,
-                                         _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned, _tech=[tech[row[i]] for i in idx])
+                                         _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned, _tech=[tech[row[i]] for i in idx],
+                                         _hashes=[hashes[row[i]] for i in idx] if hashes is not None else None,
+                                         _thumbs=[thumbs[row[i]] for i in idx] if thumbs is not None else None)
             except Exception:
                 for _, dev2, owned2 in entries[n_done + 1:]:
                     if owned2:

@@ -2,6 +2,8 @@
 // contours, subject region.
 #include "capi_internal.h"
 #include "lines_host.h"
+#include "phash_mixed_plan.h"
+#include "thumb_mixed_core.h"
 #include <thread>
 
 namespace {
@@ -107,6 +109,111 @@ void ensure_hsv_tables(fe_ctx* ctx) {
   ctx->misc_allocs.push_back(ctx->hsv_hdiv);
   FE_HIP(hipMemcpy(ctx->hsv_sdiv, sd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
   FE_HIP(hipMemcpy(ctx->hsv_hdiv, hd.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
+}
+
+// the DCT-II cosine table of the pHash entry points, made once per context
+void ensure_phash_cos(fe_ctx* ctx) {
+  if (ctx->phash_cos) return;
+  double tab[8 * 32];
+  phash_cos_table(tab);
+  FE_HIP(hipMalloc((void**)&ctx->phash_cos, sizeof(tab)));
+  ctx->misc_allocs.push_back(ctx->phash_cos);
+  FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
+}
+
+// What the mixed-size entry points check alike: the list, the order and every image's pointer and size. max_h / max_w: the entry point's
+// limits; below_2_31: h * w must stay below 2^31 as well. false: FE_ERR_INVALID with the message in the context.
+bool mixed_list_ok(Ctx& C, const char* who, const void* list, const int32_t* hw, int n, int order, const uint8_t* const* images, int max_h, int max_w,
+                   bool below_2_31) {
+  char b[240];
+  if (!list || !hw || n <= 0) {
+    snprintf(b, sizeof b, "%s: bad arguments (null list, null output or n <= 0)", who);
+    C.err = b;
+    return false;
+  }
+  if (order != FE_ORDER_BGR && order != FE_ORDER_RGB) {
+    snprintf(b, sizeof b, "%s: order %d is neither FE_ORDER_BGR (0) nor FE_ORDER_RGB (1)", who, order);
+    C.err = b;
+    return false;
+  }
+  for (int i = 0; i < n; ++i) {
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!images[i]) { snprintf(b, sizeof b, "%s: image %d is a null pointer", who, i); C.err = b; return false; }
+    if (h < 1 || w < 1 || h > max_h || w > max_w || (below_2_31 && (size_t)h * (size_t)w >= ((size_t)1 << 31))) {
+      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h must be within 1 .. %d and w within 1 .. %d%s", who, i, h, w, max_h, max_w,
+               below_2_31 ? ", h * w below 2^31" : "");
+      C.err = b;
+      return false;
+    }
+  }
+  return true;
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// fe_phash_mixed behind its argument checks: descriptors and pool of the whole list, then chunk by chunk through the arena
+void phash_mixed_run(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, uint64_t* hashes, uint8_t* small_out,
+                     double* dct_out) {
+  Ctx& C = ctx->c;
+  PhashTables tables;
+  std::vector<PhashDesc> descs(n);
+  for (int i = 0; i < n; ++i) FE_CHECK(tables.describe(hw[2 * i], hw[2 * i + 1], descs[i]), "fe_phash_mixed: image %d: a coefficient window leaves the axis", i);
+  // what an image takes of a chunk besides the pool: its rows of tmp, its descriptor and outputs and, from the host, its staged pixels
+  auto need = [&](int i) {
+    const size_t h = (size_t)hw[2 * i], w = (size_t)hw[2 * i + 1];
+    return (size_t)phash_tmp_rows((int)h, (int)w) * kPhashSide + sizeof(PhashDesc) + sizeof(uint64_t) + (small_out ? 1024 : 0) + (dct_out ? 64 * sizeof(double) : 0) + (on_device ? 0 : up256(h * w * 3));
+  };
+  const size_t pool_b = up256(tables.pool.size() * sizeof(int32_t)), slack = 8 * 256;      // slack: the alignment of a chunk's allocations
+  const size_t room = C.arena.capacity() > pool_b + slack ? C.arena.capacity() - pool_b - slack : 0;
+  for (int i = 0; i < n; ++i)
+    if (need(i) > room) {
+      char b[200];
+      snprintf(b, sizeof b, "fe_phash_mixed: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", i, hw[2 * i], hw[2 * i + 1],
+               need(i) + pool_b + slack, C.arena.capacity());
+      throw CapacityError(b);
+    }
+  ensure_phash_cos(ctx);
+  C.arena.reset();
+  const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());
+  const size_t mark = C.arena.mark();
+  for (int i0 = 0; i0 < n;) {
+    size_t used = 0, rows = 0, stage_b = 0;
+    int i1 = i0, max_w = 1, any_tall = 0;
+    for (; i1 < n; ++i1) {
+      if (i1 > i0 && (used + need(i1) > room || rows + (size_t)phash_tmp_rows(hw[2 * i1], hw[2 * i1 + 1]) > ((size_t)1 << 30) || i1 - i0 >= 65535)) break;
+      used += need(i1);
+      descs[i1].first_row = (uint32_t)rows;
+      rows += (size_t)phash_tmp_rows(hw[2 * i1], hw[2 * i1 + 1]);
+      any_tall |= descs[i1].tall;
+      max_w = std::max(max_w, (int)hw[2 * i1 + 1]);
+      if (!on_device) stage_b += up256((size_t)hw[2 * i1] * hw[2 * i1 + 1] * 3);
+    }
+    const int nb = i1 - i0;
+    C.arena.rewind(mark);
+    PhashDesc* d_desc = (PhashDesc*)C.arena.alloc((size_t)nb * sizeof(PhashDesc));
+    uint8_t* d_tmp = (uint8_t*)C.arena.alloc(rows * kPhashSide);
+    uint64_t* d_hash = (uint64_t*)C.arena.alloc((size_t)nb * sizeof(uint64_t));
+    uint8_t* d_small = small_out ? (uint8_t*)C.arena.alloc((size_t)nb * 1024) : nullptr;
+    double* d_dct = dct_out ? (double*)C.arena.alloc((size_t)nb * 64 * sizeof(double)) : nullptr;
+    uint8_t* d_stage = on_device ? nullptr : (uint8_t*)C.arena.alloc(stage_b);
+    size_t at = 0;
+    for (int i = i0; i < i1; ++i) {
+      descs[i].src = images[i];
+      if (!on_device) {      // the host images lie anywhere: one copy each, to a 256-byte boundary of the stage region
+        const size_t bytes = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+        FE_HIP(hipMemcpyAsync(d_stage + at, images[i], bytes, hipMemcpyHostToDevice, C.stream));
+        descs[i].src = d_stage + at;
+        at += up256(bytes);
+      }
+    }
+    FE_HIP(hipMemcpyAsync(d_desc, descs.data() + i0, (size_t)nb * sizeof(PhashDesc), hipMemcpyHostToDevice, C.stream));
+    launch_phash_mixed(C, d_desc, nb, rows, max_w, any_tall, order == FE_ORDER_BGR, d_pool, d_tmp, ctx->phash_cos, d_hash, d_small, d_dct);
+    FE_HIP(hipMemcpyAsync(hashes + i0, d_hash, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, C.stream));
+    if (small_out) FE_HIP(hipMemcpyAsync(small_out + (size_t)i0 * 1024, d_small, (size_t)nb * 1024, hipMemcpyDeviceToHost, C.stream));
+    if (dct_out) FE_HIP(hipMemcpyAsync(dct_out + (size_t)i0 * 64, d_dct, (size_t)nb * 64 * sizeof(double), hipMemcpyDeviceToHost, C.stream));
+    FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next chunk
+    i0 = i1;
+  }
 }
 
 // Brings the contour records of one micro-batch to the host: counts [nb] exact; records [nb][max_contours][8], per image the first
@@ -556,14 +663,16 @@ int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int 
   return fe_api(ctx, [&] {
     Ctx& C = ctx->c;
     FE_CHECK(img && hashes && n > 0 && h > 0 && w > 0, "bad arguments");
-    if (!ctx->phash_cos) {
-      double tab[8 * 32];
-      phash_cos_table(tab);
-      FE_HIP(hipMalloc((void**)&ctx->phash_cos, sizeof(tab)));
-      ctx->misc_allocs.push_back(ctx->phash_cos);
-      FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
     const size_t per = (size_t)h * w * 3;
+    if (phash_tall(h, w)) {      // Image.resize's vertical-pass-first case: the descriptor path has the kernel for it
+      FE_CHECK(w <= 32768 && h <= 65536, "phash: bad shape %d x %d x %d", n, h, w);
+      std::vector<const uint8_t*> ptrs(n);
+      std::vector<int32_t> sizes(2 * (size_t)n);
+      for (int i = 0; i < n; ++i) { ptrs[i] = img + (size_t)i * per; sizes[2 * i] = h; sizes[2 * i + 1] = w; }
+      phash_mixed_run(ctx, ptrs.data(), sizes.data(), n, on_device, bgr ? FE_ORDER_BGR : FE_ORDER_RGB, hashes, small_out, dct_out);
+      return;
+    }
+    ensure_phash_cos(ctx);
     // chunks of up to 256 images whatever the model micro-batch (a wave per row: large chunks fill the chip, scratch is 32 B per
     // row), but at most 1 GiB of pixels: host input is staged through two device buffers of one chunk each
     const int mb = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1 << 30) / per));
@@ -584,6 +693,124 @@ int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int 
       FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next micro-batch
     }
   });
+}
+
+/* fe_phash for a list of images of any sizes: two launches per arena chunk of the list, all tables in one call-scoped pool */
+int fe_phash_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, uint64_t* hashes, uint8_t* small_out,
+                   double* dct_out) {
+  return fe_api(ctx, OnError::Capacity, [&]() -> int {
+    if (!mixed_list_ok(ctx->c, "fe_phash_mixed", (images && hashes) ? (const void*)images : nullptr, hw, n, order, images, 65536, 32768, false)) return FE_ERR_INVALID;
+    phash_mixed_run(ctx, images, hw, n, on_device, order, hashes, small_out, dct_out);
+    return FE_OK;
+  });
+}
+
+/* fe_thumbnail_jpeg for a list of images of any sizes, each with its own plan: one launch per stage per arena chunk of the list */
+int fe_thumbnail_jpeg_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, const fe_thumb_plan* plans,
+                            int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  return fe_api(ctx, OnError::Capacity, [&]() -> int {
+    Ctx& C = ctx->c;
+    char b[240];
+    if (!mixed_list_ok(C, "fe_thumbnail_jpeg_mixed", (images && plans && out && lengths) ? (const void*)images : nullptr, hw, n, order, images, INT32_MAX,
+                       INT32_MAX, true))
+      return FE_ERR_INVALID;
+    if (quality < 1 || quality > 100) {
+      snprintf(b, sizeof b, "fe_thumbnail_jpeg_mixed: quality %d (1 .. 100)", quality);
+      C.err = b;
+      return FE_ERR_INVALID;
+    }
+    ThumbTables tables;
+    std::vector<ThumbDesc> descs(n);
+    int max_oh = 1, max_ow = 1;
+    for (int i = 0; i < n; ++i) {
+      const fe_thumb_plan& p = plans[i];
+      if (const char* why = tables.describe(hw[2 * i], hw[2 * i + 1], p.oh, p.ow, p.fx, p.fy, p.reduce_box, p.resize_box, p.tall, descs[i])) {
+        snprintf(b, sizeof b, "fe_thumbnail_jpeg_mixed: image %d (%d x %d): %s", i, hw[2 * i], hw[2 * i + 1], why);
+        C.err = b;
+        return FE_ERR_INVALID;
+      }
+      max_oh = std::max(max_oh, (int)p.oh); max_ow = std::max(max_ow, (int)p.ow);
+    }
+    const size_t dcap = std::min(cap, jpeg_bound(max_oh, max_ow));      // no encode is longer, so the device rows need not be
+    C.arena.reset();
+    const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());
+    const size_t mark = C.arena.mark();
+    // The arena budget of thumbnail_run. An image takes its output row and its scratch; when the chunk is done the scratch is dead and
+    // the gathered bytes (at most a row per image) take its place.
+    const size_t whole = std::min<size_t>((size_t)1 << 30, C.arena.capacity() - C.arena.capacity() / 8);
+    const size_t budget = whole > mark ? whole - mark : 0;
+    auto need = [&](int i) {
+      const size_t stage = on_device ? 0 : up256((size_t)hw[2 * i] * hw[2 * i + 1] * 3);
+      return dcap + std::max(thumb_mixed_scratch_bytes(descs[i]) + stage, dcap) + 4 * 256;
+    };
+    std::vector<uint8_t> blob, packed;
+    std::vector<int32_t> lens;
+    bool overflow = false;
+    for (int i0 = 0; i0 < n;) {
+      size_t used = 0;
+      int i1 = i0;
+      for (; i1 < n; ++i1) {
+        if (i1 > i0 && (used + need(i1) > budget || i1 - i0 >= 4096)) break;
+        used += need(i1);
+      }
+      const int nb = i1 - i0;
+      C.arena.rewind(mark);
+      uint8_t* d_out = (uint8_t*)C.arena.alloc((size_t)nb * dcap);
+      int32_t* d_len = (int32_t*)C.arena.alloc((size_t)nb * sizeof(int32_t));
+      const size_t scratch = C.arena.mark();
+      for (int i = i0; i < i1; ++i) {
+        descs[i].src = images[i];
+        if (!on_device) {
+          const size_t bytes = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+          uint8_t* d = (uint8_t*)C.arena.alloc(bytes);
+          FE_HIP(hipMemcpyAsync(d, images[i], bytes, hipMemcpyHostToDevice, C.stream));
+          descs[i].src = d;
+        }
+      }
+      thumbnails_mixed_launch(C, descs.data() + i0, nb, d_pool, order == FE_ORDER_BGR, quality, blob, d_out, dcap, d_len);
+      lens.resize(nb);
+      FE_HIP(hipMemcpyAsync(lens.data(), d_len, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+      size_t total = 0, longest = 0;
+      for (int i = 0; i < nb; ++i) {
+        const int32_t len = lens[i];
+        lengths[i0 + i] = len;
+        if (len <= 0 || (size_t)len > cap) { overflow = true; continue; }
+        total += (size_t)len;
+        longest = std::max(longest, (size_t)len);
+      }
+      if (total) {      // one gather of the used bytes into the dead scratch, one copy down, and the rows are dealt out on the host
+        C.arena.rewind(scratch);
+        uint8_t* d_packed = (uint8_t*)C.arena.alloc(total);
+        jpeg_gather(C, d_out, dcap, d_len, nb, longest, d_packed);
+        packed.resize(total);
+        FE_HIP(hipMemcpyAsync(packed.data(), d_packed, total, hipMemcpyDeviceToHost, C.stream));
+        FE_HIP(hipStreamSynchronize(C.stream));   // the arena is recycled by the next chunk
+        size_t at = 0;
+        for (int i = 0; i < nb; ++i) {
+          const int32_t len = lens[i];
+          if (len <= 0 || (size_t)len > cap) continue;
+          memcpy(out + (size_t)(i0 + i) * cap, packed.data() + at, (size_t)len);
+          at += (size_t)len;
+        }
+      }
+      i0 = i1;
+    }
+    if (overflow) {
+      snprintf(b, sizeof b, "jpeg: an image needs more than the %zu bytes of its output row (fe_jpeg_bound(%d, %d) = %zu always fits)", cap, max_oh, max_ow,
+               jpeg_bound(max_oh, max_ow));
+      throw CapacityError(b);
+    }
+    return FE_OK;
+  });
+}
+
+/* how many per-size coefficient tables the context has cached (fe_resize_u8 / fe_resize_u8_box / fe_phash / fe_thumbnail_jpeg add one or two per
+ * new size; the mixed-size entry points add none) */
+int fe_resize_cache_entries(fe_ctx* ctx, int32_t* entries) {
+  if (!ctx || !entries) return FE_ERR_INVALID;
+  *entries = (int32_t)(ctx->c.resize_cache.size() + ctx->c.resize_box_cache.size());
+  return FE_OK;
 }
 
 }  // extern "C"

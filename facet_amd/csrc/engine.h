@@ -236,6 +236,16 @@ void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int b
 bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes,
                      int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
+// thumbnails of a list of images of any sizes (kernels_jpeg.hip; descriptors and pool: thumb_mixed_core.h): one chunk's reduce, resize
+// and encode, one launch per stage. descs [n] host descriptors with device sources; their buffers and every scratch array come from the
+// arena (the caller rewinds); host_blob must outlive the stream's work. d_out [n][cap] / d_lengths [n] as launch_jpeg_encode leaves them.
+struct ThumbDesc;
+size_t thumb_mixed_scratch_bytes(const ThumbDesc& d);
+void thumbnails_mixed_launch(Ctx& c, ThumbDesc* descs, int n, const int32_t* d_pool, int bgr, int quality, std::vector<uint8_t>& host_blob,
+                             uint8_t* d_out, size_t cap, int32_t* d_lengths);
+// the bytes of every row that fitted (0 < length <= cap), back to back in row order, into d_packed; max_len: the longest of them
+void jpeg_gather(Ctx& c, const uint8_t* d_rows, size_t cap, const int32_t* d_lengths, int n, size_t max_len, uint8_t* d_packed);
+
 // ---- JPEG decode: file bytes -> resident uint8 batch, Pillow's pixels (kernels_jpeg_dec.hip, jpeg_dec_core.h) ----
 void jpeg_probe(const uint8_t* data, size_t len, int flags, int32_t out[10]);      // the fields of fe_jpeg_info_ex, host only
 void jpeg_scaled_size(int h, int w, int scale, int* sh, int* sw);                  // ceil(h / scale), ceil(w / scale): what a scaled decode gives
@@ -247,6 +257,12 @@ void phash_cos_table(double* out);                       // [8][32] = cos(pi k (
 size_t phash_tmp_bytes(int n, int h);
 void launch_phash(Ctx& c, const uint8_t* d_img, int n, int h, int w, int bgr, uint8_t* d_tmp, const double* d_cos, uint64_t* d_hashes,
                   uint8_t* d_small, double* d_dct);
+// one chunk of a list of images of any sizes (descriptors and pool: phash_mixed_plan.h): d_descs [n] with first_row ascending from 0,
+// rows their total, max_w the widest, any_tall: one of them is tall (Image.resize's vertical-pass-first case), d_tmp [rows][32] scratch;
+// outputs as launch_phash's
+struct PhashDesc;
+void launch_phash_mixed(Ctx& c, const PhashDesc* d_descs, int n, size_t rows, int max_w, int any_tall, int bgr, const int32_t* d_pool, uint8_t* d_tmp,
+                        const double* d_cos, uint64_t* d_hashes, uint8_t* d_small, double* d_dct);
 void launch_hamming_pairs(const uint64_t* d_hashes, int n, int maxd, int64_t cap, int* d_pairs, unsigned long long* d_count, hipStream_t s);
 
 // ---- face clustering sweeps: core distances, mutual-reachability MST, best cosine match (kernels_cluster.hip) ----

@@ -21,3 +21,10 @@ def phash_batch(engine, images, bgr=False):
     """uint8 [n,h,w,3] RGB images (host array, or the `(ptr, n, h, w)` tuple of a resident batch; bgr=True when its bytes are
     B,G,R) -> the reference's phash strings, one per image."""
     return to_hex(engine.phash(images, bgr=bgr))
+
+
+def phash_mixed(engine, images, order='rgb'):
+    """Images that each have their own size (a list of uint8 [h,w,3] arrays, or `(device_pointers, sizes)` for resident images; order:
+    'rgb' or 'bgr' bytes) -> uint64 [n], the hash `fe_phash` gives each image alone, from one `fe_phash_mixed` call. `to_hex` turns them
+    into the reference's strings."""
+    return engine.phash_mixed(images, order=order)

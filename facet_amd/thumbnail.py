@@ -121,6 +121,14 @@ def thumbnails(engine, images, size=640, quality=80, bgr=False):
     return engine.thumbnail_jpeg(images, thumbnail_plan(w, h, size), quality=quality, bgr=bgr)
 
 
+def thumbnails_mixed(engine, images, size=640, quality=80, order='rgb'):
+    """Images that each have their own size (a list of uint8 [h,w,3] arrays, or `(device_pointers, sizes)` for resident images; order:
+    'rgb' or 'bgr' bytes) -> list of bytes, the reference's generate_photo_thumbnail(pil_img, size, quality) of every image, from one
+    `fe_thumbnail_jpeg_mixed` call with one `thumbnail_plan` per image."""
+    sizes = images[1] if isinstance(images, tuple) else [np.asarray(a).shape[:2] for a in images]
+    return engine.thumbnail_jpeg_mixed(images, [thumbnail_plan(w, h, size) for h, w in sizes], quality=quality, order=order)
+
+
 def generate_photo_thumbnail(engine, pil_img, size=640, quality=80):
     """The reference's signature plus the engine: PIL image -> JPEG bytes. Modes other than RGB are converted first, which the
     reference does when it loads a photo."""

@@ -781,7 +781,8 @@ int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int 
 /* Perceptual hash: `imagehash.phash(pil_img)` with its defaults (hash_size 8, highfreq_factor 4), which the reference stores as
  * str(...) in the `phash` column for every image (processing/batch_processor.py:216, multi_pass.py:449, scorer.py:972):
  * image.convert('L') ((R*19595 + G*38470 + B*7471 + 0x8000) >> 16), .resize((32, 32), LANCZOS) (PIL's two-pass 22-bit fixed-point
- * resampler, horizontal pass first, each pass clipped to uint8, a pass skipped when its axis is already 32),
+ * resampler, horizontal pass first - vertical pass first for an image more than 100 times taller than wide, as Image.resize has it -
+ * each pass clipped to uint8, a pass skipped when its axis is already 32),
  * scipy.fftpack.dct over axis 0 then axis 1 (unnormalised DCT-II, fp64), the top-left 8x8 block compared with its numpy.median.
  * img [n][h][w][3] uint8 on the host (on_device = 0) or the device, read once; bgr = 1: the bytes of a pixel are B,G,R.
  * hashes [n]: bit 63 = coefficient [0][0], row-major downwards, so the reference's string is the value as 16 lowercase hex
@@ -790,6 +791,43 @@ int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int 
  * observed; the tests allow 1e-6) may fall on either side. */
 int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int on_device, uint64_t* hashes, uint8_t* small_out,
              double* dct_out);
+/* fe_phash for a list of images that each have their own size, in two launches per arena chunk of the list whatever the sizes: a wave
+ * per image row over the rows of all images, then one workgroup per image. images / hw / on_device / order: as for fe_image_stats_mixed;
+ * device images may sit at any byte alignment. Any h, w >= 1 within fe_phash's limits (w <= 32768, h <= 65536). hashes [n], small_out
+ * [n][32][32] (nullable), dct_out [n][64] (nullable): in input order, every bit and every double equal to fe_phash's for that image
+ * alone. The coefficient tables of the call - one per distinct side length, shared by the images that have it - live in one pool that is
+ * uploaded once and dropped with the call: nothing is cached per size, unlike fe_phash. Host images are staged chunk by chunk through
+ * the arena, device images are read in place.
+ * A null pointer, a bad size or a bad order returns FE_ERR_INVALID, the message names the index of the image, nothing is launched. An
+ * image whose own scratch (its pixels when they are staged, 32 bytes per row, its descriptor and outputs, next to the pool) exceeds the
+ * arena returns FE_ERR_CAPACITY, the message names its index, nothing is launched. */
+int fe_phash_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, uint64_t* hashes,
+                   uint8_t* small_out, double* dct_out);
+
+/* fe_thumbnail_jpeg for a list of images that each have their own size and their own plan: reduce, the two LANCZOS passes and the five
+ * encoder passes run once per arena chunk of the list, each over all images of the chunk. plans [n]: what
+ * facet_amd.thumbnail.thumbnail_plan(w_i, h_i, size) gives - oh, ow: the thumbnail's size; fx, fy: the factors of Image.reduce (1, 1:
+ * none) over the integer box reduce_box (x0, y0, x1, y1; read only when a factor exceeds 1); resize_box (x0, y0, x1, y1): the box of the
+ * LANCZOS resize in pixels of the (reduced) image; tall: Image.resize's vertical-pass-first case. A plan with oh = h, ow = w, factors 1
+ * and the whole-image box means the image is encoded as it is. images / hw / on_device / order: as for fe_image_stats_mixed (h * w below
+ * 2^31); device images may sit at any byte alignment. out [n][cap], lengths [n], quality and FE_ERR_CAPACITY: fe_thumbnail_jpeg's
+ * contract, with fe_jpeg_bound(max oh, max ow) as the bound that always fits; nothing is stored past a row. Every row holds the bytes
+ * fe_thumbnail_jpeg writes for that image alone. The resize tables - one per distinct (input size, box, output size) - live in one pool
+ * that is uploaded once and dropped with the call: nothing is cached per size, unlike fe_thumbnail_jpeg.
+ * A null pointer, a bad size, a bad order, a bad quality or a plan that does not fit its image returns FE_ERR_INVALID, the message names
+ * the index of the image, nothing is launched. */
+typedef struct fe_thumb_plan {
+  int32_t oh, ow, fx, fy;
+  int32_t reduce_box[4];
+  float resize_box[4];
+  int32_t tall;
+} fe_thumb_plan;
+int fe_thumbnail_jpeg_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order,
+                            const fe_thumb_plan* plans, int quality, uint8_t* out, size_t cap, int32_t* lengths);
+
+/* Number of per-size resampling tables the context holds (fe_resize_u8, fe_resize_u8_box, fe_phash and fe_thumbnail_jpeg add one or two
+ * per new size and never free them; the mixed-size entry points add none). A counter for tests and leak hunts. */
+int fe_resize_cache_entries(fe_ctx* ctx, int32_t* entries);
 
 /* Near-duplicate search over stored hashes (reference utils/duplicate.py:89-119, an O(n^2) numpy loop): every pair i < j with
  * popcount(hashes[i] ^ hashes[j]) <= max_distance. hashes [n] on the host (on_device = 0) or the device. count receives the

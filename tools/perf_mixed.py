@@ -10,13 +10,18 @@ perf_mixed.py --stats [--repeats R]: the technical statistics alone (written to 
 and 256 shapes, resident as RGB: the per-shape-group path as process_batch does it (per group a device allocation, fe_swap_rb_u8,
 fe_image_stats on the BGR copy, the frees), fe_image_stats alone on a BGR copy made beforehand, and one fe_image_stats_mixed call on the
 RGB pixels at the default segment size and at 65 536, 262 144 and 1 048 576 pixels; then one 6000 x 4000 image alone. Every figure is
-the median of R calls after one warm-up call, with the fastest and the slowest beside it."""
+the median of R calls after one warm-up call, with the fastest and the slowest beside it.
+
+perf_mixed.py --index [--repeats R]: the `phash` and `thumbnail` columns alone (written to profiles/mixed_index_perf.txt). The same chunks and
+the 6000 x 4000 image: per shape group as process_batch computes them (a device allocation, fe_swap_rb_u8, fe_phash / fe_thumbnail_jpeg on
+the BGR copy, the free - what a mixed chunk cost before fe_phash_mixed / fe_thumbnail_jpeg_mixed existed) against one mixed call on the RGB
+pixels; then process_images with both columns on and mixed_sizes off / on, and the device memory in use over three chunks of new shapes."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from facet_amd import Engine
-from facet_amd._lib import FE_MODEL_AESTHETIC
+from facet_amd._lib import FE_MODEL_AESTHETIC, FE_MODEL_TOPIQ
 from facet_amd.batch import BatchScorer
 from facet_amd.precision import describe, load_models
 from facet_amd.weights import synthetic_state_dict
@@ -27,6 +32,7 @@ ap.add_argument("chunks_of_256", nargs="?", type=int, default=3)
 ap.add_argument("--mixed-only", action="store_true", help="skip the rows with mixed_sizes off")
 ap.add_argument("--policies", default="f32,parity")
 ap.add_argument("--stats", action="store_true", help="the statistics table instead of the process_images table")
+ap.add_argument("--index", action="store_true", help="the pHash / thumbnail table instead of the process_images table")
 ap.add_argument("--repeats", type=int, default=7)
 args = ap.parse_args()
 n, fresh_chunks = args.n, args.chunks_of_256
@@ -114,6 +120,77 @@ if args.stats:
         shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
         stats_rows(e, f"{n} images, {n_shapes} shapes", chunk(shapes), args.repeats)
     stats_rows(e, "1 image 4000 x 6000", [np.ascontiguousarray(np.tile(field, (3, 5, 1))[:4000, :6000])], args.repeats)
+    e.close()
+    sys.exit(0)
+
+def index_rows(e, label, imgs, repeats):
+    """The two index columns of a chunk that is resident as RGB, grouped by shape as _process_images_mixed lays it out: per shape group as
+    process_batch computes them (a device allocation, fe_swap_rb_u8, fe_phash / fe_thumbnail_jpeg on the BGR copy, the free) against one
+    fe_phash_mixed / fe_thumbnail_jpeg_mixed call on the RGB pixels."""
+    from facet_amd.phash import phash_batch, phash_mixed
+    from facet_amd.thumbnail import thumbnails, thumbnails_mixed
+    groups = {}
+    for i, a in enumerate(imgs):
+        groups.setdefault(a.shape[:2], []).append(i)
+    bufs, ptrs, sizes = [], [None] * len(imgs), [a.shape[:2] for a in imgs]
+    for (h, w), idx in groups.items():
+        d = e.dev_alloc(len(idx) * h * w * 3)
+        e.h2d(d, np.stack([imgs[i] for i in idx]))
+        bufs.append((d, len(idx), h, w))
+        for j, i in enumerate(idx):
+            ptrs[i] = d.value + j * h * w * 3
+
+    def per_group(stage):
+        for d, k, h, w in bufs:
+            d_bgr = e.dev_alloc(k * h * w * 3)
+            try:
+                e.swap_rb(d, k * h * w, d_bgr)
+                stage((d_bgr, k, h, w))
+            finally:
+                e.dev_free(d_bgr)
+
+    rows = (("phash", lambda b: phash_batch(e, b, bgr=True), lambda: phash_mixed(e, (ptrs, sizes))),
+            ("thumbnail 640 q80", lambda b: thumbnails(e, b, 640, 80, bgr=True), lambda: thumbnails_mixed(e, (ptrs, sizes), 640, 80)))
+    for name, stage, mixed in rows:
+        print(f"{label:22} {name + ': per group (alloc + swap + call)':48} {timed(lambda: per_group(stage), repeats)}", flush=True)
+        print(f"{label:22} {name + ': one mixed call':48} {timed(mixed, repeats)}", flush=True)
+    for b in bufs:
+        e.dev_free(b[0])
+
+
+if args.index:
+    e = Engine(0, arena_bytes=(4 + 2 * 8) << 30)      # bench.py's arena for the default micro-batch of 8 at 1024 x 1024
+    print(f"{n} images per chunk, sides 776 .. 1280, resident RGB; milliseconds per chunk: median (fastest .. slowest) of {args.repeats} calls after a warm-up")
+    for n_shapes in (1, 16, 256):
+        shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+        index_rows(e, f"{n} images, {n_shapes} shapes", chunk(shapes), args.repeats)
+    index_rows(e, "1 image 4000 x 6000", [np.ascontiguousarray(np.tile(field, (3, 5, 1))[:4000, :6000])], args.repeats)
+    # process_images with both columns on (TOPIQ loaded, the other models left out): one process_batch per shape against the mixed path
+    e.load_weights(FE_MODEL_TOPIQ, synthetic_state_dict("topiq", 4))
+    print("process_images, phash + thumbnails on, TOPIQ only: milliseconds per chunk (upload included)")
+    for n_shapes in (1, 16, 256):
+        shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+        imgs = chunk(shapes)
+        for mixed in (False, True):
+            bs = BatchScorer(e, mixed_sizes=mixed, phash=True, thumbnails=True)
+            print(f"{n} images, {n_shapes:3} shapes  mixed_sizes={str(mixed):5} {timed(lambda: bs.process_images(imgs), max(3, args.repeats // 2))}", flush=True)
+    # device memory over three chunks of 256 shapes no earlier chunk had: the per-size tables of the per-group calls stay, the pools go
+    print("device MiB in use before / after each of three chunks of new shapes (phash + thumbnail of every image)")
+    from facet_amd.phash import phash_mixed
+    from facet_amd.thumbnail import thumbnails, thumbnails_mixed
+    next_shape = 1024
+    for mixed in (False, True):
+        mem = [used_mib()]
+        for r in range(3):
+            imgs = chunk([shape(next_shape + k) for k in range(256)], first=r * n)
+            next_shape += 256
+            if mixed:
+                phash_mixed(e, imgs); thumbnails_mixed(e, imgs, 640, 80)
+            else:
+                for a in imgs:
+                    e.phash(a[None]); thumbnails(e, a[None], 640, 80)
+            mem.append(used_mib())
+        print(f"{'one mixed call each' if mixed else 'per shape':22} tables {e.resize_cache_entries():5}  MiB " + " / ".join(f"{m:.0f}" for m in mem), flush=True)
     e.close()
     sys.exit(0)
 
