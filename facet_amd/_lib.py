@@ -196,6 +196,17 @@ SIGNATURES = {
     "fe_set_stats_segment": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_roi_laplacian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double)]),
+    # the mixed-size face calls: ctx, [slot,] images, hw, n, on_device, order, ...
+    "fe_face_analyze_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.c_float, C.c_int, _f32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fe_face_crops_run_mixed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float, C.c_int, _f32p, C.c_int, C.c_void_p]),
+    "fe_face_det_input_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "fe_roi_laplacian_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "fe_face_thumbnails_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fe_face_cache_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "fe_cv_resize_linear_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "fe_aesthetic_score": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]),
     "fe_swap_rb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
@@ -1456,6 +1467,65 @@ class Engine:
                                           counts.ctypes.data_as(C.POINTER(C.c_int)), C.byref(mask)))
         return faces, counts, mask.value
 
+    # -- face path over images that each have their own size: `images` is a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes)
+    #    for resident images; order 'bgr' / 'rgb' (or FE_ORDER_*) is the byte order of a pixel. include/facet_engine.h
+    @staticmethod
+    def _order(order):
+        return int({"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order))
+
+    def face_analyze_mixed(self, images, det_size=(640, 640), det_thresh=0.5, nms_thresh=0.4, max_faces=8, order='bgr'):
+        """face_analyze for a list of images of any sizes in one call: every graph runs over full micro-batches whatever the shapes.
+        -> (faces float32 [n,max_faces,739], counts int32 [n], models_run bitmask), in input order."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        faces = np.empty((max(n, 0), max_faces, FE_FACE_FLOATS), np.float32)
+        counts = np.zeros((max(n, 0),), np.int32)
+        mask = C.c_int(0)
+        self._ck(self.lib.fe_face_analyze_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), int(det_size[0]),
+                                                int(det_size[1]), float(det_thresh), float(nms_thresh), int(max_faces), faces.ctypes.data_as(_f32p),
+                                                counts.ctypes.data_as(C.POINTER(C.c_int)), C.byref(mask)))
+        return faces, counts, mask.value
+
+    def face_crops_run_mixed(self, slot, images, img_index, M, size, mean, scale, swap_rb=True, out_dim=0, want_crops=False, order='bgr'):
+        """face_crops_run with img_index into a list of images of any sizes. The crops come back in the images' own byte order."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        idx = np.ascontiguousarray(img_index, dtype=np.int32)
+        Mm = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 6)
+        m = idx.shape[0]
+        assert Mm.shape[0] == m
+        out = np.empty((m, out_dim), np.float32) if out_dim else None
+        crops = np.empty((m, size, size, 3), np.uint8) if want_crops else None
+        self._ck(self.lib.fe_face_crops_run_mixed(self.h, int(slot), ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), m,
+                                                  idx.ctypes.data_as(C.POINTER(C.c_int)), Mm.ctypes.data_as(C.POINTER(C.c_double)), int(size), float(mean),
+                                                  float(scale), int(swap_rb), out.ctypes.data_as(_f32p) if out_dim else None, int(out_dim),
+                                                  crops.ctypes.data_as(C.c_void_p) if want_crops else None))
+        return out, crops
+
+    def face_det_input_mixed(self, images, det_size=(640, 640), order='bgr'):
+        """The detector input face_analyze_mixed makes of every image: float32 [n, det_h, det_w, 4] (R, G, B, 0). For the parity tests."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        out = np.empty((max(n, 0), int(det_size[0]), int(det_size[1]), 4), np.float32)
+        self._ck(self.lib.fe_face_det_input_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), int(det_size[0]),
+                                                  int(det_size[1]), out.ctypes.data_as(_f32p)))
+        return out
+
+    def roi_laplacian_mixed(self, images, img_index, rois, order='bgr'):
+        """roi_laplacian with img_index into a list of images of any sizes -> float64 [m,4], every double equal to roi_laplacian's."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        idx = np.ascontiguousarray(img_index, dtype=np.int32)
+        r = np.ascontiguousarray(rois, dtype=np.int32).reshape(-1, 4)
+        out = np.zeros((idx.shape[0], 4), np.float64)
+        self._ck(self.lib.fe_roi_laplacian_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), idx.shape[0],
+                                                 idx.ctypes.data_as(C.POINTER(C.c_int)), r.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def face_cache_entries(self):
+        """How many cv2.resize weight tables the context keeps per size (fe_face_cache_entries): face_detect / face_analyze /
+        cv_resize_linear add to it with every new size, the mixed-size face calls never do."""
+        v = C.c_int32(0)
+        self._ck(self.lib.fe_face_cache_entries(self.h, C.byref(v)))
+        return v.value
+
     def image_stats(self, images, want_gray=False, want_hsv=False):
         """BGR uint8 [n,h,w,3] (or device tuple) -> (stats float64 [n,264], gray uint8 [n,h,w] | None, hsv uint8 [n,h,w,3] | None)."""
         p, n, h, w, dev, keep = self._img_ptr(images)
@@ -1742,6 +1812,26 @@ class Engine:
         self._ck(self.lib.fe_face_thumbnails(self.h, p, n, h, w, dev, m, idx.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
                                              sz.ctypes.data_as(C.c_void_p), int(quality), out.ctypes.data_as(C.c_void_p), cap,
                                              lengths.ctypes.data_as(C.c_void_p)))
+        return self._jpeg_rows(out, lengths)
+
+    def face_thumbnails_mixed(self, images, img_index, crops, out_sizes, quality=85, cap=None, order='bgr'):
+        """face_thumbnails with img_index into a list of images of any sizes (a list of uint8 [h, w, 3] arrays, or (device_pointers,
+        sizes)); order 'bgr' / 'rgb': the byte order of a pixel. The bytes are face_thumbnails' for each image alone."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        idx = np.ascontiguousarray(img_index, dtype=np.int32).reshape(-1)
+        m = idx.shape[0]
+        if m == 0:
+            return []
+        r = np.ascontiguousarray(crops, dtype=np.int32).reshape(m, 4)
+        sz = np.ascontiguousarray(out_sizes, dtype=np.int32).reshape(m, 2)
+        if cap is None:
+            cap = self.jpeg_bound(max(1, int(sz[:, 1].max())), max(1, int(sz[:, 0].max())))
+        cap = int(cap)
+        out = np.empty((m, cap), np.uint8)
+        lengths = np.zeros(m, np.int32)
+        self._ck(self.lib.fe_face_thumbnails_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), m,
+                                                   idx.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), sz.ctypes.data_as(C.c_void_p), int(quality),
+                                                   out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)
 
     @staticmethod

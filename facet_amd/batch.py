@@ -27,9 +27,11 @@ per distinct shape. `mixed_sizes=True` uploads the chunk once and scores all of 
 crops gather across shapes into the towers' usual chunks; TOPIQ runs per shape group inside that call) and computes the technical
 statistics of all of it with ONE fe_image_stats_mixed call on the RGB pixels. With `thumbnails=True` the thumbnails of the whole chunk come
 from ONE fe_thumbnail_jpeg_mixed call and, with `phash=True` as well, its hashes from ONE fe_phash_mixed call, both on the RGB pixels and
-both without a per-size table left in the context; faces, lines and the subject region still run per shape group on a BGR copy of the
-resident pixels (made only when one of them is on - or pHash without thumbnails, which keeps its per-group fe_phash), and the dicts come
-back in input order with the same keys and values.
+both without a per-size table left in the context. With a face analyzer the face dicts of the whole chunk come from ONE
+fe_face_analyze_mixed call, ONE fe_roi_laplacian_mixed call and (with `gpu_thumbnails=True`) ONE fe_face_thumbnails_mixed call, again on the
+RGB pixels: every face graph runs over full micro-batches whatever the shapes. Lines and the subject region still run per shape group on
+a BGR copy of the resident pixels (made only when one of them is on - or pHash without thumbnails, which keeps its per-group fe_phash),
+and the dicts come back in input order with the same keys and values.
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -106,7 +108,7 @@ class BatchScorer:
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
     def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False, _tech=None, _hashes=None,
-                      _thumbs=None):
+                      _thumbs=None, _faces=None):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
@@ -117,7 +119,9 @@ class BatchScorer:
         _tech (the mixed-size path): the technical dicts of these images (TechnicalAnalyzer.analyze_mixed), computed by the caller - the
         statistics call is skipped, and the BGR copy is made only when a stage that reads it is on.
         _hashes / _thumbs (the mixed-size path): the phash strings / thumbnail bytes of these images (fe_phash_mixed, fe_thumbnail_jpeg_mixed),
-        computed by the caller - that stage is skipped and asks for no BGR copy."""
+        computed by the caller - that stage is skipped and asks for no BGR copy.
+        _faces (the mixed-size path): the face dicts of these images (FaceAnalyzer.analyze_faces_mixed), computed by the caller - the face
+        calls are skipped, ask for no BGR copy and for no host pixels."""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -131,13 +135,13 @@ class BatchScorer:
             # one upload; the BGR copy the reference keeps as img_cv is made on the device, and every engine call reads the resident batch
             if _resident is None:
                 e.h2d(d_rgb, imgs)
-            elif (self.face_analyzer is not None and self.face_analyzer.available and not getattr(self.face_analyzer, 'gpu_thumbnails', False)) \
-                    or self.vlm_composition is not None:      # face thumbnails cut on the engine need no host pixels
+            elif (_faces is None and self.face_analyzer is not None and self.face_analyzer.available and
+                  not getattr(self.face_analyzer, 'gpu_thumbnails', False)) or self.vlm_composition is not None:      # face thumbnails cut on the engine need no host pixels
                 imgs = np.empty((n, h, w, 3), np.uint8)
                 e.d2h(imgs, d_rgb)
             faces_on = self.face_analyzer is not None and self.face_analyzer.available
             bgr_dev = None
-            if _tech is None or faces_on or (leading_lines is None and self.detect_lines) or (self.phash and _hashes is None) or \
+            if _tech is None or (faces_on and _faces is None) or (leading_lines is None and self.detect_lines) or (self.phash and _hashes is None) or \
                     (self.thumbnails and _thumbs is None) or self.subject_region:
                 d_bgr = e.dev_alloc(n * h * w * 3)
                 e.swap_rb(d_rgb, n * h * w, d_bgr)
@@ -148,8 +152,8 @@ class BatchScorer:
                 tech_ = _tech
                 if tech_ is None:
                     tech_ = TechnicalAnalyzer.analyze_batch(eng, bgr_dev, self.shadow_threshold, self.highlight_threshold, self.mono_threshold)
-                faces_ = None
-                if faces_on:
+                faces_ = _faces
+                if faces_on and faces_ is None:
                     faces_ = self.face_analyzer.analyze_faces_batch([imgs[i][..., ::-1] for i in range(n)] if imgs is not None else None,
                                                                     resident=bgr_dev)
                 lines_ = leading_lines
@@ -303,10 +307,11 @@ class BatchScorer:
         return out
 
     def _process_mixed(self, entries, out, exif, leading_lines):
-        """entries: [(indices into out, (device_ptr, k, h, w), owned)] - resident RGB batches of one shape each. One ensemble_score_mixed call
-        and one analyze_mixed call over every image of every entry, by pointers into the resident batches (the second on the aux engine's
-        worker beside the first when there is one); then process_batch per entry for the stages that run per shape, with its records and
-        technical dicts handed in. An owned batch is freed by process_batch (or here, when the ensemble call fails)."""
+        """entries: [(indices into out, (device_ptr, k, h, w), owned)] - resident RGB batches of one shape each. One ensemble_score_mixed call,
+        one analyze_mixed call and, with a face analyzer, one analyze_faces_mixed call over every image of every entry, by pointers into the
+        resident batches (all but the first on the aux engine's worker beside the first when there is one); then process_batch per entry
+        for the stages that run per shape, with its records, technical dicts and face dicts handed in. An owned batch is freed by
+        process_batch (or here, when the ensemble call fails)."""
         e = self.engine
         order, ptrs, sizes = [], [], []
         for idx, (p, k, h, w), _ in entries:
@@ -316,8 +321,13 @@ class BatchScorer:
         by_input = sorted(range(len(order)), key=lambda r: order[r])      # the calls see the images in input order
         resident = ([ptrs[r] for r in by_input], [sizes[r] for r in by_input])
 
-        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels; then the index columns
+        fa = self.face_analyzer if (self.face_analyzer is not None and self.face_analyzer.available) else None
+        host_bgr = None      # the chunk's host pixels as B,G,R views in input order, fetched below only when Pillow cuts the face thumbnails
+
+        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels; then the faces and the index columns
             tech_ = TechnicalAnalyzer.analyze_mixed(eng, resident, self.shadow_threshold, self.highlight_threshold, self.mono_threshold, order='rgb')
+            # the face dicts of the whole chunk (the analyzer holds its own context: the aux engine when there is one), R,G,B read in place
+            faces_ = fa.analyze_faces_mixed(host_bgr, resident=resident, order='rgb') if fa is not None else None
             hashes_ = thumbs_ = None
             # Indexing (thumbnails on, the reference's two columns per photo): one fe_thumbnail_jpeg_mixed and, with phash on, one
             # fe_phash_mixed over the whole chunk, R,G,B read in place, so neither asks process_batch for a BGR copy. pHash without
@@ -328,19 +338,26 @@ class BatchScorer:
                 if self.phash:
                     from .phash import phash_mixed, to_hex
                     hashes_ = to_hex(phash_mixed(eng, resident, order='rgb'))
-            return tech_, hashes_, thumbs_
+            return tech_, hashes_, thumbs_, faces_
 
         try:
+            if fa is not None and not getattr(fa, 'gpu_thumbnails', False):
+                views = {}
+                for idx, (p, k, h, w), _ in entries:
+                    a = np.empty((k, h, w, 3), np.uint8)
+                    e.d2h(a, p)
+                    views.update((i, a[j][..., ::-1]) for j, i in enumerate(idx))
+                host_bgr = [views[order[r]] for r in by_input]
             if self._pool is not None:      # beside the ensemble call, on the aux context (module docstring, "Overlap")
                 e.sync()                    # whatever filled the resident batches on this context's stream is complete
                 fut = self._pool.submit(stats, self.aux_engine)
                 try:
                     rec, mask = e.ensemble_score_mixed(resident)
                 finally:
-                    tech, hashes, thumbs = fut.result()      # also on error: the worker must be done before the buffers go
+                    tech, hashes, thumbs, faces = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score_mixed(resident)
-                tech, hashes, thumbs = stats(e)
+                tech, hashes, thumbs, faces = stats(e)
         except Exception:
             for _, dev, owned in entries:
                 if owned:
@@ -353,7 +370,8 @@ class BatchScorer:
                                          leading_lines=[leading_lines[i] for i in idx] if leading_lines is not None else None, _resident=dev,
                                          _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned, _tech=[tech[row[i]] for i in idx],
                                          _hashes=[hashes[row[i]] for i in idx] if hashes is not None else None,
-                                         _thumbs=[thumbs[row[i]] for i in idx] if thumbs is not None else None)
+                                         _thumbs=[thumbs[row[i]] for i in idx] if thumbs is not None else None,
+                                         _faces=[faces[row[i]] for i in idx] if faces is not None else None)
             except Exception:
                 for _, dev2, owned2 in entries[n_done + 1:]:
                     if owned2:

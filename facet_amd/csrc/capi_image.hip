@@ -121,34 +121,6 @@ void ensure_phash_cos(fe_ctx* ctx) {
   FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
 }
 
-// What the mixed-size entry points check alike: the list, the order and every image's pointer and size. max_h / max_w: the entry point's
-// limits; below_2_31: h * w must stay below 2^31 as well. false: FE_ERR_INVALID with the message in the context.
-bool mixed_list_ok(Ctx& C, const char* who, const void* list, const int32_t* hw, int n, int order, const uint8_t* const* images, int max_h, int max_w,
-                   bool below_2_31) {
-  char b[240];
-  if (!list || !hw || n <= 0) {
-    snprintf(b, sizeof b, "%s: bad arguments (null list, null output or n <= 0)", who);
-    C.err = b;
-    return false;
-  }
-  if (order != FE_ORDER_BGR && order != FE_ORDER_RGB) {
-    snprintf(b, sizeof b, "%s: order %d is neither FE_ORDER_BGR (0) nor FE_ORDER_RGB (1)", who, order);
-    C.err = b;
-    return false;
-  }
-  for (int i = 0; i < n; ++i) {
-    const int h = hw[2 * i], w = hw[2 * i + 1];
-    if (!images[i]) { snprintf(b, sizeof b, "%s: image %d is a null pointer", who, i); C.err = b; return false; }
-    if (h < 1 || w < 1 || h > max_h || w > max_w || (below_2_31 && (size_t)h * (size_t)w >= ((size_t)1 << 31))) {
-      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h must be within 1 .. %d and w within 1 .. %d%s", who, i, h, w, max_h, max_w,
-               below_2_31 ? ", h * w below 2^31" : "");
-      C.err = b;
-      return false;
-    }
-  }
-  return true;
-}
-
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // fe_phash_mixed behind its argument checks: descriptors and pool of the whole list, then chunk by chunk through the arena

@@ -235,6 +235,9 @@ void launch_jpeg_encode(Ctx& c, const uint8_t* d_img, int n, int h, int w, int b
 // Returns false when a row was too small for its face.
 bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes,
                      int quality, uint8_t* out, size_t cap, int32_t* lengths);
+// the same for images of any sizes: d_imgs device descriptors (face_mixed_plan.h: src, h, w) of the images img_index refers to; rgb: R,G,B pixels
+bool face_thumbnails_mixed(Ctx& c, const face_plan::ImageDesc* d_imgs, int rgb, int m, const int32_t* img_index, const int32_t* crops,
+                           const int32_t* out_sizes, int quality, uint8_t* out, size_t cap, int32_t* lengths);
 
 // thumbnails of a list of images of any sizes (kernels_jpeg.hip; descriptors and pool: thumb_mixed_core.h): one chunk's reduce, resize
 // and encode, one launch per stage. descs [n] host descriptors with device sources; their buffers and every scratch array come from the

@@ -5,6 +5,7 @@
 #include "fe_check.h"
 #include "erf_core.h"
 #include "stats_plan.h"
+#include "face_mixed_plan.h"
 #include <cstdint>
 #include <cstdio>
 #include <atomic>
@@ -476,6 +477,19 @@ void launch_scrfd_decode(const float* scores, const float* bbox, const float* kp
                          float thresh, float det_scale, int level, float* cand, int* counts, int max_cand, hipStream_t s);
 void cv_resize_tables(int src, int dst, bool clamp_fx, std::vector<int>& ofs, std::vector<short>& coef);
 void cv_warp_weight_table(std::vector<short>& wtab);
+// kernels_face_mixed.hip: the same steps for a list of images of any sizes, from the descriptors of face_mixed_plan.h. rgb: the source
+// pixels are R,G,B (0: B,G,R). descs / pool / img_of / Minv / rois are device arrays.
+// dst [nb][det_h][det_w][4] fp32: resize into the corner of the zero canvas + blobFromImage((x - 127.5) / 128, channels as the graph takes them)
+void launch_det_input_mixed(const face_plan::ImageDesc* descs, int nb, const int32_t* pool, int det_h, int det_w, int rgb, float* dst, hipStream_t s);
+// recs [n][max_cand + 1][16]: row 0 of an image holds its int count (zeroed by the caller), the candidates follow
+void launch_scrfd_decode_mixed(const float* scores, const float* bbox, const float* kps, int n, int fh, int fw, int A, int K, int stride, float thresh,
+                               const face_plan::ImageDesc* descs, int level, float* recs, int max_cand, hipStream_t s);
+void launch_warp_affine_mixed(const face_plan::ImageDesc* descs, const int* img_of, const double* Minv, int m, int S, const short* wtab, uint8_t* dst,
+                              hipStream_t s);
+// warp + launch_u8_blob in one: dst [m][S][S][4] fp32; first: the byte (0 or 2) of a source pixel that goes to channel 0
+void launch_warp_affine_blob_mixed(const face_plan::ImageDesc* descs, const int* img_of, const double* Minv, int m, int S, const short* wtab, float* dst,
+                                   float mean, float scale, int first, hipStream_t s);
+void launch_roi_laplacian_mixed(const face_plan::ImageDesc* descs, int rgb, const int* img_of, const int* rois, int m, double* out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // Per-image technical statistics (kernels_stats.hip)

@@ -73,6 +73,29 @@ __global__ __launch_bounds__(FT_THREADS) void face_hpass_kernel(const uint8_t* _
   }
 }
 
+// The same pass for a list of images of any sizes (fe_face_thumbnails_mixed): source pointer and width of the face's image come from its
+// descriptor (face_mixed_plan.h); rgb: the source pixels are R,G,B, and mid is written B,G,R as the passes after this one read it.
+__global__ __launch_bounds__(FT_THREADS) void face_hpass_mixed_kernel(const face_plan::ImageDesc* __restrict__ imgs, int rgb, const FaceThumb* __restrict__ descs,
+                                                                      uint8_t* __restrict__ mid) {
+  const FaceThumb d = descs[blockIdx.y];
+  const face_plan::ImageDesc im = imgs[d.img];
+  const int total = d.ch * d.ow;
+  const int w = im.w;
+  const uint8_t* src = im.src + ((size_t)d.y0 * w + d.x0) * 3;
+  uint8_t* dst = mid + d.mid_off;
+  for (int i = blockIdx.x * FT_THREADS + threadIdx.x; i < total; i += gridDim.x * FT_THREADS) {
+    const int xx = i % d.ow, yy = i / d.ow;
+    int first, count, kc;
+    box_window(xx, d.cw, d.sx, d.supx, d.ssx, first, count, kc);
+    const uint8_t* p = src + ((size_t)yy * w + first) * 3;
+    int s0 = 0, s1 = 0, s2 = 0;
+    for (int x = 0; x < count; ++x) { s0 += p[0]; s1 += p[1]; s2 += p[2]; p += 3; }
+    if (rgb) { const int t = s0; s0 = s2; s2 = t; }
+    uint8_t* o = dst + (size_t)i * 3;
+    o[0] = clip8_22((1 << 21) + s0 * kc); o[1] = clip8_22((1 << 21) + s1 * kc); o[2] = clip8_22((1 << 21) + s2 * kc);
+  }
+}
+
 // mid [ch][ow][3] -> pix [oh][ow][3]
 __global__ __launch_bounds__(FT_THREADS) void face_vpass_kernel(const FaceThumb* __restrict__ descs, const uint8_t* __restrict__ mid,
                                                                 uint8_t* __restrict__ pix) {
@@ -258,11 +281,13 @@ __global__ __launch_bounds__(FT_THREADS) void face_jpeg_kernel(const FaceThumb* 
 
 static_assert(FT_LDS_BLOCKS == 6 * (FE_FACE_THUMB_FUSED_SIDE / 16) * (FE_FACE_THUMB_FUSED_SIDE / 16), "the header states the fused encoder's limit");
 
-// d_bgr [n][h][w][3] on the device; img_index [m], crops [m][4], out_sizes [m][2] on the host and already validated. out [m][cap] and
-// lengths [m] are host buffers with fe_jpeg_encode's contract. Returns false when a row was too small. Faces are served in groups
-// whose scratch fits the arena; the scratch of a group is released (stream order) before the next one takes it.
-bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes,
-                     int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+// img_index [m], crops [m][4], out_sizes [m][2] on the host and already validated. out [m][cap] and lengths [m] are host buffers with
+// fe_jpeg_encode's contract. Returns false when a row was too small. Faces are served in groups whose scratch fits the arena; the
+// scratch of a group is released (stream order) before the next one takes it. hpass(grid, d_desc, mid) launches the horizontal pass, the
+// one kernel that reads the source images.
+template <class HPass>
+static bool face_thumbnails_run(Ctx& c, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes, int quality, uint8_t* out, size_t cap,
+                                int32_t* lengths, HPass&& hpass) {
   FE_CHECK(quality >= 1 && quality <= 100, "jpeg: quality %d (1 .. 100)", quality);
   const Tables* tab = jpeg_tables(c, 0, 0, quality);
   static std::atomic<uint64_t> lds_set{0};
@@ -319,8 +344,7 @@ bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, c
     if (!list_lds.empty()) FE_HIP(hipMemcpyAsync(d_list, list_lds.data(), list_lds.size() * sizeof(int), hipMemcpyHostToDevice, c.stream));
     if (!list_glb.empty())
       FE_HIP(hipMemcpyAsync(d_list + list_lds.size(), list_glb.data(), list_glb.size() * sizeof(int), hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(face_hpass_kernel, dim3((unsigned)std::min((max_h + FT_THREADS - 1) / FT_THREADS, 64), nb), dim3(FT_THREADS), 0, c.stream, d_bgr, h, w,
-                       d_desc, mid);
+    hpass(dim3((unsigned)std::min((max_h + FT_THREADS - 1) / FT_THREADS, 64), nb), d_desc, mid);
     hipLaunchKernelGGL(face_vpass_kernel, dim3((unsigned)std::min((max_v + FT_THREADS - 1) / FT_THREADS, 64), nb), dim3(FT_THREADS), 0, c.stream, d_desc, mid,
                        pix);
     if (!list_lds.empty())
@@ -344,6 +368,22 @@ bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, c
     f0 = f1;
   }
   return fits;
+}
+
+// d_bgr [n][h][w][3] on the device
+bool face_thumbnails(Ctx& c, const uint8_t* d_bgr, int n, int h, int w, int m, const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes,
+                     int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  return face_thumbnails_run(c, m, img_index, crops, out_sizes, quality, out, cap, lengths, [&](dim3 grid, const FaceThumb* d_desc, uint8_t* mid) {
+    hipLaunchKernelGGL(face_hpass_kernel, grid, dim3(FT_THREADS), 0, c.stream, d_bgr, h, w, d_desc, mid);
+  });
+}
+
+// d_imgs: device descriptors (src, h, w) of the images img_index refers to; rgb: their pixels are R,G,B
+bool face_thumbnails_mixed(Ctx& c, const face_plan::ImageDesc* d_imgs, int rgb, int m, const int32_t* img_index, const int32_t* crops,
+                           const int32_t* out_sizes, int quality, uint8_t* out, size_t cap, int32_t* lengths) {
+  return face_thumbnails_run(c, m, img_index, crops, out_sizes, quality, out, cap, lengths, [&](dim3 grid, const FaceThumb* d_desc, uint8_t* mid) {
+    hipLaunchKernelGGL(face_hpass_mixed_kernel, grid, dim3(FT_THREADS), 0, c.stream, d_imgs, rgb, d_desc, mid);
+  });
 }
 
 }  // namespace fe

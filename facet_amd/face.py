@@ -18,6 +18,7 @@ standins.synthetic_onnx). insightface internals follow the published package [DE
 gray/Laplacian are restated in numpy and thumbnails are Pillow's BOX resize + JPEG (parity with cv2's INTER_AREA + cv2.imencode is
 unpinned); the engine's thumbnails are byte for byte the Pillow ones.
 """
+import ctypes as C
 import io
 import os
 
@@ -155,6 +156,32 @@ def face_thumbnails(engine, batch, boxes_per_image, size=128, quality=85, paddin
     return out
 
 
+def _mixed_sizes(images):
+    """[(h, w), ...] of what Engine._img_list takes: a list of [h, w, 3] arrays, or (device_pointers, sizes)."""
+    if isinstance(images, tuple):
+        return [(int(h), int(w)) for h, w in images[1]]
+    return [tuple(int(v) for v in np.shape(a)[:2]) for a in images]
+
+
+def face_thumbnails_mixed(engine, images, boxes_per_image, size=128, quality=85, padding=0.3, order='bgr'):
+    """face_thumbnails for images that each have their own size: images = a list of uint8 [h, w, 3] arrays or (device_pointers, sizes);
+    order 'bgr' / 'rgb' is the byte order of their pixels. Returns the same list per image of bytes | None, for all boxes of all images in
+    one fe_face_thumbnails_mixed call."""
+    sizes = _mixed_sizes(images)
+    assert len(boxes_per_image) == len(sizes)
+    out = [[None] * len(boxes) for boxes in boxes_per_image]
+    where, idx, crops, osz = [], [], [], []
+    for i, (boxes, (h, w)) in enumerate(zip(boxes_per_image, sizes)):
+        for j, box in enumerate(boxes):
+            plan = face_thumbnail_plan(box, h, w, size, padding)
+            if plan is not None:
+                where.append((i, j)); idx.append(i); crops.append(plan[:4]); osz.append(plan[4:])
+    if where:
+        for (i, j), blob in zip(where, engine.face_thumbnails_mixed(images, idx, crops, osz, int(quality), order=order)):
+            out[i][j] = blob
+    return out
+
+
 class _GraphsHandle:
     """What ModelManager pokes at when it parks a model in RAM: .cpu() frees the device graphs, .to(dev) loads them again."""
 
@@ -231,6 +258,16 @@ class FaceEngine:
         if not isinstance(images, tuple):       # (device_ptr, n, h, w) batches are used in place
             images = np.ascontiguousarray(images, dtype=np.uint8)
         rec, counts, mask = self.engine.face_analyze(images, self.det_size, self.det_thresh, self.nms_thresh, self.max_faces)
+        return self._faces_of(rec, counts, mask)
+
+    def get_batch_mixed(self, images, order='bgr'):
+        """get_batch for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for resident
+        images; order 'bgr' / 'rgb' is the byte order of their pixels. One engine call (fe_face_analyze_mixed): every graph runs over
+        full micro-batches whatever the shapes, and no per-size table is kept."""
+        rec, counts, mask = self.engine.face_analyze_mixed(images, self.det_size, self.det_thresh, self.nms_thresh, self.max_faces, order=order)
+        return self._faces_of(rec, counts, mask)
+
+    def _faces_of(self, rec, counts, mask):
         out = []
         for i in range(rec.shape[0]):
             faces = []
@@ -412,6 +449,61 @@ class FaceAnalyzer:
             if d is not None:
                 e.dev_free(d)
         out = [self._post(faces, arr[i], lambda x1, y1, x2, y2, i=i: table[(i, x1, y1, x2, y2)], thumbnails=thumbs is None)
+               for i, faces in enumerate(per_image)]
+        if thumbs is not None:
+            for r, blobs in zip(out, thumbs):
+                for f, blob in zip(r['face_details'], blobs):
+                    f['thumbnail'] = blob
+        return out
+
+    def analyze_faces_mixed(self, images, resident=None, order='bgr'):
+        """analyze_faces_batch for images that each have their own size -> list of analyze_faces dicts. images: a list of uint8 [h, w, 3]
+        arrays in the byte order `order` names ('bgr' / 'rgb'). resident: optional (device_pointers, sizes) of the same images already in
+        device memory, in that byte order - then `images` are only read for the thumbnails of the faces found (Pillow, from B,G,R
+        arrays or views), and with `gpu_thumbnails` not at all: `images` may then be None. One fe_face_analyze_mixed call, one
+        fe_roi_laplacian_mixed call for every ROI the reference logic looks at and, with `gpu_thumbnails`, one fe_face_thumbnails_mixed call."""
+        if resident is not None:
+            sizes = _mixed_sizes(resident)
+            if self.gpu_thumbnails or images is None:
+                images = [np.broadcast_to(np.uint8(0), (h, w, 3)) for h, w in sizes]      # only their shape is read
+        if not self.available or images is None or len(images) == 0:
+            return [self._zeros() for _ in (images if images is not None else [])]
+        e = self.face_app.engine
+        d = None
+        try:
+            if resident is None:      # one upload: every image on a 256-byte boundary of one allocation, read in place by the three calls
+                arrs = [np.ascontiguousarray(np.asarray(im), dtype=np.uint8) for im in images]
+                starts, at = [], 0
+                for a in arrs:
+                    starts.append(at)
+                    at += -(-a.nbytes // 256) * 256
+                d = e.dev_alloc(max(at, 256))
+                for a, s0 in zip(arrs, starts):
+                    e.h2d(C.c_void_p(d.value + s0), a)
+                dev = ([d.value + s0 for s0 in starts], [a.shape[:2] for a in arrs])
+                host_bgr = arrs if order == 'bgr' else [a[..., ::-1] for a in arrs]
+            else:
+                assert len(resident[0]) == len(images)
+                dev, host_bgr = resident, images
+            per_image = self.face_app.get_batch_mixed(dev, order=order)
+            # as analyze_faces_batch: the first pass records the ROIs and the accepted faces, one engine call scans all ROIs
+            wanted = []
+            first = [self._post(faces, host_bgr[i], lambda x1, y1, x2, y2, i=i: (wanted.append((i, x1, y1, x2, y2)), (0.0, 0.0))[1], thumbnails=False)
+                     for i, faces in enumerate(per_image)]
+            table = {}
+            if wanted:
+                st = e.roi_laplacian_mixed(dev, [r[0] for r in wanted], [r[1:] for r in wanted], order=order)
+                for r, (ls, lss, gs, cnt) in zip(wanted, st):
+                    mean = ls / cnt
+                    table[r] = (lss / cnt - mean * mean, gs / cnt)
+            thumbs = None
+            if self.gpu_thumbnails:
+                thumbs = face_thumbnails_mixed(e, dev, [[f['bbox'] for f in r['face_details']] for r in first], self.thumbnail_size,
+                                               self.thumbnail_quality, order=order)
+        finally:
+            if d is not None:
+                e.dev_free(d)
+        out = [self._post(faces, host_bgr[i], lambda x1, y1, x2, y2, i=i: table[(i, x1, y1, x2, y2)], thumbnails=thumbs is None)
                for i, faces in enumerate(per_image)]
         if thumbs is not None:
             for r, blobs in zip(out, thumbs):

@@ -728,6 +728,43 @@ int fe_set_stats_segment(fe_ctx* ctx, int pixels);
 int fe_roi_laplacian(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int m, const int* img_index, const int* rois,
                      double* out);
 
+/* ---- the face calls for a list of images that each have their own size ---------------------------------------------------------------
+ * images [n] pointers to uint8 [h][w][3] images, hw [n][2] = h, w, on_device, order: as for fe_image_stats_mixed (h, w within 1 .. 65535,
+ * h * w below 2^31). Device images are read in place at any byte alignment, in the byte order `order` names: an RGB batch needs no BGR
+ * copy. A null list, a null image pointer, n <= 0, a bad size, an image whose aspect ratio leaves an empty detector input, a bad order or
+ * a bad det_h / det_w returns FE_ERR_INVALID; the message names the index of the image where one is at fault; the whole list is checked
+ * before anything is launched. Host images go through the arena, each on a 256-byte boundary; one that cannot fit returns
+ * FE_ERR_CAPACITY and the message names it. The cv2.resize weight tables of a call live in the arena for the length of the call: none
+ * of these calls adds to the tables the per-shape calls keep per size (fe_face_cache_entries counts those).
+ *
+ * fe_face_analyze_mixed = fe_face_analyze over the list: micro-batches of 2 * fe_set_microbatch images whatever their shapes (host input:
+ * fewer when their staged bytes pass a quarter of the arena). Per micro-batch one launch writes the detector's fp32 input from the source
+ * images (resize into the corner of the zero canvas + blobFromImage), the detector runs on all of it, one copy brings counts and
+ * candidates to the host for sort + NMS, and the landmark and recognition graphs run over ALL faces of the micro-batch, their crops warped
+ * straight into the graphs' fp32 input. faces [n][max_faces][FE_FACE_FLOATS], counts [n], models_run: as for fe_face_analyze, in input
+ * order; the same network outputs give the same records as fe_face_analyze of each image alone (a graph's summation order may depend on
+ * the batch it runs in, so records agree to rounding, not to the bit).
+ * fe_face_crops_run_mixed = fe_face_crops_run over the list (swap_rb as there: what it means for B,G,R pixels; R,G,B pixels reach the
+ * graph in the same channel order). crops_out receives the bytes in the source's order. Host images are staged all at once.
+ * fe_face_det_input_mixed: out [n][det_h][det_w][4] fp32 (host) = the detector input of every image. For the parity tests.
+ * fe_roi_laplacian_mixed / fe_face_thumbnails_mixed = fe_roi_laplacian / fe_face_thumbnails with img_index into the list; every double
+ * and every byte equals the per-shape call's. Host images are staged all at once. */
+int fe_face_analyze_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int det_h, int det_w,
+                          float det_thresh, float nms_thresh, int max_faces, float* faces, int* counts, int* models_run);
+int fe_face_crops_run_mixed(fe_ctx* ctx, int slot, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int m,
+                            const int* img_index, const double* M, int size, float mean, float scale, int swap_rb, float* out, int out_dim,
+                            uint8_t* crops_out);
+int fe_face_det_input_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int det_h, int det_w,
+                            float* out);
+int fe_roi_laplacian_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int m, const int* img_index,
+                           const int* rois, double* out);
+int fe_face_thumbnails_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int m,
+                             const int32_t* img_index, const int32_t* crops, const int32_t* out_sizes, int quality, uint8_t* out, size_t cap,
+                             int32_t* lengths);
+/* entries: the number of cv2.resize weight tables the context keeps per (source length, target length): fe_face_detect, fe_face_analyze
+ * and fe_cv_resize_linear_u8 add two with every new size, the mixed calls never do. */
+int fe_face_cache_entries(fe_ctx* ctx, int32_t* entries);
+
 /* The reference holds every image twice, as PIL RGB and as cv2 BGR (processing/batch_processor.py:200-215). With a resident batch
  * the second copy is made on the device: dst_device [pixels][3] = src [pixels][3] with the first and third byte of every pixel
  * exchanged. src: host (on_device = 0) or device memory; not in place. */

@@ -15,7 +15,14 @@ the median of R calls after one warm-up call, with the fastest and the slowest b
 perf_mixed.py --index [--repeats R]: the `phash` and `thumbnail` columns alone (written to profiles/mixed_index_perf.txt). The same chunks and
 the 6000 x 4000 image: per shape group as process_batch computes them (a device allocation, fe_swap_rb_u8, fe_phash / fe_thumbnail_jpeg on
 the BGR copy, the free - what a mixed chunk cost before fe_phash_mixed / fe_thumbnail_jpeg_mixed existed) against one mixed call on the RGB
-pixels; then process_images with both columns on and mixed_sizes off / on, and the device memory in use over three chunks of new shapes."""
+pixels; then process_images with both columns on and mixed_sizes off / on, and the device memory in use over three chunks of new shapes.
+
+perf_mixed.py --faces [--repeats R] [--det-thresh T]: the face stage alone (written to profiles/mixed_faces_perf.txt), with the stand-in
+graphs of standins/ at det_size 640 and at most 8 faces kept per photo. The same chunks: per shape group as process_batch does it (a device
+allocation, fe_swap_rb_u8, fe_face_analyze and fe_roi_laplacian on the BGR copy, the free) against one fe_face_analyze_mixed and one
+fe_roi_laplacian_mixed call on the RGB pixels; then process_images with a face analyzer (gpu_thumbnails) on and mixed_sizes off / on, and
+Engine.face_cache_entries() with the device memory in use over three chunks of new shapes. On a checkout without the mixed face calls only
+the process_images rows and the per-shape memory row are printed: that is how the parent commit is measured in the same session."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -33,6 +40,8 @@ ap.add_argument("--mixed-only", action="store_true", help="skip the rows with mi
 ap.add_argument("--policies", default="f32,parity")
 ap.add_argument("--stats", action="store_true", help="the statistics table instead of the process_images table")
 ap.add_argument("--index", action="store_true", help="the pHash / thumbnail table instead of the process_images table")
+ap.add_argument("--faces", action="store_true", help="the face-stage table instead of the process_images table")
+ap.add_argument("--det-thresh", type=float, default=0.54, help="--faces: the stand-in detector's scores crowd around 0.5; 0.54 leaves a few faces per photo")
 ap.add_argument("--repeats", type=int, default=7)
 args = ap.parse_args()
 n, fresh_chunks = args.n, args.chunks_of_256
@@ -191,6 +200,110 @@ if args.index:
                     e.phash(a[None]); thumbnails(e, a[None], 640, 80)
             mem.append(used_mib())
         print(f"{'one mixed call each' if mixed else 'per shape':22} tables {e.resize_cache_entries():5}  MiB " + " / ".join(f"{m:.0f}" for m in mem), flush=True)
+    e.close()
+    sys.exit(0)
+
+FACE_DET, FACE_NMS, FACE_MAX = (640, 640), 0.4, 8
+
+
+def face_rois(rec, counts, sizes):
+    """The face boxes a call found, clipped to their images as FaceAnalyzer._get_crop_sharpness clips them: (image indices, rois)."""
+    idx, rois = [], []
+    for i, (h, w) in enumerate(sizes):
+        for f in range(min(int(counts[i]), rec.shape[1])):
+            x1, y1, x2, y2 = (int(v) for v in rec[i, f, 0:4])
+            x1, y1, x2, y2 = max(0, x1), max(0, y1), min(w, x2), min(h, y2)
+            if x2 > x1 and y2 > y1:
+                idx.append(i); rois.append((x1, y1, x2, y2))
+    return idx, rois
+
+
+def face_rows(e, label, imgs, repeats):
+    """The face stage of a chunk that is resident as RGB, grouped by shape as _process_images_mixed lays it out."""
+    groups = {}
+    for i, a in enumerate(imgs):
+        groups.setdefault(a.shape[:2], []).append(i)
+    bufs, ptrs, sizes = [], [None] * len(imgs), [a.shape[:2] for a in imgs]
+    for (h, w), idx in groups.items():
+        d = e.dev_alloc(len(idx) * h * w * 3)
+        e.h2d(d, np.stack([imgs[i] for i in idx]))
+        bufs.append((d, len(idx), h, w))
+        for j, i in enumerate(idx):
+            ptrs[i] = d.value + j * h * w * 3
+    found, kept = [0, 0], [0, 0]      # ROIs scanned and faces kept (they went through the two crop graphs): per group, mixed
+
+    def per_group():
+        found[0] = kept[0] = 0
+        for d, k, h, w in bufs:
+            d_bgr = e.dev_alloc(k * h * w * 3)
+            try:
+                e.swap_rb(d, k * h * w, d_bgr)
+                rec, counts, _ = e.face_analyze((d_bgr, k, h, w), FACE_DET, args.det_thresh, FACE_NMS, FACE_MAX)
+                idx, rois = face_rois(rec, counts, [(h, w)] * k)
+                found[0] += len(idx)
+                kept[0] += int(np.minimum(counts, FACE_MAX).sum())
+                if idx:
+                    e.roi_laplacian((d_bgr, k, h, w), idx, rois)
+            finally:
+                e.dev_free(d_bgr)
+
+    def mixed():
+        rec, counts, _ = e.face_analyze_mixed((ptrs, sizes), FACE_DET, args.det_thresh, FACE_NMS, FACE_MAX, order='rgb')
+        idx, rois = face_rois(rec, counts, sizes)
+        found[1], kept[1] = len(idx), int(np.minimum(counts, FACE_MAX).sum())
+        if idx:
+            e.roi_laplacian_mixed((ptrs, sizes), idx, rois, order='rgb')
+
+    print(f"{label:22} {'per group: alloc + swap + fe_face_analyze + fe_roi_laplacian':62} {timed(per_group, repeats)}", flush=True)
+    print(f"{label:22} {'fe_face_analyze_mixed + fe_roi_laplacian_mixed':62} {timed(mixed, repeats)}", flush=True)
+    what = 'fe_face_analyze_mixed alone'
+    print(f"{label:22} {what:62} {timed(lambda: e.face_analyze_mixed((ptrs, sizes), FACE_DET, args.det_thresh, FACE_NMS, FACE_MAX, order='rgb'), repeats)}", flush=True)
+    print(f"{label:22} faces kept (landmark and recognition crops): {kept[0]} per group, {kept[1]} mixed; ROIs scanned: {found[0]}, {found[1]}", flush=True)
+    for b in bufs:
+        e.dev_free(b[0])
+
+
+if args.faces:
+    from standins import synthetic_onnx as S
+    from facet_amd.face import FaceAnalyzer
+    has_mixed = hasattr(Engine, "face_analyze_mixed")
+    e = Engine(0, arena_bytes=(4 + 2 * 8) << 30)      # bench.py's arena for the default micro-batch of 8 at 1024 x 1024
+    models = {"det": S.scrfd_like(seed=12, size=640)[0], "lmk": S.landmark_like(seed=13)[0], "rec": S.arcface_iresnet(layers=(1, 1, 1, 1), seed=14)[0]}
+    fa = FaceAnalyzer(min_confidence=args.det_thresh, min_face_size=10, engine=e, models=models, gpu_thumbnails=True)
+    assert fa.available
+    fa.face_app.det_thresh, fa.face_app.max_candidates, fa.face_app.max_faces = args.det_thresh, 4096, FACE_MAX
+    print(f"{n} images per chunk, sides 776 .. 1280, resident RGB; stand-in graphs, det_size 640, det_thresh {args.det_thresh}, at most {FACE_MAX} faces kept per image")
+    print(f"milliseconds per chunk: median (fastest .. slowest) of {args.repeats} calls after a warm-up")
+    if has_mixed:
+        for n_shapes in (1, 16, 256):
+            shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+            face_rows(e, f"{n} images, {n_shapes} shapes", chunk(shapes), args.repeats)
+    e.load_weights(FE_MODEL_TOPIQ, synthetic_state_dict("topiq", 4))
+    print("process_images, face analyzer (gpu_thumbnails) on, TOPIQ only: milliseconds per chunk (upload included)")
+    for n_shapes in (1, 16, 256):
+        shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+        imgs = chunk(shapes)
+        for mixed in (False, True):
+            bs = BatchScorer(e, face_analyzer=fa, mixed_sizes=mixed)
+            print(f"{n} images, {n_shapes:3} shapes  mixed_sizes={str(mixed):5} {timed(lambda: bs.process_images(imgs), max(3, args.repeats // 2))}", flush=True)
+    print("cv2.resize tables kept by the context and device MiB in use before / after each of three chunks of new shapes (faces of every image)")
+    next_shape = 1024
+    for mixed in ((False, True) if has_mixed else (False,)):
+        mem = [used_mib()]
+        tables = [e.face_cache_entries()] if has_mixed else []
+        for r in range(3):
+            imgs = chunk([shape(next_shape + k) for k in range(256)], first=r * n)
+            next_shape += 256
+            if mixed:
+                e.face_analyze_mixed(imgs, FACE_DET, args.det_thresh, FACE_NMS, FACE_MAX, order='rgb')
+            else:
+                for a in imgs:
+                    e.face_analyze(a[None], FACE_DET, args.det_thresh, FACE_NMS, FACE_MAX)
+            mem.append(used_mib())
+            if has_mixed:
+                tables.append(e.face_cache_entries())
+        print(f"{'one mixed call' if mixed else 'per shape':22} " + ("tables " + " / ".join(str(t) for t in tables) + "  " if has_mixed else "") +
+              "MiB " + " / ".join(f"{m:.0f}" for m in mem), flush=True)
     e.close()
     sys.exit(0)
 
