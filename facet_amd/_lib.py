@@ -215,6 +215,11 @@ SIGNATURES = {
     "fe_external_contours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_subject_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "fe_leading_lines_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_subject_region_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_lines_host_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fe_phash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_phash_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_thumbnail_jpeg_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -1631,6 +1636,57 @@ class Engine:
             self.h, p, n, h, w, dev, room, rec, cnt, thr.ctypes.data_as(C.c_void_p) if want_thresholds else None,
             edges.ctypes.data_as(C.c_void_p) if want_edges else None), n, max_contours)
         return (out, edges, thr) if (want_edges or want_thresholds) else out
+
+    @staticmethod
+    def _split_edges(flat, hw):
+        """The flat edge buffer of a mixed-size call -> one [h, w] view per image."""
+        ends = np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])
+        return [flat[e - h * w:e].reshape(h, w) for e, (h, w) in zip(ends.tolist(), hw.tolist())]
+
+    def leading_lines_mixed(self, images, order='bgr', canny_low=50, canny_high=150, threshold=80, min_line_length=None, max_line_gap=20,
+                            max_lines=2048, want_edges=False):
+        """leading_lines for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for
+        resident images at any byte alignment. order 'bgr' / 'rgb' (or FE_ORDER_*): the byte order of a pixel. min_line_length: one
+        value, one per image, or None = int(min(h, w) * 0.15) of each image. -> list of int32 [k,4] segment arrays in input order and, with
+        want_edges, the list of uint8 [h,w] edge images; each equal to leading_lines's for that image alone. fe_leading_lines_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        if min_line_length is None:
+            min_len = np.array([int(min(h, w) * 0.15) for h, w in hw.tolist()], np.int32)
+        else:
+            min_len = np.ascontiguousarray(np.broadcast_to(np.asarray(min_line_length, np.int32), (max(n, 0),)))
+        flat = np.empty(int((hw[:, 0].astype(np.int64) * hw[:, 1]).clip(0).sum()) if n > 0 else 0, np.uint8) if want_edges else None
+        while True:
+            lines = np.zeros((max(n, 0), max_lines, 4), np.int32)
+            counts = np.zeros(max(n, 0), np.int32)
+            self._ck(self.lib.fe_leading_lines_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), canny_low,
+                                                     canny_high, threshold, min_len.ctypes.data_as(C.c_void_p), max_line_gap, max_lines,
+                                                     lines.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                     flat.ctypes.data_as(C.c_void_p) if want_edges else None))
+            if int(counts.max()) <= max_lines:
+                break
+            max_lines = int(counts.max())          # rare: more segments than room - run again with enough
+        out = [lines[i, :counts[i]].copy() for i in range(n)]
+        return (out, self._split_edges(flat, hw)) if want_edges else out
+
+    def lines_host_ms(self):
+        """Milliseconds the host stage (hysteresis + Hough) of this context's last leading_lines / leading_lines_mixed call took."""
+        v = C.c_double(0.0)
+        self._ck(self.lib.fe_lines_host_ms(self.h, C.byref(v)))
+        return v.value
+
+    def subject_contours_mixed(self, images, order='bgr', max_contours=256, want_edges=False, want_thresholds=False):
+        """subject_contours for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for
+        resident images at any byte alignment; order as above. -> list of int64 [k,8] record arrays in input order; with want_edges /
+        want_thresholds (records, list of uint8 [h,w] edge images | None, thresholds int32 [n,2] | None). Every record, byte and threshold
+        equals subject_contours's for that image alone; runs again with more room when an image has more than max_contours.
+        fe_subject_region_mixed."""
+        ptrs, hw, n, dev, keep = self._img_list(images)
+        flat = np.empty(int((hw[:, 0].astype(np.int64) * hw[:, 1]).clip(0).sum()) if n > 0 else 0, np.uint8) if want_edges else None
+        thr = np.zeros((max(n, 0), 2), np.int32) if want_thresholds else None
+        out = self._contour_call(lambda room, rec, cnt: self.lib.fe_subject_region_mixed(
+            self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), room, rec, cnt,
+            thr.ctypes.data_as(C.c_void_p) if want_thresholds else None, flat.ctypes.data_as(C.c_void_p) if want_edges else None), max(n, 0), max_contours)
+        return (out, self._split_edges(flat, hw) if want_edges else None, thr) if (want_edges or want_thresholds) else out
 
     def phash(self, images, bgr=False, want_small=False, want_dct=False):
         """uint8 [n,h,w,3] (or device tuple), RGB or (bgr=True) BGR bytes -> uint64 [n]: imagehash.phash(pil_img) of every image as

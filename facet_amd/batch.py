@@ -29,9 +29,10 @@ statistics of all of it with ONE fe_image_stats_mixed call on the RGB pixels. Wi
 from ONE fe_thumbnail_jpeg_mixed call and, with `phash=True` as well, its hashes from ONE fe_phash_mixed call, both on the RGB pixels and
 both without a per-size table left in the context. With a face analyzer the face dicts of the whole chunk come from ONE
 fe_face_analyze_mixed call, ONE fe_roi_laplacian_mixed call and (with `gpu_thumbnails=True`) ONE fe_face_thumbnails_mixed call, again on the
-RGB pixels: every face graph runs over full micro-batches whatever the shapes. Lines and the subject region still run per shape group on
-a BGR copy of the resident pixels (made only when one of them is on - or pHash without thumbnails, which keeps its per-group fe_phash),
-and the dicts come back in input order with the same keys and values.
+RGB pixels: every face graph runs over full micro-batches whatever the shapes. With `detect_lines=True` the line scores of the whole chunk
+come from ONE fe_leading_lines_mixed call and with `subject_region=True` its subject boxes from ONE fe_subject_region_mixed call, both on
+the RGB pixels. No stage of a mixed chunk asks for a BGR copy of the resident pixels any more, except pHash without thumbnails, which
+keeps its per-group fe_phash on one; the dicts come back in input order with the same keys and values.
 
 Overlap: a context runs one call at a time (one arena, one stream), and the face / statistics / leading-lines calls spend most of
 their time in host glue (NMS, similarity transforms, Hough votes, percentile arithmetic) with the GPU idle. Give the scorer a second
@@ -108,7 +109,7 @@ class BatchScorer:
         self.mono_threshold, self.shadow_threshold, self.highlight_threshold = mono_threshold, shadow_threshold, highlight_threshold
 
     def process_batch(self, images_rgb, exif=None, leading_lines=None, _resident=None, _records=None, _borrowed=False, _tech=None, _hashes=None,
-                      _thumbs=None, _faces=None):
+                      _thumbs=None, _faces=None, _subjects=None):
         """images_rgb: uint8 [n,h,w,3] (the PIL images of a batch as one array). Returns one dict per image. exif: optional list
         of per-image dicts (iso / f_stop / shutter_speed / focal_length) and leading_lines: optional per-image
         leading_lines_score, both only used by the aggregate step (policy given).
@@ -121,7 +122,9 @@ class BatchScorer:
         _hashes / _thumbs (the mixed-size path): the phash strings / thumbnail bytes of these images (fe_phash_mixed, fe_thumbnail_jpeg_mixed),
         computed by the caller - that stage is skipped and asks for no BGR copy.
         _faces (the mixed-size path): the face dicts of these images (FaceAnalyzer.analyze_faces_mixed), computed by the caller - the face
-        calls are skipped, ask for no BGR copy and for no host pixels."""
+        calls are skipped, ask for no BGR copy and for no host pixels.
+        _subjects (the mixed-size path): the subject boxes of these images (CompositionAnalyzer.detect_subject_region_mixed), computed by
+        the caller - fe_subject_region is skipped and asks for no BGR copy. (The line scores of that path come in through leading_lines.)"""
         e = self.engine
         if _resident is None:
             imgs = np.ascontiguousarray(images_rgb, dtype=np.uint8)
@@ -142,7 +145,7 @@ class BatchScorer:
             faces_on = self.face_analyzer is not None and self.face_analyzer.available
             bgr_dev = None
             if _tech is None or (faces_on and _faces is None) or (leading_lines is None and self.detect_lines) or (self.phash and _hashes is None) or \
-                    (self.thumbnails and _thumbs is None) or self.subject_region:
+                    (self.thumbnails and _thumbs is None) or (self.subject_region and _subjects is None):
                 d_bgr = e.dev_alloc(n * h * w * 3)
                 e.swap_rb(d_rgb, n * h * w, d_bgr)
                 bgr_dev = (d_bgr, n, h, w)
@@ -168,8 +171,8 @@ class BatchScorer:
                 if self.thumbnails and thumbs_ is None:
                     from .thumbnail import thumbnails
                     thumbs_ = thumbnails(eng, bgr_dev, self.thumbnail_size, self.thumbnail_quality, bgr=True)
-                subjects_ = None
-                if self.subject_region:
+                subjects_ = _subjects
+                if self.subject_region and subjects_ is None:
                     from .composition import CompositionAnalyzer
                     subjects_ = CompositionAnalyzer.detect_subject_region_batch(eng, bgr_dev)
                 return tech_, faces_, lines_, hashes_, thumbs_, subjects_
@@ -324,7 +327,7 @@ class BatchScorer:
         fa = self.face_analyzer if (self.face_analyzer is not None and self.face_analyzer.available) else None
         host_bgr = None      # the chunk's host pixels as B,G,R views in input order, fetched below only when Pillow cuts the face thumbnails
 
-        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels; then the faces and the index columns
+        def stats(eng):      # one fe_image_stats_mixed over the whole chunk, straight from the RGB pixels; then the faces, the index columns, lines and subject boxes
             tech_ = TechnicalAnalyzer.analyze_mixed(eng, resident, self.shadow_threshold, self.highlight_threshold, self.mono_threshold, order='rgb')
             # the face dicts of the whole chunk (the analyzer holds its own context: the aux engine when there is one), R,G,B read in place
             faces_ = fa.analyze_faces_mixed(host_bgr, resident=resident, order='rgb') if fa is not None else None
@@ -338,7 +341,17 @@ class BatchScorer:
                 if self.phash:
                     from .phash import phash_mixed, to_hex
                     hashes_ = to_hex(phash_mixed(eng, resident, order='rgb'))
-            return tech_, hashes_, thumbs_, faces_
+            # Composition: one fe_leading_lines_mixed (unless the caller passed scores in) and one fe_subject_region_mixed over the whole
+            # chunk, R,G,B read in place, so neither asks process_batch for a BGR copy
+            lines_, subjects_ = leading_lines, None
+            if self.detect_lines and lines_ is None:
+                from .composition import CompositionAnalyzer
+                lines_ = [d['leading_lines_score'] for d in CompositionAnalyzer.detect_leading_lines_mixed(eng, resident, order='rgb')]
+                lines_ = dict(zip(sorted(order), lines_))      # by the caller's index, as leading_lines= is
+            if self.subject_region:
+                from .composition import CompositionAnalyzer
+                subjects_ = CompositionAnalyzer.detect_subject_region_mixed(eng, resident, order='rgb')
+            return tech_, hashes_, thumbs_, faces_, lines_, subjects_
 
         try:
             if fa is not None and not getattr(fa, 'gpu_thumbnails', False):
@@ -354,10 +367,10 @@ class BatchScorer:
                 try:
                     rec, mask = e.ensemble_score_mixed(resident)
                 finally:
-                    tech, hashes, thumbs, faces = fut.result()      # also on error: the worker must be done before the buffers go
+                    tech, hashes, thumbs, faces, leading_lines, subjects = fut.result()      # also on error: the worker must be done before the buffers go
             else:
                 rec, mask = e.ensemble_score_mixed(resident)
-                tech, hashes, thumbs, faces = stats(e)
+                tech, hashes, thumbs, faces, leading_lines, subjects = stats(e)
         except Exception:
             for _, dev, owned in entries:
                 if owned:
@@ -371,7 +384,8 @@ class BatchScorer:
                                          _records=(rec[[row[i] for i in idx]], mask), _borrowed=not owned, _tech=[tech[row[i]] for i in idx],
                                          _hashes=[hashes[row[i]] for i in idx] if hashes is not None else None,
                                          _thumbs=[thumbs[row[i]] for i in idx] if thumbs is not None else None,
-                                         _faces=[faces[row[i]] for i in idx] if faces is not None else None)
+                                         _faces=[faces[row[i]] for i in idx] if faces is not None else None,
+                                         _subjects=[subjects[row[i]] for i in idx] if subjects is not None else None)
             except Exception:
                 for _, dev2, owned2 in entries[n_done + 1:]:
                     if owned2:

@@ -5,6 +5,8 @@
     CompositionAnalyzer.detect_subject_region_batch(engine, bgr_batch) the same for a whole batch in one engine call
     CompositionAnalyzer.detect_leading_lines(img_cv, cache=None)      :191-261 - one image
     CompositionAnalyzer.detect_leading_lines_batch(engine, bgr_batch) the same for a whole batch in one engine call
+    CompositionAnalyzer.detect_subject_region_mixed / detect_leading_lines_mixed(engine, images, order=)
+                                                                      the same for a list of images of any sizes, one engine call each
     CompositionAnalyzer.integrate_leading_lines(base, lines, faces)   :262-283
 
 The reference runs cv2.GaussianBlur + cv2.Canny + cv2.HoughLinesP per image; here `fe_leading_lines` does the pixel scans on
@@ -75,6 +77,21 @@ class CompositionAnalyzer:
             bgr_batch = np.ascontiguousarray(bgr_batch, dtype=np.uint8)
             h, w = bgr_batch.shape[1:3]
         return [subject_box(r, h, w) for r in engine.subject_contours(bgr_batch)]
+
+    @staticmethod
+    def _sizes(images):
+        return [tuple(s) for s in images[1]] if isinstance(images, tuple) else [np.shape(a)[:2] for a in images]
+
+    @staticmethod
+    def detect_subject_region_mixed(engine, images, order='bgr'):
+        """images: a list of uint8 [h,w,3] arrays of any sizes, or resident (device_pointers, sizes) -> one [x1, y1, x2, y2] or None per
+        image, from one engine call (fe_subject_region_mixed)."""
+        return [subject_box(r, h, w) for r, (h, w) in zip(engine.subject_contours_mixed(images, order=order), CompositionAnalyzer._sizes(images))]
+
+    @staticmethod
+    def detect_leading_lines_mixed(engine, images, order='bgr'):
+        """images as above -> one {'leading_lines_score', 'line_count'} per image, from one engine call (fe_leading_lines_mixed)."""
+        return [score_lines(l, h, w) for l, (h, w) in zip(engine.leading_lines_mixed(images, order=order), CompositionAnalyzer._sizes(images))]
 
     @staticmethod
     def detect_subject_region(img_cv, engine=None):

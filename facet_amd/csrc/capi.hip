@@ -65,6 +65,7 @@ void fe_destroy(fe_ctx* ctx) {
     if (e) (void)hipEventDestroy(e);
   ctx->side.arena.release();
   for (void* q : ctx->misc_allocs) (void)hipFree(q);
+  if (ctx->lines_maps) (void)hipHostFree(ctx->lines_maps);
   if (ctx->clip_in) (void)hipFree(ctx->clip_in);
   if (ctx->samp_in) (void)hipFree(ctx->samp_in);
   delete ctx;

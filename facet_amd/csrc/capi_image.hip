@@ -4,6 +4,7 @@
 #include "lines_host.h"
 #include "phash_mixed_plan.h"
 #include "thumb_mixed_core.h"
+#include <chrono>
 #include <thread>
 
 namespace {
@@ -229,6 +230,55 @@ int contour_microbatch(fe_ctx* ctx, int n, size_t per_image) {
   const size_t room = ctx->c.arena.capacity() / 8 * 7;
   FE_CHECK(per_image + 4096 <= room, "contours: one image needs %zu bytes of workspace, the arena holds %zu", per_image, ctx->c.arena.capacity());
   return (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)64, room / (per_image + 4096)}));
+}
+
+// ---- what fe_leading_lines_mixed and fe_subject_region_mixed share ------------------------------------------------------------------
+// the list checks of the mixed-size calls, and the per-shape calls' own bound on an image: h * w below 2^30
+bool composition_list_ok(Ctx& C, const char* who, const uint8_t* const* images, const int32_t* hw, int n, int order) {
+  if (!mixed_list_ok(C, who, images, hw, n, order, images, INT32_MAX, INT32_MAX, false)) return false;
+  for (int i = 0; i < n; ++i)
+    if ((size_t)hw[2 * i] * (size_t)hw[2 * i + 1] >= ((size_t)1 << 30)) {
+      char b[200];
+      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h * w must stay below 2^30", who, i, hw[2 * i], hw[2 * i + 1]);
+      C.err = b;
+      return false;
+    }
+  return true;
+}
+// the plan of the list, or the capacity error that names the image whose own scratch exceeds the arena
+comp_plan::Plan composition_plan(Ctx& C, const char* who, const int32_t* hw, int n, int on_device, bool subject,
+                                 size_t max_chunk_pixels = comp_plan::kMaxChunkPixels) {
+  comp_plan::Plan plan = comp_plan::build(hw, n, !on_device, subject, C.arena.capacity(), max_chunk_pixels);
+  if (plan.bad_image >= 0) {
+    char b[240];
+    const int i = plan.bad_image;
+    snprintf(b, sizeof b, "%s: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", who, i, hw[2 * i], hw[2 * i + 1], plan.bad_bytes,
+             C.arena.capacity());
+    throw CapacityError(b);
+  }
+  return plan;
+}
+// A chunk's allocation with its blob (descriptors with their pointers, prefix tables) uploaded; host images are staged back to back.
+// `blob` must outlive the copy: the caller keeps it until it has synchronised.
+uint8_t* composition_stage_chunk(Ctx& C, const comp_plan::Chunk& ck, const uint8_t* const* images, int on_device, std::vector<uint8_t>& blob) {
+  const comp_plan::Layout& L = ck.lay;
+  C.arena.reset();
+  uint8_t* base = (uint8_t*)C.arena.alloc(L.total);
+  blob.assign(L.blob_bytes, 0);
+  comp_plan::ImageDesc* im = (comp_plan::ImageDesc*)blob.data();
+  for (int k = 0; k < ck.count; ++k) {
+    im[k] = ck.descs[k];
+    im[k].src = images[ck.first + k];
+    if (!on_device) {
+      uint8_t* d = base + L.stage + (size_t)im[k].px * 3;
+      FE_HIP(hipMemcpyAsync(d, im[k].src, (size_t)im[k].h * im[k].w * 3, hipMemcpyHostToDevice, C.stream));
+      im[k].src = d;
+    }
+  }
+  for (int t = 0; t < comp_plan::kTilings; ++t)
+    memcpy(blob.data() + L.blob_prefix + (size_t)t * (ck.count + 1) * sizeof(int32_t), ck.prefix[t].data(), (size_t)(ck.count + 1) * sizeof(int32_t));
+  FE_HIP(hipMemcpyAsync(base + L.blob, blob.data(), L.blob_bytes, hipMemcpyHostToDevice, C.stream));
+  return base;
 }
 }  // namespace
 
@@ -610,6 +660,7 @@ int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int o
     const int threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::vector<uint8_t> scratch;
     if (!edges_out) scratch.resize((size_t)mb * npx);
+    ctx->lines_host_ms = 0.0;
     ImageStager st(ctx, bgr, n, per, mb, on_device);
     for (int k = 0; k < st.chunks(); ++k) {
       const int i0 = k * mb, nb = st.count(k);
@@ -624,9 +675,135 @@ int fe_leading_lines(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int o
       uint8_t* maps = edges_out ? edges_out + (size_t)i0 * npx : scratch.data();
       FE_HIP(hipMemcpyAsync(maps, d_map, (size_t)nb * npx, hipMemcpyDeviceToHost, C.stream));
       FE_HIP(hipStreamSynchronize(C.stream));
+      const auto t0 = std::chrono::steady_clock::now();
       lines_host_stage(maps, nb, h, w, threshold, min_line_length, max_line_gap, max_lines, lines ? lines + (size_t)i0 * max_lines * 4 : nullptr,
                        counts ? counts + i0 : nullptr, threads);
+      ctx->lines_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+  });
+}
+
+/* fe_leading_lines for a list of images of any sizes: three launches and one map copy per arena chunk, the host stage over the chunk */
+int fe_leading_lines_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int canny_low, int canny_high,
+                           int threshold, const int32_t* min_line_length, int max_line_gap, int max_lines, int* lines, int* counts, uint8_t* edges_out) {
+  return fe_api(ctx, OnError::Capacity, [&]() -> int {
+    Ctx& C = ctx->c;
+    char b[240];
+    if (!composition_list_ok(C, "fe_leading_lines_mixed", images, hw, n, order)) return FE_ERR_INVALID;
+    const char* why = nullptr;
+    if ((lines != nullptr) != (counts != nullptr) || !(lines || edges_out)) why = "pass lines AND counts, and / or edges_out";
+    else if (lines && max_lines <= 0) why = "max_lines must be positive";
+    else if (lines && !min_line_length) why = "min_line_length is a null pointer";
+    else if (canny_low < 0 || canny_high < canny_low || threshold <= 0 || max_line_gap < 0) why = "bad thresholds";
+    if (why) { snprintf(b, sizeof b, "fe_leading_lines_mixed: %s", why); C.err = b; return FE_ERR_INVALID; }
+    for (int i = 0; lines && i < n; ++i)
+      if (min_line_length[i] < 0) {
+        snprintf(b, sizeof b, "fe_leading_lines_mixed: image %d: min_line_length %d is negative", i, min_line_length[i]);
+        C.err = b;
+        return FE_ERR_INVALID;
+      }
+    // Without edges_out the maps of a chunk come down into a pinned buffer the context keeps (a fresh pageable one costs more than
+    // the kernels: page faults, and a copy at a fraction of the link's rate), so a chunk of several images holds at most 2^28 pixels
+    constexpr size_t kHostMapPixels = (size_t)1 << 28;
+    const comp_plan::Plan plan = composition_plan(C, "fe_leading_lines_mixed", hw, n, on_device, false, kHostMapPixels);
+    const int threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<uint8_t> blob;
+    std::vector<size_t> offsets;
+    std::vector<int32_t> no_len;
+    size_t first_px = 0;      // of the chunk, in the caller's flat edge buffer
+    ctx->lines_host_ms = 0.0;
+    for (const comp_plan::Chunk& ck : plan.chunks) {
+      uint8_t* base = composition_stage_chunk(C, ck, images, on_device, blob);
+      launch_canny_map_mixed(base, ck, order == FE_ORDER_RGB, canny_low, canny_high, C.stream);
+      if (!edges_out && ctx->lines_maps_cap < ck.pixels) {
+        if (ctx->lines_maps) (void)hipHostFree(ctx->lines_maps);
+        ctx->lines_maps = nullptr; ctx->lines_maps_cap = 0;
+        FE_HIP(hipHostMalloc((void**)&ctx->lines_maps, ck.pixels, hipHostMallocDefault));
+        ctx->lines_maps_cap = ck.pixels;
+      }
+      uint8_t* maps = edges_out ? edges_out + first_px : ctx->lines_maps;
+      FE_HIP(hipMemcpyAsync(maps, base + ck.lay.map, ck.pixels, hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));   // the arena and the blob are recycled by the next chunk
+      offsets.resize(ck.count);
+      for (int k = 0; k < ck.count; ++k) offsets[k] = ck.descs[k].px;
+      if (!lines) no_len.assign(ck.count, 0);
+      const auto t0 = std::chrono::steady_clock::now();
+      lines_host_stage_mixed(maps, offsets.data(), hw + 2 * (size_t)ck.first, ck.count, threshold, lines ? min_line_length + ck.first : no_len.data(),
+                             max_line_gap, max_lines, lines ? lines + (size_t)ck.first * max_lines * 4 : nullptr, counts ? counts + ck.first : nullptr,
+                             threads);
+      ctx->lines_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      first_px += ck.pixels;
+    }
+    return FE_OK;
+  });
+}
+
+/* how long the host stage (hysteresis and Hough, all chunks) of the context's last fe_leading_lines / fe_leading_lines_mixed call took */
+int fe_lines_host_ms(fe_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return FE_ERR_INVALID;
+  *ms = ctx->lines_host_ms;
+  return FE_OK;
+}
+
+/* fe_subject_region for a list of images of any sizes: one memset, a fixed number of launches and two read-backs per arena chunk */
+int fe_subject_region_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int max_contours,
+                            long long* records, int* counts, int* thresholds, uint8_t* edges_out) {
+  return fe_api(ctx, OnError::Capacity, [&]() -> int {
+    Ctx& C = ctx->c;
+    if (!composition_list_ok(C, "fe_subject_region_mixed", (records && counts) ? images : nullptr, hw, n, order)) return FE_ERR_INVALID;
+    if (max_contours <= 0) { C.err = "fe_subject_region_mixed: max_contours must be positive"; return FE_ERR_INVALID; }
+    const comp_plan::Plan plan = composition_plan(C, "fe_subject_region_mixed", hw, n, on_device, true);
+    struct Rec { long long f[FE_CONTOUR_RECORD]; };
+    std::vector<uint8_t> blob;
+    std::vector<int> ctr;
+    std::vector<Rec> got;
+    std::vector<size_t> at;
+    size_t first_px = 0;
+    for (const comp_plan::Chunk& ck : plan.chunks) {
+      const comp_plan::Layout& L = ck.lay;
+      const int nb = ck.count;
+      uint8_t* base = composition_stage_chunk(C, ck, images, on_device, blob);
+      launch_subject_mixed(base, ck, order == FE_ORDER_RGB, C.stream);
+      if (thresholds) FE_HIP(hipMemcpyAsync(thresholds + 2 * (size_t)ck.first, base + L.thr, (size_t)nb * 2 * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+      if (edges_out) FE_HIP(hipMemcpyAsync(edges_out + first_px, base + L.edge, ck.pixels, hipMemcpyDeviceToHost, C.stream));
+      // one copy of the counters (listed [nb], found [nb], error, stored), then one of the chunk's records
+      ctr.resize(comp_plan::counter_ints(nb));
+      FE_HIP(hipMemcpyAsync(ctr.data(), base + L.counters, ctr.size() * sizeof(int), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));
+      const int *listed = ctr.data(), *found = listed + nb, err = found[nb], stored = found[nb + 1];
+      FE_CHECK(!(err & 1), "contours: a border walk did not close within 8 * pixels + 8 steps");
+      FE_CHECK(!(err & 2), "contours: more component roots than an image can hold");
+      size_t total = 0;
+      at.assign((size_t)nb + 1, 0);
+      for (int k = 0; k < nb; ++k) {
+        FE_CHECK(found[k] >= 0 && found[k] <= listed[k] && listed[k] <= ck.descs[k].cap, "contours: inconsistent counts of image %d (%d of %d, room %d)",
+                 ck.first + k, found[k], listed[k], ck.descs[k].cap);
+        counts[ck.first + k] = found[k];
+        total += (size_t)found[k];
+        at[k + 1] = total;
+      }
+      FE_CHECK((size_t)stored == total, "contours: %d records stored, %zu counted", stored, total);
+      got.resize(total);
+      if (total) FE_HIP(hipMemcpyAsync(got.data(), base + L.recs, total * sizeof(Rec), hipMemcpyDeviceToHost, C.stream));
+      FE_HIP(hipStreamSynchronize(C.stream));   // the arena and the blob are recycled by the next chunk
+      // the list is in the order the walks finished: by image, and in descending start_index order within one, as collect_contours leaves them
+      std::sort(got.begin(), got.end(), [](const Rec& a, const Rec& b) {
+        const long long ia = a.f[0] >> 32, ib = b.f[0] >> 32;
+        return ia != ib ? ia < ib : a.f[0] > b.f[0];
+      });
+      for (int k = 0; k < nb; ++k) {
+        const size_t keep = (size_t)std::min(found[k], max_contours);
+        Rec* out = reinterpret_cast<Rec*>(records + (size_t)(ck.first + k) * max_contours * FE_CONTOUR_RECORD);
+        for (size_t q = 0; q < keep; ++q) {
+          const Rec& r = got[at[k] + q];
+          FE_CHECK((r.f[0] >> 32) == k, "contours: a record of image %d where image %d's were counted", (int)(r.f[0] >> 32) + ck.first, ck.first + k);
+          out[q] = r;
+          out[q].f[0] = r.f[0] & 0xffffffffll;
+        }
+      }
+      first_px += ck.pixels;
+    }
+    return FE_OK;
   });
 }
 

@@ -30,6 +30,8 @@ struct fe_ctx {
   // capi_image.hip
   int* hsv_sdiv = nullptr; int* hsv_hdiv = nullptr;   // cv2 HSV division tables
   double* phash_cos = nullptr;                        // DCT-II cosine table of fe_phash
+  uint8_t* lines_maps = nullptr; size_t lines_maps_cap = 0;   // fe_leading_lines_mixed: pinned host buffer of a chunk's maps (grow-only, at most 256 MiB)
+  double lines_host_ms = 0.0;                         // fe_lines_host_ms: what the host stage of the last leading-lines call took
   int stats_segment = 0;                              // fe_set_stats_segment: pixels per pass-1 segment of fe_image_stats_mixed, 0 = default
   std::vector<void*> misc_allocs;                     // these tables and capi_face.hip's, for fe_destroy
   // capi_models.hip

@@ -6,6 +6,7 @@
 #include "erf_core.h"
 #include "stats_plan.h"
 #include "face_mixed_plan.h"
+#include "composition_mixed_plan.h"
 #include <cstdint>
 #include <cstdio>
 #include <atomic>
@@ -537,5 +538,9 @@ void launch_median_thresholds(const double* d_stats, int n, long long npx, int* 
 // sc.edge receives it; candidates = 0: d_img is a binary image (nonzero = foreground) that is used as it is.
 void launch_external_contours(const uint8_t* d_img, int nb, int h, int w, int candidates, long long min_twice_area, ContourScratch& sc,
                               hipStream_t s);
+// kernels_composition_mixed.hip: one chunk of the mixed-size lines / subject calls (composition_mixed_plan.h has the plan). base: the
+// chunk's allocation, its blob already in place.
+void launch_canny_map_mixed(uint8_t* base, const comp_plan::Chunk& ck, int rgb, int low, int high, hipStream_t s);
+void launch_subject_mixed(uint8_t* base, const comp_plan::Chunk& ck, int rgb, hipStream_t s);
 
 }  // namespace fe

@@ -10,120 +10,44 @@
 //                         image or in a 4-connected background region that reaches the frame; plus the bounding-box area bound
 //   contour_walk_kernel   one lane per remaining component follows its outer border (contour_core.h) and sums a00, a10, a01
 // [DEP-KNOWLEDGE] OpenCV is not available offline: these restate its documented algorithms; parity with cv2 is unpinned.
-#include "contour_core.h"
+#include "composition_core.h"
 #include "fe_common.h"
 
 namespace fe {
 
 namespace {
 
-constexpr int CT = 16;                                 // tile edge: 256 threads, 1 KB of LDS
-enum { SET_CAND = 0, SET_FG = 1, SET_BG = 2 };         // which pixels are labelled: Canny candidates (!= 1), nonzero, zero
-
-__device__ __forceinline__ bool in_set(int v, int mode) { return mode == SET_CAND ? v != 1 : (mode == SET_FG ? v != 0 : v == 0); }
-__device__ __forceinline__ int ld(const int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ int find_root(const int* L, int i) {
-  int p;
-  while ((p = ld(L + i)) != i) i = p;                  // parents only ever decrease: the chain ends at a root
-  return i;
-}
-// lock-free union, the larger root under the smaller one. When another thread re-parented `a` in between, what is left to join is
-// a's previous parent and b.
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-  for (;;) {
-    a = find_root(L, a);
-    b = find_root(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(L + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// the per-pixel and per-tile bodies are composition_core.h's, shared with the mixed-size kernels (kernels_composition_mixed.hip)
 __global__ __launch_bounds__(CT * CT) void ccl_local_kernel(const uint8_t* __restrict__ img, int h, int w, int mode, int conn8,
                                                             int* __restrict__ labels) {
   __shared__ int L[CT * CT];
-  const int tx = threadIdx.x, ty = threadIdx.y, lid = ty * CT + tx;
-  const int x = blockIdx.x * CT + tx, y = blockIdx.y * CT + ty;
   const size_t base = (size_t)blockIdx.z * h * w;
-  const bool inside = x < w && y < h;
-  const bool s = inside && in_set(img[base + (size_t)y * w + x], mode);
-  L[lid] = s ? lid : -1;
-  __syncthreads();
-  if (s) {                                             // the neighbours that come before this pixel in raster order, inside the tile
-    if (tx > 0 && ld(L + lid - 1) >= 0) unite(L, lid, lid - 1);
-    if (ty > 0) {
-      if (ld(L + lid - CT) >= 0) unite(L, lid, lid - CT);
-      if (conn8) {
-        if (tx > 0 && ld(L + lid - CT - 1) >= 0) unite(L, lid, lid - CT - 1);
-        if (tx < CT - 1 && ld(L + lid - CT + 1) >= 0) unite(L, lid, lid - CT + 1);
-      }
-    }
-  }
-  __syncthreads();
-  if (!inside) return;
-  int out = -1;
-  if (s) {                                             // tile order is raster order: the smallest local index is the smallest global one
-    const int r = find_root(L, lid);
-    out = (blockIdx.y * CT + r / CT) * w + blockIdx.x * CT + r % CT;
-  }
-  labels[base + (size_t)y * w + x] = out;
+  ccl_local_tile(img + base, h, w, mode, conn8, blockIdx.x, blockIdx.y, labels + base, L);
 }
 
 __global__ __launch_bounds__(CT * CT) void ccl_seam_kernel(int h, int w, int conn8, int* __restrict__ labels) {
-  const int tx = threadIdx.x, ty = threadIdx.y;
-  const int x = blockIdx.x * CT + tx, y = blockIdx.y * CT + ty;
-  if (x >= w || y >= h) return;
-  int* L = labels + (size_t)blockIdx.z * h * w;
-  const int p = y * w + x;
-  if (ld(L + p) < 0) return;
-  if (tx == 0 && x > 0 && ld(L + p - 1) >= 0) unite(L, p, p - 1);
-  if (y > 0) {
-    if (ty == 0 && ld(L + p - w) >= 0) unite(L, p, p - w);
-    if (conn8) {
-      if ((tx == 0 || ty == 0) && x > 0 && ld(L + p - w - 1) >= 0) unite(L, p, p - w - 1);
-      if ((tx == CT - 1 || ty == 0) && x + 1 < w && ld(L + p - w + 1) >= 0) unite(L, p, p - w + 1);
-    }
-  }
+  ccl_seam_px(h, w, conn8, blockIdx.x, blockIdx.y, labels + (size_t)blockIdx.z * h * w);
 }
 
 __global__ __launch_bounds__(CT * CT) void ccl_flatten_fg_kernel(const uint8_t* __restrict__ img, int h, int w, int mode, int* __restrict__ labels,
                                                                  int* __restrict__ cnt, int* __restrict__ strong, int* __restrict__ xmin,
                                                                  int* __restrict__ xmax, int* __restrict__ ymax) {
   const int x = blockIdx.x * CT + threadIdx.x, y = blockIdx.y * CT + threadIdx.y;
-  if (x >= w || y >= h) return;
   const size_t base = (size_t)blockIdx.z * h * w;
-  int* L = labels + base;
-  const int p = y * w + x;
-  if (ld(L + p) < 0) return;
-  const int r = find_root(L, p);
-  __atomic_store_n(L + p, r, __ATOMIC_RELAXED);        // a reader that still sees the old parent reaches the same root
-  atomicAdd(cnt + base + r, 1);
-  atomicMin(xmin + base + r, x);
-  atomicMax(xmax + base + r, x);
-  atomicMax(ymax + base + r, y);
-  if (mode == SET_FG ? p == r : img[base + p] == 2) __atomic_store_n(strong + base + r, 1, __ATOMIC_RELAXED);
+  ccl_flatten_fg_px(img + base, h, w, mode, x, y, labels + base, cnt + base, strong + base, xmin + base, xmax + base, ymax + base);
 }
 
 __global__ __launch_bounds__(CT * CT) void ccl_flatten_bg_kernel(int h, int w, int* __restrict__ labels, uint8_t* __restrict__ outer) {
   const int x = blockIdx.x * CT + threadIdx.x, y = blockIdx.y * CT + threadIdx.y;
-  if (x >= w || y >= h) return;
   const size_t base = (size_t)blockIdx.z * h * w;
-  int* L = labels + base;
-  const int p = y * w + x;
-  if (ld(L + p) < 0) return;
-  const int r = find_root(L, p);
-  __atomic_store_n(L + p, r, __ATOMIC_RELAXED);
-  if (x == 0 || y == 0 || x == w - 1 || y == h - 1) outer[base + r] = 1;      // every writer stores the same byte
+  ccl_flatten_bg_px(h, w, x, y, labels + base, outer + base);
 }
 
 __global__ void contour_edge_kernel(const int* __restrict__ labels, const int* __restrict__ strong, size_t npx, uint8_t* __restrict__ edge) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npx) return;
   const size_t base = (size_t)blockIdx.y * npx;
-  const int l = labels[base + p];
-  edge[base + p] = (l >= 0 && strong[base + l]) ? 255 : 0;
+  edge[base + p] = contour_edge_px(labels + base, strong + base, p);
 }
 
 __global__ __launch_bounds__(CT * CT) void contour_candidates_kernel(int h, int w, long long min_twice_area, const int* __restrict__ lab_fg,
@@ -133,23 +57,10 @@ __global__ __launch_bounds__(CT * CT) void contour_candidates_kernel(int h, int 
                                                                      int* __restrict__ work, int* __restrict__ work_count, int work_cap,
                                                                      int* __restrict__ error) {
   const int x = blockIdx.x * CT + threadIdx.x, y = blockIdx.y * CT + threadIdx.y;
-  if (x >= w || y >= h) return;
   const int img = blockIdx.z;
   const size_t base = (size_t)img * h * w;
-  const int p = y * w + x;
-  if (lab_fg[base + p] != p || !strong[base + p]) return;      // roots of kept components only
-  bool external = x == 0;
-  if (!external) {
-    const int lb = lab_bg[base + p - 1];                        // the left neighbour of a first raster pixel is background
-    external = lb >= 0 && outer[base + lb];
-  }
-  if (!external) return;
-  // |a00| of a polygon is at most twice the area of its bounding rectangle through the pixel centres
-  const long long bw = xmax[base + p] - xmin[base + p], bh = ymax[base + p] - y;
-  if (2 * bw * bh < min_twice_area) return;
-  const int slot = atomicAdd(work_count + img, 1);
-  if (slot < work_cap) work[(size_t)img * work_cap + slot] = p;
-  else atomicOr(error, 2);
+  contour_candidate_px(h, w, x, y, min_twice_area, lab_fg + base, lab_bg + base, strong + base, xmin + base, xmax + base, ymax + base, outer + base,
+                       work + (size_t)img * work_cap, work_count + img, work_cap, error);
 }
 
 __global__ __launch_bounds__(64) void contour_walk_kernel(const uint8_t* __restrict__ fgimg, int h, int w, long long min_twice_area,
@@ -161,40 +72,20 @@ __global__ __launch_bounds__(64) void contour_walk_kernel(const uint8_t* __restr
   const int nwork = min(work_count[img], work_cap);
   if (j >= nwork) return;
   const size_t base = (size_t)img * h * w;
-  const uint8_t* im = fgimg + base;
-  const int p = work[(size_t)img * work_cap + j];
-  const int x0 = p % w, y0 = p / w;
-  auto fg = [&](int x, int y) { return x >= 0 && x < w && y >= 0 && y < h && im[(size_t)y * w + x] != 0; };
-  contour::Sums a;
-  const long long steps = contour::follow_outer(fg, x0, y0, 8ll * cnt[base + p] + 8, &a);
-  if (steps < 0) { atomicOr(error, 1); return; }
-  const long long twice = a.a00 < 0 ? -a.a00 : a.a00;
-  if (twice < min_twice_area) return;
+  long long r[FE_CONTOUR_RECORD];
+  if (!contour_walk_one(fgimg + base, h, w, work[(size_t)img * work_cap + j], min_twice_area, cnt + base, xmin + base, xmax + base, ymax + base,
+                        error, r))
+    return;
   const int slot = atomicAdd(rec_count + img, 1);
   if (slot >= work_cap) return;                                 // counted, not stored
-  long long* r = recs + ((size_t)img * work_cap + slot) * FE_CONTOUR_RECORD;
-  r[0] = p; r[1] = a.a00; r[2] = a.a10; r[3] = a.a01;
-  r[4] = xmin[base + p]; r[5] = y0; r[6] = xmax[base + p]; r[7] = ymax[base + p];
+  long long* o = recs + ((size_t)img * work_cap + slot) * FE_CONTOUR_RECORD;
+  for (int k = 0; k < FE_CONTOUR_RECORD; ++k) o[k] = r[k];
 }
 
-// np.median of the uint8 image from its histogram, kept as twice the median (an even pixel count takes the mean of the two middle values),
-// then lower = int(max(0, 0.5 median)) = m2 / 4 and upper = int(min(255, 1.5 median)) = min(255, 3 m2 / 4)
 __global__ void median_thresholds_kernel(const double* __restrict__ stats, int n, long long npx, int* __restrict__ thr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double* hist = stats + (size_t)i * FE_STATS_COUNT;
-  const long long k_hi = npx / 2, k_lo = (npx & 1) ? k_hi : k_hi - 1;      // 0-based ranks of the middle values
-  long long cum = 0;
-  int v_lo = -1, v_hi = 255;
-  for (int v = 0; v < 256; ++v) {
-    cum += (long long)hist[v];
-    if (v_lo < 0 && cum > k_lo) v_lo = v;
-    if (cum > k_hi) { v_hi = v; break; }
-  }
-  if (v_lo < 0) v_lo = v_hi;
-  const int m2 = v_lo + v_hi;
-  thr[2 * i] = m2 / 4;
-  thr[2 * i + 1] = min(255, 3 * m2 / 4);
+  median_thresholds_of(stats + (size_t)i * FE_STATS_COUNT, npx, thr + 2 * i, thr + 2 * i + 1);
 }
 
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }

@@ -11,58 +11,23 @@
 // progressive probabilistic Hough transform, whose result depends on the order a fixed pseudo-random generator visits the
 // edge points in (vote, extract a segment as soon as a bin reaches the threshold, erase its points and un-vote them).
 // [DEP-KNOWLEDGE] OpenCV is not available offline: these restate its documented algorithms; parity with cv2 is unpinned.
+#include "composition_core.h"
 #include "fe_common.h"
 
 namespace fe {
 
-__device__ __forceinline__ int lines_gray(int b, int g, int r) { return (b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15; }
-__device__ __forceinline__ int lines_refl101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-  return i;
-}
-__device__ __forceinline__ int lines_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-constexpr int LB_W = 32, LB_H = 8;
-
+// the per-pixel and per-tile bodies are composition_core.h's, shared with the mixed-size kernels (kernels_composition_mixed.hip)
 __global__ __launch_bounds__(LB_W * LB_H) void lines_blur_kernel(const uint8_t* __restrict__ bgr, int h, int w, uint8_t* __restrict__ blur) {
   __shared__ int g[LB_H + 4][LB_W + 4];
   const size_t img = blockIdx.z;
-  const uint8_t* src = bgr + img * (size_t)h * w * 3;
-  const int x0 = blockIdx.x * LB_W - 2, y0 = blockIdx.y * LB_H - 2;
-  for (int i = threadIdx.y * LB_W + threadIdx.x; i < (LB_H + 4) * (LB_W + 4); i += LB_W * LB_H) {
-    const int ty = i / (LB_W + 4), tx = i - ty * (LB_W + 4);
-    const int y = lines_refl101(y0 + ty, h), x = lines_refl101(x0 + tx, w);
-    const uint8_t* p = src + ((size_t)y * w + x) * 3;
-    g[ty][tx] = lines_gray(p[0], p[1], p[2]);
-  }
-  __syncthreads();
-  const int x = blockIdx.x * LB_W + threadIdx.x, y = blockIdx.y * LB_H + threadIdx.y;
-  if (x >= w || y >= h) return;
-  const int k[5] = {1, 4, 6, 4, 1};
-  int acc = 0;
-#pragma unroll
-  for (int dy = 0; dy < 5; ++dy) {
-    int row = 0;
-#pragma unroll
-    for (int dx = 0; dx < 5; ++dx) row += k[dx] * g[threadIdx.y + dy][threadIdx.x + dx];
-    acc += k[dy] * row;
-  }
-  blur[img * (size_t)h * w + (size_t)y * w + x] = (uint8_t)((acc + 128) >> 8);
+  lines_blur_tile<false>(bgr + img * (size_t)h * w * 3, h, w, blockIdx.x, blockIdx.y, blur + img * (size_t)h * w, g);
 }
 
 __global__ void lines_sobel_kernel(const uint8_t* __restrict__ blur, int h, int w, short2* __restrict__ grad, unsigned short* __restrict__ mag) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= w || y >= h) return;
   const size_t base = (size_t)blockIdx.z * h * w;
-  const uint8_t* s = blur + base;
-  const int xm = lines_clampi(x - 1, w), xp = lines_clampi(x + 1, w), ym = lines_clampi(y - 1, h), yp = lines_clampi(y + 1, h);
-  const int a = s[(size_t)ym * w + xm], b = s[(size_t)ym * w + x], c = s[(size_t)ym * w + xp];
-  const int d = s[(size_t)y * w + xm], f = s[(size_t)y * w + xp];
-  const int g = s[(size_t)yp * w + xm], hh = s[(size_t)yp * w + x], i = s[(size_t)yp * w + xp];
-  const int dx = (c + 2 * f + i) - (a + 2 * d + g), dy = (g + 2 * hh + i) - (a + 2 * b + c);
-  grad[base + (size_t)y * w + x] = make_short2((short)dx, (short)dy);
-  mag[base + (size_t)y * w + x] = (unsigned short)(abs(dx) + abs(dy));
+  lines_sobel_px(blur + base, h, w, x, y, grad + base, mag + base);
 }
 
 // PER_IMAGE: the two thresholds of image blockIdx.z are read from thr[2 * blockIdx.z] (lower, upper) instead of low / high
@@ -73,28 +38,7 @@ __global__ void lines_nms_kernel(const short2* __restrict__ grad, const unsigned
   if (x >= w || y >= h) return;
   if (PER_IMAGE) { low = thr[2 * blockIdx.z]; high = thr[2 * blockIdx.z + 1]; }
   const size_t base = (size_t)blockIdx.z * h * w;
-  const unsigned short* mg = mag + base;
-  auto M = [&](int yy, int xx) -> int { return (xx < 0 || xx >= w || yy < 0 || yy >= h) ? 0 : (int)mg[(size_t)yy * w + xx]; };   // zero outside
-  const int m = mg[(size_t)y * w + x];
-  uint8_t out = 1;
-  if (m > low) {
-    const short2 gr = grad[base + (size_t)y * w + x];
-    const int xs = gr.x, ys = gr.y;
-    const int ax = abs(xs), ay = abs(ys) << 15;
-    const int tg22x = ax * 13573;                      // tan(22.5 deg) * 2^15, rounded
-    bool peak;
-    if (ay < tg22x) peak = m > M(y, x - 1) && m >= M(y, x + 1);                      // gradient ~horizontal
-    else {
-      const int tg67x = tg22x + (ax << 16);
-      if (ay > tg67x) peak = m > M(y - 1, x) && m >= M(y + 1, x);                    // ~vertical
-      else {
-        const int s = (xs ^ ys) < 0 ? -1 : 1;                                        // diagonal the gradient points along
-        peak = m > M(y - 1, x - s) && m > M(y + 1, x + s);
-      }
-    }
-    if (peak) out = m > high ? 2 : 0;
-  }
-  map[base + (size_t)y * w + x] = out;
+  map[base + (size_t)y * w + x] = lines_nms_px(grad + base, mag + base, h, w, x, y, low, high);
 }
 
 // d_bgr [n][h][w][3] -> d_map [n][h][w]; d_blur / d_grad / d_mag: scratch of n*h*w elements each.
@@ -103,7 +47,7 @@ void launch_canny_map(const uint8_t* d_bgr, int n, int h, int w, int low, int hi
   FE_CHECK(n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 31) && n <= 65535, "canny: bad shape");
   hipLaunchKernelGGL(lines_blur_kernel, dim3((w + LB_W - 1) / LB_W, (h + LB_H - 1) / LB_H, n), dim3(LB_W, LB_H), 0, s, d_bgr, h, w, d_blur);
   FE_HIP(hipGetLastError());
-  const dim3 blk(64, 4), grid((w + 63) / 64, (h + 3) / 4, n);
+  const dim3 blk(LS_W, LS_H), grid((w + LS_W - 1) / LS_W, (h + LS_H - 1) / LS_H, n);
   hipLaunchKernelGGL(lines_sobel_kernel, grid, blk, 0, s, d_blur, h, w, (short2*)d_grad, (unsigned short*)d_mag);
   FE_HIP(hipGetLastError());
   hipLaunchKernelGGL(lines_nms_kernel<false>, grid, blk, 0, s, (const short2*)d_grad, (const unsigned short*)d_mag, h, w, low, high, (const int*)nullptr,
@@ -115,7 +59,7 @@ void launch_canny_map(const uint8_t* d_bgr, int n, int h, int w, int low, int hi
 // device memory: d_thr [n][2] = lower, upper. Same Sobel, same suppression as above.
 void launch_canny_map_gray(const uint8_t* d_gray, int n, int h, int w, const int* d_thr, void* d_grad, void* d_mag, uint8_t* d_map, hipStream_t s) {
   FE_CHECK(n > 0 && h > 0 && w > 0 && (size_t)h * w < (1ull << 31) && n <= 65535, "canny: bad shape");
-  const dim3 blk(64, 4), grid((w + 63) / 64, (h + 3) / 4, n);
+  const dim3 blk(LS_W, LS_H), grid((w + LS_W - 1) / LS_W, (h + LS_H - 1) / LS_H, n);
   hipLaunchKernelGGL(lines_sobel_kernel, grid, blk, 0, s, d_gray, h, w, (short2*)d_grad, (unsigned short*)d_mag);
   FE_HIP(hipGetLastError());
   hipLaunchKernelGGL(lines_nms_kernel<true>, grid, blk, 0, s, (const short2*)d_grad, (const unsigned short*)d_mag, h, w, 0, 0, d_thr, d_map);

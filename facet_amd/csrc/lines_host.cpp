@@ -167,4 +167,33 @@ void lines_host_stage(uint8_t* maps, int n, int h, int w, int threshold, int min
   if (failed) throw std::runtime_error("leading lines: a host worker failed (out of memory?)");
 }
 
+// The same for n images of their own sizes: image i is maps + offsets[i], hw[2 i] x hw[2 i + 1], with its own min_len[i]. Sizes differ,
+// so a strided split would leave threads idle behind one large photo: the threads take images from a shared cursor over the images in
+// descending pixel count.
+void lines_host_stage_mixed(uint8_t* maps, const size_t* offsets, const int32_t* hw, int n, int threshold, const int32_t* min_len, int max_gap,
+                            int max_lines, int* lines, int* counts, int threads) {
+  std::vector<int> order(n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  auto npx = [&](int i) { return (size_t)hw[2 * i] * (size_t)hw[2 * i + 1]; };
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return npx(a) > npx(b); });
+  std::atomic<int> cursor{0};
+  auto work = [&]() {
+    for (int q; (q = cursor.fetch_add(1, std::memory_order_relaxed)) < n;) {
+      const int i = order[q], h = hw[2 * i], w = hw[2 * i + 1];
+      canny_hysteresis(maps + offsets[i], h, w);
+      if (lines) counts[i] = hough_lines_p(maps + offsets[i], h, w, threshold, min_len[i], max_gap, max_lines, lines + (size_t)i * max_lines * 4);
+    }
+  };
+  const int T = std::max(1, std::min({n, threads, 16}));
+  if (T == 1) { work(); return; }
+  std::atomic<bool> failed{false};
+  std::vector<std::thread> pool;
+  for (int t = 0; t < T; ++t)
+    pool.emplace_back([&] {
+      try { work(); } catch (...) { failed = true; }
+    });
+  for (auto& th : pool) th.join();
+  if (failed) throw std::runtime_error("leading lines: a host worker failed (out of memory?)");
+}
+
 }  // namespace fe

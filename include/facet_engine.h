@@ -815,6 +815,32 @@ int fe_external_contours(fe_ctx* ctx, const uint8_t* binary, int n, int h, int w
 int fe_subject_region(fe_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int on_device, int max_contours, long long* records, int* counts,
                       int* thresholds, uint8_t* edges_out);
 
+/* fe_leading_lines and fe_subject_region for a list of images that each have their own size: per arena chunk of the list every GPU stage
+ * is ONE launch over the tiles of all its images (a workgroup finds its image by bisecting a table of cumulative tile counts; nothing is
+ * described per tile), and the results of the chunk come down in one or two copies. images / hw / on_device / order: as for
+ * fe_image_stats_mixed - host or device pointers to packed [h][w][3] uint8 at any byte alignment, hw [n][2] = h, w, order FE_ORDER_BGR or
+ * FE_ORDER_RGB (the gray conversions read R, G, B in place: no swapped copy). Any h, w >= 1 with h * w below 2^30, the per-shape calls'
+ * own bound. Results are in input order, and for every image every output equals what the per-shape call returns for that image alone:
+ * each edge byte, threshold, segment and contour record, in the same order, and each count. edges_out (nullable, host) is ONE flat
+ * buffer: image i starts at the sum of h * w of the images before it.
+ * fe_leading_lines_mixed: min_line_length [n] is per image (the reference uses int(min(h, w) * 0.15)); lines [n][max_lines][4] and
+ * counts [n] as in fe_leading_lines, nullable together. Hysteresis and the Hough transform run on up to 16 host threads that take the
+ * chunk's images largest first from a shared cursor.
+ * fe_subject_region_mixed: records [n][max_contours][FE_CONTOUR_FIELDS], counts [n] (exact also beyond max_contours) and thresholds
+ * [n][2] (nullable) as in fe_subject_region.
+ * A null list, n <= 0, a null image, a side below 1, h * w >= 2^30, a bad order or bad thresholds return FE_ERR_INVALID, the message names
+ * the index of the image, nothing is launched. An image whose own scratch (8 bytes per pixel for the lines, about 55 for the subject
+ * region, 3 more when the pixels are staged from the host) exceeds the arena returns FE_ERR_CAPACITY; the message names the image, its
+ * size, the bytes needed and the bytes held, nothing is launched. */
+int fe_leading_lines_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int canny_low,
+                           int canny_high, int threshold, const int32_t* min_line_length, int max_line_gap, int max_lines, int* lines, int* counts,
+                           uint8_t* edges_out);
+int fe_subject_region_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, int max_contours,
+                            long long* records, int* counts, int* thresholds, uint8_t* edges_out);
+/* Milliseconds the host stage (hysteresis and Hough, over all chunks) of the context's last fe_leading_lines or fe_leading_lines_mixed
+ * call took: the part of such a call that is host threads rather than kernels. For measurements (tools/perf_mixed.py --composition). */
+int fe_lines_host_ms(fe_ctx* ctx, double* ms);
+
 /* Perceptual hash: `imagehash.phash(pil_img)` with its defaults (hash_size 8, highfreq_factor 4), which the reference stores as
  * str(...) in the `phash` column for every image (processing/batch_processor.py:216, multi_pass.py:449, scorer.py:972):
  * image.convert('L') ((R*19595 + G*38470 + B*7471 + 0x8000) >> 16), .resize((32, 32), LANCZOS) (PIL's two-pass 22-bit fixed-point

@@ -22,7 +22,15 @@ graphs of standins/ at det_size 640 and at most 8 faces kept per photo. The same
 allocation, fe_swap_rb_u8, fe_face_analyze and fe_roi_laplacian on the BGR copy, the free) against one fe_face_analyze_mixed and one
 fe_roi_laplacian_mixed call on the RGB pixels; then process_images with a face analyzer (gpu_thumbnails) on and mixed_sizes off / on, and
 Engine.face_cache_entries() with the device memory in use over three chunks of new shapes. On a checkout without the mixed face calls only
-the process_images rows and the per-shape memory row are printed: that is how the parent commit is measured in the same session."""
+the process_images rows and the per-shape memory row are printed: that is how the parent commit is measured in the same session.
+
+perf_mixed.py --composition [--repeats R]: leading lines and the subject region alone (written to profiles/mixed_composition_perf.txt). The
+same chunks and the 6000 x 4000 image, lines and subject separately: per shape group as process_batch does it (a device allocation,
+fe_swap_rb_u8, fe_leading_lines / fe_subject_region on the BGR copy, the free) against one fe_leading_lines_mixed / fe_subject_region_mixed
+call on the RGB pixels; for the lines also the milliseconds of the host stage (hysteresis + Hough on host threads, fe_lines_host_ms) inside
+the median call. Then process_images with both options on (TOPIQ only) and mixed_sizes off / on, and the device memory in use over three
+chunks of new shapes. On a checkout without the mixed calls only the process_images rows and the per-shape memory row are printed: that
+is how the parent commit is measured in the same session."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,6 +49,7 @@ ap.add_argument("--policies", default="f32,parity")
 ap.add_argument("--stats", action="store_true", help="the statistics table instead of the process_images table")
 ap.add_argument("--index", action="store_true", help="the pHash / thumbnail table instead of the process_images table")
 ap.add_argument("--faces", action="store_true", help="the face-stage table instead of the process_images table")
+ap.add_argument("--composition", action="store_true", help="the leading-lines / subject-region table instead of the process_images table")
 ap.add_argument("--det-thresh", type=float, default=0.54, help="--faces: the stand-in detector's scores crowd around 0.5; 0.54 leaves a few faces per photo")
 ap.add_argument("--repeats", type=int, default=7)
 args = ap.parse_args()
@@ -304,6 +313,83 @@ if args.faces:
                 tables.append(e.face_cache_entries())
         print(f"{'one mixed call' if mixed else 'per shape':22} " + ("tables " + " / ".join(str(t) for t in tables) + "  " if has_mixed else "") +
               "MiB " + " / ".join(f"{m:.0f}" for m in mem), flush=True)
+    e.close()
+    sys.exit(0)
+
+def composition_rows(e, label, imgs, repeats):
+    """Lines and subject region of a chunk that is resident as RGB, grouped by shape as _process_images_mixed lays it out: per shape group
+    as process_batch computes them against one mixed call on the RGB pixels."""
+    groups = {}
+    for i, a in enumerate(imgs):
+        groups.setdefault(a.shape[:2], []).append(i)
+    bufs, ptrs, sizes = [], [None] * len(imgs), [a.shape[:2] for a in imgs]
+    for (h, w), idx in groups.items():
+        d = e.dev_alloc(len(idx) * h * w * 3)
+        e.h2d(d, np.stack([imgs[i] for i in idx]))
+        bufs.append((d, len(idx), h, w))
+        for j, i in enumerate(idx):
+            ptrs[i] = d.value + j * h * w * 3
+    host = []
+
+    def per_group(stage, lines):
+        ms = 0.0
+        for d, k, h, w in bufs:
+            d_bgr = e.dev_alloc(k * h * w * 3)
+            try:
+                e.swap_rb(d, k * h * w, d_bgr)
+                stage((d_bgr, k, h, w))
+                ms += e.lines_host_ms() if lines else 0.0
+            finally:
+                e.dev_free(d_bgr)
+        host.append(ms)
+
+    def mixed_lines():
+        e.leading_lines_mixed((ptrs, sizes), order='rgb')
+        host.append(e.lines_host_ms())
+
+    rows = (("lines", lambda: per_group(e.leading_lines, True), mixed_lines),
+            ("subject", lambda: per_group(e.subject_contours, False), lambda: e.subject_contours_mixed((ptrs, sizes), order='rgb')))
+    for name, grouped, mixed in rows:
+        for what, call in ((name + ": per group (alloc + swap + call)", grouped), (name + ": one mixed call", mixed)):
+            del host[:]
+            t = timed(call, repeats)
+            stage = f"   host stage {np.median(host[1:]):9.2f}" if name == "lines" else ""
+            print(f"{label:22} {what:44} {t}{stage}", flush=True)
+    for b in bufs:
+        e.dev_free(b[0])
+
+
+if args.composition:
+    has_mixed = hasattr(Engine, "leading_lines_mixed")
+    e = Engine(0, arena_bytes=(4 + 2 * 8) << 30)      # bench.py's arena for the default micro-batch of 8 at 1024 x 1024
+    print(f"{n} images per chunk, sides 776 .. 1280, resident RGB; milliseconds per chunk: median (fastest .. slowest) of {args.repeats} calls after a warm-up")
+    if has_mixed:
+        for n_shapes in (1, 16, 256):
+            shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+            composition_rows(e, f"{n} images, {n_shapes} shapes", chunk(shapes), args.repeats)
+        composition_rows(e, "1 image 4000 x 6000", [np.ascontiguousarray(np.tile(field, (3, 5, 1))[:4000, :6000])], args.repeats)
+    e.load_weights(FE_MODEL_TOPIQ, synthetic_state_dict("topiq", 4))
+    print("process_images, detect_lines + subject_region on, TOPIQ only: milliseconds per chunk (upload included)")
+    for n_shapes in (1, 16, 256):
+        shapes = [shape(17 * k + 5) for k in range(n_shapes)] if n_shapes > 1 else [(1024, 1024)]
+        imgs = chunk(shapes)
+        for mixed in (False, True):
+            bs = BatchScorer(e, mixed_sizes=mixed, detect_lines=True, subject_region=True)
+            print(f"{n} images, {n_shapes:3} shapes  mixed_sizes={str(mixed):5} {timed(lambda: bs.process_images(imgs), max(3, args.repeats // 2))}", flush=True)
+    print("device MiB in use before / after each of three chunks of new shapes (lines + subject region of every image)")
+    next_shape = 1024
+    for mixed in ((False, True) if has_mixed else (False,)):
+        mem = [used_mib()]
+        for r in range(3):
+            imgs = chunk([shape(next_shape + k) for k in range(256)], first=r * n)
+            next_shape += 256
+            if mixed:
+                e.leading_lines_mixed(imgs, order='rgb'); e.subject_contours_mixed(imgs, order='rgb')
+            else:
+                for a in imgs:
+                    e.leading_lines(a[None]); e.subject_contours(a[None])
+            mem.append(used_mib())
+        print(f"{'one mixed call each' if mixed else 'per shape':22} MiB " + " / ".join(f"{m:.0f}" for m in mem), flush=True)
     e.close()
     sys.exit(0)
 
