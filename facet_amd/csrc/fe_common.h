@@ -456,7 +456,8 @@ void launch_add_rows_bcast(T* y, int ldy, const float* pos, int rows, int L, int
 void launch_affine_act(const Tensor& x, const Tensor& y, const float* scale, const float* shift, int act, const float* slope,
                        hipStream_t s);
 // op: 0 add, 1 sub, 2 mul, 3 div
-void launch_binary(const Tensor& a, const Tensor& b, const Tensor& y, int op, int act, hipStream_t s);
+// lc: logical channels of a padded feature map (channels lc .. c - 1 of y are written as zeros); -1: all channels are logical
+void launch_binary(const Tensor& a, const Tensor& b, const Tensor& y, int op, int act, hipStream_t s, int lc = -1);
 // dst dense [dims0..5] row-major; element (i0..i5) read from src[sum i_k * sstr_k]
 void launch_gather_strided(const float* src, float* dst, const long long dims[6], const long long sstr[6], hipStream_t s);
 void launch_nearest(const Tensor& x, const Tensor& y, hipStream_t s);

@@ -52,9 +52,10 @@ void launch_affine_act(const Tensor& x, const Tensor& y, const float* scale, con
   FE_HIP(hipGetLastError());
 }
 
-// ---- y = act(a (op) b), same shape ------------------------------------------------------------------------------
+// ---- y = act(a (op) b), same shape; channels from `lc` on (the padding lanes of a feature map) are written as zeros, whatever the
+//      operands hold there: 0 / 0 in a padding lane would otherwise reach the next matrix product as NaN * 0 -----------------------
 __global__ void binary_kernel(const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb, float* __restrict__ y,
-                              int ldy, size_t pixels, int c4, int op, int act) {
+                              int ldy, size_t pixels, int c4, int lc, int op, int act) {
   const size_t total = pixels * c4;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t pix = i / c4;
@@ -67,17 +68,20 @@ __global__ void binary_kernel(const float* __restrict__ a, int lda, const float*
     else if (op == 2) v = make_float4(u.x * w.x, u.y * w.y, u.z * w.z, u.w * w.w);
     else v = make_float4(u.x / w.x, u.y / w.y, u.z / w.z, u.w / w.w);
     v.x = act_one(v.x, act, 0.f); v.y = act_one(v.y, act, 0.f); v.z = act_one(v.z, act, 0.f); v.w = act_one(v.w, act, 0.f);
+    if (ch + 3 >= lc) {
+      v.x = ch < lc ? v.x : 0.f; v.y = ch + 1 < lc ? v.y : 0.f; v.z = ch + 2 < lc ? v.z : 0.f; v.w = ch + 3 < lc ? v.w : 0.f;
+    }
     *reinterpret_cast<float4*>(y + pix * ldy + ch) = v;
   }
 }
-void launch_binary(const Tensor& a, const Tensor& b, const Tensor& y, int op, int act, hipStream_t s) {
+void launch_binary(const Tensor& a, const Tensor& b, const Tensor& y, int op, int act, hipStream_t s, int lc) {
   FE_CHECK(a.c == b.c && a.c == y.c && a.pixels() == b.pixels() && a.pixels() == y.pixels() && a.c % 4 == 0 &&
                a.ld % 4 == 0 && b.ld % 4 == 0 && y.ld % 4 == 0, "binary: shapes");
   FE_CHECK(act != ACT_PRELU, "binary: PReLU is not fusable here");
   const size_t work = a.pixels() * (a.c / 4);
   if (!work) return;
   hipLaunchKernelGGL(binary_kernel, dim3(grid_for_g(work)), dim3(256), 0, s, a.p, a.ld, b.p, b.ld, y.p, y.ld, a.pixels(),
-                     a.c / 4, op, act);
+                     a.c / 4, lc < 0 ? a.c : lc, op, act);
   FE_HIP(hipGetLastError());
 }
 

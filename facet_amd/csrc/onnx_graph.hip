@@ -563,7 +563,7 @@ void Graph::exec_node(Ctx& c, int idx) {
              "graph: %s '%s' needs equal shapes (broadcasting between feature maps is not supported)", op.c_str(), n.name.c_str());
     Val y = a;
     y.t = c.arena.tensor(a.t.n, a.t.h, a.t.w, a.t.c);
-    launch_binary(a.t, b.t, y.t, code, ACT_NONE, c.stream);
+    launch_binary(a.t, b.t, y.t, code, ACT_NONE, c.stream, a.lc);   // padding lanes stay zero (Div: 0 / 0 there)
     vals_[out0()] = y;
     return;
   }
@@ -611,6 +611,18 @@ void Graph::exec_node(Ctx& c, int idx) {
     } else FE_CHECK(false, "graph: Resize '%s' needs constant scales or sizes", n.name.c_str());
     const std::string mode = n.gets("mode", "nearest");
     const std::string ctm = n.gets("coordinate_transformation_mode", old ? "asymmetric" : "half_pixel");
+    FE_CHECK(Ho > 0 && Wo > 0, "graph: Resize '%s' yields an empty output", n.name.c_str());
+    if (!(sizes && sizes->numel() == 4)) {
+      // The kernels take their source coordinates from in / out. The specification divides by the GIVEN scale, which is the same
+      // thing only where in * scale is a whole number (out = floor(in * scale)); other scales are rejected rather than resampled
+      // on a slightly different grid.
+      FE_CHECK((double)Ho == (double)x.t.h * scales->at(2) && (double)Wo == (double)x.t.w * scales->at(3),
+               "graph: Resize '%s': scales %g x %g do not map %dx%d to whole pixels; only such scales (or sizes) are supported",
+               n.name.c_str(), scales->at(2), scales->at(3), x.t.h, x.t.w);
+    }
+    // pytorch_half_pixel maps an output of length 1 to source coordinate 0, half_pixel (what the kernel computes) to the centre
+    FE_CHECK(ctm != "pytorch_half_pixel" || ((Ho > 1 || x.t.h == 1) && (Wo > 1 || x.t.w == 1)),
+             "graph: Resize '%s': pytorch_half_pixel with an output length of 1 is not supported", n.name.c_str());
     Val y = x;
     y.t = c.arena.tensor(x.t.n, Ho, Wo, x.t.c);
     if (mode == "nearest") {

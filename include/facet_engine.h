@@ -641,7 +641,8 @@ int fe_preprocess224_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
  * engine parses the .onnx bytes itself (no protobuf/onnx dependency) and executes the nodes on its own HIP kernels.
  * Supported operators: Conv (dense and depthwise), Gemm, MatMul (constant B), BatchNormalization, Relu, PRelu, LeakyRelu,
  * Sigmoid, Add/Sub/Mul/Div, MaxPool, AveragePool, GlobalAveragePool, Resize/Upsample (nearest asymmetric-floor, linear
- * half-pixel), Concat (channels), Flatten, Reshape, Transpose, Squeeze, Unsqueeze, Softmax, Identity, Dropout, Constant and
+ * half_pixel / pytorch_half_pixel; by sizes, or by scales that give whole pixels: in * scale must be an integer; rejected with
+ * a "graph: Resize" error: other scales, pytorch_half_pixel with an output length of 1, every other mode), Concat (channels), Flatten, Reshape, Transpose, Squeeze, Unsqueeze, Softmax, Identity, Dropout, Constant and
  * the constant shape arithmetic exporters emit (Shape, Gather, Cast, Slice, Concat, Floor, Ceil). Anything else fails with
  * an error (fe_last_error) naming the operator. One float image input [N,C,H,W]. */
 #define FE_GRAPH_SLOTS 8

@@ -277,15 +277,19 @@ def run(model, x):
             elif op == "Squeeze":
                 axes = a.get("axes") or (i[1].tolist() if len(i) > 1 else None)
                 y = i[0]
-                for ax in sorted(axes or [k for k, d in enumerate(y.shape) if d == 1], reverse=True):
+                for ax in sorted([ax % y.dim() for ax in axes] if axes else [k for k, d in enumerate(y.shape) if d == 1], reverse=True):
                     y = y.squeeze(ax)
             elif op == "Unsqueeze":
                 axes = a.get("axes") or i[1].tolist()
                 y = i[0]
-                for ax in sorted(axes):
+                for ax in sorted(ax % (y.dim() + len(axes)) for ax in axes):   # axes count in the OUTPUT's rank
                     y = y.unsqueeze(ax)
             elif op == "Softmax":
-                y = torch.softmax(i[0], dim=a.get("axis", -1 if opset >= 13 else 1))
+                if opset >= 13:
+                    y = torch.softmax(i[0], dim=a.get("axis", -1))
+                else:       # below opset 13 the input is coerced to 2-D at `axis` and every row normalised
+                    ax = a.get("axis", 1) % i[0].dim()
+                    y = torch.softmax(i[0].reshape(int(np.prod(i[0].shape[:ax], dtype=np.int64)), -1), dim=1).reshape(i[0].shape)
             elif op in ("Identity", "Dropout"):
                 y = i[0]
             elif op == "Constant":
