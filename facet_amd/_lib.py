@@ -898,13 +898,17 @@ class Engine:
         hw = np.ascontiguousarray(np.array([(0, 0) if a is None else a.shape[:2] for a in arrs], dtype=np.int32).reshape(len(arrs), 2))
         return (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs]), hw, len(arrs), 0, arrs
 
+    @staticmethod
+    def _hwp(hw):      # the sizes of _img_list as the mixed-size entry points take them
+        return hw.ctypes.data_as(C.POINTER(C.c_int32))
+
     def ensemble_score_mixed(self, images):
         """ensemble_score for images that each have their own size: a list of uint8 [h, w, 3] arrays, or (device_pointers, sizes) for
         resident images. -> (records float32 [n, 789] in input order, models_run bitmask). include/facet_engine.h fe_ensemble_score_mixed."""
         ptrs, hw, n, dev, keep = self._img_list(images)
         rec = np.empty((n, FE_RECORD_FLOATS), np.float32)
         mask = C.c_int(0)
-        self._ck(self.lib.fe_ensemble_score_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, rec.ctypes.data_as(_f32p), C.byref(mask)))
+        self._ck(self.lib.fe_ensemble_score_mixed(self.h, ptrs, self._hwp(hw), n, dev, rec.ctypes.data_as(_f32p), C.byref(mask)))
         return rec, mask.value
 
     def preprocess224_mixed(self, images, mode):
@@ -912,7 +916,7 @@ class Engine:
         ptrs, hw, n, dev, keep = self._img_list(images)
         crops = np.empty((n, 224, 224, 3), np.uint8)
         m = {"clip": FE_MIXED_CLIP, "samp": FE_MIXED_SAMP}.get(mode, mode)
-        self._ck(self.lib.fe_preprocess224_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(m), crops.ctypes.data_as(_u8p)))
+        self._ck(self.lib.fe_preprocess224_mixed(self.h, ptrs, self._hwp(hw), n, dev, int(m), crops.ctypes.data_as(_u8p)))
         return crops
 
     def ensemble_select(self, models=7):
@@ -1485,7 +1489,7 @@ class Engine:
         faces = np.empty((max(n, 0), max_faces, FE_FACE_FLOATS), np.float32)
         counts = np.zeros((max(n, 0),), np.int32)
         mask = C.c_int(0)
-        self._ck(self.lib.fe_face_analyze_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), int(det_size[0]),
+        self._ck(self.lib.fe_face_analyze_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), int(det_size[0]),
                                                 int(det_size[1]), float(det_thresh), float(nms_thresh), int(max_faces), faces.ctypes.data_as(_f32p),
                                                 counts.ctypes.data_as(C.POINTER(C.c_int)), C.byref(mask)))
         return faces, counts, mask.value
@@ -1499,7 +1503,7 @@ class Engine:
         assert Mm.shape[0] == m
         out = np.empty((m, out_dim), np.float32) if out_dim else None
         crops = np.empty((m, size, size, 3), np.uint8) if want_crops else None
-        self._ck(self.lib.fe_face_crops_run_mixed(self.h, int(slot), ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), m,
+        self._ck(self.lib.fe_face_crops_run_mixed(self.h, int(slot), ptrs, self._hwp(hw), n, dev, self._order(order), m,
                                                   idx.ctypes.data_as(C.POINTER(C.c_int)), Mm.ctypes.data_as(C.POINTER(C.c_double)), int(size), float(mean),
                                                   float(scale), int(swap_rb), out.ctypes.data_as(_f32p) if out_dim else None, int(out_dim),
                                                   crops.ctypes.data_as(C.c_void_p) if want_crops else None))
@@ -1509,7 +1513,7 @@ class Engine:
         """The detector input face_analyze_mixed makes of every image: float32 [n, det_h, det_w, 4] (R, G, B, 0). For the parity tests."""
         ptrs, hw, n, dev, keep = self._img_list(images)
         out = np.empty((max(n, 0), int(det_size[0]), int(det_size[1]), 4), np.float32)
-        self._ck(self.lib.fe_face_det_input_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), int(det_size[0]),
+        self._ck(self.lib.fe_face_det_input_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), int(det_size[0]),
                                                   int(det_size[1]), out.ctypes.data_as(_f32p)))
         return out
 
@@ -1519,7 +1523,7 @@ class Engine:
         idx = np.ascontiguousarray(img_index, dtype=np.int32)
         r = np.ascontiguousarray(rois, dtype=np.int32).reshape(-1, 4)
         out = np.zeros((idx.shape[0], 4), np.float64)
-        self._ck(self.lib.fe_roi_laplacian_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), idx.shape[0],
+        self._ck(self.lib.fe_roi_laplacian_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), idx.shape[0],
                                                  idx.ctypes.data_as(C.POINTER(C.c_int)), r.ctypes.data_as(C.POINTER(C.c_int)),
                                                  out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
@@ -1548,8 +1552,7 @@ class Engine:
         every double equal to image_stats's for that image. include/facet_engine.h fe_image_stats_mixed."""
         ptrs, hw, n, dev, keep = self._img_list(images)
         stats = np.empty((n, FE_STATS_DOUBLES), np.float64)
-        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
-        self._ck(self.lib.fe_image_stats_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o),
+        self._ck(self.lib.fe_image_stats_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order),
                                                stats.ctypes.data_as(C.POINTER(C.c_double))))
         return stats
 
@@ -1658,7 +1661,7 @@ class Engine:
         while True:
             lines = np.zeros((max(n, 0), max_lines, 4), np.int32)
             counts = np.zeros(max(n, 0), np.int32)
-            self._ck(self.lib.fe_leading_lines_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), canny_low,
+            self._ck(self.lib.fe_leading_lines_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), canny_low,
                                                      canny_high, threshold, min_len.ctypes.data_as(C.c_void_p), max_line_gap, max_lines,
                                                      lines.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
                                                      flat.ctypes.data_as(C.c_void_p) if want_edges else None))
@@ -1684,7 +1687,7 @@ class Engine:
         flat = np.empty(int((hw[:, 0].astype(np.int64) * hw[:, 1]).clip(0).sum()) if n > 0 else 0, np.uint8) if want_edges else None
         thr = np.zeros((max(n, 0), 2), np.int32) if want_thresholds else None
         out = self._contour_call(lambda room, rec, cnt: self.lib.fe_subject_region_mixed(
-            self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), room, rec, cnt,
+            self.h, ptrs, self._hwp(hw), n, dev, self._order(order), room, rec, cnt,
             thr.ctypes.data_as(C.c_void_p) if want_thresholds else None, flat.ctypes.data_as(C.c_void_p) if want_edges else None), max(n, 0), max_contours)
         return (out, self._split_edges(flat, hw) if want_edges else None, thr) if (want_edges or want_thresholds) else out
 
@@ -1710,8 +1713,7 @@ class Engine:
         hashes = np.empty((n,), np.uint64)
         small = np.empty((n, 32, 32), np.uint8) if want_small else None
         lo = np.empty((n, 8, 8), np.float64) if want_dct else None
-        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
-        self._ck(self.lib.fe_phash_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o), hashes.ctypes.data_as(C.c_void_p),
+        self._ck(self.lib.fe_phash_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), hashes.ctypes.data_as(C.c_void_p),
                                          small.ctypes.data_as(C.c_void_p) if want_small else None,
                                          lo.ctypes.data_as(C.c_void_p) if want_dct else None))
         return (hashes, small, lo) if (want_small or want_dct) else hashes
@@ -1809,9 +1811,8 @@ class Engine:
         cap = int(cap)
         out = np.empty((n, cap), np.uint8)
         lengths = np.zeros(n, np.int32)
-        o = {"bgr": FE_ORDER_BGR, "rgb": FE_ORDER_RGB}.get(order, order)
         try:
-            self._ck(self.lib.fe_thumbnail_jpeg_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, int(o), arr.ctypes.data_as(C.c_void_p),
+            self._ck(self.lib.fe_thumbnail_jpeg_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), arr.ctypes.data_as(C.c_void_p),
                                                       int(quality), out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         except EngineCapacityError as err:
             err.lengths = lengths
@@ -1885,7 +1886,7 @@ class Engine:
         cap = int(cap)
         out = np.empty((m, cap), np.uint8)
         lengths = np.zeros(m, np.int32)
-        self._ck(self.lib.fe_face_thumbnails_mixed(self.h, ptrs, hw.ctypes.data_as(C.POINTER(C.c_int32)), n, dev, self._order(order), m,
+        self._ck(self.lib.fe_face_thumbnails_mixed(self.h, ptrs, self._hwp(hw), n, dev, self._order(order), m,
                                                    idx.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), sz.ctypes.data_as(C.c_void_p), int(quality),
                                                    out.ctypes.data_as(C.c_void_p), cap, lengths.ctypes.data_as(C.c_void_p)))
         return self._jpeg_rows(out, lengths)

@@ -219,31 +219,31 @@ void write_face_records(const FaceBatch& F, int nb, int max_faces, int lm_size, 
 
 // ---- the mixed-size calls ---------------------------------------------------------------------------------------------------------
 using face_plan::ImageDesc;
-constexpr int kMixedMaxSide = 65535;
+constexpr MixedLimits kFaceLimits = {1, 65535, 65535, ((size_t)1 << 31) - 1, "below 2^31"};
 
 // src of every descriptor: the caller's pointer when the images are resident, else a copy in the arena on a 256-byte boundary. An image
 // that does not fit with `reserve` bytes left for the call's own scratch is a CapacityError that names it.
-void place_images(Ctx& C, const char* who, const uint8_t* const* images, int n, int on_device, size_t reserve, std::vector<ImageDesc>& descs) {
-  for (int i = 0; i < n; ++i) {
-    if (on_device) { descs[i].src = images[i]; continue; }
-    const size_t bytes = (size_t)descs[i].h * descs[i].w * 3, at = face_plan::align_up(C.arena.mark());
+void place_images(Ctx& C, const char* who, const uint8_t* const* images, const int32_t* hw, int n, int on_device, size_t reserve, ImageDesc* descs) {
+  std::vector<size_t> offs;
+  const size_t total = on_device ? 0 : mixed_list::staged_offsets(hw, 0, n, true, offs), first = mixed_list::align_up(C.arena.mark());
+  for (int i = 0; i < n && !on_device; ++i) {
+    const size_t bytes = mixed_list::image_bytes(hw, i), at = first + offs[i];
     if (at + bytes + reserve > C.arena.capacity()) {
       char b[200];
-      snprintf(b, sizeof b, "%s: image %d (%d x %d) does not fit: %zu bytes at %zu with %zu reserved, the arena holds %zu", who, i, descs[i].h, descs[i].w,
+      snprintf(b, sizeof b, "%s: image %d (%d x %d) does not fit: %zu bytes at %zu with %zu reserved, the arena holds %zu", who, i, hw[2 * i], hw[2 * i + 1],
                bytes, at, reserve, C.arena.capacity());
       throw CapacityError(b);
     }
-    uint8_t* d = (uint8_t*)C.arena.alloc(bytes);
-    FE_HIP(hipMemcpyAsync(d, images[i], bytes, hipMemcpyHostToDevice, C.stream));
-    descs[i].src = d;
   }
+  uint8_t* d_stage = on_device ? nullptr : (uint8_t*)C.arena.alloc(total);
+  stage_images(C, images, hw, 0, n, on_device, d_stage, offs.data(), [&](int i, const uint8_t* src) { descs[i].src = src; });
 }
 // descriptors that carry only src, h, w (crops, ROIs, thumbnails), placed and uploaded
 const ImageDesc* plain_descs(Ctx& C, const char* who, const uint8_t* const* images, const int32_t* hw, int n, int on_device, size_t reserve,
                              std::vector<ImageDesc>& descs) {
   descs.assign(n, ImageDesc{});
   for (int i = 0; i < n; ++i) { descs[i].h = hw[2 * i]; descs[i].w = hw[2 * i + 1]; }
-  place_images(C, who, images, n, on_device, reserve + (size_t)n * sizeof(ImageDesc) + 4096, descs);
+  place_images(C, who, images, hw, n, on_device, reserve + (size_t)n * sizeof(ImageDesc) + 4096, descs.data());
   return upload(C, descs.data(), descs.size());
 }
 bool det_size_ok(Ctx& C, const char* who, int det_h, int det_w) {
@@ -592,7 +592,7 @@ int fe_face_det_input_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
   return fe_api(ctx, OnError::Capacity, [&] {
     Ctx& C = ctx->c;
     const char* who = "fe_face_det_input_mixed";
-    if (!mixed_list_ok(C, who, (images && out) ? (const void*)images : nullptr, hw, n, order, images, kMixedMaxSide, kMixedMaxSide, true)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, who, (images && out) ? images : nullptr, hw, n, order, images, kFaceLimits)) return FE_ERR_INVALID;
     if (!det_size_ok(C, who, det_h, det_w)) return FE_ERR_INVALID;
     std::vector<ImageDesc> descs;
     face_plan::TablePool pool;
@@ -605,12 +605,11 @@ int fe_face_det_input_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
       const int nb = std::min(mbn, n - i0);
       C.arena.rewind(mark);
       float* x = (float*)C.arena.alloc((size_t)nb * px * 4 * sizeof(float));
-      std::vector<ImageDesc> part(descs.begin() + i0, descs.begin() + i0 + nb);
-      place_images(C, who, images + i0, nb, on_device, (size_t)nb * sizeof(ImageDesc) + 4096, part);
-      const ImageDesc* d_desc = upload(C, part.data(), part.size());
+      place_images(C, who, images + i0, hw + 2 * (size_t)i0, nb, on_device, (size_t)nb * sizeof(ImageDesc) + 4096, descs.data() + i0);
+      const ImageDesc* d_desc = upload(C, descs.data() + i0, (size_t)nb);
       launch_det_input_mixed(d_desc, nb, d_pool, det_h, det_w, order == FE_ORDER_RGB, x, C.stream);
       FE_HIP(hipMemcpyAsync(out + (size_t)i0 * px * 4, x, (size_t)nb * px * 4 * sizeof(float), hipMemcpyDeviceToHost, C.stream));
-      FE_HIP(hipStreamSynchronize(C.stream));      // `part` goes away; the arena is recycled by the next micro-batch
+      FE_HIP(hipStreamSynchronize(C.stream));      // the arena is recycled by the next micro-batch
     }
     return FE_OK;
   });
@@ -623,7 +622,7 @@ int fe_face_crops_run_mixed(fe_ctx* ctx, int slot, const uint8_t* const* images,
   return fe_api(ctx, OnError::Capacity, [&] {
     Ctx& C = ctx->c;
     const char* who = "fe_face_crops_run_mixed";
-    if (!mixed_list_ok(C, who, images, hw, n, order, images, kMixedMaxSide, kMixedMaxSide, true)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, who, images, hw, n, order, images, kFaceLimits)) return FE_ERR_INVALID;
     FE_CHECK(m >= 0 && size > 0 && (m == 0 || (img_index && M)), "bad arguments");
     FE_CHECK(out || crops_out, "nothing to compute: both outputs are null");
     for (int f = 0; f < m; ++f) FE_CHECK(img_index[f] >= 0 && img_index[f] < n, "crop %d refers to image %d of %d", f, img_index[f], n);
@@ -648,7 +647,7 @@ int fe_face_analyze_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32
   return fe_api(ctx, OnError::Capacity, [&] {
     Ctx& C = ctx->c;
     const char* who = "fe_face_analyze_mixed";
-    if (!mixed_list_ok(C, who, (images && faces && counts) ? (const void*)images : nullptr, hw, n, order, images, kMixedMaxSide, kMixedMaxSide, true))
+    if (!mixed_list_ok(C, who, (images && faces && counts) ? images : nullptr, hw, n, order, images, kFaceLimits))
       return FE_ERR_INVALID;
     if (!det_size_ok(C, who, det_h, det_w)) return FE_ERR_INVALID;
     if (max_faces <= 0) { C.err = "fe_face_analyze_mixed: max_faces must be positive"; return FE_ERR_INVALID; }
@@ -689,13 +688,7 @@ int fe_face_analyze_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32
       C.arena.rewind(base);
       ImageDesc* d_desc = (ImageDesc*)C.arena.alloc((size_t)nb * sizeof(ImageDesc));
       uint8_t* d_stage = staged ? (uint8_t*)C.arena.alloc(stage_b) : nullptr;
-      for (int i = i0; i < i1; ++i) {
-        descs[i].src = images[i];
-        if (staged) {      // the host images lie anywhere: one copy each, to a 256-byte boundary of the stage region
-          FE_HIP(hipMemcpyAsync(d_stage + offs[i - i0], images[i], (size_t)hw[2 * i] * hw[2 * i + 1] * 3, hipMemcpyHostToDevice, C.stream));
-          descs[i].src = d_stage + offs[i - i0];
-        }
-      }
+      stage_images(C, images, hw, i0, i1, on_device, d_stage, offs.data(), [&](int i, const uint8_t* src) { descs[i].src = src; });
       FE_HIP(hipMemcpyAsync(d_desc, descs.data() + i0, (size_t)nb * sizeof(ImageDesc), hipMemcpyHostToDevice, C.stream));
       float* d_rec = (float*)C.arena.alloc((size_t)nb * rec_floats * sizeof(float));
       FE_HIP(hipMemset2DAsync(d_rec, rec_floats * sizeof(float), 0, 16 * sizeof(float), nb, C.stream));      // the counts
@@ -766,7 +759,7 @@ int fe_roi_laplacian_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
   return fe_api(ctx, OnError::Capacity, [&] {
     Ctx& C = ctx->c;
     const char* who = "fe_roi_laplacian_mixed";
-    if (!mixed_list_ok(C, who, images, hw, n, order, images, kMixedMaxSide, kMixedMaxSide, true)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, who, images, hw, n, order, images, kFaceLimits)) return FE_ERR_INVALID;
     FE_CHECK(m >= 0 && (m == 0 || (img_index && rois && out)), "bad arguments");
     if (m == 0) return FE_OK;
     for (int f = 0; f < m; ++f) {
@@ -795,7 +788,7 @@ int fe_face_thumbnails_mixed(fe_ctx* ctx, const uint8_t* const* images, const in
   return fe_api(ctx, OnError::Capacity, [&] {
     Ctx& C = ctx->c;
     const char* who = "fe_face_thumbnails_mixed";
-    if (!mixed_list_ok(C, who, images, hw, n, order, images, kMixedMaxSide, kMixedMaxSide, true)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, who, images, hw, n, order, images, kFaceLimits)) return FE_ERR_INVALID;
     char msg[200] = "";
     if (!(m >= 0 && (m == 0 || (img_index && crops && out_sizes && out && lengths)))) snprintf(msg, sizeof msg, "%s: bad arguments", who);
     else if (quality < 1 || quality > 100) snprintf(msg, sizeof msg, "%s: quality %d (1 .. 100)", who, quality);

@@ -122,8 +122,6 @@ void ensure_phash_cos(fe_ctx* ctx) {
   FE_HIP(hipMemcpy(ctx->phash_cos, tab, sizeof(tab), hipMemcpyHostToDevice));
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // fe_phash_mixed behind its argument checks: descriptors and pool of the whole list, then chunk by chunk through the arena
 void phash_mixed_run(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, uint64_t* hashes, uint8_t* small_out,
                      double* dct_out) {
@@ -131,37 +129,25 @@ void phash_mixed_run(fe_ctx* ctx, const uint8_t* const* images, const int32_t* h
   PhashTables tables;
   std::vector<PhashDesc> descs(n);
   for (int i = 0; i < n; ++i) FE_CHECK(tables.describe(hw[2 * i], hw[2 * i + 1], descs[i]), "fe_phash_mixed: image %d: a coefficient window leaves the axis", i);
-  // what an image takes of a chunk besides the pool: its rows of tmp, its descriptor and outputs and, from the host, its staged pixels
-  auto need = [&](int i) {
-    const size_t h = (size_t)hw[2 * i], w = (size_t)hw[2 * i + 1];
-    return (size_t)phash_tmp_rows((int)h, (int)w) * kPhashSide + sizeof(PhashDesc) + sizeof(uint64_t) + (small_out ? 1024 : 0) + (dct_out ? 64 * sizeof(double) : 0) + (on_device ? 0 : up256(h * w * 3));
-  };
-  const size_t pool_b = up256(tables.pool.size() * sizeof(int32_t)), slack = 8 * 256;      // slack: the alignment of a chunk's allocations
-  const size_t room = C.arena.capacity() > pool_b + slack ? C.arena.capacity() - pool_b - slack : 0;
-  for (int i = 0; i < n; ++i)
-    if (need(i) > room) {
-      char b[200];
-      snprintf(b, sizeof b, "fe_phash_mixed: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", i, hw[2 * i], hw[2 * i + 1],
-               need(i) + pool_b + slack, C.arena.capacity());
-      throw CapacityError(b);
-    }
+  const mixed_list::Cuts cuts = phash_cuts(hw, n, small_out != nullptr, dct_out != nullptr, !on_device, tables.pool.size(), C.arena.capacity());
+  if (cuts.bad_image >= 0) throw_image_too_large("fe_phash_mixed", cuts.bad_image, hw, cuts.bad_bytes, C.arena.capacity());
   ensure_phash_cos(ctx);
   C.arena.reset();
   const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());
   const size_t mark = C.arena.mark();
-  for (int i0 = 0; i0 < n;) {
-    size_t used = 0, rows = 0, stage_b = 0;
-    int i1 = i0, max_w = 1, any_tall = 0;
-    for (; i1 < n; ++i1) {
-      if (i1 > i0 && (used + need(i1) > room || rows + (size_t)phash_tmp_rows(hw[2 * i1], hw[2 * i1 + 1]) > ((size_t)1 << 30) || i1 - i0 >= 65535)) break;
-      used += need(i1);
-      descs[i1].first_row = (uint32_t)rows;
-      rows += (size_t)phash_tmp_rows(hw[2 * i1], hw[2 * i1 + 1]);
-      any_tall |= descs[i1].tall;
-      max_w = std::max(max_w, (int)hw[2 * i1 + 1]);
-      if (!on_device) stage_b += up256((size_t)hw[2 * i1] * hw[2 * i1 + 1] * 3);
+  std::vector<size_t> offs;
+  int i0 = 0;
+  for (const int i1 : cuts.ends) {
+    size_t rows = 0;
+    int max_w = 1, any_tall = 0;
+    for (int i = i0; i < i1; ++i) {
+      descs[i].first_row = (uint32_t)rows;
+      rows += (size_t)phash_tmp_rows(hw[2 * i], hw[2 * i + 1]);
+      any_tall |= descs[i].tall;
+      max_w = std::max(max_w, (int)hw[2 * i + 1]);
     }
     const int nb = i1 - i0;
+    const size_t stage_b = on_device ? 0 : mixed_list::staged_offsets(hw, i0, i1, true, offs);
     C.arena.rewind(mark);
     PhashDesc* d_desc = (PhashDesc*)C.arena.alloc((size_t)nb * sizeof(PhashDesc));
     uint8_t* d_tmp = (uint8_t*)C.arena.alloc(rows * kPhashSide);
@@ -169,16 +155,7 @@ void phash_mixed_run(fe_ctx* ctx, const uint8_t* const* images, const int32_t* h
     uint8_t* d_small = small_out ? (uint8_t*)C.arena.alloc((size_t)nb * 1024) : nullptr;
     double* d_dct = dct_out ? (double*)C.arena.alloc((size_t)nb * 64 * sizeof(double)) : nullptr;
     uint8_t* d_stage = on_device ? nullptr : (uint8_t*)C.arena.alloc(stage_b);
-    size_t at = 0;
-    for (int i = i0; i < i1; ++i) {
-      descs[i].src = images[i];
-      if (!on_device) {      // the host images lie anywhere: one copy each, to a 256-byte boundary of the stage region
-        const size_t bytes = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
-        FE_HIP(hipMemcpyAsync(d_stage + at, images[i], bytes, hipMemcpyHostToDevice, C.stream));
-        descs[i].src = d_stage + at;
-        at += up256(bytes);
-      }
-    }
+    stage_images(C, images, hw, i0, i1, on_device, d_stage, offs.data(), [&](int i, const uint8_t* src) { descs[i].src = src; });
     FE_HIP(hipMemcpyAsync(d_desc, descs.data() + i0, (size_t)nb * sizeof(PhashDesc), hipMemcpyHostToDevice, C.stream));
     launch_phash_mixed(C, d_desc, nb, rows, max_w, any_tall, order == FE_ORDER_BGR, d_pool, d_tmp, ctx->phash_cos, d_hash, d_small, d_dct);
     FE_HIP(hipMemcpyAsync(hashes + i0, d_hash, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, C.stream));
@@ -233,48 +210,29 @@ int contour_microbatch(fe_ctx* ctx, int n, size_t per_image) {
 }
 
 // ---- what fe_leading_lines_mixed and fe_subject_region_mixed share ------------------------------------------------------------------
-// the list checks of the mixed-size calls, and the per-shape calls' own bound on an image: h * w below 2^30
-bool composition_list_ok(Ctx& C, const char* who, const uint8_t* const* images, const int32_t* hw, int n, int order) {
-  if (!mixed_list_ok(C, who, images, hw, n, order, images, INT32_MAX, INT32_MAX, false)) return false;
-  for (int i = 0; i < n; ++i)
-    if ((size_t)hw[2 * i] * (size_t)hw[2 * i + 1] >= ((size_t)1 << 30)) {
-      char b[200];
-      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h * w must stay below 2^30", who, i, hw[2 * i], hw[2 * i + 1]);
-      C.err = b;
-      return false;
-    }
-  return true;
-}
+// what the composition calls accept of an image: the per-shape calls' own bound, h * w below 2^30
+constexpr MixedLimits kCompositionLimits = {1, INT32_MAX, INT32_MAX, ((size_t)1 << 30) - 1, "below 2^30"};
 // the plan of the list, or the capacity error that names the image whose own scratch exceeds the arena
 comp_plan::Plan composition_plan(Ctx& C, const char* who, const int32_t* hw, int n, int on_device, bool subject,
                                  size_t max_chunk_pixels = comp_plan::kMaxChunkPixels) {
   comp_plan::Plan plan = comp_plan::build(hw, n, !on_device, subject, C.arena.capacity(), max_chunk_pixels);
-  if (plan.bad_image >= 0) {
-    char b[240];
-    const int i = plan.bad_image;
-    snprintf(b, sizeof b, "%s: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", who, i, hw[2 * i], hw[2 * i + 1], plan.bad_bytes,
-             C.arena.capacity());
-    throw CapacityError(b);
-  }
+  if (plan.bad_image >= 0) throw_image_too_large(who, plan.bad_image, hw, plan.bad_bytes, C.arena.capacity());
   return plan;
 }
-// A chunk's allocation with its blob (descriptors with their pointers, prefix tables) uploaded; host images are staged back to back.
-// `blob` must outlive the copy: the caller keeps it until it has synchronised.
-uint8_t* composition_stage_chunk(Ctx& C, const comp_plan::Chunk& ck, const uint8_t* const* images, int on_device, std::vector<uint8_t>& blob) {
+// A chunk's allocation with its blob (descriptors with their pointers, prefix tables) uploaded; host images are staged back to back,
+// image k at 3 * px bytes. `blob` must outlive the copy: the caller keeps it until it has synchronised.
+uint8_t* composition_stage_chunk(Ctx& C, const comp_plan::Chunk& ck, const uint8_t* const* images, const int32_t* hw, int on_device, std::vector<uint8_t>& blob) {
   const comp_plan::Layout& L = ck.lay;
   C.arena.reset();
   uint8_t* base = (uint8_t*)C.arena.alloc(L.total);
   blob.assign(L.blob_bytes, 0);
   comp_plan::ImageDesc* im = (comp_plan::ImageDesc*)blob.data();
-  for (int k = 0; k < ck.count; ++k) {
-    im[k] = ck.descs[k];
-    im[k].src = images[ck.first + k];
-    if (!on_device) {
-      uint8_t* d = base + L.stage + (size_t)im[k].px * 3;
-      FE_HIP(hipMemcpyAsync(d, im[k].src, (size_t)im[k].h * im[k].w * 3, hipMemcpyHostToDevice, C.stream));
-      im[k].src = d;
-    }
-  }
+  std::vector<size_t> offs;
+  if (!on_device) mixed_list::staged_offsets(hw, ck.first, ck.first + ck.count, false, offs);
+  stage_images(C, images, hw, ck.first, ck.first + ck.count, on_device, base + L.stage, offs.data(), [&](int i, const uint8_t* src) {
+    im[i - ck.first] = ck.descs[i - ck.first];
+    im[i - ck.first].src = src;
+  });
   for (int t = 0; t < comp_plan::kTilings; ++t)
     memcpy(blob.data() + L.blob_prefix + (size_t)t * (ck.count + 1) * sizeof(int32_t), ck.prefix[t].data(), (size_t)(ck.count + 1) * sizeof(int32_t));
   FE_HIP(hipMemcpyAsync(base + L.blob, blob.data(), L.blob_bytes, hipMemcpyHostToDevice, C.stream));
@@ -557,29 +515,10 @@ int fe_image_stats_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_
   return fe_api(ctx, OnError::Capacity, [&]() -> int {
     namespace sp = fe::stats_plan;
     Ctx& C = ctx->c;
-    char b[200];
-    if (!images || !hw || !stats || n <= 0) { C.err = "fe_image_stats_mixed: bad arguments (null list, null stats or n <= 0)"; return FE_ERR_INVALID; }
-    if (order != FE_ORDER_BGR && order != FE_ORDER_RGB) {
-      snprintf(b, sizeof b, "fe_image_stats_mixed: order %d is neither FE_ORDER_BGR (0) nor FE_ORDER_RGB (1)", order);
-      C.err = b;
-      return FE_ERR_INVALID;
-    }
-    for (int i = 0; i < n; ++i) {
-      const int h = hw[2 * i], w = hw[2 * i + 1];
-      if (!images[i]) { snprintf(b, sizeof b, "fe_image_stats_mixed: image %d is a null pointer", i); C.err = b; return FE_ERR_INVALID; }
-      if (h < 1 || w < 1 || (size_t)h * (size_t)w >= ((size_t)1 << 31)) {
-        snprintf(b, sizeof b, "fe_image_stats_mixed: image %d is %d x %d (h x w); each side must be at least 1 and h * w below 2^31", i, h, w);
-        C.err = b;
-        return FE_ERR_INVALID;
-      }
-    }
+    const char* who = "fe_image_stats_mixed";
+    if (!mixed_list_ok(C, who, (images && stats) ? images : nullptr, hw, n, order, images, kAnySideBelow2_31)) return FE_ERR_INVALID;
     const sp::Plan plan = sp::build(hw, n, !on_device, ctx->stats_segment ? ctx->stats_segment : sp::kDefaultSegment, C.arena.capacity());
-    if (plan.bad_image >= 0) {
-      const int i = plan.bad_image;
-      snprintf(b, sizeof b, "fe_image_stats_mixed: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", i, hw[2 * i], hw[2 * i + 1],
-               plan.bad_bytes, C.arena.capacity());
-      throw CapacityError(b);
-    }
+    if (plan.bad_image >= 0) throw_image_too_large(who, plan.bad_image, hw, plan.bad_bytes, C.arena.capacity());
     ensure_hsv_tables(ctx);
     std::vector<uint8_t> blob;
     for (const sp::Chunk& ck : plan.chunks) {
@@ -588,16 +527,10 @@ int fe_image_stats_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_
       uint8_t* base = (uint8_t*)C.arena.alloc(L.total);
       blob.assign(L.blob_bytes, 0);
       sp::ImageDesc* im = (sp::ImageDesc*)blob.data();
-      for (int k = 0; k < ck.count; ++k) {
-        const int i = ck.first + k;
-        const uint8_t* src = images[i];
-        if (!on_device) {      // the host images lie anywhere: one copy each, to a 256-byte boundary of the stage region
-          uint8_t* d = base + L.stage + ck.stage_off[k];
-          FE_HIP(hipMemcpyAsync(d, src, (size_t)hw[2 * i] * hw[2 * i + 1] * 3, hipMemcpyHostToDevice, C.stream));
-          src = d;
-        }
+      stage_images(C, images, hw, ck.first, ck.first + ck.count, on_device, base + L.stage, ck.stage_off.data(), [&](int i, const uint8_t* src) {
+        const int k = i - ck.first;
         im[k] = sp::ImageDesc{src, base + L.gray + ck.gray_off[k], hw[2 * i], hw[2 * i + 1], ck.nseg[k], 0};
-      }
+      });
       memcpy(blob.data() + L.blob_segs, ck.segs.data(), ck.segs.size() * sizeof(sp::SegDesc));
       memcpy(blob.data() + L.blob_strips, ck.strips.data(), ck.strips.size() * sizeof(sp::StripDesc));
       if (!ck.multi.empty()) memcpy(blob.data() + L.blob_multi, ck.multi.data(), ck.multi.size() * sizeof(int32_t));
@@ -689,7 +622,7 @@ int fe_leading_lines_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
   return fe_api(ctx, OnError::Capacity, [&]() -> int {
     Ctx& C = ctx->c;
     char b[240];
-    if (!composition_list_ok(C, "fe_leading_lines_mixed", images, hw, n, order)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, "fe_leading_lines_mixed", images, hw, n, order, images, kCompositionLimits)) return FE_ERR_INVALID;
     const char* why = nullptr;
     if ((lines != nullptr) != (counts != nullptr) || !(lines || edges_out)) why = "pass lines AND counts, and / or edges_out";
     else if (lines && max_lines <= 0) why = "max_lines must be positive";
@@ -713,7 +646,7 @@ int fe_leading_lines_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
     size_t first_px = 0;      // of the chunk, in the caller's flat edge buffer
     ctx->lines_host_ms = 0.0;
     for (const comp_plan::Chunk& ck : plan.chunks) {
-      uint8_t* base = composition_stage_chunk(C, ck, images, on_device, blob);
+      uint8_t* base = composition_stage_chunk(C, ck, images, hw, on_device, blob);
       launch_canny_map_mixed(base, ck, order == FE_ORDER_RGB, canny_low, canny_high, C.stream);
       if (!edges_out && ctx->lines_maps_cap < ck.pixels) {
         if (ctx->lines_maps) (void)hipHostFree(ctx->lines_maps);
@@ -750,7 +683,7 @@ int fe_subject_region_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
                             long long* records, int* counts, int* thresholds, uint8_t* edges_out) {
   return fe_api(ctx, OnError::Capacity, [&]() -> int {
     Ctx& C = ctx->c;
-    if (!composition_list_ok(C, "fe_subject_region_mixed", (records && counts) ? images : nullptr, hw, n, order)) return FE_ERR_INVALID;
+    if (!mixed_list_ok(C, "fe_subject_region_mixed", (records && counts) ? images : nullptr, hw, n, order, images, kCompositionLimits)) return FE_ERR_INVALID;
     if (max_contours <= 0) { C.err = "fe_subject_region_mixed: max_contours must be positive"; return FE_ERR_INVALID; }
     const comp_plan::Plan plan = composition_plan(C, "fe_subject_region_mixed", hw, n, on_device, true);
     struct Rec { long long f[FE_CONTOUR_RECORD]; };
@@ -762,7 +695,7 @@ int fe_subject_region_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
     for (const comp_plan::Chunk& ck : plan.chunks) {
       const comp_plan::Layout& L = ck.lay;
       const int nb = ck.count;
-      uint8_t* base = composition_stage_chunk(C, ck, images, on_device, blob);
+      uint8_t* base = composition_stage_chunk(C, ck, images, hw, on_device, blob);
       launch_subject_mixed(base, ck, order == FE_ORDER_RGB, C.stream);
       if (thresholds) FE_HIP(hipMemcpyAsync(thresholds + 2 * (size_t)ck.first, base + L.thr, (size_t)nb * 2 * sizeof(int), hipMemcpyDeviceToHost, C.stream));
       if (edges_out) FE_HIP(hipMemcpyAsync(edges_out + first_px, base + L.edge, ck.pixels, hipMemcpyDeviceToHost, C.stream));
@@ -848,7 +781,8 @@ int fe_phash(fe_ctx* ctx, const uint8_t* img, int n, int h, int w, int bgr, int 
 int fe_phash_mixed(fe_ctx* ctx, const uint8_t* const* images, const int32_t* hw, int n, int on_device, int order, uint64_t* hashes, uint8_t* small_out,
                    double* dct_out) {
   return fe_api(ctx, OnError::Capacity, [&]() -> int {
-    if (!mixed_list_ok(ctx->c, "fe_phash_mixed", (images && hashes) ? (const void*)images : nullptr, hw, n, order, images, 65536, 32768, false)) return FE_ERR_INVALID;
+    constexpr MixedLimits lim = {1, 65536, 32768, SIZE_MAX, nullptr};
+    if (!mixed_list_ok(ctx->c, "fe_phash_mixed", (images && hashes) ? images : nullptr, hw, n, order, images, lim)) return FE_ERR_INVALID;
     phash_mixed_run(ctx, images, hw, n, on_device, order, hashes, small_out, dct_out);
     return FE_OK;
   });
@@ -860,8 +794,7 @@ int fe_thumbnail_jpeg_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
   return fe_api(ctx, OnError::Capacity, [&]() -> int {
     Ctx& C = ctx->c;
     char b[240];
-    if (!mixed_list_ok(C, "fe_thumbnail_jpeg_mixed", (images && plans && out && lengths) ? (const void*)images : nullptr, hw, n, order, images, INT32_MAX,
-                       INT32_MAX, true))
+    if (!mixed_list_ok(C, "fe_thumbnail_jpeg_mixed", (images && plans && out && lengths) ? images : nullptr, hw, n, order, images, kAnySideBelow2_31))
       return FE_ERR_INVALID;
     if (quality < 1 || quality > 100) {
       snprintf(b, sizeof b, "fe_thumbnail_jpeg_mixed: quality %d (1 .. 100)", quality);
@@ -884,38 +817,20 @@ int fe_thumbnail_jpeg_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
     C.arena.reset();
     const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());
     const size_t mark = C.arena.mark();
-    // The arena budget of thumbnail_run. An image takes its output row and its scratch; when the chunk is done the scratch is dead and
-    // the gathered bytes (at most a row per image) take its place.
-    const size_t whole = std::min<size_t>((size_t)1 << 30, C.arena.capacity() - C.arena.capacity() / 8);
-    const size_t budget = whole > mark ? whole - mark : 0;
-    auto need = [&](int i) {
-      const size_t stage = on_device ? 0 : up256((size_t)hw[2 * i] * hw[2 * i + 1] * 3);
-      return dcap + std::max(thumb_mixed_scratch_bytes(descs[i]) + stage, dcap) + 4 * 256;
-    };
+    const std::vector<int> ends = thumb_mixed_cuts(descs.data(), n, !on_device, dcap, C.arena.capacity(), mark);
     std::vector<uint8_t> blob, packed;
     std::vector<int32_t> lens;
+    std::vector<size_t> offs;
     bool overflow = false;
-    for (int i0 = 0; i0 < n;) {
-      size_t used = 0;
-      int i1 = i0;
-      for (; i1 < n; ++i1) {
-        if (i1 > i0 && (used + need(i1) > budget || i1 - i0 >= 4096)) break;
-        used += need(i1);
-      }
+    int i0 = 0;
+    for (const int i1 : ends) {
       const int nb = i1 - i0;
       C.arena.rewind(mark);
       uint8_t* d_out = (uint8_t*)C.arena.alloc((size_t)nb * dcap);
       int32_t* d_len = (int32_t*)C.arena.alloc((size_t)nb * sizeof(int32_t));
       const size_t scratch = C.arena.mark();
-      for (int i = i0; i < i1; ++i) {
-        descs[i].src = images[i];
-        if (!on_device) {
-          const size_t bytes = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
-          uint8_t* d = (uint8_t*)C.arena.alloc(bytes);
-          FE_HIP(hipMemcpyAsync(d, images[i], bytes, hipMemcpyHostToDevice, C.stream));
-          descs[i].src = d;
-        }
-      }
+      uint8_t* d_stage = on_device ? nullptr : (uint8_t*)C.arena.alloc(mixed_list::staged_offsets(hw, i0, i1, true, offs));
+      stage_images(C, images, hw, i0, i1, on_device, d_stage, offs.data(), [&](int i, const uint8_t* src) { descs[i].src = src; });
       thumbnails_mixed_launch(C, descs.data() + i0, nb, d_pool, order == FE_ORDER_BGR, quality, blob, d_out, dcap, d_len);
       lens.resize(nb);
       FE_HIP(hipMemcpyAsync(lens.data(), d_len, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, C.stream));

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/facet_engine.h"
 #include "engine.h"
+#include "mixed_list.h"
 #include "onnx_graph.h"
 #include <algorithm>
 #include <cmath>
@@ -220,11 +221,19 @@ void download_nchw(Ctx& c, const TensorT<T>& t, int ch, float* y) {
   FE_HIP(hipStreamSynchronize(c.stream));
 }
 
-// ---- argument checks the mixed-size entry points share (capi_image.hip, capi_face.hip) ------------------------------------------------
-// What the mixed-size entry points check alike: the list, the order and every image's pointer and size. max_h / max_w: the entry point's
-// limits; below_2_31: h * w must stay below 2^31 as well. false: FE_ERR_INVALID with the message in the context.
-inline bool mixed_list_ok(Ctx& C, const char* who, const void* list, const int32_t* hw, int n, int order, const uint8_t* const* images, int max_h, int max_w,
-                   bool below_2_31) {
+// ---- the list front end of the mixed-size entry points: check, stage, refuse (mixed_list.h has the host half) ---------------------------
+// What an entry point accepts of an image: min_side <= h <= max_h, min_side <= w <= max_w, h * w <= max_pixels (`pixels` says that
+// bound in the message; nullptr: there is none).
+struct MixedLimits {
+  int min_side, max_h, max_w;
+  size_t max_pixels;
+  const char* pixels;
+};
+constexpr MixedLimits kAnySideBelow2_31 = {1, INT32_MAX, INT32_MAX, ((size_t)1 << 31) - 1, "below 2^31"};
+
+// What the mixed-size entry points check alike: the list (`list` is null when it or an output of the call is), the order and every
+// image's pointer and size. false: FE_ERR_INVALID with the message in the context.
+inline bool mixed_list_ok(Ctx& C, const char* who, const void* list, const int32_t* hw, int n, int order, const uint8_t* const* images, const MixedLimits& lim) {
   char b[240];
   if (!list || !hw || n <= 0) {
     snprintf(b, sizeof b, "%s: bad arguments (null list, null output or n <= 0)", who);
@@ -239,14 +248,36 @@ inline bool mixed_list_ok(Ctx& C, const char* who, const void* list, const int32
   for (int i = 0; i < n; ++i) {
     const int h = hw[2 * i], w = hw[2 * i + 1];
     if (!images[i]) { snprintf(b, sizeof b, "%s: image %d is a null pointer", who, i); C.err = b; return false; }
-    if (h < 1 || w < 1 || h > max_h || w > max_w || (below_2_31 && (size_t)h * (size_t)w >= ((size_t)1 << 31))) {
-      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h must be within 1 .. %d and w within 1 .. %d%s", who, i, h, w, max_h, max_w,
-               below_2_31 ? ", h * w below 2^31" : "");
+    if (h < lim.min_side || w < lim.min_side || h > lim.max_h || w > lim.max_w || (size_t)h * (size_t)w > lim.max_pixels) {
+      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); h must be within %d .. %d and w within %d .. %d%s%s", who, i, h, w, lim.min_side, lim.max_h,
+               lim.min_side, lim.max_w, lim.pixels ? ", h * w " : "", lim.pixels ? lim.pixels : "");
       C.err = b;
       return false;
     }
   }
   return true;
+}
+
+// Images [i0, i1) of the list where the kernels read them, handed to put(i, pointer): the caller's own pointer when the images are
+// resident; else the host images lie anywhere, so one copy each on the stream, to base + off[i - i0] (mixed_list::staged_offsets).
+template <class Put>
+void stage_images(Ctx& C, const uint8_t* const* images, const int32_t* hw, int i0, int i1, int on_device, uint8_t* base, const size_t* off, Put&& put) {
+  for (int i = i0; i < i1; ++i) {
+    const uint8_t* src = images[i];
+    if (!on_device) {
+      uint8_t* d = base + off[i - i0];
+      FE_HIP(hipMemcpyAsync(d, src, mixed_list::image_bytes(hw, i), hipMemcpyHostToDevice, C.stream));
+      src = d;
+    }
+    put(i, src);
+  }
+}
+
+// the FE_ERR_CAPACITY of an image whose own scratch exceeds the arena
+[[noreturn]] inline void throw_image_too_large(const char* who, int i, const int32_t* hw, size_t bytes, size_t capacity) {
+  char b[240];
+  snprintf(b, sizeof b, "%s: image %d (%d x %d) needs %zu bytes of scratch, the arena holds %zu", who, i, hw[2 * i], hw[2 * i + 1], bytes, capacity);
+  throw CapacityError(b);
 }
 
 // capi_graph.hip: the loaded graph of a slot, or an exception that names the slot

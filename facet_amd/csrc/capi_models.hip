@@ -433,21 +433,8 @@ struct ScopedTables {
   ~ScopedTables() { c.resize_scoped = nullptr; }
 };
 
-// Per-image argument checks of the mixed entry points. FE_OK, or FE_ERR_INVALID with the index of the offending image in the message.
-int mixed_check_images(fe_ctx* ctx, const char* what, const uint8_t* const* images, const int32_t* hw, int n, int min_side) {
-  char b[160];
-  if (!images || !hw || n <= 0) { ctx->c.err = std::string(what) + ": bad arguments (null list or n <= 0)"; return FE_ERR_INVALID; }
-  for (int i = 0; i < n; ++i) {
-    const int h = hw[2 * i], w = hw[2 * i + 1];
-    if (!images[i]) { snprintf(b, sizeof b, "%s: image %d is a null pointer", what, i); ctx->c.err = b; return FE_ERR_INVALID; }
-    if (h < min_side || w < min_side || (size_t)h * (size_t)w > ((size_t)1 << 28)) {
-      snprintf(b, sizeof b, "%s: image %d is %d x %d (h x w); each side must be at least %d", what, i, h, w, min_side);
-      ctx->c.err = b;
-      return FE_ERR_INVALID;
-    }
-  }
-  return FE_OK;
-}
+// what the mixed entry points here accept of an image, from a shortest side on: at most 2^28 pixels
+constexpr MixedLimits mixed_limits(int min_side) { return {min_side, INT32_MAX, INT32_MAX, (size_t)1 << 28, "at most 2^28"}; }
 
 // ensemble_run for images of mixed sizes: the same plan over cut_mixed's micro-batches (ensemble_plan.h), the 224^2 crops from the
 // descriptor-driven kernels (resize_mixed_core.h) straight into the batchers' slots. Descriptors, the table pool (LANCZOS tables of
@@ -990,7 +977,7 @@ int fe_ensemble_score_mixed(fe_ctx* ctx, const uint8_t* const* images, const int
   return fe_api(ctx, [&]() -> int {
     Ctx& C = ctx->c;
     if (!records) { C.err = "fe_ensemble_score_mixed: bad arguments (null records)"; return FE_ERR_INVALID; }
-    if (const int rc = mixed_check_images(ctx, "fe_ensemble_score_mixed", images, hw, n, 32)) return rc;
+    if (!mixed_list_ok(C, "fe_ensemble_score_mixed", images, hw, n, FE_ORDER_RGB, images, mixed_limits(32))) return FE_ERR_INVALID;
     const size_t floats = (size_t)n * FE_RECORD_FLOATS;
     if (floats > ctx->d_rec_cap) {
       if (ctx->d_rec) FE_HIP(hipFree(ctx->d_rec));
@@ -1012,14 +999,15 @@ int fe_preprocess224_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
   return fe_api(ctx, [&]() -> int {
     Ctx& C = ctx->c;
     if (!crops || (mode != FE_MIXED_CLIP && mode != FE_MIXED_SAMP)) { C.err = "fe_preprocess224_mixed: bad arguments (null crops, or mode not 0 / 1)"; return FE_ERR_INVALID; }
-    if (const int rc = mixed_check_images(ctx, "fe_preprocess224_mixed", images, hw, n, 1)) return rc;
+    if (!mixed_list_ok(C, "fe_preprocess224_mixed", images, hw, n, FE_ORDER_RGB, images, mixed_limits(1))) return FE_ERR_INVALID;
     const size_t crop_bytes = (size_t)kMixedSide * kMixedSide * 3;
+    std::vector<size_t> offs;
     for (int i0 = 0; i0 < n; i0 += ctx->microbatch) {
       const int nb = std::min(ctx->microbatch, n - i0);
       C.arena.reset();
       MixedTables tables;
       std::vector<MixedDesc> desc(nb);
-      size_t inter = 0, src_bytes = 0;
+      size_t inter = 0;
       int max_nr = 0;
       for (int j = 0; j < nb; ++j) {
         const int i = i0 + j;
@@ -1030,20 +1018,9 @@ int fe_preprocess224_mixed(fe_ctx* ctx, const uint8_t* const* images, const int3
         d.inter = (uint32_t)inter;
         inter += MixedTables::inter_bytes(d);
         if (d.ksize_h) max_nr = std::max(max_nr, (int)d.nr);
-        src_bytes += (size_t)d.h * d.w * 3;
       }
-      if (on_device) {
-        for (int j = 0; j < nb; ++j) desc[j].src = images[i0 + j];
-      } else {
-        uint8_t* d_src = (uint8_t*)C.arena.alloc(src_bytes);
-        size_t at = 0;
-        for (int j = 0; j < nb; ++j) {
-          const size_t b = (size_t)desc[j].h * desc[j].w * 3;
-          FE_HIP(hipMemcpyAsync(d_src + at, images[i0 + j], b, hipMemcpyHostToDevice, C.stream));
-          desc[j].src = d_src + at;
-          at += b;
-        }
-      }
+      uint8_t* d_src = on_device ? nullptr : (uint8_t*)C.arena.alloc(mixed_list::staged_offsets(hw, i0, i0 + nb, false, offs));
+      stage_images(C, images, hw, i0, i0 + nb, on_device, d_src, offs.data(), [&](int i, const uint8_t* src) { desc[i - i0].src = src; });
       if (tables.pool.empty()) tables.pool.push_back(0);      // every image 224 x 224: no pass, but the kernel still takes a pool
       const MixedDesc* d_desc = upload(C, desc.data(), desc.size());
       const int32_t* d_pool = upload(C, tables.pool.data(), tables.pool.size());

@@ -9,6 +9,7 @@
 // tile counts (`prefix`, n + 1 entries per tiling), then its tile inside the image from the remainder. One ImageDesc per image.
 // One arena allocation per chunk, carved by Layout; descriptors and prefix tables go up as one blob.
 #pragma once
+#include "mixed_list.h"
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -16,8 +17,8 @@
 namespace fe {
 namespace comp_plan {
 
-constexpr size_t kAlign = 256;                       // the arena's own alignment; every region starts on it
-constexpr size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+using mixed_list::kAlign;                            // the arena's own alignment; every region starts on it
+using mixed_list::align_up;
 constexpr size_t kMaxChunkPixels = ((size_t)1 << 31) - 1;      // pixel offsets and tile counts of a chunk stay below 2^31
 constexpr int kGrayRun = 8192;                       // pixels per workgroup of the subject call's gray + histogram pass
 constexpr int kWalkLanes = 64;                       // work-list entries per workgroup of the border walk
@@ -119,39 +120,28 @@ struct Plan {
 // no more pixels than this (an image alone may: h * w < 2^30 keeps it below kMaxChunkPixels)
 inline Plan build(const int32_t* hw, int n, bool staged, bool subject, size_t arena_bytes, size_t max_chunk_pixels = kMaxChunkPixels) {
   Plan plan;
-  Chunk cur;
-  auto open = [&](int first) {
-    cur = Chunk();
-    cur.first = first;
+  for (int i0 = 0; i0 < n;) {
+    Chunk cur;
+    cur.first = i0;
     for (auto& p : cur.prefix) p.assign(1, 0);
-  };
-  auto close = [&]() {
+    // the step: an image joins while the chunk's layout with it fits the arena and, behind the first, the pixel limit
+    const mixed_list::Cut c = mixed_list::cut_chunk(i0, n, [&](int i, int held, size_t& need) {
+      const int h = hw[2 * i], w = hw[2 * i + 1];
+      const size_t npx = (size_t)h * (size_t)w, cap = (size_t)work_cap(h, w);
+      need = layout((size_t)cur.count + 1, cur.pixels + npx, cur.work + cap, staged, subject).total;
+      if (need > arena_bytes || (held > 0 && cur.pixels + npx > max_chunk_pixels)) return false;
+      ++cur.count;
+      cur.descs.push_back(ImageDesc{nullptr, h, w, (uint32_t)cur.pixels, (uint32_t)cur.work, (int32_t)cap, 0});
+      for (int t = 0; t < kTilings; ++t) cur.prefix[t].push_back(cur.prefix[t].back() + tiles_of(t, h, w));
+      cur.pixels += npx;
+      cur.work += cap;
+      return true;
+    });
+    if (c.bad_image >= 0) return Plan{{}, c.bad_image, c.bad_bytes};
     cur.lay = layout((size_t)cur.count, cur.pixels, cur.work, staged, subject);
     plan.chunks.push_back(std::move(cur));
-  };
-  open(0);
-  for (int i = 0; i < n; ++i) {
-    const int h = hw[2 * i], w = hw[2 * i + 1];
-    const size_t npx = (size_t)h * (size_t)w, cap = (size_t)work_cap(h, w);
-    for (;;) {
-      const Layout L = layout((size_t)cur.count + 1, cur.pixels + npx, cur.work + cap, staged, subject);
-      if (L.total <= arena_bytes && (cur.count == 0 || cur.pixels + npx <= max_chunk_pixels)) break;
-      if (cur.count == 0) {
-        plan.chunks.clear();
-        plan.bad_image = i;
-        plan.bad_bytes = L.total;
-        return plan;
-      }
-      close();
-      open(i);
-    }
-    ++cur.count;
-    cur.descs.push_back(ImageDesc{nullptr, h, w, (uint32_t)cur.pixels, (uint32_t)cur.work, (int32_t)cap, 0});
-    for (int t = 0; t < kTilings; ++t) cur.prefix[t].push_back(cur.prefix[t].back() + tiles_of(t, h, w));
-    cur.pixels += npx;
-    cur.work += cap;
+    i0 = c.end;
   }
-  if (cur.count) close();
   return plan;
 }
 

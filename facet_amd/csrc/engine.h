@@ -243,7 +243,6 @@ bool face_thumbnails_mixed(Ctx& c, const face_plan::ImageDesc* d_imgs, int rgb, 
 // and encode, one launch per stage. descs [n] host descriptors with device sources; their buffers and every scratch array come from the
 // arena (the caller rewinds); host_blob must outlive the stream's work. d_out [n][cap] / d_lengths [n] as launch_jpeg_encode leaves them.
 struct ThumbDesc;
-size_t thumb_mixed_scratch_bytes(const ThumbDesc& d);
 void thumbnails_mixed_launch(Ctx& c, ThumbDesc* descs, int n, const int32_t* d_pool, int bgr, int quality, std::vector<uint8_t>& host_blob,
                              uint8_t* d_out, size_t cap, int32_t* d_lengths);
 // the bytes of every row that fitted (0 < length <= cap), back to back in row order, into d_packed; max_len: the longest of them

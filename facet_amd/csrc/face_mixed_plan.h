@@ -11,6 +11,7 @@
 // A list is walked in input order in micro-batches of at most `max_images`; with host input a micro-batch also ends before the image
 // whose staged bytes (each image on a 256-byte boundary) would pass `stage_room`.
 #pragma once
+#include "mixed_list.h"
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -21,8 +22,8 @@ namespace fe {
 namespace face_plan {
 
 enum Mode : int32_t { kResize = 0, kBox2 = 1, kCopy = 2 };
-constexpr size_t kAlign = 256;      // the arena's alignment; every staged image starts on it
-constexpr size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+using mixed_list::kAlign;           // the arena's alignment; every staged image starts on it
+using mixed_list::align_up;
 constexpr size_t staged_bytes(int h, int w) { return align_up((size_t)h * (size_t)w * 3); }
 
 // what the kernels read, in device memory. The calls that do not run the detector (crops, ROIs, thumbnails) fill src, h and w only.
@@ -80,28 +81,39 @@ inline bool describe(const int32_t* hw, int i, int det_h, int det_w, TablePool& 
   return true;
 }
 
-// The first image of the list whose staged bytes alone exceed stage_room, or -1. Resident input stages nothing.
-inline int too_large(const int32_t* hw, int n, bool staged, size_t stage_room) {
-  if (!staged) return -1;
-  for (int i = 0; i < n; ++i)
-    if (staged_bytes(hw[2 * i], hw[2 * i + 1]) > stage_room) return i;
-  return -1;
+// The micro-batch that starts at image i0: at most max_images images and, staged, at most stage_room bytes (*bytes, nullable, receives
+// their sum). bad_image: image i0's staged bytes alone exceed stage_room.
+inline mixed_list::Cut chunk(const int32_t* hw, int n, int i0, int max_images, bool staged, size_t stage_room, size_t* bytes) {
+  size_t used = 0;
+  const mixed_list::Cut c = mixed_list::cut_chunk(i0, n, [&](int i, int held, size_t& need) {
+    need = staged ? staged_bytes(hw[2 * i], hw[2 * i + 1]) : 0;
+    if (held >= max_images || used + need > stage_room) return false;
+    used += need;
+    return true;
+  });
+  if (bytes) *bytes = used;
+  return c;
 }
 
-// The micro-batch that starts at image i0: its end i1 (i0 < i1 <= n), at most max_images images and, staged, at most stage_room bytes.
-// offsets (nullable) receives the byte offset of every image of the micro-batch inside the stage region, *bytes (nullable) their sum.
-// Every image must pass too_large() first: then a micro-batch holds at least one image.
-inline int cut(const int32_t* hw, int n, int i0, int max_images, bool staged, size_t stage_room, std::vector<size_t>* offsets, size_t* bytes) {
-  size_t used = 0;
-  int i1 = i0;
-  if (offsets) offsets->clear();
-  for (; i1 < n && i1 - i0 < max_images; ++i1) {
-    const size_t b = staged ? staged_bytes(hw[2 * i1], hw[2 * i1 + 1]) : 0;
-    if (i1 > i0 && used + b > stage_room) break;
-    if (offsets) offsets->push_back(used);
-    used += b;
+// The first image of the list whose staged bytes alone exceed stage_room, or -1. Resident input stages nothing.
+inline int too_large(const int32_t* hw, int n, bool staged, size_t stage_room) {
+  int bad = -1;
+  for (int i0 = 0; staged && bad < 0 && i0 < n;) {
+    const mixed_list::Cut c = chunk(hw, n, i0, n, staged, stage_room, nullptr);
+    bad = c.bad_image;
+    i0 = c.end;
   }
-  if (bytes) *bytes = used;
+  return bad;
+}
+
+// The end i1 of the micro-batch that starts at image i0 (i0 < i1 <= n). offsets (nullable) receives the byte offset of every image of
+// the micro-batch inside the stage region. Every image must pass too_large() first: then a micro-batch holds at least one image.
+inline int cut(const int32_t* hw, int n, int i0, int max_images, bool staged, size_t stage_room, std::vector<size_t>* offsets, size_t* bytes) {
+  const int i1 = chunk(hw, n, i0, max_images, staged, stage_room, bytes).end;
+  if (offsets) {
+    if (staged) mixed_list::staged_offsets(hw, i0, i1, true, *offsets);
+    else offsets->assign((size_t)(i1 - i0), 0);
+  }
   return i1;
 }
 

@@ -425,14 +425,8 @@ __global__ __launch_bounds__(TM_THREADS) void jpeg_gather_kernel(const uint8_t* 
   for (size_t i = (size_t)blockIdx.x * TM_THREADS + threadIdx.x; i < (size_t)len; i += (size_t)gridDim.x * TM_THREADS) packed[off + i] = src[i];
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// arena bytes the stages of one described image take besides its output row (thumbnails_mixed_launch carves exactly these)
-size_t thumb_mixed_scratch_bytes(const ThumbDesc& d) {
-  const Geom g = make_geom(d.oh, d.ow);
-  return align256(ThumbTables::red_bytes(d)) + align256(ThumbTables::mid_bytes(d)) + align256(ThumbTables::pix_bytes(d)) + (size_t)g.nblk * (128 + 8) +
-         (size_t)jpeg_bitbuf_words(g) * 4 + sizeof(ThumbDesc) + sizeof(JpegItem) + 8;
-}
+// thumb_mixed_scratch_bytes (thumb_mixed_core.h) counts what thumbnails_mixed_launch carves from the arena per image
+static_assert(sizeof(JpegItem) == kThumbItemBytes && (BLOCK_MAX_BITS + 7) / 8 == kThumbBlockCodeBytes, "thumb_mixed_core.h restates both");
 
 // One chunk of fe_thumbnail_jpeg_mixed. descs [n]: host descriptors whose src is device memory; their three buffers are carved from the
 // arena here, with everything else the stages need (the caller rewinds). host_blob: the descriptors as uploaded - the caller keeps it
@@ -462,7 +456,7 @@ void thumbnails_mixed_launch(Ctx& c, ThumbDesc* descs, int n, const int32_t* d_p
     blocks += (size_t)g.nblk; words += it.wcap;
     max_nblk = std::max(max_nblk, g.nblk);
   }
-  const size_t desc_b = align256((size_t)n * sizeof(ThumbDesc));
+  const size_t desc_b = mixed_list::align_up((size_t)n * sizeof(ThumbDesc));
   host_blob.resize(desc_b + (size_t)n * sizeof(JpegItem));
   memcpy(host_blob.data(), descs, (size_t)n * sizeof(ThumbDesc));
   memcpy(host_blob.data() + desc_b, items.data(), (size_t)n * sizeof(JpegItem));

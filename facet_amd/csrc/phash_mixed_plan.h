@@ -7,10 +7,9 @@
 // single-tap identity when the side is already 32 (PIL skips that pass; a tap of 1.0 reproduces a byte exactly). Descriptors address it
 // by int32 offsets, two images with a side in common share a table, and nothing is cached per size.
 #pragma once
-#include "resize_coeffs.h"
+#include "mixed_list.h"
 #include <cstddef>
 #include <cstdint>
-#include <map>
 #include <vector>
 
 namespace fe {
@@ -32,39 +31,12 @@ struct PhashDesc {          // 64 bytes
   int32_t tall;
 };
 
-class PhashTables {
+class PhashTables : public mixed_list::PilTablePool {
  public:
-  std::vector<int32_t> pool;
-  size_t tables() const { return seen_.size(); }
-
   // the table of an axis of `in` samples; false: a window leaves the axis or the pool outgrows int32 offsets
   bool table(int in, int32_t& k_off, int32_t& b_off, int32_t& ksize) {
-    auto it = seen_.find(in);
-    if (it == seen_.end()) {
-      std::vector<int> kk, bounds;
-      int ks;
-      if (in == kPhashSide) {
-        ks = 1;
-        kk.assign(kPhashSide, 1 << kResizePrecisionBits);
-        bounds.resize(2 * kPhashSide);
-        for (int i = 0; i < kPhashSide; ++i) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; }
-      } else {
-        ks = pil_resize_coeffs(in, 0.0f, (float)in, kPhashSide, kFilterLanczos, kk, bounds);
-      }
-      if (ks <= 0) return false;
-      for (int i = 0; i < kPhashSide; ++i)
-        if (bounds[2 * i] < 0 || bounds[2 * i + 1] < 0 || bounds[2 * i + 1] > ks || bounds[2 * i] + bounds[2 * i + 1] > in) return false;
-      if (pool.size() + (size_t)kPhashSide * (ks + 2) > (size_t)INT32_MAX) return false;
-      Entry e;
-      e.ksize = ks;
-      e.k = (int32_t)pool.size();
-      pool.insert(pool.end(), kk.begin(), kk.end());
-      e.b = (int32_t)pool.size();
-      pool.insert(pool.end(), bounds.begin(), bounds.end());
-      it = seen_.emplace(in, e).first;
-    }
-    k_off = it->second.k; b_off = it->second.b; ksize = it->second.ksize;
-    return true;
+    if (in == kPhashSide) return add_identity(kPhashSide, k_off, b_off, ksize);
+    return add(in, 0.0f, (float)in, kPhashSide, kFilterLanczos, 0, kPhashSide, k_off, b_off, ksize);
   }
   // both tables of an h x w image; src and first_row are the caller's
   bool describe(int h, int w, PhashDesc& d) {
@@ -75,10 +47,28 @@ class PhashTables {
     if (!d.tall) return table(h, d.kv, d.bv, d.ksize_v);
     return table(h, d.kt, d.bt, d.ksize_t) && table(kPhashSide, d.kv, d.bv, d.ksize_v);
   }
-
- private:
-  struct Entry { int32_t k, b, ksize; };
-  std::map<int, Entry> seen_;
 };
+
+// ---- the arena chunks of fe_phash_mixed ------------------------------------------------------------------------------------------
+// what an image takes of a chunk besides the pool: its rows of tmp, its descriptor and outputs and, from the host, its staged pixels
+inline size_t phash_need(int h, int w, bool small, bool dct, bool staged) {
+  return (size_t)phash_tmp_rows(h, w) * kPhashSide + sizeof(PhashDesc) + sizeof(uint64_t) + (small ? 1024 : 0) + (dct ? 64 * sizeof(double) : 0) +
+         (staged ? mixed_list::align_up((size_t)h * (size_t)w * 3) : 0);
+}
+// A chunk holds what fits the arena beside the pool (and 8 alignments of slack for the chunk's allocations), at most 2^30 rows of tmp and
+// 65535 images. The ends of the chunks, or the image whose own need exceeds the arena.
+inline mixed_list::Cuts phash_cuts(const int32_t* hw, int n, bool small, bool dct, bool staged, size_t pool_words, size_t arena_bytes) {
+  const size_t fixed = mixed_list::align_up(pool_words * sizeof(int32_t)) + 8 * mixed_list::kAlign;
+  const size_t room = arena_bytes > fixed ? arena_bytes - fixed : 0;
+  size_t used = 0, rows = 0;
+  return mixed_list::cut_list(n, [&](int) { used = rows = 0; }, [&](int i, int held, size_t& need) {
+    const size_t b = phash_need(hw[2 * i], hw[2 * i + 1], small, dct, staged), r = (size_t)phash_tmp_rows(hw[2 * i], hw[2 * i + 1]);
+    need = b + fixed;
+    if (held == 0 ? b > room : (used + b > room || rows + r > ((size_t)1 << 30) || held >= 65535)) return false;
+    used += b;
+    rows += r;
+    return true;
+  });
+}
 
 }  // namespace fe

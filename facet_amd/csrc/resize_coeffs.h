@@ -2,11 +2,23 @@
 // engine (kernels_resize.hip, the mixed-size path) and the CPU harnesses under tests/native build their tables from this one function.
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <vector>
+
+#ifdef __HIPCC__
+#define FE_RHD __host__ __device__ __forceinline__
+#else
+#define FE_RHD inline
+#endif
 
 namespace fe {
 
 constexpr int kResizePrecisionBits = 32 - 8 - 2;
+// Resample.c's clip8: a fixed-point accumulator (started at 1 << 21) back to a byte; what every resampling kernel and harness ends with
+FE_RHD uint8_t pil_clip8(int v) {
+  v >>= kResizePrecisionBits;
+  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
 // the PIL filters by their FE_FILTER_* numbers (include/facet_engine.h)
 constexpr int kFilterLanczos = 1, kFilterBilinear = 2, kFilterBicubic = 3;
 

@@ -14,6 +14,7 @@
 // 224 x ksize coefficients and one of 224 x 2 bounds. Descriptors address it by int32 offsets, so the pool can live anywhere in
 // call-scoped memory and nothing is cached per size.
 #pragma once
+#include "resize_coeffs.h"
 #include <stddef.h>
 #include <stdint.h>
 
@@ -27,7 +28,6 @@
 namespace fe {
 
 constexpr int kMixedSide = 224;
-constexpr int kMixedBits = 32 - 8 - 2;
 enum MixedMode : int { MIXED_CLIP = 0, MIXED_SAMP = 1 };
 
 struct MixedDesc {          // 72 bytes
@@ -42,22 +42,17 @@ struct MixedDesc {          // 72 bytes
   int32_t slot;             // crop slot of the launch's output this image goes to
 };
 
-FE_MHD uint8_t mixed_clip8(int v) {
-  v >>= kMixedBits;
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // Horizontal pass: intermediate row r (source row r0 + r), crop column xx.
 FE_MHD void mixed_h_sample(const MixedDesc& d, const int32_t* pool, int r, int xx, uint8_t out[3]) {
   const int xmin = pool[d.bh + xx * 2], xmax = pool[d.bh + xx * 2 + 1];
   const int32_t* k = pool + d.kh + (size_t)xx * d.ksize_h;
   const uint8_t* p = d.src + ((size_t)(d.r0 + r) * d.w + xmin) * 3;
-  int s0 = 1 << (kMixedBits - 1), s1 = s0, s2 = s0;
+  int s0 = 1 << (kResizePrecisionBits - 1), s1 = s0, s2 = s0;
   for (int x = 0; x < xmax; ++x) {
     const int c = k[x];
     s0 += p[x * 3 + 0] * c; s1 += p[x * 3 + 1] * c; s2 += p[x * 3 + 2] * c;
   }
-  out[0] = mixed_clip8(s0); out[1] = mixed_clip8(s1); out[2] = mixed_clip8(s2);
+  out[0] = pil_clip8(s0); out[1] = pil_clip8(s1); out[2] = pil_clip8(s2);
 }
 
 // Vertical pass: crop pixel (yy, x). inter = this image's intermediate; read only when there was a horizontal pass, else the source
@@ -76,13 +71,13 @@ FE_MHD void mixed_v_sample(const MixedDesc& d, const int32_t* pool, const uint8_
   const int ymin = pool[d.bv + yy * 2], ymax = pool[d.bv + yy * 2 + 1];
   const int32_t* k = pool + d.kv + (size_t)yy * d.ksize_v;
   const uint8_t* p = base + (size_t)(ymin - row0) * stride;
-  int s0 = 1 << (kMixedBits - 1), s1 = s0, s2 = s0;
+  int s0 = 1 << (kResizePrecisionBits - 1), s1 = s0, s2 = s0;
   for (int y = 0; y < ymax; ++y) {
     const int c = k[y];
     const uint8_t* q = p + (size_t)y * stride;
     s0 += q[0] * c; s1 += q[1] * c; s2 += q[2] * c;
   }
-  out[0] = mixed_clip8(s0); out[1] = mixed_clip8(s1); out[2] = mixed_clip8(s2);
+  out[0] = pil_clip8(s0); out[1] = pil_clip8(s1); out[2] = pil_clip8(s2);
 }
 
 // launch_u8_to_nhwc4_norm's arithmetic on one sample
@@ -91,10 +86,8 @@ FE_MHD float mixed_norm(uint8_t v, float mean, float stdv) { return ((float)v / 
 }  // namespace fe
 
 // ---- host side: descriptors and the table pool ------------------------------------------------------------------------------------
-#include "resize_coeffs.h"
+#include "mixed_list.h"
 #include <algorithm>
-#include <map>
-#include <tuple>
 #include <vector>
 
 namespace fe {
@@ -109,10 +102,8 @@ inline int mixed_round_half_even(double v) {
 
 // Builds the descriptors and the table pool of one call on the host. Tables are shared between images: a second image of a shape adds
 // nothing to the pool.
-class MixedTables {
+class MixedTables : public mixed_list::PilTablePool {
  public:
-  std::vector<int32_t> pool;
-
   // Geometry and tables of an h x w image under `mode`; src / inter / slot are the caller's. false: a size the path does not take.
   bool describe(int mode, int h, int w, MixedDesc& d) {
     if (h < 1 || w < 1 || (mode != MIXED_CLIP && mode != MIXED_SAMP)) return false;
@@ -124,9 +115,9 @@ class MixedTables {
       d.y0 = mixed_round_half_even((d.oh - kMixedSide) / 2.0);
       d.x0 = mixed_round_half_even((d.ow - kMixedSide) / 2.0);
     }
-    if (d.ow != w && !table(w, d.ow, filter, d.x0, d.kh, d.bh, d.ksize_h)) return false;
+    if (d.ow != w && !add(w, 0.0f, (float)w, d.ow, filter, d.x0, kMixedSide, d.kh, d.bh, d.ksize_h)) return false;
     if (d.oh != h) {
-      if (!table(h, d.oh, filter, d.y0, d.kv, d.bv, d.ksize_v)) return false;
+      if (!add(h, 0.0f, (float)h, d.oh, filter, d.y0, kMixedSide, d.kv, d.bv, d.ksize_v)) return false;
       const int32_t* b = pool.data() + d.bv;
       int lo = b[0], hi = b[0] + b[1];
       for (int yy = 1; yy < kMixedSide; ++yy) { lo = std::min(lo, b[yy * 2]); hi = std::max(hi, b[yy * 2] + b[yy * 2 + 1]); }
@@ -137,32 +128,6 @@ class MixedTables {
     return d.r0 >= 0 && d.nr >= 1 && d.r0 + d.nr <= h && d.x0 >= 0 && d.x0 + kMixedSide <= d.ow && d.y0 >= 0 && d.y0 + kMixedSide <= d.oh;
   }
   static size_t inter_bytes(const MixedDesc& d) { return d.ksize_h ? (size_t)d.nr * kMixedSide * 3 : 0; }
-
- private:
-  // the 224 output samples from `first` on of the in -> out table; every window is checked against the axis
-  bool table(int in, int out, int filter, int first, int32_t& k_off, int32_t& b_off, int32_t& ksize) {
-    const auto key = std::make_tuple(in, out, filter, first);
-    auto it = seen_.find(key);
-    if (it == seen_.end()) {
-      std::vector<int> kk, bounds;
-      const int ks = pil_resize_coeffs(in, 0.0f, (float)in, out, filter, kk, bounds);
-      if (ks <= 0 || first < 0 || first + kMixedSide > out) return false;
-      for (int i = first; i < first + kMixedSide; ++i)
-        if (bounds[i * 2] < 0 || bounds[i * 2 + 1] < 0 || bounds[i * 2 + 1] > ks || bounds[i * 2] + bounds[i * 2 + 1] > in) return false;
-      if (pool.size() + (size_t)kMixedSide * (ks + 2) > (size_t)INT32_MAX) return false;
-      Entry e;
-      e.ksize = ks;
-      e.k = (int32_t)pool.size();
-      pool.insert(pool.end(), kk.begin() + (size_t)first * ks, kk.begin() + (size_t)(first + kMixedSide) * ks);
-      e.b = (int32_t)pool.size();
-      pool.insert(pool.end(), bounds.begin() + (size_t)first * 2, bounds.begin() + (size_t)(first + kMixedSide) * 2);
-      it = seen_.emplace(key, e).first;
-    }
-    k_off = it->second.k; b_off = it->second.b; ksize = it->second.ksize;
-    return true;
-  }
-  struct Entry { int32_t k, b, ksize; };
-  std::map<std::tuple<int, int, int, int>, Entry> seen_;
 };
 
 }  // namespace fe

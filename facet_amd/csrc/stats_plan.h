@@ -9,6 +9,7 @@
 // One arena allocation per chunk, carved by Layout: the zeroed block (accumulators, then the per-image 180 x 256 hue-saturation
 // histograms) first, then the records, the descriptor blob (one upload), the gray planes and, for host input, the staged pixels.
 #pragma once
+#include "mixed_list.h"
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -27,7 +28,8 @@ constexpr int kHistBins = 180 * 256;          // uint32 counts per image, both h
 constexpr size_t kHistBytes = (size_t)kHistBins * 4;
 constexpr size_t kAccumBytes = 1072;          // sizeof(StatsAccum), asserted in kernels_stats.hip
 constexpr size_t kRecordBytes = 264 * 8;      // FE_STATS_DOUBLES doubles
-constexpr size_t kAlign = 256;                // the arena's own alignment; every region and every image's planes start on it
+using mixed_list::kAlign;                     // the arena's own alignment; every region and every image's planes start on it
+using mixed_list::align_up;
 
 // what the kernels read, in device memory; `img` counts from the chunk's first image
 struct ImageDesc { const uint8_t* src; uint8_t* gray; int32_t h, w, nseg, pad; };
@@ -37,8 +39,6 @@ struct StripDesc { int32_t img, y0; };                                   // rows
 // pass 1 launches 2 * segments workgroups: workgroup b works on segment b / 2 for hue half b % 2 (hue [0, 90) and [90, 180))
 constexpr int pass1_segment(unsigned block) { return (int)(block >> 1); }
 constexpr int pass1_half(unsigned block) { return (int)(block & 1); }
-
-constexpr size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
 // byte offsets of a chunk's regions inside its one allocation
 struct Layout {
@@ -91,47 +91,39 @@ inline size_t strips_of(int h) { return ((size_t)h + kStripRows - 1) / kStripRow
 // arena as well (host input)
 inline Plan build(const int32_t* hw, int n, bool staged, int segment_pixels, size_t arena_bytes) {
   Plan plan;
-  Chunk cur;
-  size_t segs = 0, strips = 0;
-  auto close = [&]() {
+  for (int i0 = 0; i0 < n;) {
+    Chunk cur;
+    size_t segs = 0, strips = 0;
+    cur.first = i0;
+    // the step: an image joins while the chunk's layout with it fits the arena
+    const mixed_list::Cut c = mixed_list::cut_chunk(i0, n, [&](int i, int, size_t& need) {
+      const int h = hw[2 * i], w = hw[2 * i + 1];
+      const size_t npx = (size_t)h * (size_t)w;
+      const size_t s = detail::segments_of(npx, segment_pixels), r = detail::strips_of(h);
+      const size_t g = align_up(npx), st = staged ? align_up(npx * 3) : 0;
+      need = layout((size_t)cur.count + 1, segs + s, strips + r, cur.multi.size() + (s > 1 ? 1 : 0), cur.gray_bytes + g, cur.stage_bytes + st).total;
+      if (need > arena_bytes) return false;
+      const int32_t k = cur.count++;
+      cur.gray_off.push_back(cur.gray_bytes);
+      cur.stage_off.push_back(cur.stage_bytes);
+      cur.gray_bytes += g;
+      cur.stage_bytes += st;
+      cur.nseg.push_back((int32_t)s);
+      for (size_t q = 0; q < s; ++q) {
+        const size_t p0 = q * (size_t)segment_pixels, left = npx - p0;
+        cur.segs.push_back(SegDesc{k, (uint32_t)p0, (uint32_t)(left < (size_t)segment_pixels ? left : (size_t)segment_pixels), (int32_t)q});
+      }
+      for (size_t q = 0; q < r; ++q) cur.strips.push_back(StripDesc{k, (int32_t)(q * kStripRows)});
+      if (s > 1) cur.multi.push_back(k);
+      segs += s;
+      strips += r;
+      return true;
+    });
+    if (c.bad_image >= 0) return Plan{{}, c.bad_image, c.bad_bytes};
     cur.lay = layout((size_t)cur.count, segs, strips, cur.multi.size(), cur.gray_bytes, cur.stage_bytes);
     plan.chunks.push_back(std::move(cur));
-    cur = Chunk();
-    segs = strips = 0;
-  };
-  for (int i = 0; i < n; ++i) {
-    const int h = hw[2 * i], w = hw[2 * i + 1];
-    const size_t npx = (size_t)h * (size_t)w;
-    const size_t s = detail::segments_of(npx, segment_pixels), r = detail::strips_of(h);
-    const size_t g = align_up(npx), st = staged ? align_up(npx * 3) : 0;
-    for (;;) {
-      const Layout L = layout((size_t)cur.count + 1, segs + s, strips + r, cur.multi.size() + (s > 1 ? 1 : 0), cur.gray_bytes + g, cur.stage_bytes + st);
-      if (L.total <= arena_bytes) break;
-      if (cur.count == 0) {
-        plan.chunks.clear();
-        plan.bad_image = i;
-        plan.bad_bytes = L.total;
-        return plan;
-      }
-      close();
-    }
-    if (cur.count == 0) cur.first = i;
-    const int32_t k = cur.count++;
-    cur.gray_off.push_back(cur.gray_bytes);
-    cur.stage_off.push_back(cur.stage_bytes);
-    cur.gray_bytes += g;
-    cur.stage_bytes += st;
-    cur.nseg.push_back((int32_t)s);
-    for (size_t q = 0; q < s; ++q) {
-      const size_t p0 = q * (size_t)segment_pixels, left = npx - p0;
-      cur.segs.push_back(SegDesc{k, (uint32_t)p0, (uint32_t)(left < (size_t)segment_pixels ? left : (size_t)segment_pixels), (int32_t)q});
-    }
-    for (size_t q = 0; q < r; ++q) cur.strips.push_back(StripDesc{k, (int32_t)(q * kStripRows)});
-    if (s > 1) cur.multi.push_back(k);
-    segs += s;
-    strips += r;
+    i0 = c.end;
   }
-  if (cur.count) close();
   return plan;
 }
 

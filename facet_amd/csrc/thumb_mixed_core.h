@@ -11,6 +11,7 @@
 // coefficients and one of out x 2 bounds. Descriptors address it by int32 offsets, so the pool lives in call-scoped memory and nothing
 // is cached per size.
 #pragma once
+#include "resize_coeffs.h"
 #include <stddef.h>
 #include <stdint.h>
 
@@ -22,8 +23,6 @@
 #endif
 
 namespace fe {
-
-constexpr int kThumbBits = 32 - 8 - 2;
 
 struct ThumbPass {          // one resampling pass over one axis; ksize = 0: skipped
   int32_t vertical;         // 0: along the rows (output oh = ih), 1: along the columns (output ow = iw)
@@ -70,11 +69,6 @@ FE_THD void thumb_reduce_sample(const ThumbDesc& d, int y, int x, uint8_t out[3]
   pil_reduce_pixel(d.src + ((size_t)(d.y0 + ys) * d.w + (d.x0 + xs)) * 3, (size_t)d.w * 3, nx, ny, mult, out);
 }
 
-FE_THD uint8_t thumb_clip8(int v) {
-  v >>= kThumbBits;
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // Output pixel (oy, ox) of a pass over `in` [ih][iw][3]
 FE_THD void thumb_pass_sample(const ThumbPass& p, const int32_t* pool, const uint8_t* in, int oy, int ox, uint8_t out[3]) {
   const int o = p.vertical ? oy : ox;
@@ -82,22 +76,20 @@ FE_THD void thumb_pass_sample(const ThumbPass& p, const int32_t* pool, const uin
   const int32_t* k = pool + p.k + (size_t)o * p.ksize;
   const uint8_t* q = p.vertical ? in + ((size_t)first * p.iw + ox) * 3 : in + ((size_t)oy * p.iw + first) * 3;
   const size_t stride = p.vertical ? (size_t)p.iw * 3 : 3;
-  int s0 = 1 << (kThumbBits - 1), s1 = s0, s2 = s0;
+  int s0 = 1 << (kResizePrecisionBits - 1), s1 = s0, s2 = s0;
   for (int t = 0; t < count; ++t) {
     const int c = k[t];
     s0 += q[0] * c; s1 += q[1] * c; s2 += q[2] * c;
     q += stride;
   }
-  out[0] = thumb_clip8(s0); out[1] = thumb_clip8(s1); out[2] = thumb_clip8(s2);
+  out[0] = pil_clip8(s0); out[1] = pil_clip8(s1); out[2] = pil_clip8(s2);
 }
 
 }  // namespace fe
 
 // ---- host side: descriptors and the table pool ------------------------------------------------------------------------------------
-#include "resize_coeffs.h"
-#include <cstring>
-#include <map>
-#include <tuple>
+#include "mixed_list.h"
+#include <algorithm>
 #include <vector>
 
 namespace fe {
@@ -107,11 +99,8 @@ inline uint32_t pil_reduce_multiplier(int count) { return (uint32_t)(4294967296.
 
 // Builds the descriptors and the table pool of one call on the host. Tables are shared between images: a second image with the same
 // (input size, box, output size) on an axis adds nothing to the pool.
-class ThumbTables {
+class ThumbTables : public mixed_list::PilTablePool {
  public:
-  std::vector<int32_t> pool;
-  size_t tables() const { return seen_.size(); }
-
   // Geometry and tables of an h x w image under the plan of facet_amd.thumbnail.thumbnail_plan (fe_thumb_plan's fields); src and the
   // three buffers are the caller's. nullptr: described; otherwise what is wrong with the plan.
   const char* describe(int h, int w, int oh, int ow, int fx, int fy, const int32_t rbox[4], const float box[4], int tall, ThumbDesc& d) {
@@ -137,8 +126,8 @@ class ThumbTables {
     // Image.resize's two calls for a tall image: rows first, over all rw columns, then columns over the oh rows that gave
     ThumbPass hp = {0, tall ? oh : rh, rw, tall ? oh : rh, ow, 0, 0, 0};
     ThumbPass vp = {1, rh, tall ? rw : ow, oh, tall ? rw : ow, 0, 0, 0};
-    if (need_h && !table(rw, box[0], box[2], ow, hp.k, hp.b, hp.ksize)) return "a horizontal coefficient window leaves the axis";
-    if (need_v && !table(rh, box[1], box[3], oh, vp.k, vp.b, vp.ksize)) return "a vertical coefficient window leaves the axis";
+    if (need_h && !add(rw, box[0], box[2], ow, kFilterLanczos, 0, ow, hp.k, hp.b, hp.ksize)) return "a horizontal coefficient window leaves the axis";
+    if (need_v && !add(rh, box[1], box[3], oh, kFilterLanczos, 0, oh, vp.k, vp.b, vp.ksize)) return "a vertical coefficient window leaves the axis";
     if (!need_v) { hp.ih = hp.oh = rh; }      // oh == rh then
     if (!need_h) { vp.iw = vp.ow = rw; }      // ow == rw then
     d.pass[0] = tall ? vp : hp;
@@ -149,34 +138,35 @@ class ThumbTables {
   static size_t red_bytes(const ThumbDesc& d) { return thumb_reduces(d) ? (size_t)d.rh * d.rw * 3 : 0; }
   static size_t mid_bytes(const ThumbDesc& d) { return (d.pass[0].ksize && d.pass[1].ksize) ? (size_t)d.pass[0].oh * d.pass[0].ow * 3 : 0; }
   static size_t pix_bytes(const ThumbDesc& d) { return (d.pass[0].ksize || d.pass[1].ksize) ? (size_t)d.oh * d.ow * 3 : 0; }
-
- private:
-  // build_resize_coeffs(in, in0, in1, out, LANCZOS), every window checked against the axis
-  bool table(int in, float in0, float in1, int out, int32_t& k_off, int32_t& b_off, int32_t& ksize) {
-    uint32_t b0, b1;
-    memcpy(&b0, &in0, 4); memcpy(&b1, &in1, 4);
-    const auto key = std::make_tuple(in, b0, b1, out);
-    auto it = seen_.find(key);
-    if (it == seen_.end()) {
-      std::vector<int> kk, bounds;
-      const int ks = pil_resize_coeffs(in, in0, in1, out, kFilterLanczos, kk, bounds);
-      if (ks <= 0) return false;
-      for (int i = 0; i < out; ++i)
-        if (bounds[i * 2] < 0 || bounds[i * 2 + 1] < 0 || bounds[i * 2 + 1] > ks || bounds[i * 2] + bounds[i * 2 + 1] > in) return false;
-      if (pool.size() + (size_t)out * (ks + 2) > (size_t)INT32_MAX) return false;
-      Entry e;
-      e.ksize = ks;
-      e.k = (int32_t)pool.size();
-      pool.insert(pool.end(), kk.begin(), kk.end());
-      e.b = (int32_t)pool.size();
-      pool.insert(pool.end(), bounds.begin(), bounds.end());
-      it = seen_.emplace(key, e).first;
-    }
-    k_off = it->second.k; b_off = it->second.b; ksize = it->second.ksize;
-    return true;
-  }
-  struct Entry { int32_t k, b, ksize; };
-  std::map<std::tuple<int, uint32_t, uint32_t, int>, Entry> seen_;
 };
+
+// ---- the arena chunks of fe_thumbnail_jpeg_mixed ---------------------------------------------------------------------------------
+// What the encoder takes per image, restated from jpeg_core.h so that this header stays free of it (kernels_jpeg.hip asserts the two
+// constants): 6 blocks per 16 x 16 MCU, and per block 128 + 8 bytes of coefficients, bit length and offset plus its longest code in the
+// bit buffer (a multiple of 16 bytes per image).
+constexpr size_t kThumbItemBytes = 40, kThumbBlockCodeBytes = 208;      // sizeof(JpegItem), (BLOCK_MAX_BITS + 7) / 8
+inline size_t thumb_jpeg_blocks(int oh, int ow) { return 6 * (size_t)((ow + 15) / 16) * (size_t)((oh + 15) / 16); }
+// what thumbnails_mixed_launch carves from the arena for one image besides its output row
+inline size_t thumb_mixed_scratch_bytes(const ThumbDesc& d) {
+  using mixed_list::align_up;
+  const size_t nblk = thumb_jpeg_blocks(d.oh, d.ow);
+  return align_up(ThumbTables::red_bytes(d)) + align_up(ThumbTables::mid_bytes(d)) + align_up(ThumbTables::pix_bytes(d)) + nblk * (128 + 8) +
+         ((nblk * kThumbBlockCodeBytes + 15) & ~(size_t)15) + sizeof(ThumbDesc) + kThumbItemBytes + 8;
+}
+// The chunks of the list (their ends) under the arena budget of thumbnail_run, pool_bytes of the arena being the call's tables. An image
+// takes its output row of dcap bytes and its scratch (staged: its pixels too); when the chunk is done the scratch is dead and the
+// gathered bytes (at most a row per image) take its place. At most 4096 images; an image alone whatever it needs (the arena refuses it
+// if it must).
+inline std::vector<int> thumb_mixed_cuts(const ThumbDesc* descs, int n, bool staged, size_t dcap, size_t arena_bytes, size_t pool_bytes) {
+  const size_t whole = std::min<size_t>((size_t)1 << 30, arena_bytes - arena_bytes / 8), budget = whole > pool_bytes ? whole - pool_bytes : 0;
+  size_t used = 0;
+  return mixed_list::cut_list(n, [&](int) { used = 0; }, [&](int i, int held, size_t&) {
+    const size_t stage = staged ? mixed_list::align_up((size_t)descs[i].h * descs[i].w * 3) : 0;
+    const size_t need = dcap + std::max(thumb_mixed_scratch_bytes(descs[i]) + stage, dcap) + 4 * mixed_list::kAlign;
+    if (held > 0 && (used + need > budget || held >= 4096)) return false;
+    used += need;
+    return true;
+  }).ends;
+}
 
 }  // namespace fe

@@ -10,6 +10,13 @@ from PIL import Image
 SHAPES = [(33, 47), (64, 96), (96, 64), (80, 80), (300, 260), (40, 400), (224, 224), (48, 1100), (64, 96), (80, 80)]
 CLIP, SAMP = 0, 1
 
+# The list of the statistics chunking test: with a 1 MiB arena the 184 320-byte hue-saturation histogram of every image (plus 3 184 bytes
+# of accumulators and record, its gray plane and, from the host, its pixels) lets five of these into a chunk (the first five take about
+# 1 044 000 bytes from the host; a sixth histogram would pass 1 048 576) - chunks of 5, 5, 1, resident too.
+# tests/test_mixed_list_host.py asserts the counts.
+STATS_CHUNK_SHAPES = [(96, 64), (64, 96), (80, 80), (96, 64), (33, 47), (100, 60), (96, 64), (64, 96), (1, 7), (96, 65), (80, 80)]
+CHUNK_ARENA = 1 << 20
+
 
 def images(seed=7, shapes=SHAPES):
     """Smooth structure plus noise, so that neither the filters nor the models see a flat field."""

@@ -21,6 +21,21 @@ def all_images():
     return images(shapes=ALL_SHAPES)
 
 
+# The list of the chunking tests: eleven images of about 200 KB, which an engine with a 1 MiB arena cannot take at once. From the host
+# fe_phash_mixed has room for 985 856 bytes beside its 60 672-byte pool and an image needs its staged pixels (to 256 bytes) plus 32 h +
+# 1608 with both extra outputs: 207 208, 207 176, 188 232, 207 208, 54 856 (864 680; the next, 206 376, would pass the room), then five
+# more (914 408), then one - chunks of 5, 5, 1; resident there is nothing to stage and one chunk takes all. fe_thumbnail_jpeg_mixed at
+# size 64 has a budget of 7/8 MiB less its 42 700-byte pool and an image needs two rows of fe_jpeg_bound(64, 64) = 40 561 bytes, its
+# staged pixels and its scratch, 160 833 (128 x 128) to 431 681 bytes (255 x 257) in all - chunks of 2, 3, 2, 2, 2, and 5, 5, 1 resident.
+# tests/test_mixed_list_host.py asserts the counts.
+CHUNK_SHAPES = [(257, 256), (256, 257), (200, 300), (257, 256), (128, 128), (255, 257), (240, 250), (257, 256), (100, 333), (256, 256), (257, 255)]
+CHUNK_ARENA = 1 << 20
+
+
+def chunk_images():
+    return images(seed=19, shapes=CHUNK_SHAPES)
+
+
 def pil_thumbnail_pixels(a, size):
     """uint8 [oh, ow, 3]: `Image.fromarray(a).copy().thumbnail((size, size), LANCZOS)`."""
     im = Image.fromarray(a).copy()

@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 from PIL import Image
 
-from facet_amd._lib import FE_ERR_INVALID, EngineError
+from facet_amd._lib import FE_ERR_CAPACITY, FE_ERR_INVALID, EngineCapacityError, EngineError
 from facet_amd.phash import phash_mixed
 from facet_amd.thumbnail import thumbnail_plan, thumbnails_mixed
-from mixed_index_cases import ALL_SHAPES, all_images
+from mixed_index_cases import ALL_SHAPES, CHUNK_ARENA, all_images, chunk_images
 from test_phash_host import TIE_BAND
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +115,35 @@ def test_257_small_images(engine):
         by_shape.setdefault(a.shape, []).append(i)
     shape, idx = max(by_shape.items(), key=lambda kv: len(kv[1]))          # the largest group against one uniform call
     assert np.array_equal(got[0][idx], engine.phash(np.stack([arrs[i] for i in idx])))
+
+
+def test_several_chunks_give_the_same(engine):
+    """A 1 MiB arena cuts the eleven images of tests/mixed_index_cases.py into chunks of 5, 5 and 1 (the figures are there): every output
+    equals the default engine's, from the host and resident. An image that cannot fit raises and leaves the engine usable."""
+    from facet_amd import Engine
+    arrs = chunk_images()
+    want = engine.phash_mixed(arrs, want_small=True, want_dct=True)
+    e = Engine(0, arena_bytes=CHUNK_ARENA)
+    try:
+        def check(got):
+            assert np.array_equal(got[0], want[0]) and got[1].tobytes() == want[1].tobytes() and got[2].tobytes() == want[2].tobytes()
+        check(e.phash_mixed(arrs, want_small=True, want_dct=True))
+        assert np.array_equal(e.phash_mixed(arrs), want[0])
+        offs = np.concatenate([[0], np.cumsum([a.nbytes for a in arrs])])
+        buf = e.dev_alloc(int(offs[-1]))
+        try:
+            for a, o in zip(arrs, offs):
+                e.h2d(ctypes.c_void_p(buf.value + int(o)), a)
+            check(e.phash_mixed(([buf.value + int(o) for o in offs[:-1]], [a.shape[:2] for a in arrs]), want_small=True, want_dct=True))
+        finally:
+            e.dev_free(buf)
+        big = np.zeros((700, 700, 3), np.uint8)      # 1.47 MB staged
+        with pytest.raises(EngineCapacityError, match=r"image 1 \(700 x 700\) needs \d+ bytes of scratch, the arena holds 1048576") as ei:
+            e.phash_mixed([arrs[4], big])
+        assert ei.value.status == FE_ERR_CAPACITY
+        check(e.phash_mixed(arrs, want_small=True, want_dct=True))          # the next good call is still right
+    finally:
+        e.close()
 
 
 def test_bad_arguments_name_the_image_and_leave_the_context_usable(engine, imgs, singles):

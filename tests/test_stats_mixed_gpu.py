@@ -13,11 +13,11 @@ import math
 import numpy as np
 import pytest
 
-from facet_amd._lib import FE_ERR_INVALID, FE_MODEL_TOPIQ, EngineError
+from facet_amd._lib import FE_ERR_CAPACITY, FE_ERR_INVALID, FE_MODEL_TOPIQ, EngineCapacityError, EngineError
 from facet_amd.batch import BatchScorer
 from facet_amd.image_stats import TechnicalAnalyzer
 from facet_amd.weights import synthetic_state_dict
-from mixed_cases import SHAPES, images
+from mixed_cases import CHUNK_ARENA, SHAPES, STATS_CHUNK_SHAPES, images
 from oracle import technical_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +123,33 @@ def test_channel_order(engine, imgs, singles, segment):
     with _segment(engine, segment):
         got = engine.image_stats_mixed([np.ascontiguousarray(a[..., ::-1]) for a in imgs], order='rgb')
     _assert_records(got, singles, "rgb input")
+
+
+def test_several_chunks_give_the_same(engine):
+    """A 1 MiB arena cuts the eleven images of tests/mixed_cases.py into chunks of 5, 5 and 1 (the figures are there): every double of
+    the records equals the default engine's, from the host and resident. An image that cannot fit raises and leaves the engine usable."""
+    from facet_amd import Engine
+    arrs = images(seed=23, shapes=STATS_CHUNK_SHAPES)
+    want = engine.image_stats_mixed(arrs)
+    e = Engine(0, arena_bytes=CHUNK_ARENA)
+    try:
+        assert e.image_stats_mixed(arrs).tobytes() == want.tobytes()
+        offs = np.concatenate([[0], np.cumsum([a.nbytes for a in arrs])])
+        buf = e.dev_alloc(int(offs[-1]))
+        try:
+            for a, o in zip(arrs, offs):
+                e.h2d(ctypes.c_void_p(buf.value + int(o)), a)
+            got = e.image_stats_mixed(([buf.value + int(o) for o in offs[:-1]], [a.shape[:2] for a in arrs]))
+        finally:
+            e.dev_free(buf)
+        assert got.tobytes() == want.tobytes()
+        big = np.zeros((600, 500, 3), np.uint8)      # 0.3 MB of gray and 0.9 MB staged
+        with pytest.raises(EngineCapacityError, match=r"image 2 \(600 x 500\) needs \d+ bytes of scratch, the arena holds 1048576") as ei:
+            e.image_stats_mixed([arrs[0], arrs[4], big])
+        assert ei.value.status == FE_ERR_CAPACITY
+        assert e.image_stats_mixed(arrs[:7]).tobytes() == want[:7].tobytes()          # the next good call is still right
+    finally:
+        e.close()
 
 
 def _same(a, b):

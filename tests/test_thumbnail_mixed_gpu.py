@@ -11,7 +11,7 @@ from PIL import Image
 
 from facet_amd._lib import FE_ERR_CAPACITY, FE_ERR_INVALID, EngineCapacityError, EngineError
 from facet_amd.thumbnail import thumbnail_plan, thumbnails, thumbnails_mixed
-from mixed_index_cases import ALL_SHAPES, all_images
+from mixed_index_cases import ALL_SHAPES, CHUNK_ARENA, all_images, chunk_images
 from test_thumbnail_gpu import saturated_noise
 from test_thumbnail_host import pil_thumbnail
 
@@ -72,6 +72,29 @@ def test_resident_images_at_odd_byte_offsets(engine, imgs, pillow, case):
     finally:
         engine.dev_free(buf)
     assert got == list(pillow[case])
+
+
+def test_several_chunks_give_the_same(engine):
+    """A 1 MiB arena cuts the eleven images of tests/mixed_index_cases.py into chunks of 2, 3, 2, 2, 2 from the host and 5, 5, 1 resident
+    (the figures are there): the bytes, and so the lengths, equal the default engine's."""
+    from facet_amd import Engine
+    arrs = chunk_images()
+    want = thumbnails_mixed(engine, arrs, size=64)
+    assert len(want) == len(arrs) and all(want)
+    e = Engine(0, arena_bytes=CHUNK_ARENA)
+    try:
+        assert thumbnails_mixed(e, arrs, size=64) == want
+        offs = np.concatenate([[0], np.cumsum([a.nbytes for a in arrs])])
+        buf = e.dev_alloc(int(offs[-1]))
+        try:
+            for a, o in zip(arrs, offs):
+                e.h2d(ctypes.c_void_p(buf.value + int(o)), a)
+            assert thumbnails_mixed(e, ([buf.value + int(o) for o in offs[:-1]], [a.shape[:2] for a in arrs]), size=64) == want
+        finally:
+            e.dev_free(buf)
+        assert thumbnails_mixed(e, arrs[:4], size=64) == want[:4]
+    finally:
+        e.close()
 
 
 def test_capacity(engine, imgs, pillow):
