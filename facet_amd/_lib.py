@@ -110,6 +110,8 @@ SIGNATURES = {
     "fe_op_rowpass": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p] + [C.c_int] * 6 + [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, _f32p]),
     "fe_op_gemm_skinny": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_int,
                                     C.c_int, C.c_float, _f32p]),
+    "fe_op_gemm_skinny_res": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p,
+                                        C.c_int, C.c_int, C.c_int, C.c_float, _f32p]),
     "fe_op_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "fe_op_mha": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                             C.c_int, _f32p]),
@@ -692,9 +694,10 @@ class Engine:
                                         float(fill), y.ctypes.data_as(_f32p)))
         return y
 
-    def gemm_skinny(self, x, w, K, types=("f32", "f32", "f32"), scale=None, shift=None, act=None, ldy=None, fill=-7.0):
+    def gemm_skinny(self, x, w, K, types=("f32", "f32", "f32"), scale=None, shift=None, act=None, ldy=None, fill=-7.0, res=None, many_rows=False):
         """The skinny GEMM launched alone (fe_op_gemm_skinny): x [M, ldx], w [N, ldw], the first K columns of both are contracted; types =
-        (activations, weights, output) -> the WHOLE output [M, ldy] (columns >= N keep `fill`)."""
+        (activations, weights, output) -> the WHOLE output [M, ldy] (columns >= N keep `fill`). res [M, ldr >= N]: residual rows added before
+        the activation; res or many_rows (M up to 4096, chunks of 32 in one launch) go through fe_op_gemm_skinny_res."""
         (x, xp), (w, wp) = _f32(x), _f32(w)
         (M, ldx), (N, ldw) = x.shape, w.shape
         ldy = N if ldy is None else int(ldy)
@@ -702,6 +705,12 @@ class Engine:
         (scale, sp), (shift, hp) = ((None, null) if scale is None else _f32(scale)), ((None, null) if shift is None else _f32(shift))
         assert (scale is None or scale.shape == (N,)) and (shift is None or shift.shape == (N,))
         y = np.empty((M, ldy), np.float32)
+        if res is not None or many_rows:
+            (res, rp), ldr = (_f32(res), res.shape[1]) if res is not None else ((None, null), 0)
+            assert res is None or (res.ndim == 2 and res.shape[0] == M and ldr >= N), res.shape
+            self._ck(self.lib.fe_op_gemm_skinny_res(self.h, ELEM[types[0]], ELEM[types[1]], ELEM[types[2]], xp, M, int(K), ldx, wp, N, ldw, sp, hp, rp,
+                                                    ldr, ACT[act], ldy, float(fill), y.ctypes.data_as(_f32p)))
+            return y
         self._ck(self.lib.fe_op_gemm_skinny(self.h, ELEM[types[0]], ELEM[types[1]], ELEM[types[2]], xp, M, int(K), ldx, wp, N, ldw, sp, hp, ACT[act], ldy,
                                             float(fill), y.ctypes.data_as(_f32p)))
         return y

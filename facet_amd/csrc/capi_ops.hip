@@ -60,13 +60,14 @@ static void hook_convert(Ctx& C, const float* x, size_t n, float fill, float* y)
 }
 template <class TI, class TW, class TO>
 static void hook_gemm_skinny(Ctx& C, const float* x, int M, int K, int ldx, const float* w, int N, int ldw, const float* scale, const float* shift, int act,
-                             int ldy, float fill, float* y) {
+                             int ldy, float fill, float* y, const float* res = nullptr, int ldr = 0) {
   const size_t ny = (size_t)M * ldy;
+  const TO* dr = hook_up<TO>(C, res, (size_t)M * ldr);
   const TI* dx = hook_up<TI>(C, x, (size_t)M * ldx);
   const TW* dw = hook_up<TW>(C, w, (size_t)N * ldw);
   const float *ds = hook_up<float>(C, scale, (size_t)N), *dh = hook_up<float>(C, shift, (size_t)N);
   TO* dy = hook_filled<TO>(C, ny, fill);
-  launch_gemm_skinny(dx, ldx, dw, ldw, ds, dh, dy, ldy, M, N, K, act, C.stream);
+  launch_gemm_skinny(dx, ldx, dw, ldw, ds, dh, dy, ldy, M, N, K, act, C.stream, dr, ldr);
   hook_down(C, dy, ny, y);
 }
 
@@ -397,21 +398,27 @@ int fe_op_rowpass(fe_ctx* ctx, int route, int elem_in, int elem_out, const float
 
 int fe_op_gemm_skinny(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
                       const float* scale, const float* shift, int act, int ldy, float fill, float* y) {
+  if (M > 32) return fe_api(ctx, [&] { FE_CHECK(false, "bad skinny GEMM arguments"); });
+  return fe_op_gemm_skinny_res(ctx, ti, tw, to, x, M, K, ldx, w, N, ldw, scale, shift, nullptr, 0, act, ldy, fill, y);
+}
+
+int fe_op_gemm_skinny_res(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
+                          const float* scale, const float* shift, const float* res, int ldr, int act, int ldy, float fill, float* y) {
   return fe_api(ctx, [&] {
     Ctx& C = ctx->c;
     const int F = FE_ELEM_F32, B = FE_ELEM_BF16, H = FE_ELEM_F16;
-    FE_CHECK(x && w && y && M > 0 && M <= 32 && N > 0 && N <= 65536 && K > 0 && K <= 65536 && ldx >= K && ldx <= 2 * K + 64 && ldw >= K && ldw <= 2 * K + 64 && ldy >= N &&
-             ldy <= 2 * N + 64, "bad skinny GEMM arguments");
+    FE_CHECK(x && w && y && M > 0 && M <= 4096 && N > 0 && N <= 65536 && K > 0 && K <= 65536 && ldx >= K && ldx <= 2 * K + 64 && ldw >= K && ldw <= 2 * K + 64 && ldy >= N &&
+             ldy <= 2 * N + 64 && (!res || (ldr >= N && ldr <= 2 * N + 64)), "bad skinny GEMM arguments");
     FE_CHECK(act >= ACT_NONE && act <= ACT_QUICKGELU && act != ACT_PRELU, "fe_op_gemm_skinny: activation %d", act);
     auto is = [&](int a, int b, int c) { return ti == a && tw == b && to == c; };
     C.arena.reset();
-    if (is(F, F, F)) hook_gemm_skinny<float, float, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(B, B, B)) hook_gemm_skinny<bf16, bf16, bf16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(B, B, F)) hook_gemm_skinny<bf16, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(H, H, H)) hook_gemm_skinny<f16, f16, f16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(H, H, F)) hook_gemm_skinny<f16, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(F, B, F)) hook_gemm_skinny<float, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
-    else if (is(F, H, F)) hook_gemm_skinny<float, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y);
+    if (is(F, F, F)) hook_gemm_skinny<float, float, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(B, B, B)) hook_gemm_skinny<bf16, bf16, bf16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(B, B, F)) hook_gemm_skinny<bf16, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(H, H, H)) hook_gemm_skinny<f16, f16, f16>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(H, H, F)) hook_gemm_skinny<f16, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(F, B, F)) hook_gemm_skinny<float, bf16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
+    else if (is(F, H, F)) hook_gemm_skinny<float, f16, float>(C, x, M, K, ldx, w, N, ldw, scale, shift, act, ldy, fill, y, res, ldr);
     else FE_CHECK(false, "fe_op_gemm_skinny: no kernel for element types (%d, %d, %d)", ti, tw, to);
   });
 }

@@ -116,19 +116,21 @@ MHAW build_mha(DeviceWeights& dw, const WeightStore& ws, const std::string& pref
 // RT = type of the residual / output rows: T, or float around 2-byte projections (fp32 token stream, FE_PRECISION_RES32)
 template <class T, class RT>
 void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, int ldkv, int B, int Lq,
-                 int Lk, const RT* res, int ldr, RT* y, int ldy, bool causal = false);
-// y[M][N] = act(x[M][K] W^T + b) (+res)
+                 int Lk, const RT* res, int ldr, RT* y, int ldy, bool causal = false, bool out_by_image = false);
+// (out_by_image, fp32: the out-projection goes through linear_tokens - for callers whose B*Lq rows must not pick the route, Lq <= 32)
+// y[M][N] = act(x[M][K] W^T + b) (+res). fp32: M <= 32 rows without a residual take the few-row kernel; by_image (linear_tokens sets it:
+// the rows are the tokens of images of at most 32 each) sends any M and a residual there too, where the layer fits that kernel.
 void linear_forward(Ctx& c, const ConvW& w, const float* x, int ldx, int M, float* y, int ldy, int act,
-                    const float* res = nullptr, int ldr = 0);
+                    const float* res = nullptr, int ldr = 0, bool by_image = false);
 void linear_forward(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, bf16* y, int ldy, int act,
                     const bf16* res = nullptr, int ldr = 0);
 void linear_forward(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, f16* y, int ldy, int act,
                     const f16* res = nullptr, int ldr = 0);
 // fp32 rows that are the tokens of B images, L each (the transformer layers of the TOPIQ head). linear_forward picks its few-row kernel by
 // the row count, so an image's route - and the last bits of its score - would depend on what it is batched with; here the route follows L:
-// images of at most 32 tokens take the few-row kernel in chunks of 32 rows whatever B is (a row's sum does not depend on its chunk), larger
-// ones never reach it.
-void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act);
+// images of at most 32 tokens take the few-row kernel, which works in chunks of 32 rows, whatever B is (a row's sum does not depend on its
+// chunk), larger ones never reach it. res (nullable): residual rows, added before the activation on either route.
+void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act, const float* res = nullptr, int ldr = 0);
 template <class T>
 inline void linear_tokens(Ctx& c, const ConvW& w, const T* x, int ldx, int B, int L, T* y, int ldy, int act) { linear_forward(c, w, x, ldx, B * L, y, ldy, act); }
 // 2-byte operand rows, fp32 residual rows (nullable) and fp32 result rows (the projections that write an fp32 token stream)

@@ -751,12 +751,28 @@ template TensorF16 resnet_forward<f16>(Ctx&, const ResNet&, const Tensor&, std::
 // ---------------------------------------------------------------------------------------------------
 namespace fe {
 
+// whether an fp32 layer and its operand rows fit the few-row kernel
+static bool linear_few_rows_ok(const Ctx& c, const ConvW& w, const float* x, int ldx, int act) {
+  return act != ACT_PRELU && c.force_variant == 0 && ldx % 4 == 0 && (((uintptr_t)x | (uintptr_t)w.w) & 15) == 0;
+}
 void linear_forward(Ctx& c, const ConvW& w, const float* x, int ldx, int M, float* y, int ldy, int act,
-                    const float* res, int ldr) {
-  if (M <= 32 && !res && act != ACT_PRELU && c.force_variant == 0 && ldx % 4 == 0 && (((uintptr_t)x | (uintptr_t)w.w) & 15) == 0) {
+                    const float* res, int ldr, bool by_image) {
+  if ((by_image || (M <= 32 && !res)) && linear_few_rows_ok(c, w, x, ldx, act)) {
     // per-image vectors: stream the weight matrix once instead of idling 255 CUs behind one 128-row tile
-    launch_gemm_skinny(x, ldx, w.w, w.Kp, w.scale, w.shift, y, ldy, M, w.Cout, w.K, act, c.stream);
-    c.flops_accum += 2.0 * M * (double)w.Cin * (w.CoutAlg ? w.CoutAlg : w.Cout);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c.profile) { FE_HIP(hipEventCreate(&e0)); FE_HIP(hipEventCreate(&e1)); FE_HIP(hipEventRecord(e0, c.stream)); }
+    launch_gemm_skinny(x, ldx, w.w, w.Kp, w.scale, w.shift, y, ldy, M, w.Cout, w.K, act, c.stream, res, ldr);
+    const double flops = 2.0 * M * (double)w.Cin * (w.CoutAlg ? w.CoutAlg : w.Cout);
+    if (c.profile) {
+      FE_HIP(hipEventRecord(e1, c.stream)); FE_HIP(hipEventSynchronize(e1));
+      float ms = 0.f;
+      FE_HIP(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+      char nm[128];
+      snprintf(nm, sizeof nm, "few-row gemm M=%d K=%d N=%d%s", M, w.K, w.Cout, res ? " +res" : "");
+      c.timings.push_back({nm, flops, 4.0 * ((double)M * w.K + (double)M * w.Cout * (res ? 2 : 1) + (double)w.Cout * w.K), ms});
+    }
+    c.flops_accum += flops;
     return;
   }
   Tensor xt = mat_view(x, M, w.CinPad, ldx), yt = mat_view(y, M, w.Cout, ldy);
@@ -908,16 +924,20 @@ void linear_forward_res(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, f1
 void linear_forward_res(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, float* y, int ldy, int act, const float* res, int ldr) { linear_forward_s32(c, w, x, ldx, M, y, ldy, act, res, ldr); }
 void linear_forward_res(Ctx& c, const ConvW& w, const f16* x, int ldx, int M, float* y, int ldy, int act, const float* res, int ldr) { linear_forward_s32(c, w, x, ldx, M, y, ldy, act, res, ldr); }
 
-void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act) {
+void linear_tokens(Ctx& c, const ConvW& w, const float* x, int ldx, int B, int L, float* y, int ldy, int act, const float* res, int ldr) {
   const int rows = B * L;
-  if (L > 32 || rows <= 32) { linear_forward(c, w, x, ldx, rows, y, ldy, act); return; }
-  for (int m0 = 0; m0 < rows; m0 += 32) linear_forward(c, w, x + (size_t)m0 * ldx, ldx, std::min(32, rows - m0), y + (size_t)m0 * ldy, ldy, act);
+  if (L > 32) { linear_forward(c, w, x, ldx, rows, y, ldy, act, res, ldr); return; }
+  // one launch of the few-row kernel over all chunks of 32 rows; a layer it cannot take goes chunk by chunk, so M <= 32 there as well
+  if (linear_few_rows_ok(c, w, x, ldx, act)) { linear_forward(c, w, x, ldx, rows, y, ldy, act, res, ldr, /*by_image=*/true); return; }
+  for (int m0 = 0; m0 < rows; m0 += 32)
+    linear_forward(c, w, x + (size_t)m0 * ldx, ldx, std::min(32, rows - m0), y + (size_t)m0 * ldy, ldy, act, res ? res + (size_t)m0 * ldr : nullptr, ldr);
 }
 
 template <class T, class RT>
 void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, int ldkv, int B, int Lq, int Lk,
-                 const RT* res, int ldr, RT* y, int ldy, bool causal) {
+                 const RT* res, int ldr, RT* y, int ldy, bool causal, bool out_by_image) {
   constexpr bool half = sizeof(T) == 2;
+  FE_CHECK(!out_by_image || !half, "mha: the out-projection routed by image exists for fp32 only");
   const int d = m.d, H = m.heads, hd = d / H;
   const int Lp = (Lk + 31) / 32 * 32;  // padded key count: row stride of the score matrix and of V^T
   const size_t mark = c.arena.mark();
@@ -969,13 +989,18 @@ void mha_forward(Ctx& c, const MHAW& m, const T* q_in, int ldq, const T* kv_in, 
       raw_gemm(c, p, 2.0 * B * H * (double)Lq * Lk * hd);
     }
   }
-  linear_forward_res(c, m.out, (const T*)O, d, B * Lq, y, ldy, ACT_NONE, res, ldr);
+  if constexpr (!half) {
+    if (out_by_image) linear_tokens(c, m.out, O, d, B, Lq, y, ldy, ACT_NONE, res, ldr);      // (the route follows the image here too)
+    else linear_forward_res(c, m.out, O, d, B * Lq, y, ldy, ACT_NONE, res, ldr);
+  } else {
+    linear_forward_res(c, m.out, (const T*)O, d, B * Lq, y, ldy, ACT_NONE, res, ldr);
+  }
   c.arena.rewind(mark);
 }
-template void mha_forward<float, float>(Ctx&, const MHAW&, const float*, int, const float*, int, int, int, int, const float*, int, float*, int, bool);
-template void mha_forward<bf16, bf16>(Ctx&, const MHAW&, const bf16*, int, const bf16*, int, int, int, int, const bf16*, int, bf16*, int, bool);
-template void mha_forward<f16, f16>(Ctx&, const MHAW&, const f16*, int, const f16*, int, int, int, int, const f16*, int, f16*, int, bool);
-template void mha_forward<bf16, float>(Ctx&, const MHAW&, const bf16*, int, const bf16*, int, int, int, int, const float*, int, float*, int, bool);
-template void mha_forward<f16, float>(Ctx&, const MHAW&, const f16*, int, const f16*, int, int, int, int, const float*, int, float*, int, bool);
+template void mha_forward<float, float>(Ctx&, const MHAW&, const float*, int, const float*, int, int, int, int, const float*, int, float*, int, bool, bool);
+template void mha_forward<bf16, bf16>(Ctx&, const MHAW&, const bf16*, int, const bf16*, int, int, int, int, const bf16*, int, bf16*, int, bool, bool);
+template void mha_forward<f16, f16>(Ctx&, const MHAW&, const f16*, int, const f16*, int, int, int, int, const f16*, int, f16*, int, bool, bool);
+template void mha_forward<bf16, float>(Ctx&, const MHAW&, const bf16*, int, const bf16*, int, int, int, int, const float*, int, float*, int, bool, bool);
+template void mha_forward<f16, float>(Ctx&, const MHAW&, const f16*, int, const f16*, int, int, int, int, const float*, int, float*, int, bool, bool);
 
 }  // namespace fe

@@ -428,10 +428,12 @@ void launch_attention(const f16* q, int ldq, const f16* k, int ldk, const f16* v
 // output rows [.][ldo] as hi | lo (o_lo_off)
 void launch_attention_split(const f16* q, const f16* k, int ld, int lo_off, const f16* vt_hi, const f16* vt_lo, int lp, f16* o, int ldo, int o_lo_off,
                             int B, int H, int Lq, int Lk, int dmodel, hipStream_t s);
-// M <= 32 rows: one wave per output column (kernels_misc.hip); TI / TW / TO = activation / weight / output element types
+// Few rows (chunks of 32, one chunk for the per-image vectors of the heads): one wave per output column and chunk (kernels_misc.hip);
+// TI / TW / TO = activation / weight / output element types. A row's result does not depend on M or on its place in the call.
+// res (nullable): residual rows [M][ldr] of the output type, added after scale / shift and before the activation (the conv epilogue's place)
 template <class TI, class TW, class TO>
 void launch_gemm_skinny(const TI* x, int ldx, const TW* w, int ldw, const float* scale, const float* shift, TO* y,
-                        int ldy, int M, int N, int K, int act, hipStream_t s);
+                        int ldy, int M, int N, int K, int act, hipStream_t s, const TO* res = nullptr, int ldr = 0);
 void launch_sigmoid(const Tensor& x, const Tensor& y, hipStream_t s);
 void launch_add(const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s);
 // LayerNorm over last dim of a [rows][d] matrix (eps inside sqrt, biased variance); statistics in fp32

@@ -482,19 +482,29 @@ void launch_tap_gather(const T* z, int ldz, int n, int h, int w, int kh, int kw,
   FE_HIP(hipGetLastError());
 }
 
-// ---- skinny GEMM (M <= 32 rows): y[m][n] = act(sum_k x[m][k] w[n][k] * scale[n] + shift[n]) -----------------------
+// ---- skinny GEMM (chunks of M <= 32 rows): y[m][n] = act(sum_k x[m][k] w[n][k] * scale[n] + shift[n]) -----------------------
 // One wave per output column streams its weight row once (16 B per lane); the <= 32 activation rows come from L1/L2.
 // Used for the per-image vectors of the heads (SAMP pattern "convs" K up to 7524, score MLPs, CLIP projection) where a
 // 128-row MFMA tile would leave 255 of 256 CUs idle behind a K loop thousands of steps long.
 // TI / TW / TO: element types of the activations, the weight rows and the outputs (bf16 activations with bf16 weights can
 // still emit fp32: the last layer of every head does).
+// res (nullable): residual rows of the output type, added after scale / shift and before the activation, where the conv epilogue adds its
+// own. A row's result depends on that row alone, never on M or on the row's place in the call.
+// More than MR rows: blockIdx.y walks chunks of MR rows (the tokens of many images in one launch; each chunk streams the weights again,
+// from L2), which gives the short-N layers the waves one chunk of them lacks.
 template <int MR, class TI, class TW, class TO>
 __global__ void gemm_skinny_kernel(const TI* __restrict__ x, int ldx, const TW* __restrict__ w, int ldw,
                                    const float* __restrict__ scale, const float* __restrict__ shift, TO* __restrict__ y,
-                                   int ldy, int M, int N, int K, int act) {
+                                   int ldy, int M, int N, int K, int act, const TO* __restrict__ res, int ldr) {
   const int lane = threadIdx.x & 63;
   const int n = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (n >= N) return;
+  {
+    const int m0 = blockIdx.y * MR;      // this block's chunk of rows
+    x += (size_t)m0 * ldx; y += (size_t)m0 * ldy;
+    if (res) res += (size_t)m0 * ldr;
+    M = min(MR, M - m0);
+  }
   float acc[MR];
 #pragma unroll
   for (int m = 0; m < MR; ++m) acc[m] = 0.f;
@@ -520,18 +530,23 @@ __global__ void gemm_skinny_kernel(const TI* __restrict__ x, int ldx, const TW* 
     const float sc = scale ? scale[n] : 1.f, sf = shift ? shift[n] : 0.f;
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
-      if (m < M) stf(y + (size_t)m * ldy + n, fe_apply_act(acc[m] * sc + sf, act));
+      if (m < M) {
+        float v = acc[m] * sc + sf;
+        if (res) v += ldf(res + (size_t)m * ldr + n);
+        stf(y + (size_t)m * ldy + n, fe_apply_act(v, act));
+      }
     }
   }
 }
 template <class TI, class TW, class TO>
 void launch_gemm_skinny(const TI* x, int ldx, const TW* w, int ldw, const float* scale, const float* shift, TO* y,
-                        int ldy, int M, int N, int K, int act, hipStream_t s) {
-  FE_CHECK(M >= 1 && M <= 32 && K % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0, "gemm_skinny: M=%d K=%d", M, K);
+                        int ldy, int M, int N, int K, int act, hipStream_t s, const TO* res, int ldr) {
+  FE_CHECK(M >= 1 && M <= 32 * 65535 && K % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0, "gemm_skinny: M=%d K=%d", M, K);
+  FE_CHECK(!res || ldr >= N, "gemm_skinny: residual rows of %d columns, N=%d", ldr, N);
   FE_CHECK(((uintptr_t)x & (4 * sizeof(TI) - 1)) == 0 && ((uintptr_t)w & (4 * sizeof(TW) - 1)) == 0, "gemm_skinny: alignment");
   const int blocks = (N * 64 + 255) / 256;
-  if (M <= 8) hipLaunchKernelGGL((gemm_skinny_kernel<8, TI, TW, TO>), dim3(blocks), dim3(256), 0, s, x, ldx, w, ldw, scale, shift, y, ldy, M, N, K, act);
-  else hipLaunchKernelGGL((gemm_skinny_kernel<32, TI, TW, TO>), dim3(blocks), dim3(256), 0, s, x, ldx, w, ldw, scale, shift, y, ldy, M, N, K, act);
+  if (M <= 8) hipLaunchKernelGGL((gemm_skinny_kernel<8, TI, TW, TO>), dim3(blocks), dim3(256), 0, s, x, ldx, w, ldw, scale, shift, y, ldy, M, N, K, act, res, ldr);
+  else hipLaunchKernelGGL((gemm_skinny_kernel<32, TI, TW, TO>), dim3(blocks, (M + 31) / 32), dim3(256), 0, s, x, ldx, w, ldw, scale, shift, y, ldy, M, N, K, act, res, ldr);
   FE_HIP(hipGetLastError());
 }
 
@@ -854,13 +869,13 @@ FE_INST_T(f16)
 // fp32 residual stream in front of a 2-byte GEMM operand (precision option FE_PRECISION_RES32): LayerNorm reads fp32, writes 2 bytes
 template void launch_layernorm<float, bf16>(const float*, int, bf16*, int, const float*, const float*, int, int, float, hipStream_t);
 template void launch_layernorm<float, f16>(const float*, int, f16*, int, const float*, const float*, int, int, float, hipStream_t);
-template void launch_gemm_skinny<float, float, float>(const float*, int, const float*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<bf16, bf16, bf16>(const bf16*, int, const bf16*, int, const float*, const float*, bf16*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<bf16, bf16, float>(const bf16*, int, const bf16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<f16, f16, f16>(const f16*, int, const f16*, int, const float*, const float*, f16*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<f16, f16, float>(const f16*, int, const f16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<float, bf16, float>(const float*, int, const bf16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
-template void launch_gemm_skinny<float, f16, float>(const float*, int, const f16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
+template void launch_gemm_skinny<float, float, float>(const float*, int, const float*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t, const float*, int);
+template void launch_gemm_skinny<bf16, bf16, bf16>(const bf16*, int, const bf16*, int, const float*, const float*, bf16*, int, int, int, int, int, hipStream_t, const bf16*, int);
+template void launch_gemm_skinny<bf16, bf16, float>(const bf16*, int, const bf16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t, const float*, int);
+template void launch_gemm_skinny<f16, f16, f16>(const f16*, int, const f16*, int, const float*, const float*, f16*, int, int, int, int, int, hipStream_t, const f16*, int);
+template void launch_gemm_skinny<f16, f16, float>(const f16*, int, const f16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t, const float*, int);
+template void launch_gemm_skinny<float, bf16, float>(const float*, int, const bf16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t, const float*, int);
+template void launch_gemm_skinny<float, f16, float>(const float*, int, const f16*, int, const float*, const float*, float*, int, int, int, int, int, hipStream_t, const float*, int);
 
 // RGB <-> BGR of a packed uint8 image batch (the reference keeps a PIL RGB and a cv2 BGR copy of every image,
 // processing/batch_processor.py:200-215; here the second one is made on the device from the resident first one).

@@ -245,16 +245,38 @@ void clip_forward(Ctx& c, const ClipModel& m, const Tensor& x, float* feat) {
   launch_layernorm(tok, d, xa, d, m.ln_pre.g, m.ln_pre.b, rows, d, m.ln_pre.eps, c.stream);
   RT* cur = xa;
   RT* other = tok;
-  for (const ClipBlockW& w : m.blocks) {
+  // Nothing reads the token stream after the loop but the class token of every image, so in the last block the patch tokens matter as
+  // keys and values only: ln_1, K and V^T over all rows, everything behind them on the B class-token rows (fp32 tower; the 2-byte towers
+  // keep the full block). One row per image, so these rows take the few-row kernel in chunks of 32 whatever B is (linear_tokens, L = 1).
+  // FE_CLIP_FULL_LAST_BLOCK restores the full last block (A/B hook, read per call).
+  const bool prune = sizeof(T) == 4 && !getenv("FE_CLIP_FULL_LAST_BLOCK");
+  const RT* cls_rows = nullptr;      // dense [B][d] class-token rows out of the pruned block
+  for (size_t bi = 0; bi < m.blocks.size(); ++bi) {
+    const ClipBlockW& w = m.blocks[bi];
     launch_layernorm(cur, d, nb, d, w.ln1.g, w.ln1.b, rows, d, w.ln1.eps, c.stream);
+    if constexpr (sizeof(T) == 4) {
+      if (prune && bi + 1 == m.blocks.size()) {
+        const int ff = w.fc.Cout;
+        RT* ya = c.arena.array<RT>((size_t)B * d);
+        RT* yb = c.arena.array<RT>((size_t)B * d);
+        T* hc = c.arena.array<T>((size_t)B * ff);
+        mha_forward<T, RT>(c, w.attn, nb, Tk * d, nb, d, B, 1, Tk, cur, Tk * d, ya, d, /*causal=*/false, /*out_by_image=*/true);   // ya = cur[:, 0] + attn
+        launch_layernorm(ya, d, nb, d, w.ln2.g, w.ln2.b, B, d, w.ln2.eps, c.stream);      // (nb is free again: K and V^T are computed)
+        linear_tokens(c, w.fc, nb, d, B, 1, hc, ff, ACT_GELU);
+        linear_tokens(c, w.proj, hc, ff, B, 1, yb, d, ACT_NONE, ya, d);                     // yb = ya + mlp(ln2(ya))
+        cls_rows = yb;
+        break;
+      }
+    }
     mha_forward<T, RT>(c, w.attn, nb, d, nb, d, B, Tk, Tk, cur, d, other, d);          // other = cur + attn(ln1(cur))
     launch_layernorm(other, d, nb, d, w.ln2.g, w.ln2.b, rows, d, w.ln2.eps, c.stream);
     linear_forward(c, w.fc, nb, d, rows, hb, w.fc.Cout, ACT_GELU);
     linear_forward_res(c, w.proj, (const T*)hb, w.fc.Cout, rows, cur, d, ACT_NONE, (const RT*)other, d);  // cur = other + mlp(ln2(other))
   }
-  // ln_post on the class token of every image (row stride Tk*d), then the projection (fp32 out)
+  // ln_post on the class token of every image (row stride Tk*d, or the pruned block's dense rows), then the projection (fp32 out)
   T* pooled = c.arena.array<T>((size_t)B * d);
-  launch_layernorm(cur, Tk * d, pooled, d, m.ln_post.g, m.ln_post.b, B, d, m.ln_post.eps, c.stream);
+  if (cls_rows) launch_layernorm(cls_rows, d, pooled, d, m.ln_post.g, m.ln_post.b, B, d, m.ln_post.eps, c.stream);
+  else launch_layernorm(cur, Tk * d, pooled, d, m.ln_post.g, m.ln_post.b, B, d, m.ln_post.eps, c.stream);
   linear_forward_f32(c, m.proj, pooled, d, B, feat, m.out_dim, ACT_NONE);
   c.arena.rewind(mark);
 }

@@ -320,7 +320,9 @@ int fe_op_layernorm(fe_ctx* ctx, const float* x, int rows, int d, const float* g
  *
  * fe_op_gemm_skinny: y [M][ldy] (prefilled with `fill`) = act(x [M][ldx] . w [N][ldw]^T * scale [N] + shift [N]) over K columns, M <= 32,
  * scale / shift nullable; (ti, tw, to) one of (f32, f32, f32), (bf16, bf16, bf16), (bf16, bf16, f32), (f16, f16, f16), (f16, f16, f32),
- * (f32, bf16, f32), (f32, f16, f32). */
+ * (f32, bf16, f32), (f32, f16, f32). fe_op_gemm_skinny_res: the same with residual rows res [M][ldr] (nullable, rounded to the output
+ * type) added after scale / shift and before the activation, and M <= 4096 (one launch over chunks of 32 rows); res == NULL and M <= 32
+ * is fe_op_gemm_skinny. */
 #define FE_ELEM_F32 0
 #define FE_ELEM_BF16 1
 #define FE_ELEM_F16 2
@@ -330,6 +332,8 @@ int fe_op_rowpass(fe_ctx* ctx, int route, int elem_in, int elem_out, const float
                   const float* g, const float* b, int off_gb, int L, float eps, float fill, float* y);
 int fe_op_gemm_skinny(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
                       const float* scale, const float* shift, int act, int ldy, float fill, float* y);
+int fe_op_gemm_skinny_res(fe_ctx* ctx, int ti, int tw, int to, const float* x, int M, int K, int ldx, const float* w, int N, int ldw,
+                          const float* scale, const float* shift, const float* res, int ldr, int act, int ldy, float fill, float* y);
 /* test hook of the fused head_dim-64 attention kernels, launched alone (kernels_attn.hip: fp32, bf16 / f16 and split-f16 policies):
    q [B][Lq][H*64], k / v [B][Lk][H*64], bv [H*64] -> o [B][Lq][H*64] = softmax(q k^T) v + bv per (batch, head), the semantics of
    torch.nn.functional.scaled_dot_product_attention with scale = 1 (q is passed as the kernel receives it: the caller has applied any
