@@ -125,6 +125,8 @@ SIGNATURES = {
     "fe_op_vlm_rows": (C.c_int, [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_float, C.c_int, C.c_int, _f32p, _f32p]),
     "fe_op_vlm_vis_rope": (C.c_int, [C.c_void_p, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
+    "fe_op_vlm_vis_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "fe_op_vlm_prefill_attention": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p] + [C.c_int] * 6 + [C.POINTER(C.c_int32), _f32p]),
     "fe_set_conv_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "fe_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [_f32p]),
     "fe_topiq_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -1127,6 +1129,37 @@ class Engine:
         q, k = np.empty((rows, heads * hd), np.float32), np.empty((rows, heads * hd), np.float32)
         self._ck(self.lib.fe_op_vlm_vis_rope(self.h, qp, pp, fp, int(hd), rows, int(heads), int(max_blocks), q.ctypes.data_as(_f32p), k.ctypes.data_as(_f32p)))
         return q, k
+
+    def vlm_vis_attention(self, q, k, v, cu, hd, heads, max_seg=None):
+        """The segment attention of the vision towers launched alone (fe_op_vlm_vis_attention): q, k, v [N, heads * hd] (rounded to bf16),
+        cu int [n_seg + 1] (segment s = rows cu[s] .. cu[s + 1] - 1), hd 64 or 80; max_seg None: the longest segment -> o float32
+        [N, heads * hd]. The kernel reads v out of fused rows whose q and k thirds the hook fills with 1.0e4."""
+        (q, qp), (k, kp), (v, vp) = _f32(q), _f32(k), _f32(v)
+        cu, cp = self._i32(cu)
+        n_seg = cu.shape[0] - 1
+        N = q.shape[0]
+        assert cu.ndim == 1 and n_seg >= 1 and q.shape == (N, heads * hd) and k.shape == q.shape and v.shape == q.shape, (cu.shape, q.shape, k.shape, v.shape)
+        assert N == int(cu[-1]), (N, cu)
+        if max_seg is None:
+            max_seg = int(np.diff(cu).max())
+        o = np.empty_like(q)
+        self._ck(self.lib.fe_op_vlm_vis_attention(self.h, qp, kp, vp, cp, n_seg, int(max_seg), int(hd), int(heads), o.ctypes.data_as(_f32p)))
+        return o
+
+    def vlm_prefill_attention(self, q, k, v, nh, nkv, qpos0=0, max_seq=None, pad=None):
+        """The prefill attention of the VLM decoders launched alone (fe_op_vlm_prefill_attention): q [B, Lq, nh * 128], k / v
+        [B, nkv, qpos0 + Lq, 128] (rounded to bf16), pad int [B] (left padding; None: zeros); the bf16 caches of max_seq rows (None: Lk) are
+        built by the engine's own fill pass over NaN rows -> o float32 [B, Lq, nh * 128]."""
+        (q, qp), (k, kp), (v, vp) = _f32(q), _f32(k), _f32(v)
+        B, Lq, _ = q.shape
+        Lk = int(qpos0) + Lq
+        assert q.shape == (B, Lq, nh * 128) and k.shape == (B, nkv, Lk, 128) and v.shape == k.shape, (q.shape, k.shape, v.shape)
+        pd, pdp = self._i32(np.zeros(B, np.int32) if pad is None else pad)
+        assert pd.shape == (B,), pd.shape
+        o = np.empty_like(q)
+        self._ck(self.lib.fe_op_vlm_prefill_attention(self.h, qp, kp, vp, B, int(nh), int(nkv), Lq, int(qpos0), Lk if max_seq is None else int(max_seq), pdp,
+                                                      o.ctypes.data_as(_f32p)))
+        return o
 
     def vlm_vision_configure(self, n_heads=16, fullatt_block_indexes=(7, 15, 23, 31)):
         """Vision-tower geometry read by the NEXT load_weights(FE_MODEL_VLM, ...) (Qwen2_5_VLVisionConfig; defaults = Qwen2.5-VL-7B)."""

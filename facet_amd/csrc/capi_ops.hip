@@ -790,4 +790,71 @@ int fe_op_vlm_vis_rope(fe_ctx* ctx, const float* qkv, const int32_t* pos, const 
   });
 }
 
+// ---- test hooks of the attention tile (vlm_attn_tile.h) under its two kernels, each through the one function that launches it ---------------
+// n bf16 values in the arena, all 768 (a bf16 value): a row the kernel leaves unwritten shows
+static bf16* vlm_hook_768(Ctx& C, size_t n) {
+  const std::vector<float> fill(n, 768.f);
+  bf16* d = vlm_hook_bf16(C, fill.data(), n);
+  FE_HIP(hipStreamSynchronize(C.stream));      // (fill dies here)
+  return d;
+}
+
+int fe_op_vlm_vis_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* cu, int n_seg, int max_seg, int hd, int heads, float* o) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(q && k && v && cu && o && (hd == 64 || hd == 80) && heads >= 1 && heads <= 64 && n_seg >= 1 && n_seg <= 65535,
+             "bad vision attention arguments (hd 64 or 80, 1 .. 64 heads, 1 .. 65535 segments)");
+    FE_CHECK(cu[0] == 0, "fe_op_vlm_vis_attention: cu[0] = %d (0)", cu[0]);
+    int longest = 0;
+    for (int s = 0; s < n_seg; ++s) {
+      FE_CHECK(cu[s + 1] > cu[s] && cu[s + 1] <= 65536, "fe_op_vlm_vis_attention: segment %d is rows %d .. %d (at least one row, 65536 in all)", s, cu[s], cu[s + 1]);
+      longest = std::max(longest, cu[s + 1] - cu[s]);
+    }
+    FE_CHECK(max_seg == longest, "fe_op_vlm_vis_attention: max_seg %d, the longest segment has %d rows", max_seg, longest);
+    C.arena.reset();
+    const size_t N = (size_t)cu[n_seg], d = (size_t)heads * hd, n = N * d;
+    const bf16* hq = vlm_hook_bf16(C, q, n);
+    const bf16* hk = vlm_hook_bf16(C, k, n);
+    // the fused projection rows: v in the last third, a large finite value in the q and k thirds (a read from the wrong third is gross)
+    std::vector<float> fused(3 * n, 1.0e4f);
+    for (size_t r = 0; r < N; ++r) memcpy(&fused[r * 3 * d + 2 * d], v + r * d, d * sizeof(float));
+    const bf16* hqkv = vlm_hook_bf16(C, fused.data(), 3 * n);
+    const int* dcu = upload(C, cu, (size_t)n_seg + 1);
+    bf16* ho = vlm_hook_768(C, n);
+    vlm_vis_attention(C, hd, hq, hk, hqkv, ho, dcu, n_seg, max_seg, heads);
+    vlm_hook_f32(C, ho, n, o);
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
+int fe_op_vlm_prefill_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int nkv, int Lq, int qpos0, int max_seq, const int32_t* pad,
+                                float* o) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    FE_CHECK(q && k && v && pad && o && B > 0 && nh > 0 && nkv > 0 && nh % nkv == 0 && (size_t)B * nh <= 65535, "bad prefill attention arguments (nh %% nkv == 0, B nh <= 65535)");
+    FE_CHECK(Lq >= 1 && qpos0 >= 0 && qpos0 <= 8192 && Lq <= 8192 && qpos0 + Lq <= max_seq && max_seq <= 8192,
+             "fe_op_vlm_prefill_attention: %d queries from position %d in a cache of %d rows (8192 at most)", Lq, qpos0, max_seq);
+    const int Lk = qpos0 + Lq;
+    for (int b = 0; b < B; ++b) FE_CHECK(pad[b] >= 0 && pad[b] < Lk, "fe_op_vlm_prefill_attention: pad %d of %d keys", pad[b], Lk);
+    C.arena.reset();
+    const size_t nq = (size_t)B * Lq * nh * 128, nk = (size_t)B * nkv * Lk * 128, cbytes = (size_t)B * nkv * max_seq * 128 * sizeof(bf16);
+    const bf16* hq = vlm_hook_bf16(C, q, nq);
+    const bf16* hk = vlm_hook_bf16(C, k, nk);
+    const bf16* hv = vlm_hook_bf16(C, v, nk);
+    const int* dpad = upload(C, pad, (size_t)B);
+    // the caches: rows Lk .. max_seq - 1 hold bf16 NaNs (the kernel clamps its loads to row Lk - 1: they must never reach a result)
+    VlmKv kv;
+    kv.format = FE_VLM_KV_BF16; kv.max_seq = max_seq;
+    kv.k = (bf16*)C.arena.alloc(cbytes);
+    kv.v = (bf16*)C.arena.alloc(cbytes);
+    FE_HIP(hipMemsetAsync(kv.k, 0xFF, cbytes, C.stream));
+    FE_HIP(hipMemsetAsync(kv.v, 0xFF, cbytes, C.stream));
+    vlm_kv_fill(C, kv, hk, hv, B * nkv, Lk);
+    bf16* ho = vlm_hook_768(C, nq);
+    vlm_prefill_attention(C, hq, kv.k, kv.v, max_seq, B, nh, nkv, Lq, Lk, qpos0, dpad, ho);
+    vlm_hook_f32(C, ho, nq, o);
+    FE_HIP(hipStreamSynchronize(C.stream));
+  });
+}
+
 }  // extern "C"

@@ -584,6 +584,11 @@ void vlm_kv_fill(Ctx& c, const VlmKv& kv, const bf16* ksrc, const bf16* vsrc, in
 // ([B * nh * nsplit * 128], [B * nh * nsplit] twice), nsplit = ceil((len_dev ? max_seq : Lk) / 128).
 void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh, int nkv, int Lk, const int* len_dev, const int* pad, float* po, float* pm,
                           float* pl, int nsplit, bf16* out);
+// prefill attention, causal and grouped-query, head_dim 128: q / out [B * Lq][nh * 128], query i of a sequence at position qpos0 + i over keys
+// pad[b] .. qpos0 + i of the bf16 cache rows kc / vc [B][nkv][max_seq][128] (Lk = qpos0 + Lq of them are valid); pad: device [B], rows below
+// pad[b] come out as zeros
+void vlm_prefill_attention(Ctx& c, const bf16* q, const bf16* kc, const bf16* vc, int max_seq, int B, int nh, int nkv, int Lq, int Lk, int qpos0, const int* pad,
+                           bf16* out);
 // ---- the decode projections launched alone (fe_op_vlm_linear): the decoder's own choice among its kernels, or a forced one
 enum VlmLinearForce : int { VLM_LIN_AUTO = 0, VLM_LIN_FORCE_GEMV = 1, VLM_LIN_FORCE_GEMM32 = 2 };
 enum VlmLinearFamily : int { VLM_LIN_GEMV = 1, VLM_LIN_GEMM32 = 2, VLM_LIN_WRAPPER = 3 };

@@ -1436,6 +1436,17 @@ void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh,
   FE_HIP(hipGetLastError());
 }
 
+void vlm_prefill_attention(Ctx& c, const bf16* q, const bf16* kc, const bf16* vc, int max_seq, int B, int nh, int nkv, int Lq, int Lk, int qpos0, const int* pad,
+                           bf16* out) {
+  FE_CHECK(q && kc && vc && pad && out && B > 0 && nkv > 0 && nh % nkv == 0 && Lq > 0 && qpos0 >= 0 && Lk == qpos0 + Lq && Lk <= max_seq && (size_t)B * nh <= 65535,
+           "vlm prefill attention: %d x %d heads over %d KV heads, %d queries from position %d, %d keys of a cache of %d", B, nh, nkv, Lq, qpos0, Lk, max_seq);
+  const float scale = 1.0f / sqrtf(128.f);
+  const int qd = nh * 128;
+  VlmAttnParams ap{q, qd, kc, vc, out, qd, B, nh, nkv, Lq, Lk, max_seq, qpos0, scale, pad};
+  hipLaunchKernelGGL(vlm_attn_prefill_kernel, dim3((Lq + 127) / 128, B * nh), dim3(256), 0, c.stream, ap);
+  FE_HIP(hipGetLastError());
+}
+
 
 // ---- the launches of the row passes (engine.h): vlm_forward, the vision towers and the fe_op_vlm_* test hooks all come through here ------
 int vlm_grid(size_t n_threads, int max_blocks) {
@@ -1520,7 +1531,6 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
   bf16* br = c.arena.array<bf16>((size_t)rows * d);
   bf16* gg = c.arena.array<bf16>((size_t)rows * m.inter);
   bf16* uu = c.arena.array<bf16>((size_t)rows * m.inter);
-  const float scale = 1.0f / sqrtf(128.f);
   FE_CHECK(m.kcache.size() == m.layers.size() && (m.kv_format != FE_VLM_KV_E4M3 || m.kscale.size() == m.layers.size()), "vlm: no KV cache");
   const bool f8kv = m.kv_format == FE_VLM_KV_E4M3;
   // (e4m3 formats: a prefill's own K / V, see the layer loop; every prefill entry point starts at position 0)
@@ -1558,8 +1568,7 @@ void vlm_forward(Ctx& c, VlmModel& m, bf16* x, const int* pos, int B, int L, int
     if (L == 1) {
       vlm_decode_attention(c, kv, (const bf16*)qr, B, nh, nkv, Lk, len_dev, (const int*)m.pad, po, pm, pl, nsplit, ao);
     } else {
-      VlmAttnParams ap{qr, qd, rk, rv, ao, qd, B, nh, nkv, L, Lk, rseq, start, scale, m.pad};
-      hipLaunchKernelGGL(vlm_attn_prefill_kernel, dim3((L + 127) / 128, B * nh), dim3(256), 0, c.stream, ap);
+      vlm_prefill_attention(c, (const bf16*)qr, (const bf16*)rk, (const bf16*)rv, rseq, B, nh, nkv, L, Lk, start, (const int*)m.pad, ao);
       if (staged) vlm_kv_fill(c, kv, (const bf16*)pk, (const bf16*)pv, B * nkv, L);
     }
     FE_HIP(hipGetLastError());

@@ -404,6 +404,23 @@ int fe_op_vlm_rows(fe_ctx* ctx, int route, const float* x, const float* y, const
                    int ldx, int ldy, float eps, int alias, int max_blocks, float* out_x, float* out_n);
 int fe_op_vlm_vis_rope(fe_ctx* ctx, const float* qkv, const int32_t* pos, const float* inv_freq, int hd, int rows, int heads, int max_blocks, float* q_out,
                        float* k_out);
+/* Test hooks of the Qwen-VL attention tile under its two kernels, launched alone (no model) through the one function that launches each.
+ * fp32 inputs are rounded to bf16 on the device; fp32 outputs hold bf16 values; every output is filled with 768 before the launch.
+ *
+ * fe_op_vlm_vis_attention: the vision towers' non-causal attention inside packed segments. q, k, v [N][heads * hd], N = cu [n_seg], segment s
+ * = rows cu [s] .. cu [s + 1] - 1 (cu [0] == 0, every segment at least one row, max_seg = the longest, N <= 65536), hd 64 or 80,
+ * 1 .. 64 heads. The kernel reads v as the last third of fused rows [N][3 * heads * hd]; the hook fills the other two thirds with 1.0e4.
+ * o [N][heads * hd].
+ *
+ * fe_op_vlm_prefill_attention: the decoders' causal grouped-query prefill attention, head_dim 128. q [B * Lq][nh * 128]; k, v
+ * [B][nkv][Lk][128] with Lk = qpos0 + Lq; query i of a sequence sits at position qpos0 + i and sees keys pad [b] .. qpos0 + i; rows below
+ * pad [b] come out as zeros. The caches [B][nkv][max_seq][128] are built by the engine's own fill pass; their rows Lk .. max_seq - 1 hold
+ * bf16 NaNs. nh % nkv == 0, Lk <= max_seq <= 8192, 0 <= pad [b] < Lk, B * nh <= 65535. o [B * Lq][nh * 128].
+ *
+ * An argument outside these ranges is FE_ERR_RUNTIME before any launch. */
+int fe_op_vlm_vis_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* cu, int n_seg, int max_seg, int hd, int heads, float* o);
+int fe_op_vlm_prefill_attention(fe_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int nkv, int Lq, int qpos0, int max_seq,
+                                const int32_t* pad, float* o);
 
 /* developer hook: force a tile variant of the contraction kernel for every later launch (0 = automatic choice) */
 int fe_set_conv_variant(fe_ctx* ctx, int variant);
