@@ -112,15 +112,32 @@ __global__ void vlm_kv_fill_kernel(const bf16* __restrict__ ksrc, const bf16* __
   }
 }
 
-// Multimodal rotary embedding on the q and k heads of a fused QKV row block + the KV-cache append.
+// The tail both rope kernels share: rotate the pair (y1, y2) = dims (d, d + 64) of head hd by `ang`, then append it to the K cache or write
+// it to q_out. cos / sin are rounded to bf16 and y*cos, rotate_half(y)*sin and their sum are each rounded to bf16, as
+// apply_multimodal_rotary_pos_emb does on bf16 tensors. A wave holds one (row, head) and lane d its pair d, so under the e4m3 formats
+// the append quantises the row in place (vlm_kv_store_row). cpos: the row's position in the cache.
+template <int KV>
+__device__ __forceinline__ void vlm_rope_rotate_append(const float y1, const float y2, const float ang, const int hd, const int nh, const int nkv, const int d,
+                                                       const int row, const int b, const int cpos, const int max_seq, bf16* __restrict__ q_out,
+                                                       bf16* __restrict__ kc, float* __restrict__ ksc) {
+  const float c = (float)(bf16)cosf(ang), s = (float)(bf16)sinf(ang);
+  const bf16 o1 = (bf16)((float)(bf16)(y1 * c) + (float)(bf16)(-y2 * s));
+  const bf16 o2 = (bf16)((float)(bf16)(y2 * c) + (float)(bf16)(y1 * s));
+  if (hd >= nh) {      // (wave-uniform)
+    vlm_kv_store_row<KV>(kc, ksc, ((size_t)b * nkv + (hd - nh)) * max_seq + cpos, d, o1, o2);
+    return;
+  }
+  bf16* dst = q_out + ((size_t)row * nh + hd) * 128;
+  dst[d] = o1; dst[d + 64] = o2;
+}
+
+// Multimodal rotary embedding on the q and k heads of a fused QKV row block + the KV-cache append (Qwen2 / 2.5).
 //   qkv: [rows][(nh + 2 nkv) * 128]; pos: [3][rows] (temporal, height, width position of every token; equal for text tokens)
 //   q_out: [rows][nh * 128]; kc / vc: cache [B][nkv][max_seq][128], row `row` = (b, t) lands at position start + t.
 // Dimension i of a head takes frequency i % 64 and the position component of its section (sections doubled over the two halves:
-// [16, 24, 24, 16, 24, 24]); cos / sin are rounded to bf16 and x*cos, rotate_half(x)*sin and their sum are each rounded to bf16, as
-// apply_multimodal_rotary_pos_emb does on bf16 tensors. One thread per (row, head, pair d < 64).
-// KV: the cache format. A wave covers exactly one (row, head) per loop trip (64 lanes = the 64 pairs), so under the e4m3 formats the append
-// quantises the row in place (vlm_kv_store_row; ksc / vsc: the scale arrays of FE_VLM_KV_E4M3, kc / vc then the code arrays). The bf16
-// instantiation is the code this kernel was before the formats.
+// [16, 24, 24, 16, 24, 24]). One thread per (row, head, pair d < 64); a wave covers exactly one (row, head) per loop trip (64 lanes = the
+// 64 pairs). KV: the cache format; K and V rows reach the cache through vlm_kv_store_row alone (ksc / vsc: the scale arrays of
+// FE_VLM_KV_E4M3, kc / vc then the code arrays).
 template <int KV>
 __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, bf16* __restrict__ q_out,
                                       bf16* __restrict__ kc, bf16* __restrict__ vc, int rows, int L, int nh, int nkv, int s0, int s1, int start, int max_seq,
@@ -133,28 +150,12 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
     const bf16* src = qkv + ((size_t)row * heads + hd) * 128;
     const int b = row / L, t = row - b * L;
     if (hd >= nh + nkv) {      // V: plain copy into the cache
-      if constexpr (KV != FE_VLM_KV_BF16) {
-        vlm_kv_store_row<KV>(vc, vsc, ((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t, d, src[d], src[d + 64]);
-        continue;
-      }
-      bf16* dst = vc + (((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t) * 128;
-      dst[d] = src[d]; dst[d + 64] = src[d + 64];
+      vlm_kv_store_row<KV>(vc, vsc, ((size_t)b * nkv + (hd - nh - nkv)) * max_seq + start + t, d, src[d], src[d + 64]);
       continue;
     }
     const int comp = d < s0 ? 0 : (d < s0 + s1 ? 1 : 2);
     const float ang = (float)pos[(size_t)comp * rows + row] * inv_freq[d];
-    const float c = (float)(bf16)cosf(ang), s = (float)(bf16)sinf(ang);
-    const float x1 = (float)src[d], x2 = (float)src[d + 64];
-    const bf16 o1 = (bf16)((float)(bf16)(x1 * c) + (float)(bf16)(-x2 * s));
-    const bf16 o2 = (bf16)((float)(bf16)(x2 * c) + (float)(bf16)(x1 * s));
-    if constexpr (KV != FE_VLM_KV_BF16) {
-      if (hd >= nh) {      // (wave-uniform)
-        vlm_kv_store_row<KV>(kc, ksc, ((size_t)b * nkv + (hd - nh)) * max_seq + start + t, d, o1, o2);
-        continue;
-      }
-    }
-    bf16* dst = hd < nh ? q_out + ((size_t)row * nh + hd) * 128 : kc + (((size_t)b * nkv + (hd - nh)) * max_seq + start + t) * 128;
-    dst[d] = o1; dst[d + 64] = o2;
+    vlm_rope_rotate_append<KV>((float)src[d], (float)src[d + 64], ang, hd, nh, nkv, d, row, b, start + t, max_seq, q_out, kc, ksc);
   }
 }
 
@@ -163,7 +164,7 @@ __global__ void vlm_rope_cache_kernel(const bf16* __restrict__ qkv, const int* _
 // rotate_half pair of frequency l).
 //   norm: the fp32 sum of squares over the wave, n = bf16(x * rsqrt(mean + eps)), y = bf16(w * n)   (Qwen3VLTextRMSNorm on a bf16 tensor)
 //   rope: frequency j takes the height position when j % 3 == 1 and j < 3 s1, the width position when j % 3 == 2 and j < 3 s2, the temporal
-//         one otherwise (apply_interleaved_mrope); cos / sin rounded to bf16, products and sum rounded as vlm_rope_cache_kernel does
+//         one otherwise (apply_interleaved_mrope); the rotation and the append are vlm_rope_rotate_append
 // KV, ksc, vsc: the cache format, as in vlm_rope_cache_kernel
 template <int KV>
 __global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ inv_freq, const bf16* __restrict__ qn,
@@ -194,16 +195,7 @@ __global__ void vlm3_qk_rope_cache_kernel(const bf16* __restrict__ qkv, const in
     const float rs = rsqrtf(ss / 128.f + eps);
     const bf16* w = hd < nh ? qn : kn;
     const float y1 = (float)(bf16)((float)w[lane] * (float)(bf16)(x1 * rs)), y2 = (float)(bf16)((float)w[lane + 64] * (float)(bf16)(x2 * rs));
-    const float ang = (float)pos[(size_t)comp * rows + row] * fr;
-    const float c = (float)(bf16)cosf(ang), s = (float)(bf16)sinf(ang);
-    const bf16 o1 = (bf16)((float)(bf16)(y1 * c) + (float)(bf16)(-y2 * s));
-    const bf16 o2 = (bf16)((float)(bf16)(y2 * c) + (float)(bf16)(y1 * s));
-    if (hd >= nh) {      // (wave-uniform)
-      vlm_kv_store_row<KV>(kc, ksc, ((size_t)b * nkv + (hd - nh)) * max_seq + start + t, lane, o1, o2);
-      continue;
-    }
-    bf16* dst = q_out + ((size_t)row * nh + hd) * 128;
-    dst[lane] = o1; dst[lane + 64] = o2;
+    vlm_rope_rotate_append<KV>(y1, y2, (float)pos[(size_t)comp * rows + row] * fr, hd, nh, nkv, lane, row, b, start + t, max_seq, q_out, kc, ksc);
   }
 }
 
@@ -296,80 +288,6 @@ __global__ void vlm_put_rows_kernel(bf16* __restrict__ x, const bf16* __restrict
   }
 }
 
-// ---- decode GEMV: y[m][n] = sum_k x[m][k] w[n][k] (+ bias) for M <= 4 sequences - the shape of every projection of a decode step at the
-// reference's batch sizes (vlm_batch_size 2, models/vlm_tagger.py:76). Pure weight streaming: one wave per TWO output columns, 16-byte
-// loads (8 weights per lane and row), the M activation rows come from L1 / L2; fp32 accumulation, one rounding to bf16 (or fp32 out
-// for the logits). HBM-bound: N * K * 2 bytes per launch.
-template <int MR, class TO>
-__global__ __launch_bounds__(256) void vlm_gemv_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ w, int ldw, const float* __restrict__ bias,
-                                                       TO* __restrict__ y, int ldy, int M, int N, int K) {
-  // one workgroup = two output columns; its four waves take interleaved 512-column steps of K (so even the 3584-column projections put
-  // 7 waves on every SIMD) and meet in LDS
-  __shared__ float red[4][MR][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * 2;
-  const bool two = n0 + 1 < N;
-  const bf16* w0 = w + (size_t)n0 * ldw;
-  const bf16* w1 = w + (size_t)(two ? n0 + 1 : n0) * ldw;
-  float a0[MR], a1[MR];
-#pragma unroll
-  for (int m = 0; m < MR; ++m) { a0[m] = 0.f; a1[m] = 0.f; }
-  // products on v_dot2c_f32_bf16 (two bf16 pairs per instruction, fp32 accumulate): no unpacking of either operand - with it the
-  // 2- and 4-sequence steps were bound by the vector ALU, not by the weight stream
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  auto dot8 = [](const uint4 p, const uint4 q, float acc) __attribute__((always_inline)) {
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, p.x), __builtin_bit_cast(bf2, q.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, p.y), __builtin_bit_cast(bf2, q.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, p.z), __builtin_bit_cast(bf2, q.z), acc, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, p.w), __builtin_bit_cast(bf2, q.w), acc, false);
-  };
-  auto fma8 = [&](const uint4 wa, const uint4 wb, const int k) __attribute__((always_inline)) {
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      if (m < M) {
-        const uint4 xs = *reinterpret_cast<const uint4*>(x + (size_t)m * ldx + k);
-        a0[m] = dot8(xs, wa, a0[m]);
-        a1[m] = dot8(xs, wb, a1[m]);
-      }
-    }
-  };
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));      // weights are read once per step: streamed past the caches
-  auto ldw8 = [](const bf16* ptr) __attribute__((always_inline)) {
-    const v4u a = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(ptr));
-    return make_uint4(a[0], a[1], a[2], a[3]);
-  };
-  int k = wave * 512 + lane * 8;
-  for (; k + 3 * 2048 < K; k += 4 * 2048) {      // four steps per trip, their eight weight loads issued before the first is used
-    uint4 wa[4], wb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { wa[j] = ldw8(w0 + k + 2048 * j); wb[j] = ldw8(w1 + k + 2048 * j); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fma8(wa[j], wb[j], k + 2048 * j);
-  }
-  for (; k + 2048 < K; k += 2 * 2048) {
-    const uint4 p0 = ldw8(w0 + k), q0 = ldw8(w1 + k), p1 = ldw8(w0 + k + 2048), q1 = ldw8(w1 + k + 2048);
-    fma8(p0, q0, k); fma8(p1, q1, k + 2048);
-  }
-  for (; k < K; k += 2048) fma8(ldw8(w0 + k), ldw8(w1 + k), k);
-#pragma unroll
-  for (int m = 0; m < MR; ++m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a0[m] += __shfl_xor(a0[m], o); a1[m] += __shfl_xor(a1[m], o); }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < MR; ++m) { red[wave][m][0] = a0[m]; red[wave][m][1] = a1[m]; }
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < 2 * MR) {
-    const int m = t >> 1, c = t & 1;
-    if (m < M && (c == 0 || two)) {
-      const float v = (red[0][m][c] + red[1][m][c]) + (red[2][m][c] + red[3][m][c]) + (bias ? bias[n0 + c] : 0.f);
-      stf(y + (size_t)m * ldy + n0 + c, v);
-    }
-  }
-}
 // ---- e4m3 weights (FE_VLM_WEIGHTS_E4M3): a Linear layer is [Cout][KpH] codes (ConvW.w8) and [Cout] scales 2^e (ConvW.w8_scale), the format
 // of fp8_core.h. Layout along K: PLAIN order, one byte per element, rows padded with zero codes to KpH (a multiple of 64) - code k of a
 // row multiplies activation k. v_cvt_scalef32_pk_bf16_fp8 (scale 1) widens two neighbouring codes of a 32-bit word to a packed bf16 pair
@@ -386,58 +304,76 @@ __device__ __forceinline__ void vlm_e4m3_widen16(const uint4 c, uint4& lo, uint4
   lo.x = vlm_e4m3_pair<false>(c.x); lo.y = vlm_e4m3_pair<true>(c.x); lo.z = vlm_e4m3_pair<false>(c.y); lo.w = vlm_e4m3_pair<true>(c.y);
   hi.x = vlm_e4m3_pair<false>(c.z); hi.y = vlm_e4m3_pair<true>(c.z); hi.z = vlm_e4m3_pair<false>(c.w); hi.w = vlm_e4m3_pair<true>(c.w);
 }
-// vlm_gemv_kernel on e4m3 rows: N * K bytes per launch. A lane takes 16 codes per 16-byte load, so a wave covers 1024 columns of K and the
-// four waves 4096 per step; K % 16 == 0. The conversion is 8 instructions per 16 weights of a column, shared by the M rows: against the
-// 16 M dot instructions of those weights it leaves the 2- and 4-row steps where the bf16 kernel has them.
-template <int MR, class TO>
-__global__ __launch_bounds__(256) void vlm_gemv_e4m3_kernel(const bf16* __restrict__ x, int ldx, const uint8_t* __restrict__ w, int ldw, const float* __restrict__ wscale,
-                                                            const float* __restrict__ bias, TO* __restrict__ y, int ldy, int M, int N, int K) {
+// acc + the dot product of 8 bf16 pairs on v_dot2c_f32_bf16 (two bf16 pairs per instruction, fp32 accumulate): no unpacking of either
+// operand - with it the 2- and 4-sequence GEMV steps were bound by the vector ALU, not by the weight stream
+__device__ __forceinline__ float vlm_dot8(const uint4 p, const uint4 q, float acc) {
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.x), __builtin_bit_cast(vlm_bf2, q.x), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.y), __builtin_bit_cast(vlm_bf2, q.y), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.z), __builtin_bit_cast(vlm_bf2, q.z), acc, false);
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.w), __builtin_bit_cast(vlm_bf2, q.w), acc, false);
+}
+
+// ---- decode GEMV: y[m][n] = sum_k x[m][k] w[n][k] (+ bias) for M <= 4 sequences - the shape of every projection of a decode step at the
+// reference's batch sizes (vlm_batch_size 2, models/vlm_tagger.py:76). Pure weight streaming: one wave per TWO output columns, 16-byte
+// loads, the M activation rows come from L1 / L2; fp32 accumulation, one rounding to bf16 (or fp32 out for the logits). HBM-bound.
+// WT = bf16: E = 8 weights per lane and load, N * K * 2 bytes per launch; K % 8 == 0.
+// WT = uint8_t: e4m3 rows (above), E = 16 codes per lane and load, N * K bytes per launch; K % 16 == 0. The conversion is 8 instructions
+// per 16 weights of a column, shared by the M rows: against the 16 M dot instructions of those weights it leaves the 2- and 4-row steps
+// where the bf16 weights have them. The row scale (wscale; unused for bf16) multiplies the merged fp32 sum before the bias.
+template <int MR, class TO, class WT>
+__global__ __launch_bounds__(256) void vlm_gemv_kernel(const bf16* __restrict__ x, int ldx, const WT* __restrict__ w, int ldw, const float* __restrict__ wscale,
+                                                       const float* __restrict__ bias, TO* __restrict__ y, int ldy, int M, int N, int K) {
+  constexpr bool F8 = sizeof(WT) == 1;
+  constexpr int E = F8 ? 16 : 8, STEP = 256 * E;
+  // one workgroup = two output columns; its four waves take interleaved 64 E-column steps of K (so even the 3584-column projections put
+  // 7 waves on every SIMD) and meet in LDS
   __shared__ float red[4][MR][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = blockIdx.x * 2;
   const bool two = n0 + 1 < N;
-  const uint8_t* w0 = w + (size_t)n0 * ldw;
-  const uint8_t* w1 = w + (size_t)(two ? n0 + 1 : n0) * ldw;
+  const WT* w0 = w + (size_t)n0 * ldw;
+  const WT* w1 = w + (size_t)(two ? n0 + 1 : n0) * ldw;
   float a0[MR], a1[MR];
 #pragma unroll
   for (int m = 0; m < MR; ++m) { a0[m] = 0.f; a1[m] = 0.f; }
-  auto dot8 = [](const uint4 p, const uint4 q, float acc) __attribute__((always_inline)) {
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.x), __builtin_bit_cast(vlm_bf2, q.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.y), __builtin_bit_cast(vlm_bf2, q.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.z), __builtin_bit_cast(vlm_bf2, q.z), acc, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(vlm_bf2, p.w), __builtin_bit_cast(vlm_bf2, q.w), acc, false);
-  };
-  auto fma16 = [&](const uint4 ca, const uint4 cb, const int k) __attribute__((always_inline)) {
-    uint4 al, ah, bl, bh;
-    vlm_e4m3_widen16(ca, al, ah);
-    vlm_e4m3_widen16(cb, bl, bh);
+  // one load's weights of both columns against activations k .. k + E - 1 of every row (e4m3: the low 8, then the high 8)
+  auto fma_step = [&](const uint4 wa, const uint4 wb, const int k) __attribute__((always_inline)) {
+    [[maybe_unused]] uint4 al, ah, bl, bh;
+    if constexpr (F8) { vlm_e4m3_widen16(wa, al, ah); vlm_e4m3_widen16(wb, bl, bh); }
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
       if (m < M) {
-        const uint4 xl = *reinterpret_cast<const uint4*>(x + (size_t)m * ldx + k), xh = *reinterpret_cast<const uint4*>(x + (size_t)m * ldx + k + 8);
-        a0[m] = dot8(xh, ah, dot8(xl, al, a0[m]));
-        a1[m] = dot8(xh, bh, dot8(xl, bl, a1[m]));
+        const bf16* xr = x + (size_t)m * ldx + k;
+        const uint4 xl = *reinterpret_cast<const uint4*>(xr);
+        if constexpr (F8) {
+          const uint4 xh = *reinterpret_cast<const uint4*>(xr + 8);
+          a0[m] = vlm_dot8(xh, ah, vlm_dot8(xl, al, a0[m]));
+          a1[m] = vlm_dot8(xh, bh, vlm_dot8(xl, bl, a1[m]));
+        } else {
+          a0[m] = vlm_dot8(xl, wa, a0[m]);
+          a1[m] = vlm_dot8(xl, wb, a1[m]);
+        }
       }
     }
   };
   typedef unsigned v4u __attribute__((ext_vector_type(4)));      // weights are read once per step: streamed past the caches
-  auto ldw16 = [](const uint8_t* ptr) __attribute__((always_inline)) {
+  auto ldw16 = [](const WT* ptr) __attribute__((always_inline)) {
     const v4u a = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(ptr));
     return make_uint4(a[0], a[1], a[2], a[3]);
   };
-  int k = wave * 1024 + lane * 16;
-  for (; k + 3 * 4096 < K; k += 4 * 4096) {      // four steps per trip, their eight weight loads issued before the first is used
+  int k = (wave * 64 + lane) * E;
+  for (; k + 3 * STEP < K; k += 4 * STEP) {      // four steps per trip, their eight weight loads issued before the first is used
     uint4 wa[4], wb[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { wa[j] = ldw16(w0 + k + 4096 * j); wb[j] = ldw16(w1 + k + 4096 * j); }
+    for (int j = 0; j < 4; ++j) { wa[j] = ldw16(w0 + k + STEP * j); wb[j] = ldw16(w1 + k + STEP * j); }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) fma16(wa[j], wb[j], k + 4096 * j);
+    for (int j = 0; j < 4; ++j) fma_step(wa[j], wb[j], k + STEP * j);
   }
-  for (; k + 4096 < K; k += 2 * 4096) {
-    const uint4 p0 = ldw16(w0 + k), q0 = ldw16(w1 + k), p1 = ldw16(w0 + k + 4096), q1 = ldw16(w1 + k + 4096);
-    fma16(p0, q0, k); fma16(p1, q1, k + 4096);
+  for (; k + STEP < K; k += 2 * STEP) {
+    const uint4 p0 = ldw16(w0 + k), q0 = ldw16(w1 + k), p1 = ldw16(w0 + k + STEP), q1 = ldw16(w1 + k + STEP);
+    fma_step(p0, q0, k); fma_step(p1, q1, k + STEP);
   }
-  for (; k < K; k += 4096) fma16(ldw16(w0 + k), ldw16(w1 + k), k);
+  for (; k < K; k += STEP) fma_step(ldw16(w0 + k), ldw16(w1 + k), k);
 #pragma unroll
   for (int m = 0; m < MR; ++m) {
 #pragma unroll
@@ -452,8 +388,9 @@ __global__ __launch_bounds__(256) void vlm_gemv_e4m3_kernel(const bf16* __restri
   if (t < 2 * MR) {
     const int m = t >> 1, c = t & 1;
     if (m < M && (c == 0 || two)) {
-      const float v = ((red[0][m][c] + red[1][m][c]) + (red[2][m][c] + red[3][m][c])) * wscale[n0 + c] + (bias ? bias[n0 + c] : 0.f);
-      stf(y + (size_t)m * ldy + n0 + c, v);
+      float v = (red[0][m][c] + red[1][m][c]) + (red[2][m][c] + red[3][m][c]);
+      if constexpr (F8) v *= wscale[n0 + c];
+      stf(y + (size_t)m * ldy + n0 + c, v + (bias ? bias[n0 + c] : 0.f));
     }
   }
 }
@@ -462,21 +399,13 @@ static bool vlm_e4m3_gemv_ok(const ConvW& w) { return w.CinPadH % 16 == 0; }
 template <class TO>
 static void vlm_gemv(Ctx& c, const ConvW& w, const bf16* x, int ldx, int M, TO* y, int ldy, VlmLinearInfo* info = nullptr) {
   if (info) *info = VlmLinearInfo{VLM_LIN_GEMV, M == 1 ? 1 : M == 2 ? 2 : 4, 0, 0};
-  if (w.w8) {
-    FE_CHECK(w.w8_scale && vlm_e4m3_gemv_ok(w) && w.KpH % 16 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv(e4m3): unsupported layer");
-    const int K = w.CinPadH, blocks = (w.Cout + 1) / 2;
-#define VLM_GEMV8(MR) hipLaunchKernelGGL((vlm_gemv_e4m3_kernel<MR, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const uint8_t*)w.w8, w.KpH, (const float*)w.w8_scale, (const float*)w.shift, y, ldy, M, w.Cout, K)
-    if (M == 1) VLM_GEMV8(1); else if (M == 2) VLM_GEMV8(2); else VLM_GEMV8(4);
-#undef VLM_GEMV8
-    FE_HIP(hipGetLastError());
-    c.flops_accum += 2.0 * M * (double)w.Cin * w.Cout;
-    return;
-  }
-  FE_CHECK(w.wh && w.hprec == PREC_BF16 && w.KpH % 8 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv: unsupported layer");
+  if (w.w8) FE_CHECK(w.w8_scale && vlm_e4m3_gemv_ok(w) && w.KpH % 16 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv(e4m3): unsupported layer");
+  else FE_CHECK(w.wh && w.hprec == PREC_BF16 && w.KpH % 8 == 0 && ldx % 8 == 0 && M >= 1 && M <= 4 && !w.scale, "vlm_gemv: unsupported layer");
   const int K = w.CinPadH, blocks = (w.Cout + 1) / 2;
-  if (M == 1) hipLaunchKernelGGL((vlm_gemv_kernel<1, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, (const float*)w.shift, y, ldy, M, w.Cout, K);
-  else if (M == 2) hipLaunchKernelGGL((vlm_gemv_kernel<2, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, (const float*)w.shift, y, ldy, M, w.Cout, K);
-  else hipLaunchKernelGGL((vlm_gemv_kernel<4, TO>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const bf16*)w.wh, w.KpH, (const float*)w.shift, y, ldy, M, w.Cout, K);
+#define VLM_GEMV(MR, WT, wp, ws) hipLaunchKernelGGL((vlm_gemv_kernel<MR, TO, WT>), dim3(blocks), dim3(256), 0, c.stream, x, ldx, (const WT*)(wp), w.KpH, (const float*)(ws), (const float*)w.shift, y, ldy, M, w.Cout, K)
+  if (w.w8) { if (M == 1) VLM_GEMV(1, uint8_t, w.w8, w.w8_scale); else if (M == 2) VLM_GEMV(2, uint8_t, w.w8, w.w8_scale); else VLM_GEMV(4, uint8_t, w.w8, w.w8_scale); }
+  else { if (M == 1) VLM_GEMV(1, bf16, w.wh, nullptr); else if (M == 2) VLM_GEMV(2, bf16, w.wh, nullptr); else VLM_GEMV(4, bf16, w.wh, nullptr); }
+#undef VLM_GEMV
   FE_HIP(hipGetLastError());
   c.flops_accum += 2.0 * M * (double)w.Cin * w.Cout;
 }
@@ -960,130 +889,40 @@ __device__ __forceinline__ float vlm_row16_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));      // row_mirror
   return v;
 }
+// One kernel body for both cache storages. CT = bf16: a key row is 256 bytes, 16 lanes per key with 8 values each (16-byte loads, 1 KiB
+// contiguous per wave instruction). CT = uint8_t, an FE_VLM_KV_E4M3 cache: a key row is 128 contiguous codes, 16 lanes per key with 8
+// codes each (8-byte loads, 512 contiguous bytes per wave instruction), widened by v_cvt_scalef32_pk_f32_fp8 (gfx950: the OCP reading,
+// scale 1) - half the K / V bytes. The K scale multiplies the score, (sum * kscale) * scale, and the V scale the bf16-rounded probability,
+// both exactly (powers of two): the bf16 arithmetic on the dequantised rows, with the products and sums in its order (ksc / vsc: the scale
+// arrays, unused for bf16). q stays bf16, accumulation fp32, the running sum pl comes from the unrounded exponentials.
+// Both forms are bound by the vector ALU, not by the K / V bytes (G = 7, 32 sequences x 1716 keys: bf16 40 us, 2.8 TB/s). The file is
+// compiled without contraction, and the bf16 form keeps its separate multiply and add per term (its test bounds and the recorded token ids
+// rest on that rounding); the e4m3 form, written after them, takes explicit fused multiply-adds in the dot products and the P V sums: 1892
+// against 2777 vector instructions at G = 7, 34 us (profiles/vlm_fp8_kv_perf.txt).
 constexpr int VLM_DEC_CHUNK = 128;
-template <int G>
-__global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16* __restrict__ q, const bf16* __restrict__ kc, const bf16* __restrict__ vc, float* __restrict__ po,
-                                                                  float* __restrict__ pm, float* __restrict__ pl, int nh, int nkv, int Lk, int max_seq, float scale,
-                                                                  const int* __restrict__ len_dev, int nsplit, const int* __restrict__ pad) {
-  __shared__ float sc[G][VLM_DEC_CHUNK];      // scores, then probabilities
-  __shared__ float part[4][G][128];
-  if (len_dev) Lk = *len_dev + 1;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int bk = blockIdx.x, sp = blockIdx.y;
-  const int b = bk / nkv, kvh = bk - b * nkv, head0 = kvh * G;
-  const int k0 = sp * VLM_DEC_CHUNK, k1 = min(k0 + VLM_DEC_CHUNK, Lk);
-  const int padb = pad[b];      // keys below it are left padding
-  if (k0 >= Lk || k1 <= padb) {      // a chunk past the cache length or wholly in the pad: neutral element of the merge
-    if (t < G) { pm[((size_t)b * nh + head0 + t) * nsplit + sp] = -INFINITY; pl[((size_t)b * nh + head0 + t) * nsplit + sp] = 0.f; }
-    return;
-  }
-  const bf16* const K = kc + ((size_t)b * nkv + kvh) * max_seq * 128;
-  const bf16* const V = vc + ((size_t)b * nkv + kvh) * max_seq * 128;
-  // ---- scores: 16 lanes per key (8 dims each), 4 keys per wave instruction, 32 keys per wave ---------------------------------------------
-  {
-    const int sub = lane & 15, kk = lane >> 4;
-    float qf[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g) h_unpack8_bf16(*reinterpret_cast<const uint4*>(q + ((size_t)b * nh + head0 + g) * 128 + 8 * sub), qf[g]);
-    uint4 kr[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int key = k0 + wave * 32 + it * 4 + kk;
-      kr[it] = *reinterpret_cast<const uint4*>(K + (size_t)min(key, k1 - 1) * 128 + 8 * sub);
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int kl = wave * 32 + it * 4 + kk;
-      float kf[8];
-      h_unpack8_bf16(kr[it], kf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        float a = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a += kf[e] * qf[g][e];
-        a = vlm_row16_sum(a);
-        if (sub == 0) sc[g][kl] = (k0 + kl < k1 && k0 + kl >= padb) ? a * scale : -INFINITY;
-      }
-    }
-  }
-  __syncthreads();
-  // ---- softmax pieces per head: wave w takes heads w, w + 4; 2 keys per lane ---------------------------------------------------------------
-  for (int g = wave; g < G; g += 4) {
-    const float s0 = sc[g][lane], s1 = sc[g][64 + lane];
-    float mx = fmaxf(s0, s1);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    // probabilities as bf16 (the P operand of the reference's P V product)
-    const float e0 = (float)(bf16)__expf(s0 - mx), e1 = (float)(bf16)__expf(s1 - mx);
-    float sum = __expf(s0 - mx) + __expf(s1 - mx);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-    sc[g][lane] = e0; sc[g][64 + lane] = e1;
-    if (lane == 0) { pm[((size_t)b * nh + head0 + g) * nsplit + sp] = mx; pl[((size_t)b * nh + head0 + g) * nsplit + sp] = sum; }
-  }
-  __syncthreads();
-  // ---- O partials: the same 16-lanes-per-row pattern on V (eight 1-KiB loads per wave in flight): lane (sub, kk) accumulates dims
-  // 8 sub .. 8 sub + 7 over keys 32 wave + 4 it + kk for every head; the four kk groups are then added with two shuffles -----------------------
-  {
-    const int sub = lane & 15, kk = lane >> 4;
-    uint4 vr[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int key = k0 + wave * 32 + it * 4 + kk;
-      vr[it] = *reinterpret_cast<const uint4*>(V + (size_t)min(key, k1 - 1) * 128 + 8 * sub);
-    }
-    float a[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a[g][e] = 0.f;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int kl = wave * 32 + it * 4 + kk;      // probabilities of keys past the chunk's end are zero
-      float vf[8];
-      h_unpack8_bf16(vr[it], vf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float pj = sc[g][kl];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[g][e] += pj * vf[e];
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = a[g][e];
-        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-        if (kk == 0) part[wave][g][8 * sub + e] = v;
-      }
-  }
-  __syncthreads();
-  for (int i = t; i < G * 128; i += 256) {
-    const int g = i >> 7, dm = i & 127;
-    po[(((size_t)b * nh + head0 + g) * nsplit + sp) * 128 + dm] = (part[0][g][dm] + part[1][g][dm]) + (part[2][g][dm] + part[3][g][dm]);
-  }
-}
-// vlm_attn_decode_gqa_kernel on an FE_VLM_KV_E4M3 cache: the same grid, chunks, pad / len_dev handling and po / pm / pl outputs (and
-// vlm_attn_combine_kernel after it), half the K / V bytes. A key row is 128 contiguous codes: 16 lanes per key with 8 codes each (8-byte
-// loads, 512 contiguous bytes per wave instruction), widened by v_cvt_scalef32_pk_f32_fp8 (gfx950: the OCP reading, scale 1). The K scale
-// multiplies the score and the V scale the bf16-rounded probability, both exactly (powers of two): this is the bf16 kernel's arithmetic on
-// the dequantised rows, with the products and sums in its order. q stays bf16, accumulation fp32. Both kernels are bound by the vector ALU,
-// not by the K / V bytes (G = 7, 32 sequences x 1716 keys: the bf16 kernel 40 us, 2.8 TB/s), so the dot products and the P V sums here are
-// explicit fused multiply-adds - the file is compiled without contraction, which costs the bf16 kernel a multiply and an add per term:
-// 1892 against 2777 vector instructions at G = 7, 34 us (profiles/vlm_fp8_kv_perf.txt).
 __device__ __forceinline__ void vlm_e4m3_unpack8(const uint2 c, float v[8]) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   const f2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.x, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.x, 1.0f, true);
   const f2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.y, 1.0f, false), e = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(c.y, 1.0f, true);
   v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1]; v[4] = d[0]; v[5] = d[1]; v[6] = e[0]; v[7] = e[1];
 }
-template <int G>
-__global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const bf16* __restrict__ q, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc,
-                                                                       const float* __restrict__ ksc, const float* __restrict__ vsc, float* __restrict__ po,
-                                                                       float* __restrict__ pm, float* __restrict__ pl, int nh, int nkv, int Lk, int max_seq, float scale,
-                                                                       const int* __restrict__ len_dev, int nsplit, const int* __restrict__ pad) {
-  __shared__ float sc[G][VLM_DEC_CHUNK];      // scores, then probabilities times the V scales
+// a lane's 8 values of a cache row: 8 bf16 or 8 e4m3 codes
+__device__ __forceinline__ void vlm_kv_unpack8(const uint4 u, float v[8]) { h_unpack8_bf16(u, v); }
+__device__ __forceinline__ void vlm_kv_unpack8(const uint2 c, float v[8]) { vlm_e4m3_unpack8(c, v); }
+// a + x * y: fused for the e4m3 cache, a rounded product and a rounded sum for bf16
+template <bool FUSED>
+__device__ __forceinline__ float vlm_kv_madd(const float x, const float y, const float a) {
+  if constexpr (FUSED) return __builtin_fmaf(x, y, a);
+  else return a + x * y;
+}
+template <int G, class CT>
+__global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_kernel(const bf16* __restrict__ q, const CT* __restrict__ kc, const CT* __restrict__ vc,
+                                                                  const float* __restrict__ ksc, const float* __restrict__ vsc, float* __restrict__ po,
+                                                                  float* __restrict__ pm, float* __restrict__ pl, int nh, int nkv, int Lk, int max_seq, float scale,
+                                                                  const int* __restrict__ len_dev, int nsplit, const int* __restrict__ pad) {
+  constexpr bool F8 = sizeof(CT) == 1;
+  using Slice = std::conditional_t<F8, uint2, uint4>;      // a lane's 8 values of a row
+  __shared__ float sc[G][VLM_DEC_CHUNK];      // scores, then probabilities (e4m3: times the V scales)
   __shared__ float part[4][G][128];
   if (len_dev) Lk = *len_dev + 1;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1096,36 +935,39 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const 
     return;
   }
   const size_t row0 = ((size_t)b * nkv + kvh) * max_seq;
-  const uint8_t* const K = kc + row0 * 128;
-  const uint8_t* const V = vc + row0 * 128;
-  const float* const KS = ksc + row0;
-  const float* const VS = vsc + row0;
-  // ---- scores: 16 lanes per key (8 codes each), 4 keys per wave instruction, 32 keys per wave ----------------------------------------------
+  const CT* const K = kc + row0 * 128;
+  const CT* const V = vc + row0 * 128;
+  [[maybe_unused]] const float* const KS = F8 ? ksc + row0 : nullptr;      // the rows' scales (e4m3 only)
+  [[maybe_unused]] const float* const VS = F8 ? vsc + row0 : nullptr;
+  // ---- scores: 16 lanes per key (8 dims each), 4 keys per wave instruction, 32 keys per wave ---------------------------------------------
   {
     const int sub = lane & 15, kk = lane >> 4;
     float qf[G][8];
 #pragma unroll
     for (int g = 0; g < G; ++g) h_unpack8_bf16(*reinterpret_cast<const uint4*>(q + ((size_t)b * nh + head0 + g) * 128 + 8 * sub), qf[g]);
-    uint2 kr[8];
-    float ks[8];
+    Slice kr[8];
+    [[maybe_unused]] float ks[8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int key = min(k0 + wave * 32 + it * 4 + kk, k1 - 1);
-      kr[it] = *reinterpret_cast<const uint2*>(K + (size_t)key * 128 + 8 * sub);
-      ks[it] = KS[key];
+      kr[it] = *reinterpret_cast<const Slice*>(K + (size_t)key * 128 + 8 * sub);
+      if constexpr (F8) ks[it] = KS[key];
     }
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int kl = wave * 32 + it * 4 + kk;
       float kf[8];
-      vlm_e4m3_unpack8(kr[it], kf);
+      vlm_kv_unpack8(kr[it], kf);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         float a = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a = __builtin_fmaf(kf[e], qf[g][e], a);
+        for (int e = 0; e < 8; ++e) a = vlm_kv_madd<F8>(kf[e], qf[g][e], a);
         a = vlm_row16_sum(a);
-        if (sub == 0) sc[g][kl] = (k0 + kl < k1 && k0 + kl >= padb) ? (a * ks[it]) * scale : -INFINITY;
+        if (sub == 0) {
+          if constexpr (F8) a *= ks[it];
+          sc[g][kl] = (k0 + kl < k1 && k0 + kl >= padb) ? a * scale : -INFINITY;
+        }
       }
     }
   }
@@ -1136,8 +978,9 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const 
     float mx = fmaxf(s0, s1);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    // probabilities as bf16 (the P operand of the reference's P V product), then times the key's V scale: p * (2^e * code) = (p * 2^e) * code
-    const float e0 = (float)(bf16)__expf(s0 - mx) * VS[min(k0 + lane, k1 - 1)], e1 = (float)(bf16)__expf(s1 - mx) * VS[min(k0 + 64 + lane, k1 - 1)];
+    // probabilities as bf16 (the P operand of the reference's P V product); e4m3: then times the key's V scale, p * (2^e * code) = (p * 2^e) * code
+    float e0 = (float)(bf16)__expf(s0 - mx), e1 = (float)(bf16)__expf(s1 - mx);
+    if constexpr (F8) { e0 *= VS[min(k0 + lane, k1 - 1)]; e1 *= VS[min(k0 + 64 + lane, k1 - 1)]; }
     float sum = __expf(s0 - mx) + __expf(s1 - mx);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
@@ -1145,15 +988,15 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const 
     if (lane == 0) { pm[((size_t)b * nh + head0 + g) * nsplit + sp] = mx; pl[((size_t)b * nh + head0 + g) * nsplit + sp] = sum; }
   }
   __syncthreads();
-  // ---- O partials: the same 16-lanes-per-row pattern on V: lane (sub, kk) accumulates dims 8 sub .. 8 sub + 7 over keys 32 wave + 4 it + kk
-  // for every head; the four kk groups are then added with two shuffles ------------------------------------------------------------------
+  // ---- O partials: the same 16-lanes-per-row pattern on V (eight loads per wave in flight): lane (sub, kk) accumulates dims
+  // 8 sub .. 8 sub + 7 over keys 32 wave + 4 it + kk for every head; the four kk groups are then added with two shuffles -----------------------
   {
     const int sub = lane & 15, kk = lane >> 4;
-    uint2 vr[8];
+    Slice vr[8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int key = k0 + wave * 32 + it * 4 + kk;
-      vr[it] = *reinterpret_cast<const uint2*>(V + (size_t)min(key, k1 - 1) * 128 + 8 * sub);
+      vr[it] = *reinterpret_cast<const Slice*>(V + (size_t)min(key, k1 - 1) * 128 + 8 * sub);
     }
     float a[G][8];
 #pragma unroll
@@ -1164,12 +1007,12 @@ __global__ __launch_bounds__(256, 3) void vlm_attn_decode_gqa_e4m3_kernel(const 
     for (int it = 0; it < 8; ++it) {
       const int kl = wave * 32 + it * 4 + kk;      // probabilities of keys past the chunk's end are zero
       float vf[8];
-      vlm_e4m3_unpack8(vr[it], vf);
+      vlm_kv_unpack8(vr[it], vf);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const float pj = sc[g][kl];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[g][e] = __builtin_fmaf(pj, vf[e], a[g][e]);
+        for (int e = 0; e < 8; ++e) a[g][e] = vlm_kv_madd<F8>(pj, vf[e], a[g][e]);
       }
     }
 #pragma unroll
@@ -1413,13 +1256,14 @@ void vlm_decode_attention(Ctx& c, const VlmKv& kv, const bf16* q, int B, int nh,
   FE_CHECK(nkv > 0 && nh % nkv == 0 && Lk > 0 && Lk <= kv.max_seq && nsplit == ((len_dev ? kv.max_seq : Lk) + VLM_DEC_CHUNK - 1) / VLM_DEC_CHUNK, "vlm decode attention: bad shape");
   const bool f8 = kv.format == FE_VLM_KV_E4M3;
   FE_CHECK(!f8 || (kv.ks && kv.vs), "vlm decode attention: an e4m3 cache without scales");
-#define VLM_DEC_LAUNCH(GG)                                                                                                                            \
-  if (f8)                                                                                                                                             \
-    hipLaunchKernelGGL(vlm_attn_decode_gqa_e4m3_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, q, (const uint8_t*)kv.k, (const uint8_t*)kv.v, \
-                       (const float*)kv.ks, (const float*)kv.vs, po, pm, pl, nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad);                   \
-  else                                                                                                                                                \
-    hipLaunchKernelGGL(vlm_attn_decode_gqa_kernel<GG>, dim3(B * nkv, nsplit), dim3(256), 0, c.stream, q, (const bf16*)kv.k, (const bf16*)kv.v, po, pm, pl, \
-                       nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad)
+  const dim3 grid(B * nkv, nsplit);
+#define VLM_DEC_LAUNCH(GG)                                                                                                                                  \
+  if (f8)                                                                                                                                                   \
+    hipLaunchKernelGGL((vlm_attn_decode_gqa_kernel<GG, uint8_t>), grid, dim3(256), 0, c.stream, q, (const uint8_t*)kv.k, (const uint8_t*)kv.v,                  \
+                       (const float*)kv.ks, (const float*)kv.vs, po, pm, pl, nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad);                         \
+  else                                                                                                                                                      \
+    hipLaunchKernelGGL((vlm_attn_decode_gqa_kernel<GG, bf16>), grid, dim3(256), 0, c.stream, q, (const bf16*)kv.k, (const bf16*)kv.v, (const float*)kv.ks,      \
+                       (const float*)kv.vs, po, pm, pl, nh, nkv, Lk, kv.max_seq, scale, len_dev, nsplit, pad)
   switch (G) {
     case 1: VLM_DEC_LAUNCH(1); break;
     case 2: VLM_DEC_LAUNCH(2); break;

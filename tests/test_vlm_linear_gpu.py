@@ -36,7 +36,7 @@ dequantize(quantize(w))). u = 2^-24, S = sum_k |x_k w_k| + |bias|. Every bound i
 The worst err / bound per route and format is printed by every test (pytest -s); DESIGN.md records them.
 
 Which case reaches what:
-  * vlm_gemv_kernel<1|2|4> / vlm_gemv_e4m3_kernel<1|2|4>, bf16 and fp32 out: test_gemv, M = 1, 2, 3 auto and 4 forced. K = 8 / 16 (one
+  * vlm_gemv_kernel<1|2|4, TO, bf16> / vlm_gemv_kernel<1|2|4, TO, uint8_t>, bf16 and fp32 out: test_gemv, M = 1, 2, 3 auto and 4 forced. K = 8 / 16 (one
     lane), 520 / 1040 (wave 0 only, ragged), 2048 / 4096 (all four waves full), 2056 / 4112 (third loop twice for lane 0),
     6152 / 12304 (second loop + tail), 12296 / 24592 (one trip of each loop + a one-lane tail); N = 1, 2, 5 (single column, odd last pair)
   * ldx != K: test_gemv_ldx (K = 520 in rows of 544) and test_gemm32_ldx

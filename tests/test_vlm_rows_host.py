@@ -40,9 +40,17 @@ def test_the_helpers_are_the_only_launch_sites():
     """Each of these kernels is launched from one host function, which vlm_forward and the hooks call."""
     src = "".join(open(os.path.join(ROOT, "facet_amd", "csrc", f)).read() for f in ("model_vlm.hip", "model_vlm_vision.hip", "model_vlm_ln_vision.hip", "capi_ops.hip",
                                                                                   "capi_vlm.hip"))
+    launch = lambda kernel, text: len(re.findall(r"hipLaunchKernelGGL\(\(?%s" % re.escape(kernel), text))
     for kernel, sites in (("vlm_rope_cache_kernel<", 1), ("vlm3_qk_rope_cache_kernel<", 1), ("vlm_rmsnorm_kernel,", 1), ("vlm_add_kernel,", 1),
-                          ("vlm_silu_mul_kernel,", 1), ("vlm_add_rmsnorm_kernel<", 2), ("vlm_vis_rope_kernel<", 2)):
-        assert len(re.findall(r"hipLaunchKernelGGL\(\(?%s" % re.escape(kernel), src)) == sites, kernel
+                          ("vlm_silu_mul_kernel,", 1), ("vlm_add_rmsnorm_kernel<", 2), ("vlm_vis_rope_kernel<", 2), ("vlm_attn_decode_gqa_kernel<", 2),
+                          ("vlm_gemv_kernel<", 1)):
+        assert launch(kernel, src) == sites, kernel
+    assert "_e4m3_kernel" not in src          # one decode attention and one GEMV kernel name, whatever the storage
+    # the decode attention (one launch per cache storage) and the GEMV are launched inside their host functions and nowhere else
+    attn = src[src.index("void vlm_decode_attention("):src.index("void vlm_prefill_attention(")]
+    gemv = src[src.index("static void vlm_gemv("):src.index("vlm_gemm32_kernel(")]
+    assert launch("vlm_attn_decode_gqa_kernel<GG, uint8_t>", attn) == 1 and launch("vlm_attn_decode_gqa_kernel<GG, bf16>", attn) == 1
+    assert launch("vlm_gemv_kernel<MR, TO, WT>", gemv) == 1
     fwd = src[src.index("void vlm_forward("):src.index("void vlm_select(")]
     assert "hipLaunchKernelGGL(vlm_finish_add_rmsnorm_kernel" not in fwd and fwd.count("vlm_few_rows_rmsnorm(") == 2 and "vlm_rope_cache(c, rope" in fwd
 
