@@ -249,6 +249,8 @@ SIGNATURES = {
     "fe_jpeg_thumbnail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "fe_hamming_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, _i64p]),
+    "fe_burst_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+                                 C.c_int64, C.c_void_p]),
     "fe_knn_core_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fe_mreach_mst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
@@ -265,6 +267,7 @@ FE_SIM_K_MAX = 32
 FE_JPEG_PROGRESSIVE = 1    # flag of fe_jpeg_probe_ex / fe_jpeg_decode_ex (and the status of a progressive file without it)
 FE_JPEG_FLAG_PARALLEL = 0x100      # flag of the decode entry points: baseline segments decoded by one lane per 128-byte subsequence
 FE_SIM_NO_DATE = -(1 << 63)
+FE_BURST_HAS_HASH, FE_BURST_HAS_DATE = 1, 2      # flags of fe_burst_links
 
 
 class _SimRowsC(C.Structure):
@@ -2035,6 +2038,42 @@ class Engine:
                 return pairs[:count.value].copy()
             room = count.value
         raise EngineError(f"hamming_pairs: {count.value} pairs found after making room for {room}")
+
+    def burst_links(self, hashes, times, flags, thr, window_s, rapid_s, person_off=None, person_ids=None):
+        """Rows in the reference's burst order. hashes: uint64 [n] (host array) or (device_ptr, n); times: int64 [n] seconds; flags:
+        uint8 [n] of FE_BURST_HAS_HASH | FE_BURST_HAS_DATE; person_off int32 [n+1] / person_ids int32: CSR lists, ascending and distinct
+        per row, or both None; thr / window_s / rapid_s: the settings floored to integers (facet_amd.bursts.burst_settings).
+        -> int32 [n]: per row the largest earlier row it is similar to, or -1 (fe_burst_links)."""
+        if isinstance(hashes, tuple):
+            p, n = hashes
+            dev, keep = 1, None
+        else:
+            keep = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1)
+            p, n, dev = keep.ctypes.data_as(C.c_void_p), keep.shape[0], 0
+        n = int(n)
+        t = np.ascontiguousarray(times, dtype=np.int64).reshape(-1)
+        f = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        if t.shape[0] != n or f.shape[0] != n:
+            raise ValueError(f"burst_links: {n} hashes, {t.shape[0]} times, {f.shape[0]} flags")
+        if (person_off is None) != (person_ids is None):
+            raise ValueError("burst_links: person_off and person_ids go together")
+        off = ids = None
+        if person_off is not None:
+            off = np.ascontiguousarray(person_off, dtype=np.int32).reshape(-1)
+            ids = np.ascontiguousarray(person_ids, dtype=np.int32).reshape(-1)
+            if off.shape[0] != n + 1:
+                raise ValueError(f"burst_links: person_off has {off.shape[0]} entries for {n} rows")
+        n_ids = 0 if ids is None else ids.shape[0]
+        if ids is not None and n_ids == 0:
+            ids = np.zeros(1, np.int32)                            # a pointer that is not null; none of it is read
+        lim = (1 << 63) - 1
+        clamp = lambda v, m: max(-m - 1, min(int(v), m))          # whatever the settings gave, as a C integer
+        link = np.empty(n, np.int32)
+        self._ck(self.lib.fe_burst_links(self.h, p, dev, t.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), n,
+                                         off.ctypes.data_as(C.c_void_p) if off is not None else None,
+                                         ids.ctypes.data_as(C.c_void_p) if ids is not None else None, n_ids,
+                                         clamp(thr, (1 << 31) - 1), clamp(window_s, lim), clamp(rapid_s, lim), link.ctypes.data_as(C.c_void_p)))
+        return link
 
     @staticmethod
     def _rows_ptr(x):

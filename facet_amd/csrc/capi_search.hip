@@ -71,6 +71,42 @@ int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, 
   });
 }
 
+/* per row the largest earlier row it is similar to: the pair test of process_bursts (reference processing/scorer.py:1943-1968) */
+int fe_burst_links(fe_ctx* ctx, const uint64_t* hashes, int on_device, const int64_t* times, const uint8_t* flags, int n, const int32_t* person_off,
+                   const int32_t* person_ids, int n_person_ids, int thr, int64_t window_s, int64_t rapid_s, int32_t* link) {
+  return fe_api(ctx, [&] {
+    Ctx& C = ctx->c;
+    char b[200];
+    auto invalid = [&](const char* msg) { ctx->c.err = std::string("fe_burst_links: ") + msg; return FE_ERR_INVALID; };
+    if (n < 0) return invalid("negative n");
+    if (n == 0) return FE_OK;
+    if (!hashes || !times || !flags || !link) return invalid("null pointer");
+    if (n_person_ids < 0 || (person_off == nullptr) != (person_ids == nullptr)) return invalid("person_off and person_ids go together, n_person_ids >= 0");
+    const int64_t t_max = (int64_t)1 << 61;
+    for (int i = 0; i < n; ++i) {
+      if (flags[i] & ~(FE_BURST_HAS_HASH | FE_BURST_HAS_DATE)) { snprintf(b, sizeof(b), "flags[%d] = %d has bits outside FE_BURST_HAS_HASH | FE_BURST_HAS_DATE", i, (int)flags[i]); return invalid(b); }
+      if ((flags[i] & FE_BURST_HAS_DATE) && (times[i] < -t_max || times[i] > t_max)) { snprintf(b, sizeof(b), "times[%d] = %lld is outside +-2^61", i, (long long)times[i]); return invalid(b); }
+    }
+    if (person_off) {
+      if (person_off[0] < 0 || person_off[n] > n_person_ids) { snprintf(b, sizeof(b), "person_off runs from %d to %d with %d ids", person_off[0], person_off[n], n_person_ids); return invalid(b); }
+      for (int i = 0; i < n; ++i)
+        if (person_off[i] > person_off[i + 1]) { snprintf(b, sizeof(b), "person_off[%d] = %d > person_off[%d] = %d", i, person_off[i], i + 1, person_off[i + 1]); return invalid(b); }
+      for (int i = 0; i < n; ++i)                                      // every offset is now known to lie in 0 .. n_person_ids
+        for (int k = person_off[i] + 1; k < person_off[i + 1]; ++k)
+          if (person_ids[k - 1] >= person_ids[k]) { snprintf(b, sizeof(b), "person ids of row %d are not ascending and distinct", i); return invalid(b); }
+    }
+    if (n == 1) { link[0] = -1; return FE_OK; }
+    // dist is 0 .. 64 or 999 and d is below 2^62: beyond these the settings change nothing
+    const int thr_c = std::max(-1, std::min(thr, 999));
+    const int64_t s_max = (int64_t)1 << 62;
+    const int64_t window_c = std::max<int64_t>(-1, std::min(window_s, s_max)), rapid_c = std::max<int64_t>(-1, std::min(rapid_s, s_max));
+    C.arena.reset();
+    const uint64_t* d_h = resident(C, hashes, (size_t)n, on_device);
+    burst_links(C, d_h, times, flags, n, person_off, person_ids, n_person_ids, thr_c, window_c, rapid_c, link);
+    return FE_OK;
+  });
+}
+
 /* core distance (distance to the k-th nearest row, the row itself counted) of every row: HDBSCAN's first stage (reference faces/clusterer.py:188-197) */
 int fe_knn_core_distances(fe_ctx* ctx, const float* x, int n, int d, int on_device, int normalise, int k, double* core, int32_t* core_idx) {
   return fe_api(ctx, [&] {

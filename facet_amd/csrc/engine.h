@@ -269,6 +269,11 @@ void launch_phash_mixed(Ctx& c, const PhashDesc* d_descs, int n, size_t rows, in
                         const double* d_cos, uint64_t* d_hashes, uint8_t* d_small, double* d_dct);
 void launch_hamming_pairs(const uint64_t* d_hashes, int n, int maxd, int64_t cap, int* d_pairs, unsigned long long* d_count, hipStream_t s);
 
+// ---- burst links over stored hashes (kernels_burst.hip; arguments as fe_burst_links, already checked and clamped) ----
+void burst_lower_bounds(const int64_t* times, const uint8_t* flags, int n, int64_t reach, int32_t* lo);   // host
+void burst_links(Ctx& c, const uint64_t* d_hash, const int64_t* times, const uint8_t* flags, int n, const int32_t* person_off, const int32_t* person_ids,
+                 int n_ids, int thr, int64_t window_s, int64_t rapid_s, int32_t* link);
+
 // ---- face clustering sweeps: core distances, mutual-reachability MST, best cosine match (kernels_cluster.hip) ----
 int cluster_max_rounds(int n);                           // ceil(log2 n) + 1: the Boruvka round bound
 void cluster_core_distances(Ctx& c, const float* x, int n, int d, int on_device, int normalise, int k, double* core, int32_t* core_idx);

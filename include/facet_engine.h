@@ -921,6 +921,27 @@ int fe_resize_cache_entries(fe_ctx* ctx, int32_t* entries);
 int fe_hamming_pairs(fe_ctx* ctx, const uint64_t* hashes, int n, int on_device, int max_distance, int64_t max_pairs, int32_t* pairs,
                      int64_t* count);
 
+/* Burst detection over stored hashes (reference processing/scorer.py:1880-1986, `process_bursts`: a Python loop that compares each
+ * photo with every member of the open burst and parses both date strings per comparison). Rows are in the reference's order
+ * (`ORDER BY date_taken`). link [n] (host) receives, per row i, the largest j < i with similar(i, j), or -1:
+ *   both rows have FE_BURST_HAS_DATE, d = |times[i] - times[j]|, dist = popcount(hashes[i] ^ hashes[j]), or 999 unless both rows
+ *   have FE_BURST_HAS_HASH, and
+ *     d <= window_s and dist <= thr, or
+ *     d <= rapid_s and dist <= 2 thr and the rows share a person (either list empty, or the lists intersect).
+ * The open burst of the reference is the run [s, i-1], so row i joins it exactly when link[i] >= s; that recurrence and the choice
+ * of the lead are the caller's (facet_amd/bursts.py). hashes [n] on the host (on_device = 0) or the device (fe_phash's output in
+ * place); times [n] seconds (any epoch, |t| <= 2^61; ignored without FE_BURST_HAS_DATE) and flags [n] on the host. person_off
+ * [n + 1] / person_ids [n_person_ids] (host): CSR lists of int32 ids, ascending and distinct within a row; both null = no row has a
+ * person. thr, window_s and rapid_s are the reference's settings already floored to integers; any value is accepted (a negative
+ * one lets no pair pass its rule). The lower end of each row's search is exact for any row order (prefix maximum of the times, made on
+ * the host). n < 2 launches nothing (link[0] = -1). Null pointers, flags outside the two bits, times out of range, offsets that are
+ * not monotone within 0 .. n_person_ids and lists that are not ascending return FE_ERR_INVALID with a message and launch nothing. */
+#define FE_BURST_HAS_HASH 1
+#define FE_BURST_HAS_DATE 2
+int fe_burst_links(fe_ctx* ctx, const uint64_t* hashes, int on_device, const int64_t* times, const uint8_t* flags, int n,
+                   const int32_t* person_off, const int32_t* person_ids, int n_person_ids, int thr, int64_t window_s, int64_t rapid_s,
+                   int32_t* link);
+
 /* Face clustering (reference faces/clusterer.py): `FaceClusterer.cluster_faces` L2-normalises the stored ArcFace embeddings
  * (:157-158) and runs HDBSCAN on them (:188-197 with the `hdbscan` package's approximate boruvka_balltree, or cuML on an NVIDIA GPU
  * :167-181). The three calls below are the O(n^2 d) parts as exact sweeps on the fp32 matrix cores; the n x n matrix is never
