@@ -198,6 +198,10 @@ SIGNATURES = {
     "fe_image_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "fe_image_stats_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "fe_set_stats_segment": (C.c_int, [C.c_void_p, C.c_int]),
+    "fe_tag_vocab_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "fe_set_tag_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "fe_tag_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fe_tag_select_sims": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fe_roi_laplacian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double)]),
     # the mixed-size face calls: ctx, [slot,] images, hw, n, on_device, order, ...
@@ -2224,6 +2228,57 @@ class Engine:
         out = np.empty((n, T), np.float32)
         self._ck(self.lib.fe_tag_similarities(self.h, ep, n, tp, T, d, out.ctypes.data_as(_f32p)))
         return out
+
+    def tag_vocab(self, text, tag_of_prompt):
+        """The context's tag vocabulary (fe_tag_vocab_set): text float32 [T,d] (L2-normalised rows), tag_of_prompt int [T] with the tag
+        id of every prompt - ids 0 .. G-1, all used, first appearing in ascending order. Packed once; a second call replaces it;
+        text=None clears it. -> G."""
+        if text is None:
+            self._ck(self.lib.fe_tag_vocab_set(self.h, None, 0, 0, None, 0))
+            self._tag_dims = None
+            return 0
+        t = np.ascontiguousarray(text, dtype=np.float32)
+        ids = np.ascontiguousarray(tag_of_prompt, dtype=np.int32).reshape(-1)
+        if t.ndim != 2 or ids.shape[0] != t.shape[0]:
+            raise ValueError(f"tag_vocab: text of shape {t.shape} with {ids.shape[0]} tag ids")
+        G = int(ids.max()) + 1 if ids.size else 0
+        self._ck(self.lib.fe_tag_vocab_set(self.h, t.ctypes.data_as(C.c_void_p), t.shape[0], t.shape[1], ids.ctypes.data_as(C.c_void_p), G))
+        self._tag_dims = (t.shape[0], t.shape[1], G)
+        return G
+
+    def set_tag_chunk(self, rows=0):
+        """Rows per chunk of tag_select / tag_select_sims: 0 = sized from the arena, else a positive count (the arena's size still caps it)."""
+        self._ck(self.lib.fe_set_tag_chunk(self.h, int(rows)))
+
+    def _tag_select(self, fn, who, x, width, threshold, max_tags):
+        if isinstance(x, tuple):
+            p, n, ld = x
+            dev, keep = 1, None
+        else:
+            keep = np.ascontiguousarray(x, dtype=np.float32)
+            if keep.ndim != 2 or (width is not None and keep.shape[1] != width):
+                raise ValueError(f"{who}: rows of shape {keep.shape}, the vocabulary wants [n, {width}]")
+            p, n, ld, dev = keep.ctypes.data_as(C.c_void_p), keep.shape[0], keep.shape[1], 0
+        n, k = int(n), int(max_tags)
+        ids = np.full((n, max(k, 0)), -1, np.int32)
+        scores = np.zeros((n, max(k, 0)), np.float32)
+        counts = np.zeros(n, np.int32)
+        self._ck(fn(self.h, p, n, int(ld), dev, float(threshold), k, ids.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p),
+                    counts.ctypes.data_as(C.c_void_p)))
+        return ids, scores, counts
+
+    def tag_select(self, emb, threshold, max_tags):
+        """emb: float32 [n,d] (host array) or (device_ptr, n, ld) - n rows of d floats, ld floats apart, read in place (the ensemble
+        record at column 21: (records_ptr + 84, n, 789)). -> ids int32 [n,max_tags] padded with -1, scores float32 [n,max_tags] padded
+        with 0, counts int32 [n]: per row the reference's tag choice (per-tag max over the synonyms, float(score) >= threshold,
+        descending score, ties by tag id, the first max_tags) on the vocabulary of tag_vocab (fe_tag_select)."""
+        dims = getattr(self, "_tag_dims", None)
+        return self._tag_select(self.lib.fe_tag_select, "tag_select", emb, dims[1] if dims else None, threshold, max_tags)
+
+    def tag_select_sims(self, sims, threshold, max_tags):
+        """The selection of tag_select alone on given similarities: float32 [n,T] (host array) or (device_ptr, n, ld) (fe_tag_select_sims)."""
+        dims = getattr(self, "_tag_dims", None)
+        return self._tag_select(self.lib.fe_tag_select_sims, "tag_select_sims", sims, dims[0] if dims else None, threshold, max_tags)
 
     def clip_encode_text(self, tokens, out_dim=768):
         """tokens: int [n, 77] -> un-normalised text features [n, 768]."""

@@ -19,7 +19,8 @@ as the last step, from the multi-pass metrics mapping (multi_pass.py:713-752); `
 narrower mapping of the single-pass path (batch_processor.py:272-296).
 
 Engine calls per batch: fe_ensemble_score (TOPIQ + CLIP + aesthetic + U2-Net-P + SAMP-Net), fe_image_stats (technical scans),
-fe_face_analyze + fe_roi_laplacian (+ fe_face_thumbnails with `gpu_thumbnails=True`; through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger),
+fe_face_analyze + fe_roi_laplacian (+ fe_face_thumbnails with `gpu_thumbnails=True`; through FaceAnalyzer.analyze_faces_batch), fe_tag_similarities (through CLIPTagger; with `gpu_tag_select=True`
+fe_tag_select instead: the tags' selection on the device too, CLIPTagger.select_batch),
 fe_phash (with `phash=True`), fe_thumbnail_jpeg (with `thumbnails=True`), fe_subject_region (with `subject_region=True`).
 
 Mixed sizes: `process_images` / `process_files` take a chunk of photos of any sizes. By default the chunk is cut into one process_batch
@@ -84,7 +85,10 @@ class BatchScorer:
     def __init__(self, engine, tagger=None, face_analyzer=None, tag_threshold=0.22, max_tags=5, mono_threshold=0.10,
                  shadow_threshold=0.15, highlight_threshold=0.10, power_weight=2.0, line_weight=1.0, policy=None, detect_lines=False,
                  aux_engine=None, phash=False, vlm_composition=None, thumbnails=False, thumbnail_size=640, thumbnail_quality=80,
-                 subject_region=False, mixed_sizes=False):
+                 subject_region=False, mixed_sizes=False, gpu_tag_select=False):
+        # tags from CLIPTagger.select_batch (fe_tag_select: per-tag max, threshold and top-k on the device; the similarities stay there)
+        # instead of get_tags_batch (GEMM on the device, the [n, T] matrix back, the selection in Python). Off by default.
+        self.gpu_tag_select = gpu_tag_select
         # process_images / process_files: one fe_ensemble_score_mixed call for the whole chunk instead of one fe_ensemble_score per distinct
         # shape (module docstring, "Mixed sizes"). Off by default.
         self.mixed_sizes = mixed_sizes
@@ -196,7 +200,12 @@ class BatchScorer:
                 e.dev_free(d_bgr)
         tags = None
         if self.tagger is not None and self.tagger.text_embeddings is not None and mask & 2:
-            tags = self.tagger.get_tags_batch(rec[:, 21:789], self.engine, self.tag_threshold, self.max_tags)
+            if self.gpu_tag_select:
+                if getattr(self.tagger, '_engine', None) is not self.engine:
+                    self.tagger.use_engine(self.engine)
+                tags = self.tagger.select_batch(rec[:, 21:789], self.tag_threshold, self.max_tags)
+            else:
+                tags = self.tagger.get_tags_batch(rec[:, 21:789], self.engine, self.tag_threshold, self.max_tags)
         out = []
         for i in range(n):
             t = tech[i]

@@ -52,6 +52,16 @@ struct fe_ctx {
     Arena arena;
     hipEvent_t ev_start = nullptr, ev_join = nullptr, ev_read[2] = {nullptr, nullptr};   // ev_read: its last read of a ping-pong buffer
   } side;
+  // capi_tags.hip: the one tag vocabulary of the context (fe_tag_vocab_set), packed once; freed with the context
+  struct TagVocab {
+    DeviceWeights dw;                 // owns w's rows, perm and goff
+    ConvW w;                          // the text rows [T][d] as a Linear without bias
+    int32_t* perm = nullptr;          // device [T]: prompts sorted by (tag, prompt index)
+    int32_t* goff = nullptr;          // device [G + 1]: CSR offsets of the tags in perm
+    int T = 0, G = 0, d = 0;
+  };
+  std::unique_ptr<TagVocab> tag_vocab;
+  int tag_chunk = 0;                  // fe_set_tag_chunk: rows per chunk of fe_tag_select / fe_tag_select_sims, 0 = sized from the arena
   // capi_models.hip and capi_face.hip, through out_buf()
   float* d_out = nullptr;   // persistent device staging for per-image results
   size_t d_out_cap = 0;

@@ -274,6 +274,11 @@ void burst_lower_bounds(const int64_t* times, const uint8_t* flags, int n, int64
 void burst_links(Ctx& c, const uint64_t* d_hash, const int64_t* times, const uint8_t* flags, int n, const int32_t* person_off, const int32_t* person_ids,
                  int n_ids, int thr, int64_t window_s, int64_t rapid_s, int32_t* link);
 
+// ---- tag selection over prompt similarities (kernels_tags.hip; arguments as fe_tag_select_sims, already checked) ----
+void launch_tag_select(const float* d_sims, long long ld, int n, int T, int G, const int32_t* d_perm, const int32_t* d_goff, double threshold,
+                       int max_tags, int32_t* d_ids, float* d_scores, int32_t* d_counts, hipStream_t s);
+void launch_gather_rows(const float* d_src, long long ld, int n, int d, float* d_dst, hipStream_t s);   // [n][d] rows ld floats apart -> packed
+
 // ---- face clustering sweeps: core distances, mutual-reachability MST, best cosine match (kernels_cluster.hip) ----
 int cluster_max_rounds(int n);                           // ceil(log2 n) + 1: the Boruvka round bound
 void cluster_core_distances(Ctx& c, const float* x, int n, int d, int on_device, int normalise, int k, double* core, int32_t* core_idx);

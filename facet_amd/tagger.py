@@ -5,6 +5,11 @@ get_tags_with_scores; is_artwork; attrs tag_vocabulary, text_embeddings. The tex
 (SURVEY §8f-3), so text embeddings come either from `clip_model.encode_text` when the given model has one, or from
 `set_text_embeddings()` (precomputed [T,768], L2-normalised). Without them every call returns [] exactly like the
 reference does when `clip_model is None` (:38-39, :89-90).
+
+Whole libraries: `use_engine(engine)` hands the vocabulary to the engine once, and `select_batch` / `scores_batch` / `is_artwork_batch`
+answer get_tags_from_embedding / get_tags_with_scores / is_artwork for every row from one `fe_tag_select` call (matmul, per-tag max,
+threshold, sort and top-k on the device; only ids and scores come back). facet_amd/tag_existing.py builds the reference's two library
+loops on it.
 """
 import numpy as np
 
@@ -80,6 +85,68 @@ class CLIPTagger:
             kept = sorted(((t, s) for t, s in scores.items() if s >= threshold), key=lambda x: x[1], reverse=True)
             out.append([t for t, _ in kept[:max_tags]])
         return out
+
+    # ---- the selection on the engine (fe_tag_select): similarities, per-tag max, threshold and top-k in one call ----------------------
+    def use_engine(self, engine):
+        """Sets the engine's tag vocabulary from tag_names / text_embeddings (packed once, Engine.tag_vocab) and keeps the engine for
+        select_batch / scores_batch / is_artwork_batch. Tag ids are the tags in order of first appearance: the reference's dict order.
+        Call it again after set_text_embeddings."""
+        if self.text_embeddings is None:
+            raise ValueError("use_engine: no text embeddings yet (set_text_embeddings / precompute_text_embeddings)")
+        self._tag_list = list(dict.fromkeys(self.tag_names))
+        index = {t: i for i, t in enumerate(self._tag_list)}
+        engine.tag_vocab(self.text_embeddings, [index[t] for t in self.tag_names])
+        self._engine = engine
+        return self
+
+    def _rows(self, embeddings):
+        """[n,768] array, (device_ptr, n, ld), or a list of blobs / arrays (a blob of the wrong length raises ValueError with its index)."""
+        if isinstance(embeddings, (tuple, np.ndarray)):
+            return embeddings
+        d = self.text_embeddings.shape[1]
+        out = np.empty((len(embeddings), d), np.float32)
+        for i, e in enumerate(embeddings):
+            v = bytes_to_embedding(e) if isinstance(e, (bytes, bytearray, memoryview)) else np.asarray(e, np.float32).reshape(-1)
+            if v.shape[0] != d:
+                raise ValueError(f"embedding {i} has {v.shape[0]} floats, the vocabulary has {d}")
+            out[i] = v
+        return out
+
+    def _select(self, embeddings, threshold, max_tags):
+        engine = getattr(self, "_engine", None)
+        if engine is None:
+            raise RuntimeError("no engine: call use_engine(engine) first")
+        rows = self._rows(embeddings)
+        n = rows[1] if isinstance(rows, tuple) else len(rows)
+        if n == 0:
+            return np.empty((0, max_tags), np.int32), np.empty((0, max_tags), np.float32), np.empty(0, np.int32)
+        return engine.tag_select(rows, threshold, min(int(max_tags), len(self._tag_list)))
+
+    def select_batch(self, embeddings, threshold=0.25, max_tags=5):
+        """get_tags_from_embedding for every row in one engine call -> list[list[str]]."""
+        if self.text_embeddings is None:
+            return [[] for _ in range(embeddings[1] if isinstance(embeddings, tuple) else len(embeddings))]
+        if max_tags <= 0:      # the reference's slice [:max_tags]
+            full = self.select_batch(embeddings, threshold, len(self._tag_list))
+            return [t[:max_tags] for t in full]
+        ids, _, counts = self._select(embeddings, threshold, max_tags)
+        names = self._tag_list
+        return [[names[g] for g in row[:c]] for row, c in zip(ids.tolist(), counts.tolist())]
+
+    def scores_batch(self, embeddings, threshold=0.20):
+        """get_tags_with_scores for every row in one engine call -> list[dict], each in vocabulary order with round(score, 3)."""
+        if self.text_embeddings is None:
+            return [{} for _ in range(embeddings[1] if isinstance(embeddings, tuple) else len(embeddings))]
+        ids, scores, counts = self._select(embeddings, threshold, len(self._tag_list))
+        names, out = self._tag_list, []
+        for row, sc, c in zip(ids.tolist(), scores.tolist(), counts.tolist()):      # tolist: float32 -> the same value as a Python float
+            kept = sorted(zip(row[:c], sc[:c]))
+            out.append({names[g]: round(s, 3) for g, s in kept})
+        return out
+
+    def is_artwork_batch(self, embeddings, threshold=0.24):
+        """is_artwork for every row in one engine call -> list[bool]."""
+        return [bool(set(t) & self.art_tags) for t in self.select_batch(embeddings, threshold=threshold, max_tags=10)]
 
     def get_tags_with_scores(self, clip_embedding_bytes, threshold=0.20):
         if self.text_embeddings is None or clip_embedding_bytes is None:

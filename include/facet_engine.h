@@ -618,6 +618,39 @@ int fe_clip_encode_text(fe_ctx* ctx, const int32_t* tokens, int n, int ctx_len, 
  * CLIPTagger.get_tags_from_embedding (models/tagger.py:100-106); selection (max over synonyms, threshold, top-k) stays on host. */
 int fe_tag_similarities(fe_ctx* ctx, const float* emb, int n, const float* text, int T, int d, float* sims);
 
+/* Tag selection on the device: the whole of CLIPTagger.get_tags_from_embedding (models/tagger.py:100-114) for n stored embeddings in
+ * one call - similarities, per-tag max over the synonyms, threshold, sort and top-k - for the library-wide passes of the reference
+ * (photos.py:578-625 --recompute-tags, tag_existing.py:16-63 after every scan, is_artwork). Only the chosen ids and scores come back.
+ *
+ * fe_tag_vocab_set keeps ONE vocabulary per context: text [T][d] (host, L2-normalised rows; d a multiple of 4 in 4 .. 8192) is packed
+ * once for the GEMM; tag_of_prompt [T] (host) gives each prompt its tag id in 0 .. G-1. Every id must be used and the ids must first
+ * appear in ascending order (tag id = position of the tag in the reference's dict, which breaks ties); the prompts of a tag need not
+ * be contiguous. Limits: 1 <= G <= T <= 4096. A second call replaces the vocabulary; T = 0 clears it. A broken limit or id rule
+ * returns FE_ERR_INVALID with a message that names it, and the vocabulary in place stays.
+ *
+ * fe_tag_select: emb is n rows of d floats (d from the vocabulary), ld >= d floats apart, on the host (on_device = 0) or the device
+ * (records read in place: fe_ensemble_score's record at column 21 with ld = 789; rows that are not packed on a 16-byte boundary are
+ * gathered into a packed chunk buffer first). Per row, exactly as the reference:
+ *   score of a tag  = its prompts' similarities folded in prompt order: the first, replaced only by a later one that is > it
+ *                     (a NaN in first place stays, a later NaN is skipped);
+ *   kept            iff (double)score >= threshold (the reference compares float(sim) with a Python float; NaN never passes);
+ *   order           descending score, ties by ascending tag id; the first max_tags.
+ * Outputs (host): ids [n][max_tags] padded with -1, scores [n][max_tags] padded with 0, counts [n] = the entries written.
+ * 1 <= max_tags <= G. Rows go through in chunks sized from the arena (at most 131072 rows; fe_set_tag_chunk(rows) sets a smaller
+ * size, 0 restores the default): per chunk one upload or gather, the GEMM on the cached text rows, one selection launch, one copy of
+ * the outputs. The similarities never leave the device. The GEMM picks its kernel by the rows of a chunk, so the last bits of a
+ * similarity may depend on the chunk size (as they depend on the batch in fe_tag_similarities); exact inputs give equal results.
+ * Without a vocabulary: FE_ERR_NOT_LOADED. n = 0 returns FE_OK.
+ *
+ * fe_tag_select_sims: the selection alone on a given sims matrix of n rows of T floats, ld >= T apart, host or device (read in place
+ * at any ld and alignment); same outputs, same vocabulary (its grouping is what is used). */
+int fe_tag_vocab_set(fe_ctx* ctx, const float* text, int T, int d, const int32_t* tag_of_prompt, int G);
+int fe_set_tag_chunk(fe_ctx* ctx, int rows);
+int fe_tag_select(fe_ctx* ctx, const float* emb, int n, int ld, int on_device, double threshold, int max_tags, int32_t* ids, float* scores,
+                  int32_t* counts);
+int fe_tag_select_sims(fe_ctx* ctx, const float* sims, int n, int ld, int on_device, double threshold, int max_tags, int32_t* ids,
+                       float* scores, int32_t* counts);
+
 /* The whole ensemble on one resident batch — what processing/batch_processor.py:169-360 sequences per image.
  * records [n][FE_RECORD_FLOATS]: [0] topiq raw MOS, [1] aesthetic raw, [2..9] SAMP pattern logits, [10..15] SAMP
  * attributes, [16..20] SAMP score distribution, [21..788] L2-normalised CLIP embedding. Fields of models that are
